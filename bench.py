@@ -13,7 +13,13 @@ device.  Weights are already resident in HBM when the timed region starts
 
 The default (steps=255, warmup=1) is exactly the reference's `-n 256 -t 0 -v`
 figure: its clock starts after the first token and the rate is (pos-1)/elapsed
-(src/main.zig:1039-1047).
+(src/main.zig:1039-1047).  `--steps K` is the number of timed steps: a generation that
+ends inside them (context full, or BOS) starts over from BOS, as a new one would.
+
+`--dump-outputs DIR` writes what the timed path returned after its last step, for comparing two
+builds output for output (same arguments, same seeded weights, same inputs):
+  DIR/tokens.npy   float64 [K]      the token ids of the K timed steps (what l2z_greedy_run hands back)
+  DIR/logits.npy   float32 [vocab]  the logits of the last timed step (l2z_logits_read)
 
 Rank 0 prints ONE JSON line.  It carries `roofline` for the dominant kernel and, at N=1,
 `cpu_baseline`: the C oracle (a port, 1 thread -- the reference is single threaded, main.zig:5 /
@@ -51,6 +57,7 @@ MFMA_BF16_PEAK_TF = 2500.0  # dense bf16 matrix peak (MI355X_MICROARCH.md: ~2.5 
 # to the unsharded pass) on three transports, then scheme B (Wo / W2 by columns, 2 all-reduces per layer: logit tolerance)
 LEGS = ["rccl", "p2p-gather", "p2p-consume", "rccl-allreduce", "p2p-allreduce"]
 SCHEME_B_LEGS = ("rccl-allreduce", "p2p-allreduce")
+LEG_DUMPS = ".legs"  # DIR/.legs/<leg>/: every leg's --dump-outputs until the headline leg's are moved into DIR
 RCCL_LEGS = ("rccl", "rccl-allreduce")
 LEG_TEXT = {
     "rccl-allreduce": "scheme B: ncclAllReduce of the ranks' partial [dim] vectors (Wo / W2 sharded by columns), "
@@ -217,8 +224,32 @@ def cpu_baseline(ck, cfg, shared, name: str) -> dict:
                                     f"{cfg.n_layers} layers", build)
 
 
+def greedy_steps(s, w, steps: int) -> np.ndarray:
+    """Exactly `steps` greedy positions on runstate s: a generation that ends (context full, or BOS) starts over from
+    BOS.  Returns the token ids of all of them."""
+    toks, n, fresh = [], 0, False
+    while n < steps:
+        got = s.greedy_run(w, steps - n)
+        if len(got):
+            toks.append(got)
+            n += len(got)
+        elif fresh:
+            raise RuntimeError("l2z_greedy_run produced no token from BOS")
+        fresh = n < steps
+        if fresh:
+            s.greedy_begin([])
+    return np.concatenate(toks) if toks else np.zeros(0, np.int32)
+
+
+def dump_outputs(d: str, toks, logits) -> None:
+    """bench.py --dump-outputs: what the timed path returned after its last step (module docstring)."""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "tokens.npy"), np.asarray(toks, dtype=np.float64))
+    np.save(os.path.join(d, "logits.npy"), np.asarray(logits, dtype=np.float32))
+
+
 def run_once(B, cfg, shared, seed, steps, warmup, comm=None, sync_ok=None):
-    """Returns (tokens produced in the timed region, elapsed seconds on this rank, runstate, weights).
+    """Returns (token ids of the timed steps, elapsed seconds on this rank, runstate, weights).
 
     sync_ok(ok) -> bool is the multi-rank barrier: every rank reports whether its phase worked and
     learns whether all did, so that a failure on one rank makes ALL ranks raise here instead of
@@ -242,10 +273,10 @@ def run_once(B, cfg, shared, seed, steps, warmup, comm=None, sync_ok=None):
                 o.close()
         raise RuntimeError(f"set-up / warm-up failed on some rank ({err})")
     t0 = time.perf_counter()
-    toks = ()
+    toks = np.zeros(0, np.int32)
     dt = 0.0
     try:
-        toks = s.greedy_run(w, steps)  # synchronises before returning the tokens
+        toks = greedy_steps(s, w, steps)  # synchronises before returning the tokens
         s.synchronize()
         dt = time.perf_counter() - t0
     except Exception as e:  # noqa: BLE001
@@ -254,7 +285,7 @@ def run_once(B, cfg, shared, seed, steps, warmup, comm=None, sync_ok=None):
     if not ok:
         s.close(); w.close()
         raise RuntimeError(f"timed region failed on some rank ({err})")
-    return len(toks), dt, s, w
+    return toks, dt, s, w
 
 
 def profile_kinds(B, s, w, cfg, pos0: int, n_prof: int = 4) -> dict:
@@ -465,10 +496,13 @@ def single_gpu(args) -> None:
     B, ck = pkg.binding, pkg.checkpoint
     shapes = {n: (c, sh) for n, c, sh in ck.iter_configs()}
     cfg, shared = shapes[args.workload]
-    steps = max(1, min(args.steps, cfg.seq_len - args.warmup))
+    steps = max(1, args.steps)
     if B.device_count() < 1:
         raise SystemExit("bench.py: no HIP device visible (the HIP path has no CPU fallback)")
-    n_tok, dt, s, w = run_once(B, cfg, shared, args.seed, steps, args.warmup, None, None)
+    toks, dt, s, w = run_once(B, cfg, shared, args.seed, steps, args.warmup, None, None)
+    n_tok = len(toks)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, toks, s.logits())
     n_prof = 4
     pos0 = args.warmup + n_tok
     by_kind = profile_kinds(B, s, w, cfg, pos0, n_prof)
@@ -485,7 +519,7 @@ def single_gpu(args) -> None:
                     s.greedy_run(w, args.warmup)
                 s.synchronize()
                 t0 = time.perf_counter()
-                k = len(s.greedy_run(w, steps))
+                k = len(greedy_steps(s, w, steps))
                 s.synchronize()
                 xs.append(k / (time.perf_counter() - t0))
             repeats = {"n": len(xs), "min": float(np.min(xs)), "median": float(np.median(xs)), "max": float(np.max(xs)),
@@ -556,18 +590,21 @@ def single_gpu(args) -> None:
     }
     if not args.no_extra and args.workload != "stories15M":
         c15, sh15 = shapes["stories15M"]
-        n15, dt15, s15, w15 = run_once(B, c15, sh15, args.seed, 255, 1)
+        t15, dt15, s15, w15 = run_once(B, c15, sh15, args.seed, 255, 1)
         s15.close(); w15.close()
+        n15 = len(t15)
         # stories110M (BASELINE config 3's shape): 438 MB of weights per token do not fit the
         # 256 MB Infinity Cache, so an HBM fraction is meaningful, though launch latency dominates
         c110, sh110 = shapes["stories110M"]
-        n110, dt110, s110, w110 = run_once(B, c110, sh110, args.seed, 255, 1)
+        t110, dt110, s110, w110 = run_once(B, c110, sh110, args.seed, 255, 1)
         s110.close(); w110.close()
+        n110 = len(t110)
         bytes110 = weight_bytes_per_token(c110)
         # stories42M (llama2.c's public checkpoint; hidden_dim 1376: rows that end in a partial 64-lane step)
         c42, sh42 = shapes["stories42M"]
-        n42, dt42, s42, w42 = run_once(B, c42, sh42, args.seed, 255, 1)
+        t42, dt42, s42, w42 = run_once(B, c42, sh42, args.seed, 255, 1)
         s42.close(); w42.close()
+        n42 = len(t42)
         # long context on the headline shape: the prompt fills the cache through the batched
         # prefill, then 32 greedy positions near the end of the 2048-token context are timed
         long_ctx = None
@@ -671,7 +708,7 @@ def leg_main(args) -> int:
     B, ck = pkg.binding, pkg.checkpoint
     shapes = {n: (c, sh) for n, c, sh in ck.iter_configs()}
     cfg, shared = shapes[args.workload]
-    steps = max(1, min(args.steps, cfg.seq_len - args.warmup))
+    steps = max(1, args.steps)
     if B.device_count() < 1:
         raise SystemExit("bench.py: no HIP device visible (the HIP path has no CPU fallback)")
     n_dev = B.device_count()
@@ -809,13 +846,18 @@ def leg_main(args) -> int:
             dist.barrier()
     s = w = None
     try:
-        n_tok, dt, s, w = run_once(B, cfg, shared, args.seed, steps, args.warmup, comm, all_ok)
+        toks, dt, s, w = run_once(B, cfg, shared, args.seed, steps, args.warmup, comm, all_ok)
+        n_tok = len(toks)
         ran = True
     except Exception as e:  # noqa: BLE001  (a gather timed out, a launch failed, ...)
         print(f"[rank {rank}] run with transport {kind} failed: {e}", file=sys.stderr)
         ran = False
     if not all_ok(ran):
         return fail("run failed")
+    if args.dump_outputs:
+        lg = s.logits()  # every rank: the read is collective on a sharded runstate
+        if rank == 0:
+            dump_outputs(args.dump_outputs, toks, lg)
     agree = ranks_agree(s)
     form_ran = s.form()  # bit 3: scheme B
     t = torch.tensor([dt], dtype=torch.float64)
@@ -980,6 +1022,8 @@ def multi_main(args) -> None:
                "--workload", args.workload, "--seed", str(args.seed)]
         if args.no_extra:
             cmd.append("--no-extra")
+        if args.dump_outputs:
+            cmd += ["--dump-outputs", os.path.join(args.dump_outputs, LEG_DUMPS, kind)]
         # the child makes its own gloo group on the leg's port: torchrun's agent-store settings must not
         # reach it (with TORCHELASTIC_USE_AGENT_STORE a tcp:// rendezvous looks for the agent's store)
         env = {k: v for k, v in os.environ.items() if not k.startswith("TORCHELASTIC_")}
@@ -1041,6 +1085,12 @@ def multi_main(args) -> None:
             best_b = max(ok_b, key=lambda l: l["tokens_per_s"]) if ok_b else None
             out = lines[best["transport"]]
             out.pop("leg", None)
+            if args.dump_outputs:  # the headline leg's outputs
+                import shutil
+                legs_dir = os.path.join(args.dump_outputs, LEG_DUMPS)
+                for f in os.listdir(os.path.join(legs_dir, best["transport"])):
+                    os.replace(os.path.join(legs_dir, best["transport"], f), os.path.join(args.dump_outputs, f))
+                shutil.rmtree(legs_dir)
             out["comm"] = {"transport": best["transport"], "scheme": best.get("scheme"),
                            "selection": "fastest leg whose ranks agree, either scheme (scheme A: logits bit-identical to the "
                                         "unsharded pass; scheme B: within the fp32 tolerance, ranks bit-identical to each other)",
@@ -1074,6 +1124,8 @@ def main() -> None:
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's outputs after its last step to DIR/<name>.npy")
     ap.add_argument("--leg", default=None, choices=LEGS, help=argparse.SUPPRESS)  # child of an N > 1 run
     ap.add_argument("--leg-port", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()

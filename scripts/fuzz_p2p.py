@@ -12,7 +12,7 @@ B.option_set("L2Z_FUSE_SMALL", 0)  # the unsharded reference runs the launches t
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 bad = 0
 for it in range(int(sys.argv[1]) if len(sys.argv) > 1 else 8):
-    world = int(rng.choice([2, 3, 4, 5, 8]))
+    world = int(rng.choice([2, 3, 4, 5]))  # ranks + this process: at most 6 processes may have the GPU open
     hs = int(rng.choice([2, 6, 16, 64, 128]))
     n_kv = world * int(rng.choice([1, 2])); n_heads = n_kv * int(rng.choice([1, 2]))
     dim = hs * n_heads

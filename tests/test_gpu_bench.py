@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -43,6 +44,28 @@ def test_bench_line_has_the_contract_fields(gpu):
     by_shape = out["extra"]["cpu_baseline_by_shape"]
     assert set(by_shape) == {"stories15M", "stories110M"} and all(v["value"] > 0 and v["cores"] == 1 for v in by_shape.values())
     assert out["extra"]["stories15M_tokens_per_s"] > 0 and out["extra"]["prefill"]["roofline"]["bound"] == "mfma"
+
+
+def test_bench_steps_are_exact_and_outputs_dump_reproducibly(gpu, tmp_path):
+    """--steps K times exactly K steps, also past the end of the context (stories15M: 256 positions; the generation
+    starts over from BOS), and --dump-outputs writes the same arrays on two runs with the same arguments."""
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "stories15M", "--steps", "300",
+                            "--warmup", "5", "--no-extra", "--no-cpu-baseline", "--dump-outputs", str(d)],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert p.returncode == 0, p.stderr.decode()[-3000:]
+        lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1 and json.loads(lines[0])["steps"] == 300
+        assert sorted(os.listdir(d)) == ["logits.npy", "tokens.npy"]
+        dumps.append({f: np.load(d / f) for f in ("tokens.npy", "logits.npy")})
+    toks, logits = dumps[0]["tokens.npy"], dumps[0]["logits.npy"]
+    assert toks.dtype == np.float64 and toks.shape == (300,) and np.all((toks >= 0) & (toks < 32000))
+    assert logits.dtype == np.float32 and logits.shape == (32000,) and np.isfinite(logits).all()
+    assert int(np.argmax(logits)) == int(toks[-1])
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
 
 
 @pytest.mark.parametrize("leg_name", ["rccl", "rccl-allreduce"])

@@ -12,6 +12,9 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
+# The test process holds the GPU open while its rank processes run: at most 6 processes may have a GPU open at once,
+# so a test starts at most 4 ranks (8-way sharding runs in-process on emulated ranks: test_gpu_parity.py, test_gpu_fuzz.py)
+MAX_RANK_PROCS = 4
 
 MODELS = [
     ("toy-gqa", dict(dim=64, hidden_dim=176, n_layers=3, n_heads=8, n_kv_heads=4, vocab_size=512, seq_len=96), False, 2),
@@ -21,7 +24,6 @@ MODELS = [
     # n = 4096: the row kernel, whose writer lanes push their outputs to the peers themselves
     ("row-kernel-7B-width", dict(dim=4096, hidden_dim=8192, n_layers=2, n_heads=32, n_kv_heads=8, vocab_size=8192, seq_len=320), False, 4),
     ("row-kernel-7B-width", dict(dim=4096, hidden_dim=8192, n_layers=2, n_heads=32, n_kv_heads=8, vocab_size=8192, seq_len=320), False, 2),
-    ("row-kernel-7B-width", dict(dim=4096, hidden_dim=8192, n_layers=2, n_heads=32, n_kv_heads=8, vocab_size=8192, seq_len=320), False, 8),
 ]
 
 
@@ -32,6 +34,7 @@ def grid_cap(world: int) -> str:
 
 
 def run_ranks(tmp_path, world, spec, env_extra=None, timeout=300):
+    assert world <= MAX_RANK_PROCS, f"{world} rank processes + this one exceed the processes a GPU may have open"
     (tmp_path / "model.json").write_text(json.dumps(spec))
     env = dict(os.environ, L2Z_P2P_TIMEOUT_S="30", L2Z_GRID_CAP=grid_cap(world))
     env.update(env_extra or {})
@@ -87,7 +90,7 @@ def test_multiprocess_peer_write_gather_is_bit_identical(gpu, ck, tmp_path, mode
     s.close(); w.close()
 
 
-@pytest.mark.parametrize("world,mode", [(2, "consume"), (4, "gather"), (8, "gather"), (4, "scheme_b")])
+@pytest.mark.parametrize("world,mode", [(2, "consume"), (4, "gather"), (2, "gather"), (4, "scheme_b")])
 def test_argmax_tie_across_ranks_takes_the_lowest_index(gpu, ck, tmp_path, world, mode, options):
     """main.zig:715-726 over a SHARDED vocabulary: greedy steps of a shard group exchange one (max, first index) candidate
     per rank instead of gathering the logits (csrc/misc_kernels.hip argmax_kernel, ArgmaxArgs::xchg).  The classifier is
@@ -157,7 +160,7 @@ def test_multiprocess_scheme_b_allreduce(gpu, ck, tmp_path, model, mode, options
     s.close(); w.close()
 
 
-@pytest.mark.parametrize("world", [2, 4, 8])
+@pytest.mark.parametrize("world", [2, 4])
 def test_multiprocess_scheme_b_batched_prefill(gpu, ck, tmp_path, world, options):
     """Scheme B's batched prompt pass with REAL processes: per layer two bulk all-reduces of the ranks' partial [tokens,
     dim] products -- reduce-scatter through the arenas' bulk regions (every peer gets the columns of ITS slice, adds the
@@ -279,7 +282,8 @@ def test_bench_legs_on_one_gpu(gpu, tmp_path):
     env = dict(os.environ, L2Z_BENCH_LEG_TIMEOUT_S="200", L2Z_P2P_TIMEOUT_S="20", L2Z_BENCH_NO_SHARDED_PREFILL="1")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                        "--gpus", "2", "--steps", "48", "--warmup", "1", "--workload", "stories110M"],
+                        "--gpus", "2", "--steps", "48", "--warmup", "1", "--workload", "stories110M",
+                        "--dump-outputs", str(tmp_path / "dump")],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
     assert p.returncode == 0 and len(lines) == 1, p.stdout.decode()[-3000:] + p.stderr.decode()[-3000:]
@@ -308,6 +312,9 @@ def test_bench_legs_on_one_gpu(gpu, tmp_path):
     assert out["comm"]["scheme"] == legs[out["comm"]["transport"]]["scheme"]
     assert out["comm"]["scheme_a"]["transport"] == max([t for t in ok if legs[t]["scheme"] == "A"], key=lambda t: legs[t]["tokens_per_s"])
     assert out["value"] == legs[out["comm"]["transport"]]["tokens_per_s"] and out["n_gpus"] == 2
+    # --dump-outputs: the headline leg's outputs, nothing of the other legs left behind
+    assert sorted(os.listdir(tmp_path / "dump")) == ["logits.npy", "tokens.npy"]
+    assert np.load(tmp_path / "dump" / "tokens.npy").shape == (48,)
     if not legs["rccl"]["ok"]:
         assert legs["rccl"]["why"], legs["rccl"]
         assert out["comm"]["rccl"]["initialised"] is False

@@ -217,15 +217,19 @@ def test_prefill_attention_kernels_vs_softmax_reference(gpu, orc, H, KV, hs, for
     accumulators' registers; two key parts per tile).  150 queries at positions 37 .. 186 (three query
     tiles, the last one partial, key tiles that start before the chunk) against main.zig:361-389 in
     float64, and a few (query, head) pairs against the oracle's own dot / softmax / weighted sum.  Outputs
-    are convex combinations of V entries (|v| <= 2): bound 3e-6."""
-    if form.startswith("flash") and hs not in (64, 128):
-        pytest.skip("the flash form takes head sizes 64 and 128")
+    are convex combinations of V entries (|v| <= 2): bound 3e-6.  The flash form takes head sizes 64 and 128 only:
+    any other is refused (L2Z_ERR_INVALID, nothing launched)."""
     pos0, P, S = 37, 150, 200
     dim, kvd, kv_mul = H * hs, KV * hs, H // KV
     rng = np.random.default_rng(hs + H)
     q = rng.standard_normal((P, dim), dtype=np.float32)
     kc = rng.standard_normal((S, kvd), dtype=np.float32)
     vc = rng.uniform(-2, 2, (S, kvd)).astype(np.float32)
+    if form == "flash" and hs not in (64, 128):
+        with pytest.raises(gpu.L2ZError, match="the flash form takes head sizes 64 and 128") as e:
+            gpu.prefill_attention(PF_ATTN_FORMS[form], q, kc, vc, pos0, H, KV, hs)
+        assert e.value.code == gpu.ERR_INVALID
+        return
     got = gpu.prefill_attention(PF_ATTN_FORMS[form], q, kc, vc, pos0, H, KV, hs)
     ref = np.empty((P, dim), np.float64)
     for h in range(H):
@@ -698,8 +702,6 @@ def test_sharded_prefill_emulated_ranks_bit_identical(gpu, ck, world, name, kw, 
     model takes.  Also with pos0 > 0 (a second call continuing the context).  x3 = 2: every product on the bf16 matrix cores
     (the streams-* shapes take them by default: stream form at 51 / 101 tokens, its K ranges from the WHOLE model's rows);
     the planes kernels' k order and ranges do not depend on the rows a rank owns either."""
-    if x3 == 2 and name.startswith("streams"):
-        pytest.skip("these matrices take the bf16 cores by default")
     options(L2Z_FUSE_SMALL=0, L2Z_PF_X3=x3)  # (fuse: the decode step at the end -- the unsharded pass runs the launches the shards run)
     cfg = ck.Config(**kw)
     w0, s0 = gpu.Weights(cfg, None, False, seed=23), gpu.RunState(cfg)
