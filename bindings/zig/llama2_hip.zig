@@ -99,6 +99,18 @@ pub extern fn l2z_prefill(
     w: *const L2zWeights,
 ) c_int;
 pub extern fn l2z_synchronize(s: *L2zRunState) c_int;
+/// Batched decode (no reference equivalent): up to batch_max sequences, one runstate each, one token each, one sweep
+/// of the weights -- the state change of l2z_transformer(tokens[i], pos[i], config, states[i], w) for every i.
+pub const batch_max: c_int = 16;
+pub extern fn l2z_transformer_batch(
+    n: c_int,
+    tokens: [*]const i32,
+    pos: [*]const i32,
+    config: *const L2zConfig,
+    states: [*]const *L2zRunState,
+    w: *const L2zWeights,
+) c_int;
+pub extern fn l2z_argmax_batch(n: c_int, states: [*]const *L2zRunState, out_tokens: [*]i32) c_int;
 
 pub const Error = error{DeviceForwardFailed};
 

@@ -155,6 +155,29 @@ int l2z_prefill(const int32_t *tokens, int n_tokens, int pos0, const l2z_config 
 /* wait for everything queued on the runstate's stream */
 int l2z_synchronize(l2z_runstate *s);
 
+/* ---- batched decode (no reference equivalent: the reference steps one sequence) ----
+ * Up to L2Z_BATCH_MAX independent sequences, one runstate each, advanced by one token with ONE sweep of the weights.
+ * Same state change as l2z_transformer(tokens[i], pos[i], config, states[i], w) for i = 0 .. n-1: KV row pos[i] of
+ * every layer is written in states[i] and no other cache row is touched; states[i]'s logits hold its result, and
+ * l2z_argmax / l2z_logits_read / l2z_probs_read work on it unchanged.  A runstate moves freely between l2z_prefill,
+ * l2z_transformer and batched steps.
+ * Contract (else L2Z_ERR_INVALID, or L2Z_ERR_STATE for pos / tokens, with no state changed and nothing enqueued):
+ * 1 <= n <= L2Z_BATCH_MAX; the runstates pairwise distinct, unsharded (comm == NULL), on one device and made with
+ * *config; 0 <= pos[i] < seq_len and 0 <= tokens[i] < vocab_size; dims l2z_prefill accepts (multiples of 4,
+ * head_size <= 256).
+ * Streams: the pass waits for everything queued on every runstate's stream, and every runstate's stream waits for the
+ * pass (events, no device-wide sync), so later calls on any of them see its results.
+ * BATCH INVARIANCE: a sequence's logits and KV rows are bit-identical whether it runs alone (n = 1) or in a batch of
+ * 2 ... 16, whatever the other sequences hold, and in any order within the batch (every product takes one kernel form
+ * and one summation order independent of n).  They equal l2z_transformer's up to summation order (the fp32 parity
+ * bar), not bit for bit. */
+#define L2Z_BATCH_MAX 16
+int l2z_transformer_batch(int n, const int32_t *tokens, const int32_t *pos, const l2z_config *config,
+                          l2z_runstate *const *states, const l2z_weights *w);
+/* out_tokens[i] = argmax of states[i]'s logits (strict '>', lowest index wins): one launch, one sync.  The runstates
+ * follow l2z_transformer_batch's rules (distinct, unsharded, one device, one config). */
+int l2z_argmax_batch(int n, l2z_runstate *const *states, int32_t *out_tokens);
+
 /* ---- multi-GPU shard group: one process per GPU, xGMI ----
  * The reference is single-threaded and single-device; this is what the build
  * adds.  Two transports for the per-layer all-gathers:

@@ -174,6 +174,11 @@ int l2z_runstate_form(const l2z_runstate *s, int *form);
  * Applies to objects created afterwards.  L2Z_ERR_INVALID for an unknown name. */
 int l2z_option_set(const char *env_name, long long value);
 
+/* Measurement (scripts/batch_bench.py): one l2z_transformer_batch call, then `iters` more back to back, timed by device
+ * events on the pass's stream; *out_ms = milliseconds per step.  The steps rewrite the same KV rows. */
+int l2z_batch_time(int n, const int32_t *tokens, const int32_t *pos, const l2z_config *config,
+                   l2z_runstate *const *states, const l2z_weights *w, int iters, double *out_ms);
+
 #ifdef __cplusplus
 }
 #endif

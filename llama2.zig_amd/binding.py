@@ -87,6 +87,9 @@ def lib():
     L.l2z_probs_read.argtypes = [vp, C.c_float, fp]
     L.l2z_runstate_read.argtypes = [vp, C.c_char_p, sz, sz, fp]
     L.l2z_prefill.argtypes = [i32p, C.c_int, C.c_int, cfgp, vp, vp]
+    L.l2z_transformer_batch.argtypes = [C.c_int, i32p, i32p, cfgp, C.POINTER(vp), vp]
+    L.l2z_argmax_batch.argtypes = [C.c_int, C.POINTER(vp), i32p]
+    L.l2z_batch_time.argtypes = [C.c_int, i32p, i32p, cfgp, C.POINTER(vp), vp, C.c_int, C.POINTER(C.c_double)]
     L.l2z_greedy_begin.argtypes = [vp, i32p, C.c_int]
     L.l2z_greedy_run.argtypes = [cfgp, vp, vp, C.c_int, i32p, ip]
     L.l2z_profile_forward.argtypes = [C.c_int, C.c_int, cfgp, vp, vp, C.POINTER(C.c_double), ip,
@@ -376,6 +379,44 @@ class RunState:
             self.close()
         except Exception:
             pass
+
+
+BATCH_MAX = 16  # L2Z_BATCH_MAX
+
+
+def _batch_args(states, tokens, pos):
+    n = len(states)
+    ss = (C.c_void_p * max(n, 1))(*[s.h for s in states])
+    t = np.ascontiguousarray(tokens, np.int32)
+    p = np.ascontiguousarray(pos, np.int32)
+    return n, ss, t, p
+
+
+def transformer_batch(states, tokens, pos, w: Weights) -> None:
+    """l2z_transformer_batch: transformer(tokens[i], pos[i]) on states[i] for every i, one sweep of the weights.
+    The config is states[0]'s (the call checks that every runstate and the weights share it)."""
+    n, ss, t, p = _batch_args(states, tokens, pos)
+    cfg = states[0].cfg if n else L2ZConfig()
+    _chk(lib().l2z_transformer_batch(n, t.ctypes.data_as(C.POINTER(C.c_int32)), p.ctypes.data_as(C.POINTER(C.c_int32)),
+                                     C.byref(cfg), ss, w.h))
+
+
+def argmax_batch(states) -> np.ndarray:
+    """l2z_argmax_batch: the argmax of every runstate's logits, one launch."""
+    n = len(states)
+    ss = (C.c_void_p * max(n, 1))(*[s.h for s in states])
+    out = np.zeros(max(n, 1), np.int32)
+    _chk(lib().l2z_argmax_batch(n, ss, out.ctypes.data_as(C.POINTER(C.c_int32))))
+    return out[:n].copy()
+
+
+def batch_time(states, tokens, pos, w: Weights, iters: int) -> float:
+    """l2z_batch_time: milliseconds per batched step, device events over `iters` steps (after one untimed)."""
+    n, ss, t, p = _batch_args(states, tokens, pos)
+    ms = C.c_double(0.0)
+    _chk(lib().l2z_batch_time(n, t.ctypes.data_as(C.POINTER(C.c_int32)), p.ctypes.data_as(C.POINTER(C.c_int32)),
+                              C.byref(states[0].cfg), ss, w.h, iters, C.byref(ms)))
+    return ms.value
 
 
 def emu_transformer(states, weights, token: int, pos: int) -> None:

@@ -1,0 +1,295 @@
+// batch_host.cpp -- host side of the batched decode step (l2z_transformer_batch, l2z_argmax_batch): up to
+// L2Z_BATCH_MAX independent sequences advanced by one token with one sweep of the weights.  Kernels: the short-prompt
+// GEMM forms with per-row epilogues (prefill_skinny.hip, G_*_ROWS) and batch_decode.hip.
+#include <cstring>
+
+#include "batch_decode.h"
+#include "l2z_state.h"
+#include "prefill_common.h"
+
+static_assert(l2z::kBatchMax == L2Z_BATCH_MAX, "include/llama2_hip.h L2Z_BATCH_MAX");
+
+namespace l2z {
+
+// Scratch of the batched step, owned by the runstate that is states[0] of a call (allocated on its first such call,
+// freed with it): the activation rows of kBatchMax sequences, the attention scores, the device table and its pinned
+// host twin, and the events that order the pass against the runstates' own streams.
+struct BatchScratch {
+    float *x = nullptr, *xn = nullptr, *q = nullptr, *att = nullptr, *h1 = nullptr, *scores = nullptr;
+    int ld_xn = 0, ld_att = 0, ld_h1 = 0;
+    BatchTable *d_tab = nullptr, *h_tab = nullptr;
+    int *d_tokens_out = nullptr, *h_tokens_out = nullptr;
+    hipEvent_t ev_in[kBatchMax] = {};
+    hipEvent_t ev_done = nullptr;
+    hipEvent_t ev_upload = nullptr;  // the last table copy: the pinned table may be rewritten once it has completed
+};
+
+void batch_free(l2z_runstate *s)
+{
+    BatchScratch *b = s->bt;
+    if (b == nullptr) return;
+    void *ptrs[] = {b->x, b->xn, b->q, b->att, b->h1, b->scores, b->d_tab, b->d_tokens_out};
+    for (void *p : ptrs)
+        if (p) (void)hipFree(p);
+    if (b->h_tab) (void)hipHostFree(b->h_tab);
+    if (b->h_tokens_out) (void)hipHostFree(b->h_tokens_out);
+    for (hipEvent_t e : b->ev_in)
+        if (e) (void)hipEventDestroy(e);
+    if (b->ev_done) (void)hipEventDestroy(b->ev_done);
+    if (b->ev_upload) (void)hipEventDestroy(b->ev_upload);
+    delete b;
+    s->bt = nullptr;
+}
+
+namespace {
+
+// Row pitch of the activation matrices the GEMMs read: rounded up to 256 floats, at least 768, the pad columns zero and
+// never written (the short-prompt forms multiply whole 256-k stages, at least three: prefill_common.h pad_k)
+int bt_ld(int n)
+{
+    const int r = (n + 255) / 256 * 256;
+    return r < 768 ? 768 : r;
+}
+
+int batch_alloc(l2z_runstate *s)
+{
+    if (s->bt != nullptr) return L2Z_OK;
+    const l2z_config &c = s->cfg;
+    BatchScratch *b = new BatchScratch();
+    s->bt = b;  // freed with the runstate whatever happens below
+    b->ld_xn = bt_ld(c.dim); b->ld_att = bt_ld(c.dim); b->ld_h1 = bt_ld(c.hidden_dim);
+    const size_t R = kBatchMax;
+    struct { void **p; size_t bytes; } want[] = {
+        {(void **)&b->x, R * c.dim * 4}, {(void **)&b->xn, R * b->ld_xn * 4}, {(void **)&b->q, R * c.dim * 4},
+        {(void **)&b->att, R * b->ld_att * 4}, {(void **)&b->h1, R * b->ld_h1 * 4},
+        {(void **)&b->scores, R * (size_t)c.n_heads * c.seq_len * 4},
+        {(void **)&b->d_tab, sizeof(BatchTable)}, {(void **)&b->d_tokens_out, R * 4}};
+    for (auto &w : want) {
+        const hipError_t e = hipMalloc(w.p, w.bytes);
+        if (e != hipSuccess) {
+            *w.p = nullptr;
+            set_error("batched step scratch allocation (%zu bytes) failed: %s", w.bytes, hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
+        }
+    }
+    L2Z_HIP(hipHostMalloc((void **)&b->h_tab, sizeof(BatchTable), hipHostMallocDefault));
+    L2Z_HIP(hipHostMalloc((void **)&b->h_tokens_out, R * 4, hipHostMallocDefault));
+    for (hipEvent_t &e : b->ev_in) L2Z_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    L2Z_HIP(hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
+    L2Z_HIP(hipEventCreateWithFlags(&b->ev_upload, hipEventDisableTiming));
+    // the pad columns are multiplied against whatever follows a W row: zeros, once
+    L2Z_HIP(hipMemset(b->xn, 0, R * b->ld_xn * 4));
+    L2Z_HIP(hipMemset(b->att, 0, R * b->ld_att * 4));
+    L2Z_HIP(hipMemset(b->h1, 0, R * b->ld_h1 * 4));
+    return L2Z_OK;
+}
+
+int no_device_check()
+{
+    int nd = 0;
+    const hipError_t e = hipGetDeviceCount(&nd);
+    L2Z_CHECK(e == hipSuccess && nd > 0, L2Z_ERR_NO_DEVICE, "no HIP device available; this library has no CPU fallback");
+    return L2Z_OK;
+}
+
+// the runstates of one call: non-null, pairwise distinct, unsharded, on one device, all made with *c (c: states[0]'s
+// when the call names no config)
+int check_states(const char *fn, int n, l2z_runstate *const *states, const l2z_config *c)
+{
+    L2Z_CHECK(n >= 1 && n <= kBatchMax, L2Z_ERR_INVALID, "%s: n = %d outside [1, %d]", fn, n, kBatchMax);
+    L2Z_CHECK(states != nullptr, L2Z_ERR_INVALID, "%s: null runstate array", fn);
+    for (int i = 0; i < n; i++) {
+        const l2z_runstate *s = states[i];
+        L2Z_CHECK(s != nullptr, L2Z_ERR_INVALID, "%s: states[%d] is null", fn, i);
+        for (int j = 0; j < i; j++)
+            L2Z_CHECK(states[j] != s, L2Z_ERR_INVALID, "%s: states[%d] and states[%d] are the same runstate", fn, j, i);
+        L2Z_CHECK(s->comm == nullptr && s->sh.world == 1, L2Z_ERR_INVALID, "%s: states[%d] is a shard (shard groups are not batched)", fn, i);
+        L2Z_CHECK(memcmp(c != nullptr ? c : &states[0]->cfg, &s->cfg, sizeof(l2z_config)) == 0, L2Z_ERR_INVALID,
+                  "%s: states[%d] was made with another config", fn, i);
+        L2Z_CHECK(s->device == states[0]->device, L2Z_ERR_INVALID, "%s: states[%d] is on device %d, states[0] on %d", fn, i,
+                  s->device, states[0]->device);
+    }
+    return L2Z_OK;
+}
+
+// the pass waits for everything already queued on every runstate's stream
+int join_streams(BatchScratch *b, int n, l2z_runstate *const *states)
+{
+    hipStream_t st = states[0]->stream;
+    for (int i = 1; i < n; i++) {
+        L2Z_HIP(hipEventRecord(b->ev_in[i], states[i]->stream));
+        L2Z_HIP(hipStreamWaitEvent(st, b->ev_in[i], 0));
+    }
+    return L2Z_OK;
+}
+
+// ... and every runstate's stream waits for the pass
+int release_streams(BatchScratch *b, int n, l2z_runstate *const *states)
+{
+    L2Z_HIP(hipEventRecord(b->ev_done, states[0]->stream));
+    for (int i = 1; i < n; i++) L2Z_HIP(hipStreamWaitEvent(states[i]->stream, b->ev_done, 0));
+    return L2Z_OK;
+}
+
+// the table of this call -> the device, one copy from the pinned buffer (rewritten only once the last copy is done)
+int upload_table(BatchScratch *b, const BatchTable &t, hipStream_t st)
+{
+    L2Z_HIP(hipEventSynchronize(b->ev_upload));
+    memcpy(b->h_tab, &t, sizeof t);
+    L2Z_HIP(hipMemcpyAsync(b->d_tab, b->h_tab, sizeof t, hipMemcpyHostToDevice, st));
+    L2Z_HIP(hipEventRecord(b->ev_upload, st));
+    return L2Z_OK;
+}
+
+GemmArgs gemm(const float *x, int ldx, const float *w, int ldw, int N, int K, int P)
+{
+    GemmArgs a = {};
+    a.x = x; a.ldx = ldx; a.w = w; a.ldw = ldw; a.N = N; a.K = K; a.P = P; a.n_scale = 1;
+    return a;
+}
+
+// One step of n sequences on states[0]'s stream.  Every product is the one-tile short-prompt form at P = n whatever n
+// is (launch_batch_skinny): a row's bits do not depend on n, on the other rows, or on its place in the batch.
+int batch_step(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *w, BatchScratch *b)
+{
+    hipStream_t st = s0->stream;
+    const int dim = c.dim, hid = c.hidden_dim, hs = dim / c.n_heads, kvd = hs * c.n_kv_heads;
+    const BatchTable *tab = b->d_tab;
+    L2Z_HIP(launch_prefill_embed(b->x, w->tok_emb, tab->tokens, dim, n, st));  // :295
+    for (int l = 0; l < c.n_layers; l++) {
+        const size_t layer_off = (size_t)l * c.seq_len * kvd;
+        L2Z_HIP(launch_prefill_rmsnorm(b->xn, b->ld_xn, b->x, w->rms_att + (size_t)l * dim, dim, n, st));  // :305
+        {   // q (:308-351): RoPE at each row's own position
+            GemmArgs a = gemm(b->xn, b->ld_xn, w->wq + (size_t)l * dim * dim, dim, dim, dim, n);
+            a.out = b->q; a.ldo = dim; a.rope = s0->rope; a.head_size = hs; a.row_pos = tab->pos;
+            L2Z_HIP(launch_batch_skinny(G_ROPE_ROWS, a, st));
+        }
+        {   // k | v (:354-358) into each row's own caches, row = its position
+            GemmArgs a = gemm(b->xn, b->ld_xn, w->wk + (size_t)l * kvd * dim, dim, kvd, dim, n);
+            a.w2 = w->wv + (size_t)l * kvd * dim;
+            a.rope = s0->rope; a.head_size = hs; a.ldkv = kvd; a.kv_head_stride = (size_t)c.seq_len * hs;
+            a.row_pos = tab->pos; a.row_kc = tab->kc; a.row_vc = tab->vc; a.layer_off = layer_off;
+            L2Z_HIP(launch_batch_skinny(G_QKV_ROWS, a, st));
+        }
+        {   // :361-389
+            BatchAttnArgs a = {};
+            a.q = b->q; a.ldq = dim; a.out = b->att; a.ldo = b->ld_att; a.scores = b->scores; a.tab = tab;
+            a.layer_off = layer_off; a.kv_head_stride = (size_t)c.seq_len * hs;
+            a.n_heads = c.n_heads; a.kv_mul = c.n_heads / c.n_kv_heads; a.head_size = hs; a.seq_len = c.seq_len;
+            L2Z_HIP(launch_batch_attention(a, n, st));
+        }
+        {   // :392-395
+            GemmArgs a = gemm(b->att, b->ld_att, w->wo + (size_t)l * dim * dim, dim, dim, dim, n);
+            a.out = b->x; a.ldo = dim; a.res = b->x; a.ldres = dim;
+            L2Z_HIP(launch_batch_skinny(G_RESID, a, st));
+        }
+        L2Z_HIP(launch_prefill_rmsnorm(b->xn, b->ld_xn, b->x, w->rms_ffn + (size_t)l * dim, dim, n, st));  // :398
+        {   // :405-416: W1 | W3 (rows 2 dim apart in their shared slot) with silu(a) * b in the epilogue
+            GemmArgs a = gemm(b->xn, b->ld_xn, w->w1 + (size_t)l * hid * 2 * dim, 2 * dim, hid, dim, n);
+            a.w2 = w->w3 + (size_t)l * hid * 2 * dim;
+            a.out = b->h1; a.ldo = b->ld_h1;
+            L2Z_HIP(launch_batch_skinny(G_SWIGLU, a, st));
+        }
+        {   // :419-422
+            GemmArgs a = gemm(b->h1, b->ld_h1, w->w2 + (size_t)l * dim * hid, hid, dim, hid, n);
+            a.out = b->x; a.ldo = dim; a.res = b->x; a.ldres = dim;
+            L2Z_HIP(launch_batch_skinny(G_RESID, a, st));
+        }
+    }
+    L2Z_HIP(launch_prefill_rmsnorm(b->xn, b->ld_xn, b->x, w->rms_final, dim, n, st));  // :426
+    {   // :429: each row's logits straight into its runstate
+        GemmArgs a = gemm(b->xn, b->ld_xn, w->wcls, dim, c.vocab_size, dim, n);
+        a.row_out = tab->logits;
+        L2Z_HIP(launch_batch_skinny(G_OUT_ROWS, a, st));
+    }
+    return L2Z_OK;
+}
+
+}  // namespace
+}  // namespace l2z
+
+using namespace l2z;
+
+extern "C" int l2z_transformer_batch(int n, const int32_t *tokens, const int32_t *pos, const l2z_config *config,
+                                     l2z_runstate *const *states, const l2z_weights *w)
+{
+    L2Z_TRY(no_device_check());
+    L2Z_CHECK(tokens != nullptr && pos != nullptr && config != nullptr && w != nullptr, L2Z_ERR_INVALID,
+              "l2z_transformer_batch: null argument");
+    L2Z_TRY(check_states("l2z_transformer_batch", n, states, config));
+    for (int i = 0; i < n; i++) {
+        L2Z_TRY(check_pair(config, states[i], w));
+        L2Z_CHECK(pos[i] >= 0 && pos[i] < config->seq_len, L2Z_ERR_STATE, "l2z_transformer_batch: pos[%d] = %d outside [0,%d)", i,
+                  pos[i], config->seq_len);
+        L2Z_CHECK(tokens[i] >= 0 && tokens[i] < config->vocab_size, L2Z_ERR_STATE,
+                  "l2z_transformer_batch: tokens[%d] = %d out of vocabulary", i, tokens[i]);
+    }
+    L2Z_TRY(prefill_check(config, states[0]));
+    L2Z_CHECK(states[0]->sh.hs <= 256, L2Z_ERR_INVALID, "l2z_transformer_batch: head_size above 256");
+    L2Z_HIP(hipSetDevice(states[0]->device));
+    L2Z_TRY(batch_alloc(states[0]));
+    BatchScratch *b = states[0]->bt;
+    BatchTable t = {};
+    for (int i = 0; i < n; i++) {
+        t.tokens[i] = tokens[i];
+        t.pos[i] = pos[i];
+        t.kc[i] = states[i]->key_cache;
+        t.vc[i] = states[i]->value_cache;
+        t.logits[i] = states[i]->logits;
+    }
+    L2Z_TRY(join_streams(b, n, states));
+    L2Z_TRY(upload_table(b, t, states[0]->stream));
+    L2Z_TRY(batch_step(n, *config, states[0], w, b));
+    L2Z_TRY(release_streams(b, n, states));
+    for (int i = 0; i < n; i++) {
+        l2z_runstate *s = states[i];
+        s->n_part = 0;  // l2z_argmax scans the logits: the classifier left no per-block candidates
+        s->logits_partial = false;
+        s->host_pos = pos[i] + 1;
+    }
+    return L2Z_OK;
+}
+
+extern "C" int l2z_argmax_batch(int n, l2z_runstate *const *states, int32_t *out_tokens)
+{
+    L2Z_TRY(no_device_check());
+    L2Z_CHECK(out_tokens != nullptr, L2Z_ERR_INVALID, "l2z_argmax_batch: null argument");
+    L2Z_TRY(check_states("l2z_argmax_batch", n, states, nullptr));
+    L2Z_HIP(hipSetDevice(states[0]->device));
+    L2Z_TRY(batch_alloc(states[0]));
+    BatchScratch *b = states[0]->bt;
+    BatchTable t = {};
+    for (int i = 0; i < n; i++) t.logits[i] = states[i]->logits;
+    hipStream_t st = states[0]->stream;
+    L2Z_TRY(join_streams(b, n, states));
+    L2Z_TRY(upload_table(b, t, st));
+    L2Z_HIP(launch_batch_argmax(b->d_tab, states[0]->cfg.vocab_size, b->d_tokens_out, n, st));
+    L2Z_HIP(hipMemcpyAsync(b->h_tokens_out, b->d_tokens_out, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    L2Z_HIP(hipStreamSynchronize(st));
+    memcpy(out_tokens, b->h_tokens_out, (size_t)n * 4);
+    return L2Z_OK;
+}
+
+// Testing support (include/llama2_hip_test.h): `iters` batched steps back to back, timed by device events on the pass's
+// stream (scripts/batch_bench.py)
+extern "C" int l2z_batch_time(int n, const int32_t *tokens, const int32_t *pos, const l2z_config *config,
+                              l2z_runstate *const *states, const l2z_weights *w, int iters, double *out_ms)
+{
+    L2Z_CHECK(iters >= 1 && out_ms != nullptr, L2Z_ERR_INVALID, "l2z_batch_time: bad arguments");
+    L2Z_TRY(l2z_transformer_batch(n, tokens, pos, config, states, w));  // validates, allocates
+    hipStream_t st = states[0]->stream;
+    hipEvent_t e0, e1;
+    L2Z_HIP(hipEventCreate(&e0));
+    L2Z_HIP(hipEventCreate(&e1));
+    int rc = L2Z_OK;
+    if (hipEventRecord(e0, st) != hipSuccess) rc = L2Z_ERR_HIP;
+    for (int i = 0; i < iters && rc == L2Z_OK; i++) rc = l2z_transformer_batch(n, tokens, pos, config, states, w);
+    float ms = 0.0f;
+    if (rc == L2Z_OK && (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
+                         hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
+        rc = L2Z_ERR_HIP;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (rc == L2Z_OK) *out_ms = ms / iters;
+    return rc;
+}

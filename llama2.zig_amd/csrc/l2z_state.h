@@ -11,6 +11,8 @@
 
 namespace l2z {
 
+struct BatchScratch;  // batch_host.cpp
+
 // ----- shard geometry (DESIGN.md "Sharding"; world == 1 -> everything local) -----
 struct Shard {
     int rank = 0, world = 1;
@@ -135,6 +137,7 @@ struct l2z_runstate {
     bool fused_qkv_attn = false;  // small models: qkv + RoPE + KV write + attention in one launch
     int max_blocks = 0;
     int tl_attn_seq = 0;           // attention launches enqueued so far (AttnArgs::tl_seq, measurement builds)
+    l2z::BatchScratch *bt = nullptr;  // batched decode scratch of the calls that name this runstate first (batch_host.cpp)
 };
 
 namespace l2z {
@@ -160,5 +163,8 @@ bool prefill_usable(const l2z_runstate *s);
 bool prefill_shard_takes_the_unsharded_kernels(const l2z_config &c, const Shard &sh);
 int prefill_check(const l2z_config *config, const l2z_runstate *s);
 int prefill_tokens(l2z_runstate *s, const l2z_weights *w, const int32_t *tokens, int n_tokens, int pos0);
+
+// batch_host.cpp
+void batch_free(l2z_runstate *s);
 
 }  // namespace l2z

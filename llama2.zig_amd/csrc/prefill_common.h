@@ -17,8 +17,13 @@ constexpr int kPfBlock = 256;
 
 enum GemmEpi { G_STORE = 0, G_RESID = 1, G_ROPE = 2, G_ROPE_CACHE = 3, G_CACHE = 4, G_SWIGLU = 5,
                G_QKV = 6,    // q | k | v in one launch: the epilogue of the block's column range (direct-to-LDS tile kernel only)
-               G_SWIGLU_IL = 7 };  // W1 | W3 as ONE matrix of alternating rows (the device blob's slot: DESIGN.md 2): feature 2 p is
+               G_SWIGLU_IL = 7,    // W1 | W3 as ONE matrix of alternating rows (the device blob's slot: DESIGN.md 2): feature 2 p is
                                    // W1's row p, 2 p + 1 W3's -- adjacent lanes; out[token][p] = silu(a) * b (stream kernel only)
+               // the batched decode step (batch_host.cpp): every row its own sequence -- position row_pos[token], caches
+               // row_kc / row_vc[token] + layer_off, logits row_out[token] (short-prompt direct-to-LDS form only)
+               G_ROPE_ROWS = 8,    // q: RoPE at row_pos[token], out[token][f]
+               G_QKV_ROWS = 9,     // wk | wv (paired): RoPE'd key into row_kc[token], value into row_vc[token], row row_pos[token]
+               G_OUT_ROWS = 10 };  // row_out[token][f] = product (the classifier straight into each runstate's logits)
 
 // main.zig:411-416 on the W3 product: out holds W1 x, becomes silu(W1 x) * (W3 x)
 __device__ __forceinline__ float swiglu_merge(float h1, float h3)
@@ -67,6 +72,12 @@ struct GemmArgs {
     // G_RESID (stream form, sk > 1): != 0: the blocks leave their K range's sums in sk_part and END -- the next rmsnorm
     // launch adds them and the residual (l2z_internal.h DeferredSum)
     int defer;
+    // G_*_ROWS (batched decode): per-row position, cache bases (layer 0; layer_off floats added), output rows
+    const int *row_pos;
+    float *const *row_kc;
+    float *const *row_vc;
+    float *const *row_out;
+    size_t layer_off;
 };
 
 
@@ -195,6 +206,8 @@ inline int pad_k(int K, int granule, int ldx)
 // prefill_skinny.hip: the short-prompt (P <= 64 tokens) GEMM forms; picks the form and the token tiling
 hipError_t launch_prefill_skinny(int epi, const GemmArgs &a, hipStream_t st);
 hipError_t launch_prefill_skinny_pair(int epi, const GemmArgs &a, hipStream_t st);  // G_SWIGLU: w | w2 gated; G_QKV: wk | wv
+// the batched decode step's products (G_ROPE_ROWS, G_OUT_ROWS; G_QKV_ROWS paired): the one-tile form at every P <= 16
+hipError_t launch_batch_skinny(int epi, const GemmArgs &a, hipStream_t st);
 
 
 }  // namespace l2z

@@ -46,7 +46,7 @@ __global__ __launch_bounds__(kPfBlock) void prefill_skinny_dma(const GemmArgs a)
     constexpr int WST = 16 * kSkLD2, XST = 16 * TMS * kSkLD2, ST = NW * WST + XST;  // floats per stage: W rows, then X rows
     constexpr int LPS = 4 * NW + 4 * TMS;  // this wave's loads per stage
     static_assert(SW >= 3 && SW <= 4, "ring depth");
-    static_assert(NW == 1 || (NW == 2 && (EPI == G_SWIGLU || EPI == G_QKV)), "paired forms");
+    static_assert(NW == 1 || (NW == 2 && (EPI == G_SWIGLU || EPI == G_QKV || EPI == G_QKV_ROWS)), "paired forms");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 15, q = lane >> 4;
     // 1-D grid when there are several token tiles (a.nty > 0): the blocks that read the same 16 rows of W
@@ -151,20 +151,26 @@ __global__ __launch_bounds__(kPfBlock) void prefill_skinny_dma(const GemmArgs a)
         }
         const int tok = m0 + 16 * tm + 4 * (l >> 4) + r;
         const int f = n0 + (l & 15);
-        if (EPI == G_ROPE || EPI == G_ROPE_CACHE || EPI == G_QKV) {
+        if (EPI == G_ROPE || EPI == G_ROPE_CACHE || EPI == G_QKV || EPI == G_ROPE_ROWS || EPI == G_QKV_ROWS) {
             const float partner = __shfl_xor(v, 1, 64);  // feature f ^ 1, same token (main.zig:346-349)
             const int hs = a.head_size;
-            const int pos = a.pos0 + (tok < a.P ? tok : 0);
+            const int pos = (EPI == G_ROPE_ROWS || EPI == G_QKV_ROWS) ? a.row_pos[tok < a.P ? tok : 0] : a.pos0 + (tok < a.P ? tok : 0);
             const float2 cs = a.rope[(size_t)pos * (size_t)(hs >> 1) + (size_t)(((f < a.N ? f : 0) % hs) >> 1)];
             v = (f & 1) ? partner * cs.y + v * cs.x : v * cs.x - partner * cs.y;
         }
         if (tok < a.P && f < a.N) {
             if (NW == 2 && EPI == G_SWIGLU) a.out[(size_t)tok * a.ldo + f] = swiglu_merge(v, v2);  // :411-416
+            else if (NW == 2 && EPI == G_QKV_ROWS) {  // this row's own sequence: its caches, its position
+                const size_t i = kv_index(a, a.ldkv, a.row_pos[tok], f);
+                a.row_kc[tok][a.layer_off + i] = v;
+                a.row_vc[tok][a.layer_off + i] = v2;
+            }
             else if (NW == 2) {  // wk | wv: key-cache row (RoPE above), value-cache row
                 a.outk[kv_index(a, a.ldkv, a.pos0 + tok, f)] = v;
                 a.outv[kv_index(a, a.ldkv, a.pos0 + tok, f)] = v2;
             }
-            else if (EPI == G_STORE || EPI == G_ROPE) a.out[(size_t)tok * a.ldo + f] = v;
+            else if (EPI == G_STORE || EPI == G_ROPE || EPI == G_ROPE_ROWS) a.out[(size_t)tok * a.ldo + f] = v;
+            else if (EPI == G_OUT_ROWS) a.row_out[tok][f] = v;
             else if (EPI == G_RESID) a.out[(size_t)tok * a.ldo + f] = a.res[(size_t)tok * a.ldres + f] + v;
             else if (EPI == G_SWIGLU) a.out[(size_t)tok * a.ldo + f] = swiglu_merge(a.out[(size_t)tok * a.ldo + f], v);
             else a.out[kv_index(a, a.ldo, a.pos0 + tok, f)] = v;
@@ -243,8 +249,9 @@ hipError_t launch_prefill_skinny_pair(int epi, const GemmArgs &a, hipStream_t st
     if (!skinny_one_tile(a)) return hipErrorNotSupported;
     constexpr int SW = 3;
     const size_t lds = (size_t)SW * (32 + 16) * kSkLD2 * sizeof(float);
-    const void *fn = epi == G_SWIGLU ? (const void *)prefill_skinny_dma<G_SWIGLU, 1, SW, 2>
-                   : epi == G_QKV    ? (const void *)prefill_skinny_dma<G_QKV, 1, SW, 2> : nullptr;
+    const void *fn = epi == G_SWIGLU   ? (const void *)prefill_skinny_dma<G_SWIGLU, 1, SW, 2>
+                   : epi == G_QKV      ? (const void *)prefill_skinny_dma<G_QKV, 1, SW, 2>
+                   : epi == G_QKV_ROWS ? (const void *)prefill_skinny_dma<G_QKV_ROWS, 1, SW, 2> : nullptr;
     if (fn == nullptr) return hipErrorInvalidValue;
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
@@ -263,6 +270,22 @@ hipError_t launch_prefill_skinny_pair(int epi, const GemmArgs &a, hipStream_t st
     }
     void *params[] = {&args};
     return hipLaunchKernel(fn, g1, dim3(kPfBlock), params, lds, st);
+}
+
+// The batched decode step (batch_host.cpp): P <= 16 rows, one token tile -- the form, the grid and the K order of every
+// product are functions of the matrix alone, never of P, and an MFMA's output row depends on its own input row only: a
+// row's result is the same bits whatever the other rows hold and however many there are.
+hipError_t launch_batch_skinny(int epi, const GemmArgs &a, hipStream_t st)
+{
+    if (a.P < 1 || a.P > 16) return hipErrorInvalidValue;
+    switch (epi) {
+        case G_ROPE_ROWS: return skinny_launch_t<G_ROPE_ROWS, 1>(a, st);
+        case G_OUT_ROWS: return skinny_launch_t<G_OUT_ROWS, 1>(a, st);
+        case G_QKV_ROWS: return launch_prefill_skinny_pair(G_QKV_ROWS, a, st);
+        case G_RESID: return skinny_launch_t<G_RESID, 1>(a, st);
+        case G_SWIGLU: return launch_prefill_skinny_pair(G_SWIGLU, a, st);
+    }
+    return hipErrorInvalidValue;
 }
 
 hipError_t launch_prefill_skinny(int epi, const GemmArgs &a, hipStream_t st)

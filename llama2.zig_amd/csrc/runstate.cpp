@@ -176,6 +176,7 @@ extern "C" void l2z_runstate_free(l2z_runstate *s)
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (s->h_stage) (void)hipHostFree(s->h_stage);
+    l2z::batch_free(s);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }
