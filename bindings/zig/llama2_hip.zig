@@ -111,6 +111,18 @@ pub extern fn l2z_transformer_batch(
     w: *const L2zWeights,
 ) c_int;
 pub extern fn l2z_argmax_batch(n: c_int, states: [*]const *L2zRunState, out_tokens: [*]i32) c_int;
+/// main.zig:1002-1012 for n runstates on the device: the token the host samplers draw from states[i]'s logits with
+/// temperature[i], top_p[i] and the drawn number coins[i] (one std.Random.float(f32) per sampled token).
+pub extern fn l2z_sample_batch(
+    n: c_int,
+    states: [*]const *L2zRunState,
+    temperature: [*]const f32,
+    top_p: [*]const f32,
+    coins: [*]const f32,
+    out_tokens: [*]i32,
+) c_int;
+/// dst takes src's KV-cache rows 0 .. n_pos-1 and its logits; dst's next position is n_pos (one prompt, many samples).
+pub extern fn l2z_runstate_fork(dst: *L2zRunState, src: *const L2zRunState, n_pos: c_int) c_int;
 
 pub const Error = error{DeviceForwardFailed};
 

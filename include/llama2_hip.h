@@ -177,6 +177,27 @@ int l2z_transformer_batch(int n, const int32_t *tokens, const int32_t *pos, cons
 /* out_tokens[i] = argmax of states[i]'s logits (strict '>', lowest index wins): one launch, one sync.  The runstates
  * follow l2z_transformer_batch's rules (distinct, unsharded, one device, one config). */
 int l2z_argmax_batch(int n, l2z_runstate *const *states, int32_t *out_tokens);
+/* src/main.zig:1002-1012 on the device for n runstates, one launch, one sync: out_tokens[i] = the token the host
+ * samplers draw from states[i]'s logits with temperature[i], top_p[i] and the random number coins[i] (the
+ * std.Random.float(f32) value the reference draws, :731 / :789):
+ *   temperature[i] == 0: the argmax, as l2z_argmax_batch (the coin is not used);
+ *   else probs = softmax(logits / temperature[i]), bit for bit what l2z_probs_read returns, then
+ *   top_p[i] == 0 or 1: sample (:728-741): the first token whose cdf (a sequential f32 sum in token order) exceeds
+ *                       the coin, else vocab_size - 1;
+ *   otherwise:          sample_top_p (:754-798) with the candidates ordered by (probability descending, token id
+ *                       ascending), the host sampler's total order, and its sequential f32 sums.
+ * The logits are not modified.  A row's token depends on its own runstate and arguments alone (BATCH INVARIANCE).
+ * Contract (else L2Z_ERR_INVALID with nothing enqueued): the runstates follow l2z_transformer_batch's rules;
+ * temperature[i] finite and >= 0, top_p[i] in [0, 1], coins[i] in [0, 1).  Streams as in l2z_transformer_batch. */
+int l2z_sample_batch(int n, l2z_runstate *const *states, const float *temperature, const float *top_p,
+                     const float *coins, int32_t *out_tokens);
+/* dst becomes a copy of src's first n_pos positions: KV-cache rows 0 .. n_pos-1 of every layer and src's logits
+ * (device to device, no sync).  dst's rows >= n_pos are not touched; its next position is n_pos, so it continues
+ * src's sequence from there (N samples of one prompt run the prompt once).  The greedy loop's state is not copied
+ * (l2z_greedy_begin starts it over).  dst's stream waits for src's, and src's for the copies.
+ * Contract: dst and src distinct, unsharded, on one device, made with one config (else L2Z_ERR_INVALID);
+ * 0 <= n_pos <= seq_len (else L2Z_ERR_STATE); nothing is enqueued on a refusal. */
+int l2z_runstate_fork(l2z_runstate *dst, const l2z_runstate *src, int n_pos);
 
 /* ---- multi-GPU shard group: one process per GPU, xGMI ----
  * The reference is single-threaded and single-device; this is what the build

@@ -178,6 +178,13 @@ int l2z_option_set(const char *env_name, long long value);
  * events on the pass's stream; *out_ms = milliseconds per step.  The steps rewrite the same KV rows. */
 int l2z_batch_time(int n, const int32_t *tokens, const int32_t *pos, const l2z_config *config,
                    l2z_runstate *const *states, const l2z_weights *w, int iters, double *out_ms);
+/* Place exact logits (vocab_size floats) in an unsharded runstate: the distributions l2z_sample_batch is tested on
+ * (ties at the top-p cut, peaked, uniform, one-hot).  Synchronous. */
+int l2z_logits_write(l2z_runstate *s, const float *logits);
+/* Measurement (scripts/sample_bench.py): one l2z_sample_batch launch, then `iters` more back to back without the copy
+ * back, timed by device events on states[0]'s stream; *out_ms = milliseconds per launch. */
+int l2z_sample_time(int n, l2z_runstate *const *states, const float *temperature, const float *top_p,
+                    const float *coins, int iters, double *out_ms);
 
 #ifdef __cplusplus
 }

@@ -90,6 +90,10 @@ def lib():
     L.l2z_transformer_batch.argtypes = [C.c_int, i32p, i32p, cfgp, C.POINTER(vp), vp]
     L.l2z_argmax_batch.argtypes = [C.c_int, C.POINTER(vp), i32p]
     L.l2z_batch_time.argtypes = [C.c_int, i32p, i32p, cfgp, C.POINTER(vp), vp, C.c_int, C.POINTER(C.c_double)]
+    L.l2z_sample_batch.argtypes = [C.c_int, C.POINTER(vp), fp, fp, fp, i32p]
+    L.l2z_runstate_fork.argtypes = [vp, vp, C.c_int]
+    L.l2z_logits_write.argtypes = [vp, fp]
+    L.l2z_sample_time.argtypes = [C.c_int, C.POINTER(vp), fp, fp, fp, C.c_int, C.POINTER(C.c_double)]
     L.l2z_greedy_begin.argtypes = [vp, i32p, C.c_int]
     L.l2z_greedy_run.argtypes = [cfgp, vp, vp, C.c_int, i32p, ip]
     L.l2z_profile_forward.argtypes = [C.c_int, C.c_int, cfgp, vp, vp, C.POINTER(C.c_double), ip,
@@ -319,6 +323,12 @@ class RunState:
         _chk(lib().l2z_probs_read(self.h, C.c_float(temperature), _fp(out)))
         return out
 
+    def write_logits(self, logits) -> None:
+        """l2z_logits_write (test hook): place exact logits in the runstate."""
+        lg = _f32(logits)
+        assert lg.size == self.cfg.vocab_size
+        _chk(lib().l2z_logits_write(self.h, _fp(lg)))
+
     def read(self, name: str, offset: int, count: int) -> np.ndarray:
         out = np.empty(count, np.float32)
         _chk(lib().l2z_runstate_read(self.h, name.encode(), offset, count, _fp(out)))
@@ -417,6 +427,39 @@ def batch_time(states, tokens, pos, w: Weights, iters: int) -> float:
     _chk(lib().l2z_batch_time(n, t.ctypes.data_as(C.POINTER(C.c_int32)), p.ctypes.data_as(C.POINTER(C.c_int32)),
                               C.byref(states[0].cfg), ss, w.h, iters, C.byref(ms)))
     return ms.value
+
+
+def _sample_args(states, temperature, top_p, coins):
+    n = len(states)
+    ss = (C.c_void_p * max(n, 1))(*[s.h for s in states])
+    vals = []
+    for v in (temperature, top_p, coins):
+        a = np.zeros(max(n, 1), np.float32)
+        a[:n] = np.broadcast_to(np.asarray(v, np.float32), (n,)) if n else []
+        vals.append(a)
+    return n, ss, vals
+
+
+def sample_batch(states, temperature, top_p, coins) -> np.ndarray:
+    """l2z_sample_batch: one token per runstate, drawn on the device from its logits with temperature[i], top_p[i] and
+    the number coins[i] exactly as the host samplers draw (scalars apply to every row)."""
+    n, ss, (t, p, c) = _sample_args(states, temperature, top_p, coins)
+    out = np.zeros(max(n, 1), np.int32)
+    _chk(lib().l2z_sample_batch(n, ss, _fp(t), _fp(p), _fp(c), out.ctypes.data_as(C.POINTER(C.c_int32))))
+    return out[:n].copy()
+
+
+def sample_time(states, temperature, top_p, coins, iters: int) -> float:
+    """l2z_sample_time: milliseconds per l2z_sample_batch launch, device events over `iters` launches."""
+    n, ss, (t, p, c) = _sample_args(states, temperature, top_p, coins)
+    ms = C.c_double(0.0)
+    _chk(lib().l2z_sample_time(n, ss, _fp(t), _fp(p), _fp(c), iters, C.byref(ms)))
+    return ms.value
+
+
+def runstate_fork(dst: RunState, src: RunState, n_pos: int) -> None:
+    """l2z_runstate_fork: dst takes src's KV rows 0 .. n_pos-1 and its logits; dst's next position is n_pos."""
+    _chk(lib().l2z_runstate_fork(dst.h, src.h, n_pos))
 
 
 def emu_transformer(states, weights, token: int, pos: int) -> None:

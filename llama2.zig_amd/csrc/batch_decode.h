@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 
@@ -18,6 +19,9 @@ struct BatchTable {
     float *kc[kBatchMax];
     float *vc[kBatchMax];
     float *logits[kBatchMax];
+    float temperature[kBatchMax];  // l2z_sample_batch only
+    float top_p[kBatchMax];
+    float coin[kBatchMax];
 };
 
 // Decode attention (main.zig:361-389) for n rows, one block per (head, row): row b reads its own caches up to
@@ -35,5 +39,48 @@ hipError_t launch_batch_attention(const BatchAttnArgs &a, int n, hipStream_t st)
 
 // out[b] = argmax of tab->logits[b][0 .. vocab) (main.zig:715-726: strict '>', lowest index wins), one block per row
 hipError_t launch_batch_argmax(const BatchTable *tab, int vocab, int *out, int n, hipStream_t st);
+
+// The argmax of lg[0 .. vocab) for a block of 1024 threads, valid in thread 0: each thread scans its indices in
+// increasing order (strict '>' keeps the lowest, :720), the candidates combine by (value, then lower index).
+// s_val / s_idx: 16 entries of LDS each.  Shared by the argmax of the batched step and l2z_sample_batch's rows at
+// temperature 0, which must pick the same token.
+__device__ inline int block_argmax_1024(const float *lg, int vocab, float *s_val, int *s_idx)
+{
+    const int tid = threadIdx.x;
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = tid; i < vocab; i += 1024) {
+        const float v = lg[i];
+        if (bi == 0x7fffffff || v > best) { best = v; bi = i; }
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float ov = __shfl_xor(best, off, 64);
+        const int oi = __shfl_xor(bi, off, 64);
+        if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > best || (ov == best && oi < bi))) { best = ov; bi = oi; }
+    }
+    if ((tid & 63) == 0) { s_val[tid >> 6] = best; s_idx[tid >> 6] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 16; w++) {
+            const float ov = s_val[w];
+            const int oi = s_idx[w];
+            if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > best || (ov == best && oi < bi))) { best = ov; bi = oi; }
+        }
+    }
+    return bi == 0x7fffffff ? 0 : bi;
+}
+
+// l2z_sample_batch (sample_batch.hip): row b draws one token from tab->logits[b] with tab->temperature[b],
+// tab->top_p[b] and tab->coin[b] exactly as the host samplers do (llama2.zig_amd/host, main.zig:728-798), one block of
+// 1024 threads per row.  scratch: sample_scratch_floats(vocab) floats per row, row_stride apart.
+struct SampleArgs {
+    const BatchTable *tab;
+    float *scratch;
+    size_t row_stride;
+    int vocab;
+    int *out;
+};
+inline size_t sample_scratch_floats(int vocab) { return 5 * (((size_t)vocab + 63) / 64 * 64); }
+hipError_t launch_sample_batch(const SampleArgs &a, int n, hipStream_t st);
 
 }  // namespace l2z

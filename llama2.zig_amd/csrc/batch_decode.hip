@@ -92,35 +92,12 @@ __global__ __launch_bounds__(kBaBlock) void batch_attention_kernel(const BatchAt
     }
 }
 
-// one block per row: the row's logits scanned in increasing index per thread (strict '>' keeps the lowest, :720),
-// the candidates combined by (value, then lower index)
 __global__ __launch_bounds__(1024) void batch_argmax_kernel(const BatchTable *tab, int vocab, int *out)
 {
     __shared__ float s_val[16];
     __shared__ int s_idx[16];
-    const int tid = threadIdx.x, b = blockIdx.x;
-    const float *lg = tab->logits[b];
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = tid; i < vocab; i += 1024) {
-        const float v = lg[i];
-        if (bi == 0x7fffffff || v > best) { best = v; bi = i; }
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float ov = __shfl_xor(best, off, 64);
-        const int oi = __shfl_xor(bi, off, 64);
-        if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > best || (ov == best && oi < bi))) { best = ov; bi = oi; }
-    }
-    if ((tid & 63) == 0) { s_val[tid >> 6] = best; s_idx[tid >> 6] = bi; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < 16; w++) {
-            const float ov = s_val[w];
-            const int oi = s_idx[w];
-            if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > best || (ov == best && oi < bi))) { best = ov; bi = oi; }
-        }
-        out[b] = bi == 0x7fffffff ? 0 : bi;
-    }
+    const int bi = block_argmax_1024(tab->logits[blockIdx.x], vocab, s_val, s_idx);
+    if (threadIdx.x == 0) out[blockIdx.x] = bi;
 }
 
 }  // namespace

@@ -1,6 +1,9 @@
 // batch_host.cpp -- host side of the batched decode step (l2z_transformer_batch, l2z_argmax_batch): up to
 // L2Z_BATCH_MAX independent sequences advanced by one token with one sweep of the weights.  Kernels: the short-prompt
-// GEMM forms with per-row epilogues (prefill_skinny.hip, G_*_ROWS) and batch_decode.hip.
+// GEMM forms with per-row epilogues (prefill_skinny.hip, G_*_ROWS) and batch_decode.hip.  Also what a batch of samples
+// needs around the step: the on-device sampler l2z_sample_batch (sample_batch.hip) and the prompt copy
+// l2z_runstate_fork.
+#include <cmath>
 #include <cstring>
 
 #include "batch_decode.h"
@@ -22,13 +25,15 @@ struct BatchScratch {
     hipEvent_t ev_in[kBatchMax] = {};
     hipEvent_t ev_done = nullptr;
     hipEvent_t ev_upload = nullptr;  // the last table copy: the pinned table may be rewritten once it has completed
+    float *smp = nullptr;            // l2z_sample_batch: kBatchMax rows of sample_scratch_floats(vocab) (on first use)
+    size_t smp_stride = 0;
 };
 
 void batch_free(l2z_runstate *s)
 {
     BatchScratch *b = s->bt;
     if (b == nullptr) return;
-    void *ptrs[] = {b->x, b->xn, b->q, b->att, b->h1, b->scores, b->d_tab, b->d_tokens_out};
+    void *ptrs[] = {b->x, b->xn, b->q, b->att, b->h1, b->scores, b->d_tab, b->d_tokens_out, b->smp};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (b->h_tab) (void)hipHostFree(b->h_tab);
@@ -268,6 +273,174 @@ extern "C" int l2z_argmax_batch(int n, l2z_runstate *const *states, int32_t *out
     L2Z_HIP(hipStreamSynchronize(st));
     memcpy(out_tokens, b->h_tokens_out, (size_t)n * 4);
     return L2Z_OK;
+}
+
+namespace l2z {
+namespace {
+
+int sample_alloc(l2z_runstate *s)
+{
+    BatchScratch *b = s->bt;
+    if (b->smp != nullptr) return L2Z_OK;
+    const size_t stride = sample_scratch_floats(s->cfg.vocab_size), bytes = kBatchMax * stride * 4;
+    const hipError_t e = hipMalloc(&b->smp, bytes);
+    if (e != hipSuccess) {
+        b->smp = nullptr;
+        set_error("l2z_sample_batch scratch allocation (%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
+    }
+    b->smp_stride = stride;
+    return L2Z_OK;
+}
+
+// l2z_sample_batch's checks, table and launch on states[0]'s stream (no copy back)
+int sample_enqueue(int n, l2z_runstate *const *states, const float *temperature, const float *top_p, const float *coins)
+{
+    L2Z_TRY(no_device_check());
+    L2Z_CHECK(temperature != nullptr && top_p != nullptr && coins != nullptr, L2Z_ERR_INVALID,
+              "l2z_sample_batch: null argument");
+    L2Z_TRY(check_states("l2z_sample_batch", n, states, nullptr));
+    for (int i = 0; i < n; i++) {
+        L2Z_CHECK(std::isfinite(temperature[i]) && temperature[i] >= 0.0f, L2Z_ERR_INVALID,
+                  "l2z_sample_batch: temperature[%d] = %g (finite, >= 0)", i, (double)temperature[i]);
+        L2Z_CHECK(top_p[i] >= 0.0f && top_p[i] <= 1.0f, L2Z_ERR_INVALID, "l2z_sample_batch: top_p[%d] = %g outside [0, 1]", i,
+                  (double)top_p[i]);
+        L2Z_CHECK(coins[i] >= 0.0f && coins[i] < 1.0f, L2Z_ERR_INVALID, "l2z_sample_batch: coins[%d] = %g outside [0, 1)", i,
+                  (double)coins[i]);
+    }
+    L2Z_HIP(hipSetDevice(states[0]->device));
+    L2Z_TRY(batch_alloc(states[0]));
+    L2Z_TRY(sample_alloc(states[0]));
+    BatchScratch *b = states[0]->bt;
+    BatchTable t = {};
+    for (int i = 0; i < n; i++) {
+        t.logits[i] = states[i]->logits;
+        t.temperature[i] = temperature[i];
+        t.top_p[i] = top_p[i];
+        t.coin[i] = coins[i];
+    }
+    hipStream_t st = states[0]->stream;
+    L2Z_TRY(join_streams(b, n, states));
+    L2Z_TRY(upload_table(b, t, st));
+    SampleArgs a = {};
+    a.tab = b->d_tab; a.scratch = b->smp; a.row_stride = b->smp_stride; a.vocab = states[0]->cfg.vocab_size;
+    a.out = b->d_tokens_out;
+    L2Z_HIP(launch_sample_batch(a, n, st));
+    return L2Z_OK;
+}
+
+}  // namespace
+}  // namespace l2z
+
+extern "C" int l2z_sample_batch(int n, l2z_runstate *const *states, const float *temperature, const float *top_p,
+                                const float *coins, int32_t *out_tokens)
+{
+    L2Z_CHECK(out_tokens != nullptr, L2Z_ERR_INVALID, "l2z_sample_batch: null argument");
+    L2Z_TRY(sample_enqueue(n, states, temperature, top_p, coins));
+    BatchScratch *b = states[0]->bt;
+    hipStream_t st = states[0]->stream;
+    L2Z_HIP(hipMemcpyAsync(b->h_tokens_out, b->d_tokens_out, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    L2Z_TRY(release_streams(b, n, states));
+    L2Z_HIP(hipStreamSynchronize(st));
+    memcpy(out_tokens, b->h_tokens_out, (size_t)n * 4);
+    return L2Z_OK;
+}
+
+extern "C" int l2z_runstate_fork(l2z_runstate *dst, const l2z_runstate *src, int n_pos)
+{
+    L2Z_TRY(no_device_check());
+    L2Z_CHECK(dst != nullptr && src != nullptr, L2Z_ERR_INVALID, "l2z_runstate_fork: null runstate");
+    L2Z_CHECK(dst != src, L2Z_ERR_INVALID, "l2z_runstate_fork: dst and src are the same runstate");
+    L2Z_CHECK(dst->comm == nullptr && dst->sh.world == 1 && src->comm == nullptr && src->sh.world == 1, L2Z_ERR_INVALID,
+              "l2z_runstate_fork: shard runstates are not forked");
+    L2Z_CHECK(memcmp(&dst->cfg, &src->cfg, sizeof(l2z_config)) == 0, L2Z_ERR_INVALID,
+              "l2z_runstate_fork: dst was made with another config");
+    L2Z_CHECK(dst->device == src->device, L2Z_ERR_INVALID, "l2z_runstate_fork: dst is on device %d, src on %d", dst->device,
+              src->device);
+    const l2z_config &c = src->cfg;
+    L2Z_CHECK(n_pos >= 0 && n_pos <= c.seq_len, L2Z_ERR_STATE, "l2z_runstate_fork: n_pos = %d outside [0, %d]", n_pos,
+              c.seq_len);
+    L2Z_HIP(hipSetDevice(src->device));
+    hipEvent_t ev_src = nullptr, ev_dst = nullptr;
+    L2Z_HIP(hipEventCreateWithFlags(&ev_src, hipEventDisableTiming));
+    int rc = L2Z_OK;
+    auto hip = [&rc](hipError_t e, const char *what) {
+        if (rc == L2Z_OK && e != hipSuccess) {
+            set_error("l2z_runstate_fork: %s: %s", what, hipGetErrorString(e));
+            rc = L2Z_ERR_HIP;
+        }
+    };
+    hip(hipEventCreateWithFlags(&ev_dst, hipEventDisableTiming), "hipEventCreate");
+    // dst's stream waits for what src's has queued (the rows and logits being copied) ...
+    hip(hipEventRecord(ev_src, src->stream), "hipEventRecord");
+    hip(hipStreamWaitEvent(dst->stream, ev_src, 0), "hipStreamWaitEvent");
+    // ... the caches are head-major [layer][kv head][seq_len][head_size]: positions 0 .. n_pos - 1 are one
+    // run of n_pos * head_size floats per (layer, kv head), seq_len * head_size floats apart
+    const size_t hs = (size_t)c.dim / c.n_heads, pitch = (size_t)c.seq_len * hs * 4, width = (size_t)n_pos * hs * 4;
+    const size_t rows = (size_t)c.n_layers * c.n_kv_heads;
+    if (n_pos > 0 && rc == L2Z_OK) {
+        hip(hipMemcpy2DAsync(dst->key_cache, pitch, src->key_cache, pitch, width, rows, hipMemcpyDeviceToDevice, dst->stream),
+            "key cache copy");
+        hip(hipMemcpy2DAsync(dst->value_cache, pitch, src->value_cache, pitch, width, rows, hipMemcpyDeviceToDevice,
+                             dst->stream),
+            "value cache copy");
+    }
+    if (rc == L2Z_OK)
+        hip(hipMemcpyAsync(dst->logits, src->logits, (size_t)c.vocab_size * 4, hipMemcpyDeviceToDevice, dst->stream),
+            "logits copy");
+    // ... and src's stream waits for the copies: its next step overwrites the logits they read
+    hip(hipEventRecord(ev_dst, dst->stream), "hipEventRecord");
+    hip(hipStreamWaitEvent(src->stream, ev_dst, 0), "hipStreamWaitEvent");
+    (void)hipEventDestroy(ev_src);  // released by the runtime once the streams are past them
+    if (ev_dst) (void)hipEventDestroy(ev_dst);
+    if (rc != L2Z_OK) return rc;
+    dst->n_part = 0;  // l2z_argmax scans the copied logits, not dst's own classifier candidates
+    dst->logits_partial = false;
+    dst->host_pos = n_pos;
+    return L2Z_OK;
+}
+
+// Testing support (include/llama2_hip_test.h): place exact logits in a runstate (vocab_size floats), queued on its stream
+extern "C" int l2z_logits_write(l2z_runstate *s, const float *logits)
+{
+    L2Z_TRY(no_device_check());
+    L2Z_CHECK(s != nullptr && logits != nullptr, L2Z_ERR_INVALID, "l2z_logits_write: null argument");
+    L2Z_CHECK(s->comm == nullptr && s->sh.world == 1, L2Z_ERR_INVALID, "l2z_logits_write: shard runstate");
+    L2Z_HIP(hipSetDevice(s->device));
+    L2Z_HIP(hipMemcpyAsync(s->logits, logits, (size_t)s->cfg.vocab_size * 4, hipMemcpyHostToDevice, s->stream));
+    L2Z_HIP(hipStreamSynchronize(s->stream));
+    s->n_part = 0;
+    s->logits_partial = false;
+    return L2Z_OK;
+}
+
+// Testing support: `iters` l2z_sample_batch launches back to back (no copy back), timed by device events on the
+// launches' stream (scripts/sample_bench.py)
+extern "C" int l2z_sample_time(int n, l2z_runstate *const *states, const float *temperature, const float *top_p,
+                               const float *coins, int iters, double *out_ms)
+{
+    L2Z_CHECK(iters >= 1 && out_ms != nullptr, L2Z_ERR_INVALID, "l2z_sample_time: bad arguments");
+    L2Z_TRY(sample_enqueue(n, states, temperature, top_p, coins));  // validates, allocates, warms up
+    hipStream_t st = states[0]->stream;
+    hipEvent_t e0, e1;
+    L2Z_HIP(hipEventCreate(&e0));
+    L2Z_HIP(hipEventCreate(&e1));
+    int rc = L2Z_OK;
+    if (hipEventRecord(e0, st) != hipSuccess) rc = L2Z_ERR_HIP;
+    BatchScratch *b = states[0]->bt;
+    SampleArgs a = {};
+    a.tab = b->d_tab; a.scratch = b->smp; a.row_stride = b->smp_stride; a.vocab = states[0]->cfg.vocab_size;
+    a.out = b->d_tokens_out;
+    for (int i = 0; i < iters && rc == L2Z_OK; i++)
+        if (launch_sample_batch(a, n, st) != hipSuccess) rc = L2Z_ERR_HIP;
+    float ms = 0.0f;
+    if (rc == L2Z_OK && (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
+                         hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
+        rc = L2Z_ERR_HIP;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (rc == L2Z_OK) *out_ms = ms / iters;
+    return rc;
 }
 
 // Testing support (include/llama2_hip_test.h): `iters` batched steps back to back, timed by device events on the pass's

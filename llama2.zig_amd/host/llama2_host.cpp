@@ -240,9 +240,10 @@ size_t argmax(const float *x, size_t n)
     return maxi;
 }
 
-size_t sample(const float *probs, size_t n, Prng &rng)
+size_t sample(const float *probs, size_t n, Prng &rng) { return sample_coin(probs, n, rng.next_f32()); }  // :731
+
+size_t sample_coin(const float *probs, size_t n, float r)
 {
-    const float r = rng.next_f32();  // :731
     float cdf = 0.0f;
     for (size_t i = 0; i < n; i++) {
         cdf += probs[i];
@@ -305,32 +306,40 @@ size_t sample_top_p(const float *probs, size_t n, float p, std::vector<IndexedF3
     return sample_top_p_margin(probs, n, p, scratch, rng, nullptr);
 }
 
-size_t sample_top_p_margin(const float *probs, size_t n, float p, std::vector<IndexedF32> &scratch,
-                           Prng &rng, float *margin)
+// :759-786: the candidates in `scratch`, sorted; false when there is none
+static bool nucleus(const float *probs, size_t n, float p, std::vector<IndexedF32> &scratch, size_t *cutoff_index,
+                    float *cumulative)
 {
-    if (margin) *margin = 1.0f;
     // :759-770 candidates below (1-p)/(n-1) cannot be in the nucleus
     const float cutoff = (1.0f - p) / ((float)n - 1.0f);
     scratch.clear();
     for (size_t i = 0; i < n; i++)
         if (probs[i] >= cutoff) scratch.push_back({(uint32_t)i, probs[i]});
-    if (scratch.empty()) return argmax(probs, n);  // reference asserts; be safe in release
+    if (scratch.empty()) return false;  // reference asserts; be safe in release
     // :774 sorts descending by probability with std.sort.pdq, an UNSTABLE sort whose order among
     // equal probabilities is an implementation detail of Zig's library (not available here).  The
     // comparator is made total -- ties go to the lower token id -- so that the nucleus and the
     // sampled token are at least deterministic across standard libraries; with tied probabilities
     // at the cut they can differ from the reference binary's for the same seed.
     sort_desc(scratch);
-    float cumulative = 0.0f;
-    size_t cutoff_index = scratch.size() - 1;  // :778
+    float cum = 0.0f;
+    *cutoff_index = scratch.size() - 1;  // :778
     for (size_t i = 0; i < scratch.size(); i++) {
-        cumulative += scratch[i].value;
-        if (cumulative > p) {  // :781
-            cutoff_index = i;
+        cum += scratch[i].value;
+        if (cum > p) {  // :781
+            *cutoff_index = i;
             break;
         }
     }
-    const float r = rng.next_f32() * cumulative;  // :789
+    *cumulative = cum;
+    return true;
+}
+
+// :789-797 with the drawn number `coin`
+static size_t nucleus_draw(const std::vector<IndexedF32> &scratch, size_t cutoff_index, float cumulative, float coin,
+                           float *margin)
+{
+    const float r = coin * cumulative;  // :789
     float cdf = 0.0f;
     if (margin) {  // how close the draw is to a boundary of the truncated cdf (tests: is a flip a near tie?)
         float m = r;  // the boundary at 0
@@ -346,6 +355,26 @@ size_t sample_top_p_margin(const float *probs, size_t n, float p, std::vector<In
         if (r < cdf) return scratch[i].index;
     }
     return scratch[cutoff_index].index;  // :797
+}
+
+size_t sample_top_p_margin(const float *probs, size_t n, float p, std::vector<IndexedF32> &scratch,
+                           Prng &rng, float *margin)
+{
+    if (margin) *margin = 1.0f;
+    size_t cutoff_index = 0;
+    float cumulative = 0.0f;
+    if (!nucleus(probs, n, p, scratch, &cutoff_index, &cumulative)) return argmax(probs, n);  // (no number drawn)
+    return nucleus_draw(scratch, cutoff_index, cumulative, rng.next_f32(), margin);
+}
+
+size_t sample_top_p_coin(const float *probs, size_t n, float p, std::vector<IndexedF32> &scratch, float coin,
+                         float *margin)
+{
+    if (margin) *margin = 1.0f;
+    size_t cutoff_index = 0;
+    float cumulative = 0.0f;
+    if (!nucleus(probs, n, p, scratch, &cutoff_index, &cumulative)) return argmax(probs, n);
+    return nucleus_draw(scratch, cutoff_index, cumulative, coin, margin);
 }
 
 int is_raw_byte(std::string_view s)
@@ -449,4 +478,13 @@ size_t l2zh_sample_top_p_rng(const float *probs, size_t n, float p, void *rng, f
     return sample_top_p_margin(probs, n, p, scratch, *static_cast<Prng *>(rng), margin);
 }
 size_t l2zh_sample_rng(const float *probs, size_t n, void *rng) { return sample(probs, n, *static_cast<Prng *>(rng)); }
+// the next number of a generator (std.Random.float(f32), one per sampled token) and the samplers given that number:
+// what the CLI's -b mode hands l2z_sample_batch, and what tests replay it with
+float l2zh_prng_next_f32(void *rng) { return static_cast<Prng *>(rng)->next_f32(); }
+size_t l2zh_sample_coin(const float *probs, size_t n, float coin) { return sample_coin(probs, n, coin); }
+size_t l2zh_sample_top_p_coin(const float *probs, size_t n, float p, float coin, float *margin)
+{
+    std::vector<IndexedF32> scratch;
+    return sample_top_p_coin(probs, n, p, scratch, coin, margin);
+}
 }

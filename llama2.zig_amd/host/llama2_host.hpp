@@ -53,6 +53,8 @@ void softmax(float *x, size_t n);
 size_t argmax(const float *x, size_t n);
 // :728-741
 size_t sample(const float *probs, size_t n, Prng &rng);
+// the same with the drawn number given (r in [0, 1))
+size_t sample_coin(const float *probs, size_t n, float r);
 // :752-798
 struct IndexedF32 {
     uint32_t index;
@@ -64,6 +66,10 @@ size_t sample_top_p(const float *probs, size_t n, float p, std::vector<IndexedF3
 // truncated cumulative distribution: how close this draw was to picking a neighbouring candidate
 size_t sample_top_p_margin(const float *probs, size_t n, float p, std::vector<IndexedF32> &scratch,
                            Prng &rng, float *margin);
+// the same draw with the number given: coin = what rng.next_f32() would return (when there is a candidate at all:
+// without one the rng forms return the argmax and draw nothing)
+size_t sample_top_p_coin(const float *probs, size_t n, float p, std::vector<IndexedF32> &scratch, float coin,
+                         float *margin);
 // :1055-1076  "<0xXX>" -> byte, only if printable or whitespace; -1 otherwise
 int is_raw_byte(std::string_view s);
 

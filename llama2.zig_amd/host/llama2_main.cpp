@@ -4,6 +4,7 @@
 //
 //   llama2 <checkpoint> [-t temp] [-p top_p] [-n steps] [-i prompt] [-s seed] [-v] [-z tokenizer]
 //          [-g n_gpus]   (extension: rows / heads sharded over n GPUs, one process per GPU)
+//          [-b n]        (extension: n independent samples of the prompt, stepped together: run_batch)
 //
 // At -t 0 the whole generation loop runs on the device (l2z_greedy_run) and the host
 // only prints; otherwise one l2z_transformer + l2z_logits_read per position feeds the
@@ -41,7 +42,9 @@ static const char *usage_text =
     " -v, --verbose             print model info and tokens/s\n"
     " -z, --tokenizer <path>    path to the tokenizer to use, default to \"tokenizer.bin\"\n"
     " --tokens                  (extension) also print the token ids to stderr, one line\n"
-    " -g, --gpus <int>          (extension) shard weight rows / heads over this many GPUs, default 1\n";
+    " -g, --gpus <int>          (extension) shard weight rows / heads over this many GPUs, default 1\n"
+    " -b, --batch <int>         (extension) generate this many independent samples of the prompt together, 1-16,\n"
+    "                           default 1; sample i draws from seed + i\n";
 
 static bool verbose = false;
 #define LOGV(...)                                 \
@@ -109,6 +112,111 @@ static bool exchange_handles(const std::string &dir, const std::vector<pid_t> &k
     return true;
 }
 
+// -b N, N >= 2: N independent samples of the prompt.  The prompt's positions run once, on s (one batched prefill where
+// the sampled path of main() takes it, else stepped); l2z_runstate_fork copies them to N - 1 more runstates; then each
+// position is one l2z_transformer_batch and one l2z_sample_batch over the samples still running.  A sample leaves at
+// BOS (:1017) or at the -n limit.  Sample i draws its numbers from its own generator seeded seed + i, one per sampled
+// token as :1009-1012 draw them, so sample 0 uses the stream of the run without -b.  The texts print when every sample
+// has ended, each behind a line "--- sample i ---".
+static int run_batch(int nb, const l2z_config &cfg, const l2z_weights *w, l2z_runstate *s, const Tokenizer &tok,
+                     const std::vector<int32_t> &prompt, size_t seq_len, float temperature, float top_p, uint64_t seed,
+                     bool dump_tokens)
+{
+    struct Sample {
+        l2z_runstate *st = nullptr;
+        Prng rng;
+        std::string text;
+        std::vector<int32_t> ids;
+        size_t token = 1;  // last emitted (the input of the next position)
+        bool alive = true;
+    };
+    std::vector<Sample> sm((size_t)nb);
+    int rc = 0;
+    sm[0].st = s;
+    for (int i = 0; i < nb; i++) {
+        sm[(size_t)i].rng.seed_with(seed + (uint64_t)i);
+        if (i > 0 && rc == 0 && l2z_runstate_init(&cfg, nullptr, &sm[(size_t)i].st) != L2Z_OK) rc = die("RunState.init");
+    }
+    auto cleanup = [&](int r) {
+        for (size_t i = 1; i < sm.size(); i++)
+            if (sm[i].st) l2z_runstate_free(sm[i].st);
+        return r;
+    };
+    if (rc) return cleanup(rc);
+    // :1017-1034 for one sample: false when the sequence ended
+    auto emit = [&](Sample &x, size_t next) -> bool {
+        x.ids.push_back((int32_t)next);
+        if (next == 1) return x.alive = false;
+        std::string_view piece = tok.tokens[next];
+        if (x.token == 1 && !piece.empty() && piece[0] == ' ') piece.remove_prefix(1);
+        const int byte = is_raw_byte(piece);
+        if (byte >= 0) x.text.push_back((char)byte);
+        else x.text.append(piece.data(), piece.size());
+        x.token = next;
+        return true;
+    };
+    // the prompt positions (:999-1000): the same tokens in every sample
+    const size_t n_prompt = std::min(prompt.size(), seq_len);
+    for (Sample &x : sm)
+        for (size_t p = 0; p < n_prompt && emit(x, (size_t)prompt[p]);) p++;
+    size_t pos = n_prompt;
+    if (sm[0].alive && pos < seq_len) {
+        const char *pf_env = getenv("L2Z_PREFILL");
+        std::vector<int32_t> in(n_prompt);
+        for (size_t i = 0; i < n_prompt; i++) in[i] = i == 0 ? 1 : prompt[i - 1];
+        size_t done = 0;
+        if (n_prompt >= L2Z_PREFILL_MIN_PROMPT && !(pf_env && atoi(pf_env) == 0) &&
+            l2z_prefill(in.data(), (int)n_prompt, 0, &cfg, s, w) == L2Z_OK)
+            done = n_prompt;
+        for (; done < n_prompt; done++)
+            if (l2z_transformer(in[done], (int)done, &cfg, s, w) != L2Z_OK) return cleanup(die("transformer"));
+        for (int i = 1; i < nb; i++)
+            if (l2z_runstate_fork(sm[(size_t)i].st, s, (int)n_prompt) != L2Z_OK) return cleanup(die("runstate_fork"));
+    }
+    std::vector<l2z_runstate *> act_st;
+    std::vector<int32_t> act_tok, act_pos, out;
+    std::vector<float> temps, tops, coins;
+    std::vector<size_t> act;
+    size_t sampled = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (; pos < seq_len; pos++) {
+        act.clear();
+        for (size_t i = 0; i < sm.size(); i++)
+            if (sm[i].alive) act.push_back(i);
+        if (act.empty()) break;
+        const size_t n = act.size();
+        act_st.resize(n); act_tok.resize(n); act_pos.assign(n, (int32_t)pos); out.resize(n);
+        temps.assign(n, temperature); tops.assign(n, top_p); coins.resize(n);
+        for (size_t j = 0; j < n; j++) {
+            Sample &x = sm[act[j]];
+            act_st[j] = x.st;
+            act_tok[j] = (int32_t)x.token;
+            coins[j] = temperature == 0.0f ? 0.0f : x.rng.next_f32();  // :731 / :789, one number per sampled token
+        }
+        if (l2z_transformer_batch((int)n, act_tok.data(), act_pos.data(), &cfg, act_st.data(), w) != L2Z_OK)
+            return cleanup(die("transformer_batch"));
+        if (l2z_sample_batch((int)n, act_st.data(), temps.data(), tops.data(), coins.data(), out.data()) != L2Z_OK)
+            return cleanup(die("sample_batch"));
+        for (size_t j = 0; j < n; j++) emit(sm[act[j]], (size_t)out[j]);
+        sampled += n;
+    }
+    for (size_t i = 0; i < sm.size(); i++) {
+        printf("--- sample %zu ---\n", i);
+        fwrite(sm[i].text.data(), 1, sm[i].text.size(), stdout);
+        fputc('\n', stdout);
+    }
+    fflush(stdout);
+    const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (sampled > 0) LOGV("\n%u tokens per second (%d samples together)\n", (unsigned)(el > 0.0 ? sampled / el : 0.0), nb);
+    if (dump_tokens)
+        for (size_t i = 0; i < sm.size(); i++) {
+            fprintf(stderr, "tokens[%zu]:", i);
+            for (int32_t t : sm[i].ids) fprintf(stderr, " %d", t);
+            fprintf(stderr, "\n");
+        }
+    return cleanup(0);
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 2) {  // :833-836
@@ -121,8 +229,9 @@ int main(int argc, char **argv)
     size_t seq_len = 0;
     std::string tokenizer_path = "tokenizer.bin";
     bool dump_tokens = false;
-    int n_gpus = 1;
-    Prng prng((uint64_t)std::chrono::system_clock::now().time_since_epoch().count());  // :844-845
+    int n_gpus = 1, n_batch = 1;
+    uint64_t seed = (uint64_t)std::chrono::system_clock::now().time_since_epoch().count();
+    Prng prng(seed);  // :844-845
 
     auto need = [&](int &i, const char *what) -> const char * {  // :863-867 etc.
         if (++i >= argc) {
@@ -181,7 +290,8 @@ int main(int argc, char **argv)
                 fprintf(stderr, "unable to parse --seed argument '%s'\n", v);
                 return 1;
             }
-            prng.seed_with((uint64_t)s);  // :926
+            seed = (uint64_t)s;
+            prng.seed_with(seed);  // :926
         } else if (a == "-v" || a == "--verbose") {
             verbose = true;
         } else if (a == "--tokens") {
@@ -192,6 +302,15 @@ int main(int argc, char **argv)
                 fprintf(stderr, "unable to use --gpus argument '%s'\n", argv[i]);
                 return 1;
             }
+        } else if (a == "-b" || a == "--batch") {
+            const char *v = need(i, "batch");
+            char *end = nullptr;
+            const long nb = strtol(v, &end, 10);
+            if (end == v || *end || nb < 1 || nb > L2Z_BATCH_MAX) {
+                fprintf(stderr, "unable to use --batch argument '%s' (1 to %d)\n", v, L2Z_BATCH_MAX);
+                return 1;
+            }
+            n_batch = (int)nb;
         } else {  // :929-933
             fprintf(stderr, "error: unknown argument '%s'\n", argv[i]);
             fputs(usage_text, stdout);
@@ -200,6 +319,10 @@ int main(int argc, char **argv)
     }
     if (!bin_path) {
         fputs(usage_text, stdout);
+        return 1;
+    }
+    if (n_batch > 1 && n_gpus > 1) {
+        fprintf(stderr, "error: --batch and --gpus do not combine: shard groups are not batched\n");
         return 1;
     }
 
@@ -351,6 +474,13 @@ int main(int argc, char **argv)
 
     seq_len = seq_len == 0 ? (size_t)cfg.seq_len : seq_len;                        // :992
     seq_len = seq_len < 1 ? 1 : (seq_len > (size_t)cfg.seq_len ? (size_t)cfg.seq_len : seq_len);  // :993
+
+    if (n_batch > 1) {
+        const int rc = run_batch(n_batch, cfg, w, s, tok, prompt, seq_len, temperature, top_p, seed, dump_tokens);
+        l2z_runstate_free(s);
+        l2z_weights_free(w);
+        return finish(rc);
+    }
 
     std::vector<float> logits((size_t)cfg.vocab_size);
     std::vector<IndexedF32> logits_indexed;
