@@ -30,6 +30,15 @@ int l2z_weights_init_synthetic(const l2z_config *config, int shared_weights, uin
  * (single-GPU weights only; used by tests to check uploads / the generator). */
 int l2z_weights_read(const l2z_weights *w, size_t offset, size_t count, float *out);
 
+/* The 29-bit packed copy of each layer's W1 | W3 slot that the decode's ffn13 launch streams (csrc/packed_w.h,
+ * DESIGN.md 4.9; unsharded weights, built at init unless L2Z_PACKED_W=0): how many layers' slots are packed, out of how
+ * many of a width the packed kernel takes.  A slot with a NaN, an Inf, a denormal or a span of more than 31 binades
+ * stays f32 only. */
+int l2z_weights_packed_count(const l2z_weights *w, int *n_packed, int *n_candidates);
+/* Decode the packed slot of `layer` ON THE DEVICE back to f32: 2 * hidden_dim rows (row 2r = W1 row r, row 2r + 1 = W3
+ * row r) x dim, row-major, into out (n_floats >= that).  L2Z_ERR_STATE if that slot is not packed. */
+int l2z_weights_packed_read(const l2z_weights *w, int layer, float *out, size_t n_floats);
+
 /* copy a named RunState buffer to the host: "x","xb","hb","q","att","logits",
  * "key_cache","value_cache" (tests only) */
 int l2z_runstate_read(l2z_runstate *s, const char *name, size_t offset, size_t count, float *out);

@@ -168,6 +168,8 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, bool with_step, Prof 
         *epi = sh.rank == 0 ? EPI_RESID : EPI_STORE;
         push_to(a, 1);
     };
+    // packed weights: ffn13 streams the 29-bit copy of its W1 | W3 slot where the weights have one
+    const bool pk = s->packed_w && w->pk_blob != nullptr && !sb && sh.world == 1 && !consume;
     for (int l = 0; l < c.n_layers; l++) {
         // :354 loff; inside a layer the device cache is head-major, [kv heads][seq_len][head_size]: the rows
         // one head's attention reads are one contiguous run
@@ -243,6 +245,7 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, bool with_step, Prof 
             a.rms_w = w->rms_ffn + (size_t)l * dim;
             x_in(a, s->x, gi, sh.dim_loc);
             if (!sb) push_to(a, 2);
+            if (pk && w->pk[l].p != nullptr) { a.pk = w->pk[l].p; a.pk_e = w->pk[l].e; }
             L2Z_LAUNCH(KIND_FFN13, launch_matvec(a, PRO_RMS, EPI_SWIGLU, mb, g_cus, st, nullptr, &pushed));
         }
         if (!sb) L2Z_TRY(gather(s->hb, sh.hid_loc));

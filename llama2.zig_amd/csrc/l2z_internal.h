@@ -133,6 +133,10 @@ struct MatvecArgs {
     int push_gi;              // index of the gather the outputs belong to
     // x is a gathered vector that is read as LL words from this rank's landing slot (xin.slots != null)
     LLIn xin;
+    // Packed weights (packed_w.h): pk != null -> the row kernel streams the 29-bit copy of w0 (base
+    // exponent pk_e) instead of its f32 rows.  EPI_SWIGLU on the W1 | W3 slot of unsharded weights only (ffn13)
+    const uint32_t *pk;
+    int pk_e;
 };
 
 // main.zig:361-389: scores, softmax, att.V for the local heads of one layer
@@ -175,6 +179,11 @@ hipError_t launch_fused_qkv_attn(const FusedQkvAttnArgs &a, int n_heads, hipStre
 // Launchers (matvec.hip, attention.hip, misc_kernels.hip).  All return a hipError_t from the launch.
 // pushed: set to whether a.push was honoured (row kernel only)
 // (a.push / a.xin are all-or-nothing: matvec_ll_supported tells beforehand whether they will be)
+// packed_w.hip: the 29-bit weight copy -- exponent stats of a matrix (stats: max e, min e, bad; preset 0, 255, 0), its
+// packing (rows x n, row-major; pk: (rows / 2) * pk::pair_dw(n / 4) dwords), and the decode back to f32 (tests)
+hipError_t launch_pk_stats(const float *m, size_t count, uint32_t *stats, hipStream_t st);
+hipError_t launch_pk_pack(const float *m, int rows, int n, int e_base, uint32_t *pk, hipStream_t st);
+hipError_t launch_pk_unpack(const uint32_t *pk, int rows, int n, int e_base, float *out, hipStream_t st);
 hipError_t launch_matvec(const MatvecArgs &a, int pro, int epi, int max_blocks_per_cu, int n_cus,
                          hipStream_t st, int *out_grid = nullptr, bool *pushed = nullptr);
 // true if a launch with this width takes the vector kernels, which honour push and xin

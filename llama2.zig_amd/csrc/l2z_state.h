@@ -70,6 +70,15 @@ struct l2z_weights {
     const float *wq = nullptr, *wk = nullptr, *wv = nullptr, *wo = nullptr;
     // w1 / w3: row 0 of W1 / of W3 in the shared slot; consecutive rows of either are 2 * dim floats apart
     const float *w1 = nullptr, *w2 = nullptr, *w3 = nullptr, *wcls = nullptr;
+    // the 29-bit packed copy of each layer's W1 | W3 slot that ffn13 streams in decode (packed_w.h, DESIGN.md 4.9;
+    // unsharded weights, L2Z_PACKED_W); pk[layer].p == null: that slot stays f32 only
+    struct PkMat {
+        const uint32_t *p = nullptr;
+        int e = 0;          // base exponent E
+    };
+    uint32_t *pk_blob = nullptr;
+    std::vector<PkMat> pk;
+    int pk_packed = 0, pk_candidates = 0;
 };
 
 enum { KIND_QKV = 0, KIND_ATTN, KIND_WO, KIND_FFN13, KIND_FFN2, KIND_CLS, KIND_ARGMAX, KIND_GATHER, KIND_COUNT };
@@ -136,6 +145,7 @@ struct l2z_runstate {
     bool logits_partial = false;
     bool fused_qkv_attn = false;  // small models: qkv + RoPE + KV write + attention in one launch
     int max_blocks = 0;
+    bool packed_w = true;          // L2Z_PACKED_W at creation: decode mat-vecs stream the weights' packed copy where it exists
     int tl_attn_seq = 0;           // attention launches enqueued so far (AttnArgs::tl_seq, measurement builds)
     l2z::BatchScratch *bt = nullptr;  // batched decode scratch of the calls that name this runstate first (batch_host.cpp)
 };

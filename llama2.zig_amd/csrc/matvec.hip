@@ -18,6 +18,7 @@
 //    step can be replayed without host involvement.
 // matvec.hip: the fused mat-vec kernels (narrow rows, wide rows, generic scalar) and their launcher.
 #include "matvec_device.h"
+#include "packed_w.h"
 
 namespace l2z {
 namespace {
@@ -235,7 +236,126 @@ __global__ __launch_bounds__(kBlock) void matvec_kernel(const MatvecArgs a)
 // t, t+256, ...; per-thread component accumulators, (x+y)+(z+w), wave xor-shuffle,
 // then the 4 wave partials are added in wave order.  Still a function of n only.
 // ---------------------------------------------------------------------------
-template <int PRO, int EPI, int XC, bool LL>
+// Packed weights (PK, packed_w.h): the raw dwords of one lane's chunk of a batch.  Plane q of 16 bytes per lane lands
+// in q4[q], single-dword plane r in q1[r]: fixed registers whatever the step count S, so a chunk of a runtime S is
+// loaded with wave-uniform predicates and no register is indexed at run time
+struct PkRaw {
+    v4u q4[7];
+    uint32_t q1[3];
+};
+
+__device__ __forceinline__ void pk_load_raw(const uint32_t *src, int lane, int s, PkRaw &r)
+{
+    const int q = pk::lane_dw(s) / 4, rem = pk::lane_dw(s) % 4;
+#pragma unroll
+    for (int i = 0; i < 7; i++)
+        if (i < q) r.q4[i] = __builtin_nontemporal_load((const v4u *)(src + i * 256 + lane * 4));
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+        if (i < rem) r.q1[i] = __builtin_nontemporal_load(src + q * 256 + i * 64 + lane);
+}
+
+// ... and its values, exactly the f32 bits, into the fp32 kernel's registers; steps past the row end are zero there too
+template <int S>
+__device__ __forceinline__ void pk_decode_lane(const PkRaw &r, int e31, v4f (&wa)[4], v4f (&wb)[4])
+{
+    constexpr int N = pk::lane_dw(S), Q = N / 4;
+    uint32_t d[N > 0 ? N : 1], t[8 * S > 0 ? 8 * S : 1];
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        if (i < 4 * Q) {
+            const v4u v = r.q4[i / 4];
+            d[i] = (i % 4 == 0) ? v.x : (i % 4 == 1) ? v.y : (i % 4 == 2) ? v.z : v.w;
+        } else {
+            d[i] = r.q1[i - 4 * Q];
+        }
+    }
+    pk::decode_lane_t<S>(d, t);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        if (k < S) {
+            wa[k] = v4f{__builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k]), e31), __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 1]), e31),
+                        __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 2]), e31), __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 3]), e31)};
+            wb[k] = v4f{__builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 4]), e31), __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 5]), e31),
+                        __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 6]), e31), __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 7]), e31)};
+        } else {
+            wa[k] = v4f{0.f, 0.f, 0.f, 0.f};
+            wb[k] = v4f{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Wide rows (n >= 4096, n/4 a multiple of 64: the 7B shapes): the WHOLE BLOCK works on
+// one pair.  Rows 2p and 2p+1 are adjacent in memory, so a block reads one contiguous
+// 8n-byte run per unit and consecutive blocks read consecutive runs -- the chip sweeps
+// the matrix linearly, like a plain streaming read (DRAM page locality: +10 % over
+// giving every wave its own row pair, measured).  Thread t takes float4 columns
+// t, t+256, ...; per-thread component accumulators, (x+y)+(z+w), wave xor-shuffle,
+// then the 4 wave partials are added in wave order.  Still a function of n only.
+// ---------------------------------------------------------------------------
+typedef unsigned v2u_ __attribute__((ext_vector_type(2)));
+typedef unsigned v3u_ __attribute__((ext_vector_type(3)));
+
+// Packed weights (PK, packed_w.h): one lane's S-step chunk of a batch -- lane_dw(S) dwords in planes of 16 bytes per
+// lane and one plane of the rest, each a linear sweep of the wave -- into raw[0 .. lane_dw(S))
+template <int S>
+__device__ __forceinline__ void pk_load_lane(const uint32_t *src, int lane, uint32_t (&raw)[pk::kMaxLaneDw])
+{
+    constexpr int N = pk::lane_dw(S), Q = N / 4, R = N % 4;
+#pragma unroll
+    for (int q = 0; q < Q; q++) {
+        const v4u t = __builtin_nontemporal_load((const v4u *)(src + q * 256 + lane * 4));
+        raw[4 * q] = t.x; raw[4 * q + 1] = t.y; raw[4 * q + 2] = t.z; raw[4 * q + 3] = t.w;
+    }
+    const uint32_t *r = src + Q * 256 + lane * R;
+    if constexpr (R == 3) {
+        const v3u_ t = __builtin_nontemporal_load((const v3u_ *)r);
+        raw[4 * Q] = t.x; raw[4 * Q + 1] = t.y; raw[4 * Q + 2] = t.z;
+    } else if constexpr (R == 2) {
+        const v2u_ t = __builtin_nontemporal_load((const v2u_ *)r);
+        raw[4 * Q] = t.x; raw[4 * Q + 1] = t.y;
+    } else if constexpr (R == 1) {
+        raw[4 * Q] = __builtin_nontemporal_load(r);
+    }
+}
+
+// ... and its values, exactly the f32 bits, into the fp32 kernel's registers; steps past the row end are zero there too
+template <int S>
+__device__ __forceinline__ void pk_decode_lane(const uint32_t (&raw)[pk::kMaxLaneDw], int e31, v4f (&wa)[4], v4f (&wb)[4])
+{
+    uint32_t t[8 * S > 0 ? 8 * S : 1];
+    pk::decode_lane_t<S>(raw, t);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        if (k < S) {
+            wa[k] = v4f{__builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k]), e31), __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 1]), e31),
+                        __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 2]), e31), __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 3]), e31)};
+            wb[k] = v4f{__builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 4]), e31), __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 5]), e31),
+                        __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 6]), e31), __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 7]), e31)};
+        } else {
+            wa[k] = v4f{0.f, 0.f, 0.f, 0.f};
+            wb[k] = v4f{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Wide rows (n >= 4096, n/4 a multiple of 64: the 7B shapes): the WHOLE BLOCK works on
+// one pair.  Rows 2p and 2p+1 are adjacent in memory, so a block reads one contiguous
+// 8n-byte run per unit and consecutive blocks read consecutive runs -- the chip sweeps
+// the matrix linearly, like a plain streaming read (DRAM page locality: +10 % over
+// giving every wave its own row pair, measured).  Thread t takes float4 columns
+// t, t+256, ...; per-thread component accumulators, (x+y)+(z+w), wave xor-shuffle,
+// then the 4 wave partials are added in wave order.  Still a function of n only.
+//
+// PK: the same kernel streaming the 29-bit packed copy of the weights (packed_w.h): the pair's chunks
+// are read in the same (unit, batch) order, 116 instead of 128 bytes per lane and batch, and decoded into the same
+// wa[] / wb[] right before the FMAs, so every sum is the fp32 kernel's bit for bit.  The next batch's loads are issued
+// before the current one is decoded (the raw words are double-buffered): the decode never stands between a batch's
+// arrival and the next request.
+// ---------------------------------------------------------------------------
+template <int PRO, int EPI, int XC, bool LL, bool PK = false>
 __global__ __launch_bounds__(kBlock) void matvec_row_kernel(const MatvecArgs a)
 {
     constexpr int U = 4;
@@ -263,7 +383,7 @@ __global__ __launch_bounds__(kBlock) void matvec_row_kernel(const MatvecArgs a)
     }
     int u = blockIdx.x;  // grid <= n_units
     const float *pa, *pb;
-    pair_rows<EPI>(m, u, pa, pb);
+    if constexpr (!PK) pair_rows<EPI>(m, u, pa, pb);
     v4f wa[U], wb[U];
     auto load = [&](int cb) {  // columns cb + tid + 256k; validity is wave-uniform (n4 % 64 == 0)
         const v4f *a4 = (const v4f *)pa + cb + tid, *b4 = (const v4f *)pb + cb + tid;
@@ -284,9 +404,48 @@ __global__ __launch_bounds__(kBlock) void matvec_row_kernel(const MatvecArgs a)
             wb[k] = ldg_nt(b4 + off);
         }
     };
+    // PK: raw words of the batch being decoded and of the next one, and their in-row steps
+    PkRaw raw, nraw;
+    int s_cur = 4, s_nxt = 4;
+    const int e31 = m.pk_e - 31;
+    const uint32_t *pp = nullptr;
+    size_t pdw = 0, last_off = 0;
+    int s_last = 4;
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    auto pk_load = [&](int b_, PkRaw &dst, int &s_out) __attribute__((always_inline)) {
+        if constexpr (PK) {
+            const bool last = b_ + 1 == n_batches;
+            const uint32_t *src = pp + (last ? last_off : (size_t)b_ * (4 * 64 * pk::kMaxLaneDw) + (size_t)wave_u * (64 * pk::kMaxLaneDw));
+            s_out = (XC == 4 || !last) ? 4 : s_last;  // n = 4096: one full batch
+            pk_load_raw(src, lane, XC == 4 ? 4 : s_out, dst);
+        }
+    };
+    auto pk_decode = [&]() __attribute__((always_inline)) {
+        if constexpr (PK) {
+            if constexpr (XC == 4) {
+                pk_decode_lane<4>(raw, e31, wa, wb);
+            } else {
+                switch (s_cur) {  // wave-uniform
+                    case 4: pk_decode_lane<4>(raw, e31, wa, wb); break;
+                    case 3: pk_decode_lane<3>(raw, e31, wa, wb); break;
+                    case 2: pk_decode_lane<2>(raw, e31, wa, wb); break;
+                    case 1: pk_decode_lane<1>(raw, e31, wa, wb); break;
+                    default: pk_decode_lane<0>(raw, e31, wa, wb); break;
+                }
+            }
+        }
+    };
     EpiIn ein = epi_prefetch<EPI>(m, u, tid == 0);
     EpiIn ein_next = ein;
-    load(0);
+    if constexpr (PK) {
+        pdw = pk::pair_dw(n4);
+        last_off = pk::chunk_off(n4, n_batches - 1, wave_u);
+        s_last = pk::steps(n4, n_batches - 1, wave_u);
+        pp = pair_packed(m, u, pdw);
+        pk_load(0, raw, s_cur);
+    } else {
+        load(0);
+    }
     if constexpr (LL)
         xstage_finish_ll<PRO, XC>(poll, a.rms_w, m.n, n4_pad, xl, gr, xs, scratch);
     else
@@ -297,6 +456,19 @@ __global__ __launch_bounds__(kBlock) void matvec_row_kernel(const MatvecArgs a)
     int best_i = 0x7fffffff;
     int b = 0, parity = 0;
     while (true) {
+        if constexpr (PK) {
+            const bool unit_done = (b + 1 == n_batches);
+            const int u_next = unit_done ? u + ustride : u;
+            const int b_next = unit_done ? 0 : b + 1;
+            if (u_next < n_units) {
+                if (unit_done) {
+                    pp = pair_packed(m, u_next, pdw);
+                    ein_next = epi_prefetch<EPI>(m, u_next, tid == 0);
+                }
+                pk_load(b_next, nraw, s_nxt);
+            }
+            pk_decode();
+        }
 #pragma unroll
         for (int k = 0; k < U; k++) {
             const v4f xv = xs4[b * (kBlock * U) + tid + kBlock * k];
@@ -307,7 +479,7 @@ __global__ __launch_bounds__(kBlock) void matvec_row_kernel(const MatvecArgs a)
         const int u_next = unit_done ? u + ustride : u;
         const int b_next = unit_done ? 0 : b + 1;
         const bool more = u_next < n_units;
-        if (more) {
+        if (!PK && more) {
             if (unit_done) {
                 pair_rows<EPI>(m, u_next, pa, pb);
                 ein_next = epi_prefetch<EPI>(m, u_next, tid == 0);
@@ -317,15 +489,15 @@ __global__ __launch_bounds__(kBlock) void matvec_row_kernel(const MatvecArgs a)
         if (unit_done) {
             const float sa = wave_sum(hsum4(acc_a));
             const float sb = wave_sum(hsum4(acc_b));
-            float *pp = part + parity * (2 * kWaves);
+            float *pp_ = part + parity * (2 * kWaves);
             if (lane == 0) {
-                pp[wave] = sa;
-                pp[kWaves + wave] = sb;
+                pp_[wave] = sa;
+                pp_[kWaves + wave] = sb;
             }
             __syncthreads();
             if (tid == 0) {
-                const float ta = ((pp[0] + pp[1]) + pp[2]) + pp[3];
-                const float tb = ((pp[kWaves] + pp[kWaves + 1]) + pp[kWaves + 2]) + pp[kWaves + 3];
+                const float ta = ((pp_[0] + pp_[1]) + pp_[2]) + pp_[3];
+                const float tb = ((pp_[kWaves] + pp_[kWaves + 1]) + pp_[kWaves + 2]) + pp_[kWaves + 3];
                 pair_epilogue<EPI>(m, u, ta, tb, true, ein);
                 if (EPI == EPI_ARGMAX) {
                     const int ra_ = 2 * u, rb_ = ra_ + 1;
@@ -339,6 +511,10 @@ __global__ __launch_bounds__(kBlock) void matvec_row_kernel(const MatvecArgs a)
             acc_b = v4f{0.f, 0.f, 0.f, 0.f};
         }
         if (!more) break;
+        if constexpr (PK) {
+            raw = nraw;
+            s_cur = s_nxt;
+        }
         u = u_next;
         b = b_next;
     }
@@ -398,11 +574,18 @@ MvLaunch mv_pick(int lpr, bool big_x)
     return big_x ? mv_entry<PRO, EPI, 64, 12, LL>() : mv_entry<PRO, EPI, 64, 4, LL>();
 }
 
-template <int PRO, int EPI, bool LL>
+template <int PRO, int EPI, bool LL, bool PK = false>
 const void *mv_row_fn(bool big_x)
 {
-    return big_x ? reinterpret_cast<const void *>(&matvec_row_kernel<PRO, EPI, 12, LL>)
-                 : reinterpret_cast<const void *>(&matvec_row_kernel<PRO, EPI, 4, LL>);
+    return big_x ? reinterpret_cast<const void *>(&matvec_row_kernel<PRO, EPI, 12, LL, PK>)
+                 : reinterpret_cast<const void *>(&matvec_row_kernel<PRO, EPI, 4, LL, PK>);
+}
+
+// packed weights: ffn13 (rmsnorm + W1 | W3 + SwiGLU), the one decode launch they pay off on
+const void *mv_row_pick_packed(int pro, int epi, bool big_x)
+{
+    if (pro == PRO_RMS && epi == EPI_SWIGLU) return mv_row_fn<PRO_RMS, EPI_SWIGLU, false, true>(big_x);
+    return nullptr;
 }
 
 // ll: x is read as LL words from the landing slot (sharded runs).  Only the (prologue, epilogue)
@@ -513,6 +696,10 @@ hipError_t launch_matvec(const MatvecArgs &a_in, int pro, int epi, int max_block
     if (ll && !vec) return hipErrorNotSupported;  // callers ask matvec_ll_supported() first
     MvLaunch k = mv_pick_pe(pro, epi, lpr, a.n > 4096, vec, ll);
     if (use_row) k.fn = mv_row_pick(pro, epi, a.n > 4096, ll);
+    if (a.pk != nullptr) {  // packed weights: the row kernel's packed form or nothing (no quiet f32 fall-back)
+        if (!use_row || ll || !pk::width_ok(a.n)) return hipErrorInvalidValue;
+        k.fn = mv_row_pick_packed(pro, epi, a.n > 4096);
+    }
     if (k.fn == nullptr) return hipErrorInvalidValue;
     size_t lds;
     int n_units;

@@ -19,6 +19,8 @@ struct MvLocals {
     const P2pArgs *push;  // sharded: LL words of the outputs go straight to the peers
     int push_e;
     size_t push_base;     // index of out0[0] in the gathered vector
+    const uint32_t *pk;  // packed W1 | W3 slot (MatvecArgs::pk; packed row kernel only)
+    int pk_e;
 };
 
 template <int EPI>
@@ -38,6 +40,7 @@ __device__ __forceinline__ MvLocals mv_locals(const MatvecArgs &a)
     m.push = a.push;
     m.push_e = m.push ? a.push_ctl[kCtlEpoch] + a.push_gi : 0;
     m.push_base = m.push ? (size_t)m.push->rank * m.push->count : 0;
+    m.pk = a.pk; m.pk_e = a.pk_e;
     return m;
 }
 
@@ -63,6 +66,14 @@ __device__ __forceinline__ void pair_rows(const MvLocals &m, int p, const float 
         pa = wa + (size_t)row_a * (size_t)m.n;
         pb = wb + (size_t)row_b * (size_t)m.n;
     }
+}
+
+// packed form of pair_rows (EPI_SWIGLU: pair p = rows 2p, 2p + 1 of the slot): the pair's 29-bit chunks (pair_dw
+// dwords, packed_w.h)
+__device__ __forceinline__ const uint32_t *pair_packed(const MvLocals &m, int p, size_t pair_dw)
+{
+    if (p >= m.n_pairs) p = m.n_pairs - 1;
+    return m.pk + (size_t)p * pair_dw;
 }
 
 // What the epilogue of pair p reads from memory (residual values, RoPE cos/sin).  Loaded by

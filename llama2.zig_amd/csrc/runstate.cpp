@@ -37,6 +37,7 @@ extern "C" int l2z_runstate_init(const l2z_config *config, const l2z_comm *comm,
     const Tunables &tn = tunables();
     s->max_blocks = tn.max_blocks_per_cu;  // per CU; the launcher also caps at the occupancy query
     s->use_graphs = tn.no_graph == 0;
+    s->packed_w = tn.packed_w != 0;
     // Peer-write gathers are plain kernels (or no launch at all): captured with the rest of the
     // step.  RCCL collectives are captured too (stream capture of ncclAllGather; if the capture
     // fails the step is launched eagerly, ensure_graph).

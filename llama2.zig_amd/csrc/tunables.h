@@ -54,6 +54,9 @@ struct Tunables {
                                //                     unsharded pass's cross-kernel work: planes written by rmsnorm, the attention output, the
                                //                     SwiGLU epilogue -- four launches per layer -- and the ranges' sums of Wo / W2 added by
                                //                     the rmsnorm launch behind them)
+    int packed_w = 1;          // L2Z_PACKED_W        0: no packed weight copy is built and runstates stream the f32 weights in decode (the A/B
+                               //                     switch and the escape hatch of DESIGN.md 4.9; same bits either way).  Read when Weights
+                               //                     objects (build the copy) and RunState objects (take it) are created
     int pf_panel_max = -1;     // L2Z_PF_PANEL_MAX    longest chunk that takes the panel kernel (default and maximum 96 tokens): tests of both sides
                                //                     of the switch-over
 

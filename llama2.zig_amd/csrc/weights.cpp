@@ -11,6 +11,7 @@
 #include <mutex>
 
 #include "l2z_state.h"
+#include "packed_w.h"
 #include "tunables.h"
 
 namespace l2z {
@@ -257,6 +258,59 @@ int weights_alloc(const l2z_config *config, int shared_weights, const l2z_comm *
     return L2Z_OK;
 }
 
+// The packed copy of each layer's W1 | W3 slot (packed_w.h), built on the device from the complete f32
+// blob: a stats pass per slot, one host read of the stats, one allocation, a packing pass per encodable slot.  Unsharded
+// weights of a width the row kernel runs only; everything else (prefill, batched decode, shards, l2z_weights_read)
+// keeps reading the f32 blob.  Best effort: a failed allocation or launch leaves the weights without a packed copy (f32
+// decode), never failing init.
+void build_packed(l2z_weights *w)
+{
+    if (tunables().packed_w == 0 || !w->file_layout) return;
+    const l2z_config &c = w->cfg;
+    const size_t dim = c.dim, hid = c.hidden_dim;
+    const int rows = 2 * c.hidden_dim, cols = c.dim, L = c.n_layers;
+    if (!pk::width_ok(cols)) return;
+    w->pk.assign(L, l2z_weights::PkMat{});
+    w->pk_candidates = L;
+    auto slot = [&](int l) { return w->w1 + (size_t)l * hid * 2 * dim; };
+    std::vector<uint32_t> stats(3 * (size_t)L);
+    for (int l = 0; l < L; l++) {
+        stats[3 * l] = 0;
+        stats[3 * l + 1] = 255;
+        stats[3 * l + 2] = 0;
+    }
+    uint32_t *d_stats = nullptr;
+    hipError_t e = hipMalloc((void **)&d_stats, stats.size() * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemcpy(d_stats, stats.data(), stats.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    for (int l = 0; l < L && e == hipSuccess; l++) e = launch_pk_stats(slot(l), (size_t)rows * cols, d_stats + 3 * l, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(stats.data(), d_stats, stats.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (d_stats) (void)hipFree(d_stats);
+    const size_t per = (size_t)(rows / 2) * pk::pair_dw(cols / 4);
+    size_t total = 0;
+    for (int l = 0; l < L; l++) total += pk::encodable(stats[3 * l], stats[3 * l + 1], stats[3 * l + 2]) ? per : 0;
+    if (e == hipSuccess && total > 0) {
+        e = hipMalloc((void **)&w->pk_blob, total * sizeof(uint32_t));
+        if (e != hipSuccess) w->pk_blob = nullptr;  // no room for the copy: decode streams the f32 weights
+    }
+    size_t off = 0;
+    for (int l = 0; l < L && e == hipSuccess && w->pk_blob; l++) {
+        if (!pk::encodable(stats[3 * l], stats[3 * l + 1], stats[3 * l + 2])) continue;
+        e = launch_pk_pack(slot(l), rows, cols, (int)stats[3 * l], w->pk_blob + off, nullptr);
+        w->pk[l].p = w->pk_blob + off;
+        w->pk[l].e = (int)stats[3 * l];
+        w->pk_packed++;
+        off += per;
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        if (w->pk_blob) (void)hipFree(w->pk_blob);
+        w->pk_blob = nullptr;
+        w->pk.assign(L, l2z_weights::PkMat{});
+        w->pk_packed = 0;
+    }
+}
+
 }  // namespace
 
 extern "C" int l2z_abi_version(void) { return L2Z_ABI_VERSION; }
@@ -348,6 +402,7 @@ extern "C" int l2z_weights_init(const l2z_config *config, const float *data, siz
         l2z_weights_free(w);
         return L2Z_ERR_HIP;
     }
+    build_packed(w);
     *out = w;
     return L2Z_OK;
 }
@@ -387,6 +442,7 @@ extern "C" int l2z_weights_init_synthetic(const l2z_config *config, int shared_w
         l2z_weights_free(w);
         return L2Z_ERR_HIP;
     }
+    build_packed(w);
     *out = w;
     return L2Z_OK;
 }
@@ -432,5 +488,34 @@ extern "C" void l2z_weights_free(l2z_weights *w)
 {
     if (!w) return;
     if (w->blob) (void)hipFree(w->blob);
+    if (w->pk_blob) (void)hipFree(w->pk_blob);
     delete w;
+}
+
+extern "C" int l2z_weights_packed_count(const l2z_weights *w, int *n_packed, int *n_candidates)
+{
+    L2Z_CHECK(w != nullptr && n_packed != nullptr && n_candidates != nullptr, L2Z_ERR_INVALID,
+              "l2z_weights_packed_count: null argument");
+    *n_packed = w->pk_packed;
+    *n_candidates = w->pk_candidates;
+    return L2Z_OK;
+}
+
+extern "C" int l2z_weights_packed_read(const l2z_weights *w, int layer, float *out, size_t n_floats)
+{
+    L2Z_CHECK(w != nullptr && out != nullptr, L2Z_ERR_INVALID, "l2z_weights_packed_read: null argument");
+    L2Z_CHECK(layer >= 0 && (size_t)layer < w->pk.size(), L2Z_ERR_INVALID, "l2z_weights_packed_read: no packed layer %d", layer);
+    const auto &pm = w->pk[layer];
+    L2Z_CHECK(pm.p != nullptr, L2Z_ERR_STATE, "l2z_weights_packed_read: layer %d is not packed", layer);
+    const int rows = 2 * w->cfg.hidden_dim, cols = w->cfg.dim;
+    const size_t count = (size_t)rows * cols;
+    L2Z_CHECK(n_floats >= count, L2Z_ERR_INVALID, "l2z_weights_packed_read: need %zu floats", count);
+    L2Z_HIP(hipSetDevice(w->device));
+    float *d = nullptr;
+    L2Z_HIP(hipMalloc((void **)&d, count * sizeof(float)));
+    hipError_t e = launch_pk_unpack(pm.p, rows, cols, pm.e, d, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(out, d, count * sizeof(float), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    L2Z_HIP(e);
+    return L2Z_OK;
 }
