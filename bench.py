@@ -8,6 +8,7 @@ device.  Weights are already resident in HBM when the timed region starts
 (synthetic llama2.c-v0 checkpoint of the named shape, generated on device).
 
   python bench.py                       # N=1, llama2-7b shape, 255 steps after 1 warm-up
+  python bench.py --full                # the same, and every side measurement below (~30 s more at this shape)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N   # rows/heads sharded over N GPUs (strong scaling)
 
@@ -21,9 +22,15 @@ builds output for output (same arguments, same seeded weights, same inputs):
   DIR/tokens.npy   float64 [K]      the token ids of the K timed steps (what l2z_greedy_run hands back)
   DIR/logits.npy   float32 [vocab]  the logits of the last timed step (l2z_logits_read)
 
-Rank 0 prints ONE JSON line.  It carries `roofline` for the dominant kernel and, at N=1,
-`cpu_baseline`: the C oracle (a port, 1 thread -- the reference is single threaded, main.zig:5 /
-README.md:107) timed on this box's host cores on a bounded sample of the same workload.
+Rank 0 prints ONE JSON line.  A plain run does what its headline needs and nothing more: set-up,
+warm-up, the K timed steps, the dump if asked for, the line.  Everything else the benchmark measures
+runs only with `--full` (`--no-extra` / `--no-cpu-baseline` then leave parts of it out):
+  roofline       the dominant kernel against the HBM peak, per-kind launch times, stream-read / copy probes
+  cpu_baseline   at N=1: the C oracle (a port, 1 thread -- the reference is single threaded, main.zig:5 /
+                 README.md:107) timed on this box's host cores on a bounded sample of the same workload
+  extra          at N=1: in-process repeats, the batched prefill, the other shapes, long context, the
+                 scaling model, CPU baselines by shape
+  leg extras     at N>1: per-leg cross-device latencies, sharded prefill, predicted vs measured
 
 N > 1.  The per-layer all-gathers have three transports and nothing but a real
 multi-GPU node can rank them, so the run times EVERY one of them as its own "leg" -- the same K
@@ -246,6 +253,20 @@ def dump_outputs(d: str, toks, logits) -> None:
     os.makedirs(d, exist_ok=True)
     np.save(os.path.join(d, "tokens.npy"), np.asarray(toks, dtype=np.float64))
     np.save(os.path.join(d, "logits.npy"), np.asarray(logits, dtype=np.float32))
+
+
+# For 1.5-2 s after a 7B-shape run frees its device memory (27 GB of weights, their packed ffn13 copy and the KV cache:
+# ~40 GB), a run whose timed steps fall in that window reads ~2 % low on the MI355X: 232-233 against 237-238 tok/s when
+# the next process starts 0-1 s after the free, no effect from 1.5 s on, nor when that process waits 2 s before its
+# warm-up.  It fits the driver clearing freed memory in the background before handing it out again.  A --full run frees
+# the headline's weights half a minute before it exits; a plain run waits instead, so that back-to-back runs measure
+# what they measured before.
+SETTLE_BYTES_PER_S = 8e9  # well under the rate that window implies (>= 20 GB/s)
+
+
+def settle_freed(nbytes: int) -> None:
+    """Wait until the device has cleared the `nbytes` of weights this process has just freed."""
+    time.sleep(nbytes / SETTLE_BYTES_PER_S)
 
 
 def run_once(B, cfg, shared, seed, steps, warmup, comm=None, sync_ok=None):
@@ -503,6 +524,20 @@ def single_gpu(args) -> None:
     n_tok = len(toks)
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, toks, s.logits())
+    out = {
+        "metric": "tokens/s (argmax, -t 0)", "value": n_tok / dt, "unit": "tokens/s",
+        "n_gpus": 1, "steps": n_tok, "warmup": args.warmup,
+        "ms_per_step": dt / n_tok * 1e3, "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": workload_text(args, cfg), "parallelism": "1 GPU", "ranks_agree": None,
+                   "weight_bytes_per_token": weight_bytes_per_token(cfg)},
+    }
+    if not args.full:
+        s.close()
+        w.close()
+        print(json.dumps(out), flush=True)
+        settle_freed(ck.weights_count(cfg, shared) * 4)
+        return
     n_prof = 4
     pos0 = args.warmup + n_tok
     by_kind = profile_kinds(B, s, w, cfg, pos0, n_prof)
@@ -579,15 +614,7 @@ def single_gpu(args) -> None:
     s.close()
     w.close()
 
-    out = {
-        "metric": "tokens/s (argmax, -t 0)", "value": n_tok / dt, "unit": "tokens/s",
-        "n_gpus": 1, "steps": n_tok, "warmup": args.warmup,
-        "ms_per_step": dt / n_tok * 1e3, "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": workload_text(args, cfg), "parallelism": "1 GPU", "ranks_agree": None,
-                   "weight_bytes_per_token": weight_bytes_per_token(cfg)},
-        "roofline": roofline,
-    }
+    out["roofline"] = roofline
     if not args.no_extra and args.workload != "stories15M":
         c15, sh15 = shapes["stories15M"]
         t15, dt15, s15, w15 = run_once(B, c15, sh15, args.seed, 255, 1)
@@ -815,7 +842,7 @@ def leg_main(args) -> int:
     # hand-over costs between rank 0 and each peer over the IPC-mapped arenas -- the number the leg's tokens/s has to be
     # read against (a rank's token makes `gathers` hand-overs; SURVEY.md 8e: latency, not bandwidth, is the bound).
     cross = None
-    if kind not in RCCL_LEGS and all(x["p2p"] for x in trs):
+    if args.full and kind not in RCCL_LEGS and all(x["p2p"] for x in trs):
         cross = {"ll_word_round_trip_us": {}, "peer_copy_16KB_us": {}, "devices": None,
                  "note": "rank 0 <-> rank p: one 8-byte {value, epoch} word each way per round trip (2000 trips, device "
                          "clock, one polling thread per side: l2z_comm_p2p_pingpong); hipMemcpyAsync of 16 KB into rank "
@@ -865,15 +892,17 @@ def leg_main(args) -> int:
     dt = float(t.item())
 
     n_prof = 4
-    pos0 = args.warmup + n_tok
-    by_kind = profile_kinds(B, s, w, cfg, pos0, n_prof)
-    roofline, rd_avg = roofline_of(B, s, w, cfg, world, by_kind, n_prof, pos0, args.workload, n_tok, dt)
+    by_kind, roofline, rd_avg = None, None, None
+    if args.full:
+        pos0 = args.warmup + n_tok
+        by_kind = profile_kinds(B, s, w, cfg, pos0, n_prof)
+        roofline, rd_avg = roofline_of(B, s, w, cfg, world, by_kind, n_prof, pos0, args.workload, n_tok, dt)
 
     # the row-sharded prefill (every rank its column blocks, [tokens, n / world] blocks exchanged through
     # the arena's bulk regions on the p2p legs, ncclAllGather on the RCCL leg): a diagnostic beside the
     # decode figure
     prefill_sharded = None
-    if not args.no_extra and os.environ.get("L2Z_BENCH_NO_SHARDED_PREFILL", "") != "1":
+    if args.full and not args.no_extra and os.environ.get("L2Z_BENCH_NO_SHARDED_PREFILL", "") != "1":
         err = None
         dtp = 0.0
         n_p = min(512, cfg.seq_len - 1)
@@ -903,12 +932,14 @@ def leg_main(args) -> int:
             prefill_sharded = {"error": str(err) if err else "failed on another rank"}
     s.close()
     w.close()
+    if not args.full:  # the next leg's timed steps must not fall in the clearing of this one's weights
+        settle_freed(ck.weights_count(cfg, shared) * 4 // world)
 
     # Predicted vs measured, in the same process: rank 0 alone re-runs ITS OWN whole sharded pass with free hand-overs
     # (extra.scaling_model.solo_rank's bed: the peers' arenas a local sink, no wait ever blocks) for this leg's structure;
     # measured / predicted < 1 is what the hand-overs (latency above, rank skew, xGMI) cost on this box.
     predicted = None
-    if not args.no_extra and world > 1 and os.environ.get("L2Z_BENCH_NO_SOLO", "") != "1":
+    if args.full and not args.no_extra and world > 1 and os.environ.get("L2Z_BENCH_NO_SOLO", "") != "1":
         solo_leg = kind if kind in dict(SOLO_FORMS) else ("p2p-allreduce" if scheme_b else "p2p-gather")
         if rank == 0:
             try:
@@ -927,7 +958,7 @@ def leg_main(args) -> int:
         dist.barrier()
 
     n_g = (2 if scheme_b else 4) * cfg.n_layers + 1
-    launches = by_kind["gather"][1] // n_prof
+    launches = by_kind["gather"][1] // n_prof if by_kind else None
     bytes_tok = weight_bytes_per_token(cfg, world)
     ideal_ms = bytes_tok / (rd_avg * 1e9) * 1e3 if rd_avg else None
     rccl_lib = None
@@ -942,7 +973,7 @@ def leg_main(args) -> int:
            "gathers": n_g, "collectives": (f"{n_g - 1} all-reduces of [dim] + the logits all-gather" if scheme_b else
                                            f"{n_g} all-gathers"), "gather_launches_per_token": launches,
            "us_per_gather": (by_kind["gather"][0] / max(by_kind["gather"][1], 1) * 1e3) if launches else None,
-           "graph_nodes_per_layer": 5 + ((launches - 1) // cfg.n_layers if launches > 1 else 0),
+           "graph_nodes_per_layer": (5 + ((launches - 1) // cfg.n_layers if launches > 1 else 0)) if launches is not None else None,
            "rccl_ranks": [x["rccl_ranks"] for x in trs], "p2p_connected": [x["p2p"] for x in trs],
            # this rank's weight bytes at the plain streaming-read rate measured on this box: roughly what a
            # step would take with free gathers; the rest of ms_per_step is gather + launch overhead
@@ -964,7 +995,7 @@ def leg_main(args) -> int:
                                    f"rows/heads sharded x{args.gpus}, all-gathers by {LEG_TEXT[kind]}"),
                    "ranks_agree": bool(agree),
                    "weight_bytes_per_token": bytes_tok * world},
-        "roofline": roofline,
+        **({"roofline": roofline} if args.full else {}),
         "leg": leg,
     }
     if rank == 0:
@@ -1020,6 +1051,8 @@ def multi_main(args) -> None:
         cmd = [sys.executable, os.path.abspath(__file__), "--leg", kind, "--leg-port", str(port[0]),
                "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup),
                "--workload", args.workload, "--seed", str(args.seed)]
+        if args.full:
+            cmd.append("--full")
         if args.no_extra:
             cmd.append("--no-extra")
         if args.dump_outputs:
@@ -1122,8 +1155,10 @@ def main() -> None:
     ap.add_argument("--workload", default="llama2-7b",
                     choices=["llama2-7b", "stories110M", "stories42M", "stories15M"])
     ap.add_argument("--seed", type=int, default=2024)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement: roofline, CPU baselines, extra shapes and figures, leg diagnostics")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: leave out `extra` and the legs' sharded prefill and prediction")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the timed path's outputs after its last step to DIR/<name>.npy")
     ap.add_argument("--leg", default=None, choices=LEGS, help=argparse.SUPPRESS)  # child of an N > 1 run

@@ -3,8 +3,8 @@
 # after the test suite reads ~3 % low: the chip's state), the gpu-marked suite last.
 cd "$GRAFT_REPO_ROOT"; O=gpurun_out; mkdir -p $O
 export TMPDIR=/tmp
-python bench.py > $O/r05_final_bench.json 2> $O/r05_final_bench.err; tail -c 300 $O/r05_final_bench.err
-python bench.py --steps 20 --warmup 5 > $O/r05_final_bench_driver_args.json 2>> $O/r05_final_bench.err
+python bench.py --full > $O/r05_final_bench.json 2> $O/r05_final_bench.err; tail -c 300 $O/r05_final_bench.err
+python bench.py --steps 20 --warmup 5 --full > $O/r05_final_bench_driver_args.json 2>> $O/r05_final_bench.err
 python - <<'PY'
 import json
 for f in ("r05_final_bench.json", "r05_final_bench_driver_args.json"):
@@ -33,7 +33,7 @@ bash scripts/pmc_traffic.sh r05 > $O/r05_final_pmc.log 2>&1; tail -9 $O/r05_fina
 timeout 600 python -u scripts/solo_rank.py llama2-7b 128 > $O/r05_solo_rank.md 2>&1; cat $O/r05_solo_rank.md
 # four ranks on this one GPU, all five legs (a proxy for the control path and for the structures' ranking)
 L2Z_BENCH_LEG_TIMEOUT_S=240 timeout 1100 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 \
-  --master-port 29533 bench.py --gpus 4 --steps 64 --warmup 1 > $O/r05_bench_4ranks_1gpu.json 2> $O/r05_bench_4ranks_1gpu.err
+  --master-port 29533 bench.py --gpus 4 --steps 64 --warmup 1 --full > $O/r05_bench_4ranks_1gpu.json 2> $O/r05_bench_4ranks_1gpu.err
 echo "4-rank bench rc=$?"
 python - <<'PY'
 import json

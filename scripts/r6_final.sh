@@ -3,8 +3,8 @@
 # after the test suite reads ~3 % low: the chip's state), fuzz sweeps and the gpu-marked suite last.
 cd "$GRAFT_REPO_ROOT"; O=gpurun_out; mkdir -p $O
 export TMPDIR=/tmp
-python bench.py > $O/r06_final_bench.json 2> $O/r06_final_bench.err; tail -c 300 $O/r06_final_bench.err
-python bench.py --steps 20 --warmup 5 > $O/r06_final_bench_driver_args.json 2>> $O/r06_final_bench.err
+python bench.py --full > $O/r06_final_bench.json 2> $O/r06_final_bench.err; tail -c 300 $O/r06_final_bench.err
+python bench.py --steps 20 --warmup 5 --full > $O/r06_final_bench_driver_args.json 2>> $O/r06_final_bench.err
 python - <<'PY'
 import json
 for f in ("r06_final_bench.json", "r06_final_bench_driver_args.json"):
@@ -49,7 +49,7 @@ timeout 600 python -u scripts/solo_rank.py llama2-7b 128 > $O/r06_solo_rank.md 2
 # two and four ranks on this one GPU, all five legs (a proxy for the control path, the structures' ranking, and the new per-leg diagnostics)
 for n in 2 4; do
   L2Z_BENCH_LEG_TIMEOUT_S=300 timeout 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 \
-    --master-port 2953$n bench.py --gpus $n --steps 64 --warmup 1 > $O/r06_bench_${n}ranks_1gpu.json 2> $O/r06_bench_${n}ranks_1gpu.err
+    --master-port 2953$n bench.py --gpus $n --steps 64 --warmup 1 --full > $O/r06_bench_${n}ranks_1gpu.json 2> $O/r06_bench_${n}ranks_1gpu.err
   echo "$n-rank bench rc=$?"
 done
 python - <<'PY'

@@ -1,6 +1,6 @@
-"""bench.py's contract at N = 1 on the GPU box: ONE JSON line with the fields the driver reads, the
-`roofline` and `cpu_baseline` objects, and round 3's hygiene fields -- on a small workload so that it runs in
-seconds (the headline 7B run is the driver's own)."""
+"""bench.py's contract at N = 1 on the GPU box: ONE JSON line with the fields the driver reads; with --full also the
+`roofline` and `cpu_baseline` objects and round 3's hygiene fields, without it nothing but the headline -- on a small
+workload so that it runs in seconds (the headline 7B run is the driver's own)."""
 import json
 import os
 import subprocess
@@ -13,15 +13,34 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_bench_line_has_the_contract_fields(gpu):
+HEADLINE_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                 "vs_baseline", "dtype", "data", "config"}
+
+
+def test_plain_bench_line_is_the_headline_alone(gpu):
+    """Without --full the run sets up, warms up, times its steps and prints the headline: no roofline, no CPU baseline,
+    no side measurements."""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "stories110M", "--steps", "64",
-                        "--warmup", "1"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                        "--warmup", "1"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
     assert len(lines) == 1
     out = json.loads(lines[0])
-    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
-              "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
+    assert set(out) == HEADLINE_KEYS, sorted(out)
+    assert out["metric"] == "tokens/s (argmax, -t 0)" and out["unit"] == "tokens/s" and out["higher_is_better"] is True
+    assert out["n_gpus"] == 1 and out["steps"] == 64 and out["warmup"] == 1 and out["dtype"] == "f32"
+    assert out["value"] > 0 and abs(out["value"] - 1e3 / out["ms_per_step"]) < 1e-6 * out["value"]
+    assert "stories110M" in out["config"]["workload"]
+
+
+def test_bench_line_has_the_contract_fields(gpu):
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "stories110M", "--steps", "64",
+                        "--warmup", "1", "--full"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    for k in sorted(HEADLINE_KEYS) + ["roofline", "cpu_baseline"]:
         assert k in out, k
     assert out["n_gpus"] == 1 and out["steps"] == 64 and out["warmup"] == 1 and out["higher_is_better"] is True
     assert out["unit"] == "tokens/s" and out["dtype"] == "f32" and out["data"] == "synthetic" and out["vs_baseline"] is None

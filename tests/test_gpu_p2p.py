@@ -282,7 +282,7 @@ def test_bench_legs_on_one_gpu(gpu, tmp_path):
     env = dict(os.environ, L2Z_BENCH_LEG_TIMEOUT_S="200", L2Z_P2P_TIMEOUT_S="20", L2Z_BENCH_NO_SHARDED_PREFILL="1")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                        "--gpus", "2", "--steps", "48", "--warmup", "1", "--workload", "stories110M",
+                        "--gpus", "2", "--steps", "48", "--warmup", "1", "--workload", "stories110M", "--full",
                         "--dump-outputs", str(tmp_path / "dump")],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
