@@ -98,6 +98,19 @@ pub extern fn l2z_prefill(
     s: *L2zRunState,
     w: *const L2zWeights,
 ) c_int;
+/// l2z_prefill's state change plus, per position, the log-prob of targets[i] (-1: none -> 0) and the top-1 token id (no
+/// reference equivalent).  out_logprob is null iff targets is; out_top1 may be null; not both.
+pub extern fn l2z_score(
+    tokens: [*]const i32,
+    n_tokens: c_int,
+    pos0: c_int,
+    targets: ?[*]const i32,
+    config: *const L2zConfig,
+    s: *L2zRunState,
+    w: *const L2zWeights,
+    out_logprob: ?[*]f32,
+    out_top1: ?[*]i32,
+) c_int;
 pub extern fn l2z_synchronize(s: *L2zRunState) c_int;
 /// Batched decode (no reference equivalent): up to batch_max sequences, one runstate each, one token each, one sweep
 /// of the weights -- the state change of l2z_transformer(tokens[i], pos[i], config, states[i], w) for every i.

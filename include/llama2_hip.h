@@ -19,6 +19,7 @@
  *   state.logits after return    :1005-1012  l2z_logits_read       (D2H, for samplers)
  *   logits / temperature, softmax :1005-1008  l2z_probs_read        (on the device, then D2H)
  *   while (pos < seq_len) loop at -t 0 :995  l2z_greedy_begin / l2z_greedy_run
+ *   (no reference equivalent)                l2z_score             (log-prob and top-1 of every position of a text)
  *   matmul, rmsnorm, softmax, ... :432-726   kernel-level hooks of the same names, for tests only:
  *                                            include/llama2_hip_test.h
  *
@@ -151,6 +152,31 @@ int l2z_greedy_run(const l2z_config *config, l2z_runstate *s, const l2z_weights 
 #define L2Z_PREFILL_MIN_PROMPT 4
 int l2z_prefill(const int32_t *tokens, int n_tokens, int pos0, const l2z_config *config,
                 l2z_runstate *s, const l2z_weights *w);
+
+/* ---- scoring a token sequence (no reference equivalent: the reference only generates) ----
+ * STATE CHANGE: exactly l2z_prefill(tokens, n_tokens, pos0, ...) -- the KV-cache rows pos0 .. pos0+n_tokens-1 of every
+ * layer and the runstate's logits (last position) are bit-identical to what l2z_prefill leaves (same chunks, same
+ * launches per layer), so a caller scores a prompt and goes on generating from it, forks it or batches it.
+ * OUTPUTS, for i = 0 .. n_tokens-1, with z_i the f32 logits of position pos0+i (final rmsnorm of the residual row, times
+ * the classifier matrix -- the embedding when the checkpoint shares them -- by the prefill pass's GEMM kernels):
+ *   out_logprob[i] = z_i[targets[i]] - (m_i + log sum_v exp(z_i[v] - m_i)),  m_i = max_v z_i[v], all in f32; the sums
+ *                    run in a fixed order that depends on vocab_size only (same bits run to run, whatever the workspace).
+ *                    targets[i] == -1: no target at this position, out_logprob[i] = 0.  The usual call passes
+ *                    targets[i] = tokens[i+1] and -1 for the last.
+ *   out_top1[i]    = argmax_v z_i[v], strict '>', lowest index wins (l2z_argmax's rule).
+ * out_logprob may be NULL iff targets is NULL; out_top1 may be NULL; not both absent.  Synchronous (the outputs are host
+ * arrays).  The logits never exist as a [n_tokens, vocab] matrix: the classifier product is written one slab of
+ * vocabulary rows at a time into a workspace of at most 64 MB (32 MB + the per-row partials at the default chunking),
+ * allocated on the runstate's first l2z_score call and freed with it.
+ * Contract (a refusal enqueues nothing and changes no state): L2Z_ERR_INVALID for NULL tokens, n_tokens < 1, both outputs
+ * absent, targets without out_logprob or the reverse, a sharded runstate (comm != NULL), dims l2z_prefill refuses;
+ * L2Z_ERR_STATE for positions outside [0, seq_len), a token outside the vocabulary, a target outside {-1} u [0, vocab_size).
+ * OUT OF SCOPE: sharded runstates (the vocabulary rows are sharded there: it would take an exchange of one (max, sum,
+ * argmax, target logit) tuple per rank and row), and a batch of sequences per call -- callers loop; N continuations of one
+ * prompt: score the prompt once, l2z_runstate_fork, score each continuation with pos0 = n_prompt. */
+int l2z_score(const int32_t *tokens, int n_tokens, int pos0, const int32_t *targets,
+              const l2z_config *config, l2z_runstate *s, const l2z_weights *w,
+              float *out_logprob, int32_t *out_top1);
 
 /* wait for everything queued on the runstate's stream */
 int l2z_synchronize(l2z_runstate *s);

@@ -194,6 +194,10 @@ int l2z_logits_write(l2z_runstate *s, const float *logits);
  * back, timed by device events on states[0]'s stream; *out_ms = milliseconds per launch. */
 int l2z_sample_time(int n, l2z_runstate *const *states, const float *temperature, const float *top_p,
                     const float *coins, int iters, double *out_ms);
+/* l2z_score's classifier product on this runstate goes out in slabs of `slab_cols` vocabulary rows: a positive multiple
+ * of 4096 (the reduction's segment; else L2Z_ERR_INVALID), or 0 for the default (by the workspace budget).  Applies from
+ * the next l2z_score call.  The outputs do not depend on it, bit for bit: that is what the tests use it for. */
+int l2z_score_slab_set(l2z_runstate *s, int slab_cols);
 
 #ifdef __cplusplus
 }

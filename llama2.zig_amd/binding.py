@@ -87,6 +87,9 @@ def lib():
     L.l2z_probs_read.argtypes = [vp, C.c_float, fp]
     L.l2z_runstate_read.argtypes = [vp, C.c_char_p, sz, sz, fp]
     L.l2z_prefill.argtypes = [i32p, C.c_int, C.c_int, cfgp, vp, vp]
+    if hasattr(L, "l2z_score"):  # (an older build loaded through L2Z_LIB lacks it)
+        L.l2z_score.argtypes = [i32p, C.c_int, C.c_int, i32p, cfgp, vp, vp, fp, i32p]
+        L.l2z_score_slab_set.argtypes = [vp, C.c_int]
     L.l2z_transformer_batch.argtypes = [C.c_int, i32p, i32p, cfgp, C.POINTER(vp), vp]
     L.l2z_argmax_batch.argtypes = [C.c_int, C.POINTER(vp), i32p]
     L.l2z_batch_time.argtypes = [C.c_int, i32p, i32p, cfgp, C.POINTER(vp), vp, C.c_int, C.POINTER(C.c_double)]
@@ -306,6 +309,26 @@ class RunState:
         t = np.ascontiguousarray(tokens, np.int32)
         _chk(lib().l2z_prefill(t.ctypes.data_as(C.POINTER(C.c_int32)), t.size, pos0,
                                C.byref(self.cfg), self.h, w.h))
+
+    def score(self, tokens, pos0: int, w: Weights, targets=None, top1: bool = True):
+        """l2z_score: prefill(tokens, pos0) plus, per position, (log-prob of its target, top-1 token id) as two arrays.
+        targets=None: the next token of each position, none (-1, log-prob 0) for the last; top1=False: no top-1 (None)."""
+        t = np.ascontiguousarray(tokens, np.int32)
+        if targets is None:
+            tg = np.append(t[1:], np.int32(-1)).astype(np.int32)
+        else:
+            tg = np.ascontiguousarray(targets, np.int32)
+            assert tg.size == t.size
+        lp = np.zeros(t.size, np.float32)
+        tp = np.zeros(t.size, np.int32) if top1 else None
+        i32p = C.POINTER(C.c_int32)
+        _chk(lib().l2z_score(t.ctypes.data_as(i32p), t.size, pos0, tg.ctypes.data_as(i32p), C.byref(self.cfg), self.h, w.h,
+                             _fp(lp), tp.ctypes.data_as(i32p) if top1 else None))
+        return lp, tp
+
+    def score_slab_set(self, slab_cols: int) -> None:
+        """l2z_score_slab_set (test hook): vocabulary rows per slab of score()'s classifier product, 0: the default."""
+        _chk(lib().l2z_score_slab_set(self.h, slab_cols))
 
     def argmax(self) -> int:
         t = C.c_int(0)

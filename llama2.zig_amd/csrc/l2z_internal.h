@@ -341,6 +341,21 @@ int prefill_next_chunk_of(const l2z_config &c, int remaining);
 // asked prefill_panel_shape first treat that as an error on a shard (the unsharded pass would have taken it)
 hipError_t launch_prefill_panel(const PanelProduct &p, int n_cus, const SplitKWs *ws, hipStream_t st);
 int prefill_tile_form(int N, int P, int pair);  // 0: 128x64, 1: 64x64, 2: 32x64, 3: 32x32, 4: 128x128
+// ---- score.hip: l2z_score's reductions over the classifier logits of a chunk, one vocabulary slab at a time ----
+constexpr int kScoreSeg = 4096;   // columns per segment of the reduction: slabs are whole segments, so the sums never depend on the slab
+struct ScoreArgs {
+    const float *slab;    // [P, ld] logits of vocabulary columns col0 .. col0 + n - 1 (ld: a multiple of kScoreSeg, >= n)
+    int ld, n, col0, P;
+    const int *targets;   // [P] target token of each row, -1: none; null: no log-probs asked for
+    float *part_m, *part_s;   // [P, nseg] per segment: max, sum of exp(z - max) ...
+    int *part_i;              // ... and the first index of the max (vocabulary index)
+    float *tgt;           // [P] the target's logit
+    int seg0, nseg;       // first segment of this slab (col0 / kScoreSeg), segments of the whole vocabulary
+    float *out_logprob;   // finish: [P] (null: not asked for)
+    int *out_top1;        // finish: [P] (null: not asked for)
+};
+hipError_t launch_score_reduce(const ScoreArgs &a, hipStream_t st);   // a slab's segments -> part_*, tgt
+hipError_t launch_score_finish(const ScoreArgs &a, hipStream_t st);   // the segments in order -> out_logprob, out_top1
 size_t matvec_lds_bytes(int n);
 
 }  // namespace l2z

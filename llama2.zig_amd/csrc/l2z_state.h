@@ -111,6 +111,13 @@ struct l2z_runstate {
     int pf_planes_att = 0, pf_planes_h1 = 0;   // PLANES_*: whether the attention output's / the gated rows' planes stand (prefill_host.cpp)
     l2z::SplitKWs pf_sk = {nullptr, nullptr, 0, 0, nullptr, 0, nullptr, 0};  // split-K workspace of the tile GEMM (chunks of <= 256 tokens)
     int pf_cap = 0;             // tokens per chunk the scratch above was allocated for
+    // l2z_score (prefill_host.cpp; allocated on the first call, a runstate that never scores holds none of it):
+    // sc_ws: one allocation per chunk capacity -- the [sc_cap, sc_slab_n] logits slab, the segments' partials, the targets' logits;
+    // sc_seq: targets, log-probs and top-1 ids of a whole call (seq_len each), copied to the host once per call
+    void *sc_ws = nullptr, *sc_seq = nullptr;
+    size_t sc_ws_bytes = 0;
+    int sc_cap = 0, sc_slab_n = 0;   // tokens per chunk / vocabulary columns per slab sc_ws was allocated for
+    int sc_slab_force = 0;           // l2z_score_slab_set (tests): columns per slab, 0: by the workspace budget
     float *d_probs = nullptr;     // l2z_probs_read: softmax(logits / temperature), allocated on first use
     float *h_stage = nullptr;     // ... and its pinned host landing buffer
     float *d_part_val = nullptr;  // classifier launch's per-block argmax candidates
@@ -172,7 +179,9 @@ bool prefill_enabled();
 bool prefill_usable(const l2z_runstate *s);
 bool prefill_shard_takes_the_unsharded_kernels(const l2z_config &c, const Shard &sh);
 int prefill_check(const l2z_config *config, const l2z_runstate *s);
-int prefill_tokens(l2z_runstate *s, const l2z_weights *w, const int32_t *tokens, int n_tokens, int pos0);
+struct ScoreCall;  // prefill_host.cpp: what an l2z_score call adds to every chunk of the pass (null: plain prefill)
+int prefill_tokens(l2z_runstate *s, const l2z_weights *w, const int32_t *tokens, int n_tokens, int pos0,
+                   const ScoreCall *score = nullptr);
 
 // batch_host.cpp
 void batch_free(l2z_runstate *s);

@@ -413,6 +413,101 @@ int prefill_classifier(l2z_runstate *s, const l2z_weights *w)
 }  // namespace
 
 namespace l2z {
+// device arrays of one l2z_score call, element 0 = the call's first token (null: not asked for)
+struct ScoreCall {
+    const int *d_targets;
+    float *d_logprob;
+    int *d_top1;
+};
+}  // namespace l2z
+
+namespace {
+// ---------------------------------------------------------------------------
+// l2z_score: what the batched pass adds per chunk (kernels: score.hip).  The layer loop above is untouched: after the last
+// layer the chunk's residual rows stand in pf_x (W2 of the last layer finishes itself), so
+//   1. final rmsnorm of all P rows into pf_xn (the layers are done with it),
+//   2. [P, dim] x [vocab, dim]^T by launch_prefill_gemm(PG_STORE), one SLAB of vocabulary rows at a time into sc_ws -- with the
+//      whole matrix's row count as n_launch_whole and prefill_split_k of the whole product, so a slab's cores, kernel family
+//      and K ranges are the whole product's (the tile choice inside a family never changes a bit: prefill_gemm.hip) --
+//   3. a row reduce over the slab's segments, and after the last slab the fold of all segments into log-prob / top-1.
+// The reduction's segments are a function of vocab_size alone (score.hip), so neither the slab width nor the chunk capacity
+// the workspace was sized for can change a bit of the outputs.
+constexpr size_t kScoreSlabBytes = (size_t)32 << 20;   // the slab: read back out of the on-die caches by the reduce
+constexpr size_t kScoreWsMaxBytes = (size_t)64 << 20;  // everything a runstate allocates for scoring per chunk capacity
+
+int score_nseg(const l2z_config &c) { return (c.vocab_size + kScoreSeg - 1) / kScoreSeg; }
+
+int score_alloc(l2z_runstate *s, int need)
+{
+    const l2z_config &c = s->cfg;
+    const size_t nseg = (size_t)score_nseg(c);
+    const size_t cap = std::max((size_t)s->sc_cap, (size_t)(need + 511) / 512 * 512);
+    size_t cols = s->sc_slab_force > 0 ? (size_t)s->sc_slab_force : kScoreSlabBytes / 4 / cap / kScoreSeg * kScoreSeg;
+    cols = std::min(std::max(cols, (size_t)kScoreSeg), nseg * kScoreSeg);
+    if (s->sc_slab_force == 0) {   // slabs of equal width (the last one may be short by less than a segment's worth more)
+        const size_t n_slabs = (nseg * kScoreSeg + cols - 1) / cols;
+        cols = (nseg + n_slabs - 1) / n_slabs * kScoreSeg;
+    }
+    if (s->sc_seq == nullptr) {
+        L2Z_HIP(hipMalloc(&s->sc_seq, (size_t)c.seq_len * 3 * 4));
+    }
+    if (s->sc_ws != nullptr && cap == (size_t)s->sc_cap && cols == (size_t)s->sc_slab_n) return L2Z_OK;
+    const size_t bytes = cap * cols * 4 + cap * nseg * 12 + cap * 4;
+    L2Z_CHECK(bytes <= kScoreWsMaxBytes, L2Z_ERR_INVALID,
+              "l2z_score: chunks of %zu tokens need a %zu-byte workspace (limit %zu): lower L2Z_PF_CHUNK", cap, bytes, kScoreWsMaxBytes);
+    L2Z_HIP(hipStreamSynchronize(s->stream));
+    if (s->sc_ws) { (void)hipFree(s->sc_ws); s->sc_ws = nullptr; s->sc_cap = 0; s->sc_slab_n = 0; s->sc_ws_bytes = 0; }
+    hipError_t e = hipMalloc(&s->sc_ws, bytes);
+    if (e != hipSuccess) {
+        s->sc_ws = nullptr;
+        set_error("score workspace allocation (%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
+    }
+    s->sc_cap = (int)cap; s->sc_slab_n = (int)cols; s->sc_ws_bytes = bytes;
+    return L2Z_OK;
+}
+
+int score_chunk(l2z_runstate *s, const l2z_weights *w, const ScoreCall *sc, int done, int P)
+{
+    const l2z_config &c = s->cfg;
+    hipStream_t st = s->stream;
+    const int dim = c.dim, V = c.vocab_size, ldxn = s->pf_ld_xn, nseg = score_nseg(c);
+    L2Z_CHECK(s->sc_ws != nullptr && P <= s->sc_cap, L2Z_ERR_INVALID, "l2z_score: no workspace for a chunk of %d tokens", P);
+    L2Z_CHECK(!s->pf_pending.valid, L2Z_ERR_INVALID, "l2z_score: the last layer left its residual product's sums behind");
+    L2Z_HIP(launch_prefill_rmsnorm(s->pf_xn, ldxn, s->pf_x, w->rms_final, dim, P, st));   // :426, all rows
+    const int kp = (dim + 63) / 64 * 64;
+    const int sk = prefill_split_k(V, P, kp, false);
+    // chunks the split forms take: a slab's K ranges' sums must fit the split-K workspace (sized for the layers' launches)
+    int cols = s->sc_slab_n;
+    if (P <= kSplitKMaxTokens) {
+        const size_t ranges = (size_t)std::max(sk, x3_stream_shape(V, P, kp) ? x3_stream_sk(V, P, kp) : 1);
+        const size_t rows = (size_t)(P + 127) / 128 * 128;
+        while (cols > kScoreSeg && ((size_t)cols + 256) * ranges * rows > s->pf_sk.part_floats) cols -= kScoreSeg;
+    }
+    float *slab = (float *)s->sc_ws;
+    ScoreArgs a = {};
+    a.slab = slab; a.ld = s->sc_slab_n; a.P = P; a.nseg = nseg;
+    a.part_m = slab + (size_t)s->sc_cap * s->sc_slab_n;
+    a.part_s = a.part_m + (size_t)s->sc_cap * nseg;
+    a.part_i = (int *)(a.part_s + (size_t)s->sc_cap * nseg);
+    a.tgt = (float *)(a.part_i + (size_t)s->sc_cap * nseg);
+    a.targets = sc->d_targets ? sc->d_targets + done : nullptr;
+    for (int col0 = 0; col0 < V; col0 += cols) {
+        const int n = std::min(cols, V - col0);
+        // (the first slab's launch cuts the rows into their planes of bf16 terms where the product runs on those cores; they stand for the rest)
+        L2Z_HIP(launch_prefill_gemm(PG_STORE, s->pf_xn, ldxn, w->wcls + (size_t)col0 * dim, slab, a.ld, P, n, dim, 0, s->rope,
+                                    s->sh.hs, st, nullptr, 0, 1, 0, sk, &s->pf_sk, 0, V, col0 == 0 ? PLANES_SPLIT : PLANES_READY));
+        a.n = n; a.col0 = col0; a.seg0 = col0 / kScoreSeg;
+        L2Z_HIP(launch_score_reduce(a, st));
+    }
+    a.out_logprob = sc->d_logprob ? sc->d_logprob + done : nullptr;
+    a.out_top1 = sc->d_top1 ? sc->d_top1 + done : nullptr;
+    L2Z_HIP(launch_score_finish(a, st));
+    return L2Z_OK;
+}
+}  // namespace
+
+namespace l2z {
 
 // Row-sharded == unsharded bit for bit needs every rank to take the kernel -- the summation order -- the unsharded
 // pass takes.  The one kernel with a per-rank shape condition is the K-range panel kernel (a wave's 16 rows lie in one
@@ -507,7 +602,7 @@ int prefill_next_chunk_of(const l2z_config &c, int remaining)
 
 // positions pos0 .. pos0+n-1 in chunks; leaves the last position's residual row in RunState.x
 int prefill_tokens(l2z_runstate *s, const l2z_weights *w, const int32_t *tokens, int n_tokens,
-                          int pos0)
+                          int pos0, const ScoreCall *score)
 {
     const l2z_config *config = &s->cfg;
     int done = 0;
@@ -515,6 +610,7 @@ int prefill_tokens(l2z_runstate *s, const l2z_weights *w, const int32_t *tokens,
         const int P = prefill_next_chunk_of(*config, n_tokens - done);
         L2Z_TRY(prefill_alloc(s, P));
         L2Z_TRY(prefill_chunk(s, w, tokens + done, P, pos0 + done));
+        if (score) L2Z_TRY(score_chunk(s, w, score, done, P));   // l2z_score: every row's logits, reduced (reads pf_x, writes scratch only)
         if (done + P == n_tokens)
             L2Z_HIP(hipMemcpyAsync(s->x, s->pf_x + (size_t)(P - 1) * config->dim, (size_t)config->dim * 4,
                                    hipMemcpyDeviceToDevice, s->stream));
@@ -527,19 +623,11 @@ int prefill_tokens(l2z_runstate *s, const l2z_weights *w, const int32_t *tokens,
 
 }  // namespace l2z
 
-extern "C" int l2z_prefill(const int32_t *tokens, int n_tokens, int pos0, const l2z_config *config,
-                           l2z_runstate *s, const l2z_weights *w)
+// the pass behind l2z_prefill and l2z_score, arguments checked: the chunks, then the last position's logits
+static int prefill_pass(const int32_t *tokens, int n_tokens, int pos0, const l2z_config *config, l2z_runstate *s,
+                        const l2z_weights *w, const ScoreCall *score)
 {
-    L2Z_TRY(check_pair(config, s, w));
-    L2Z_CHECK(tokens != nullptr && n_tokens >= 1, L2Z_ERR_INVALID, "l2z_prefill: no tokens");
-    L2Z_CHECK(pos0 >= 0 && pos0 + n_tokens <= config->seq_len, L2Z_ERR_STATE,
-              "l2z_prefill: positions %d..%d outside [0,%d)", pos0, pos0 + n_tokens - 1, config->seq_len);
-    for (int i = 0; i < n_tokens; i++)
-        L2Z_CHECK(tokens[i] >= 0 && tokens[i] < config->vocab_size, L2Z_ERR_STATE,
-                  "l2z_prefill: tokens[%d] = %d out of vocabulary", i, tokens[i]);
-    L2Z_TRY(prefill_check(config, s));
-    L2Z_HIP(hipSetDevice(s->device));
-    L2Z_TRY(prefill_tokens(s, w, tokens, n_tokens, pos0));
+    L2Z_TRY(prefill_tokens(s, w, tokens, n_tokens, pos0, score));
     // the last position's residual row is RunState.x: the usual final rmsnorm + classifier
     // launch (:426-429) leaves the logits in place
     const int last_pos = pos0 + n_tokens - 1;
@@ -554,6 +642,72 @@ extern "C" int l2z_prefill(const int32_t *tokens, int n_tokens, int pos0, const 
     L2Z_HIP(hipStreamSynchronize(s->stream));
     L2Z_TRY(comm_check(s->comm));
     s->host_pos = pos0 + n_tokens;
+    return L2Z_OK;
+}
+
+extern "C" int l2z_prefill(const int32_t *tokens, int n_tokens, int pos0, const l2z_config *config,
+                           l2z_runstate *s, const l2z_weights *w)
+{
+    L2Z_TRY(check_pair(config, s, w));
+    L2Z_CHECK(tokens != nullptr && n_tokens >= 1, L2Z_ERR_INVALID, "l2z_prefill: no tokens");
+    L2Z_CHECK(pos0 >= 0 && pos0 + n_tokens <= config->seq_len, L2Z_ERR_STATE,
+              "l2z_prefill: positions %d..%d outside [0,%d)", pos0, pos0 + n_tokens - 1, config->seq_len);
+    for (int i = 0; i < n_tokens; i++)
+        L2Z_CHECK(tokens[i] >= 0 && tokens[i] < config->vocab_size, L2Z_ERR_STATE,
+                  "l2z_prefill: tokens[%d] = %d out of vocabulary", i, tokens[i]);
+    L2Z_TRY(prefill_check(config, s));
+    L2Z_HIP(hipSetDevice(s->device));
+    return prefill_pass(tokens, n_tokens, pos0, config, s, w, nullptr);
+}
+
+// l2z_prefill's state change, plus every position's log-prob of its target and top-1 (include/llama2_hip.h)
+extern "C" int l2z_score(const int32_t *tokens, int n_tokens, int pos0, const int32_t *targets, const l2z_config *config,
+                         l2z_runstate *s, const l2z_weights *w, float *out_logprob, int32_t *out_top1)
+{
+    L2Z_TRY(check_pair(config, s, w));
+    L2Z_CHECK(tokens != nullptr && n_tokens >= 1, L2Z_ERR_INVALID, "l2z_score: no tokens");
+    L2Z_CHECK(out_logprob != nullptr || out_top1 != nullptr, L2Z_ERR_INVALID, "l2z_score: no output asked for");
+    L2Z_CHECK((targets != nullptr) == (out_logprob != nullptr), L2Z_ERR_INVALID,
+              "l2z_score: targets and out_logprob go together (both, or neither)");
+    L2Z_CHECK(s->comm == nullptr && s->sh.world == 1, L2Z_ERR_INVALID,
+              "l2z_score: sharded runstates are not supported (the vocabulary rows are sharded there)");
+    L2Z_TRY(prefill_check(config, s));
+    L2Z_CHECK(pos0 >= 0 && pos0 + n_tokens <= config->seq_len, L2Z_ERR_STATE,
+              "l2z_score: positions %d..%d outside [0,%d)", pos0, pos0 + n_tokens - 1, config->seq_len);
+    for (int i = 0; i < n_tokens; i++) {
+        L2Z_CHECK(tokens[i] >= 0 && tokens[i] < config->vocab_size, L2Z_ERR_STATE,
+                  "l2z_score: tokens[%d] = %d out of vocabulary", i, tokens[i]);
+        L2Z_CHECK(targets == nullptr || (targets[i] >= -1 && targets[i] < config->vocab_size), L2Z_ERR_STATE,
+                  "l2z_score: targets[%d] = %d is neither -1 nor in the vocabulary", i, targets[i]);
+    }
+    L2Z_HIP(hipSetDevice(s->device));
+    int longest = 0;   // the plan's longest chunk sizes the workspace before anything is enqueued
+    for (int done = 0; done < n_tokens;) {
+        const int P = prefill_next_chunk_of(*config, n_tokens - done);
+        longest = std::max(longest, P);
+        done += P;
+    }
+    L2Z_TRY(score_alloc(s, longest));
+    int *d_targets = (int *)s->sc_seq;
+    float *d_logprob = (float *)(d_targets + config->seq_len);
+    int *d_top1 = (int *)(d_logprob + config->seq_len);
+    const ScoreCall sc = {targets ? d_targets : nullptr, out_logprob ? d_logprob : nullptr, out_top1 ? d_top1 : nullptr};
+    if (targets) L2Z_HIP(hipMemcpyAsync(d_targets, targets, (size_t)n_tokens * 4, hipMemcpyHostToDevice, s->stream));
+    L2Z_TRY(prefill_pass(tokens, n_tokens, pos0, config, s, w, &sc));   // (synchronous: ends in a stream sync)
+    if (out_logprob) L2Z_HIP(hipMemcpyAsync(out_logprob, d_logprob, (size_t)n_tokens * 4, hipMemcpyDeviceToHost, s->stream));
+    if (out_top1) L2Z_HIP(hipMemcpyAsync(out_top1, d_top1, (size_t)n_tokens * 4, hipMemcpyDeviceToHost, s->stream));
+    L2Z_HIP(hipStreamSynchronize(s->stream));
+    return L2Z_OK;
+}
+
+// Testing support (include/llama2_hip_test.h): vocabulary columns per slab of l2z_score's classifier product on this
+// runstate -- a positive multiple of the reduction's segment (4096), or 0 for the default.  The outputs do not depend on it.
+extern "C" int l2z_score_slab_set(l2z_runstate *s, int slab_cols)
+{
+    L2Z_CHECK(s != nullptr, L2Z_ERR_INVALID, "l2z_score_slab_set: null runstate");
+    L2Z_CHECK(slab_cols >= 0 && slab_cols % kScoreSeg == 0, L2Z_ERR_INVALID,
+              "l2z_score_slab_set: %d is not a multiple of %d", slab_cols, kScoreSeg);
+    s->sc_slab_force = slab_cols;
     return L2Z_OK;
 }
 

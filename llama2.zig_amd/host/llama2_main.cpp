@@ -5,6 +5,7 @@
 //   llama2 <checkpoint> [-t temp] [-p top_p] [-n steps] [-i prompt] [-s seed] [-v] [-z tokenizer]
 //          [-g n_gpus]   (extension: rows / heads sharded over n GPUs, one process per GPU)
 //          [-b n]        (extension: n independent samples of the prompt, stepped together: run_batch)
+//          [--score]     (extension: no generation -- the log-prob of every prompt token and the perplexity: run_score)
 //
 // At -t 0 the whole generation loop runs on the device (l2z_greedy_run) and the host
 // only prints; otherwise one l2z_transformer + l2z_logits_read per position feeds the
@@ -44,7 +45,9 @@ static const char *usage_text =
     " --tokens                  (extension) also print the token ids to stderr, one line\n"
     " -g, --gpus <int>          (extension) shard weight rows / heads over this many GPUs, default 1\n"
     " -b, --batch <int>         (extension) generate this many independent samples of the prompt together, 1-16,\n"
-    "                           default 1; sample i draws from seed + i\n";
+    "                           default 1; sample i draws from seed + i\n"
+    " --score                   (extension) generate nothing: print pos, token id, piece, log-prob and top-1 id of every\n"
+    "                           token of the prompt (-i), then tokens, nll/token and perplexity; not with -g or -b\n";
 
 static bool verbose = false;
 #define LOGV(...)                                 \
@@ -217,6 +220,65 @@ static int run_batch(int nb, const l2z_config &cfg, const l2z_weights *w, l2z_ru
     return cleanup(0);
 }
 
+// --score: the prompt as generation feeds it -- BOS, then its tokens (:999-1000) -- through one l2z_score call: position i
+// reads token i of that sequence and is scored on prompt[i].  One line per position, then the totals (host double).  Where the
+// library refuses the model's dims (L2Z_ERR_INVALID, as l2z_prefill does) the positions are stepped and the log-softmax is
+// the host's; same output.
+static int run_score(const l2z_config &cfg, const l2z_weights *w, l2z_runstate *s, const Tokenizer &tok,
+                     const std::vector<int32_t> &prompt)
+{
+    const size_t n = prompt.size();
+    if (n == 0) {
+        fprintf(stderr, "error: --score needs a prompt (-i)\n");
+        return 1;
+    }
+    if (n > (size_t)cfg.seq_len) {
+        fprintf(stderr, "error: --score: the prompt has %zu tokens, the model's seq_len is %d\n", n, cfg.seq_len);
+        return 1;
+    }
+    std::vector<int32_t> in(n), top1(n);
+    std::vector<float> lp(n);
+    for (size_t i = 0; i < n; i++) in[i] = i == 0 ? 1 : prompt[i - 1];
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = l2z_score(in.data(), (int)n, 0, prompt.data(), &cfg, s, w, lp.data(), top1.data());
+    if (rc == L2Z_ERR_INVALID) {
+        LOGV("score: %s -- stepping the positions\n", l2z_last_error());
+        std::vector<float> z((size_t)cfg.vocab_size);
+        for (size_t i = 0; i < n; i++) {
+            if (l2z_transformer(in[i], (int)i, &cfg, s, w) != L2Z_OK) return die("transformer");
+            if (l2z_logits_read(s, z.data()) != L2Z_OK) return die("logits_read");
+            size_t best = 0;
+            for (size_t v = 1; v < z.size(); v++)
+                if (z[v] > z[best]) best = v;
+            double sum = 0.0;
+            for (float v : z) sum += std::exp((double)v - (double)z[best]);
+            lp[i] = (float)((double)z[(size_t)prompt[i]] - ((double)z[best] + std::log(sum)));
+            top1[i] = (int32_t)best;
+        }
+    } else if (rc != L2Z_OK) {
+        return die("score");
+    }
+    const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    double total = 0.0;
+    for (size_t i = 0; i < n; i++) {
+        std::string piece = "\"";
+        for (unsigned char ch : tok.tokens[(size_t)prompt[i]]) {
+            char buf[8];
+            if (ch == '"' || ch == '\\') { piece.push_back('\\'); piece.push_back((char)ch); }
+            else if (ch < 0x20 || ch == 0x7f) { snprintf(buf, sizeof buf, "\\x%02x", ch); piece += buf; }
+            else piece.push_back((char)ch);
+        }
+        piece.push_back('"');
+        printf("%zu\t%d\t%s\t%.6f\t%d\n", i, prompt[i], piece.c_str(), (double)lp[i], top1[i]);
+        total += (double)lp[i];
+    }
+    const double nll = -total / (double)n;
+    printf("tokens: %zu\nnll/token: %.6f\nperplexity: %.6f\n", n, nll, std::exp(nll));
+    fflush(stdout);
+    LOGV("\n%u tokens per second (scored)\n", (unsigned)(el > 0.0 ? (double)n / el : 0.0));
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 2) {  // :833-836
@@ -228,7 +290,7 @@ int main(int argc, char **argv)
     float temperature = 1.0f, top_p = 0.9f;  // :840-841
     size_t seq_len = 0;
     std::string tokenizer_path = "tokenizer.bin";
-    bool dump_tokens = false;
+    bool dump_tokens = false, score = false;
     int n_gpus = 1, n_batch = 1;
     uint64_t seed = (uint64_t)std::chrono::system_clock::now().time_since_epoch().count();
     Prng prng(seed);  // :844-845
@@ -296,6 +358,8 @@ int main(int argc, char **argv)
             verbose = true;
         } else if (a == "--tokens") {
             dump_tokens = true;
+        } else if (a == "--score") {
+            score = true;
         } else if (a == "-g" || a == "--gpus") {
             n_gpus = atoi(need(i, "gpus"));
             if (n_gpus < 1 || n_gpus > 16) {
@@ -323,6 +387,11 @@ int main(int argc, char **argv)
     }
     if (n_batch > 1 && n_gpus > 1) {
         fprintf(stderr, "error: --batch and --gpus do not combine: shard groups are not batched\n");
+        return 1;
+    }
+    if (score && (n_batch > 1 || n_gpus > 1)) {
+        fprintf(stderr, "error: --score does not combine with %s: one sequence on one GPU is scored per run\n",
+                n_batch > 1 ? "--batch" : "--gpus");
         return 1;
     }
 
@@ -471,6 +540,12 @@ int main(int argc, char **argv)
         return finish(1);
     }
     const size_t prompt_len = prompt.size();
+    if (score) {
+        const int rc = run_score(cfg, w, s, tok, prompt);
+        l2z_runstate_free(s);
+        l2z_weights_free(w);
+        return finish(rc);
+    }
 
     seq_len = seq_len == 0 ? (size_t)cfg.seq_len : seq_len;                        // :992
     seq_len = seq_len < 1 ? 1 : (seq_len > (size_t)cfg.seq_len ? (size_t)cfg.seq_len : seq_len);  // :993
