@@ -111,6 +111,20 @@ pub extern fn l2z_score(
     out_logprob: ?[*]f32,
     out_top1: ?[*]i32,
 ) c_int;
+/// Speculative greedy decoding (no reference equivalent): tokens[0] is the sequence's token at pos0, tokens[1 ..] are
+/// guesses for the positions after it; one sweep of the weights.  out_next[i] = the model's argmax after tokens[0 .. i],
+/// out_accepted = a = how many leading guesses it agrees with; out_next[0 .. a] are the sequence's next a + 1 tokens and
+/// the next position is pos0 + a + 1.  The ids a greedy loop emits do not depend on the guesses.
+pub extern fn l2z_verify(
+    tokens: [*]const i32,
+    n_tokens: c_int,
+    pos0: c_int,
+    config: *const L2zConfig,
+    s: *L2zRunState,
+    w: *const L2zWeights,
+    out_next: [*]i32,
+    out_accepted: *c_int,
+) c_int;
 pub extern fn l2z_synchronize(s: *L2zRunState) c_int;
 /// Batched decode (no reference equivalent): up to batch_max sequences, one runstate each, one token each, one sweep
 /// of the weights -- the state change of l2z_transformer(tokens[i], pos[i], config, states[i], w) for every i.

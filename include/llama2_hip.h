@@ -20,6 +20,7 @@
  *   logits / temperature, softmax :1005-1008  l2z_probs_read        (on the device, then D2H)
  *   while (pos < seq_len) loop at -t 0 :995  l2z_greedy_begin / l2z_greedy_run
  *   (no reference equivalent)                l2z_score             (log-prob and top-1 of every position of a text)
+ *   (no reference equivalent)                l2z_verify            (several positions of one sequence per sweep: speculation)
  *   matmul, rmsnorm, softmax, ... :432-726   kernel-level hooks of the same names, for tests only:
  *                                            include/llama2_hip_test.h
  *
@@ -224,6 +225,38 @@ int l2z_sample_batch(int n, l2z_runstate *const *states, const float *temperatur
  * Contract: dst and src distinct, unsharded, on one device, made with one config (else L2Z_ERR_INVALID);
  * 0 <= n_pos <= seq_len (else L2Z_ERR_STATE); nothing is enqueued on a refusal. */
 int l2z_runstate_fork(l2z_runstate *dst, const l2z_runstate *src, int n_pos);
+
+/* ---- speculative greedy decoding: verify up to L2Z_BATCH_MAX - 1 guessed tokens of ONE sequence in one sweep ----
+ * One sequence, n_tokens consecutive positions, one sweep of the weights.
+ * tokens[0] is the sequence's token at pos0 (known); tokens[1 .. n_tokens-1] are GUESSES for pos0+1 ...
+ * Row i computes z_i = the logits of position pos0+i given tokens[0..i] on top of the cache rows < pos0,
+ * next_i = argmax z_i (strict '>', lowest index: l2z_argmax's rule).
+ * *out_accepted = a = the largest a in [0, n_tokens-1] with tokens[j] == next_{j-1} for all 1 <= j <= a.
+ * out_next[0 .. n_tokens-1] = next_i; entries 0 .. a are the sequence's next a+1 tokens, the rest are what the model
+ * would have said after a wrong guess (diagnostic only).
+ * STATE on return: KV rows pos0 .. pos0+a of every layer are the sequence's; the runstate's logits are z_a
+ * (l2z_argmax == out_next[a]; l2z_logits_read / l2z_probs_read / l2z_sample_batch work on them); the next position is
+ * pos0+a+1.  Rows pos0+a+1 .. pos0+n_tokens-1 have been written with the rejected guesses' keys and values: they are
+ * beyond the next position, which every entry point overwrites before it reads (pos strictly increasing).  No row
+ * < pos0 and no row >= pos0+n_tokens is touched.  Synchronous (one copy back, one sync).
+ * The products are the batched step's (one kernel form whatever n_tokens is); attention is a multi-query, causal form
+ * split over fixed segments of absolute positions that reads each K / V row once per call (flash arithmetic: agrees
+ * with l2z_transformer up to summation order, the fp32 parity bar, not bit for bit).
+ * DRAFT INVARIANCE: z_i and the K / V rows of position p = pos0+i are a function of the model, the tokens at positions
+ * 0 .. p and p alone.  They do not depend on n_tokens, on i, on pos0, on the guesses behind row i, or on how earlier
+ * positions were cut into calls -- provided the earlier positions were themselves produced by l2z_verify (rows produced
+ * by l2z_prefill / l2z_transformer are inputs like any other: same inputs, same bits).  Consequence: a greedy loop over
+ * l2z_verify emits the same ids, and ends with the same logits and cache bits, for every drafter and every number of
+ * guesses, none included.  Speculation changes the time, never the text.
+ * Contract (a refusal enqueues nothing and changes no state): L2Z_ERR_INVALID for NULL arguments, n_tokens outside
+ * [1, L2Z_BATCH_MAX], a sharded runstate, dims l2z_transformer_batch refuses; L2Z_ERR_STATE for pos0 < 0,
+ * pos0 + n_tokens > seq_len, a token outside the vocabulary; L2Z_ERR_NO_DEVICE without a device.
+ * Scratch (on the runstate's first call, freed with it): the batched step's activation rows, L2Z_BATCH_MAX x vocab_size
+ * floats of logits, the attention partials.
+ * OUT OF SCOPE: sampled speculation (temperature > 0 needs the rejection-sampling rule and per-row probabilities), several
+ * sequences per call, sharded runstates, hipGraph replay of the pass (its grid depends on pos0). */
+int l2z_verify(const int32_t *tokens, int n_tokens, int pos0, const l2z_config *config, l2z_runstate *s,
+               const l2z_weights *w, int32_t *out_next, int *out_accepted);
 
 /* ---- multi-GPU shard group: one process per GPU, xGMI ----
  * The reference is single-threaded and single-device; this is what the build

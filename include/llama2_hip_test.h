@@ -198,6 +198,14 @@ int l2z_sample_time(int n, l2z_runstate *const *states, const float *temperature
  * of 4096 (the reduction's segment; else L2Z_ERR_INVALID), or 0 for the default (by the workspace budget).  Applies from
  * the next l2z_score call.  The outputs do not depend on it, bit for bit: that is what the tests use it for. */
 int l2z_score_slab_set(l2z_runstate *s, int slab_cols);
+/* Row `row` (0 .. n_tokens - 1) of the logits matrix of this runstate's last l2z_verify call: every z_i, not only the
+ * accepted z_a the runstate keeps (vocab_size floats).  L2Z_ERR_STATE when there is no such row.  Synchronous. */
+int l2z_verify_logits_read(l2z_runstate *s, int row, float *out);
+/* Measurement (scripts/verify_bench.py): one l2z_verify call, then `iters` passes back to back (verdict launches and
+ * their copy included, no sync), timed by device events on the runstate's stream; *out_ms = milliseconds per pass.  The
+ * passes rewrite the same KV rows.  The twin of l2z_batch_time. */
+int l2z_verify_time(const int32_t *tokens, int n_tokens, int pos0, const l2z_config *config, l2z_runstate *s,
+                    const l2z_weights *w, int iters, double *out_ms);
 
 #ifdef __cplusplus
 }

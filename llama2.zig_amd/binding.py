@@ -90,6 +90,10 @@ def lib():
     if hasattr(L, "l2z_score"):  # (an older build loaded through L2Z_LIB lacks it)
         L.l2z_score.argtypes = [i32p, C.c_int, C.c_int, i32p, cfgp, vp, vp, fp, i32p]
         L.l2z_score_slab_set.argtypes = [vp, C.c_int]
+    if hasattr(L, "l2z_verify"):
+        L.l2z_verify.argtypes = [i32p, C.c_int, C.c_int, cfgp, vp, vp, i32p, ip]
+        L.l2z_verify_logits_read.argtypes = [vp, C.c_int, fp]
+        L.l2z_verify_time.argtypes = [i32p, C.c_int, C.c_int, cfgp, vp, vp, C.c_int, C.POINTER(C.c_double)]
     L.l2z_transformer_batch.argtypes = [C.c_int, i32p, i32p, cfgp, C.POINTER(vp), vp]
     L.l2z_argmax_batch.argtypes = [C.c_int, C.POINTER(vp), i32p]
     L.l2z_batch_time.argtypes = [C.c_int, i32p, i32p, cfgp, C.POINTER(vp), vp, C.c_int, C.POINTER(C.c_double)]
@@ -330,6 +334,32 @@ class RunState:
         """l2z_score_slab_set (test hook): vocabulary rows per slab of score()'s classifier product, 0: the default."""
         _chk(lib().l2z_score_slab_set(self.h, slab_cols))
 
+    def verify(self, tokens, pos0: int, w: Weights):
+        """l2z_verify: tokens[0] is the sequence's token at pos0, tokens[1:] are guesses for the positions after it.
+        Returns (next: int32[n], accepted): next[i] = the model's argmax after tokens[:i + 1]; next[:accepted + 1] are
+        the sequence's next tokens and the runstate stands at pos0 + accepted + 1 with the logits behind next[accepted]."""
+        t = np.ascontiguousarray(tokens, np.int32)
+        nxt = np.zeros(max(t.size, 1), np.int32)
+        a = C.c_int(0)
+        i32p = C.POINTER(C.c_int32)
+        _chk(lib().l2z_verify(t.ctypes.data_as(i32p), t.size, pos0, C.byref(self.cfg), self.h, w.h, nxt.ctypes.data_as(i32p),
+                              C.byref(a)))
+        return nxt[: t.size].copy(), a.value
+
+    def verify_logits(self, row: int) -> np.ndarray:
+        """l2z_verify_logits_read (test hook): row `row` of the last verify() call's logits matrix."""
+        out = np.empty(self.cfg.vocab_size, np.float32)
+        _chk(lib().l2z_verify_logits_read(self.h, row, _fp(out)))
+        return out
+
+    def verify_time(self, tokens, pos0: int, w: Weights, iters: int) -> float:
+        """l2z_verify_time: milliseconds per verify pass, device events over `iters` passes (after one untimed)."""
+        t = np.ascontiguousarray(tokens, np.int32)
+        ms = C.c_double(0.0)
+        _chk(lib().l2z_verify_time(t.ctypes.data_as(C.POINTER(C.c_int32)), t.size, pos0, C.byref(self.cfg), self.h, w.h, iters,
+                                   C.byref(ms)))
+        return ms.value
+
     def argmax(self) -> int:
         t = C.c_int(0)
         _chk(lib().l2z_argmax(self.h, C.byref(t)))
@@ -483,6 +513,79 @@ def sample_time(states, temperature, top_p, coins, iters: int) -> float:
 def runstate_fork(dst: RunState, src: RunState, n_pos: int) -> None:
     """l2z_runstate_fork: dst takes src's KV rows 0 .. n_pos-1 and its logits; dst's next position is n_pos."""
     _chk(lib().l2z_runstate_fork(dst.h, src.h, n_pos))
+
+
+HOST_LIB_PATH = os.path.join(_HERE, "host", "libllama2_host.so")
+_host = None
+
+
+def host_lib():
+    """libllama2_host.so: the host logic above the C ABI (tokenizer, samplers, the prompt-lookup drafter); no HIP."""
+    global _host
+    if _host is None:
+        if not os.path.exists(HOST_LIB_PATH):
+            raise FileNotFoundError(f"{HOST_LIB_PATH} not built; run `python -c 'import __graft_entry__ as g; g.build()'`")
+        H = C.CDLL(HOST_LIB_PATH)
+        H.l2zh_lookup_draft.argtypes = [C.POINTER(C.c_int32), C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        H.l2zh_lookup_draft.restype = C.c_size_t
+        _host = H
+    return _host
+
+
+def lookup_draft(history, k: int, max_ngram: int = 3) -> np.ndarray:
+    """Prompt-lookup drafter (l2zh_lookup_draft): for g = max_ngram .. 1 the most recent earlier occurrence of the last g
+    tokens of `history`; the up to k tokens that followed it, or none."""
+    h = np.ascontiguousarray(history, np.int32)
+    out = np.zeros(max(int(k), 1), np.int32)
+    i32p = C.POINTER(C.c_int32)
+    n = host_lib().l2zh_lookup_draft(h.ctypes.data_as(i32p), h.size, int(max_ngram), int(k), out.ctypes.data_as(i32p))
+    return out[:n].copy()
+
+
+def speculate_greedy(s: RunState, w: Weights, prompt, n_steps: int, k: int, drafter=None):
+    """The loop of `llama2 -t 0 --spec k`: greedy decoding of n_steps positions (0 = seq_len) from BOS + prompt, up to k
+    guessed tokens verified per sweep of the weights (RunState.verify).  drafter(history, k) -> guesses (history: BOS, then
+    everything emitted; at most k ids are used); default lookup_draft.  Returns (tokens, stats): tokens = the `next` of
+    every position from 0 as l2z_greedy_run reports them (prompt positions echo the prompt; a BOS ends the run and is the
+    last id), stats = {"calls", "offered", "accepted", "emitted"} (emitted: ids that came out of verify calls).  The ids do
+    not depend on k or on the drafter (DRAFT INVARIANCE)."""
+    if not 0 <= k <= BATCH_MAX - 1:
+        raise ValueError(f"k = {k} outside [0, {BATCH_MAX - 1}]")
+    if drafter is None:
+        drafter = lookup_draft
+    seq_len = s.cfg.seq_len
+    steps = seq_len if n_steps == 0 else max(1, min(int(n_steps), seq_len))
+    hist, out = [1], []
+    stats = {"calls": 0, "offered": 0, "accepted": 0, "emitted": 0}
+
+    def emit(t):
+        out.append(int(t))
+        hist.append(int(t))
+        return int(t) != 1
+
+    alive, pos = True, 0
+    prompt = [int(t) for t in prompt][:steps]
+    while alive and pos < len(prompt):
+        alive = emit(prompt[pos])
+        pos += alive
+    if alive and pos < steps:
+        s.prefill(np.array(hist, np.int32), 0, w)
+        alive = emit(s.argmax())
+        pos += alive
+    while alive and pos < steps:
+        kk = min(k, steps - pos - 1)
+        guesses = [int(g) for g in drafter(np.array(hist, np.int32), kk)][:kk] if kk > 0 else []
+        nxt, a = s.verify([hist[-1]] + guesses, pos, w)
+        stats["calls"] += 1
+        stats["offered"] += len(guesses)
+        stats["accepted"] += a
+        for t in nxt[: a + 1]:
+            if not (alive and pos < steps):
+                break
+            alive = emit(t)
+            stats["emitted"] += 1
+            pos += alive
+    return np.array(out, np.int32), stats
 
 
 def emu_transformer(states, weights, token: int, pos: int) -> None:

@@ -83,4 +83,30 @@ struct SampleArgs {
 inline size_t sample_scratch_floats(int vocab) { return 5 * (((size_t)vocab + 63) / 64 * 64); }
 hipError_t launch_sample_batch(const SampleArgs &a, int n, hipStream_t st);
 
+// l2z_verify (verify.hip): n rows of ONE sequence at consecutive positions tab->pos[i] = pos0 + i, all on one cache.
+// Attention is multi-query, causal and split over positions: a block owns (head, segment), the segments are
+// kVerifySeg ABSOLUTE positions each -- segment s = positions [s * kVerifySeg, (s + 1) * kVerifySeg) whatever pos0 and
+// n are -- loads each K and V row of its segment once and uses it for every row; it leaves per (row, head, segment)
+// the flash partials (max, sum e^(s - max), sum e^(s - max) v).  launch_verify_combine folds a row's segments in
+// segment order and divides.  Every order is a function of head_size, the segment and the row's position alone.
+constexpr int kVerifySeg = 64;
+inline int verify_segments(int seq_len) { return (seq_len + kVerifySeg - 1) / kVerifySeg; }
+struct VerifyAttnArgs {
+    const float *q;    // [n, ldq], RoPE applied
+    float *out;        // [n, ldo]
+    float *part_o;     // [kBatchMax, n_heads, seg_cap, head_size]
+    float *part_ml;    // [kBatchMax, n_heads, seg_cap, 2]: max, sum
+    const float *kc, *vc;  // the layer's caches, head-major [kv head][seq_len][head_size]
+    size_t kv_head_stride;
+    int ldq, ldo, n_heads, kv_mul, head_size, seg_cap, pos0;
+};
+hipError_t launch_verify_attention(const VerifyAttnArgs &a, int n, hipStream_t st);
+hipError_t launch_verify_combine(const VerifyAttnArgs &a, int n, hipStream_t st);
+
+// The verdict of a verify pass, on the device: next[i] = argmax of logits + i * vocab (block_argmax_1024: the tie rule
+// of l2z_argmax_batch); a = the number of leading guesses tab->tokens[j] == next[j - 1], j = 1 ..; out[0 .. n) = next,
+// out[n] = a; row a of the logits matrix is copied to dst (the runstate's logits).  Two launches.
+hipError_t launch_verify_accept(const BatchTable *tab, const float *logits, int vocab, int *out, float *dst, int n,
+                                hipStream_t st);
+
 }  // namespace l2z

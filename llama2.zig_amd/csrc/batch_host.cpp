@@ -2,7 +2,8 @@
 // L2Z_BATCH_MAX independent sequences advanced by one token with one sweep of the weights.  Kernels: the short-prompt
 // GEMM forms with per-row epilogues (prefill_skinny.hip, G_*_ROWS) and batch_decode.hip.  Also what a batch of samples
 // needs around the step: the on-device sampler l2z_sample_batch (sample_batch.hip) and the prompt copy
-// l2z_runstate_fork.
+// l2z_runstate_fork.  And l2z_verify: the same step with the rows being consecutive positions of ONE sequence
+// (speculative greedy decoding), attention and verdict by verify.hip.
 #include <cmath>
 #include <cstring>
 
@@ -27,17 +28,24 @@ struct BatchScratch {
     hipEvent_t ev_upload = nullptr;  // the last table copy: the pinned table may be rewritten once it has completed
     float *smp = nullptr;            // l2z_sample_batch: kBatchMax rows of sample_scratch_floats(vocab) (on first use)
     size_t smp_stride = 0;
+    // l2z_verify (on the runstate's first call): the [kBatchMax, vocab] logits matrix, the attention partials
+    // ([kBatchMax, n_heads, v_seg_cap, head_size] and [..., 2]), next[0 .. n) | accepted on the device and pinned
+    float *v_logits = nullptr, *v_part_o = nullptr, *v_part_ml = nullptr;
+    int *d_vout = nullptr, *h_vout = nullptr;
+    int v_seg_cap = 0, v_rows = 0;   // v_rows: rows of the last call (l2z_verify_logits_read)
 };
 
 void batch_free(l2z_runstate *s)
 {
     BatchScratch *b = s->bt;
     if (b == nullptr) return;
-    void *ptrs[] = {b->x, b->xn, b->q, b->att, b->h1, b->scores, b->d_tab, b->d_tokens_out, b->smp};
+    void *ptrs[] = {b->x, b->xn, b->q, b->att, b->h1, b->scores, b->d_tab, b->d_tokens_out, b->smp,
+                    b->v_logits, b->v_part_o, b->v_part_ml, b->d_vout};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (b->h_tab) (void)hipHostFree(b->h_tab);
     if (b->h_tokens_out) (void)hipHostFree(b->h_tokens_out);
+    if (b->h_vout) (void)hipHostFree(b->h_vout);
     for (hipEvent_t e : b->ev_in)
         if (e) (void)hipEventDestroy(e);
     if (b->ev_done) (void)hipEventDestroy(b->ev_done);
@@ -155,7 +163,9 @@ GemmArgs gemm(const float *x, int ldx, const float *w, int ldw, int N, int K, in
 
 // One step of n sequences on states[0]'s stream.  Every product is the one-tile short-prompt form at P = n whatever n
 // is (launch_batch_skinny): a row's bits do not depend on n, on the other rows, or on its place in the batch.
-int batch_step(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *w, BatchScratch *b)
+// verify_pos0 >= 0 (l2z_verify): the rows are positions verify_pos0 .. of s0's own sequence, and attention is the
+// multi-query position-split form over s0's cache (verify.hip) instead of one block per (head, row).
+int batch_step(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *w, BatchScratch *b, int verify_pos0 = -1)
 {
     hipStream_t st = s0->stream;
     const int dim = c.dim, hid = c.hidden_dim, hs = dim / c.n_heads, kvd = hs * c.n_kv_heads;
@@ -176,7 +186,16 @@ int batch_step(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *
             a.row_pos = tab->pos; a.row_kc = tab->kc; a.row_vc = tab->vc; a.layer_off = layer_off;
             L2Z_HIP(launch_batch_skinny(G_QKV_ROWS, a, st));
         }
-        {   // :361-389
+        if (verify_pos0 >= 0) {  // :361-389, flash form
+            VerifyAttnArgs a = {};
+            a.q = b->q; a.ldq = dim; a.out = b->att; a.ldo = b->ld_att; a.part_o = b->v_part_o; a.part_ml = b->v_part_ml;
+            a.kc = s0->key_cache + layer_off; a.vc = s0->value_cache + layer_off;
+            a.kv_head_stride = (size_t)c.seq_len * hs;
+            a.n_heads = c.n_heads; a.kv_mul = c.n_heads / c.n_kv_heads; a.head_size = hs; a.seg_cap = b->v_seg_cap;
+            a.pos0 = verify_pos0;
+            L2Z_HIP(launch_verify_attention(a, n, st));
+            L2Z_HIP(launch_verify_combine(a, n, st));
+        } else {  // :361-389
             BatchAttnArgs a = {};
             a.q = b->q; a.ldq = dim; a.out = b->att; a.ldo = b->ld_att; a.scores = b->scores; a.tab = tab;
             a.layer_off = layer_off; a.kv_head_stride = (size_t)c.seq_len * hs;
@@ -457,6 +476,134 @@ extern "C" int l2z_batch_time(int n, const int32_t *tokens, const int32_t *pos, 
     int rc = L2Z_OK;
     if (hipEventRecord(e0, st) != hipSuccess) rc = L2Z_ERR_HIP;
     for (int i = 0; i < iters && rc == L2Z_OK; i++) rc = l2z_transformer_batch(n, tokens, pos, config, states, w);
+    float ms = 0.0f;
+    if (rc == L2Z_OK && (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
+                         hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
+        rc = L2Z_ERR_HIP;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (rc == L2Z_OK) *out_ms = ms / iters;
+    return rc;
+}
+
+// ---- l2z_verify: n consecutive positions of ONE sequence in one sweep, and which guesses the model agrees with ----
+namespace l2z {
+namespace {
+
+int verify_alloc(l2z_runstate *s)
+{
+    BatchScratch *b = s->bt;
+    if (b->v_logits != nullptr && b->v_part_o != nullptr && b->v_part_ml != nullptr && b->d_vout != nullptr &&
+        b->h_vout != nullptr)
+        return L2Z_OK;
+    const l2z_config &c = s->cfg;
+    const size_t R = kBatchMax, segs = (size_t)verify_segments(c.seq_len), hs = (size_t)c.dim / c.n_heads;
+    struct { void **p; size_t bytes; } want[] = {
+        {(void **)&b->v_logits, R * (size_t)c.vocab_size * 4},
+        {(void **)&b->v_part_o, R * c.n_heads * segs * hs * 4},
+        {(void **)&b->v_part_ml, R * c.n_heads * segs * 2 * 4},
+        {(void **)&b->d_vout, (R + 1) * 4}};
+    for (auto &w : want) {
+        if (*w.p != nullptr) continue;
+        const hipError_t e = hipMalloc(w.p, w.bytes);
+        if (e != hipSuccess) {
+            *w.p = nullptr;
+            set_error("l2z_verify scratch allocation (%zu bytes) failed: %s", w.bytes, hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
+        }
+    }
+    if (b->h_vout == nullptr) L2Z_HIP(hipHostMalloc((void **)&b->h_vout, (R + 1) * 4, hipHostMallocDefault));
+    b->v_seg_cap = (int)segs;
+    return L2Z_OK;
+}
+
+// l2z_verify's checks (a refusal enqueues nothing), then the table, the pass, the verdict and its copy back on s's
+// stream; no sync
+int verify_enqueue(const int32_t *tokens, int n, int pos0, const l2z_config *config, l2z_runstate *s, const l2z_weights *w)
+{
+    L2Z_TRY(no_device_check());
+    L2Z_CHECK(tokens != nullptr && config != nullptr && s != nullptr && w != nullptr, L2Z_ERR_INVALID,
+              "l2z_verify: null argument");
+    L2Z_CHECK(n >= 1 && n <= kBatchMax, L2Z_ERR_INVALID, "l2z_verify: n_tokens = %d outside [1, %d]", n, kBatchMax);
+    L2Z_CHECK(s->comm == nullptr && s->sh.world == 1, L2Z_ERR_INVALID, "l2z_verify: the runstate is a shard");
+    L2Z_TRY(check_pair(config, s, w));
+    L2Z_TRY(prefill_check(config, s));
+    L2Z_CHECK(s->sh.hs <= 256, L2Z_ERR_INVALID, "l2z_verify: head_size above 256");
+    L2Z_CHECK(pos0 >= 0 && pos0 <= config->seq_len - n, L2Z_ERR_STATE, "l2z_verify: positions %d .. %d outside [0, %d)", pos0,
+              pos0 + n - 1, config->seq_len);
+    for (int i = 0; i < n; i++)
+        L2Z_CHECK(tokens[i] >= 0 && tokens[i] < config->vocab_size, L2Z_ERR_STATE, "l2z_verify: tokens[%d] = %d out of vocabulary",
+                  i, tokens[i]);
+    L2Z_HIP(hipSetDevice(s->device));
+    L2Z_TRY(batch_alloc(s));
+    L2Z_TRY(verify_alloc(s));
+    BatchScratch *b = s->bt;
+    BatchTable t = {};
+    for (int i = 0; i < n; i++) {
+        t.tokens[i] = tokens[i];
+        t.pos[i] = pos0 + i;
+        t.kc[i] = s->key_cache;
+        t.vc[i] = s->value_cache;
+        t.logits[i] = b->v_logits + (size_t)i * config->vocab_size;
+    }
+    hipStream_t st = s->stream;
+    L2Z_TRY(upload_table(b, t, st));
+    L2Z_TRY(batch_step(n, *config, s, w, b, pos0));
+    L2Z_HIP(launch_verify_accept(b->d_tab, b->v_logits, config->vocab_size, b->d_vout, s->logits, n, st));
+    L2Z_HIP(hipMemcpyAsync(b->h_vout, b->d_vout, (size_t)(n + 1) * 4, hipMemcpyDeviceToHost, st));
+    b->v_rows = n;
+    s->n_part = 0;  // l2z_argmax scans the logits the verdict copied
+    s->logits_partial = false;
+    return L2Z_OK;
+}
+
+}  // namespace
+}  // namespace l2z
+
+extern "C" int l2z_verify(const int32_t *tokens, int n_tokens, int pos0, const l2z_config *config, l2z_runstate *s,
+                          const l2z_weights *w, int32_t *out_next, int *out_accepted)
+{
+    L2Z_TRY(no_device_check());
+    L2Z_CHECK(out_next != nullptr && out_accepted != nullptr, L2Z_ERR_INVALID, "l2z_verify: null argument");
+    L2Z_TRY(verify_enqueue(tokens, n_tokens, pos0, config, s, w));
+    BatchScratch *b = s->bt;
+    L2Z_HIP(hipStreamSynchronize(s->stream));
+    memcpy(out_next, b->h_vout, (size_t)n_tokens * 4);
+    *out_accepted = b->h_vout[n_tokens];
+    s->host_pos = pos0 + *out_accepted + 1;
+    return L2Z_OK;
+}
+
+// Testing support (include/llama2_hip_test.h): row `row` of the last l2z_verify call's logits matrix
+extern "C" int l2z_verify_logits_read(l2z_runstate *s, int row, float *out)
+{
+    L2Z_TRY(no_device_check());
+    L2Z_CHECK(s != nullptr && out != nullptr, L2Z_ERR_INVALID, "l2z_verify_logits_read: null argument");
+    L2Z_CHECK(s->bt != nullptr && s->bt->v_logits != nullptr && row >= 0 && row < s->bt->v_rows, L2Z_ERR_STATE,
+              "l2z_verify_logits_read: row %d is not a row of this runstate's last l2z_verify call", row);
+    L2Z_HIP(hipSetDevice(s->device));
+    L2Z_HIP(hipMemcpyAsync(out, s->bt->v_logits + (size_t)row * s->cfg.vocab_size, (size_t)s->cfg.vocab_size * 4,
+                           hipMemcpyDeviceToHost, s->stream));
+    L2Z_HIP(hipStreamSynchronize(s->stream));
+    return L2Z_OK;
+}
+
+// Testing support: one l2z_verify call, then `iters` passes back to back (verdict and its copy included, no sync), timed
+// by device events on the runstate's stream (scripts/verify_bench.py).  The passes rewrite the same KV rows.
+extern "C" int l2z_verify_time(const int32_t *tokens, int n_tokens, int pos0, const l2z_config *config, l2z_runstate *s,
+                               const l2z_weights *w, int iters, double *out_ms)
+{
+    L2Z_CHECK(iters >= 1 && out_ms != nullptr, L2Z_ERR_INVALID, "l2z_verify_time: bad arguments");
+    int32_t next[kBatchMax];
+    int acc = 0;
+    L2Z_TRY(l2z_verify(tokens, n_tokens, pos0, config, s, w, next, &acc));  // validates, allocates
+    hipStream_t st = s->stream;
+    hipEvent_t e0, e1;
+    L2Z_HIP(hipEventCreate(&e0));
+    L2Z_HIP(hipEventCreate(&e1));
+    int rc = L2Z_OK;
+    if (hipEventRecord(e0, st) != hipSuccess) rc = L2Z_ERR_HIP;
+    for (int i = 0; i < iters && rc == L2Z_OK; i++) rc = verify_enqueue(tokens, n_tokens, pos0, config, s, w);
     float ms = 0.0f;
     if (rc == L2Z_OK && (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
                          hipEventElapsedTime(&ms, e0, e1) != hipSuccess))

@@ -396,6 +396,24 @@ int is_raw_byte(std::string_view s)
     return (print || space) ? byte : -1;
 }
 
+size_t lookup_draft(const int32_t *history, size_t n, int max_ngram, int k, int32_t *out)
+{
+    if (k <= 0 || history == nullptr) return 0;
+    for (size_t g = max_ngram > 0 ? (size_t)max_ngram : 0; g >= 1; g--) {
+        if (g + 1 > n) continue;  // no j >= 0 below n - g
+        const int32_t *tail = history + (n - g);
+        for (size_t j = n - g; j-- > 0;) {  // most recent first
+            size_t m = 0;
+            while (m < g && history[j + m] == tail[m]) m++;
+            if (m < g) continue;
+            const size_t from = j + g, cnt = std::min((size_t)k, n - from);
+            for (size_t i = 0; i < cnt; i++) out[i] = history[from + i];
+            return cnt;
+        }
+    }
+    return 0;
+}
+
 }  // namespace l2zhost
 
 // ---- C hooks so the tests can drive the host logic through ctypes ----
@@ -444,6 +462,11 @@ long l2zh_tokenizer_encode_quadratic(void *t, const char *bytes, size_t n, int32
     if (!static_cast<Tokenizer *>(t)->encode_quadratic(std::string_view(bytes, n), &v, &e)) return -1;
     for (size_t i = 0; i < v.size() && i < cap; i++) out[i] = v[i];
     return (long)v.size();
+}
+// the drafter of `llama2 --spec` and binding.lookup_draft: out has room for k ids; returns how many it wrote
+size_t l2zh_lookup_draft(const int32_t *history, size_t n_history, int max_ngram, int k, int32_t *out)
+{
+    return lookup_draft(history, n_history, max_ngram, k, out);
 }
 int l2zh_is_raw_byte(const char *s, size_t n) { return is_raw_byte(std::string_view(s, n)); }
 void l2zh_prng_floats(uint64_t seed, float *out, size_t n)

@@ -70,6 +70,10 @@ size_t sample_top_p_margin(const float *probs, size_t n, float p, std::vector<In
 // without one the rng forms return the argmax and draw nothing)
 size_t sample_top_p_coin(const float *probs, size_t n, float p, std::vector<IndexedF32> &scratch, float coin,
                          float *margin);
+// Prompt-lookup drafter for l2z_verify (no reference equivalent; no model): for g = max_ngram down to 1, the MOST RECENT
+// j < n - g with history[j .. j + g) == history[n - g .. n); on the first hit the tokens that followed it,
+// history[j + g .. min(j + g + k, n)), go to out (room for k) and their number is returned; no hit: 0.  O(n * g) per call.
+size_t lookup_draft(const int32_t *history, size_t n, int max_ngram, int k, int32_t *out);
 // :1055-1076  "<0xXX>" -> byte, only if printable or whitespace; -1 otherwise
 int is_raw_byte(std::string_view s);
 

@@ -6,6 +6,8 @@
 //          [-g n_gpus]   (extension: rows / heads sharded over n GPUs, one process per GPU)
 //          [-b n]        (extension: n independent samples of the prompt, stepped together: run_batch)
 //          [--score]     (extension: no generation -- the log-prob of every prompt token and the perplexity: run_score)
+//          [--spec K]    (extension, -t 0 only: speculative greedy decoding -- up to K tokens guessed by prompt lookup are
+//                         verified per sweep of the weights by l2z_verify; the text does not depend on K: run_spec)
 //
 // At -t 0 the whole generation loop runs on the device (l2z_greedy_run) and the host
 // only prints; otherwise one l2z_transformer + l2z_logits_read per position feeds the
@@ -47,7 +49,11 @@ static const char *usage_text =
     " -b, --batch <int>         (extension) generate this many independent samples of the prompt together, 1-16,\n"
     "                           default 1; sample i draws from seed + i\n"
     " --score                   (extension) generate nothing: print pos, token id, piece, log-prob and top-1 id of every\n"
-    "                           token of the prompt (-i), then tokens, nll/token and perplexity; not with -g or -b\n";
+    "                           token of the prompt (-i), then tokens, nll/token and perplexity; not with -g or -b\n"
+    " --spec <int>              (extension) speculative greedy decoding, needs -t 0: guess up to this many tokens (0-15) by\n"
+    "                           looking the last tokens up in the text so far, verify them in one pass; the text is the same\n"
+    "                           for every value.  A pass of one token costs ~1.25x a plain -t 0 step, so it pays on text that\n"
+    "                           repeats its context; not with -b, -g or --score\n";
 
 static bool verbose = false;
 #define LOGV(...)                                 \
@@ -279,6 +285,81 @@ static int run_score(const l2z_config &cfg, const l2z_weights *w, l2z_runstate *
     return 0;
 }
 
+// --spec K: the greedy loop of :995-1042 over l2z_verify.  The prompt (BOS, then its tokens) is one l2z_prefill, the first
+// generated token l2z_argmax; then every call feeds the last token and up to K guesses (lookup_draft over everything emitted
+// so far) and emits the 1 + accepted tokens it returns.  Steps without a guess, and K = 0, still go through l2z_verify with
+// one row: the ids must not depend on the drafter, and l2z_transformer's bits differ from a verify row's at near-ties.
+static int run_spec(int K, const l2z_config &cfg, const l2z_weights *w, l2z_runstate *s, const Tokenizer &tok,
+                    const std::vector<int32_t> &prompt, size_t seq_len, bool dump_tokens)
+{
+    std::vector<int32_t> hist{1}, produced;  // hist: the sequence as the model reads it (BOS first)
+    size_t token = 1, pos = 0;
+    bool timer_started = false;
+    std::chrono::steady_clock::time_point t0;
+    auto emit = [&](size_t next) -> bool {  // :1017-1041, as main()'s
+        produced.push_back((int32_t)next);
+        hist.push_back((int32_t)next);
+        if (next == 1) return false;
+        std::string_view piece = tok.tokens[next];
+        if (token == 1 && !piece.empty() && piece[0] == ' ') piece.remove_prefix(1);
+        const int byte = is_raw_byte(piece);
+        token = next;
+        if (byte >= 0) {
+            fputc(byte, stdout);
+            return true;
+        }
+        fwrite(piece.data(), 1, piece.size(), stdout);
+        if (!timer_started) {
+            fflush(stdout);
+            timer_started = true;
+            t0 = std::chrono::steady_clock::now();
+        }
+        return true;
+    };
+    bool alive = true;
+    const size_t n_prompt = std::min(prompt.size(), seq_len);
+    while (alive && pos < n_prompt) {  // :999-1000
+        alive = emit((size_t)prompt[pos]);
+        if (alive) pos++;
+    }
+    long calls = 0, offered = 0, accepted = 0, from_calls = 0;
+    if (alive && pos < seq_len) {
+        if (l2z_prefill(hist.data(), (int)hist.size(), 0, &cfg, s, w) != L2Z_OK) return die("prefill");
+        int first = 0;
+        if (l2z_argmax(s, &first) != L2Z_OK) return die("argmax");
+        alive = emit((size_t)first);
+        if (alive) pos++;
+    }
+    int32_t in[L2Z_BATCH_MAX], next[L2Z_BATCH_MAX];
+    while (alive && pos < seq_len) {
+        in[0] = (int32_t)token;
+        const size_t room = seq_len - pos - 1;  // positions after this one that may still emit
+        const int k = (int)std::min<size_t>((size_t)K, room);
+        const int nd = (int)lookup_draft(hist.data(), hist.size(), 3, k, in + 1);
+        int a = 0;
+        if (l2z_verify(in, 1 + nd, (int)pos, &cfg, s, w, next, &a) != L2Z_OK) return die("verify");
+        calls++; offered += nd; accepted += a;
+        for (int i = 0; i <= a && alive && pos < seq_len; i++) {
+            alive = emit((size_t)next[i]);
+            from_calls++;
+            if (alive) pos++;
+        }
+    }
+    fflush(stdout);
+    if (timer_started) {
+        const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        LOGV("\n\n%u tokens per second\n", (unsigned)(pos >= 1 && el > 0.0 ? (double)(pos - 1) / el : 0.0));
+    }
+    LOGV("spec: %ld verify calls, %.2f tokens per call, %ld guesses offered, %ld accepted\n", calls,
+         calls ? (double)from_calls / (double)calls : 0.0, offered, accepted);
+    if (dump_tokens) {
+        fprintf(stderr, "tokens:");
+        for (int32_t t : produced) fprintf(stderr, " %d", t);
+        fprintf(stderr, "\n");
+    }
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 2) {  // :833-836
@@ -291,7 +372,7 @@ int main(int argc, char **argv)
     size_t seq_len = 0;
     std::string tokenizer_path = "tokenizer.bin";
     bool dump_tokens = false, score = false;
-    int n_gpus = 1, n_batch = 1;
+    int n_gpus = 1, n_batch = 1, spec = -1;
     uint64_t seed = (uint64_t)std::chrono::system_clock::now().time_since_epoch().count();
     Prng prng(seed);  // :844-845
 
@@ -360,6 +441,15 @@ int main(int argc, char **argv)
             dump_tokens = true;
         } else if (a == "--score") {
             score = true;
+        } else if (a == "--spec") {
+            const char *v = need(i, "spec");
+            char *end = nullptr;
+            const long k = strtol(v, &end, 10);
+            if (end == v || *end || k < 0 || k > L2Z_BATCH_MAX - 1) {
+                fprintf(stderr, "unable to use --spec argument '%s' (0 to %d)\n", v, L2Z_BATCH_MAX - 1);
+                return 1;
+            }
+            spec = (int)k;
         } else if (a == "-g" || a == "--gpus") {
             n_gpus = atoi(need(i, "gpus"));
             if (n_gpus < 1 || n_gpus > 16) {
@@ -392,6 +482,15 @@ int main(int argc, char **argv)
     if (score && (n_batch > 1 || n_gpus > 1)) {
         fprintf(stderr, "error: --score does not combine with %s: one sequence on one GPU is scored per run\n",
                 n_batch > 1 ? "--batch" : "--gpus");
+        return 1;
+    }
+    if (spec >= 0 && (score || n_batch > 1 || n_gpus > 1)) {
+        fprintf(stderr, "error: --spec does not combine with %s: one sequence on one GPU is decoded per run\n",
+                score ? "--score" : n_batch > 1 ? "--batch" : "--gpus");
+        return 1;
+    }
+    if (spec >= 0 && temperature != 0.0f) {
+        fprintf(stderr, "error: --spec is greedy decoding only: add -t 0 (the temperature is %g)\n", temperature);
         return 1;
     }
 
@@ -550,6 +649,12 @@ int main(int argc, char **argv)
     seq_len = seq_len == 0 ? (size_t)cfg.seq_len : seq_len;                        // :992
     seq_len = seq_len < 1 ? 1 : (seq_len > (size_t)cfg.seq_len ? (size_t)cfg.seq_len : seq_len);  // :993
 
+    if (spec >= 0) {
+        const int rc = run_spec(spec, cfg, w, s, tok, prompt, seq_len, dump_tokens);
+        l2z_runstate_free(s);
+        l2z_weights_free(w);
+        return finish(rc);
+    }
     if (n_batch > 1) {
         const int rc = run_batch(n_batch, cfg, w, s, tok, prompt, seq_len, temperature, top_p, seed, dump_tokens);
         l2z_runstate_free(s);
