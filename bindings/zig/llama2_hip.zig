@@ -125,6 +125,23 @@ pub extern fn l2z_verify(
     out_next: [*]i32,
     out_accepted: *c_int,
 ) c_int;
+/// Speculative decoding under the sampler (no reference equivalent): l2z_verify with out_next[i] = the token
+/// l2z_sample_batch draws from row i's logits with (temperature, top_p, coins[i]); coins[i] is the number of position
+/// pos0 + i (one std.Random.float(f32) per generated token, kept when its row is rejected and passed again).  A guess is
+/// accepted when it is the token drawn.  temperature 0: l2z_verify, coins may be null.
+pub extern fn l2z_verify_sample(
+    tokens: [*]const i32,
+    n_tokens: c_int,
+    pos0: c_int,
+    temperature: f32,
+    top_p: f32,
+    coins: ?[*]const f32,
+    config: *const L2zConfig,
+    s: *L2zRunState,
+    w: *const L2zWeights,
+    out_next: [*]i32,
+    out_accepted: *c_int,
+) c_int;
 pub extern fn l2z_synchronize(s: *L2zRunState) c_int;
 /// Batched decode (no reference equivalent): up to batch_max sequences, one runstate each, one token each, one sweep
 /// of the weights -- the state change of l2z_transformer(tokens[i], pos[i], config, states[i], w) for every i.

@@ -21,6 +21,7 @@
  *   while (pos < seq_len) loop at -t 0 :995  l2z_greedy_begin / l2z_greedy_run
  *   (no reference equivalent)                l2z_score             (log-prob and top-1 of every position of a text)
  *   (no reference equivalent)                l2z_verify            (several positions of one sequence per sweep: speculation)
+ *   (no reference equivalent)                l2z_verify_sample     (the same under the sampler: -t / -p speculation)
  *   matmul, rmsnorm, softmax, ... :432-726   kernel-level hooks of the same names, for tests only:
  *                                            include/llama2_hip_test.h
  *
@@ -253,10 +254,39 @@ int l2z_runstate_fork(l2z_runstate *dst, const l2z_runstate *src, int n_pos);
  * pos0 + n_tokens > seq_len, a token outside the vocabulary; L2Z_ERR_NO_DEVICE without a device.
  * Scratch (on the runstate's first call, freed with it): the batched step's activation rows, L2Z_BATCH_MAX x vocab_size
  * floats of logits, the attention partials.
- * OUT OF SCOPE: sampled speculation (temperature > 0 needs the rejection-sampling rule and per-row probabilities), several
- * sequences per call, sharded runstates, hipGraph replay of the pass (its grid depends on pos0). */
+ * OUT OF SCOPE: several sequences per call, sharded runstates, hipGraph replay of the pass (its grid depends on pos0). */
 int l2z_verify(const int32_t *tokens, int n_tokens, int pos0, const l2z_config *config, l2z_runstate *s,
                const l2z_weights *w, int32_t *out_next, int *out_accepted);
+/* ---- speculative decoding under the sampler: l2z_verify with every row DRAWN instead of arg-maxed ----
+ * The pass, the KV rows written, out_accepted's definition, the STATE on return (logits = z_a, next position pos0+a+1),
+ * synchronisation and scratch are l2z_verify's.  The one difference: next_i = the token l2z_sample_batch draws from z_i
+ * with (temperature, top_p, coins[i]) -- that launch's kernel, on the n rows of the pass, so the host sampler's bits.
+ * THE RULE.  A drafter that proposes ONE token x per position as a function of the earlier tokens only (prompt lookup,
+ *   any deterministic callable, a draft model decoded greedily) has the draft distribution q = delta_x.  Rejection
+ *   sampling then accepts x with probability min(1, p(x) / q(x)) = p(x), else draws from max(0, p - q) renormalised = p
+ *   restricted to tokens != x.  That is the law of: draw y from p with the position's own random number; y == x accepts
+ *   the guess, otherwise y is the token.  No ratio, no residual distribution; p is what the sampler samples from.
+ * Give every POSITION its own coin -- coin g belongs to the g-th generated token, as the plain loop draws one per token
+ * (main.zig:731 / :789) -- and pass row i the coin of position pos0+i.  A row behind a rejected guess is discarded and its
+ * position drawn again by the next call WITH THE SAME COIN.  Then the law of the text is the plain sampler's, provided the
+ * drafter never looks at the coins, and
+ * COIN INVARIANCE: given the model, the prompt, temperature, top_p and the coin sequence, the ids do not depend on the
+ * number of guesses or on the drafter, nor do the final logits and the cache rows below the next position, bit for bit
+ * (z_i depends on the tokens at 0 .. pos0+i alone: DRAFT INVARIANCE; the draw on z_i and its position's coin alone:
+ * l2z_sample_batch's BATCH INVARIANCE).  Speculation changes the time, never the text.
+ * Against the reference's stream of numbers the position-indexed coins differ in one place: sample_top_p with no
+ * candidate above its cutoff (the reference asserts there, :771) returns the argmax and draws nothing.  That takes top_p < 1 / vocab_size (the
+ * largest probability is at least 1 / vocab_size, up to rounding); here the position's coin is simply not used.
+ * temperature == 0: next_i is the argmax and coins may be NULL; outputs, logits and cache bits equal l2z_verify's on the
+ * same arguments (its launches).
+ * Contract, on top of l2z_verify's (a refusal enqueues nothing and changes no state): L2Z_ERR_INVALID for a temperature
+ * that is not finite or < 0, top_p outside [0, 1], coins == NULL with temperature > 0, a coins[i] outside [0, 1).
+ * Scratch: l2z_verify's and l2z_sample_batch's (5 x vocab_size floats per row).
+ * OUT OF SCOPE: a drafter that itself samples (the general p / q rule with the draft's probabilities on the device),
+ * several sequences per call, sharded runstates, hipGraph replay, log-probs of the emitted tokens. */
+int l2z_verify_sample(const int32_t *tokens, int n_tokens, int pos0, float temperature, float top_p,
+                      const float *coins, const l2z_config *config, l2z_runstate *s, const l2z_weights *w,
+                      int32_t *out_next, int *out_accepted);
 
 /* ---- multi-GPU shard group: one process per GPU, xGMI ----
  * The reference is single-threaded and single-device; this is what the build

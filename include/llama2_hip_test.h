@@ -198,7 +198,7 @@ int l2z_sample_time(int n, l2z_runstate *const *states, const float *temperature
  * of 4096 (the reduction's segment; else L2Z_ERR_INVALID), or 0 for the default (by the workspace budget).  Applies from
  * the next l2z_score call.  The outputs do not depend on it, bit for bit: that is what the tests use it for. */
 int l2z_score_slab_set(l2z_runstate *s, int slab_cols);
-/* Row `row` (0 .. n_tokens - 1) of the logits matrix of this runstate's last l2z_verify call: every z_i, not only the
+/* Row `row` (0 .. n_tokens - 1) of the logits matrix of this runstate's last l2z_verify or l2z_verify_sample call: every z_i, not only the
  * accepted z_a the runstate keeps (vocab_size floats).  L2Z_ERR_STATE when there is no such row.  Synchronous. */
 int l2z_verify_logits_read(l2z_runstate *s, int row, float *out);
 /* Measurement (scripts/verify_bench.py): one l2z_verify call, then `iters` passes back to back (verdict launches and
@@ -206,6 +206,11 @@ int l2z_verify_logits_read(l2z_runstate *s, int row, float *out);
  * passes rewrite the same KV rows.  The twin of l2z_batch_time. */
 int l2z_verify_time(const int32_t *tokens, int n_tokens, int pos0, const l2z_config *config, l2z_runstate *s,
                     const l2z_weights *w, int iters, double *out_ms);
+/* Measurement (scripts/verify_sample_bench.py): the twin of l2z_verify_time for l2z_verify_sample -- one call, then `iters`
+ * passes back to back (the rows' draws, the accept scan and the copy included, no sync); *out_ms = milliseconds per pass. */
+int l2z_verify_sample_time(const int32_t *tokens, int n_tokens, int pos0, float temperature, float top_p,
+                           const float *coins, const l2z_config *config, l2z_runstate *s, const l2z_weights *w, int iters,
+                           double *out_ms);
 
 #ifdef __cplusplus
 }

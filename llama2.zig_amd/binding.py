@@ -94,6 +94,10 @@ def lib():
         L.l2z_verify.argtypes = [i32p, C.c_int, C.c_int, cfgp, vp, vp, i32p, ip]
         L.l2z_verify_logits_read.argtypes = [vp, C.c_int, fp]
         L.l2z_verify_time.argtypes = [i32p, C.c_int, C.c_int, cfgp, vp, vp, C.c_int, C.POINTER(C.c_double)]
+    if hasattr(L, "l2z_verify_sample"):
+        L.l2z_verify_sample.argtypes = [i32p, C.c_int, C.c_int, C.c_float, C.c_float, fp, cfgp, vp, vp, i32p, ip]
+        L.l2z_verify_sample_time.argtypes = [i32p, C.c_int, C.c_int, C.c_float, C.c_float, fp, cfgp, vp, vp, C.c_int,
+                                             C.POINTER(C.c_double)]
     L.l2z_transformer_batch.argtypes = [C.c_int, i32p, i32p, cfgp, C.POINTER(vp), vp]
     L.l2z_argmax_batch.argtypes = [C.c_int, C.POINTER(vp), i32p]
     L.l2z_batch_time.argtypes = [C.c_int, i32p, i32p, cfgp, C.POINTER(vp), vp, C.c_int, C.POINTER(C.c_double)]
@@ -360,6 +364,34 @@ class RunState:
                                    C.byref(ms)))
         return ms.value
 
+    def verify_sample(self, tokens, pos0: int, w: Weights, temperature: float, top_p: float, coins):
+        """l2z_verify_sample: verify() with next[i] drawn as sample_batch draws it from row i's logits with
+        (temperature, top_p, coins[i]); coins[i] is the coin of position pos0 + i (None: NULL, for temperature 0).
+        Returns (next: int32[n], accepted) as verify()."""
+        t = np.ascontiguousarray(tokens, np.int32)
+        c = None if coins is None else np.ascontiguousarray(coins, np.float32)
+        if c is not None and c.size < t.size:
+            raise ValueError(f"{c.size} coins for {t.size} rows")
+        nxt = np.zeros(max(t.size, 1), np.int32)
+        a = C.c_int(0)
+        i32p = C.POINTER(C.c_int32)
+        _chk(lib().l2z_verify_sample(t.ctypes.data_as(i32p), t.size, pos0, C.c_float(temperature), C.c_float(top_p),
+                                     None if c is None else _fp(c), C.byref(self.cfg), self.h, w.h,
+                                     nxt.ctypes.data_as(i32p), C.byref(a)))
+        return nxt[: t.size].copy(), a.value
+
+    def verify_sample_time(self, tokens, pos0: int, w: Weights, temperature: float, top_p: float, coins, iters: int) -> float:
+        """l2z_verify_sample_time: milliseconds per sampled verify pass, device events over `iters` passes."""
+        t = np.ascontiguousarray(tokens, np.int32)
+        c = None if coins is None else np.ascontiguousarray(coins, np.float32)
+        if c is not None and c.size < t.size:
+            raise ValueError(f"{c.size} coins for {t.size} rows")
+        ms = C.c_double(0.0)
+        _chk(lib().l2z_verify_sample_time(t.ctypes.data_as(C.POINTER(C.c_int32)), t.size, pos0, C.c_float(temperature),
+                                          C.c_float(top_p), None if c is None else _fp(c), C.byref(self.cfg), self.h, w.h,
+                                          iters, C.byref(ms)))
+        return ms.value
+
     def argmax(self) -> int:
         t = C.c_int(0)
         _chk(lib().l2z_argmax(self.h, C.byref(t)))
@@ -528,6 +560,8 @@ def host_lib():
         H = C.CDLL(HOST_LIB_PATH)
         H.l2zh_lookup_draft.argtypes = [C.POINTER(C.c_int32), C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int32)]
         H.l2zh_lookup_draft.restype = C.c_size_t
+        H.l2zh_prng_floats.argtypes = [C.c_uint64, C.POINTER(C.c_float), C.c_size_t]
+        H.l2zh_prng_floats.restype = None
         _host = H
     return _host
 
@@ -584,6 +618,66 @@ def speculate_greedy(s: RunState, w: Weights, prompt, n_steps: int, k: int, draf
                 break
             alive = emit(t)
             stats["emitted"] += 1
+            pos += alive
+    return np.array(out, np.int32), stats
+
+
+def coin_stream(seed: int, n: int) -> np.ndarray:
+    """The first n next_f32() of the CLI's Prng(seed) (l2zh_prng_floats): the coins of `llama2 -s seed`, one per
+    generated token in generation order."""
+    out = np.zeros(max(int(n), 1), np.float32)
+    host_lib().l2zh_prng_floats(C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _fp(out), int(n))
+    return out[: int(n)].copy()
+
+
+def speculate_sample(s: RunState, w: Weights, prompt, n_steps: int, k: int, temperature: float, top_p: float, coins,
+                     drafter=None):
+    """The loop of `llama2 --spec-sample k`: speculate_greedy's loop and return convention with every generated token
+    DRAWN (RunState.verify_sample).  coins[g] is the coin of the g-th generated token whatever call draws it: the first
+    comes from the prefill's logits by sample_batch([s], ...) with coins[0]; a call at generated index g passes
+    coins[g : g + 1 + len(guesses)]; a position behind a rejected guess is drawn again by the next call with the same
+    coin.  The drafter must not look at the coins.  The ids do not depend on k or on the drafter (COIN INVARIANCE).
+    ValueError if `coins` is too short for n_steps."""
+    if not 0 <= k <= BATCH_MAX - 1:
+        raise ValueError(f"k = {k} outside [0, {BATCH_MAX - 1}]")
+    if drafter is None:
+        drafter = lookup_draft
+    coins = np.ascontiguousarray(coins, np.float32).reshape(-1)
+    seq_len = s.cfg.seq_len
+    steps = seq_len if n_steps == 0 else max(1, min(int(n_steps), seq_len))
+    prompt = [int(t) for t in prompt][:steps]
+    if coins.size < steps - len(prompt):
+        raise ValueError(f"{coins.size} coins for {steps - len(prompt)} generated positions")
+    hist, out = [1], []
+    stats = {"calls": 0, "offered": 0, "accepted": 0, "emitted": 0}
+
+    def emit(t):
+        out.append(int(t))
+        hist.append(int(t))
+        return int(t) != 1
+
+    alive, pos, g = True, 0, 0  # g: generated tokens so far = the index of the next coin
+    while alive and pos < len(prompt):
+        alive = emit(prompt[pos])
+        pos += alive
+    if alive and pos < steps:
+        s.prefill(np.array(hist, np.int32), 0, w)
+        alive = emit(sample_batch([s], temperature, top_p, coins[0])[0])
+        g += 1
+        pos += alive
+    while alive and pos < steps:
+        kk = min(k, steps - pos - 1)
+        guesses = [int(t) for t in drafter(np.array(hist, np.int32), kk)][:kk] if kk > 0 else []
+        nxt, a = s.verify_sample([hist[-1]] + guesses, pos, w, temperature, top_p, coins[g: g + 1 + len(guesses)])
+        stats["calls"] += 1
+        stats["offered"] += len(guesses)
+        stats["accepted"] += a
+        for t in nxt[: a + 1]:
+            if not (alive and pos < steps):
+                break
+            alive = emit(t)
+            stats["emitted"] += 1
+            g += 1
             pos += alive
     return np.array(out, np.int32), stats
 

@@ -108,5 +108,9 @@ hipError_t launch_verify_combine(const VerifyAttnArgs &a, int n, hipStream_t st)
 // out[n] = a; row a of the logits matrix is copied to dst (the runstate's logits).  Two launches.
 hipError_t launch_verify_accept(const BatchTable *tab, const float *logits, int vocab, int *out, float *dst, int n,
                                 hipStream_t st);
+// The second of those launches alone, for next ids that already stand in out[0 .. n): l2z_verify_sample's rows are drawn
+// by launch_sample_batch (tab->logits[i] = logits + i * vocab, out = the same out) before it.
+hipError_t launch_verify_accept_ids(const BatchTable *tab, const float *logits, int vocab, int *out, float *dst, int n,
+                                    hipStream_t st);
 
 }  // namespace l2z

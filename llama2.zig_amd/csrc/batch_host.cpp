@@ -517,26 +517,38 @@ int verify_alloc(l2z_runstate *s)
     return L2Z_OK;
 }
 
+// How a sampled pass draws its rows (l2z_verify_sample): row i is l2z_sample_batch's draw from z_i with coins[i]
+struct VerifyDraw {
+    float temperature, top_p;
+    const float *coins;
+};
+
 // l2z_verify's checks (a refusal enqueues nothing), then the table, the pass, the verdict and its copy back on s's
-// stream; no sync
-int verify_enqueue(const int32_t *tokens, int n, int pos0, const l2z_config *config, l2z_runstate *s, const l2z_weights *w)
+// stream; no sync.  draw == nullptr: the greedy verdict; else the rows' ids are sample_batch_kernel's (temperature > 0).
+int verify_enqueue(const char *fn, const int32_t *tokens, int n, int pos0, const l2z_config *config, l2z_runstate *s,
+                   const l2z_weights *w, const VerifyDraw *draw = nullptr)
 {
     L2Z_TRY(no_device_check());
-    L2Z_CHECK(tokens != nullptr && config != nullptr && s != nullptr && w != nullptr, L2Z_ERR_INVALID,
-              "l2z_verify: null argument");
-    L2Z_CHECK(n >= 1 && n <= kBatchMax, L2Z_ERR_INVALID, "l2z_verify: n_tokens = %d outside [1, %d]", n, kBatchMax);
-    L2Z_CHECK(s->comm == nullptr && s->sh.world == 1, L2Z_ERR_INVALID, "l2z_verify: the runstate is a shard");
+    L2Z_CHECK(tokens != nullptr && config != nullptr && s != nullptr && w != nullptr, L2Z_ERR_INVALID, "%s: null argument",
+              fn);
+    L2Z_CHECK(n >= 1 && n <= kBatchMax, L2Z_ERR_INVALID, "%s: n_tokens = %d outside [1, %d]", fn, n, kBatchMax);
+    L2Z_CHECK(s->comm == nullptr && s->sh.world == 1, L2Z_ERR_INVALID, "%s: the runstate is a shard", fn);
     L2Z_TRY(check_pair(config, s, w));
     L2Z_TRY(prefill_check(config, s));
-    L2Z_CHECK(s->sh.hs <= 256, L2Z_ERR_INVALID, "l2z_verify: head_size above 256");
-    L2Z_CHECK(pos0 >= 0 && pos0 <= config->seq_len - n, L2Z_ERR_STATE, "l2z_verify: positions %d .. %d outside [0, %d)", pos0,
+    L2Z_CHECK(s->sh.hs <= 256, L2Z_ERR_INVALID, "%s: head_size above 256", fn);
+    L2Z_CHECK(pos0 >= 0 && pos0 <= config->seq_len - n, L2Z_ERR_STATE, "%s: positions %d .. %d outside [0, %d)", fn, pos0,
               pos0 + n - 1, config->seq_len);
     for (int i = 0; i < n; i++)
-        L2Z_CHECK(tokens[i] >= 0 && tokens[i] < config->vocab_size, L2Z_ERR_STATE, "l2z_verify: tokens[%d] = %d out of vocabulary",
+        L2Z_CHECK(tokens[i] >= 0 && tokens[i] < config->vocab_size, L2Z_ERR_STATE, "%s: tokens[%d] = %d out of vocabulary", fn,
                   i, tokens[i]);
+    if (draw != nullptr)  // l2z_sample_batch's rules
+        for (int i = 0; i < n; i++)
+            L2Z_CHECK(draw->coins[i] >= 0.0f && draw->coins[i] < 1.0f, L2Z_ERR_INVALID, "%s: coins[%d] = %g outside [0, 1)", fn,
+                      i, (double)draw->coins[i]);
     L2Z_HIP(hipSetDevice(s->device));
     L2Z_TRY(batch_alloc(s));
     L2Z_TRY(verify_alloc(s));
+    if (draw != nullptr) L2Z_TRY(sample_alloc(s));
     BatchScratch *b = s->bt;
     BatchTable t = {};
     for (int i = 0; i < n; i++) {
@@ -545,15 +557,42 @@ int verify_enqueue(const int32_t *tokens, int n, int pos0, const l2z_config *con
         t.kc[i] = s->key_cache;
         t.vc[i] = s->value_cache;
         t.logits[i] = b->v_logits + (size_t)i * config->vocab_size;
+        if (draw != nullptr) {
+            t.temperature[i] = draw->temperature;
+            t.top_p[i] = draw->top_p;
+            t.coin[i] = draw->coins[i];
+        }
     }
     hipStream_t st = s->stream;
     L2Z_TRY(upload_table(b, t, st));
     L2Z_TRY(batch_step(n, *config, s, w, b, pos0));
-    L2Z_HIP(launch_verify_accept(b->d_tab, b->v_logits, config->vocab_size, b->d_vout, s->logits, n, st));
+    if (draw != nullptr) {  // the rows' draws by l2z_sample_batch's kernel, then the accept scan over them
+        SampleArgs a = {};
+        a.tab = b->d_tab; a.scratch = b->smp; a.row_stride = b->smp_stride; a.vocab = config->vocab_size;
+        a.out = b->d_vout;
+        L2Z_HIP(launch_sample_batch(a, n, st));
+        L2Z_HIP(launch_verify_accept_ids(b->d_tab, b->v_logits, config->vocab_size, b->d_vout, s->logits, n, st));
+    } else {
+        L2Z_HIP(launch_verify_accept(b->d_tab, b->v_logits, config->vocab_size, b->d_vout, s->logits, n, st));
+    }
     L2Z_HIP(hipMemcpyAsync(b->h_vout, b->d_vout, (size_t)(n + 1) * 4, hipMemcpyDeviceToHost, st));
     b->v_rows = n;
     s->n_part = 0;  // l2z_argmax scans the logits the verdict copied
     s->logits_partial = false;
+    return L2Z_OK;
+}
+
+// l2z_verify_sample's own argument rules (before verify_enqueue's, which queue nothing either); *draw: what to pass on,
+// nullptr at temperature 0 (the greedy verdict, l2z_verify's launches)
+int verify_sample_args(float temperature, float top_p, const float *coins, VerifyDraw *store, const VerifyDraw **draw)
+{
+    L2Z_CHECK(std::isfinite(temperature) && temperature >= 0.0f, L2Z_ERR_INVALID,
+              "l2z_verify_sample: temperature = %g (finite, >= 0)", (double)temperature);
+    L2Z_CHECK(top_p >= 0.0f && top_p <= 1.0f, L2Z_ERR_INVALID, "l2z_verify_sample: top_p = %g outside [0, 1]", (double)top_p);
+    L2Z_CHECK(temperature == 0.0f || coins != nullptr, L2Z_ERR_INVALID,
+              "l2z_verify_sample: coins is NULL at temperature %g", (double)temperature);
+    *store = VerifyDraw{temperature, top_p, coins};
+    *draw = temperature == 0.0f ? nullptr : store;
     return L2Z_OK;
 }
 
@@ -565,7 +604,25 @@ extern "C" int l2z_verify(const int32_t *tokens, int n_tokens, int pos0, const l
 {
     L2Z_TRY(no_device_check());
     L2Z_CHECK(out_next != nullptr && out_accepted != nullptr, L2Z_ERR_INVALID, "l2z_verify: null argument");
-    L2Z_TRY(verify_enqueue(tokens, n_tokens, pos0, config, s, w));
+    L2Z_TRY(verify_enqueue("l2z_verify", tokens, n_tokens, pos0, config, s, w));
+    BatchScratch *b = s->bt;
+    L2Z_HIP(hipStreamSynchronize(s->stream));
+    memcpy(out_next, b->h_vout, (size_t)n_tokens * 4);
+    *out_accepted = b->h_vout[n_tokens];
+    s->host_pos = pos0 + *out_accepted + 1;
+    return L2Z_OK;
+}
+
+extern "C" int l2z_verify_sample(const int32_t *tokens, int n_tokens, int pos0, float temperature, float top_p,
+                                 const float *coins, const l2z_config *config, l2z_runstate *s, const l2z_weights *w,
+                                 int32_t *out_next, int *out_accepted)
+{
+    L2Z_TRY(no_device_check());
+    L2Z_CHECK(out_next != nullptr && out_accepted != nullptr, L2Z_ERR_INVALID, "l2z_verify_sample: null argument");
+    VerifyDraw store;
+    const VerifyDraw *draw = nullptr;
+    L2Z_TRY(verify_sample_args(temperature, top_p, coins, &store, &draw));
+    L2Z_TRY(verify_enqueue("l2z_verify_sample", tokens, n_tokens, pos0, config, s, w, draw));
     BatchScratch *b = s->bt;
     L2Z_HIP(hipStreamSynchronize(s->stream));
     memcpy(out_next, b->h_vout, (size_t)n_tokens * 4);
@@ -603,7 +660,38 @@ extern "C" int l2z_verify_time(const int32_t *tokens, int n_tokens, int pos0, co
     L2Z_HIP(hipEventCreate(&e1));
     int rc = L2Z_OK;
     if (hipEventRecord(e0, st) != hipSuccess) rc = L2Z_ERR_HIP;
-    for (int i = 0; i < iters && rc == L2Z_OK; i++) rc = verify_enqueue(tokens, n_tokens, pos0, config, s, w);
+    for (int i = 0; i < iters && rc == L2Z_OK; i++) rc = verify_enqueue("l2z_verify", tokens, n_tokens, pos0, config, s, w);
+    float ms = 0.0f;
+    if (rc == L2Z_OK && (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
+                         hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
+        rc = L2Z_ERR_HIP;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (rc == L2Z_OK) *out_ms = ms / iters;
+    return rc;
+}
+
+// Testing support: l2z_verify_time for a sampled pass (scripts/verify_sample_bench.py): one l2z_verify_sample call, then
+// `iters` passes back to back with the rows' draws, the accept scan and the copy included, no sync.
+extern "C" int l2z_verify_sample_time(const int32_t *tokens, int n_tokens, int pos0, float temperature, float top_p,
+                                      const float *coins, const l2z_config *config, l2z_runstate *s, const l2z_weights *w,
+                                      int iters, double *out_ms)
+{
+    L2Z_CHECK(iters >= 1 && out_ms != nullptr, L2Z_ERR_INVALID, "l2z_verify_sample_time: bad arguments");
+    int32_t next[kBatchMax];
+    int acc = 0;
+    L2Z_TRY(l2z_verify_sample(tokens, n_tokens, pos0, temperature, top_p, coins, config, s, w, next, &acc));
+    VerifyDraw store;
+    const VerifyDraw *draw = nullptr;
+    L2Z_TRY(verify_sample_args(temperature, top_p, coins, &store, &draw));
+    hipStream_t st = s->stream;
+    hipEvent_t e0, e1;
+    L2Z_HIP(hipEventCreate(&e0));
+    L2Z_HIP(hipEventCreate(&e1));
+    int rc = L2Z_OK;
+    if (hipEventRecord(e0, st) != hipSuccess) rc = L2Z_ERR_HIP;
+    for (int i = 0; i < iters && rc == L2Z_OK; i++)
+        rc = verify_enqueue("l2z_verify_sample", tokens, n_tokens, pos0, config, s, w, draw);
     float ms = 0.0f;
     if (rc == L2Z_OK && (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
                          hipEventElapsedTime(&ms, e0, e1) != hipSuccess))

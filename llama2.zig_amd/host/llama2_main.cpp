@@ -8,6 +8,8 @@
 //          [--score]     (extension: no generation -- the log-prob of every prompt token and the perplexity: run_score)
 //          [--spec K]    (extension, -t 0 only: speculative greedy decoding -- up to K tokens guessed by prompt lookup are
 //                         verified per sweep of the weights by l2z_verify; the text does not depend on K: run_spec)
+//          [--spec-sample K]  (extension: the same under the run's -t / -p / -s by l2z_verify_sample: a guess is accepted
+//                         when it is the token the sampler draws with that position's own random number: run_spec)
 //
 // At -t 0 the whole generation loop runs on the device (l2z_greedy_run) and the host
 // only prints; otherwise one l2z_transformer + l2z_logits_read per position feeds the
@@ -53,7 +55,11 @@ static const char *usage_text =
     " --spec <int>              (extension) speculative greedy decoding, needs -t 0: guess up to this many tokens (0-15) by\n"
     "                           looking the last tokens up in the text so far, verify them in one pass; the text is the same\n"
     "                           for every value.  A pass of one token costs ~1.25x a plain -t 0 step, so it pays on text that\n"
-    "                           repeats its context; not with -b, -g or --score\n";
+    "                           repeats its context; not with -b, -g or --score\n"
+    " --spec-sample <int>       (extension) speculative decoding under the sampler (-t, -p, -s as given): guess up to this\n"
+    "                           many tokens (0-15) as --spec does; a guess is accepted when it is the token the sampler\n"
+    "                           draws with that position's own random number, so the text is the same for every value and\n"
+    "                           its law is the plain sampler's.  At -t 0 it is --spec; not with --spec, -b, -g or --score\n";
 
 static bool verbose = false;
 #define LOGV(...)                                 \
@@ -289,9 +295,24 @@ static int run_score(const l2z_config &cfg, const l2z_weights *w, l2z_runstate *
 // generated token l2z_argmax; then every call feeds the last token and up to K guesses (lookup_draft over everything emitted
 // so far) and emits the 1 + accepted tokens it returns.  Steps without a guess, and K = 0, still go through l2z_verify with
 // one row: the ids must not depend on the drafter, and l2z_transformer's bits differ from a verify row's at near-ties.
+// --spec-sample K (draw != nullptr): the same loop over l2z_verify_sample with the run's temperature and top_p.  Generated
+// token g is drawn with coin g of Prng(seed), whatever call draws it: the coins are taken from the generator lazily, in
+// generation order, and KEPT -- a coin drawn for a row behind a rejected guess is the coin of that position in the next
+// call.  The first generated token is l2z_sample_batch's draw from the prefill's logits with coin 0.  At -t 0 no coin is
+// drawn and the calls are --spec's.
+struct SpecDraw {
+    float temperature, top_p;
+    Prng *rng;
+};
 static int run_spec(int K, const l2z_config &cfg, const l2z_weights *w, l2z_runstate *s, const Tokenizer &tok,
-                    const std::vector<int32_t> &prompt, size_t seq_len, bool dump_tokens)
+                    const std::vector<int32_t> &prompt, size_t seq_len, bool dump_tokens, const SpecDraw *draw = nullptr)
 {
+    const bool sampled = draw != nullptr && draw->temperature != 0.0f;
+    std::vector<float> coins;  // coins[g]: generated token g's
+    size_t gen = 0;            // generated tokens so far
+    auto coins_upto = [&](size_t n) {
+        while (coins.size() < n) coins.push_back(draw->rng->next_f32());
+    };
     std::vector<int32_t> hist{1}, produced;  // hist: the sequence as the model reads it (BOS first)
     size_t token = 1, pos = 0;
     bool timer_started = false;
@@ -326,8 +347,16 @@ static int run_spec(int K, const l2z_config &cfg, const l2z_weights *w, l2z_runs
     if (alive && pos < seq_len) {
         if (l2z_prefill(hist.data(), (int)hist.size(), 0, &cfg, s, w) != L2Z_OK) return die("prefill");
         int first = 0;
-        if (l2z_argmax(s, &first) != L2Z_OK) return die("argmax");
+        if (sampled) {
+            coins_upto(1);
+            int32_t t = 0;
+            if (l2z_sample_batch(1, &s, &draw->temperature, &draw->top_p, coins.data(), &t) != L2Z_OK) return die("sample_batch");
+            first = t;
+        } else if (l2z_argmax(s, &first) != L2Z_OK) {
+            return die("argmax");
+        }
         alive = emit((size_t)first);
+        gen++;
         if (alive) pos++;
     }
     int32_t in[L2Z_BATCH_MAX], next[L2Z_BATCH_MAX];
@@ -337,11 +366,19 @@ static int run_spec(int K, const l2z_config &cfg, const l2z_weights *w, l2z_runs
         const int k = (int)std::min<size_t>((size_t)K, room);
         const int nd = (int)lookup_draft(hist.data(), hist.size(), 3, k, in + 1);
         int a = 0;
-        if (l2z_verify(in, 1 + nd, (int)pos, &cfg, s, w, next, &a) != L2Z_OK) return die("verify");
+        if (draw != nullptr) {
+            if (sampled) coins_upto(gen + 1 + (size_t)nd);
+            if (l2z_verify_sample(in, 1 + nd, (int)pos, draw->temperature, draw->top_p, sampled ? coins.data() + gen : nullptr,
+                                  &cfg, s, w, next, &a) != L2Z_OK)
+                return die("verify_sample");
+        } else if (l2z_verify(in, 1 + nd, (int)pos, &cfg, s, w, next, &a) != L2Z_OK) {
+            return die("verify");
+        }
         calls++; offered += nd; accepted += a;
         for (int i = 0; i <= a && alive && pos < seq_len; i++) {
             alive = emit((size_t)next[i]);
             from_calls++;
+            gen++;
             if (alive) pos++;
         }
     }
@@ -350,8 +387,8 @@ static int run_spec(int K, const l2z_config &cfg, const l2z_weights *w, l2z_runs
         const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         LOGV("\n\n%u tokens per second\n", (unsigned)(pos >= 1 && el > 0.0 ? (double)(pos - 1) / el : 0.0));
     }
-    LOGV("spec: %ld verify calls, %.2f tokens per call, %ld guesses offered, %ld accepted\n", calls,
-         calls ? (double)from_calls / (double)calls : 0.0, offered, accepted);
+    LOGV("%s: %ld verify calls, %.2f tokens per call, %ld guesses offered, %ld accepted\n",
+         draw != nullptr ? "spec-sample" : "spec", calls, calls ? (double)from_calls / (double)calls : 0.0, offered, accepted);
     if (dump_tokens) {
         fprintf(stderr, "tokens:");
         for (int32_t t : produced) fprintf(stderr, " %d", t);
@@ -372,7 +409,7 @@ int main(int argc, char **argv)
     size_t seq_len = 0;
     std::string tokenizer_path = "tokenizer.bin";
     bool dump_tokens = false, score = false;
-    int n_gpus = 1, n_batch = 1, spec = -1;
+    int n_gpus = 1, n_batch = 1, spec = -1, spec_sample = -1;
     uint64_t seed = (uint64_t)std::chrono::system_clock::now().time_since_epoch().count();
     Prng prng(seed);  // :844-845
 
@@ -450,6 +487,15 @@ int main(int argc, char **argv)
                 return 1;
             }
             spec = (int)k;
+        } else if (a == "--spec-sample") {
+            const char *v = need(i, "spec-sample");
+            char *end = nullptr;
+            const long k = strtol(v, &end, 10);
+            if (end == v || *end || k < 0 || k > L2Z_BATCH_MAX - 1) {
+                fprintf(stderr, "unable to use --spec-sample argument '%s' (0 to %d)\n", v, L2Z_BATCH_MAX - 1);
+                return 1;
+            }
+            spec_sample = (int)k;
         } else if (a == "-g" || a == "--gpus") {
             n_gpus = atoi(need(i, "gpus"));
             if (n_gpus < 1 || n_gpus > 16) {
@@ -484,13 +530,24 @@ int main(int argc, char **argv)
                 n_batch > 1 ? "--batch" : "--gpus");
         return 1;
     }
+    if (spec_sample >= 0 && (spec >= 0 || score || n_batch > 1 || n_gpus > 1)) {
+        fprintf(stderr, "error: --spec-sample does not combine with %s: one sequence on one GPU is decoded per run%s\n",
+                spec >= 0 ? "--spec" : score ? "--score" : n_batch > 1 ? "--batch" : "--gpus",
+                spec >= 0 ? ", by one of the two loops" : "");
+        return 1;
+    }
+    if (spec_sample >= 0 && !(std::isfinite(temperature) && temperature >= 0.0f)) {
+        fprintf(stderr, "error: --spec-sample needs a temperature that is finite and >= 0 (it is %g)\n", temperature);
+        return 1;
+    }
     if (spec >= 0 && (score || n_batch > 1 || n_gpus > 1)) {
         fprintf(stderr, "error: --spec does not combine with %s: one sequence on one GPU is decoded per run\n",
                 score ? "--score" : n_batch > 1 ? "--batch" : "--gpus");
         return 1;
     }
     if (spec >= 0 && temperature != 0.0f) {
-        fprintf(stderr, "error: --spec is greedy decoding only: add -t 0 (the temperature is %g)\n", temperature);
+        fprintf(stderr, "error: --spec is greedy decoding only: add -t 0 (the temperature is %g), or use --spec-sample\n",
+                temperature);
         return 1;
     }
 
@@ -649,8 +706,10 @@ int main(int argc, char **argv)
     seq_len = seq_len == 0 ? (size_t)cfg.seq_len : seq_len;                        // :992
     seq_len = seq_len < 1 ? 1 : (seq_len > (size_t)cfg.seq_len ? (size_t)cfg.seq_len : seq_len);  // :993
 
-    if (spec >= 0) {
-        const int rc = run_spec(spec, cfg, w, s, tok, prompt, seq_len, dump_tokens);
+    if (spec >= 0 || spec_sample >= 0) {
+        const SpecDraw draw = {temperature, top_p, &prng};
+        const int rc = run_spec(spec >= 0 ? spec : spec_sample, cfg, w, s, tok, prompt, seq_len, dump_tokens,
+                                spec_sample >= 0 ? &draw : nullptr);
         l2z_runstate_free(s);
         l2z_weights_free(w);
         return finish(rc);
