@@ -212,6 +212,36 @@ int l2z_verify_sample_time(const int32_t *tokens, int n_tokens, int pos0, float 
                            const float *coins, const l2z_config *config, l2z_runstate *s, const l2z_weights *w, int iters,
                            double *out_ms);
 
+/* ---- preview entry points ----
+ * Public through the Python binding, exported by libllama2_hip_test.so only: not part of ABI version 2 (include/llama2_hip.h
+ * and its 31 functions are unchanged).  Promotion into the product header, the Zig shim and the CLI (llama2 -b N with one
+ * prompt per line) belongs to the change that cuts ABI version 3. */
+
+/* Ragged batched prefill: the prompts of n sequences, one runstate each, in ONE pass -- every weight matrix streamed once per
+ * chunk of the concatenated rows instead of once per sequence (what l2z_transformer_batch is to l2z_transformer, for
+ * l2z_prefill).  Sequence j contributes n_tokens[j] consecutive positions starting at pos0[j]; tokens = the sequences'
+ * tokens concatenated in order (the sum of n_tokens[] entries).
+ * For every j the call leaves the state l2z_prefill(tokens_j, n_tokens[j], pos0[j], config, states[j], w) leaves: KV rows
+ * pos0[j] .. pos0[j] + n_tokens[j] - 1 of every layer of states[j] written -- and NO other cache row of any runstate --
+ * and states[j]'s logits those of its last position, so l2z_argmax, l2z_logits_read, l2z_probs_read, l2z_sample_batch,
+ * l2z_transformer_batch, l2z_verify and l2z_runstate_fork go on from there.  Values agree with l2z_prefill's up to summation
+ * order (the fp32 parity bar), not bit for bit: the GEMM form follows the chunk's TOTAL row count and the attention kernel
+ * is another one.
+ * The concatenated rows are cut into chunks by l2z_prefill's plan applied to the total (L2Z_PF_CHUNK as there); a sequence
+ * may straddle a chunk boundary, and pos0[j] > 0 continues a sequence (after l2z_runstate_fork, or an earlier call).
+ * Neighbour invariance: for a fixed layout -- the same n, n_tokens[], pos0[], order and chunking -- sequence j's KV rows
+ * and logits are bit-identical whatever tokens the other sequences hold and whatever their caches contain, and from run to
+ * run.  Nothing more is promised: the other sequences' LENGTHS matter, because the total row count selects the kernel form.
+ * The prefill scratch is states[0]'s (freed with it).  The pass runs on states[0]'s stream after everything queued on every
+ * runstate's stream, and every runstate's stream waits for it (l2z_transformer_batch's rule; no device-wide sync); like
+ * l2z_prefill the call returns once its work has completed.
+ * A refusal enqueues nothing and changes no state.  L2Z_ERR_INVALID: a NULL argument, n outside [1, L2Z_BATCH_MAX], an
+ * n_tokens[j] < 1, runstates that are not pairwise distinct, unsharded, on one device and made with *config, weights of
+ * another config, dims l2z_prefill refuses.  L2Z_ERR_STATE: pos0[j] < 0, pos0[j] + n_tokens[j] > seq_len, a token outside
+ * the vocabulary.  L2Z_ERR_NO_DEVICE without a device. */
+int l2z_prefill_batch(int n, const int32_t *tokens, const int32_t *n_tokens, const int32_t *pos0,
+                      const l2z_config *config, l2z_runstate *const *states, const l2z_weights *w);
+
 #ifdef __cplusplus
 }
 #endif

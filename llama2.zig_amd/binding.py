@@ -103,6 +103,8 @@ def lib():
     L.l2z_batch_time.argtypes = [C.c_int, i32p, i32p, cfgp, C.POINTER(vp), vp, C.c_int, C.POINTER(C.c_double)]
     L.l2z_sample_batch.argtypes = [C.c_int, C.POINTER(vp), fp, fp, fp, i32p]
     L.l2z_runstate_fork.argtypes = [vp, vp, C.c_int]
+    if hasattr(L, "l2z_prefill_batch"):
+        L.l2z_prefill_batch.argtypes = [C.c_int, i32p, i32p, i32p, cfgp, C.POINTER(vp), vp]
     L.l2z_logits_write.argtypes = [vp, fp]
     L.l2z_sample_time.argtypes = [C.c_int, C.POINTER(vp), fp, fp, fp, C.c_int, C.POINTER(C.c_double)]
     L.l2z_greedy_begin.argtypes = [vp, i32p, C.c_int]
@@ -540,6 +542,24 @@ def sample_time(states, temperature, top_p, coins, iters: int) -> float:
     ms = C.c_double(0.0)
     _chk(lib().l2z_sample_time(n, ss, _fp(t), _fp(p), _fp(c), iters, C.byref(ms)))
     return ms.value
+
+
+def prefill_batch(states, token_lists, pos0s, w: Weights) -> None:
+    """l2z_prefill_batch: prefill(token_lists[j], pos0s[j]) on states[j] for every j, ONE pass over the concatenated rows
+    (a preview entry point of the test library: include/llama2_hip_test.h).  pos0s: one int per sequence, or a scalar."""
+    n = len(states)
+    ss = (C.c_void_p * max(n, 1))(*[s.h for s in states])
+    lists = [np.ascontiguousarray(t, np.int32).reshape(-1) for t in token_lists]
+    assert len(lists) == n, "one token list per runstate"
+    nt = np.zeros(max(n, 1), np.int32)
+    nt[:n] = [t.size for t in lists]
+    p0 = np.zeros(max(n, 1), np.int32)
+    p0[:n] = np.broadcast_to(np.asarray(pos0s, np.int32), (n,)) if n else []
+    t = np.ascontiguousarray(np.concatenate(lists + [np.zeros(1, np.int32)]), np.int32)  # (never empty)
+    cfg = states[0].cfg if n else L2ZConfig()
+    i32p = C.POINTER(C.c_int32)
+    _chk(lib().l2z_prefill_batch(n, t.ctypes.data_as(i32p), nt.ctypes.data_as(i32p), p0.ctypes.data_as(i32p),
+                                 C.byref(cfg), ss, w.h))
 
 
 def runstate_fork(dst: RunState, src: RunState, n_pos: int) -> None:

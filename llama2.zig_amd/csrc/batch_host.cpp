@@ -230,6 +230,17 @@ int batch_step(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *
 }
 
 }  // namespace
+
+// the same rules for the batched prompt pass (prefill_batch_host.cpp)
+int batch_no_device_check() { return no_device_check(); }
+int batch_check_states(const char *fn, int n, l2z_runstate *const *states, const l2z_config *c) { return check_states(fn, n, states, c); }
+int batch_join_streams(int n, l2z_runstate *const *states)
+{
+    L2Z_TRY(batch_alloc(states[0]));
+    return join_streams(states[0]->bt, n, states);
+}
+int batch_release_streams(int n, l2z_runstate *const *states) { return release_streams(states[0]->bt, n, states); }
+
 }  // namespace l2z
 
 using namespace l2z;

@@ -309,6 +309,35 @@ hipError_t launch_prefill_attention(const float *q, int ldq, const float *kcache
                                     int form = 0,            // tests: 1 block per (head, query), 2 tiled, 3 flash; 0 by shape
                                     void *x3 = nullptr, int kp = 0,   // != null: out's planes of bf16 terms too (x3[token][3][kp]) ...
                                     bool *planes_written = nullptr);  // ... if the form that ran writes them (the flash form does)
+// ---- prefill_ragged.hip: a chunk whose rows belong to SEVERAL sequences (l2z_prefill_batch; prefill_batch_host.cpp) ----
+constexpr int kRaggedMaxSeq = 16;   // L2Z_BATCH_MAX
+struct RaggedSeq {     // one sequence's rows of a chunk
+    float *kc, *vc;    // its runstate's key / value caches (layer 0): [layer][kv head][seq_len][head_size]
+    int row0, rows;    // its first row in the chunk, how many
+    int pos0;          // position of row0
+    int pad;
+};
+// The table of one chunk (device pointers; built on the host and uploaded with the tokens).  tiles: the flash attention's
+// blocks -- .x the sequence slot, .y the first of its (up to 64) queries as a row of that sequence's segment --, the
+// ones with the most key rows first.
+struct RaggedChunk {
+    const RaggedSeq *seq;   // [n_seq]
+    const int *row_seq;     // [P] slot of each row
+    const int *row_pos;     // [P] position of each row
+    const int2 *tiles;      // [n_tiles]
+    int n_seq, n_tiles;
+    float *k, *v;           // scratch: the chunk's key / value rows [P, kv_dim] between the product and the scatter
+};
+// q [P, dim] rotated in place, k rotated, and k / v stored into row row_pos[r] of sequence row_seq[r]'s caches: the
+// arithmetic of the q | k | v product's own epilogue (prefill_gemm.hip), one launch
+hipError_t launch_ragged_rope_scatter(float *q, int ldq, const RaggedChunk &rg, int P, int dim, int kv_dim, int head_size,
+                                      const float2 *rope, size_t layer_off, size_t kv_head_stride, hipStream_t st);
+// causal attention of every row over rows 0 .. row_pos[r] of its OWN sequence's cache, one launch: the MFMA flash form at
+// head sizes 64 and 128 (one block per (tile, head)), else one block per (head, row) with the decode kernel's arithmetic.
+// x3 / kp / planes_written: as launch_prefill_attention.  A function of the shape and the table only.
+hipError_t launch_ragged_attention(const float *q, int ldq, float *out, int ldo, const RaggedChunk &rg, int P, int n_heads,
+                                   int head_size, size_t layer_off, size_t kv_head_stride, int kv_mul, int seq_len,
+                                   hipStream_t st, void *x3 = nullptr, int kp = 0, bool *planes_written = nullptr);
 // ---- prefill_panel.hip: chunks of <= 32 tokens of matrices that stream from HBM (K ranges with a resident X panel) ----
 enum PanelEpi { PANEL_STORE = 0, PANEL_RESID = 1, PANEL_SWIGLU = 2, PANEL_QKV = 3 };
 struct PanelProduct {

@@ -155,6 +155,11 @@ struct l2z_runstate {
     bool packed_w = true;          // L2Z_PACKED_W at creation: decode mat-vecs stream the weights' packed copy where it exists
     int tl_attn_seq = 0;           // attention launches enqueued so far (AttnArgs::tl_seq, measurement builds)
     l2z::BatchScratch *bt = nullptr;  // batched decode scratch of the calls that name this runstate first (batch_host.cpp)
+    // l2z_prefill_batch scratch of the calls that name this runstate first (prefill_batch_host.cpp): a chunk's key / value
+    // rows [rg_cap, kv_dim] between their product and the scatter into the sequences' caches, and the chunk's table
+    float *rg_k = nullptr, *rg_v = nullptr;
+    void *rg_tab = nullptr;
+    int rg_cap = 0;
 };
 
 namespace l2z {
@@ -183,7 +188,19 @@ struct ScoreCall;  // prefill_host.cpp: what an l2z_score call adds to every chu
 int prefill_tokens(l2z_runstate *s, const l2z_weights *w, const int32_t *tokens, int n_tokens, int pos0,
                    const ScoreCall *score = nullptr);
 
+// ... what l2z_prefill_batch shares with l2z_prefill (prefill_batch_host.cpp): the chunk scratch, one chunk's layers with
+// the rows' sequences given by the table (every stage but q | k | v + attention is l2z_prefill's own), the classifier launch
+int prefill_scratch(l2z_runstate *s, int need);
+int prefill_ragged_chunk(l2z_runstate *s, const l2z_weights *w, const int32_t *tokens, int P, const RaggedChunk &rg);
+int prefill_last_logits(l2z_runstate *s, const l2z_weights *w);
+
 // batch_host.cpp
 void batch_free(l2z_runstate *s);
+// the rules the batched calls share: the runstates of one call (check_states), and the pass on states[0]'s stream ordered
+// against every runstate's own stream (join before, release after)
+int batch_no_device_check();
+int batch_check_states(const char *fn, int n, l2z_runstate *const *states, const l2z_config *c);
+int batch_join_streams(int n, l2z_runstate *const *states);      // (allocates states[0]'s batch scratch: the events)
+int batch_release_streams(int n, l2z_runstate *const *states);
 
 }  // namespace l2z

@@ -123,7 +123,9 @@ StageOut stage_out(const l2z_runstate *s, int k)
 // The launches of stage k of layer l.  One rank: straight into the destination matrix.  Sharded: this
 // rank's [P, n_loc] block, contiguous, at pf_stage + rank * P * n_loc; the exchange and the unpack
 // into the destination follow (comm_bulk_allgather, or the emulated-rank driver's copies).
-int prefill_stage(l2z_runstate *s, const l2z_weights *w, int l, int k, int P, int pos0)
+// rg != null (l2z_prefill_batch): the rows belong to several sequences, which only the q | k | v epilogue and the attention
+// see (below); pos0 is not read.
+int prefill_stage(l2z_runstate *s, const l2z_weights *w, int l, int k, int P, int pos0, const RaggedChunk *rg = nullptr)
 {
     const l2z_config &c = s->cfg;
     const Shard &sh = s->sh;
@@ -193,7 +195,27 @@ int prefill_stage(l2z_runstate *s, const l2z_weights *w, int l, int k, int P, in
     // Wo / W2 may leave their K ranges' sums to the rmsnorm launch that reads the residual stream next (the unsharded pass; W2
     // of the last layer finishes itself: the classifier reads x)
     const bool may_defer = !sharded && tunables().pf_fuse_planes != 0;
-    if (k == PF_ATT) {
+    if (k == PF_ATT && rg != nullptr) {
+        // Rows of several sequences: the three products with the plain-store epilogue into scratch (the forms of the
+        // whole model's q | k | v launch at this chunk length, as where the single-sequence pass launches them apart),
+        // then ONE launch that rotates q and k at each row's own position and stores k / v into each row's own caches,
+        // then ONE attention launch in which a row sees its own sequence's cache only (prefill_ragged.hip).
+        L2Z_CHECK(!sharded, L2Z_ERR_INVALID, "batched prefill: rows of several sequences on a shard");
+        const long long n_qkv = (long long)dim + 2 * kvd_whole;
+        const size_t layer_off = (size_t)l * c.seq_len * kvd;
+        L2Z_HIP(launch_prefill_gemm(PG_STORE, s->pf_xn, ldxn, w->wq + (size_t)l * dim * dim, s->pf_q, dim, P, dim, dim, 0,
+                                    s->rope, hs, st, nullptr, 0, 1, 0, sk_qkv, ws, 0, n_qkv, xn_planes));
+        L2Z_HIP(launch_prefill_gemm(PG_STORE, s->pf_xn, ldxn, w->wk + (size_t)l * kvd * dim, rg->k, kvd, P, kvd, dim, 0,
+                                    s->rope, hs, st, nullptr, 0, 1, 0, sk_qkv, ws, 0, n_qkv, PLANES_READY));   // (q's planes stand)
+        L2Z_HIP(launch_prefill_gemm(PG_STORE, s->pf_xn, ldxn, w->wv + (size_t)l * kvd * dim, rg->v, kvd, P, kvd, dim, 0,
+                                    s->rope, hs, st, nullptr, 0, 1, 0, sk_qkv, ws, 0, n_qkv, PLANES_READY));
+        L2Z_HIP(launch_ragged_rope_scatter(s->pf_q, dim, *rg, P, dim, kvd, hs, s->rope, layer_off, kvh_stride, st));
+        bool att_planes = false;
+        const bool want = planes_for(dim, dim, sk_wo);
+        L2Z_HIP(launch_ragged_attention(s->pf_q, dim, out, ldo, *rg, P, c.n_heads, hs, layer_off, kvh_stride,
+                                        c.n_heads / c.n_kv_heads, c.seq_len, st, want ? ws->x3 : nullptr, dim, &att_planes));
+        s->pf_planes_att = att_planes ? PLANES_READY : PLANES_SPLIT;
+    } else if (k == PF_ATT) {
         {
             PanelProduct pp = {};
             pp.x = s->pf_xn; pp.ldx = ldxn; pp.K = dim;
@@ -413,6 +435,17 @@ int prefill_classifier(l2z_runstate *s, const l2z_weights *w)
 }  // namespace
 
 namespace l2z {
+int prefill_scratch(l2z_runstate *s, int need) { return prefill_alloc(s, need); }
+int prefill_last_logits(l2z_runstate *s, const l2z_weights *w) { return prefill_classifier(s, w); }
+// one chunk of l2z_prefill_batch (an unsharded runstate): prefill_chunk's launches, the rows' sequences by the table
+int prefill_ragged_chunk(l2z_runstate *s, const l2z_weights *w, const int32_t *tokens, int P, const RaggedChunk &rg)
+{
+    L2Z_TRY(prefill_begin_chunk(s, w, tokens, P));
+    for (int l = 0; l < s->cfg.n_layers; l++)
+        for (int k = 0; k < PF_STAGES; k++) L2Z_TRY(prefill_stage(s, w, l, k, P, 0, &rg));
+    return L2Z_OK;
+}
+
 // device arrays of one l2z_score call, element 0 = the call's first token (null: not asked for)
 struct ScoreCall {
     const int *d_targets;
