@@ -254,7 +254,8 @@ int l2z_runstate_fork(l2z_runstate *dst, const l2z_runstate *src, int n_pos);
  * pos0 + n_tokens > seq_len, a token outside the vocabulary; L2Z_ERR_NO_DEVICE without a device.
  * Scratch (on the runstate's first call, freed with it): the batched step's activation rows, L2Z_BATCH_MAX x vocab_size
  * floats of logits, the attention partials.
- * OUT OF SCOPE: several sequences per call, sharded runstates, hipGraph replay of the pass (its grid depends on pos0). */
+ * OUT OF SCOPE: several sequences per call (the preview entry point l2z_verify_batch of llama2_hip_test.h does that, with
+ * this call's bits per sequence), sharded runstates, hipGraph replay of the pass (its grid depends on pos0). */
 int l2z_verify(const int32_t *tokens, int n_tokens, int pos0, const l2z_config *config, l2z_runstate *s,
                const l2z_weights *w, int32_t *out_next, int *out_accepted);
 /* ---- speculative decoding under the sampler: l2z_verify with every row DRAWN instead of arg-maxed ----

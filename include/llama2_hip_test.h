@@ -199,7 +199,8 @@ int l2z_sample_time(int n, l2z_runstate *const *states, const float *temperature
  * the next l2z_score call.  The outputs do not depend on it, bit for bit: that is what the tests use it for. */
 int l2z_score_slab_set(l2z_runstate *s, int slab_cols);
 /* Row `row` (0 .. n_tokens - 1) of the logits matrix of this runstate's last l2z_verify or l2z_verify_sample call: every z_i, not only the
- * accepted z_a the runstate keeps (vocab_size floats).  L2Z_ERR_STATE when there is no such row.  Synchronous. */
+ * accepted z_a the runstate keeps (vocab_size floats).  L2Z_ERR_STATE when there is no such row.  Synchronous.  After
+ * l2z_verify_batch the matrix is states[0]'s: row r of the concatenated rows; the call's other runstates have no row. */
 int l2z_verify_logits_read(l2z_runstate *s, int row, float *out);
 /* Measurement (scripts/verify_bench.py): one l2z_verify call, then `iters` passes back to back (verdict launches and
  * their copy included, no sync), timed by device events on the runstate's stream; *out_ms = milliseconds per pass.  The
@@ -241,6 +242,37 @@ int l2z_verify_sample_time(const int32_t *tokens, int n_tokens, int pos0, float 
  * the vocabulary.  L2Z_ERR_NO_DEVICE without a device. */
 int l2z_prefill_batch(int n, const int32_t *tokens, const int32_t *n_tokens, const int32_t *pos0,
                       const l2z_config *config, l2z_runstate *const *states, const l2z_weights *w);
+
+/* Batched speculative decoding: the verify pass of l2z_verify / l2z_verify_sample for n sequences, one runstate each, in ONE
+ * sweep of the weights.  Sequence j contributes n_tokens[j] consecutive positions from pos0[j]: its first token is known, the
+ * rest are guesses.  tokens, coins and out_next are the sequences' rows concatenated in order: R = the sum of n_tokens[] rows,
+ * R <= L2Z_BATCH_MAX; out_accepted has n entries.
+ * temperature == NULL: every sequence is greedy; top_p and coins are ignored and may be NULL.  Otherwise temperature[j] and
+ * top_p[j] are per sequence and coins is per row; a sequence with temperature[j] == 0 is arg-maxed (its coins are not read).
+ * THE DEFINING PROPERTY: for every j the outputs and the state left in states[j] are bit-identical to what the
+ * single-sequence call leaves on the same state -- l2z_verify(tokens_j, n_tokens[j], pos0[j], config, states[j], w, ...), or
+ * l2z_verify_sample with temperature[j], top_p[j] and coins_j -- whatever n is, whatever the other sequences hold, and in any
+ * order of the sequences within the call.  Outputs and state: out_next_j and out_accepted[j]; KV rows pos0[j] ..
+ * pos0[j] + n_tokens[j] - 1 of every layer; the runstate's logits (z_a); the next position pos0[j] + a_j + 1.  (DRAFT
+ * INVARIANCE and BATCH INVARIANCE of include/llama2_hip.h, extended: the products take one kernel form whatever the row count,
+ * and the attention's orders depend on head_size, the segment and the row's position alone.)  No cache row outside a
+ * sequence's own pos0[j] .. pos0[j] + n_tokens[j] - 1 is written, in any runstate.
+ * With one row per sequence the call is a batched decode step on the position-split attention; its bits are l2z_verify's,
+ * not l2z_transformer_batch's.
+ * The pass runs on states[0]'s stream after everything queued on every runstate's stream, and every runstate's stream waits
+ * for it (l2z_transformer_batch's rule); the scratch is states[0]'s; the call is synchronous as l2z_verify is (one copy back,
+ * one sync).  Afterwards l2z_verify_logits_read(states[0], r, ...) returns concatenated row r; on states[j], j > 0, it
+ * refuses with L2Z_ERR_STATE until that runstate's next call of its own.
+ * A refusal enqueues nothing and changes no state.  L2Z_ERR_INVALID: a NULL required argument, n outside [1, L2Z_BATCH_MAX],
+ * an n_tokens[j] < 1, R > L2Z_BATCH_MAX, runstates that are not pairwise distinct, unsharded, on one device and made with
+ * *config, weights of another config, dims l2z_verify refuses, a temperature[j] that is not finite and >= 0, a top_p[j]
+ * outside [0, 1] (or top_p == NULL beside temperature), coins == NULL with any temperature[j] > 0, a coin of such a sequence
+ * outside [0, 1).  L2Z_ERR_STATE: pos0[j] < 0, pos0[j] + n_tokens[j] > seq_len, a token outside the vocabulary.
+ * L2Z_ERR_NO_DEVICE without a device. */
+int l2z_verify_batch(int n, const int32_t *tokens, const int32_t *n_tokens, const int32_t *pos0,
+                     const float *temperature, const float *top_p, const float *coins,
+                     const l2z_config *config, l2z_runstate *const *states, const l2z_weights *w,
+                     int32_t *out_next, int32_t *out_accepted);
 
 #ifdef __cplusplus
 }

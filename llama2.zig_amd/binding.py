@@ -105,6 +105,8 @@ def lib():
     L.l2z_runstate_fork.argtypes = [vp, vp, C.c_int]
     if hasattr(L, "l2z_prefill_batch"):
         L.l2z_prefill_batch.argtypes = [C.c_int, i32p, i32p, i32p, cfgp, C.POINTER(vp), vp]
+    if hasattr(L, "l2z_verify_batch"):
+        L.l2z_verify_batch.argtypes = [C.c_int, i32p, i32p, i32p, fp, fp, fp, cfgp, C.POINTER(vp), vp, i32p, i32p]
     L.l2z_logits_write.argtypes = [vp, fp]
     L.l2z_sample_time.argtypes = [C.c_int, C.POINTER(vp), fp, fp, fp, C.c_int, C.POINTER(C.c_double)]
     L.l2z_greedy_begin.argtypes = [vp, i32p, C.c_int]
@@ -562,6 +564,52 @@ def prefill_batch(states, token_lists, pos0s, w: Weights) -> None:
                                  C.byref(cfg), ss, w.h))
 
 
+def verify_batch(states, token_lists, pos0s, w: Weights, temperature=None, top_p=None, coin_lists=None):
+    """l2z_verify_batch: RunState.verify(token_lists[j], pos0s[j]) on states[j] for every j in ONE sweep of the weights, bit
+    for bit (a preview entry point of the test library: include/llama2_hip_test.h).  temperature=None: greedy; otherwise
+    temperature and top_p are one value per sequence (or a scalar for all) and coin_lists[j] holds a coin per row of
+    sequence j (None, or a None entry, where the temperature is 0): RunState.verify_sample per sequence.
+    Returns (list of next arrays, accepted array).  states[0].verify_logits(r) then reads concatenated row r."""
+    n = len(states)
+    ss = (C.c_void_p * max(n, 1))(*[s.h for s in states])
+    lists = [np.ascontiguousarray(t, np.int32).reshape(-1) for t in token_lists]
+    assert len(lists) == n, "one token list per runstate"
+    nt = np.zeros(max(n, 1), np.int32)
+    nt[:n] = [t.size for t in lists]
+    p0 = np.zeros(max(n, 1), np.int32)
+    p0[:n] = np.broadcast_to(np.asarray(pos0s, np.int32), (n,)) if n else []
+    t = np.ascontiguousarray(np.concatenate(lists + [np.zeros(1, np.int32)]), np.int32)  # (never empty)
+    rows = int(nt[:n].sum())
+    tp = pp = cp = None
+    if temperature is not None:
+        tp, pp = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float32)
+        tp[:n] = np.broadcast_to(np.asarray(temperature, np.float32), (n,)) if n else []
+        pp[:n] = np.broadcast_to(np.asarray(1.0 if top_p is None else top_p, np.float32), (n,)) if n else []
+        if coin_lists is not None:
+            assert len(coin_lists) == n, "one coin list per runstate"
+            cp = np.zeros(rows + 1, np.float32)
+            r = 0
+            for j, c in enumerate(coin_lists):
+                if c is not None:
+                    c = np.ascontiguousarray(c, np.float32).reshape(-1)
+                    if c.size < lists[j].size:
+                        raise ValueError(f"sequence {j}: {c.size} coins for {lists[j].size} rows")
+                    cp[r: r + lists[j].size] = c[: lists[j].size]
+                elif tp[j] > 0:
+                    raise ValueError(f"sequence {j}: no coins at temperature {tp[j]}")
+                r += lists[j].size
+    nxt = np.zeros(rows + 1, np.int32)
+    acc = np.zeros(max(n, 1), np.int32)
+    cfg = states[0].cfg if n else L2ZConfig()
+    i32p = C.POINTER(C.c_int32)
+    _chk(lib().l2z_verify_batch(n, t.ctypes.data_as(i32p), nt.ctypes.data_as(i32p), p0.ctypes.data_as(i32p),
+                                None if tp is None else _fp(tp), None if pp is None else _fp(pp),
+                                None if cp is None else _fp(cp), C.byref(cfg), ss, w.h, nxt.ctypes.data_as(i32p),
+                                acc.ctypes.data_as(i32p)))
+    ends = np.cumsum(nt[:n])
+    return [nxt[e - m: e].copy() for e, m in zip(ends, nt[:n])], acc[:n].copy()
+
+
 def runstate_fork(dst: RunState, src: RunState, n_pos: int) -> None:
     """l2z_runstate_fork: dst takes src's KV rows 0 .. n_pos-1 and its logits; dst's next position is n_pos."""
     _chk(lib().l2z_runstate_fork(dst.h, src.h, n_pos))
@@ -700,6 +748,95 @@ def speculate_sample(s: RunState, w: Weights, prompt, n_steps: int, k: int, temp
             g += 1
             pos += alive
     return np.array(out, np.int32), stats
+
+
+def speculate_batch(states, w: Weights, prompts, n_steps: int, k: int, drafter=None, *, temperature=None, top_p=None,
+                    coins=None, batched_prefill=True):
+    """speculate_greedy's loop (temperature=None) or speculate_sample's for len(states) sequences at once: every round ONE
+    verify_batch call advances all the sequences still running, each with min(k + 1, 16 // live) rows -- its last token and
+    the drafter's guesses.  A sequence that emits BOS or reaches n_steps drops out.  Sampled mode: temperature and top_p are
+    one value per sequence or a scalar, coins[j] is sequence j's coin stream indexed by generated token as in
+    speculate_sample.  The prompts go through prefill_batch (batched_prefill=True: values agree with RunState.prefill's up
+    to summation order) or through RunState.prefill per sequence (False: every sequence's ids are then speculate_greedy's /
+    speculate_sample's on a fresh runstate, bit for bit, whatever the other sequences are).
+    Returns (list of token arrays, stats): per sequence the return convention of speculate_greedy; stats is per call:
+    speculate_greedy's keys plus "rows" (rows of all verify_batch calls) and "rows_per_call" (a list)."""
+    if not 0 <= k <= BATCH_MAX - 1:
+        raise ValueError(f"k = {k} outside [0, {BATCH_MAX - 1}]")
+    n = len(states)
+    if not 1 <= n <= BATCH_MAX or len(prompts) != n:
+        raise ValueError(f"{n} runstates and {len(prompts)} prompts (1 .. {BATCH_MAX}, one prompt each)")
+    if drafter is None:
+        drafter = lookup_draft
+    sampled = temperature is not None
+    seq_len = states[0].cfg.seq_len
+    steps = seq_len if n_steps == 0 else max(1, min(int(n_steps), seq_len))
+    prompts = [[int(t) for t in p][:steps] for p in prompts]
+    if sampled:
+        temps = np.broadcast_to(np.asarray(temperature, np.float32), (n,))
+        tops = np.broadcast_to(np.asarray(1.0 if top_p is None else top_p, np.float32), (n,))
+        if coins is None or len(coins) != n:
+            raise ValueError("sampled mode takes one coin stream per sequence")
+        coins = [np.ascontiguousarray(c, np.float32).reshape(-1) for c in coins]
+        for j in range(n):
+            if coins[j].size < steps - len(prompts[j]):
+                raise ValueError(f"sequence {j}: {coins[j].size} coins for {steps - len(prompts[j])} generated positions")
+    hist, out = [[1] for _ in range(n)], [[] for _ in range(n)]
+    alive, pos, gen = [True] * n, [0] * n, [0] * n  # gen: generated tokens so far = the index of the next coin
+    stats = {"calls": 0, "offered": 0, "accepted": 0, "emitted": 0, "rows": 0, "rows_per_call": []}
+
+    def emit(j, t):
+        out[j].append(int(t))
+        hist[j].append(int(t))
+        alive[j] = int(t) != 1
+        pos[j] += alive[j]
+
+    for j in range(n):
+        while alive[j] and pos[j] < len(prompts[j]):
+            emit(j, prompts[j][pos[j]])
+    first = [j for j in range(n) if alive[j] and pos[j] < steps]
+    if first:
+        if batched_prefill:
+            prefill_batch([states[j] for j in first], [np.array(hist[j], np.int32) for j in first], 0, w)
+        else:
+            for j in first:
+                states[j].prefill(np.array(hist[j], np.int32), 0, w)
+        if sampled:
+            ids = sample_batch([states[j] for j in first], temps[first], tops[first], [coins[j][0] for j in first])
+        else:
+            ids = argmax_batch([states[j] for j in first])
+        for j, t in zip(first, ids):
+            emit(j, t)
+            gen[j] += 1
+    while True:
+        live = [j for j in range(n) if alive[j] and pos[j] < steps]
+        if not live:
+            break
+        rows_each = min(k + 1, BATCH_MAX // len(live))
+        lists, clists = [], []
+        for j in live:
+            kk = min(rows_each - 1, steps - pos[j] - 1)
+            guesses = [int(g) for g in drafter(np.array(hist[j], np.int32), kk)][:kk] if kk > 0 else []
+            lists.append([hist[j][-1]] + guesses)
+            if sampled:
+                clists.append(coins[j][gen[j]: gen[j] + 1 + len(guesses)])
+            stats["offered"] += len(guesses)
+        if sampled:
+            nxts, accs = verify_batch([states[j] for j in live], lists, [pos[j] for j in live], w, temps[live], tops[live], clists)
+        else:
+            nxts, accs = verify_batch([states[j] for j in live], lists, [pos[j] for j in live], w)
+        stats["calls"] += 1
+        stats["rows"] += sum(len(t) for t in lists)
+        stats["rows_per_call"].append(sum(len(t) for t in lists))
+        for j, nxt, a in zip(live, nxts, accs):
+            stats["accepted"] += int(a)
+            for t in nxt[: int(a) + 1]:
+                if not (alive[j] and pos[j] < steps):
+                    break
+                emit(j, t)
+                stats["emitted"] += 1
+                gen[j] += 1
+    return [np.array(o, np.int32) for o in out], stats
 
 
 def emu_transformer(states, weights, token: int, pos: int) -> None:

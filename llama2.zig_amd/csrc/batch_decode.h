@@ -113,4 +113,38 @@ hipError_t launch_verify_accept(const BatchTable *tab, const float *logits, int 
 hipError_t launch_verify_accept_ids(const BatchTable *tab, const float *logits, int vocab, int *out, float *dst, int n,
                                     hipStream_t st);
 
+// l2z_verify_batch (verify_batch.hip): the rows of a step are GROUPS of consecutive positions, one group per sequence --
+// group j is rows first[j] .. first[j] + count[j] - 1 at positions pos0[j] .. of the sequence whose caches are kc[j] /
+// vc[j] (layer 0's bases) and whose runstate logits are dst[j].  Uploaded behind the step's BatchTable in the same copy.
+struct VerifyGroupTable {
+    int32_t first[kBatchMax], count[kBatchMax], pos0[kBatchMax];
+    float *kc[kBatchMax];
+    float *vc[kBatchMax];
+    float *dst[kBatchMax];
+};
+// Attention of every group in one launch per layer: block (head, segment, group) runs verify_attention_kernel's body
+// (verify_device.h) on the group's rows and the group's cache, so a row's partials are the bits l2z_verify leaves for
+// it.  The grid is (n_heads, max_segments, n_groups), max_segments = the deepest group's segment count; a block past
+// its own group's last segment returns at once.  Partials are indexed by the row's place in the step (part_o / part_ml
+// of VerifyAttnArgs); the combine takes a row's segment count from tab->pos[row].
+struct VerifyBatchAttnArgs {
+    const float *q;  // [rows, ldq], RoPE applied
+    float *out;      // [rows, ldo]
+    float *part_o, *part_ml;
+    const BatchTable *tab;
+    const VerifyGroupTable *groups;
+    size_t layer_off;  // floats per layer of a cache
+    size_t kv_head_stride;
+    int ldq, ldo, n_heads, kv_mul, head_size, seg_cap;
+};
+hipError_t launch_verify_batch_attention(const VerifyBatchAttnArgs &a, int n_groups, int max_segments, hipStream_t st);
+hipError_t launch_verify_batch_combine(const VerifyBatchAttnArgs &a, int n_rows, hipStream_t st);
+// The verdict per group: group j's accept length a_j over its own rows (tab->tokens against out[0 .. n_rows), the rows'
+// next ids) -> out[n_rows + j]; row first[j] + a_j of the logits matrix -> groups->dst[j].  One launch.
+// launch_verify_batch_argmax fills out[0 .. n_rows) for a greedy pass (block_argmax_1024, as launch_verify_accept's
+// first launch); a sampled pass has launch_sample_batch fill it.
+hipError_t launch_verify_batch_argmax(const float *logits, int vocab, int *out, int n_rows, hipStream_t st);
+hipError_t launch_verify_batch_accept(const BatchTable *tab, const VerifyGroupTable *groups, const float *logits, int vocab,
+                                      int *out, int n_rows, int n_groups, hipStream_t st);
+
 }  // namespace l2z

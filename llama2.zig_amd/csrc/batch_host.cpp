@@ -3,7 +3,9 @@
 // GEMM forms with per-row epilogues (prefill_skinny.hip, G_*_ROWS) and batch_decode.hip.  Also what a batch of samples
 // needs around the step: the on-device sampler l2z_sample_batch (sample_batch.hip) and the prompt copy
 // l2z_runstate_fork.  And l2z_verify: the same step with the rows being consecutive positions of ONE sequence
-// (speculative greedy decoding), attention and verdict by verify.hip.
+// (speculative greedy decoding), attention and verdict by verify.hip.  And l2z_verify_batch: that pass for the rows of
+// several sequences at once, attention and verdict per sequence by verify_batch.hip.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -22,6 +24,7 @@ struct BatchScratch {
     float *x = nullptr, *xn = nullptr, *q = nullptr, *att = nullptr, *h1 = nullptr, *scores = nullptr;
     int ld_xn = 0, ld_att = 0, ld_h1 = 0;
     BatchTable *d_tab = nullptr, *h_tab = nullptr;
+    VerifyGroupTable *d_groups = nullptr, *h_groups = nullptr;  // l2z_verify_batch: behind the table, in the same allocations
     int *d_tokens_out = nullptr, *h_tokens_out = nullptr;
     hipEvent_t ev_in[kBatchMax] = {};
     hipEvent_t ev_done = nullptr;
@@ -31,7 +34,7 @@ struct BatchScratch {
     // l2z_verify (on the runstate's first call): the [kBatchMax, vocab] logits matrix, the attention partials
     // ([kBatchMax, n_heads, v_seg_cap, head_size] and [..., 2]), next[0 .. n) | accepted on the device and pinned
     float *v_logits = nullptr, *v_part_o = nullptr, *v_part_ml = nullptr;
-    int *d_vout = nullptr, *h_vout = nullptr;
+    int *d_vout = nullptr, *h_vout = nullptr;  // 2 * kBatchMax ints (l2z_verify_batch: next[0 .. rows) | accepted[0 .. n))
     int v_seg_cap = 0, v_rows = 0;   // v_rows: rows of the last call (l2z_verify_logits_read)
 };
 
@@ -76,7 +79,7 @@ int batch_alloc(l2z_runstate *s)
         {(void **)&b->x, R * c.dim * 4}, {(void **)&b->xn, R * b->ld_xn * 4}, {(void **)&b->q, R * c.dim * 4},
         {(void **)&b->att, R * b->ld_att * 4}, {(void **)&b->h1, R * b->ld_h1 * 4},
         {(void **)&b->scores, R * (size_t)c.n_heads * c.seq_len * 4},
-        {(void **)&b->d_tab, sizeof(BatchTable)}, {(void **)&b->d_tokens_out, R * 4}};
+        {(void **)&b->d_tab, sizeof(BatchTable) + sizeof(VerifyGroupTable)}, {(void **)&b->d_tokens_out, R * 4}};
     for (auto &w : want) {
         const hipError_t e = hipMalloc(w.p, w.bytes);
         if (e != hipSuccess) {
@@ -85,7 +88,9 @@ int batch_alloc(l2z_runstate *s)
             return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
         }
     }
-    L2Z_HIP(hipHostMalloc((void **)&b->h_tab, sizeof(BatchTable), hipHostMallocDefault));
+    L2Z_HIP(hipHostMalloc((void **)&b->h_tab, sizeof(BatchTable) + sizeof(VerifyGroupTable), hipHostMallocDefault));
+    b->d_groups = (VerifyGroupTable *)(b->d_tab + 1);
+    b->h_groups = (VerifyGroupTable *)(b->h_tab + 1);
     L2Z_HIP(hipHostMalloc((void **)&b->h_tokens_out, R * 4, hipHostMallocDefault));
     for (hipEvent_t &e : b->ev_in) L2Z_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     L2Z_HIP(hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
@@ -154,6 +159,18 @@ int upload_table(BatchScratch *b, const BatchTable &t, hipStream_t st)
     return L2Z_OK;
 }
 
+// ... and the row groups of an l2z_verify_batch call behind it, still one copy
+int upload_tables(BatchScratch *b, const BatchTable &t, const VerifyGroupTable &g, hipStream_t st)
+{
+    static_assert(sizeof(BatchTable) % alignof(VerifyGroupTable) == 0, "the group table sits right behind the step's table");
+    L2Z_HIP(hipEventSynchronize(b->ev_upload));
+    memcpy(b->h_tab, &t, sizeof t);
+    memcpy(b->h_groups, &g, sizeof g);
+    L2Z_HIP(hipMemcpyAsync(b->d_tab, b->h_tab, sizeof t + sizeof g, hipMemcpyHostToDevice, st));
+    L2Z_HIP(hipEventRecord(b->ev_upload, st));
+    return L2Z_OK;
+}
+
 GemmArgs gemm(const float *x, int ldx, const float *w, int ldw, int N, int K, int P)
 {
     GemmArgs a = {};
@@ -165,7 +182,10 @@ GemmArgs gemm(const float *x, int ldx, const float *w, int ldw, int N, int K, in
 // is (launch_batch_skinny): a row's bits do not depend on n, on the other rows, or on its place in the batch.
 // verify_pos0 >= 0 (l2z_verify): the rows are positions verify_pos0 .. of s0's own sequence, and attention is the
 // multi-query position-split form over s0's cache (verify.hip) instead of one block per (head, row).
-int batch_step(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *w, BatchScratch *b, int verify_pos0 = -1)
+// vb_groups > 0 (l2z_verify_batch): the rows are the groups of b->d_groups, each on its own sequence's cache; attention is
+// that form per group in one launch (verify_batch.hip), vb_segments = the deepest group's segment count.
+int batch_step(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *w, BatchScratch *b, int verify_pos0 = -1,
+               int vb_groups = 0, int vb_segments = 0)
 {
     hipStream_t st = s0->stream;
     const int dim = c.dim, hid = c.hidden_dim, hs = dim / c.n_heads, kvd = hs * c.n_kv_heads;
@@ -186,7 +206,14 @@ int batch_step(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *
             a.row_pos = tab->pos; a.row_kc = tab->kc; a.row_vc = tab->vc; a.layer_off = layer_off;
             L2Z_HIP(launch_batch_skinny(G_QKV_ROWS, a, st));
         }
-        if (verify_pos0 >= 0) {  // :361-389, flash form
+        if (vb_groups > 0) {  // :361-389, flash form per group
+            VerifyBatchAttnArgs a = {};
+            a.q = b->q; a.ldq = dim; a.out = b->att; a.ldo = b->ld_att; a.part_o = b->v_part_o; a.part_ml = b->v_part_ml;
+            a.tab = tab; a.groups = b->d_groups; a.layer_off = layer_off; a.kv_head_stride = (size_t)c.seq_len * hs;
+            a.n_heads = c.n_heads; a.kv_mul = c.n_heads / c.n_kv_heads; a.head_size = hs; a.seg_cap = b->v_seg_cap;
+            L2Z_HIP(launch_verify_batch_attention(a, vb_groups, vb_segments, st));
+            L2Z_HIP(launch_verify_batch_combine(a, n, st));
+        } else if (verify_pos0 >= 0) {  // :361-389, flash form
             VerifyAttnArgs a = {};
             a.q = b->q; a.ldq = dim; a.out = b->att; a.ldo = b->ld_att; a.part_o = b->v_part_o; a.part_ml = b->v_part_ml;
             a.kc = s0->key_cache + layer_off; a.vc = s0->value_cache + layer_off;
@@ -513,7 +540,7 @@ int verify_alloc(l2z_runstate *s)
         {(void **)&b->v_logits, R * (size_t)c.vocab_size * 4},
         {(void **)&b->v_part_o, R * c.n_heads * segs * hs * 4},
         {(void **)&b->v_part_ml, R * c.n_heads * segs * 2 * 4},
-        {(void **)&b->d_vout, (R + 1) * 4}};
+        {(void **)&b->d_vout, 2 * R * 4}};
     for (auto &w : want) {
         if (*w.p != nullptr) continue;
         const hipError_t e = hipMalloc(w.p, w.bytes);
@@ -523,7 +550,7 @@ int verify_alloc(l2z_runstate *s)
             return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
         }
     }
-    if (b->h_vout == nullptr) L2Z_HIP(hipHostMalloc((void **)&b->h_vout, (R + 1) * 4, hipHostMallocDefault));
+    if (b->h_vout == nullptr) L2Z_HIP(hipHostMalloc((void **)&b->h_vout, 2 * R * 4, hipHostMallocDefault));
     b->v_seg_cap = (int)segs;
     return L2Z_OK;
 }
@@ -639,6 +666,109 @@ extern "C" int l2z_verify_sample(const int32_t *tokens, int n_tokens, int pos0, 
     memcpy(out_next, b->h_vout, (size_t)n_tokens * 4);
     *out_accepted = b->h_vout[n_tokens];
     s->host_pos = pos0 + *out_accepted + 1;
+    return L2Z_OK;
+}
+
+// ---- l2z_verify_batch: the verify pass for the rows of several sequences in one sweep (include/llama2_hip_test.h) ----
+extern "C" int l2z_verify_batch(int n, const int32_t *tokens, const int32_t *n_tokens, const int32_t *pos0,
+                                const float *temperature, const float *top_p, const float *coins, const l2z_config *config,
+                                l2z_runstate *const *states, const l2z_weights *w, int32_t *out_next, int32_t *out_accepted)
+{
+    const char *fn = "l2z_verify_batch";
+    // ---- checks: a refusal enqueues nothing and changes no state ----
+    L2Z_TRY(no_device_check());
+    L2Z_CHECK(tokens != nullptr && n_tokens != nullptr && pos0 != nullptr && config != nullptr && w != nullptr &&
+                  out_next != nullptr && out_accepted != nullptr,
+              L2Z_ERR_INVALID, "%s: null argument", fn);
+    L2Z_TRY(check_states(fn, n, states, config));
+    int R = 0;
+    for (int j = 0; j < n; j++) {
+        L2Z_CHECK(n_tokens[j] >= 1 && n_tokens[j] <= kBatchMax, L2Z_ERR_INVALID, "%s: n_tokens[%d] = %d outside [1, %d]", fn, j,
+                  n_tokens[j], kBatchMax);
+        R += n_tokens[j];
+    }
+    L2Z_CHECK(R <= kBatchMax, L2Z_ERR_INVALID, "%s: %d rows in all, above %d", fn, R, kBatchMax);
+    for (int j = 0; j < n; j++) L2Z_TRY(check_pair(config, states[j], w));
+    L2Z_TRY(prefill_check(config, states[0]));
+    L2Z_CHECK(states[0]->sh.hs <= 256, L2Z_ERR_INVALID, "%s: head_size above 256", fn);
+    bool sampled = false;  // any sequence at temperature > 0: the rows' ids are sample_batch_kernel's
+    if (temperature != nullptr) {  // l2z_verify_sample's rules, per sequence
+        L2Z_CHECK(top_p != nullptr, L2Z_ERR_INVALID, "%s: top_p is NULL beside a temperature array", fn);
+        for (int j = 0, r = 0; j < n; r += n_tokens[j], j++) {
+            L2Z_CHECK(std::isfinite(temperature[j]) && temperature[j] >= 0.0f, L2Z_ERR_INVALID,
+                      "%s: temperature[%d] = %g (finite, >= 0)", fn, j, (double)temperature[j]);
+            L2Z_CHECK(top_p[j] >= 0.0f && top_p[j] <= 1.0f, L2Z_ERR_INVALID, "%s: top_p[%d] = %g outside [0, 1]", fn, j,
+                      (double)top_p[j]);
+            if (temperature[j] == 0.0f) continue;
+            sampled = true;
+            L2Z_CHECK(coins != nullptr, L2Z_ERR_INVALID, "%s: coins is NULL at temperature[%d] = %g", fn, j, (double)temperature[j]);
+            for (int i = 0; i < n_tokens[j]; i++)
+                L2Z_CHECK(coins[r + i] >= 0.0f && coins[r + i] < 1.0f, L2Z_ERR_INVALID, "%s: coins[%d] = %g outside [0, 1)", fn,
+                          r + i, (double)coins[r + i]);
+        }
+    }
+    for (int j = 0, r = 0; j < n; r += n_tokens[j], j++) {
+        L2Z_CHECK(pos0[j] >= 0 && pos0[j] <= config->seq_len - n_tokens[j], L2Z_ERR_STATE,
+                  "%s: sequence %d: positions %d .. %lld outside [0, %d)", fn, j, pos0[j], (long long)pos0[j] + n_tokens[j] - 1,
+                  config->seq_len);
+        for (int i = 0; i < n_tokens[j]; i++)
+            L2Z_CHECK(tokens[r + i] >= 0 && tokens[r + i] < config->vocab_size, L2Z_ERR_STATE,
+                      "%s: sequence %d: tokens[%d] = %d out of vocabulary", fn, j, i, tokens[r + i]);
+    }
+    l2z_runstate *s0 = states[0];
+    L2Z_HIP(hipSetDevice(s0->device));
+    L2Z_TRY(batch_alloc(s0));
+    L2Z_TRY(verify_alloc(s0));
+    if (sampled) L2Z_TRY(sample_alloc(s0));
+    BatchScratch *b = s0->bt;
+    // ---- the step's table (a row per position) and the row groups (one per sequence) ----
+    BatchTable t = {};
+    VerifyGroupTable g = {};
+    int segments = 1;
+    for (int j = 0, r = 0; j < n; r += n_tokens[j], j++) {
+        g.first[j] = r; g.count[j] = n_tokens[j]; g.pos0[j] = pos0[j];
+        g.kc[j] = states[j]->key_cache; g.vc[j] = states[j]->value_cache; g.dst[j] = states[j]->logits;
+        segments = std::max(segments, (pos0[j] + n_tokens[j] - 1) / kVerifySeg + 1);
+        for (int i = 0; i < n_tokens[j]; i++) {
+            t.tokens[r + i] = tokens[r + i];
+            t.pos[r + i] = pos0[j] + i;
+            t.kc[r + i] = states[j]->key_cache;
+            t.vc[r + i] = states[j]->value_cache;
+            t.logits[r + i] = b->v_logits + (size_t)(r + i) * config->vocab_size;
+            if (sampled) {  // a temperature-0 sequence's rows are arg-maxed by the sampler's kernel: no coin is read
+                t.temperature[r + i] = temperature[j];
+                t.top_p[r + i] = top_p[j];
+                t.coin[r + i] = temperature[j] > 0.0f ? coins[r + i] : 0.0f;
+            }
+        }
+    }
+    hipStream_t st = s0->stream;
+    L2Z_TRY(join_streams(b, n, states));
+    L2Z_TRY(upload_tables(b, t, g, st));
+    L2Z_TRY(batch_step(R, *config, s0, w, b, -1, n, segments));
+    if (sampled) {
+        SampleArgs a = {};
+        a.tab = b->d_tab; a.scratch = b->smp; a.row_stride = b->smp_stride; a.vocab = config->vocab_size;
+        a.out = b->d_vout;
+        L2Z_HIP(launch_sample_batch(a, R, st));
+    } else {
+        L2Z_HIP(launch_verify_batch_argmax(b->v_logits, config->vocab_size, b->d_vout, R, st));
+    }
+    L2Z_HIP(launch_verify_batch_accept(b->d_tab, b->d_groups, b->v_logits, config->vocab_size, b->d_vout, R, n, st));
+    L2Z_HIP(hipMemcpyAsync(b->h_vout, b->d_vout, (size_t)(R + n) * 4, hipMemcpyDeviceToHost, st));
+    L2Z_TRY(release_streams(b, n, states));
+    for (int j = 0; j < n; j++) {
+        l2z_runstate *s = states[j];
+        s->n_part = 0;  // l2z_argmax scans the logits the verdict copied
+        s->logits_partial = false;
+        if (s->bt != nullptr) s->bt->v_rows = j == 0 ? R : 0;  // l2z_verify_logits_read: the matrix is states[0]'s
+    }
+    L2Z_HIP(hipStreamSynchronize(st));
+    memcpy(out_next, b->h_vout, (size_t)R * 4);
+    for (int j = 0; j < n; j++) {
+        out_accepted[j] = b->h_vout[R + j];
+        states[j]->host_pos = pos0[j] + out_accepted[j] + 1;
+    }
     return L2Z_OK;
 }
 

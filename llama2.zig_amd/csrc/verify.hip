@@ -10,169 +10,24 @@
 // segments in segment order) depends on head_size and the segment alone, never on pos0, n or the row's index.
 #include "batch_decode.h"
 #include "kernel_common.h"
+#include "verify_device.h"
 
 namespace l2z {
 namespace {
 
-constexpr int kVaBlock = 256;
-constexpr int kVaUB = 4;  // K / V rows a lane has in flight
-constexpr int kVcUB = 8;  // combine: segments' partials a thread has in flight
-constexpr int kVaPerLane = kVerifySeg / 64;  // scores of one row a lane holds in the softmax sweep
-constexpr int kVaLds = kBatchMax * kVerifySeg > 16 * kVaBlock ? kBatchMax * kVerifySeg : 16 * kVaBlock;  // floats
-static_assert(kVerifySeg % 64 == 0, "a wave sweeps a row of scores in whole 64-lane steps");
-
-// Block (h, seg): head h over the keys t of segment seg that the call's rows see (t <= pos0 + n - 1).  A K row is read by
-// TPR lanes (float4 each) as in batch_attention_kernel, ONCE, and dotted with every row's q slice (registers); the
-// scores of the segment sit in LDS ([row][key]); a wave owns rows w, w + 4, ... for max / exp / sum; then each V row is
-// read once and added into every row's accumulator.
+// Block (h, seg): head h over the keys t of segment seg that the call's rows see (verify_device.h)
 __global__ __launch_bounds__(kVaBlock) void verify_attention_kernel(const VerifyAttnArgs a, const int n)
 {
     __shared__ __attribute__((aligned(16))) float sc[kVaLds];  // scores [row][key], then the groups' V sums (4 rows a round)
-    const int h = blockIdx.x, seg = blockIdx.y, tid = threadIdx.x;
-    const int hs = a.head_size, E = hs >> 2;
-    int TPR = 1;
-    while (TPR < E) TPR <<= 1;
-    const int G = kVaBlock / TPR, g = tid / TPR, c = tid % TPR;
-    const int seg0 = seg * kVerifySeg;
-    const int last = min(seg0 + kVerifySeg, a.pos0 + n) - 1;  // the last key of this segment any row of the call sees
-    const int nk = last - seg0 + 1;                           // ... so keys seg0 .. seg0 + nk - 1 are all it handles
-    const int i0 = max(0, seg0 - a.pos0);                     // rows below i0 end before this segment
-    const size_t head_off = (size_t)(h / a.kv_mul) * a.kv_head_stride;
-    const float *kbase = a.kc + head_off, *vbase = a.vc + head_off;
-    const v4f zero = {0.f, 0.f, 0.f, 0.f};
-    const float div = sqrtf((float)hs);
-    v4f qv[kBatchMax];
-#pragma unroll
-    for (int i = 0; i < kBatchMax; i++)
-        qv[i] = (i >= i0 && i < n && c < E) ? *(const v4f *)(a.q + (size_t)i * a.ldq + (size_t)h * hs + 4 * c) : zero;
-    // scores sc[i][t - seg0] = q_i . k_t / sqrt(head_size), -inf where row i does not see t
-    for (int tl0 = g; tl0 < nk; tl0 += G * kVaUB) {
-        v4f kv[kVaUB];
-#pragma unroll
-        for (int u = 0; u < kVaUB; u++) {
-            const int t = min(seg0 + tl0 + G * u, last);  // clamped: masked below
-            kv[u] = c < E ? *(const v4f *)(kbase + (size_t)t * hs + 4 * c) : zero;
-        }
-#pragma unroll
-        for (int u = 0; u < kVaUB; u++) {
-            const int tl = tl0 + G * u, t = seg0 + tl;
-#pragma unroll
-            for (int i = 0; i < kBatchMax; i++)
-                if (i >= i0 && i < n) {
-                    const float p = lanes_sum(hsum4(fma4(qv[i], kv[u], zero)), TPR);
-                    if (c == 0 && tl < nk) sc[i * kVerifySeg + tl] = t <= a.pos0 + i ? p / div : -INFINITY;
-                }
-        }
-    }
-    __syncthreads();
-    // per row: m = max, e = exp(s - m) in place, l = sum e (masked keys and the keys behind the call's last: -inf, so
-    // exactly 0, adding nothing)
-    {
-        const int lane = tid & 63;
-        for (int i = tid >> 6; i < kBatchMax; i += kVaBlock / 64)
-            if (i >= i0 && i < n) {
-                float *r = sc + i * kVerifySeg;
-                float sv[kVaPerLane], m = -INFINITY;
-#pragma unroll
-                for (int j = 0; j < kVaPerLane; j++) {
-                    sv[j] = lane + 64 * j < nk ? r[lane + 64 * j] : -INFINITY;
-                    m = fmaxf(m, sv[j]);
-                }
-                m = wave_max(m);  // finite: key seg0 <= pos0 + i is seen
-                float l = 0.0f;
-#pragma unroll
-                for (int j = 0; j < kVaPerLane; j++) {  // a lane's keys in increasing t, then the lanes (wave_sum's fixed order)
-                    const float e = expf(sv[j] - m);
-                    if (lane + 64 * j < nk) r[lane + 64 * j] = e;
-                    l += e;
-                }
-                l = wave_sum(l);
-                if (lane == 0) {
-                    float *ml = a.part_ml + (((size_t)i * a.n_heads + h) * a.seg_cap + seg) * 2;
-                    ml[0] = m;
-                    ml[1] = l;
-                }
-            }
-    }
-    __syncthreads();
-    // acc_i = sum_t e[i][t] v_t: group g takes t = seg0 + g, + G, ... in increasing t
-    v4f acc[kBatchMax];
-#pragma unroll
-    for (int i = 0; i < kBatchMax; i++) acc[i] = zero;
-    for (int tl0 = g; tl0 < nk; tl0 += G * kVaUB) {
-        v4f vv[kVaUB];
-#pragma unroll
-        for (int u = 0; u < kVaUB; u++) {
-            const int t = min(seg0 + tl0 + G * u, last);
-            vv[u] = c < E ? *(const v4f *)(vbase + (size_t)t * hs + 4 * c) : zero;
-        }
-#pragma unroll
-        for (int u = 0; u < kVaUB; u++) {
-            const int tl = tl0 + G * u;
-            if (tl < nk) {
-#pragma unroll
-                for (int i = 0; i < kBatchMax; i++)
-                    if (i >= i0 && i < n) {
-                        const float wt = sc[i * kVerifySeg + tl];
-                        if (wt > 0.0f) {  // an unseen key's weight is 0: skipped, so the sum is that of the seen keys alone
-                            const v4f w4 = {wt, wt, wt, wt};
-                            acc[i] = fma4(w4, vv[u], acc[i]);
-                        }
-                    }
-            }
-        }
-    }
-    __syncthreads();
-    // the groups' sums combined in g order, four rows per round through the score buffer
-    v4f *buf = (v4f *)sc;
-#pragma unroll
-    for (int r = 0; r < kBatchMax / 4; r++)
-        if (4 * r + 3 >= i0 && 4 * r < n) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) buf[j * kVaBlock + tid] = acc[4 * r + j];
-            __syncthreads();
-            if (tid < 4 * TPR) {
-                const int j = tid / TPR, cc = tid % TPR, i = 4 * r + j;
-                if (cc < E && i >= i0 && i < n) {
-                    v4f o = buf[j * kVaBlock + cc];
-                    for (int gg = 1; gg < G; gg++) o += buf[j * kVaBlock + gg * TPR + cc];
-                    *(v4f *)(a.part_o + (((size_t)i * a.n_heads + h) * a.seg_cap + seg) * hs + 4 * cc) = o;
-                }
-            }
-            __syncthreads();
-        }
+    verify_attention_body(a, n, blockIdx.x, blockIdx.y, sc);
 }
 
-// Block (h, i): row i's segments 0 .. (pos0 + i) / kVerifySeg folded in segment order (online rescale), then the divide.
-// One segment goes through the same arithmetic as many (the fold starts from max = -inf, sum = 0).
+// Block (h, i): row i's segments 0 .. (pos0 + i) / kVerifySeg folded in segment order, then the divide (verify_device.h)
 __global__ __launch_bounds__(64) void verify_combine_kernel(const VerifyAttnArgs a)
 {
     const int h = blockIdx.x, i = blockIdx.y;
-    const int ns = (a.pos0 + i) / kVerifySeg + 1;
-    const size_t base = ((size_t)i * a.n_heads + h) * a.seg_cap;
-    for (int d = threadIdx.x; d < a.head_size; d += 64) {
-        float M = -INFINITY, L = 0.0f, O = 0.0f;
-        for (int s0 = 0; s0 < ns; s0 += kVcUB) {  // kVcUB segments' partials in flight, folded in segment order
-            float m[kVcUB], l[kVcUB], o[kVcUB];
-#pragma unroll
-            for (int u = 0; u < kVcUB; u++) {
-                const size_t s = base + min(s0 + u, ns - 1);  // clamped: dropped below
-                m[u] = a.part_ml[s * 2];
-                l[u] = a.part_ml[s * 2 + 1];
-                o[u] = a.part_o[s * a.head_size + d];
-            }
-#pragma unroll
-            for (int u = 0; u < kVcUB; u++)
-                if (s0 + u < ns) {
-                    const float mn = fmaxf(M, m[u]);
-                    const float ea = expf(M - mn), eb = expf(m[u] - mn);
-                    L = L * ea + l[u] * eb;
-                    O = O * ea + o[u] * eb;
-                    M = mn;
-                }
-        }
-        a.out[(size_t)i * a.ldo + (size_t)h * a.head_size + d] = O / L;
-    }
+    verify_combine_body(a.part_o, a.part_ml, ((size_t)i * a.n_heads + h) * a.seg_cap, (a.pos0 + i) / kVerifySeg + 1, a.head_size,
+                        a.out + (size_t)i * a.ldo + (size_t)h * a.head_size);
 }
 
 __global__ __launch_bounds__(1024) void verify_argmax_kernel(const float *logits, int vocab, int *out)
