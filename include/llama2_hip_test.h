@@ -274,6 +274,43 @@ int l2z_verify_batch(int n, const int32_t *tokens, const int32_t *n_tokens, cons
                      const l2z_config *config, l2z_runstate *const *states, const l2z_weights *w,
                      int32_t *out_next, int32_t *out_accepted);
 
+/* Tree speculation: the verify pass of l2z_verify / l2z_verify_sample for a TREE of guesses on one sequence, in ONE sweep of
+ * the weights -- several candidate continuations cost what one chain of as many rows costs.
+ * Node 0 is the sequence's known token at pos0, parent[0] == -1.  Node i > 0 is a guess with 0 <= parent[i] < i (topological
+ * order); depth_i = the number of edges from node i to the root, and node i stands for position pos0 + depth_i.
+ * 1 <= n_nodes <= L2Z_BATCH_MAX; siblings carry pairwise different tokens.  A chain (parent[i] == i - 1) is l2z_verify's call.
+ * Row i: z_i = the logits of position pos0 + depth_i given the tokens on the path root -> i on top of cache rows < pos0.
+ * out_next[i] = the argmax of z_i (l2z_argmax's tie rule) at temperature == 0, otherwise the token l2z_sample_batch's kernel
+ * draws from z_i with (temperature, top_p, coins[depth_i]): coins has one entry per DEPTH, coins[d] = the coin of position
+ * pos0 + d, shared by all nodes of that depth; it may be NULL at temperature 0.
+ * The verdict (on the device): cur = 0; while cur has a child c with tokens[c] == out_next[cur], cur = c.
+ * out_path[0 .. a] = the nodes walked (out_path[0] == 0), *out_accepted = a; the sequence's next a + 1 tokens are
+ * out_next[out_path[d]], d = 0 .. a.  out_path has room for n_nodes entries.
+ * State on return (the shape of l2z_verify's): KV rows pos0 .. pos0 + a of every layer are the accepted path's, the runstate's
+ * logits are z of node out_path[a], the next position is pos0 + a + 1.  During the pass node i's keys and values sit in cache
+ * row pos0 + i; the accepted ones are moved into place on the device.  Rows pos0 + a + 1 .. pos0 + n_nodes - 1 hold rejected
+ * nodes' rows: beyond the next position, which every entry point overwrites before it reads.  No row < pos0 and no row
+ * >= pos0 + n_nodes is touched.  The call is synchronous; l2z_verify_logits_read(s, i, ...) returns z_i afterwards.
+ * PATH INVARIANCE: z_i, node i's K / V rows and -- after the call -- cache rows pos0 .. pos0 + a and the runstate's logits
+ * equal, BIT FOR BIT, what l2z_verify computes at row depth_i when it is given the tokens on the path root -> i as a chain on
+ * the same cache rows < pos0.  They do not depend on the other branches, on n_nodes or on the numbering of the nodes.  So a
+ * greedy loop over this call emits the ids of the loop over l2z_verify whatever the drafter proposes, and a sampled loop the
+ * ids of the loop over l2z_verify_sample for the same coin sequence: the token of a position is drawn from that position's
+ * distribution with that position's coin whatever the tree looks like, so the text keeps the plain sampler's law.
+ * A refusal enqueues nothing and changes no state.  L2Z_ERR_INVALID: a NULL argument, n_nodes outside [1, L2Z_BATCH_MAX],
+ * parent[0] != -1, a parent[i] outside [0, i), two siblings with one token, a sharded runstate, dims l2z_transformer_batch
+ * refuses, l2z_verify_sample's rules for temperature / top_p / coins applied to coins[0 .. max depth].  L2Z_ERR_STATE:
+ * pos0 < 0, pos0 + n_nodes > seq_len, a token outside the vocabulary.  L2Z_ERR_NO_DEVICE without a device. */
+int l2z_verify_tree(const int32_t *tokens, const int32_t *parent, int n_nodes, int pos0,
+                    float temperature, float top_p, const float *coins,
+                    const l2z_config *config, l2z_runstate *s, const l2z_weights *w,
+                    int32_t *out_next, int32_t *out_path, int *out_accepted);
+/* Measurement (scripts/verify_tree_bench.py): the twin of l2z_verify_time for l2z_verify_tree -- one call, then `iters` passes
+ * back to back (verdict, compaction and the copy included, no sync); *out_ms = milliseconds per pass. */
+int l2z_verify_tree_time(const int32_t *tokens, const int32_t *parent, int n_nodes, int pos0,
+                         float temperature, float top_p, const float *coins,
+                         const l2z_config *config, l2z_runstate *s, const l2z_weights *w, int iters, double *out_ms);
+
 #ifdef __cplusplus
 }
 #endif

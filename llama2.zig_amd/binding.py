@@ -107,6 +107,10 @@ def lib():
         L.l2z_prefill_batch.argtypes = [C.c_int, i32p, i32p, i32p, cfgp, C.POINTER(vp), vp]
     if hasattr(L, "l2z_verify_batch"):
         L.l2z_verify_batch.argtypes = [C.c_int, i32p, i32p, i32p, fp, fp, fp, cfgp, C.POINTER(vp), vp, i32p, i32p]
+    if hasattr(L, "l2z_verify_tree"):
+        L.l2z_verify_tree.argtypes = [i32p, i32p, C.c_int, C.c_int, C.c_float, C.c_float, fp, cfgp, vp, vp, i32p, i32p, ip]
+        L.l2z_verify_tree_time.argtypes = [i32p, i32p, C.c_int, C.c_int, C.c_float, C.c_float, fp, cfgp, vp, vp, C.c_int,
+                                           C.POINTER(C.c_double)]
     L.l2z_logits_write.argtypes = [vp, fp]
     L.l2z_sample_time.argtypes = [C.c_int, C.POINTER(vp), fp, fp, fp, C.c_int, C.POINTER(C.c_double)]
     L.l2z_greedy_begin.argtypes = [vp, i32p, C.c_int]
@@ -396,6 +400,41 @@ class RunState:
                                           iters, C.byref(ms)))
         return ms.value
 
+    def verify_tree(self, tokens, parent, pos0: int, w: Weights, temperature: float = 0.0, top_p: float = 1.0, coins=None):
+        """l2z_verify_tree (a preview entry point of the test library: include/llama2_hip_test.h): verify() for a TREE of
+        guesses.  tokens[0] is the sequence's token at pos0 with parent[0] == -1; node i > 0 is a guess behind node
+        parent[i] < i and stands for position pos0 + depth_i.  coins[d] is the coin of position pos0 + d (one per DEPTH;
+        None at temperature 0).  Returns (next: int32[n], path: int32[accepted + 1], accepted): next[i] = the model's id
+        after the tokens on the path root -> i, path = the nodes the verdict walked from the root; the sequence's next
+        tokens are next[path] and the runstate stands at pos0 + accepted + 1 with the logits behind next[path[-1]]."""
+        t = np.ascontiguousarray(tokens, np.int32).reshape(-1)
+        par = np.ascontiguousarray(parent, np.int32).reshape(-1)
+        if par.size != t.size:
+            raise ValueError(f"{par.size} parents for {t.size} nodes")
+        c = None if coins is None else np.ascontiguousarray(coins, np.float32).reshape(-1)
+        tb, pb = np.zeros(max(t.size, 1), np.int32), np.zeros(max(t.size, 1), np.int32)
+        tb[: t.size], pb[: t.size] = t, par
+        nxt, path = np.zeros(max(t.size, 1), np.int32), np.zeros(max(t.size, 1), np.int32)
+        a = C.c_int(0)
+        i32p = C.POINTER(C.c_int32)
+        _chk(lib().l2z_verify_tree(tb.ctypes.data_as(i32p), pb.ctypes.data_as(i32p), t.size, pos0, C.c_float(temperature),
+                                   C.c_float(top_p), None if c is None else _fp(c), C.byref(self.cfg), self.h, w.h,
+                                   nxt.ctypes.data_as(i32p), path.ctypes.data_as(i32p), C.byref(a)))
+        return nxt[: t.size].copy(), path[: a.value + 1].copy(), a.value
+
+    def verify_tree_time(self, tokens, parent, pos0: int, w: Weights, iters: int, temperature: float = 0.0,
+                         top_p: float = 1.0, coins=None) -> float:
+        """l2z_verify_tree_time: milliseconds per tree verify pass, device events over `iters` passes (after one untimed)."""
+        t = np.ascontiguousarray(tokens, np.int32).reshape(-1)
+        par = np.ascontiguousarray(parent, np.int32).reshape(-1)
+        c = None if coins is None else np.ascontiguousarray(coins, np.float32).reshape(-1)
+        ms = C.c_double(0.0)
+        i32p = C.POINTER(C.c_int32)
+        _chk(lib().l2z_verify_tree_time(t.ctypes.data_as(i32p), par.ctypes.data_as(i32p), t.size, pos0, C.c_float(temperature),
+                                        C.c_float(top_p), None if c is None else _fp(c), C.byref(self.cfg), self.h, w.h,
+                                        iters, C.byref(ms)))
+        return ms.value
+
     def argmax(self) -> int:
         t = C.c_int(0)
         _chk(lib().l2z_argmax(self.h, C.byref(t)))
@@ -628,6 +667,9 @@ def host_lib():
         H = C.CDLL(HOST_LIB_PATH)
         H.l2zh_lookup_draft.argtypes = [C.POINTER(C.c_int32), C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int32)]
         H.l2zh_lookup_draft.restype = C.c_size_t
+        H.l2zh_lookup_draft_tree.argtypes = [C.POINTER(C.c_int32), C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        H.l2zh_lookup_draft_tree.restype = C.c_size_t
         H.l2zh_prng_floats.argtypes = [C.c_uint64, C.POINTER(C.c_float), C.c_size_t]
         H.l2zh_prng_floats.restype = None
         _host = H
@@ -642,6 +684,21 @@ def lookup_draft(history, k: int, max_ngram: int = 3) -> np.ndarray:
     i32p = C.POINTER(C.c_int32)
     n = host_lib().l2zh_lookup_draft(h.ctypes.data_as(i32p), h.size, int(max_ngram), int(k), out.ctypes.data_as(i32p))
     return out[:n].copy()
+
+
+def lookup_draft_tree(history, depth: int, budget: int, max_ngram: int = 3):
+    """Tree form of the prompt-lookup drafter (l2zh_lookup_draft_tree): EVERY earlier occurrence of the last g tokens of
+    `history` (g = max_ngram .. 1, most recent first) contributes the up to `depth` tokens that followed it; the
+    continuations are merged into a trie until `budget` (at most 15) guesses exist.  Returns (tokens, parent) of the
+    guesses: guess k is tree node k + 1 (node 0 = the root, the sequence's last token), parent[k] its parent's tree node
+    in [0, k].  The first continuation is lookup_draft(history, depth): guesses 0, 1, ... form that chain."""
+    h = np.ascontiguousarray(history, np.int32)
+    budget = max(0, min(int(budget), BATCH_MAX - 1))
+    tok, par = np.zeros(max(budget, 1), np.int32), np.zeros(max(budget, 1), np.int32)
+    i32p = C.POINTER(C.c_int32)
+    n = host_lib().l2zh_lookup_draft_tree(h.ctypes.data_as(i32p), h.size, int(max_ngram), int(depth), budget,
+                                          tok.ctypes.data_as(i32p), par.ctypes.data_as(i32p))
+    return tok[:n].copy(), par[:n].copy()
 
 
 def speculate_greedy(s: RunState, w: Weights, prompt, n_steps: int, k: int, drafter=None):
@@ -741,6 +798,75 @@ def speculate_sample(s: RunState, w: Weights, prompt, n_steps: int, k: int, temp
         stats["offered"] += len(guesses)
         stats["accepted"] += a
         for t in nxt[: a + 1]:
+            if not (alive and pos < steps):
+                break
+            alive = emit(t)
+            stats["emitted"] += 1
+            g += 1
+            pos += alive
+    return np.array(out, np.int32), stats
+
+
+def speculate_tree(s: RunState, w: Weights, prompt, n_steps: int, depth: int, budget: int, drafter=None, temperature=None,
+                   top_p=None, coins=None):
+    """speculate_greedy's loop (temperature=None) or speculate_sample's with a TREE of guesses verified per sweep of the
+    weights (RunState.verify_tree): up to `budget` guessed nodes, at most `depth` edges below the sequence's last token.
+    drafter(history, depth, budget) -> (tokens, parent) of the guesses in lookup_draft_tree's convention, which is the
+    default; nodes deeper than asked, beyond the budget or behind a dropped node are not used.  Sampled mode: coins[g] is
+    the coin of the g-th generated token as in speculate_sample, so a call at generated index g passes
+    coins[g : g + 1 + max depth].  The return convention is speculate_greedy's; stats["offered"] counts guessed nodes,
+    stats["accepted"] edges walked.  The ids do not depend on depth, budget or the drafter (PATH INVARIANCE): they are
+    speculate_greedy's, or speculate_sample's for the same coins."""
+    if not 0 <= budget <= BATCH_MAX - 1:
+        raise ValueError(f"budget = {budget} outside [0, {BATCH_MAX - 1}]")
+    if drafter is None:
+        drafter = lookup_draft_tree
+    sampled = temperature is not None
+    seq_len = s.cfg.seq_len
+    steps = seq_len if n_steps == 0 else max(1, min(int(n_steps), seq_len))
+    prompt = [int(t) for t in prompt][:steps]
+    if sampled:
+        coins = np.ascontiguousarray(coins, np.float32).reshape(-1)
+        top_p = 1.0 if top_p is None else top_p
+        if coins.size < steps - len(prompt):
+            raise ValueError(f"{coins.size} coins for {steps - len(prompt)} generated positions")
+    hist, out = [1], []
+    stats = {"calls": 0, "offered": 0, "accepted": 0, "emitted": 0}
+
+    def emit(t):
+        out.append(int(t))
+        hist.append(int(t))
+        return int(t) != 1
+
+    alive, pos, g = True, 0, 0  # g: generated tokens so far = the index of the next coin
+    while alive and pos < len(prompt):
+        alive = emit(prompt[pos])
+        pos += alive
+    if alive and pos < steps:
+        s.prefill(np.array(hist, np.int32), 0, w)
+        alive = emit(sample_batch([s], temperature, top_p, coins[0])[0] if sampled else s.argmax())
+        g += 1
+        pos += alive
+    while alive and pos < steps:
+        dd, bb = min(int(depth), steps - pos - 1), min(int(budget), seq_len - pos - 1)
+        tokens, parent, dep = [hist[-1]], [-1], [0]
+        if dd > 0 and bb > 0:
+            gt, gp = drafter(np.array(hist, np.int32), dd, bb)
+            node = {0: 0}  # the drafter's tree node -> ours
+            for k, (t, p) in enumerate(zip(gt, gp)):
+                p = node.get(int(p))
+                if p is None or dep[p] + 1 > dd or len(tokens) > bb:
+                    continue
+                node[k + 1] = len(tokens)
+                tokens.append(int(t)); parent.append(p); dep.append(dep[p] + 1)
+        if sampled:
+            nxt, path, a = s.verify_tree(tokens, parent, pos, w, temperature, top_p, coins[g: g + 1 + max(dep)])
+        else:
+            nxt, path, a = s.verify_tree(tokens, parent, pos, w)
+        stats["calls"] += 1
+        stats["offered"] += len(tokens) - 1
+        stats["accepted"] += a
+        for t in nxt[path]:
             if not (alive and pos < steps):
                 break
             alive = emit(t)

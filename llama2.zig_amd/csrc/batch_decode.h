@@ -147,4 +147,42 @@ hipError_t launch_verify_batch_argmax(const float *logits, int vocab, int *out, 
 hipError_t launch_verify_batch_accept(const BatchTable *tab, const VerifyGroupTable *groups, const float *logits, int vocab,
                                       int *out, int n_rows, int n_groups, hipStream_t st);
 
+// l2z_verify_tree (verify_tree.hip): the rows of a step are the nodes of a TREE of guesses on ONE sequence.  Node i stands
+// for position pos0 + depth[i] (tab->pos[i]) and keeps its K / V in PHYSICAL cache row pos0 + i (tab->kc[i] / vc[i] are the
+// cache bases shifted by (i - depth[i]) * head_size floats, so the step's epilogue stores there).  Uploaded behind the
+// step's BatchTable in the same copy, where VerifyGroupTable sits for l2z_verify_batch.
+struct VerifyTreeTable {
+    int32_t parent[kBatchMax];  // parent[0] = -1, 0 <= parent[i] < i
+    int32_t depth[kBatchMax];   // edges from node i to the root
+    uint32_t below[kBatchMax];  // bit i of below[j]: node j lies on the path root -> i (j == i included)
+    uint32_t level[kBatchMax];  // bit i of level[d]: depth[i] == d
+};
+// Attention: block (head, segment) over kVerifySeg ABSOLUTE positions, the score buffer indexed by position as in
+// launch_verify_attention.  Row i finds the key of position t in cache row t for t < pos0 and in row pos0 + (its ancestor
+// of depth t - pos0) up to its own position; deeper positions are masked (weight exactly 0, V row skipped).  Every
+// summation order is verify_device.h's, so row i's partials are the bits l2z_verify leaves for row depth[i] of the chain
+// root -> i.  max_depth = the deepest node's depth; the grid is (n_heads, (pos0 + max_depth) / kVerifySeg + 1).
+struct VerifyTreeAttnArgs {
+    const float *q;  // [n, ldq], RoPE applied
+    float *out;      // [n, ldo]
+    float *part_o, *part_ml;
+    const float *kc, *vc;  // the layer's caches, head-major [kv head][seq_len][head_size]
+    const VerifyTreeTable *tree;
+    size_t kv_head_stride;
+    int ldq, ldo, n_heads, kv_mul, head_size, seg_cap, pos0;
+};
+hipError_t launch_verify_tree_attention(const VerifyTreeAttnArgs &a, int n, int max_depth, hipStream_t st);
+hipError_t launch_verify_tree_combine(const VerifyTreeAttnArgs &a, int n, int max_depth, hipStream_t st);
+// The verdict: out[0 .. n) = the rows' next ids (launch_verify_tree_argmax: block_argmax_1024 per row; a sampled pass has
+// launch_sample_batch fill them).  launch_verify_tree_accept walks the tree from the root -- while the node has a child
+// whose token is the node's next id, go there -- and leaves out[n] = a (edges walked), out[n + 1 + d] = the node at depth d
+// (d = 0 .. a), and the last node's row of the logits matrix in dst.
+hipError_t launch_verify_tree_argmax(const float *logits, int vocab, int *out, int n, hipStream_t st);
+hipError_t launch_verify_tree_accept(const BatchTable *tab, const VerifyTreeTable *tree, const float *logits, int vocab, int *out,
+                                     float *dst, int n, hipStream_t st);
+// The accepted path's K / V rows into place, read from the verdict on the device (res = launch_verify_tree_accept's out):
+// row pos0 + path[d] -> row pos0 + d for d = 1 .. a, every layer and kv head of both caches (kc / vc: layer 0's bases).
+hipError_t launch_verify_tree_compact(float *kc, float *vc, const int *res, int n, int pos0, int head_size, size_t kv_head_stride,
+                                      int n_layers, int n_kv_heads, hipStream_t st);
+
 }  // namespace l2z

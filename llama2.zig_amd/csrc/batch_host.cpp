@@ -4,7 +4,8 @@
 // needs around the step: the on-device sampler l2z_sample_batch (sample_batch.hip) and the prompt copy
 // l2z_runstate_fork.  And l2z_verify: the same step with the rows being consecutive positions of ONE sequence
 // (speculative greedy decoding), attention and verdict by verify.hip.  And l2z_verify_batch: that pass for the rows of
-// several sequences at once, attention and verdict per sequence by verify_batch.hip.
+// several sequences at once, attention and verdict per sequence by verify_batch.hip.  And l2z_verify_tree: the rows being
+// the nodes of a tree of guesses on one sequence, attention, verdict and compaction by verify_tree.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -25,6 +26,7 @@ struct BatchScratch {
     int ld_xn = 0, ld_att = 0, ld_h1 = 0;
     BatchTable *d_tab = nullptr, *h_tab = nullptr;
     VerifyGroupTable *d_groups = nullptr, *h_groups = nullptr;  // l2z_verify_batch: behind the table, in the same allocations
+    VerifyTreeTable *d_tree = nullptr, *h_tree = nullptr;       // l2z_verify_tree: in the group table's place
     int *d_tokens_out = nullptr, *h_tokens_out = nullptr;
     hipEvent_t ev_in[kBatchMax] = {};
     hipEvent_t ev_done = nullptr;
@@ -34,7 +36,8 @@ struct BatchScratch {
     // l2z_verify (on the runstate's first call): the [kBatchMax, vocab] logits matrix, the attention partials
     // ([kBatchMax, n_heads, v_seg_cap, head_size] and [..., 2]), next[0 .. n) | accepted on the device and pinned
     float *v_logits = nullptr, *v_part_o = nullptr, *v_part_ml = nullptr;
-    int *d_vout = nullptr, *h_vout = nullptr;  // 2 * kBatchMax ints (l2z_verify_batch: next[0 .. rows) | accepted[0 .. n))
+    int *d_vout = nullptr, *h_vout = nullptr;  // 3 * kBatchMax ints (l2z_verify_batch: next[0 .. rows) | accepted[0 .. n);
+                                               // l2z_verify_tree: next[0 .. n) | accepted | path[0 .. accepted])
     int v_seg_cap = 0, v_rows = 0;   // v_rows: rows of the last call (l2z_verify_logits_read)
 };
 
@@ -59,6 +62,9 @@ void batch_free(l2z_runstate *s)
 
 namespace {
 
+// what follows the step's table in its allocations: the row groups of l2z_verify_batch or the tree of l2z_verify_tree
+constexpr size_t kTabExtra = std::max(sizeof(VerifyGroupTable), sizeof(VerifyTreeTable));
+
 // Row pitch of the activation matrices the GEMMs read: rounded up to 256 floats, at least 768, the pad columns zero and
 // never written (the short-prompt forms multiply whole 256-k stages, at least three: prefill_common.h pad_k)
 int bt_ld(int n)
@@ -79,7 +85,7 @@ int batch_alloc(l2z_runstate *s)
         {(void **)&b->x, R * c.dim * 4}, {(void **)&b->xn, R * b->ld_xn * 4}, {(void **)&b->q, R * c.dim * 4},
         {(void **)&b->att, R * b->ld_att * 4}, {(void **)&b->h1, R * b->ld_h1 * 4},
         {(void **)&b->scores, R * (size_t)c.n_heads * c.seq_len * 4},
-        {(void **)&b->d_tab, sizeof(BatchTable) + sizeof(VerifyGroupTable)}, {(void **)&b->d_tokens_out, R * 4}};
+        {(void **)&b->d_tab, sizeof(BatchTable) + kTabExtra}, {(void **)&b->d_tokens_out, R * 4}};
     for (auto &w : want) {
         const hipError_t e = hipMalloc(w.p, w.bytes);
         if (e != hipSuccess) {
@@ -88,9 +94,11 @@ int batch_alloc(l2z_runstate *s)
             return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
         }
     }
-    L2Z_HIP(hipHostMalloc((void **)&b->h_tab, sizeof(BatchTable) + sizeof(VerifyGroupTable), hipHostMallocDefault));
+    L2Z_HIP(hipHostMalloc((void **)&b->h_tab, sizeof(BatchTable) + kTabExtra, hipHostMallocDefault));
     b->d_groups = (VerifyGroupTable *)(b->d_tab + 1);
     b->h_groups = (VerifyGroupTable *)(b->h_tab + 1);
+    b->d_tree = (VerifyTreeTable *)(b->d_tab + 1);
+    b->h_tree = (VerifyTreeTable *)(b->h_tab + 1);
     L2Z_HIP(hipHostMalloc((void **)&b->h_tokens_out, R * 4, hipHostMallocDefault));
     for (hipEvent_t &e : b->ev_in) L2Z_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     L2Z_HIP(hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
@@ -171,6 +179,18 @@ int upload_tables(BatchScratch *b, const BatchTable &t, const VerifyGroupTable &
     return L2Z_OK;
 }
 
+// ... or the tree of an l2z_verify_tree call
+int upload_tables(BatchScratch *b, const BatchTable &t, const VerifyTreeTable &g, hipStream_t st)
+{
+    static_assert(sizeof(BatchTable) % alignof(VerifyTreeTable) == 0, "the tree table sits right behind the step's table");
+    L2Z_HIP(hipEventSynchronize(b->ev_upload));
+    memcpy(b->h_tab, &t, sizeof t);
+    memcpy(b->h_tree, &g, sizeof g);
+    L2Z_HIP(hipMemcpyAsync(b->d_tab, b->h_tab, sizeof t + sizeof g, hipMemcpyHostToDevice, st));
+    L2Z_HIP(hipEventRecord(b->ev_upload, st));
+    return L2Z_OK;
+}
+
 GemmArgs gemm(const float *x, int ldx, const float *w, int ldw, int N, int K, int P)
 {
     GemmArgs a = {};
@@ -184,8 +204,10 @@ GemmArgs gemm(const float *x, int ldx, const float *w, int ldw, int N, int K, in
 // multi-query position-split form over s0's cache (verify.hip) instead of one block per (head, row).
 // vb_groups > 0 (l2z_verify_batch): the rows are the groups of b->d_groups, each on its own sequence's cache; attention is
 // that form per group in one launch (verify_batch.hip), vb_segments = the deepest group's segment count.
+// tree_depth >= 0 beside verify_pos0 >= 0 (l2z_verify_tree): the rows are the nodes of b->d_tree, the deepest tree_depth
+// edges from the root, on s0's cache; attention is that form with every row on its own path (verify_tree.hip).
 int batch_step(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *w, BatchScratch *b, int verify_pos0 = -1,
-               int vb_groups = 0, int vb_segments = 0)
+               int vb_groups = 0, int vb_segments = 0, int tree_depth = -1)
 {
     hipStream_t st = s0->stream;
     const int dim = c.dim, hid = c.hidden_dim, hs = dim / c.n_heads, kvd = hs * c.n_kv_heads;
@@ -213,6 +235,15 @@ int batch_step(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *
             a.n_heads = c.n_heads; a.kv_mul = c.n_heads / c.n_kv_heads; a.head_size = hs; a.seg_cap = b->v_seg_cap;
             L2Z_HIP(launch_verify_batch_attention(a, vb_groups, vb_segments, st));
             L2Z_HIP(launch_verify_batch_combine(a, n, st));
+        } else if (verify_pos0 >= 0 && tree_depth >= 0) {  // :361-389, flash form along each row's path
+            VerifyTreeAttnArgs a = {};
+            a.q = b->q; a.ldq = dim; a.out = b->att; a.ldo = b->ld_att; a.part_o = b->v_part_o; a.part_ml = b->v_part_ml;
+            a.kc = s0->key_cache + layer_off; a.vc = s0->value_cache + layer_off; a.tree = b->d_tree;
+            a.kv_head_stride = (size_t)c.seq_len * hs;
+            a.n_heads = c.n_heads; a.kv_mul = c.n_heads / c.n_kv_heads; a.head_size = hs; a.seg_cap = b->v_seg_cap;
+            a.pos0 = verify_pos0;
+            L2Z_HIP(launch_verify_tree_attention(a, n, tree_depth, st));
+            L2Z_HIP(launch_verify_tree_combine(a, n, tree_depth, st));
         } else if (verify_pos0 >= 0) {  // :361-389, flash form
             VerifyAttnArgs a = {};
             a.q = b->q; a.ldq = dim; a.out = b->att; a.ldo = b->ld_att; a.part_o = b->v_part_o; a.part_ml = b->v_part_ml;
@@ -540,7 +571,7 @@ int verify_alloc(l2z_runstate *s)
         {(void **)&b->v_logits, R * (size_t)c.vocab_size * 4},
         {(void **)&b->v_part_o, R * c.n_heads * segs * hs * 4},
         {(void **)&b->v_part_ml, R * c.n_heads * segs * 2 * 4},
-        {(void **)&b->d_vout, 2 * R * 4}};
+        {(void **)&b->d_vout, 3 * R * 4}};
     for (auto &w : want) {
         if (*w.p != nullptr) continue;
         const hipError_t e = hipMalloc(w.p, w.bytes);
@@ -550,7 +581,7 @@ int verify_alloc(l2z_runstate *s)
             return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
         }
     }
-    if (b->h_vout == nullptr) L2Z_HIP(hipHostMalloc((void **)&b->h_vout, 2 * R * 4, hipHostMallocDefault));
+    if (b->h_vout == nullptr) L2Z_HIP(hipHostMalloc((void **)&b->h_vout, 3 * R * 4, hipHostMallocDefault));
     b->v_seg_cap = (int)segs;
     return L2Z_OK;
 }
@@ -770,6 +801,144 @@ extern "C" int l2z_verify_batch(int n, const int32_t *tokens, const int32_t *n_t
         states[j]->host_pos = pos0[j] + out_accepted[j] + 1;
     }
     return L2Z_OK;
+}
+
+// ---- l2z_verify_tree: the verify pass for a TREE of guesses on one sequence (include/llama2_hip_test.h) ----
+namespace l2z {
+namespace {
+
+// l2z_verify_tree's checks (a refusal enqueues nothing), then the tables, the pass, the verdict, the compaction and the
+// verdict's copy back on s's stream; no sync.
+int verify_tree_enqueue(const int32_t *tokens, const int32_t *parent, int n, int pos0, float temperature, float top_p,
+                        const float *coins, const l2z_config *config, l2z_runstate *s, const l2z_weights *w)
+{
+    const char *fn = "l2z_verify_tree";
+    L2Z_TRY(no_device_check());
+    L2Z_CHECK(tokens != nullptr && parent != nullptr && config != nullptr && s != nullptr && w != nullptr, L2Z_ERR_INVALID,
+              "%s: null argument", fn);
+    L2Z_CHECK(n >= 1 && n <= kBatchMax, L2Z_ERR_INVALID, "%s: n_nodes = %d outside [1, %d]", fn, n, kBatchMax);
+    L2Z_CHECK(parent[0] == -1, L2Z_ERR_INVALID, "%s: parent[0] = %d (the root's is -1)", fn, parent[0]);
+    VerifyTreeTable g = {};
+    int max_depth = 0;
+    g.parent[0] = -1;
+    g.below[0] = 1u;
+    g.level[0] = 1u;
+    for (int i = 1; i < n; i++) {
+        L2Z_CHECK(parent[i] >= 0 && parent[i] < i, L2Z_ERR_INVALID, "%s: parent[%d] = %d outside [0, %d)", fn, i, parent[i], i);
+        g.parent[i] = parent[i];
+        g.depth[i] = g.depth[parent[i]] + 1;
+        g.level[g.depth[i]] |= 1u << i;
+        for (int j = i; j >= 0; j = g.parent[j]) g.below[j] |= 1u << i;
+        max_depth = std::max(max_depth, g.depth[i]);
+    }
+    for (int i = 1; i < n; i++)
+        for (int j = 1; j < i; j++)
+            L2Z_CHECK(parent[i] != parent[j] || tokens[i] != tokens[j], L2Z_ERR_INVALID,
+                      "%s: nodes %d and %d are siblings with one token (%d)", fn, j, i, tokens[i]);
+    L2Z_CHECK(s->comm == nullptr && s->sh.world == 1, L2Z_ERR_INVALID, "%s: the runstate is a shard", fn);
+    L2Z_TRY(check_pair(config, s, w));
+    L2Z_TRY(prefill_check(config, s));
+    L2Z_CHECK(s->sh.hs <= 256, L2Z_ERR_INVALID, "%s: head_size above 256", fn);
+    VerifyDraw store;
+    const VerifyDraw *draw = nullptr;
+    L2Z_TRY(verify_sample_args(temperature, top_p, coins, &store, &draw));
+    if (draw != nullptr)  // one coin per depth
+        for (int d = 0; d <= max_depth; d++)
+            L2Z_CHECK(coins[d] >= 0.0f && coins[d] < 1.0f, L2Z_ERR_INVALID, "%s: coins[%d] = %g outside [0, 1)", fn, d,
+                      (double)coins[d]);
+    L2Z_CHECK(pos0 >= 0 && pos0 <= config->seq_len - n, L2Z_ERR_STATE, "%s: cache rows %d .. %lld outside [0, %d)", fn, pos0,
+              (long long)pos0 + n - 1, config->seq_len);
+    for (int i = 0; i < n; i++)
+        L2Z_CHECK(tokens[i] >= 0 && tokens[i] < config->vocab_size, L2Z_ERR_STATE, "%s: tokens[%d] = %d out of vocabulary", fn,
+                  i, tokens[i]);
+    L2Z_HIP(hipSetDevice(s->device));
+    L2Z_TRY(batch_alloc(s));
+    L2Z_TRY(verify_alloc(s));
+    if (draw != nullptr) L2Z_TRY(sample_alloc(s));
+    BatchScratch *b = s->bt;
+    const size_t hs = (size_t)config->dim / config->n_heads;
+    BatchTable t = {};
+    for (int i = 0; i < n; i++) {
+        t.tokens[i] = tokens[i];
+        t.pos[i] = pos0 + g.depth[i];  // RoPE and the cache index of the step's epilogue ...
+        t.kc[i] = s->key_cache + (size_t)(i - g.depth[i]) * hs;  // ... which so lands in physical row pos0 + i (i >= depth)
+        t.vc[i] = s->value_cache + (size_t)(i - g.depth[i]) * hs;
+        t.logits[i] = b->v_logits + (size_t)i * config->vocab_size;
+        if (draw != nullptr) {
+            t.temperature[i] = draw->temperature;
+            t.top_p[i] = draw->top_p;
+            t.coin[i] = draw->coins[g.depth[i]];
+        }
+    }
+    hipStream_t st = s->stream;
+    L2Z_TRY(upload_tables(b, t, g, st));
+    L2Z_TRY(batch_step(n, *config, s, w, b, pos0, 0, 0, max_depth));
+    if (draw != nullptr) {
+        SampleArgs a = {};
+        a.tab = b->d_tab; a.scratch = b->smp; a.row_stride = b->smp_stride; a.vocab = config->vocab_size;
+        a.out = b->d_vout;
+        L2Z_HIP(launch_sample_batch(a, n, st));
+    } else {
+        L2Z_HIP(launch_verify_tree_argmax(b->v_logits, config->vocab_size, b->d_vout, n, st));
+    }
+    L2Z_HIP(launch_verify_tree_accept(b->d_tab, b->d_tree, b->v_logits, config->vocab_size, b->d_vout, s->logits, n, st));
+    L2Z_HIP(launch_verify_tree_compact(s->key_cache, s->value_cache, b->d_vout, n, pos0, (int)hs, (size_t)config->seq_len * hs,
+                                       config->n_layers, config->n_kv_heads, st));
+    L2Z_HIP(hipMemcpyAsync(b->h_vout, b->d_vout, (size_t)(2 * n + 1) * 4, hipMemcpyDeviceToHost, st));
+    b->v_rows = n;
+    s->n_part = 0;  // l2z_argmax scans the logits the verdict copied
+    s->logits_partial = false;
+    return L2Z_OK;
+}
+
+}  // namespace
+}  // namespace l2z
+
+extern "C" int l2z_verify_tree(const int32_t *tokens, const int32_t *parent, int n_nodes, int pos0, float temperature,
+                               float top_p, const float *coins, const l2z_config *config, l2z_runstate *s,
+                               const l2z_weights *w, int32_t *out_next, int32_t *out_path, int *out_accepted)
+{
+    L2Z_TRY(no_device_check());
+    L2Z_CHECK(out_next != nullptr && out_path != nullptr && out_accepted != nullptr, L2Z_ERR_INVALID,
+              "l2z_verify_tree: null argument");
+    L2Z_TRY(verify_tree_enqueue(tokens, parent, n_nodes, pos0, temperature, top_p, coins, config, s, w));
+    BatchScratch *b = s->bt;
+    L2Z_HIP(hipStreamSynchronize(s->stream));
+    const int a = b->h_vout[n_nodes];
+    memcpy(out_next, b->h_vout, (size_t)n_nodes * 4);
+    memcpy(out_path, b->h_vout + n_nodes + 1, (size_t)(a + 1) * 4);
+    *out_accepted = a;
+    s->host_pos = pos0 + a + 1;
+    return L2Z_OK;
+}
+
+// Testing support: l2z_verify_time for a tree (scripts/verify_tree_bench.py): one l2z_verify_tree call, then `iters` passes
+// back to back (verdict, compaction and the copy included, no sync).  The passes rewrite the same KV rows; a pass whose
+// verdict moved rows leaves the next one the same inputs, since every node's row is written again before it is read.
+extern "C" int l2z_verify_tree_time(const int32_t *tokens, const int32_t *parent, int n_nodes, int pos0, float temperature,
+                                    float top_p, const float *coins, const l2z_config *config, l2z_runstate *s,
+                                    const l2z_weights *w, int iters, double *out_ms)
+{
+    L2Z_CHECK(iters >= 1 && out_ms != nullptr, L2Z_ERR_INVALID, "l2z_verify_tree_time: bad arguments");
+    int32_t next[kBatchMax], path[kBatchMax];
+    int acc = 0;
+    L2Z_TRY(l2z_verify_tree(tokens, parent, n_nodes, pos0, temperature, top_p, coins, config, s, w, next, path, &acc));
+    hipStream_t st = s->stream;
+    hipEvent_t e0, e1;
+    L2Z_HIP(hipEventCreate(&e0));
+    L2Z_HIP(hipEventCreate(&e1));
+    int rc = L2Z_OK;
+    if (hipEventRecord(e0, st) != hipSuccess) rc = L2Z_ERR_HIP;
+    for (int i = 0; i < iters && rc == L2Z_OK; i++)
+        rc = verify_tree_enqueue(tokens, parent, n_nodes, pos0, temperature, top_p, coins, config, s, w);
+    float ms = 0.0f;
+    if (rc == L2Z_OK && (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
+                         hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
+        rc = L2Z_ERR_HIP;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (rc == L2Z_OK) *out_ms = ms / iters;
+    return rc;
 }
 
 // Testing support (include/llama2_hip_test.h): row `row` of the last l2z_verify call's logits matrix

@@ -414,6 +414,38 @@ size_t lookup_draft(const int32_t *history, size_t n, int max_ngram, int k, int3
     return 0;
 }
 
+size_t lookup_draft_tree(const int32_t *history, size_t n, int max_ngram, int depth, int budget, int32_t *tokens_out,
+                         int32_t *parent_out)
+{
+    if (depth <= 0 || budget <= 0 || history == nullptr) return 0;
+    if (budget > 15) budget = 15;
+    size_t nodes = 0;  // guess nodes so far; guess k is tree node k + 1
+    for (size_t g = max_ngram > 0 ? (size_t)max_ngram : 0; g >= 1; g--) {
+        if (g + 1 > n) continue;
+        const int32_t *tail = history + (n - g);
+        for (size_t j = n - g; j-- > 0;) {  // most recent first
+            size_t m = 0;
+            while (m < g && history[j + m] == tail[m]) m++;
+            if (m < g) continue;
+            const size_t from = j + g, cnt = std::min((size_t)depth, n - from);
+            int32_t cur = 0;  // the root
+            for (size_t i = 0; i < cnt; i++) {
+                int32_t child = -1;
+                for (size_t c = 0; c < nodes && child < 0; c++)
+                    if (parent_out[c] == cur && tokens_out[c] == history[from + i]) child = (int32_t)c + 1;
+                if (child < 0) {
+                    if (nodes == (size_t)budget) return nodes;
+                    tokens_out[nodes] = history[from + i];
+                    parent_out[nodes] = cur;
+                    child = (int32_t)++nodes;
+                }
+                cur = child;
+            }
+        }
+    }
+    return nodes;
+}
+
 }  // namespace l2zhost
 
 // ---- C hooks so the tests can drive the host logic through ctypes ----
@@ -467,6 +499,12 @@ long l2zh_tokenizer_encode_quadratic(void *t, const char *bytes, size_t n, int32
 size_t l2zh_lookup_draft(const int32_t *history, size_t n_history, int max_ngram, int k, int32_t *out)
 {
     return lookup_draft(history, n_history, max_ngram, k, out);
+}
+// the tree drafter of binding.lookup_draft_tree: tokens_out / parent_out have room for budget (<= 15) guess nodes
+size_t l2zh_lookup_draft_tree(const int32_t *history, size_t n_history, int max_ngram, int depth, int budget,
+                              int32_t *tokens_out, int32_t *parent_out)
+{
+    return lookup_draft_tree(history, n_history, max_ngram, depth, budget, tokens_out, parent_out);
 }
 int l2zh_is_raw_byte(const char *s, size_t n) { return is_raw_byte(std::string_view(s, n)); }
 void l2zh_prng_floats(uint64_t seed, float *out, size_t n)

@@ -74,6 +74,14 @@ size_t sample_top_p_coin(const float *probs, size_t n, float p, std::vector<Inde
 // j < n - g with history[j .. j + g) == history[n - g .. n); on the first hit the tokens that followed it,
 // history[j + g .. min(j + g + k, n)), go to out (room for k) and their number is returned; no hit: 0.  O(n * g) per call.
 size_t lookup_draft(const int32_t *history, size_t n, int max_ngram, int k, int32_t *out);
+// The tree form of it, for l2z_verify_tree: EVERY hit of lookup_draft's rule (g = max_ngram down to 1, most recent first)
+// contributes the up to `depth` tokens that followed it; the continuations are merged into a trie below the root (= the
+// sequence's last token, tree node 0) until `budget` (at most 15) guess nodes exist.  Guess k (k = 0 ..) is tree node k + 1
+// in insertion order: its token goes to tokens_out[k], its parent's tree node (0 .. k) to parent_out[k]; returns the number
+// of guesses.  The first continuation inserted is lookup_draft(history, n, max_ngram, depth): guesses 0, 1, ... form that
+// chain.  Deterministic; no model, no coins.
+size_t lookup_draft_tree(const int32_t *history, size_t n, int max_ngram, int depth, int budget, int32_t *tokens_out,
+                         int32_t *parent_out);
 // :1055-1076  "<0xXX>" -> byte, only if printable or whitespace; -1 otherwise
 int is_raw_byte(std::string_view s);
 
