@@ -1,5 +1,7 @@
-// batch_decode.h -- kernels of the batched decode step (batch_decode.hip; host side: batch_host.cpp).  One row per
-// independent sequence: every row's position, KV caches and logits come from a small device table.
+// batch_decode.h -- the kernels that run on the batched step's rows, as the host sees them: the step's own attention and
+// argmax (batch_decode.hip; host side batch_host.cpp), the row sampler (sample_batch.hip) and the verify family's
+// attention forms and verdicts (verify.hip, verify_batch.hip, verify_tree.hip; host side verify_host.cpp).  Every row's
+// token, position, KV caches and logits come from a small device table.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -83,35 +85,41 @@ struct SampleArgs {
 inline size_t sample_scratch_floats(int vocab) { return 5 * (((size_t)vocab + 63) / 64 * 64); }
 hipError_t launch_sample_batch(const SampleArgs &a, int n, hipStream_t st);
 
-// l2z_verify (verify.hip): n rows of ONE sequence at consecutive positions tab->pos[i] = pos0 + i, all on one cache.
-// Attention is multi-query, causal and split over positions: a block owns (head, segment), the segments are
-// kVerifySeg ABSOLUTE positions each -- segment s = positions [s * kVerifySeg, (s + 1) * kVerifySeg) whatever pos0 and
-// n are -- loads each K and V row of its segment once and uses it for every row; it leaves per (row, head, segment)
-// the flash partials (max, sum e^(s - max), sum e^(s - max) v).  launch_verify_combine folds a row's segments in
-// segment order and divides.  Every order is a function of head_size, the segment and the row's position alone.
+// The verify family (verify.hip, verify_batch.hip, verify_tree.hip; host side: verify_host.cpp): the rows of a step are
+// guessed positions, attention is multi-query, causal and split over positions.  A block owns (head, segment), the
+// segments are kVerifySeg ABSOLUTE positions each -- segment s = positions [s * kVerifySeg, (s + 1) * kVerifySeg) whatever
+// the call's first position and row count are -- loads each K and V row of its segment once and uses it for every row; it
+// leaves per (row, head, segment) the flash partials (max, sum e^(s - max), sum e^(s - max) v).  The combine folds a row's
+// segments in segment order and divides.  Every order is a function of head_size, the segment and the row's position alone.
 constexpr int kVerifySeg = 64;
 inline int verify_segments(int seq_len) { return (seq_len + kVerifySeg - 1) / kVerifySeg; }
-struct VerifyAttnArgs {
-    const float *q;    // [n, ldq], RoPE applied
-    float *out;        // [n, ldo]
+// What the three attention forms share: the rows' queries, outputs and partials
+struct VerifyAttnGeom {
+    const float *q;    // [rows, ldq], RoPE applied
+    float *out;        // [rows, ldo]
     float *part_o;     // [kBatchMax, n_heads, seg_cap, head_size]
     float *part_ml;    // [kBatchMax, n_heads, seg_cap, 2]: max, sum
-    const float *kc, *vc;  // the layer's caches, head-major [kv head][seq_len][head_size]
     size_t kv_head_stride;
-    int ldq, ldo, n_heads, kv_mul, head_size, seg_cap, pos0;
+    int ldq, ldo, n_heads, kv_mul, head_size, seg_cap;
+};
+
+// l2z_verify, l2z_verify_sample (verify.hip): n rows of ONE sequence at consecutive positions tab->pos[i] = pos0 + i, all
+// on one cache.
+struct VerifyAttnArgs : VerifyAttnGeom {
+    const float *kc, *vc;  // the layer's caches, head-major [kv head][seq_len][head_size]
+    int pos0;
 };
 hipError_t launch_verify_attention(const VerifyAttnArgs &a, int n, hipStream_t st);
 hipError_t launch_verify_combine(const VerifyAttnArgs &a, int n, hipStream_t st);
 
-// The verdict of a verify pass, on the device: next[i] = argmax of logits + i * vocab (block_argmax_1024: the tie rule
-// of l2z_argmax_batch); a = the number of leading guesses tab->tokens[j] == next[j - 1], j = 1 ..; out[0 .. n) = next,
-// out[n] = a; row a of the logits matrix is copied to dst (the runstate's logits).  Two launches.
+// The verdict of a verify pass, on the device, in two launches.  First the rows' next ids into out[0 .. rows): the argmax
+// of logits + i * vocab (block_argmax_1024: the tie rule of l2z_argmax_batch) by launch_verify_argmax, or the draws of
+// launch_sample_batch (tab->logits[i] = logits + i * vocab, out = the same out) for a sampled pass.  Then the form's own
+// accept kernel.  The chain's: a = the number of leading guesses tab->tokens[j] == next[j - 1], j = 1 ..; out[n] = a; row
+// a of the logits matrix is copied to dst (the runstate's logits).
+hipError_t launch_verify_argmax(const float *logits, int vocab, int *out, int rows, hipStream_t st);
 hipError_t launch_verify_accept(const BatchTable *tab, const float *logits, int vocab, int *out, float *dst, int n,
                                 hipStream_t st);
-// The second of those launches alone, for next ids that already stand in out[0 .. n): l2z_verify_sample's rows are drawn
-// by launch_sample_batch (tab->logits[i] = logits + i * vocab, out = the same out) before it.
-hipError_t launch_verify_accept_ids(const BatchTable *tab, const float *logits, int vocab, int *out, float *dst, int n,
-                                    hipStream_t st);
 
 // l2z_verify_batch (verify_batch.hip): the rows of a step are GROUPS of consecutive positions, one group per sequence --
 // group j is rows first[j] .. first[j] + count[j] - 1 at positions pos0[j] .. of the sequence whose caches are kc[j] /
@@ -122,28 +130,21 @@ struct VerifyGroupTable {
     float *vc[kBatchMax];
     float *dst[kBatchMax];
 };
+static_assert(sizeof(BatchTable) % alignof(VerifyGroupTable) == 0, "the group table sits right behind the step's table");
 // Attention of every group in one launch per layer: block (head, segment, group) runs verify_attention_kernel's body
 // (verify_device.h) on the group's rows and the group's cache, so a row's partials are the bits l2z_verify leaves for
 // it.  The grid is (n_heads, max_segments, n_groups), max_segments = the deepest group's segment count; a block past
-// its own group's last segment returns at once.  Partials are indexed by the row's place in the step (part_o / part_ml
-// of VerifyAttnArgs); the combine takes a row's segment count from tab->pos[row].
-struct VerifyBatchAttnArgs {
-    const float *q;  // [rows, ldq], RoPE applied
-    float *out;      // [rows, ldo]
-    float *part_o, *part_ml;
+// its own group's last segment returns at once.  Partials are indexed by the row's place in the step; the combine takes
+// a row's segment count from tab->pos[row].
+struct VerifyBatchAttnArgs : VerifyAttnGeom {
     const BatchTable *tab;
     const VerifyGroupTable *groups;
     size_t layer_off;  // floats per layer of a cache
-    size_t kv_head_stride;
-    int ldq, ldo, n_heads, kv_mul, head_size, seg_cap;
 };
 hipError_t launch_verify_batch_attention(const VerifyBatchAttnArgs &a, int n_groups, int max_segments, hipStream_t st);
 hipError_t launch_verify_batch_combine(const VerifyBatchAttnArgs &a, int n_rows, hipStream_t st);
 // The verdict per group: group j's accept length a_j over its own rows (tab->tokens against out[0 .. n_rows), the rows'
 // next ids) -> out[n_rows + j]; row first[j] + a_j of the logits matrix -> groups->dst[j].  One launch.
-// launch_verify_batch_argmax fills out[0 .. n_rows) for a greedy pass (block_argmax_1024, as launch_verify_accept's
-// first launch); a sampled pass has launch_sample_batch fill it.
-hipError_t launch_verify_batch_argmax(const float *logits, int vocab, int *out, int n_rows, hipStream_t st);
 hipError_t launch_verify_batch_accept(const BatchTable *tab, const VerifyGroupTable *groups, const float *logits, int vocab,
                                       int *out, int n_rows, int n_groups, hipStream_t st);
 
@@ -157,27 +158,20 @@ struct VerifyTreeTable {
     uint32_t below[kBatchMax];  // bit i of below[j]: node j lies on the path root -> i (j == i included)
     uint32_t level[kBatchMax];  // bit i of level[d]: depth[i] == d
 };
+static_assert(sizeof(BatchTable) % alignof(VerifyTreeTable) == 0, "the tree table sits right behind the step's table");
 // Attention: block (head, segment) over kVerifySeg ABSOLUTE positions, the score buffer indexed by position as in
 // launch_verify_attention.  Row i finds the key of position t in cache row t for t < pos0 and in row pos0 + (its ancestor
 // of depth t - pos0) up to its own position; deeper positions are masked (weight exactly 0, V row skipped).  Every
 // summation order is verify_device.h's, so row i's partials are the bits l2z_verify leaves for row depth[i] of the chain
 // root -> i.  max_depth = the deepest node's depth; the grid is (n_heads, (pos0 + max_depth) / kVerifySeg + 1).
-struct VerifyTreeAttnArgs {
-    const float *q;  // [n, ldq], RoPE applied
-    float *out;      // [n, ldo]
-    float *part_o, *part_ml;
-    const float *kc, *vc;  // the layer's caches, head-major [kv head][seq_len][head_size]
+struct VerifyTreeAttnArgs : VerifyAttnArgs {
     const VerifyTreeTable *tree;
-    size_t kv_head_stride;
-    int ldq, ldo, n_heads, kv_mul, head_size, seg_cap, pos0;
 };
 hipError_t launch_verify_tree_attention(const VerifyTreeAttnArgs &a, int n, int max_depth, hipStream_t st);
 hipError_t launch_verify_tree_combine(const VerifyTreeAttnArgs &a, int n, int max_depth, hipStream_t st);
-// The verdict: out[0 .. n) = the rows' next ids (launch_verify_tree_argmax: block_argmax_1024 per row; a sampled pass has
-// launch_sample_batch fill them).  launch_verify_tree_accept walks the tree from the root -- while the node has a child
-// whose token is the node's next id, go there -- and leaves out[n] = a (edges walked), out[n + 1 + d] = the node at depth d
-// (d = 0 .. a), and the last node's row of the logits matrix in dst.
-hipError_t launch_verify_tree_argmax(const float *logits, int vocab, int *out, int n, hipStream_t st);
+// The verdict: launch_verify_tree_accept walks the tree from the root over the rows' next ids out[0 .. n) -- while the node
+// has a child whose token is the node's next id, go there -- and leaves out[n] = a (edges walked), out[n + 1 + d] = the node
+// at depth d (d = 0 .. a), and the last node's row of the logits matrix in dst.
 hipError_t launch_verify_tree_accept(const BatchTable *tab, const VerifyTreeTable *tree, const float *logits, int vocab, int *out,
                                      float *dst, int n, hipStream_t st);
 // The accepted path's K / V rows into place, read from the verdict on the device (res = launch_verify_tree_accept's out):

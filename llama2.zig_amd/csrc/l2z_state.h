@@ -11,7 +11,7 @@
 
 namespace l2z {
 
-struct BatchScratch;  // batch_host.cpp
+struct BatchScratch;  // batch_host.h
 
 // ----- shard geometry (DESIGN.md "Sharding"; world == 1 -> everything local) -----
 struct Shard {
@@ -196,11 +196,5 @@ int prefill_last_logits(l2z_runstate *s, const l2z_weights *w);
 
 // batch_host.cpp
 void batch_free(l2z_runstate *s);
-// the rules the batched calls share: the runstates of one call (check_states), and the pass on states[0]'s stream ordered
-// against every runstate's own stream (join before, release after)
-int batch_no_device_check();
-int batch_check_states(const char *fn, int n, l2z_runstate *const *states, const l2z_config *c);
-int batch_join_streams(int n, l2z_runstate *const *states);      // (allocates states[0]'s batch scratch: the events)
-int batch_release_streams(int n, l2z_runstate *const *states);
 
 }  // namespace l2z

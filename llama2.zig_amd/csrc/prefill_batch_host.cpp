@@ -7,7 +7,7 @@
 #include <cstring>
 #include <vector>
 
-#include "l2z_state.h"
+#include "batch_host.h"
 
 using namespace l2z;
 
@@ -46,10 +46,10 @@ extern "C" int l2z_prefill_batch(int n, const int32_t *tokens, const int32_t *n_
                                  const l2z_config *config, l2z_runstate *const *states, const l2z_weights *w)
 {
     // ---- checks: a refusal enqueues nothing and changes no state ----
-    L2Z_TRY(batch_no_device_check());
+    L2Z_TRY(no_device_check());
     L2Z_CHECK(tokens != nullptr && n_tokens != nullptr && pos0 != nullptr && config != nullptr && w != nullptr, L2Z_ERR_INVALID,
               "l2z_prefill_batch: null argument");
-    L2Z_TRY(batch_check_states("l2z_prefill_batch", n, states, config));
+    L2Z_TRY(check_states("l2z_prefill_batch", n, states, config));
     long long total_ll = 0;
     for (int j = 0; j < n; j++) {
         L2Z_TRY(check_pair(config, states[j], w));
@@ -80,7 +80,8 @@ extern "C" int l2z_prefill_batch(int n, const int32_t *tokens, const int32_t *n_
     L2Z_TRY(ragged_alloc(s0, longest));
 
     // ---- the pass, on states[0]'s stream: it waits for every runstate's stream ... ----
-    L2Z_TRY(batch_join_streams(n, states));
+    L2Z_TRY(batch_alloc(s0));  // (the events)
+    L2Z_TRY(join_streams(s0->bt, n, states));
     int first[kRaggedMaxSeq];   // a sequence's first row among the concatenated rows
     for (int j = 0, g = 0; j < n; g += n_tokens[j], j++) first[j] = g;
     std::vector<unsigned char> h_tab(tab_bytes(s0->rg_cap));
@@ -131,7 +132,7 @@ extern "C" int l2z_prefill_batch(int n, const int32_t *tokens, const int32_t *n_
     }
     // ---- ... and every runstate's stream waits for the pass: the usual final rmsnorm + classifier launch (:426-429) of
     // each runstate, on its own stream, leaves its logits in place ----
-    L2Z_TRY(batch_release_streams(n, states));
+    L2Z_TRY(release_streams(s0->bt, n, states));
     int last_pos[kRaggedMaxSeq], last_tok[kRaggedMaxSeq];
     for (int j = 0; j < n; j++) {
         l2z_runstate *s = states[j];

@@ -1,7 +1,7 @@
-// verify.hip -- the kernels l2z_verify adds to the batched step (host side: batch_host.cpp): attention for n rows of ONE
+// verify.hip -- the kernels l2z_verify adds to the batched step (host side: verify_host.cpp): attention for n rows of ONE
 // sequence at consecutive positions, and the verdict (per-row argmax, accept length, hand-over of the accepted logits).
 // l2z_verify_sample runs the same pass; its rows' ids come from sample_batch_kernel (sample_batch.hip) instead of the
-// argmax, and the accept scan and hand-over here run against those (launch_verify_accept_ids).
+// argmax.  The argmax also serves the greedy passes of l2z_verify_batch and l2z_verify_tree.
 //
 // DRAFT INVARIANCE (include/llama2_hip.h): what a row at position p computes is a function of p and the tokens 0 .. p.
 // Here that means: the segment grid is fixed in ABSOLUTE positions (kVerifySeg keys per segment), a key the row may not
@@ -38,8 +38,8 @@ __global__ __launch_bounds__(1024) void verify_argmax_kernel(const float *logits
     if (threadIdx.x == 0) out[blockIdx.x] = bi;
 }
 
-// out[0 .. n) = the rows' next ids (verify_argmax_kernel, or sample_batch_kernel for a sampled pass).  Every block finds the accept length a itself (at most 15
-// compares), block 0 writes it to out[n]; row a of the logits matrix -> dst.
+// out[0 .. n) = the rows' next ids (verify_argmax_kernel, or sample_batch_kernel for a sampled pass).  Every block finds
+// the accept length a itself (at most 15 compares), block 0 writes it to out[n]; row a of the logits matrix -> dst.
 __global__ __launch_bounds__(256) void verify_accept_kernel(const BatchTable *tab, const float *logits, int vocab, int *out,
                                                             float *dst, int n)
 {
@@ -58,8 +58,7 @@ __global__ __launch_bounds__(256) void verify_accept_kernel(const BatchTable *ta
 
 bool verify_args_ok(const VerifyAttnArgs &a, int n)
 {
-    return n >= 1 && n <= kBatchMax && a.head_size >= 4 && a.head_size <= 256 && (a.head_size & 3) == 0 && a.pos0 >= 0 &&
-           (a.pos0 + n - 1) / kVerifySeg < a.seg_cap;
+    return n >= 1 && n <= kBatchMax && a.pos0 >= 0 && verify_geom_ok(a, (a.pos0 + n - 1) / kVerifySeg + 1);
 }
 
 }  // namespace
@@ -79,18 +78,15 @@ hipError_t launch_verify_combine(const VerifyAttnArgs &a, int n, hipStream_t st)
     return hipGetLastError();
 }
 
-hipError_t launch_verify_accept(const BatchTable *tab, const float *logits, int vocab, int *out, float *dst, int n,
-                                hipStream_t st)
+hipError_t launch_verify_argmax(const float *logits, int vocab, int *out, int rows, hipStream_t st)
 {
-    if (n < 1 || n > kBatchMax || vocab < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(verify_argmax_kernel, dim3(n), dim3(1024), 0, st, logits, vocab, out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_verify_accept_ids(tab, logits, vocab, out, dst, n, st);
+    if (rows < 1 || rows > kBatchMax || vocab < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(verify_argmax_kernel, dim3(rows), dim3(1024), 0, st, logits, vocab, out);
+    return hipGetLastError();
 }
 
-hipError_t launch_verify_accept_ids(const BatchTable *tab, const float *logits, int vocab, int *out, float *dst, int n,
-                                    hipStream_t st)
+hipError_t launch_verify_accept(const BatchTable *tab, const float *logits, int vocab, int *out, float *dst, int n,
+                                hipStream_t st)
 {
     if (n < 1 || n > kBatchMax || vocab < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(verify_accept_kernel, dim3((vocab + 255) / 256), dim3(256), 0, st, tab, logits, vocab, out, dst, n);

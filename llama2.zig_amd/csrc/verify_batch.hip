@@ -1,4 +1,4 @@
-// verify_batch.hip -- the kernels l2z_verify_batch adds to the batched step (host side: batch_host.cpp): the verify pass
+// verify_batch.hip -- the kernels l2z_verify_batch adds to the batched step (host side: verify_host.cpp): the verify pass
 // of verify.hip for the rows of SEVERAL sequences at once.  Group j of VerifyGroupTable is one sequence's consecutive
 // positions on that sequence's own cache; attention, combine and verdict run per group in one launch each.
 //
@@ -21,16 +21,14 @@ __global__ __launch_bounds__(kVaBlock) void verify_batch_attention_kernel(const 
     const VerifyGroupTable *gt = b.groups;
     const int first = gt->first[grp], n = gt->count[grp], pos0 = gt->pos0[grp];
     if (seg > (pos0 + n - 1) / kVerifySeg) return;
-    VerifyAttnArgs a;
-    a.q = b.q + (size_t)first * b.ldq;
-    a.out = nullptr;  // (the combine's)
-    a.part_o = b.part_o + (size_t)first * b.n_heads * b.seg_cap * b.head_size;
-    a.part_ml = b.part_ml + (size_t)first * b.n_heads * b.seg_cap * 2;
+    VerifyAttnArgs a;  // the group as a call of its own: its rows, its cache, its pos0
+    static_cast<VerifyAttnGeom &>(a) = b;  // (out is the combine's: the body does not look at it)
+    a.q += (size_t)first * b.ldq;
+    a.part_o += (size_t)first * b.n_heads * b.seg_cap * b.head_size;
+    a.part_ml += (size_t)first * b.n_heads * b.seg_cap * 2;
     a.kc = gt->kc[grp] + b.layer_off;
     a.vc = gt->vc[grp] + b.layer_off;
-    a.kv_head_stride = b.kv_head_stride;
-    a.ldq = b.ldq; a.ldo = b.ldo; a.n_heads = b.n_heads; a.kv_mul = b.kv_mul; a.head_size = b.head_size;
-    a.seg_cap = b.seg_cap; a.pos0 = pos0;
+    a.pos0 = pos0;
     verify_attention_body(a, n, blockIdx.x, seg, sc);
 }
 
@@ -40,14 +38,6 @@ __global__ __launch_bounds__(64) void verify_batch_combine_kernel(const VerifyBa
     const int h = blockIdx.x, i = blockIdx.y;
     verify_combine_body(b.part_o, b.part_ml, ((size_t)i * b.n_heads + h) * b.seg_cap, b.tab->pos[i] / kVerifySeg + 1, b.head_size,
                         b.out + (size_t)i * b.ldo + (size_t)h * b.head_size);
-}
-
-__global__ __launch_bounds__(1024) void verify_batch_argmax_kernel(const float *logits, int vocab, int *out)
-{
-    __shared__ float s_val[16];
-    __shared__ int s_idx[16];
-    const int bi = block_argmax_1024(logits + (size_t)blockIdx.x * vocab, vocab, s_val, s_idx);
-    if (threadIdx.x == 0) out[blockIdx.x] = bi;
 }
 
 // Block (x, group): verify_accept_kernel per group.  Every block finds its group's accept length itself over the group's
@@ -72,33 +62,24 @@ __global__ __launch_bounds__(256) void verify_batch_accept_kernel(const BatchTab
     if (blockIdx.x == 0 && threadIdx.x == 0) out[n_rows + grp] = acc;
 }
 
-bool verify_batch_args_ok(const VerifyBatchAttnArgs &a)
+bool verify_batch_args_ok(const VerifyBatchAttnArgs &a, int nseg)
 {
-    return a.head_size >= 4 && a.head_size <= 256 && (a.head_size & 3) == 0 && a.seg_cap >= 1 && a.n_heads >= 1 &&
-           a.tab != nullptr && a.groups != nullptr;
+    return verify_geom_ok(a, nseg) && a.n_heads >= 1 && a.tab != nullptr && a.groups != nullptr;
 }
 
 }  // namespace
 
 hipError_t launch_verify_batch_attention(const VerifyBatchAttnArgs &a, int n_groups, int max_segments, hipStream_t st)
 {
-    if (!verify_batch_args_ok(a) || n_groups < 1 || n_groups > kBatchMax || max_segments < 1 || max_segments > a.seg_cap)
-        return hipErrorInvalidValue;
+    if (!verify_batch_args_ok(a, max_segments) || n_groups < 1 || n_groups > kBatchMax) return hipErrorInvalidValue;
     hipLaunchKernelGGL(verify_batch_attention_kernel, dim3(a.n_heads, max_segments, n_groups), dim3(kVaBlock), 0, st, a);
     return hipGetLastError();
 }
 
 hipError_t launch_verify_batch_combine(const VerifyBatchAttnArgs &a, int n_rows, hipStream_t st)
 {
-    if (!verify_batch_args_ok(a) || n_rows < 1 || n_rows > kBatchMax) return hipErrorInvalidValue;
+    if (!verify_batch_args_ok(a, 1) || n_rows < 1 || n_rows > kBatchMax) return hipErrorInvalidValue;
     hipLaunchKernelGGL(verify_batch_combine_kernel, dim3(a.n_heads, n_rows), dim3(64), 0, st, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_verify_batch_argmax(const float *logits, int vocab, int *out, int n_rows, hipStream_t st)
-{
-    if (n_rows < 1 || n_rows > kBatchMax || vocab < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(verify_batch_argmax_kernel, dim3(n_rows), dim3(1024), 0, st, logits, vocab, out);
     return hipGetLastError();
 }
 

@@ -1,4 +1,4 @@
-// verify_tree.hip -- the kernels l2z_verify_tree adds to the batched step (host side: batch_host.cpp): the verify pass of
+// verify_tree.hip -- the kernels l2z_verify_tree adds to the batched step (host side: verify_host.cpp): the verify pass of
 // verify.hip for the nodes of a TREE of guesses.  Node i stands for position pos0 + depth_i; its K / V rows sit in
 // PHYSICAL cache row pos0 + i (the G_QKV_ROWS epilogue stores there through a shifted base), and row i attends to the cache
 // rows below pos0 and to its own ancestors' rows.
@@ -106,34 +106,7 @@ __global__ __launch_bounds__(kVaBlock) void verify_tree_attention_kernel(const V
         }
     }
     __syncthreads();
-    // per row: m = max, e = exp(s - m) in place, l = sum e (verify_attention_body's sweep)
-    {
-        const int lane = tid & 63;
-        for (int i = tid >> 6; i < kBatchMax; i += kVaBlock / 64)
-            if ((act >> i) & 1u) {
-                float *r = sc + i * kVerifySeg;
-                float sv[kVaPerLane], m = -INFINITY;
-#pragma unroll
-                for (int j = 0; j < kVaPerLane; j++) {
-                    sv[j] = lane + 64 * j < nk ? r[lane + 64 * j] : -INFINITY;
-                    m = fmaxf(m, sv[j]);
-                }
-                m = wave_max(m);  // finite: the row sees slot 0 of a segment that starts at or below its position
-                float l = 0.0f;
-#pragma unroll
-                for (int j = 0; j < kVaPerLane; j++) {
-                    const float e = expf(sv[j] - m);
-                    if (lane + 64 * j < nk) r[lane + 64 * j] = e;
-                    l += e;
-                }
-                l = wave_sum(l);
-                if (lane == 0) {
-                    float *ml = a.part_ml + (((size_t)i * a.n_heads + h) * a.seg_cap + seg) * 2;
-                    ml[0] = m;
-                    ml[1] = l;
-                }
-            }
-    }
+    verify_softmax_sweep(a, h, seg, act, nk, sc);
     __syncthreads();
     // acc_i = sum over slots of e[i][slot] v: group g takes slots g, g + G, ... in increasing slot -- its context slots ...
     v4f acc[kBatchMax];
@@ -192,24 +165,7 @@ __global__ __launch_bounds__(kVaBlock) void verify_tree_attention_kernel(const V
             }
     }
     __syncthreads();
-    // the groups' sums combined in g order, four rows per round through the score buffer
-    v4f *buf = (v4f *)sc;
-#pragma unroll
-    for (int r = 0; r < kBatchMax / 4; r++)
-        if ((act >> (4 * r)) & 0xFu) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) buf[j * kVaBlock + tid] = acc[4 * r + j];
-            __syncthreads();
-            if (tid < 4 * TPR) {
-                const int j = tid / TPR, cc = tid % TPR, i = 4 * r + j;
-                if (cc < E && ((act >> i) & 1u)) {
-                    v4f o = buf[j * kVaBlock + cc];
-                    for (int gg = 1; gg < G; gg++) o += buf[j * kVaBlock + gg * TPR + cc];
-                    *(v4f *)(a.part_o + (((size_t)i * a.n_heads + h) * a.seg_cap + seg) * hs + 4 * cc) = o;
-                }
-            }
-            __syncthreads();
-        }
+    verify_group_fold(a, h, seg, act, acc, TPR, sc);
 }
 
 // Block (h, i): row i's segments 0 .. (pos0 + depth_i) / kVerifySeg folded in segment order, then the divide
@@ -218,14 +174,6 @@ __global__ __launch_bounds__(64) void verify_tree_combine_kernel(const VerifyTre
     const int h = blockIdx.x, i = blockIdx.y;
     verify_combine_body(a.part_o, a.part_ml, ((size_t)i * a.n_heads + h) * a.seg_cap, (a.pos0 + a.tree->depth[i]) / kVerifySeg + 1,
                         a.head_size, a.out + (size_t)i * a.ldo + (size_t)h * a.head_size);
-}
-
-__global__ __launch_bounds__(1024) void verify_tree_argmax_kernel(const float *logits, int vocab, int *out)
-{
-    __shared__ float s_val[16];
-    __shared__ int s_idx[16];
-    const int bi = block_argmax_1024(logits + (size_t)blockIdx.x * vocab, vocab, s_val, s_idx);
-    if (threadIdx.x == 0) out[blockIdx.x] = bi;
 }
 
 // out[0 .. n) = the rows' next ids.  Every block walks the tree itself (cur = 0; while cur has a child whose token is
@@ -279,8 +227,8 @@ __global__ __launch_bounds__(256) void verify_tree_compact_kernel(float *kc, flo
 
 bool verify_tree_args_ok(const VerifyTreeAttnArgs &a, int n, int max_depth)
 {
-    return n >= 1 && n <= kBatchMax && max_depth >= 0 && max_depth < n && a.head_size >= 4 && a.head_size <= 256 &&
-           (a.head_size & 3) == 0 && a.pos0 >= 0 && (a.pos0 + max_depth) / kVerifySeg < a.seg_cap && a.tree != nullptr;
+    return n >= 1 && n <= kBatchMax && max_depth >= 0 && max_depth < n && a.pos0 >= 0 && a.tree != nullptr &&
+           verify_geom_ok(a, (a.pos0 + max_depth) / kVerifySeg + 1);
 }
 
 }  // namespace
@@ -297,13 +245,6 @@ hipError_t launch_verify_tree_combine(const VerifyTreeAttnArgs &a, int n, int ma
 {
     if (!verify_tree_args_ok(a, n, max_depth)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(verify_tree_combine_kernel, dim3(a.n_heads, n), dim3(64), 0, st, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_verify_tree_argmax(const float *logits, int vocab, int *out, int n, hipStream_t st)
-{
-    if (n < 1 || n > kBatchMax || vocab < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(verify_tree_argmax_kernel, dim3(n), dim3(1024), 0, st, logits, vocab, out);
     return hipGetLastError();
 }
 
