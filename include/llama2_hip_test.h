@@ -134,6 +134,20 @@ int l2z_prefill_split_k(long long n_features_whole, int n_tokens, int k, int pai
  * STREAM form of that kernel (chunks of L2Z_PF_X3_STREAM_MIN = 33 ... 128 tokens) with n - 1 K ranges per output tile -- part of
  * the arithmetic, a function of the chunk length and the WHOLE model's matrix.  k: the product's K (rounded up to 64 here). */
 int l2z_prefill_cores(long long n_features_whole, int n_tokens, int k);
+/* Which kernel a product of the batched prefill takes, and in which form (host logic; the CU count is the current device's,
+ * 256 without one).  shape: kind 0 one matrix (epi: 0 store, 1 residual, 2 RoPE, 3 RoPE into the key cache, 4 into the value
+ * cache, 5 SwiGLU merge), 1 q | k | v fused (n_features = nq + 2 nkv), 2 W1 | W3 paired (n_features of each; w13_one_matrix:
+ * their rows alternate in one slot), 3 k | v paired; n_features / nq / nkv are THIS rank's rows of n_scale ranks;
+ * n_launch_whole: rows of the whole model's launch the product is a part of (0: n_features * n_scale); sk: l2z_prefill_split_k
+ * of the whole product; part_floats, cnt_ints: the split workspace.  plan: family 1 stream, 2 short-prompt (tms token tiles
+ * of 16 per block, paired), 3 split-K, 4 k-groups on two blocks, 5 tile; -1 invalid, -2 not supported (launch the products
+ * apart), -3 the workspace is too small.  epi: the kernel's epilogue (6 q | k | v, 7 W1 | W3 interleaved); k: K as the kernel
+ * walks it; x3: on the bf16 cores; sk: K ranges per tile; tile: as l2z_prefill_tile; stream form: feat features per block, tm
+ * token tiles of 32, ring depth nbuf, one_round: one block per CU. */
+typedef struct { int kind, epi, n_tokens, n_features, k, ldx, n_scale, sk, nq, nkv, w13_one_matrix, cnt_ints;
+                 long long n_launch_whole, part_floats; } l2z_gemm_shape;
+typedef struct { int family, epi, k, x3, sk, tile, feat, tm, nbuf, one_round, tms, paired; } l2z_gemm_plan;
+int l2z_prefill_gemm_plan(const l2z_gemm_shape *shape, l2z_gemm_plan *plan);
 
 /* ---- emulated ranks ---- */
 /* Testing support: N emulated ranks in ONE process on ONE GPU (RCCL refuses two ranks on

@@ -162,6 +162,8 @@ def lib():
     L.l2z_prefill_tile.argtypes = [C.c_int, C.c_int, C.c_int]
     if hasattr(L, "l2z_prefill_cores"):
         L.l2z_prefill_cores.argtypes = [C.c_longlong, C.c_int, C.c_int]
+    if hasattr(L, "l2z_prefill_gemm_plan"):
+        L.l2z_prefill_gemm_plan.argtypes = [C.POINTER(GemmShape), C.POINTER(GemmPlan)]
     if hasattr(L, "l2z_prefill_split_k"):
         L.l2z_prefill_split_k.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int]
     L.l2z_emu_prefill.argtypes = [C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int32), C.c_int, C.c_int]
@@ -1021,6 +1023,38 @@ def prefill_split_k(n_features_whole: int, n_tokens: int, k: int, paired: bool =
     if r < 0:
         raise L2ZError(r, lib().l2z_last_error().decode(errors="replace"))
     return r
+
+
+class GemmShape(C.Structure):
+    """include/llama2_hip_test.h l2z_gemm_shape."""
+    _fields_ = [(n, C.c_int) for n in ("kind", "epi", "n_tokens", "n_features", "k", "ldx", "n_scale", "sk", "nq", "nkv",
+                                       "w13_one_matrix", "cnt_ints")] + [("n_launch_whole", C.c_longlong), ("part_floats", C.c_longlong)]
+
+
+class GemmPlan(C.Structure):
+    """include/llama2_hip_test.h l2z_gemm_plan."""
+    _fields_ = [(n, C.c_int) for n in ("family", "epi", "k", "x3", "sk", "tile", "feat", "tm", "nbuf", "one_round", "tms", "paired")]
+
+
+GEMM_KINDS = ("single", "qkv", "w13", "kv")
+GEMM_FAMILIES = {-1: "invalid", -2: "not supported", -3: "no workspace", 1: "stream", 2: "short", 3: "split-k", 4: "two-block", 5: "tile"}
+
+
+def prefill_gemm_plan(kind: str, n_tokens: int, n_features: int, k: int, **kw) -> dict:
+    """The kernel form a product of the batched prefill takes (host logic): l2z_prefill_gemm_plan's plan as a dict, `family`
+    and `tile` by name.  kw: the other fields of l2z_gemm_shape; ldx defaults to the pass's padded rows (multiples of 256,
+    at least 768), the workspace to a large one."""
+    sh = GemmShape(kind=GEMM_KINDS.index(kind), n_tokens=n_tokens, n_features=n_features, k=k, n_scale=1, sk=1,
+                   ldx=max(768, (k + 255) // 256 * 256), part_floats=1 << 40, cnt_ints=1 << 16)
+    for name, v in kw.items():
+        if name not in dict(GemmShape._fields_):
+            raise TypeError(name)
+        setattr(sh, name, int(v))
+    pl = GemmPlan()
+    _chk(lib().l2z_prefill_gemm_plan(C.byref(sh), C.byref(pl)))
+    d = {n: getattr(pl, n) for n, _ in GemmPlan._fields_}
+    d["family"], d["tile"] = GEMM_FAMILIES[pl.family], TILE_FORMS[pl.tile]
+    return d
 
 
 def prefill_cores(n_features_whole: int, n_tokens: int, k: int) -> int:

@@ -179,17 +179,6 @@ int upload_table(BatchScratch *b, const BatchTable &t, hipStream_t st, const voi
     return L2Z_OK;
 }
 
-namespace {
-
-GemmArgs gemm(const float *x, int ldx, const float *w, int ldw, int N, int K, int P)
-{
-    GemmArgs a = {};
-    a.x = x; a.ldx = ldx; a.w = w; a.ldw = ldw; a.N = N; a.K = K; a.P = P; a.n_scale = 1;
-    return a;
-}
-
-}  // namespace
-
 // Every product is the one-tile short-prompt form at P = n whatever n is (launch_batch_skinny): a row's bits do not depend
 // on n, on the other rows, or on its place in the batch.
 int batch_step(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *w, BatchScratch *b, LayerAttention attention)

@@ -307,3 +307,16 @@ extern "C" int l2z_prefill_tile(int n_features, int n_tokens, int paired)
     L2Z_CHECK(n_features > 0 && n_tokens > 0, L2Z_ERR_INVALID, "l2z_prefill_tile: bad arguments");
     return prefill_tile_form(n_features, n_tokens, paired);
 }
+
+extern "C" int l2z_prefill_gemm_plan(const l2z_gemm_shape *shape, l2z_gemm_plan *plan)
+{
+    L2Z_CHECK(shape != nullptr && plan != nullptr, L2Z_ERR_INVALID, "l2z_prefill_gemm_plan: null argument");
+    GemmShape g = {};
+    g.kind = shape->kind; g.epi = shape->epi; g.P = shape->n_tokens; g.N = shape->n_features; g.K = shape->k; g.ldx = shape->ldx;
+    g.n_scale = shape->n_scale; g.n_launch_whole = shape->n_launch_whole; g.sk = shape->sk; g.nq = shape->nq; g.nkv = shape->nkv;
+    g.w13_one_matrix = shape->w13_one_matrix; g.part_floats = (size_t)shape->part_floats; g.cnt_ints = shape->cnt_ints;
+    const GemmPlan p = prefill_gemm_plan(g);
+    static_assert(sizeof(l2z_gemm_plan) == sizeof(GemmPlan), "include/llama2_hip_test.h l2z_gemm_plan");
+    memcpy(plan, &p, sizeof p);
+    return L2Z_OK;
+}

@@ -253,9 +253,9 @@ struct DeferredSum {
     int sk, feat, tm;    // K ranges per tile, features per tile (128 / 192 / 256), token tiles of 32
     bool valid;
 };
-// launch_prefill_gemm*'s planes argument: the consumer's planes are not there yet (the launcher splits x into ws->x3), stand
-// in ws->x3 (the launch before multiplied the same x, or x's producer wrote them), or stand in ws->x3b
-enum { PLANES_SPLIT = 0, PLANES_READY = 1, PLANES_READY_B = 2 };
+// GemmLaunch::planes_ready: the consumer's planes are not there yet (the launcher splits x into ws->x3), stand in ws->x3 (the
+// launch before multiplied the same x, or x's producer wrote them), or stand in ws->x3b.  (A named enum: a bool does not convert.)
+enum PlanesReady { PLANES_SPLIT = 0, PLANES_READY = 1, PLANES_READY_B = 2 };
 constexpr int kSplitKMaxTokens = 256;  // longest chunk the split-K family takes
 constexpr int kPanelWsRows = 6 * kSplitKMaxTokens;  // rows of the widest launch the partial-product workspace holds (panel kernel: ranges x 16 tms)
 // K ranges per output tile for a [P, K] x [n_whole, K]^T product (1: the unsplit family).  Part of the
@@ -263,38 +263,47 @@ constexpr int kPanelWsRows = 6 * kSplitKMaxTokens;  // rows of the widest launch
 int prefill_split_k(long long n_whole, int P, int K, bool pair);
 enum PrefillGemmEpi { PG_STORE = 0, PG_RESID = 1, PG_ROPE = 2, PG_ROPE_CACHE = 3, PG_CACHE = 4,
                       PG_SWIGLU = 5 };  // out = silu(out) * (X W^T): the W3 product merged into W1's
-// PG_RESID: out = res + X W^T (res == nullptr: in place, res = out, ldres = ldo)
-hipError_t launch_prefill_gemm(int epi, const float *x, int ldx, const float *w, float *out, int ldo,
-                               int P, int N, int K, int pos0, const float2 *rope, int head_size,
-                               hipStream_t st, const float *res = nullptr, int ldres = 0,
-                               int n_scale = 1,  // n_scale: ranks the rows are sharded over (kernel-form choices look at the whole matrix)
-                               size_t kv_head_stride = 0,  // PG_*CACHE: out is a head-major cache (MatvecArgs::kv_head_stride)
-                               int sk = 1, const SplitKWs *ws = nullptr,   // sk > 1: the split-K family (prefill_split_k)
-                               int ldw = 0,   // floats between rows of w (0: K; W1 / W3 of the device blob: 2 K)
-                               long long n_launch_whole = 0,   // rows of the whole model's launch this product is a part of (q, k, v
-                                                               // launched apart: dim + 2 kv_dim; 0: N * n_scale) -- the stream form's K ranges
-                               int planes_ready = PLANES_SPLIT,    // PLANES_*: whether x's planes stand already, and where
-                               DeferredSum *defer = nullptr);      // PG_RESID: != null: the launch MAY leave its K ranges' sums to the next
-                                                                   // rmsnorm launch (sets valid; the stream form with > 1 range does)
 // the stream form of the planes kernel (prefill_gemm.hip): which products take it, and their K ranges
 bool x3_applies(long long n_whole, int K);
 bool x3_stream_shape(long long n_whole, int P, int K);
 int x3_stream_sk(long long n_whole, int P, int K);
-hipError_t launch_prefill_gemm_qkv(const float *x, int ldx, const float *wq, const float *wk, const float *wv,
-                                   float *q_out, int ldq, float *kcache, float *vcache, int ldkv, int P, int nq,
-                                   int nkv, int K, int pos0, const float2 *rope, int head_size, hipStream_t st,
-                                   size_t kv_head_stride = 0, int n_scale = 1, int sk = 1, const SplitKWs *ws = nullptr,
-                                   int planes_ready = PLANES_SPLIT);
-// planes_out: the launch may ALSO leave the planes of its output (K' = N columns, kp_out >= N bf16 per plane row) in
-// ws->x3b; *planes_written says whether the form that ran did (the stream form does)
-hipError_t launch_prefill_gemm_swiglu_pair(const float *x, int ldx, const float *w1, const float *w3,
-                                           float *out, int ldo, int P, int N, int K, hipStream_t st,
-                                           int n_scale = 1, int sk = 1, const SplitKWs *ws = nullptr, int ldw = 0,
-                                           int planes_ready = PLANES_SPLIT, int kp_out = 0, bool *planes_written = nullptr);
-hipError_t launch_prefill_gemm_kv_pair(const float *x, int ldx, const float *wk, const float *wv, float *kcache,
-                                       float *vcache, int ldkv, int P, int nkv, int K, int pos0, const float2 *rope,
-                                       int head_size, hipStream_t st, int n_scale = 1, size_t kv_head_stride = 0,
-                                       int sk = 1, long long n_launch_whole = 0);
+// ---- which kernel form a product of the batched pass takes (prefill_gemm.hip prefill_gemm_plan; the launchers themselves:
+// prefill_common.h launch_prefill_gemm) ----
+enum GemmKind { GEMM_SINGLE = 0,   // one matrix, the epilogue a PrefillGemmEpi
+                GEMM_QKV,          // q | k | v of a layer in one launch (N = nq + 2 nkv)
+                GEMM_W13,          // W1 | W3 in one launch, silu(a) * b in the epilogue (N = features of each)
+                GEMM_KV };         // k | v in one launch (short prompts; N = nkv)
+// everything the choice looks at: numbers only
+struct GemmShape {
+    int kind, epi;                 // GemmKind; PrefillGemmEpi (GEMM_SINGLE only)
+    int P, N, K, ldx;
+    int n_scale;                   // ranks the rows are sharded over: the choice looks at the WHOLE model's matrix
+    long long n_launch_whole;      // GemmLaunch::n_launch_whole
+    int sk;                        // GemmLaunch::sk
+    int nq, nkv;                   // GEMM_QKV
+    int w13_one_matrix;            // GEMM_W13: W1 and W3 alternate row by row in one slot (ldw == 2 K, w3 == w1 + K)
+    size_t part_floats;            // SplitKWs' sizes (0: not there)
+    int cnt_ints;
+};
+enum GemmFamily { GF_INVALID = -1, GF_NOT_SUPPORTED = -2, GF_NO_WORKSPACE = -3,   // hipErrorInvalidValue / NotSupported / OutOfMemory
+                  GF_STREAM = 1,   // the stream form of the planes kernel
+                  GF_SHORT,        // the short-prompt kernels (prefill_skinny.hip)
+                  GF_SPLIT_K,      // the tile kernel, sk K ranges per tile
+                  GF_TWO_BLOCK,    // the tile kernel, a tile's two k-groups on two blocks
+                  GF_TILE };       // the tile kernel
+enum TileForm { TILE_128x64 = 0, TILE_64x64, TILE_32x64, TILE_32x32, TILE_128x128 };
+struct GemmPlan {
+    int family;                    // GemmFamily
+    int epi;                       // the kernel's epilogue (GemmEpi: G_QKV, G_SWIGLU_IL, ... for the fused kinds)
+    int K;                         // K as the kernel walks it (pad_k)
+    int x3;                        // 1: the bf16 matrix cores multiply it
+    int sk;                        // K ranges per output tile (stream, split-K)
+    int tile;                      // TileForm (split-K, two-block, tile)
+    int feat, tm, nbuf, one_round; // stream: features per block (128 / 192 / 256), token tiles of 32, ring depth, one block per CU
+    int tms, paired;               // short-prompt: token tiles of 16 per block (1 / 2), two matrices in one launch
+};
+// Pure: launches nothing; its only look at the device is the CU count (256 without one).
+GemmPlan prefill_gemm_plan(const GemmShape &s);
 hipError_t launch_prefill_rmsnorm(float *o, int ldo, const float *x, const float *w, int n, int P,
                                   hipStream_t st,    // o: rows of ldo floats (the pad columns are left alone)
                                   void *x3 = nullptr, int kp = 0,    // != null: o's planes of bf16 terms too (x3[token][3][kp], kp == n)
@@ -369,7 +378,7 @@ int prefill_next_chunk_of(const l2z_config &c, int remaining);
 // hipErrorNotSupported: this rank's rows / pointers / workspace do not take the kernel (rows % 16, alignment) -- callers that
 // asked prefill_panel_shape first treat that as an error on a shard (the unsharded pass would have taken it)
 hipError_t launch_prefill_panel(const PanelProduct &p, int n_cus, const SplitKWs *ws, hipStream_t st);
-int prefill_tile_form(int N, int P, int pair);  // 0: 128x64, 1: 64x64, 2: 32x64, 3: 32x32, 4: 128x128
+int prefill_tile_form(int N, int P, int pair);  // TileForm
 // ---- score.hip: l2z_score's reductions over the classifier logits of a chunk, one vocabulary slab at a time ----
 constexpr int kScoreSeg = 4096;   // columns per segment of the reduction: slabs are whole segments, so the sums never depend on the slab
 struct ScoreArgs {

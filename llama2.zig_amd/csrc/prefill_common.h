@@ -203,9 +203,37 @@ inline int pad_k(int K, int granule, int ldx)
     return ke <= ldx ? ke : -1;
 }
 
+// A product's operands and shape by name; the caller adds the epilogue's inputs (out, res, rope, the caches ...).
+inline GemmArgs gemm(const float *x, int ldx, const float *w, int ldw, int N, int K, int P)
+{
+    GemmArgs a = {};
+    a.x = x; a.ldx = ldx; a.w = w; a.ldw = ldw; a.N = N; a.K = K; a.P = P; a.n_scale = 1;
+    return a;
+}
+
+// What a launch of the batched pass needs beside the kernel's arguments.
+struct GemmLaunch {
+    int sk = 1;                               // > 1: the split-K family (prefill_split_k)
+    const SplitKWs *ws = nullptr;
+    long long n_launch_whole = 0;             // rows of the whole model's launch this product is a part of (q, k, v launched
+                                              // apart: dim + 2 kv_dim; 0: N * n_scale) -- the stream form's K ranges
+    PlanesReady planes_ready = PLANES_SPLIT;  // whether x's planes stand already, and where
+    DeferredSum *defer = nullptr;             // PG_RESID: != null: the launch MAY leave its K ranges' sums to the next rmsnorm
+                                              // launch (sets valid; the stream form with > 1 range does)
+    int kp_out = 0;                           // GEMM_W13: the launch may ALSO leave the planes of its output (K' = N columns,
+                                              // kp_out >= N bf16 per plane row) in ws->x3b ...
+    bool planes_written = false;              // ... result: whether the form that ran did
+};
+// C[P,N] (+)= X[P,K] W[N,K]^T with the kind's epilogue; K % 4 == 0, 16-byte aligned rows.  a: GEMM_SINGLE w, out (PG_RESID:
+// res, null: in place); GEMM_QKV w = wq, wk, wv, out = q, outk, outv, nq, nkv, ldkv; GEMM_W13 w = W1, w2 = W3; GEMM_KV w = wk,
+// w2 = wv, outk, outv, ldkv.  a.ldw 0: K.  hipErrorNotSupported (the fused kinds): the shape does not take one launch -- the
+// caller launches the products apart.
+hipError_t launch_prefill_gemm(GemmKind kind, int epi, const GemmArgs &a, GemmLaunch &l, hipStream_t st);
+
 // prefill_skinny.hip: the short-prompt (P <= 64 tokens) GEMM forms; picks the form and the token tiling
 hipError_t launch_prefill_skinny(int epi, const GemmArgs &a, hipStream_t st);
 hipError_t launch_prefill_skinny_pair(int epi, const GemmArgs &a, hipStream_t st);  // G_SWIGLU: w | w2 gated; G_QKV: wk | wv
+bool skinny_one_tile(long long n_whole, int K, int P);   // one token tile of 16 per block (the paired form needs it), or two
 // the batched decode step's products (G_ROPE_ROWS, G_OUT_ROWS; G_QKV_ROWS paired): the one-tile form at every P <= 16
 hipError_t launch_batch_skinny(int epi, const GemmArgs &a, hipStream_t st);
 

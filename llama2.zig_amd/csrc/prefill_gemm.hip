@@ -98,7 +98,6 @@ static int g_cus_hint()
 // efficiencies from interleaved A/B runs on the 7B and 110M shapes (larger tiles bring
 // fewer bytes per flop into the CU).  The 7B shape at 512 tokens keeps 128 x 64; 65..128-token prompts,
 // small models and row shards (N / world features) take the 32-token forms.
-enum TileForm { TILE_128x64 = 0, TILE_64x64, TILE_32x64, TILE_32x32, TILE_128x128 };
 static TileForm choose_tile(int N, int P, bool pair)
 {
     const long long cus = g_cus_hint();
@@ -1053,64 +1052,64 @@ DmaForm dma_form(bool x3)
     return f;
 }
 
-template <int EPI, int TM, int TN, int KS>
-hipError_t gemm_launch_t(const GemmArgs &a, hipStream_t st)
-{
-    constexpr int BMt = 64 * TM, BNt = 64 * TN;
-    static_assert((BMt / 4) % (4 * KS) == 0 && (BNt / 4) % (4 * KS) == 0, "tile rows per wave");
-    if (a.K % 64 != 0 || a.ldx % 4 != 0) return hipErrorInvalidValue;   // (the launchers round K up: pad_k)
-    const DmaForm f = dma_form<EPI, TM, TN, KS, false>(a.x3 != nullptr);
-    GemmArgs args = a;
-    const dim3 grid1 = dma_grid((a.N + BNt - 1) / BNt, (a.P + BMt - 1) / BMt, &args);
-    void *params[] = {&args};
-    return hipLaunchKernel(f.fn, grid1, dim3(f.threads), params, f.lds, st);
-}
+// tokens x features (of each matrix when paired) of a block's output tile, by TileForm
+constexpr struct { int tok, feat; } kTileDims[5] = {{128, 64}, {64, 64}, {32, 64}, {32, 32}, {128, 128}};
 
-// the direct-to-LDS tile kernel with fewer waves per block -- 32 x 64 (1 x 2 waves per k-group) and
-// 32 x 32 (1 x 1) output tiles: same k split and order as the 2 x 2 forms (bit-identical results), more
-// blocks for grids that would leave CUs idle.  false: shape not taken (K % 64, alignment).
-template <int EPI, int WM, int WN>
-bool gemm_launch_small(const GemmArgs &a, hipStream_t st, hipError_t *err)
+// The tile kernel's form for an output tile -- the one ladder, for the plain, paired and q | k | v products alike.
+// SPLIT 0: the unsplit family; the 32-token forms run fewer waves per block (1 x 2 and 1 x 1 per k-group instead of 2 x 2):
+// same k split and order (bit-identical results), more blocks for grids that would leave CUs idle.  SPLIT 1: the split-K
+// family, every form the same bits for the same sk.  SPLIT 2: k-groups on two blocks, the unsplit family's bits with twice
+// the blocks.  Forms no plan asks for are not instantiated: 128 x 128 of a paired product, of the split-K family, of the
+// unsplit q | k | v launch; 32 x 32 of a split family (a two-block 32 x 32 plan -- there is none -- would get 32 x 64).
+template <int EPI, bool PAIR, int SPLIT>
+DmaForm tile_form(int tile, bool x3)
 {
-    if (a.K % 64 != 0 || a.ldx % 4 != 0) return false;
-    constexpr int KS = 2, BMt = 32 * WM, BNt = 32 * WN;
-    const DmaForm f = dma_form<EPI, 1, 1, KS, false, WM, WN>(a.x3 != nullptr);
-    dim3 grid((a.N + BNt - 1) / BNt, (a.P + BMt - 1) / BMt);
-    GemmArgs args = a;
-    const dim3 grid1 = dma_grid((int)grid.x, (int)grid.y, &args);
-    void *params[] = {&args};
-    *err = hipLaunchKernel(f.fn, grid1, dim3(f.threads), params, f.lds, st);
-    return true;
-}
-
-template <int EPI>
-hipError_t gemm_launch(const GemmArgs &a, hipStream_t st)
-{
-    // 64 x 64 tiles fill the 256 CUs from N = 4096 at 256 tokens; beyond that 128 x 64 halves
-    // the LDS operand reads per MFMA (measured on the 7B shape: 94.7 vs 89.5 TFLOP/s at 512)
-    hipError_t e;
-    switch (choose_tile(a.N, a.P, false)) {
-    case TILE_128x128: return gemm_launch_t<EPI, 2, 2, 2>(a, st);
-    case TILE_128x64: return gemm_launch_t<EPI, 2, 1, 2>(a, st);
-    case TILE_32x64: if (gemm_launch_small<EPI, 1, 2>(a, st, &e)) return e; break;
-    case TILE_32x32: if (gemm_launch_small<EPI, 1, 1>(a, st, &e)) return e; break;
-    default: break;
+    constexpr int KS = 2, TN = PAIR ? 2 : 1;
+    switch (tile) {
+    case TILE_128x128:
+        if constexpr (!PAIR && SPLIT != 1 && !(EPI == G_QKV && SPLIT == 0)) return dma_form<EPI, 2, 2, KS, false, 2, 2, SPLIT>(x3);
+        else return {nullptr, 0, 0};
+    case TILE_128x64: return dma_form<EPI, 2, TN, KS, PAIR, 2, 2, SPLIT>(x3);
+    case TILE_64x64: return dma_form<EPI, 1, TN, KS, PAIR, 2, 2, SPLIT>(x3);
+    case TILE_32x32:
+        if constexpr (SPLIT == 0) return dma_form<EPI, 1, TN, KS, PAIR, 1, 1, SPLIT>(x3);
+        [[fallthrough]];
+    default: return dma_form<EPI, 1, TN, KS, PAIR, 1, 2, SPLIT>(x3);
     }
-    return gemm_launch_t<EPI, 1, 1, 2>(a, st);
+}
+
+// launch of a tile-kernel plan (GF_TILE, GF_SPLIT_K, GF_TWO_BLOCK); a.K is the padded K, a.N the features of each matrix
+template <int EPI, bool PAIR>
+hipError_t launch_tile(GemmArgs a, const GemmPlan &p, const SplitKWs *ws, hipStream_t st)
+{
+    const bool x3 = a.x3 != nullptr;
+    DmaForm f = {nullptr, 0, 0};
+    if (p.family == GF_TILE) f = tile_form<EPI, PAIR, 0>(p.tile, x3);
+    else {
+        a.sk = p.family == GF_SPLIT_K ? p.sk : 2;   // (two-block: the grid's z extent, dma_grid)
+        a.sk_part = ws->part; a.sk_cnt = ws->cnt;
+        if (p.family == GF_SPLIT_K) f = tile_form<EPI, PAIR, 1>(p.tile, x3);
+        // residual products, the fused q | k | v launch and the paired W1 | W3 product
+        else if constexpr (EPI == G_RESID || EPI == G_QKV || PAIR) f = tile_form<EPI, PAIR, 2>(p.tile, x3);
+    }
+    if (f.fn == nullptr) return hipErrorInvalidValue;
+    const int tok = kTileDims[p.tile].tok, feat = kTileDims[p.tile].feat;
+    const dim3 grid = dma_grid((a.N + feat - 1) / feat, (a.P + tok - 1) / tok, &a);
+    void *params[] = {&a};
+    return hipLaunchKernel(f.fn, grid, dim3(f.threads), params, f.lds, st);
 }
 
 // ---- the split-K family (prefill_gemm_dma SPLIT) ----
 // Output tile for a product whose K is cut into sk ranges: the same cost model as choose_tile with sk times the
 // blocks and 1 / sk of the work per block.  Every form gives the same bits for the same sk.
-enum SkTile { SKT_128x64 = 0, SKT_64x64, SKT_32x64 };
-static SkTile choose_tile_sk(int N, int P, int sk)
+static TileForm choose_tile_sk(int N, int P, int sk)
 {
     const long long cus = g_cus_hint();
-    static const struct { int tok; double eff; } form[3] = {{128, 1.0}, {64, 0.87}, {32, 0.80}};
+    static const struct { int tok; double eff; } form[3] = {{128, 1.0}, {64, 0.87}, {32, 0.80}};   // TILE_128x64, 64x64, 32x64
     int best = -1;
     double best_cost = 0.0;
     for (int f = 0; f < 3; f++) {
-        if (f == SKT_128x64 && P <= 64) continue;
+        if (f == TILE_128x64 && P <= 64) continue;
         const long long blocks = (long long)((N + 63) / 64) * ((P + form[f].tok - 1) / form[f].tok) * sk;
         const double cost = (double)((blocks + cus - 1) / cus) * (form[f].tok * 64) / sk / form[f].eff;
         if (best < 0 || cost < best_cost * 0.999) {
@@ -1118,59 +1117,19 @@ static SkTile choose_tile_sk(int N, int P, int sk)
             best_cost = cost;
         }
     }
-    return (SkTile)best;
+    return (TileForm)best;
 }
 
-template <int EPI, int TM, int TN, bool PAIR, int WM, int WN>
-hipError_t dma_launch_split(GemmArgs a, int n_feat, int sk, const SplitKWs *ws, hipStream_t st)
-{
-    constexpr int KS = 2, BMt = 32 * WM * TM, BNt = 32 * WN * TN;
-    constexpr int feat = PAIR ? BNt / 2 : BNt;  // features (of each matrix when paired) per block
-    if (ws == nullptr || ws->part == nullptr || ws->cnt == nullptr) return hipErrorInvalidValue;
-    const int ntx = (n_feat + feat - 1) / feat, nty = (a.P + BMt - 1) / BMt;
-    if ((size_t)ntx * nty * sk * BMt * BNt > ws->part_floats || ntx * nty > ws->cnt_ints) return hipErrorOutOfMemory;
-    a.sk = sk; a.sk_part = ws->part; a.sk_cnt = ws->cnt;
-    const DmaForm f = dma_form<EPI, TM, TN, KS, PAIR, WM, WN, 1>(a.x3 != nullptr);
-    const dim3 grid = dma_grid(ntx, nty, &a);
-    void *params[] = {&a};
-    return hipLaunchKernel(f.fn, grid, dim3(f.threads), params, f.lds, st);
-}
-
-// unpaired / fused-qkv products (TN = 1 forms) and the paired W1 | W3 product (TN = 2 forms)
-template <int EPI, bool PAIR>
-hipError_t gemm_launch_sk(const GemmArgs &a, int n_feat, int sk, const SplitKWs *ws, hipStream_t st)
-{
-    constexpr int TN = PAIR ? 2 : 1;
-    switch (choose_tile_sk(n_feat, a.P, sk)) {
-    case SKT_128x64: return dma_launch_split<EPI, 2, TN, PAIR, 2, 2>(a, n_feat, sk, ws, st);
-    case SKT_64x64: return dma_launch_split<EPI, 1, TN, PAIR, 2, 2>(a, n_feat, sk, ws, st);
-    default: return dma_launch_split<EPI, 1, TN, PAIR, 1, 2>(a, n_feat, sk, ws, st);
-    }
-}
-
-// ---- k-groups on two blocks (prefill_gemm_dma SPLIT == 2): the unsplit family's bits with twice the blocks ----
-template <int EPI, int TM, int TN, bool PAIR, int WM, int WN>
-hipError_t dma_launch_kgs(GemmArgs a, int n_feat, const SplitKWs *ws, hipStream_t st)
-{
-    constexpr int KS = 2, BMt = 32 * WM * TM, BNt = 32 * WN * TN;
-    constexpr int feat = PAIR ? BNt / 2 : BNt;
-    const int ntx = (n_feat + feat - 1) / feat, nty = (a.P + BMt - 1) / BMt;
-    if ((size_t)ntx * nty * BMt * BNt > ws->part_floats || 2 * ntx * nty > ws->cnt_ints) return hipErrorOutOfMemory;
-    a.sk = 2; a.sk_part = ws->part; a.sk_cnt = ws->cnt;  // sk: the grid's z extent (dma_grid)
-    const DmaForm f = dma_form<EPI, TM, TN, KS, PAIR, WM, WN, 2>(a.x3 != nullptr);
-    const dim3 grid = dma_grid(ntx, nty, &a);
-    void *params[] = {&a};
-    return hipLaunchKernel(f.fn, grid, dim3(f.threads), params, f.lds, st);
-}
-
+// ---- k-groups on two blocks (prefill_gemm_dma SPLIT == 2) ----
 // Whether a [P, N] product (N = features of each matrix when paired) goes out in the two-block form, and on which
 // tile.  Same bits either way, so this is grid fill only: the cost model of choose_tile with twice the blocks of
 // half the depth, plus the hand-off (~7 us: a dump, a counter, the other block's read) in the model's units.
 struct KgsChoice { bool use; TileForm tile; };
-static KgsChoice choose_kgs(int N, int P, int K, bool pair, const SplitKWs *ws, bool x3)
+static KgsChoice choose_kgs(const GemmShape &s, int K, bool x3)
 {
+    const bool pair = s.kind == GEMM_W13;
     KgsChoice none = {false, TILE_64x64};
-    if (ws == nullptr || ws->part == nullptr || K % 64 != 0 || x3) return none;   // (the planes form has no two-block variant)
+    if (s.part_floats == 0 || K % 64 != 0 || x3) return none;   // (the planes form has no two-block variant)
     // Measured (7B shape, whole prefill, interleaved; profiles/r03_prefill_kgs_ab.txt): the form pays where the
     // unsplit family runs ONE 8-wave block of a 128-token tile per CU -- two independent 4-wave blocks of half
     // the LDS hide each other's stage barriers: 512 tokens 58.56 -> 57.32 ms on 128 x 64 tiles -- and loses or
@@ -1178,31 +1137,16 @@ static KgsChoice choose_kgs(int N, int P, int K, bool pair, const SplitKWs *ws, 
     // 110M shape: +10 %).  A cost model of the choose_tile kind picked it for q | k | v and W1 | W3 at 256
     // tokens and lost 5 %: so the rule is the measured one -- chunks of >= 512 tokens, on the 128-token tile the
     // unsplit family takes.
-    if (P < 512) return none;
-    const TileForm tu = choose_tile(N, P, pair);
+    if (s.P < 512) return none;
+    const TileForm tu = choose_tile(s.N, s.P, pair);
     if (tu != TILE_128x64 && tu != TILE_128x128) return none;
     {   // the dump of one k-group per tile and two counters per tile must fit the runstate's workspace (sized for
         // 1024-token chunks: L2Z_PF_CHUNK up to 2048 does not fit) -- else the one-block form, same bits
         const size_t bm = 128, bn = tu == TILE_128x128 ? 128 : (pair ? 128 : 64), feat = pair ? bn / 2 : bn;
-        const size_t ntx = ((size_t)N + feat - 1) / feat, nty = ((size_t)P + bm - 1) / bm;
-        if (ntx * nty * bm * bn > ws->part_floats || 2 * ntx * nty > (size_t)ws->cnt_ints) return none;
+        const size_t ntx = ((size_t)s.N + feat - 1) / feat, nty = ((size_t)s.P + bm - 1) / bm;
+        if (ntx * nty * bm * bn > s.part_floats || 2 * ntx * nty > (size_t)s.cnt_ints) return none;
     }
     return {true, tu};
-}
-
-// unpaired products with a residual epilogue, the fused q | k | v launch (TN = 1 forms) and the paired W1 | W3 product
-template <int EPI, bool PAIR>
-hipError_t gemm_launch_kgs(const GemmArgs &a, int n_feat, TileForm tile, const SplitKWs *ws, hipStream_t st)
-{
-    constexpr int TN = PAIR ? 2 : 1;
-    switch (tile) {
-    case TILE_128x128:
-        if constexpr (!PAIR) return dma_launch_kgs<EPI, 2, 2, false, 2, 2>(a, n_feat, ws, st);
-        return hipErrorInvalidValue;
-    case TILE_128x64: return dma_launch_kgs<EPI, 2, TN, PAIR, 2, 2>(a, n_feat, ws, st);
-    case TILE_64x64: return dma_launch_kgs<EPI, 1, TN, PAIR, 2, 2>(a, n_feat, ws, st);
-    default: return dma_launch_kgs<EPI, 1, TN, PAIR, 1, 2>(a, n_feat, ws, st);
-    }
 }
 
 // The launch's activation matrix as three planes of bf16 terms (prefill_common.h split3): x3[token][plane][kp], element k of
@@ -1219,10 +1163,9 @@ __global__ __launch_bounds__(256) void prefill_split3_kernel(const float *x, int
     o[0] = t.t1; o[per_row] = t.t2; o[2 * per_row] = t.t3;
 }
 
-// before a launch of the planes form: a.K is the padded K; fills ws->x3 from a.x
-hipError_t prepare_x3(GemmArgs &a, const SplitKWs *ws, hipStream_t st, long long n_whole, int planes_ready = PLANES_SPLIT)
+// before a launch on the bf16 cores (the plan's x3): a.K is the padded K; fills ws->x3 from a.x
+hipError_t prepare_x3(GemmArgs &a, const SplitKWs *ws, hipStream_t st, PlanesReady planes_ready)
 {
-    if (!x3_applies(n_whole, a.K)) return hipSuccess;   // a.x3 stays null: the f32 matrix cores
     if (ws == nullptr || ws->x3 == nullptr || (size_t)a.P * 3 * a.K * sizeof(__bf16) > ws->x3_bytes) return hipErrorInvalidValue;
     a.x3 = ws->x3; a.kp = a.K; a.ldx3 = 3 * a.K;
     if (planes_ready == PLANES_READY_B) {   // the W1 | W3 launch's epilogue left them in the second planes matrix
@@ -1237,59 +1180,91 @@ hipError_t prepare_x3(GemmArgs &a, const SplitKWs *ws, hipStream_t st, long long
     return hipGetLastError();
 }
 
-// launch of the stream form; a.K is the padded K, a.N this rank's rows, n_whole the whole model's (the K ranges)
-template <int EPI>
-hipError_t launch_x3_stream(GemmArgs a, long long n_whole, const SplitKWs *ws, hipStream_t st, int planes_ready = PLANES_SPLIT,
-                            DeferredSum *defer = nullptr)
+// ---- the stream form ----
+// Ring depth by features per block and token tiles: what fits the LDS beside the planes' stages
+static int stream_ring(int feat, int tm)
 {
-    if (defer) defer->valid = false;
-    if (const hipError_t e = prepare_x3(a, ws, st, n_whole, planes_ready); e != hipSuccess) return e;
+    if (feat == 256) return tm == 1 ? 4 : 3;
+    if (feat == 192) return tm == 1 ? 5 : 4;
+    return tm == 1 ? 7 : tm == 2 ? L2Z_X3_NBUF2 : 4;
+}
+// ... and the kernel of (features per block, token tiles): the ring depths are stream_ring's
+template <int EPI>
+const void *stream_kernel(int feat, int tm)
+{
+    if (feat == 256) {
+        if constexpr (EPI == G_ROPE || EPI == G_ROPE_CACHE) return nullptr;   // (never planned: sixteen waves of these would spill)
+        else return tm == 1 ? (const void *)prefill_x3_stream<EPI, 1, 4, 8> : (const void *)prefill_x3_stream<EPI, 2, 3, 8>;
+    }
+    if (feat == 192) return tm == 1 ? (const void *)prefill_x3_stream<EPI, 1, 5, 6> : (const void *)prefill_x3_stream<EPI, 2, 4, 6>;
+    switch (tm) {
+    case 1: return (const void *)prefill_x3_stream<EPI, 1, 7, 4>;
+    case 2: return (const void *)prefill_x3_stream<EPI, 2, L2Z_X3_NBUF2, 4>;
+    case 3: return (const void *)prefill_x3_stream<EPI, 3, 4, 4>;
+    default: return (const void *)prefill_x3_stream<EPI, 4, 4, 4>;
+    }
+}
+
+// the stream form's part of the plan; K is the padded K, N this rank's rows, n_whole the whole model's (the K ranges)
+static void plan_stream(GemmPlan &p, const GemmShape &s, int N, long long n_whole)
+{
     // Features per block (grid fill only: the K ranges -- the arithmetic -- are x3_stream_sk's whatever the tile).  Chunks of
     // <= 64 tokens may run 192 features on twelve waves or 256 on sixteen instead of 128 on eight: a block streams its W at
     // ~20 GB/s whatever its width (profiles/r06s), so the launch wants as many blocks as fit ONE round -- the narrowest tile
     // that does -- and the wider tiles send the planes through the L2 less often.  (q | k | v: a tile may lie across two of the matrices; a wave's 32 features never do.)  7B shape: q | k | v 192 features (256 blocks of 4 ranges), W1 | W3 192 (230 blocks of 2
     // ranges: 85 us against 105 with 172 blocks of 256 features), wo / W2 128 (256 blocks of 8 ranges).
-    const int sk = x3_stream_sk(n_whole, a.P, a.K), tm = (a.P + 31) / 32, cus = g_cus_hint();
+    const int sk = x3_stream_sk(n_whole, s.P, p.K), tm = (s.P + 31) / 32, cus = g_cus_hint();
     int feat = 128;
-    if (x3_stream_tile(a.P) == 256 && tm <= 2 && (long long)((a.N + 127) / 128) * sk > cus) {
+    if (x3_stream_tile(s.P) == 256 && tm <= 2 && (long long)((N + 127) / 128) * sk > cus) {
         // the NARROWEST tile whose blocks fit one round (the most blocks: the least W per block)
         for (int f : {192, 256}) {
-            if (f == 256 && (EPI == G_ROPE || EPI == G_ROPE_CACHE)) continue;   // (sixteen waves of these would spill: 128 registers)
-            if ((long long)((a.N + f - 1) / f) * sk <= cus) { feat = f; break; }
+            if (f == 256 && (p.epi == G_ROPE || p.epi == G_ROPE_CACHE)) continue;   // (sixteen waves of these would spill: 128 registers)
+            if ((long long)((N + f - 1) / f) * sk <= cus) { feat = f; break; }
         }
     }
-    const int ntx = (a.N + feat - 1) / feat;
-    if (ws->part == nullptr || ws->cnt == nullptr || (size_t)ntx * sk * tm * 32 * feat > ws->part_floats || 2 * ntx > ws->cnt_ints)
-        return hipErrorOutOfMemory;
-    a.sk = sk; a.sk_part = ws->part; a.sk_cnt = ws->cnt;
-    if (EPI == G_RESID && defer != nullptr && sk > 1 && a.res == a.out && a.ldres == a.ldo) {   // (in place: x += the product)
-        a.defer = 1;
-        defer->part = ws->part; defer->sk = sk; defer->feat = feat; defer->tm = tm; defer->valid = true;
-    }
+    const int ntx = (N + feat - 1) / feat;
+    p.family = s.part_floats == 0 || s.cnt_ints == 0 || (size_t)ntx * sk * tm * 32 * feat > s.part_floats || 2 * ntx > s.cnt_ints
+                   ? GF_NO_WORKSPACE : GF_STREAM;
+    p.x3 = 1; p.sk = sk; p.feat = feat; p.tm = tm; p.nbuf = stream_ring(feat, tm);
     // one round of blocks (one per CU: the ring takes the LDS): the ranges of a tile share its reduction and epilogue
     // (same sums in the same order either way: grid fill only, so a rank's own row count decides)
-    a.ntx = ntx * sk <= cus ? 0 : ntx;
-    const void *fn;
-    int nbuf;
-    if (feat == 256) {
-        if constexpr (EPI == G_ROPE || EPI == G_ROPE_CACHE) return hipErrorInvalidValue;   // (never chosen above)
-        else if (tm == 1) { fn = (const void *)prefill_x3_stream<EPI, 1, 4, 8>; nbuf = 4; }
-        else { fn = (const void *)prefill_x3_stream<EPI, 2, 3, 8>; nbuf = 3; }
-    } else if (feat == 192) {
-        if (tm == 1) { fn = (const void *)prefill_x3_stream<EPI, 1, 5, 6>; nbuf = 5; }
-        else { fn = (const void *)prefill_x3_stream<EPI, 2, 4, 6>; nbuf = 4; }
-    } else {
-        switch (tm) {
-        case 1: fn = (const void *)prefill_x3_stream<EPI, 1, 7, 4>; nbuf = 7; break;
-        case 2: fn = (const void *)prefill_x3_stream<EPI, 2, L2Z_X3_NBUF2, 4>; nbuf = L2Z_X3_NBUF2; break;
-        case 3: fn = (const void *)prefill_x3_stream<EPI, 3, 4, 4>; nbuf = 4; break;
-        default: fn = (const void *)prefill_x3_stream<EPI, 4, 4, 4>; nbuf = 4; break;
-        }
+    p.one_round = ntx * sk <= cus;
+}
+
+// launch of a GF_STREAM plan; a.K is the padded K, a.N this rank's rows, a.x3 the planes
+template <int EPI>
+hipError_t launch_x3_stream(GemmArgs a, const GemmPlan &p, const SplitKWs *ws, hipStream_t st, DeferredSum *defer)
+{
+    const int ntx = (a.N + p.feat - 1) / p.feat;
+    a.sk = p.sk; a.sk_part = ws->part; a.sk_cnt = ws->cnt;
+    if (EPI == G_RESID && defer != nullptr && p.sk > 1 && a.res == a.out && a.ldres == a.ldo) {   // (in place: x += the product)
+        a.defer = 1;
+        defer->part = ws->part; defer->sk = p.sk; defer->feat = p.feat; defer->tm = p.tm; defer->valid = true;
     }
-    const size_t lds = (size_t)nbuf * (3 * 32 * tm * 64 + feat * 128);
+    a.ntx = p.one_round ? 0 : ntx;
+    const void *fn = stream_kernel<EPI>(p.feat, p.tm);
+    if (fn == nullptr) return hipErrorInvalidValue;
+    const size_t lds = (size_t)p.nbuf * (3 * 32 * p.tm * 64 + p.feat * 128);
     if (lds > 48 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     void *params[] = {&a};
-    return hipLaunchKernel(fn, dim3((unsigned)(ntx * sk)), dim3((unsigned)(feat * 4)), params, lds, st);
+    return hipLaunchKernel(fn, dim3((unsigned)(ntx * p.sk)), dim3((unsigned)(p.feat * 4)), params, lds, st);
+}
+
+// the runtime epilogue as a template argument: f(std::integral_constant<int, epi>)
+template <class F>
+hipError_t with_epi(int epi, F &&f)
+{
+    switch (epi) {
+    case G_STORE: return f(std::integral_constant<int, G_STORE>{});
+    case G_RESID: return f(std::integral_constant<int, G_RESID>{});
+    case G_ROPE: return f(std::integral_constant<int, G_ROPE>{});
+    case G_ROPE_CACHE: return f(std::integral_constant<int, G_ROPE_CACHE>{});
+    case G_CACHE: return f(std::integral_constant<int, G_CACHE>{});
+    case G_SWIGLU: return f(std::integral_constant<int, G_SWIGLU>{});
+    case G_QKV: return f(std::integral_constant<int, G_QKV>{});
+    case G_SWIGLU_IL: return f(std::integral_constant<int, G_SWIGLU_IL>{});
+    }
+    return hipErrorInvalidValue;
 }
 
 }  // namespace
@@ -1327,202 +1302,134 @@ int prefill_split_k(long long n_whole, int P, int K, bool pair)
     return sk;
 }
 
-// out[P,N] = silu(X W1^T) * (X W3^T) in one launch (direct-to-LDS tile kernel, paired form).
-// hipErrorNotSupported when the shape does not take that kernel: the caller launches the two GEMMs.
-hipError_t launch_prefill_gemm_swiglu_pair(const float *x, int ldx, const float *w1, const float *w3,
-                                           float *out, int ldo, int P, int N, int K, hipStream_t st, int n_scale,
-                                           int sk, const SplitKWs *ws, int ldw, int planes_ready, int kp_out, bool *planes_written)
+// Which kernel a product takes, and in which form (l2z_internal.h): the stream form of the planes kernel, else the short-prompt
+// kernels, else the tile kernel -- split-K, two-block or plain.  GEMM_QKV: hipErrorNotSupported when no kernel takes the three
+// in one launch or a tile would straddle two of the matrices; GEMM_W13 / GEMM_KV: when the shape takes a short-prompt form that
+// has no paired variant.
+GemmPlan prefill_gemm_plan(const GemmShape &s)
 {
-    if (planes_written) *planes_written = false;
-    if (((uintptr_t)x & 15) || ((uintptr_t)w1 & 15) || ((uintptr_t)w3 & 15)) return hipErrorInvalidValue;
-    GemmArgs a = {x, w3, w1, out, out, P, N, K, ldx, ldo, ldo, 0, nullptr, 0, n_scale > 0 ? n_scale : 1, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0};
-    a.ldw = ldw > 0 ? ldw : K;
+    GemmPlan p = {};
+    p.family = GF_INVALID; p.sk = 1; p.K = s.K;
+    const bool single = s.kind == GEMM_SINGLE, qkv = s.kind == GEMM_QKV, pair = s.kind == GEMM_W13, kv = s.kind == GEMM_KV;
+    const auto is = [&p](GemmFamily f) { p.family = f; return p; };
+    if (s.P <= 0 || s.N <= 0 || s.K <= 0 || (s.K % 4) != 0 || (s.ldx % 4) != 0) return p;
+    if (single && (s.epi < G_STORE || s.epi > G_SWIGLU)) return p;
+    if (qkv && s.N != s.nq + 2 * s.nkv) return p;
+    const int n_scale = s.n_scale > 0 ? s.n_scale : 1;
     constexpr int skinny_max = Tunables::pf_skinny_max;
-    if (const int kp = pad_k(K, 64, ldx); kp > 0 && ldw == 2 * K && w3 == w1 + K &&
-        x3_stream_shape(2LL * N * a.n_scale, P, kp)) {
-        // the stream form takes W1 | W3 as ONE matrix of alternating rows (the blob's slot)
-        GemmArgs b = a;
-        b.w = w1; b.w2 = nullptr; b.N = 2 * N; b.K = kp; b.ldw = K;
-        // the gated rows' planes beside them (the W2 launch's operand): only whole 64-k rows -- the split launch writes the
-        // zeros of pad columns -- and only where the second planes matrix exists (the unsharded pass)
-        if (kp_out == N && (N & 63) == 0 && ws != nullptr && ws->x3b != nullptr && (size_t)P * 3 * kp_out * sizeof(__bf16) <= ws->x3b_bytes) {
-            b.x3_out = ws->x3b; b.kp_out = kp_out;
-            if (planes_written) *planes_written = true;
+    // n_whole: the rows of the WHOLE model's launch this product belongs to (q | k | v launched apart count as one: n_launch_whole)
+    const long long n_whole = single && s.n_launch_whole > 0 ? s.n_launch_whole : (pair ? 2LL : 1LL) * s.N * n_scale;
+    const int kp = pad_k(s.K, 64, s.ldx);   // whole 64-k stages (see pad_k)
+    p.epi = qkv || kv ? G_QKV : pair ? G_STORE : s.epi;
+    if (kv) {   // short prompts only (sk > 1: the tile kernel's split-K family takes k and v; so does the stream form)
+        if (s.P > skinny_max || s.sk > 1) return is(GF_NOT_SUPPORTED);
+        if (s.n_launch_whole > 0 && x3_stream_shape(s.n_launch_whole, s.P, (s.K + 63) / 64 * 64)) return is(GF_NOT_SUPPORTED);
+    } else if (kp > 0 && !(single && s.epi == G_SWIGLU) && (!pair || s.w13_one_matrix) && x3_stream_shape(n_whole, s.P, kp)) {
+        // (the stream form takes W1 | W3 as ONE matrix of alternating rows -- the blob's slot; the caller's three launches of
+        // a q | k | v it refuses take the stream form too, same ranges)
+        if (qkv && (s.nq % 128 != 0 || s.nkv % 128 != 0)) return is(GF_NOT_SUPPORTED);
+        p.K = kp;
+        if (pair) p.epi = G_SWIGLU_IL;
+        plan_stream(p, s, pair ? 2 * s.N : s.N, n_whole);
+        return p;
+    }
+    if (s.P <= skinny_max && s.sk <= 1) {   // prefill_skinny.hip
+        if (qkv) return is(GF_NOT_SUPPORTED);
+        if (pair) p.epi = G_SWIGLU;
+        p.paired = pair || kv;
+        p.tms = skinny_one_tile((long long)s.N * n_scale, s.K, s.P) ? 1 : 2;
+        return is(p.paired && p.tms != 1 ? GF_NOT_SUPPORTED : GF_SHORT);
+    }
+    if (kp < 0) return p;
+    p.K = kp;
+    p.x3 = x3_applies(n_whole, kp);
+    if (s.sk > 1) {
+        if (single && kp / 64 < s.sk) return p;
+        if (qkv && (s.nq % 64 != 0 || s.nkv % 64 != 0)) return is(GF_NOT_SUPPORTED);  // 64-feature tiles (a tile must not straddle q | k | v)
+        p.sk = s.sk;
+        p.tile = choose_tile_sk(s.N, s.P, s.sk);
+        const size_t tok = kTileDims[p.tile].tok, bn = pair ? 128 : 64, ntx = ((size_t)s.N + 63) / 64, nty = ((size_t)s.P + tok - 1) / tok;
+        if (s.part_floats == 0 || s.cnt_ints == 0) return p;
+        return is(ntx * nty * s.sk * tok * bn > s.part_floats || ntx * nty > (size_t)s.cnt_ints ? GF_NO_WORKSPACE : GF_SPLIT_K);
+    }
+    if (!single || s.epi == G_RESID) {   // wo, W2, q | k | v, W1 | W3: the two-block form where the grid is short of blocks (same bits)
+        const KgsChoice c = choose_kgs(s, kp, p.x3 != 0);
+        const int feat_k = kTileDims[c.tile].feat;   // a tile must not straddle q | k | v
+        if (c.use && (!qkv || (s.nq % feat_k == 0 && s.nkv % feat_k == 0))) {
+            p.tile = c.tile;
+            return is(GF_TWO_BLOCK);
         }
-        return launch_x3_stream<G_SWIGLU_IL>(b, 2LL * N * a.n_scale, ws, st, planes_ready);
     }
-    if (P <= skinny_max && sk <= 1) return launch_prefill_skinny_pair(G_SWIGLU, a, st);  // prefill_skinny.hip (or not supported)
-    K = a.K = pad_k(K, 64, ldx);   // whole 64-k stages (see pad_k)
-    if (K < 0 || ldx % 4 != 0) return hipErrorInvalidValue;
-    if (const hipError_t e = prepare_x3(a, ws, st, 2LL * N * a.n_scale, planes_ready); e != hipSuccess) return e;
-    // (the gated rows' planes beside them, as in the stream form: every paired tile form finishes in the same epilogue)
-    if (a.x3 != nullptr && kp_out == N && (N & 63) == 0 && ws != nullptr && ws->x3b != nullptr && (size_t)P * 3 * kp_out * sizeof(__bf16) <= ws->x3b_bytes) {
-        a.x3_out = ws->x3b; a.kp_out = kp_out;
-        if (planes_written) *planes_written = true;
+    // 64 x 64 tiles fill the 256 CUs from N = 4096 at 256 tokens; beyond that 128 x 64 halves
+    // the LDS operand reads per MFMA (measured on the 7B shape: 94.7 vs 89.5 TFLOP/s at 512)
+    p.tile = choose_tile(s.N, s.P, pair);
+    if (qkv) {
+        // 128 x 64 tiles mean q alone already gives every CU its one resident block: three such launches
+        // measured 445 us against 453 for the 768-block one (7B, 512 tokens).  With the smaller tiles several
+        // blocks share a CU and the longer grid keeps them supplied: 128 tokens 21.8 -> 19.4 ms fused.
+        // (The same on the bf16 cores: 7B, 1024 / 512 tokens 74.3 / 40.6 ms with three launches, 80.3 / 41.6 fused on 128 x 64
+        // tiles -- the caller's k and v launches reuse q's planes: planes_ready.)
+        if (p.tile == TILE_128x64 || p.tile == TILE_128x128) return is(GF_NOT_SUPPORTED);
+        const int feat = kTileDims[p.tile].feat;
+        if (s.nq % feat != 0 || s.nkv % feat != 0) {
+            if (s.nq % 32 != 0 || s.nkv % 32 != 0) return is(GF_NOT_SUPPORTED);
+            p.tile = TILE_32x32;
+        }
     }
-    if (sk > 1) return gemm_launch_sk<G_STORE, true>(a, N, sk, ws, st);
-    {
-        const KgsChoice c = choose_kgs(N, P, K, true, ws, a.x3 != nullptr);
-        if (c.use) return gemm_launch_kgs<G_STORE, true>(a, N, c.tile, ws, st);
-    }
-    constexpr int KS = 2;
-    // tokens x (features of W1 + the same features of W3) per block, chosen like the unpaired tiles
-    const TileForm tf = choose_tile(N, P, true);
-    const int tok = tf == TILE_128x64 ? 128 : tf == TILE_64x64 ? 64 : 32, feat = tf == TILE_32x32 ? 32 : 64;
-    const DmaForm f = tf == TILE_128x64 ? dma_form<G_STORE, 2, 2, KS, true>(a.x3 != nullptr)
-                    : tf == TILE_64x64  ? dma_form<G_STORE, 1, 2, KS, true>(a.x3 != nullptr)
-                    : tf == TILE_32x64  ? dma_form<G_STORE, 1, 2, KS, true, 1, 2>(a.x3 != nullptr)
-                                        : dma_form<G_STORE, 1, 2, KS, true, 1, 1>(a.x3 != nullptr);
-    const dim3 grid = dma_grid((N + feat - 1) / feat, (P + tok - 1) / tok, &a);
-    void *params[] = {&a};
-    return hipLaunchKernel(f.fn, grid, dim3(f.threads), params, f.lds, st);
+    return is(GF_TILE);
 }
 
-// q | k | v of one layer in ONE launch of the direct-to-LDS tile kernel (main.zig:308-358): N = nq + 2 nkv
-// features, the block's column range picks the matrix and the epilogue (RoPE into q, RoPE into the key
-// cache rows pos0 + token, plain into the value cache rows).  hipErrorNotSupported when the shape does
-// not take that kernel or a tile would straddle two ranges: the caller launches the three GEMMs.
-hipError_t launch_prefill_gemm_qkv(const float *x, int ldx, const float *wq, const float *wk, const float *wv,
-                                   float *q_out, int ldq, float *kcache, float *vcache, int ldkv, int P, int nq,
-                                   int nkv, int K, int pos0, const float2 *rope, int head_size, hipStream_t st,
-                                   size_t kv_head_stride, int n_scale, int sk, const SplitKWs *ws, int planes_ready)
+// Validate pointers, plan, prepare the planes, dispatch on the plan (prefill_common.h).
+hipError_t launch_prefill_gemm(GemmKind kind, int epi, const GemmArgs &in, GemmLaunch &l, hipStream_t st)
 {
-    constexpr int skinny_max = Tunables::pf_skinny_max;
-    if (const int kp = pad_k(K, 64, ldx); kp > 0 && x3_stream_shape((long long)(nq + 2 * nkv) * (n_scale > 0 ? n_scale : 1), P, kp)) {
-        if (nq % 128 != 0 || nkv % 128 != 0) return hipErrorNotSupported;   // (the caller's three launches take the stream form, same ranges)
-        if (((uintptr_t)x & 15) || ((uintptr_t)wq & 15) || ((uintptr_t)wk & 15) || ((uintptr_t)wv & 15)) return hipErrorInvalidValue;
-        GemmArgs b = {x, nullptr, wq, q_out, q_out, P, nq + 2 * nkv, kp, ldx, ldq, ldq, pos0, rope, head_size, n_scale > 0 ? n_scale : 1,
-                      wk, wv, kcache, vcache, nq, nkv, ldkv, kv_head_stride, 0, 0};
-        b.ldw = K;
-        return launch_x3_stream<G_QKV>(b, (long long)(nq + 2 * nkv) * b.n_scale, ws, st, planes_ready);
+    l.planes_written = false;
+    if (l.defer) l.defer->valid = false;
+    GemmArgs a = in;
+    for (const float *ptr : {a.x, a.w, a.w2, a.wk, a.wv})
+        if ((uintptr_t)ptr & 15) return hipErrorInvalidValue;
+    if (a.res == nullptr) { a.res = a.out; a.ldres = a.ldo; }  // PG_RESID in place
+    if (a.n_scale <= 0) a.n_scale = 1;   // (read by the plan and by prefill_skinny.hip's host code only: no tile or stream kernel reads it)
+    if (a.ldw <= 0) a.ldw = a.K;
+    const SplitKWs *ws = l.ws;
+    const bool pair = kind == GEMM_W13;
+    GemmShape s = {};
+    s.kind = kind; s.epi = epi; s.P = a.P; s.N = a.N; s.K = a.K; s.ldx = a.ldx; s.n_scale = a.n_scale;
+    s.n_launch_whole = l.n_launch_whole; s.sk = l.sk; s.nq = a.nq; s.nkv = a.nkv;
+    s.w13_one_matrix = pair && a.ldw == 2 * a.K && a.w2 == a.w + a.K;
+    s.part_floats = ws != nullptr && ws->part != nullptr ? ws->part_floats : 0;
+    s.cnt_ints = ws != nullptr && ws->cnt != nullptr ? ws->cnt_ints : 0;
+    const GemmPlan p = prefill_gemm_plan(s);
+    switch (p.family) {
+    case GF_INVALID: return hipErrorInvalidValue;
+    case GF_NOT_SUPPORTED: return hipErrorNotSupported;
+    case GF_NO_WORKSPACE: return hipErrorOutOfMemory;
+    case GF_SHORT: return p.paired ? launch_prefill_skinny_pair(p.epi, a, st) : launch_prefill_skinny(p.epi, a, st);
+    default: break;
     }
-    if (P <= skinny_max && sk <= 1) return hipErrorNotSupported;
-    if (((uintptr_t)x & 15) || ((uintptr_t)wq & 15) || ((uintptr_t)wk & 15) || ((uintptr_t)wv & 15)) return hipErrorInvalidValue;
-    const int ldw_true = K;        // W rows are K floats apart; the loop runs over whole 64-k stages (see pad_k)
-    K = pad_k(K, 64, ldx);
-    if (K < 0 || ldx % 4 != 0) return hipErrorInvalidValue;
-    const int N = nq + 2 * nkv;
-    const long long n_qkv_whole = (long long)N * (n_scale > 0 ? n_scale : 1);
-    const bool x3 = x3_applies(n_qkv_whole, K);   // the bf16 matrix cores (prepare_x3 decides the same)
-    if (sk > 1) {  // the split family: 64-feature tiles (a tile must not straddle q | k | v)
-        if (nq % 64 != 0 || nkv % 64 != 0) return hipErrorNotSupported;
-        GemmArgs as = {x, nullptr, wq, q_out, q_out, P, N, K, ldx, ldq, ldq, pos0, rope, head_size, n_scale > 0 ? n_scale : 1,
-                       wk, wv, kcache, vcache, nq, nkv, ldkv, kv_head_stride, 0, 0};
-        as.ldw = ldw_true;
-        if (const hipError_t e = prepare_x3(as, ws, st, (long long)N * as.n_scale, planes_ready); e != hipSuccess) return e;
-        return gemm_launch_sk<G_QKV, false>(as, N, sk, ws, st);
+    const int n_each = a.N;
+    a.K = p.K;
+    if (p.x3)
+        if (const hipError_t e = prepare_x3(a, ws, st, l.planes_ready); e != hipSuccess) return e;
+    // W1 | W3: the gated rows' planes beside them (the W2 launch's operand; every paired form of the planes kernel finishes in
+    // the same epilogue): only whole 64-k rows -- the split launch writes the zeros of pad columns -- and only where the second
+    // planes matrix exists (the unsharded pass)
+    if (pair && a.x3 != nullptr && l.kp_out == n_each && (n_each & 63) == 0 && ws->x3b != nullptr &&
+        (size_t)a.P * 3 * l.kp_out * sizeof(__bf16) <= ws->x3b_bytes) {
+        a.x3_out = ws->x3b; a.kp_out = l.kp_out;
+        l.planes_written = true;
     }
-    {
-        const KgsChoice c = choose_kgs(N, P, K, false, ws, x3);
-        const int feat_k = c.tile == TILE_128x128 ? 128 : 64;  // a tile must not straddle q | k | v
-        if (c.use && nq % feat_k == 0 && nkv % feat_k == 0) {
-            GemmArgs ak = {x, nullptr, wq, q_out, q_out, P, N, K, ldx, ldq, ldq, pos0, rope, head_size, n_scale > 0 ? n_scale : 1,
-                           wk, wv, kcache, vcache, nq, nkv, ldkv, kv_head_stride, 0, 0};
-            ak.ldw = ldw_true;
-            return gemm_launch_kgs<G_QKV, false>(ak, N, c.tile, ws, st);   // (never in the planes mode: choose_kgs)
-        }
+    if (p.family == GF_STREAM && pair) {   // ONE matrix of alternating rows
+        a.w2 = nullptr; a.N = 2 * n_each; a.ldw = in.K;
     }
-    TileForm tf = choose_tile(N, P, false);
-    // 128 x 64 tiles mean q alone already gives every CU its one resident block: three such launches
-    // measured 445 us against 453 for the 768-block one (7B, 512 tokens).  With the smaller tiles several
-    // blocks share a CU and the longer grid keeps them supplied: 128 tokens 21.8 -> 19.4 ms fused.
-    // (The same on the bf16 cores: 7B, 1024 / 512 tokens 74.3 / 40.6 ms with three launches, 80.3 / 41.6 fused on 128 x 64
-    // tiles -- the caller's k and v launches reuse q's planes: planes_ready.)
-    (void)x3;
-    if (tf == TILE_128x64 || tf == TILE_128x128) return hipErrorNotSupported;
-    int feat = tf == TILE_32x32 ? 32 : 64;
-    if (nq % feat != 0 || nkv % feat != 0) {
-        if (nq % 32 != 0 || nkv % 32 != 0) return hipErrorNotSupported;
-        tf = TILE_32x32;
-        feat = 32;
-    }
-    GemmArgs a = {x, nullptr, wq, q_out, q_out, P, N, K, ldx, ldq, ldq, pos0, rope, head_size, 1,
-                  wk, wv, kcache, vcache, nq, nkv, ldkv, kv_head_stride, 0, 0};
-    a.ldw = ldw_true;
-    if (const hipError_t e = prepare_x3(a, ws, st, n_qkv_whole, planes_ready); e != hipSuccess) return e;
-    constexpr int KS = 2;
-    const int tok = tf == TILE_128x64 ? 128 : tf == TILE_64x64 ? 64 : 32;
-    const DmaForm f = tf == TILE_128x64 ? dma_form<G_QKV, 2, 1, KS, false>(a.x3 != nullptr)
-                    : tf == TILE_64x64  ? dma_form<G_QKV, 1, 1, KS, false>(a.x3 != nullptr)
-                    : tf == TILE_32x64  ? dma_form<G_QKV, 1, 1, KS, false, 1, 2>(a.x3 != nullptr)
-                                        : dma_form<G_QKV, 1, 1, KS, false, 1, 1>(a.x3 != nullptr);
-    const dim3 grid = dma_grid(N / feat, (P + tok - 1) / tok, &a);
-    void *params[] = {&a};
-    return hipLaunchKernel(f.fn, grid, dim3(f.threads), params, f.lds, st);
-}
-
-// k | v of one layer in ONE launch for short prompts (P <= 64: prefill_skinny.hip's paired form; X is
-// brought into the CU once for both).  hipErrorNotSupported otherwise: the caller launches the two.
-hipError_t launch_prefill_gemm_kv_pair(const float *x, int ldx, const float *wk, const float *wv, float *kcache,
-                                       float *vcache, int ldkv, int P, int nkv, int K, int pos0, const float2 *rope,
-                                       int head_size, hipStream_t st, int n_scale, size_t kv_head_stride, int sk,
-                                       long long n_launch_whole)
-{
-    constexpr int skinny_max = Tunables::pf_skinny_max;
-    if (P > skinny_max || sk > 1) return hipErrorNotSupported;  // sk > 1: the tile kernel's split-K family takes it
-    if (n_launch_whole > 0 && x3_stream_shape(n_launch_whole, P, (K + 63) / 64 * 64)) return hipErrorNotSupported;  // the stream form takes k and v
-    if (((uintptr_t)x & 15) || ((uintptr_t)wk & 15) || ((uintptr_t)wv & 15)) return hipErrorInvalidValue;
-    GemmArgs a = {x, wv, wk, kcache, kcache, P, nkv, K, ldx, ldkv, ldkv, pos0, rope, head_size, n_scale > 0 ? n_scale : 1,
-                  wk, wv, kcache, vcache, 0, nkv, ldkv, kv_head_stride, 0, 0};
-    a.ldw = K;
-    return launch_prefill_skinny_pair(G_QKV, a, st);
-}
-
-// C[P,N] (+)= X[P,K] W[N,K]^T with the chosen epilogue; K % 4 == 0, 16-byte aligned rows
-hipError_t launch_prefill_gemm(int epi, const float *x, int ldx, const float *w, float *out, int ldo,
-                               int P, int N, int K, int pos0, const float2 *rope, int head_size,
-                               hipStream_t st, const float *res, int ldres, int n_scale, size_t kv_head_stride,
-                               int sk, const SplitKWs *ws, int ldw, long long n_launch_whole, int planes_ready, DeferredSum *defer)
-{
-    if (P <= 0 || N <= 0 || K <= 0 || (K % 4) != 0 || (ldx % 4) != 0) return hipErrorInvalidValue;
-    if (((uintptr_t)x & 15) || ((uintptr_t)w & 15)) return hipErrorInvalidValue;
-    if (defer) defer->valid = false;
-    if (res == nullptr) { res = out; ldres = ldo; }  // PG_RESID in place
-    GemmArgs a = {x, nullptr, w, out, res, P, N, K, ldx, ldo, ldres, pos0, rope, head_size, n_scale > 0 ? n_scale : 1, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, kv_head_stride, 0, 0};
-    a.ldw = ldw > 0 ? ldw : K;
-    constexpr int skinny_max = Tunables::pf_skinny_max;
-    // n_whole: the rows of the WHOLE model's launch this product belongs to (q | k | v count as one: n_launch_whole)
-    if (const int kp = pad_k(K, 64, ldx); kp > 0 && epi != G_SWIGLU &&
-        x3_stream_shape(n_launch_whole > 0 ? n_launch_whole : (long long)N * a.n_scale, P, kp)) {
-        const long long nw = n_launch_whole > 0 ? n_launch_whole : (long long)N * a.n_scale;
-        a.K = kp;
-        switch (epi) {
-            case G_STORE: return launch_x3_stream<G_STORE>(a, nw, ws, st, planes_ready);
-            case G_RESID: return launch_x3_stream<G_RESID>(a, nw, ws, st, planes_ready, defer);
-            case G_ROPE: return launch_x3_stream<G_ROPE>(a, nw, ws, st, planes_ready);
-            case G_ROPE_CACHE: return launch_x3_stream<G_ROPE_CACHE>(a, nw, ws, st, planes_ready);
-            case G_CACHE: return launch_x3_stream<G_CACHE>(a, nw, ws, st, planes_ready);
-        }
-    }
-    if (P <= skinny_max && sk <= 1) return launch_prefill_skinny(epi, a, st);  // prefill_skinny.hip
-    K = a.K = pad_k(K, 64, ldx);   // whole 64-k stages (see pad_k)
-    if (K < 0) return hipErrorInvalidValue;
-    if (const hipError_t e = prepare_x3(a, ws, st, n_launch_whole > 0 ? n_launch_whole : (long long)N * a.n_scale, planes_ready); e != hipSuccess) return e;
-    if (sk > 1) {
-        if (K / 64 < sk) return hipErrorInvalidValue;
-        switch (epi) {
-            case G_STORE: return gemm_launch_sk<G_STORE, false>(a, N, sk, ws, st);
-            case G_RESID: return gemm_launch_sk<G_RESID, false>(a, N, sk, ws, st);
-            case G_ROPE: return gemm_launch_sk<G_ROPE, false>(a, N, sk, ws, st);
-            case G_ROPE_CACHE: return gemm_launch_sk<G_ROPE_CACHE, false>(a, N, sk, ws, st);
-            case G_CACHE: return gemm_launch_sk<G_CACHE, false>(a, N, sk, ws, st);
-            case G_SWIGLU: return gemm_launch_sk<G_SWIGLU, false>(a, N, sk, ws, st);
-        }
+    return with_epi(p.epi, [&](auto e) -> hipError_t {
+        constexpr int EPI = decltype(e)::value;
+        if (p.family == GF_STREAM) {
+            if constexpr (EPI != G_SWIGLU) return launch_x3_stream<EPI>(a, p, ws, st, l.defer);
+        } else if (pair) {
+            if constexpr (EPI == G_STORE) return launch_tile<G_STORE, true>(a, p, ws, st);
+        } else if constexpr (EPI != G_SWIGLU_IL) return launch_tile<EPI, false>(a, p, ws, st);
         return hipErrorInvalidValue;
-    }
-    if (epi == G_RESID) {  // wo, W2: the two-block form where the grid is short of blocks (same bits)
-        const KgsChoice c = choose_kgs(N, P, K, false, ws, a.x3 != nullptr);
-        if (c.use) return gemm_launch_kgs<G_RESID, false>(a, N, c.tile, ws, st);
-    }
-    switch (epi) {
-        case G_STORE: return gemm_launch<G_STORE>(a, st);
-        case G_RESID: return gemm_launch<G_RESID>(a, st);
-        case G_ROPE: return gemm_launch<G_ROPE>(a, st);
-        case G_ROPE_CACHE: return gemm_launch<G_ROPE_CACHE>(a, st);
-        case G_CACHE: return gemm_launch<G_CACHE>(a, st);
-        case G_SWIGLU: return gemm_launch<G_SWIGLU>(a, st);
-    }
-    return hipErrorInvalidValue;
+    });
 }
 
 // host logic behind the launches, for tests (include/llama2_hip_test.h): no device needed

@@ -6,6 +6,7 @@
 #include <mutex>
 
 #include "l2z_state.h"
+#include "prefill_common.h"
 
 using namespace l2z;
 
@@ -120,6 +121,90 @@ StageOut stage_out(const l2z_runstate *s, int k)
     }
 }
 
+// What the products of one chunk share, and their builder: operands and shape by name (prefill_common.h gemm) plus the
+// chunk's place; the caller adds the outputs.
+struct Chunk {
+    int P, pos0, world, hs;
+    const float2 *rope;
+    const SplitKWs *ws;
+    hipStream_t st;
+};
+Chunk chunk_of(l2z_runstate *s, int P, int pos0) { return {P, pos0, s->sh.world, s->sh.hs, s->rope, &s->pf_sk, s->stream}; }
+GemmArgs product(const Chunk &c, const float *x, int ldx, const float *w, int ldw, int N, int K)
+{
+    GemmArgs a = gemm(x, ldx, w, ldw, N, K, c.P);
+    a.n_scale = c.world; a.pos0 = c.pos0; a.rope = c.rope; a.head_size = c.hs;
+    return a;
+}
+GemmLaunch launch_of(const Chunk &c, int sk, PlanesReady planes = PLANES_SPLIT)
+{
+    GemmLaunch l;
+    l.sk = sk; l.ws = c.ws; l.planes_ready = planes;
+    return l;
+}
+
+// q of the local heads ([P, nq]) and the k / v rows of the local kv heads into the layer's caches
+struct QkvProduct {
+    const float *x;
+    int ldx, K;
+    const float *wq, *wk, *wv;
+    int nq, nkv;
+    float *q, *kc, *vc;
+    size_t kvh_stride;
+    long long n_whole;   // the whole model's q | k | v launch (the stream form's K ranges)
+};
+// One launch where a kernel takes the three (:308-358), else q, then -- kv_pair: short prompts -- k | v together, else k and
+// v, which reuse q's planes.
+int launch_qkv(const Chunk &c, const QkvProduct &p, GemmLaunch l, bool kv_pair)
+{
+    GemmArgs q = product(c, p.x, p.ldx, p.wq, p.K, p.nq, p.K);
+    q.out = p.q; q.ldo = p.nq;
+    GemmArgs k = product(c, p.x, p.ldx, p.wk, p.K, p.nkv, p.K);
+    k.out = p.kc; k.ldo = p.nkv; k.kv_head_stride = p.kvh_stride;
+    GemmArgs a = q;
+    a.N = p.nq + 2 * p.nkv; a.nq = p.nq; a.nkv = p.nkv; a.wk = p.wk; a.wv = p.wv; a.outk = p.kc; a.outv = p.vc; a.ldkv = p.nkv;
+    a.kv_head_stride = p.kvh_stride;
+    const hipError_t qe = launch_prefill_gemm(GEMM_QKV, 0, a, l, c.st);
+    if (qe != hipErrorNotSupported) {
+        L2Z_HIP(qe);
+        return L2Z_OK;
+    }
+    l.n_launch_whole = p.n_whole;
+    L2Z_HIP(launch_prefill_gemm(GEMM_SINGLE, PG_ROPE, q, l, c.st));   // :308-351
+    l.planes_ready = PLANES_READY;   // (q's planes stand)
+    if (kv_pair) {
+        GemmArgs kv = k;
+        kv.w2 = p.wv; kv.outk = p.kc; kv.outv = p.vc; kv.ldkv = p.nkv;
+        const hipError_t ke = launch_prefill_gemm(GEMM_KV, 0, kv, l, c.st);
+        if (ke != hipErrorNotSupported) {
+            L2Z_HIP(ke);
+            return L2Z_OK;
+        }
+    }
+    L2Z_HIP(launch_prefill_gemm(GEMM_SINGLE, PG_ROPE_CACHE, k, l, c.st));   // :354-357
+    k.w = p.wv; k.out = p.vc;
+    L2Z_HIP(launch_prefill_gemm(GEMM_SINGLE, PG_CACHE, k, l, c.st));        // :358
+    return L2Z_OK;
+}
+
+// :405-416: W1 (a.w) and W3 (a.w2) in one launch with silu(a) * b as its epilogue where a kernel takes the shape, else two
+// GEMMs, the second one merging into the first one's output (W1's planes stand for it -- or rmsnorm's).  l.planes_written:
+// whether the gated rows' planes were left beside them (l.kp_out).
+int launch_w13(const Chunk &c, GemmArgs a, GemmLaunch &l)
+{
+    const hipError_t pe = launch_prefill_gemm(GEMM_W13, 0, a, l, c.st);
+    if (pe != hipErrorNotSupported) {
+        L2Z_HIP(pe);
+        return L2Z_OK;
+    }
+    const float *w3 = a.w2;
+    a.w2 = nullptr;
+    L2Z_HIP(launch_prefill_gemm(GEMM_SINGLE, PG_STORE, a, l, c.st));    // :405
+    a.w = w3;
+    L2Z_HIP(launch_prefill_gemm(GEMM_SINGLE, PG_SWIGLU, a, l, c.st));   // :408 + :411-416 in the epilogue
+    return L2Z_OK;
+}
+
 // The launches of stage k of layer l.  One rank: straight into the destination matrix.  Sharded: this
 // rank's [P, n_loc] block, contiguous, at pf_stage + rank * P * n_loc; the exchange and the unpack
 // into the destination follow (comm_bulk_allgather, or the emulated-rank driver's copies).
@@ -130,6 +215,7 @@ int prefill_stage(l2z_runstate *s, const l2z_weights *w, int l, int k, int P, in
     const l2z_config &c = s->cfg;
     const Shard &sh = s->sh;
     hipStream_t st = s->stream;
+    const Chunk ch = chunk_of(s, P, pos0);
     const int dim = c.dim, hid = c.hidden_dim, kvd = sh.kvd_loc, hs = sh.hs;
     const bool sharded = sh.world > 1;
     const StageOut o = stage_out(s, k);
@@ -141,9 +227,10 @@ int prefill_stage(l2z_runstate *s, const l2z_weights *w, int l, int k, int P, in
     // K ranges per output tile (split-K family, prefill_gemm.hip): part of the arithmetic, so taken from the WHOLE
     // model's matrices -- q | k | v as one launch's width whether or not they go out as one launch
     const int kvd_whole = c.n_kv_heads * hs;
+    const long long n_qkv = (long long)dim + 2 * kvd_whole;
     const int ldxn = s->pf_ld_xn, ldatt = s->pf_ld_att, ldh1 = s->pf_ld_h1;   // padded rows of the GEMM inputs (pf_ld)
     const int dim64 = (dim + 63) / 64 * 64, hid64 = (hid + 63) / 64 * 64;     // K as the tile GEMM walks it
-    const int sk_qkv = prefill_split_k((long long)dim + 2 * kvd_whole, P, dim64, false);
+    const int sk_qkv = prefill_split_k(n_qkv, P, dim64, false);
     const int sk_wo = prefill_split_k(dim, P, dim64, false), sk_w2 = prefill_split_k(dim, P, hid64, false);
     const int sk_h1 = prefill_split_k(hid, P, dim64, true);
     const SplitKWs *ws = &s->pf_sk;
@@ -151,7 +238,7 @@ int prefill_stage(l2z_runstate *s, const l2z_weights *w, int l, int k, int P, in
     // the WHOLE model's matrix so that a shard takes what the unsharded pass takes.
     auto panel = [&](PanelProduct &pp, long long n_whole, bool *taken) -> int {
         *taken = false;
-        const long long widest_whole = std::max((long long)dim + 2 * kvd_whole, 2LL * hid) + 128;
+        const long long widest_whole = std::max(n_qkv, 2LL * hid) + 128;
         if (!prefill_panel_shape(n_whole, P, pp.K, widest_whole)) return L2Z_OK;
         pp.P = P;
         const hipError_t e = launch_prefill_panel(pp, g_cus, ws, st);
@@ -182,9 +269,9 @@ int prefill_stage(l2z_runstate *s, const l2z_weights *w, int l, int k, int P, in
                (x3_stream_shape(n_whole, P, kp) || P > Tunables::pf_skinny_max || sk > 1) && ws->x3 != nullptr &&
                (size_t)P * 3 * kp * 2 <= ws->x3_bytes;
     };
-    int xn_planes = PLANES_SPLIT;
+    PlanesReady xn_planes = PLANES_SPLIT;
     if (k == PF_ATT || k == PF_H1) {  // :305 / :398
-        const bool pl = k == PF_ATT ? planes_for((long long)dim + 2 * kvd_whole, dim, sk_qkv) : planes_for(2LL * hid, dim, sk_h1);
+        const bool pl = k == PF_ATT ? planes_for(n_qkv, dim, sk_qkv) : planes_for(2LL * hid, dim, sk_h1);
         // (... and adds the K ranges' sums the residual product before it left behind: DeferredSum)
         L2Z_HIP(launch_prefill_rmsnorm(s->pf_xn, ldxn, s->pf_x, (k == PF_ATT ? w->rms_att : w->rms_ffn) + (size_t)l * dim, dim, P, st,
                                        pl ? ws->x3 : nullptr, dim, &s->pf_pending));
@@ -195,20 +282,39 @@ int prefill_stage(l2z_runstate *s, const l2z_weights *w, int l, int k, int P, in
     // Wo / W2 may leave their K ranges' sums to the rmsnorm launch that reads the residual stream next (the unsharded pass; W2
     // of the last layer finishes itself: the classifier reads x)
     const bool may_defer = !sharded && tunables().pf_fuse_planes != 0;
+    // Wo / W2 (:392-395 / :419-422): x += the product of the stage before's output (its planes where they stand)
+    auto residual = [&](const float *x, int ldx, const float *wm, int K, int sk, PlanesReady planes, bool defer) -> int {
+        const float *res = s->pf_x + sh.dim0;
+        PanelProduct pp = {};
+        pp.x = x; pp.ldx = ldx; pp.K = K; pp.w0 = wm; pp.rows0 = sh.dim_loc;
+        pp.mode = PANEL_RESID; pp.out = out; pp.ldo = ldo; pp.res = res; pp.ldres = dim;
+        L2Z_TRY(panel(pp, dim, &taken));
+        if (taken) return L2Z_OK;
+        GemmArgs a = product(ch, x, ldx, wm, K, sh.dim_loc, K);
+        a.out = out; a.ldo = ldo; a.res = res; a.ldres = dim;
+        GemmLaunch gl = launch_of(ch, sk, sharded ? PLANES_SPLIT : planes);
+        gl.defer = defer ? &s->pf_pending : nullptr;
+        L2Z_HIP(launch_prefill_gemm(GEMM_SINGLE, PG_RESID, a, gl, st));
+        return L2Z_OK;
+    };
     if (k == PF_ATT && rg != nullptr) {
         // Rows of several sequences: the three products with the plain-store epilogue into scratch (the forms of the
         // whole model's q | k | v launch at this chunk length, as where the single-sequence pass launches them apart),
         // then ONE launch that rotates q and k at each row's own position and stores k / v into each row's own caches,
         // then ONE attention launch in which a row sees its own sequence's cache only (prefill_ragged.hip).
         L2Z_CHECK(!sharded, L2Z_ERR_INVALID, "batched prefill: rows of several sequences on a shard");
-        const long long n_qkv = (long long)dim + 2 * kvd_whole;
         const size_t layer_off = (size_t)l * c.seq_len * kvd;
-        L2Z_HIP(launch_prefill_gemm(PG_STORE, s->pf_xn, ldxn, w->wq + (size_t)l * dim * dim, s->pf_q, dim, P, dim, dim, 0,
-                                    s->rope, hs, st, nullptr, 0, 1, 0, sk_qkv, ws, 0, n_qkv, xn_planes));
-        L2Z_HIP(launch_prefill_gemm(PG_STORE, s->pf_xn, ldxn, w->wk + (size_t)l * kvd * dim, rg->k, kvd, P, kvd, dim, 0,
-                                    s->rope, hs, st, nullptr, 0, 1, 0, sk_qkv, ws, 0, n_qkv, PLANES_READY));   // (q's planes stand)
-        L2Z_HIP(launch_prefill_gemm(PG_STORE, s->pf_xn, ldxn, w->wv + (size_t)l * kvd * dim, rg->v, kvd, P, kvd, dim, 0,
-                                    s->rope, hs, st, nullptr, 0, 1, 0, sk_qkv, ws, 0, n_qkv, PLANES_READY));
+        GemmLaunch gl = launch_of(ch, sk_qkv, xn_planes);
+        gl.n_launch_whole = n_qkv;
+        struct { const float *w; float *out; int n; } qkv[3] = {{w->wq + (size_t)l * dim * dim, s->pf_q, dim},
+                                                                {w->wk + (size_t)l * kvd * dim, rg->k, kvd},
+                                                                {w->wv + (size_t)l * kvd * dim, rg->v, kvd}};
+        for (const auto &m : qkv) {
+            GemmArgs a = product(ch, s->pf_xn, ldxn, m.w, dim, m.n, dim);
+            a.out = m.out; a.ldo = m.n;
+            L2Z_HIP(launch_prefill_gemm(GEMM_SINGLE, PG_STORE, a, gl, st));
+            gl.planes_ready = PLANES_READY;   // (q's planes stand)
+        }
         L2Z_HIP(launch_ragged_rope_scatter(s->pf_q, dim, *rg, P, dim, kvd, hs, s->rope, layer_off, kvh_stride, st));
         bool att_planes = false;
         const bool want = planes_for(dim, dim, sk_wo);
@@ -216,41 +322,18 @@ int prefill_stage(l2z_runstate *s, const l2z_weights *w, int l, int k, int P, in
                                         c.n_heads / c.n_kv_heads, c.seq_len, st, want ? ws->x3 : nullptr, dim, &att_planes));
         s->pf_planes_att = att_planes ? PLANES_READY : PLANES_SPLIT;
     } else if (k == PF_ATT) {
+        const QkvProduct qp = {s->pf_xn, ldxn, dim, w->wq + (size_t)l * sh.dim_loc * dim, w->wk + (size_t)l * kvd * dim,
+                               w->wv + (size_t)l * kvd * dim, sh.dim_loc, kvd, s->pf_q, kc, vc, kvh_stride, n_qkv};
         {
             PanelProduct pp = {};
-            pp.x = s->pf_xn; pp.ldx = ldxn; pp.K = dim;
-            pp.w0 = w->wq + (size_t)l * sh.dim_loc * dim; pp.w1 = w->wk + (size_t)l * kvd * dim; pp.w2 = w->wv + (size_t)l * kvd * dim;
+            pp.x = qp.x; pp.ldx = ldxn; pp.K = dim;
+            pp.w0 = qp.wq; pp.w1 = qp.wk; pp.w2 = qp.wv;
             pp.rows0 = sh.dim_loc; pp.rows1 = kvd; pp.rows2 = kvd;
             pp.mode = PANEL_QKV; pp.out = s->pf_q; pp.ldo = sh.dim_loc; pp.outk = kc; pp.outv = vc; pp.ldkv = kvd;
             pp.head_size = hs; pp.pos0 = pos0; pp.kv_head_stride = kvh_stride; pp.rope = s->rope;
-            L2Z_TRY(panel(pp, (long long)dim + 2 * kvd_whole, &taken));
+            L2Z_TRY(panel(pp, n_qkv, &taken));
         }
-        if (!taken) {
-        // q of the local heads ([P, dim_loc]) and the k / v rows of the local kv heads: one launch where
-        // the tile kernel takes the shape (:308-358), else three
-        const float *wq = w->wq + (size_t)l * sh.dim_loc * dim, *wk = w->wk + (size_t)l * kvd * dim,
-                    *wv = w->wv + (size_t)l * kvd * dim;
-        const hipError_t qe = launch_prefill_gemm_qkv(s->pf_xn, ldxn, wq, wk, wv, s->pf_q, sh.dim_loc, kc, vc, kvd, P,
-                                                      sh.dim_loc, kvd, dim, pos0, s->rope, hs, st, kvh_stride, sh.world,
-                                                      sk_qkv, ws, xn_planes);
-        if (qe == hipErrorNotSupported) {
-            const long long n_qkv = (long long)dim + 2 * kvd_whole;   // the whole model's q | k | v launch (the stream form's K ranges)
-            L2Z_HIP(launch_prefill_gemm(PG_ROPE, s->pf_xn, ldxn, wq, s->pf_q, sh.dim_loc, P, sh.dim_loc, dim, pos0,
-                                        s->rope, hs, st, nullptr, 0, sh.world, 0, sk_qkv, ws, 0, n_qkv, xn_planes));  // :308-351
-            const hipError_t ke = launch_prefill_gemm_kv_pair(s->pf_xn, ldxn, wk, wv, kc, vc, kvd, P, kvd, dim, pos0,
-                                                              s->rope, hs, st, sh.world, kvh_stride, sk_qkv, n_qkv);  // short prompts: k | v together
-            if (ke == hipErrorNotSupported) {
-                L2Z_HIP(launch_prefill_gemm(PG_ROPE_CACHE, s->pf_xn, ldxn, wk, kc, kvd, P, kvd, dim, pos0, s->rope, hs,
-                                            st, nullptr, 0, sh.world, kvh_stride, sk_qkv, ws, 0, n_qkv, PLANES_READY));   // :354-357 (q's planes stand)
-                L2Z_HIP(launch_prefill_gemm(PG_CACHE, s->pf_xn, ldxn, wv, vc, kvd, P, kvd, dim, pos0, s->rope, hs, st,
-                                            nullptr, 0, sh.world, kvh_stride, sk_qkv, ws, 0, n_qkv, PLANES_READY));       // :358
-            } else {
-                L2Z_HIP(ke);
-            }
-        } else {
-            L2Z_HIP(qe);
-        }
-        }
+        if (!taken) L2Z_TRY(launch_qkv(ch, qp, launch_of(ch, sk_qkv, xn_planes), true));
         // (the attention output's planes for the Wo product: nothing reads ws->x3 any more -- q | k | v are done)
         bool att_planes = false;
         const bool want = planes_for(dim, dim, sk_wo);
@@ -259,21 +342,9 @@ int prefill_stage(l2z_runstate *s, const l2z_weights *w, int l, int k, int P, in
                                          want ? ws->x3 : nullptr, dim, &att_planes));  // :361-389
         s->pf_planes_att = att_planes ? PLANES_READY : PLANES_SPLIT;
     } else if (k == PF_WO) {
-        const float *res = s->pf_x + sh.dim0;
-        {
-            PanelProduct pp = {};
-            pp.x = s->pf_att; pp.ldx = ldatt; pp.K = dim; pp.w0 = w->wo + (size_t)l * sh.dim_loc * dim; pp.rows0 = sh.dim_loc;
-            pp.mode = PANEL_RESID; pp.out = out; pp.ldo = ldo; pp.res = res; pp.ldres = dim;
-            L2Z_TRY(panel(pp, dim, &taken));
-        }
-        if (!taken)
-        L2Z_HIP(launch_prefill_gemm(PG_RESID, s->pf_att, ldatt, w->wo + (size_t)l * sh.dim_loc * dim, out, ldo,
-                                    P, sh.dim_loc, dim, pos0, s->rope, hs, st, res, dim, sh.world, 0, sk_wo, ws, 0, 0,
-                                    sharded ? PLANES_SPLIT : s->pf_planes_att, may_defer ? &s->pf_pending : nullptr));   // :392-395
+        L2Z_TRY(residual(s->pf_att, ldatt, w->wo + (size_t)l * sh.dim_loc * dim, dim, sk_wo, s->pf_planes_att, may_defer));
         s->pf_planes_att = PLANES_SPLIT;
     } else if (k == PF_H1) {
-        // :405-416: W1 and W3 in one launch with silu(a) * b as its epilogue where the tile kernel
-        // takes the shape, else two GEMMs, the second one merging into the first one's output
         // W1 | W3 share one slot of the device blob, rows alternating: rows of either are 2 dim apart
         const float *w1 = w->w1 + (size_t)l * sh.hid_loc * 2 * dim, *w3 = w->w3 + (size_t)l * sh.hid_loc * 2 * dim;
         {
@@ -284,33 +355,15 @@ int prefill_stage(l2z_runstate *s, const l2z_weights *w, int l, int k, int P, in
         }
         s->pf_planes_h1 = PLANES_SPLIT;
         if (taken) return L2Z_OK;
-        bool h1_planes = false;
-        const hipError_t pe = launch_prefill_gemm_swiglu_pair(s->pf_xn, ldxn, w1, w3, out, ldo, P, sh.hid_loc, dim, st, sh.world,
-                                                              sk_h1, ws, 2 * dim, xn_planes,
-                                                              planes_for(dim, hid, sk_w2) ? hid : 0, &h1_planes);
-        if (pe == hipSuccess && h1_planes) s->pf_planes_h1 = PLANES_READY_B;
-        if (pe == hipErrorNotSupported) {
-            L2Z_HIP(launch_prefill_gemm(PG_STORE, s->pf_xn, ldxn, w1, out, ldo, P, sh.hid_loc, dim, pos0, s->rope,
-                                        hs, st, nullptr, 0, sh.world, 0, sk_h1, ws, 2 * dim, 0, xn_planes));                      // :405
-            L2Z_HIP(launch_prefill_gemm(PG_SWIGLU, s->pf_xn, ldxn, w3, out, ldo, P, sh.hid_loc, dim, pos0, s->rope,
-                                        hs, st, nullptr, 0, sh.world, 0, sk_h1, ws, 2 * dim, 0,
-                                        xn_planes));  // :408 + :411-416 in the epilogue (W1's planes stand -- or rmsnorm's)
-        } else {
-            L2Z_HIP(pe);
-        }
+        GemmArgs a = product(ch, s->pf_xn, ldxn, w1, 2 * dim, sh.hid_loc, dim);
+        a.w2 = w3; a.out = out; a.ldo = ldo;
+        GemmLaunch gl = launch_of(ch, sk_h1, xn_planes);
+        gl.kp_out = planes_for(dim, hid, sk_w2) ? hid : 0;
+        L2Z_TRY(launch_w13(ch, a, gl));
+        if (gl.planes_written) s->pf_planes_h1 = PLANES_READY_B;
     } else {
-        const float *res = s->pf_x + sh.dim0;
-        {
-            PanelProduct pp = {};
-            pp.x = s->pf_h1; pp.ldx = ldh1; pp.K = hid; pp.w0 = w->w2 + (size_t)l * sh.dim_loc * hid; pp.rows0 = sh.dim_loc;
-            pp.mode = PANEL_RESID; pp.out = out; pp.ldo = ldo; pp.res = res; pp.ldres = dim;
-            L2Z_TRY(panel(pp, dim, &taken));
-        }
-        if (!taken)
-        L2Z_HIP(launch_prefill_gemm(PG_RESID, s->pf_h1, ldh1, w->w2 + (size_t)l * sh.dim_loc * hid, out, ldo,
-                                    P, sh.dim_loc, hid, pos0, s->rope, hs, st, res, dim, sh.world, 0, sk_w2, ws, 0, 0,
-                                    sharded ? PLANES_SPLIT : s->pf_planes_h1,
-                                    may_defer && l + 1 < c.n_layers ? &s->pf_pending : nullptr));   // :419-422
+        L2Z_TRY(residual(s->pf_h1, ldh1, w->w2 + (size_t)l * sh.dim_loc * hid, hid, sk_w2, s->pf_planes_h1,
+                         may_defer && l + 1 < c.n_layers));
         s->pf_planes_h1 = PLANES_SPLIT;
     }
     return L2Z_OK;
@@ -323,61 +376,45 @@ int prefill_stage(l2z_runstate *s, const l2z_weights *w, int l, int k, int P, in
 //   half 0: rmsnorm, q | k | v of the local heads, attention -> pf_att [P, dimc_pad]; Wo columns -> pf_part
 //   half 1: rmsnorm, W1 | W3 of the local rows -> pf_h1 [P, hidc_pad]; W2 columns -> pf_part
 // The products are split across ranks differently than in the unsharded pass: logits at the parity tolerance, the ranks
-// bit-identical to each other (tests/test_gpu_scheme_b.py).
+// bit-identical to each other (tests/test_gpu_scheme_b.py).  The chains of the row-sharded pass (launch_qkv, launch_w13),
+// without what scheme B never does: the panel kernel, k | v paired, planes written by their producer, deferred sums.
 int prefill_half_b(l2z_runstate *s, const l2z_weights *w, int l, int half, int P, int pos0)
 {
     const l2z_config &c = s->cfg;
     const Shard &sh = s->sh;
     hipStream_t st = s->stream;
+    const Chunk ch = chunk_of(s, P, pos0);
     const int dim = c.dim, kvd = sh.kvd_loc, hs = sh.hs;
     float *kc = s->key_cache + (size_t)l * c.seq_len * kvd;
     float *vc = s->value_cache + (size_t)l * c.seq_len * kvd;
     const size_t kvh_stride = (size_t)c.seq_len * hs;
-    const SplitKWs *ws = &s->pf_sk;
     // kernel forms are chosen from what every rank sees alike: the whole matrices' row counts and the shards' widths
-    const int kvd_whole = c.n_kv_heads * hs;
-    const int epi = sh.rank == 0 ? PG_RESID : PG_STORE;
+    const long long n_qkv = (long long)dim + 2 * c.n_kv_heads * hs;
     const int ldxn = s->pf_ld_xn, ldatt = s->pf_ld_att, ldh1 = s->pf_ld_h1;   // padded rows of the GEMM inputs (pf_ld)
     const int dim64 = (dim + 63) / 64 * 64;
+    // this rank's column shard of Wo / W2 ([dim, kc_pad]): its partial product, rank 0's with the residual (:392-395 / :419-422)
+    auto partial = [&](const float *x, int ldx, const float *wm, int kc_pad) -> int {
+        GemmArgs a = product(ch, x, ldx, wm, kc_pad, dim, kc_pad);
+        a.n_scale = 1; a.out = s->pf_part; a.ldo = dim; a.res = s->pf_x; a.ldres = dim;
+        GemmLaunch gl = launch_of(ch, prefill_split_k(dim, P, (kc_pad + 63) / 64 * 64, false));
+        L2Z_HIP(launch_prefill_gemm(GEMM_SINGLE, sh.rank == 0 ? PG_RESID : PG_STORE, a, gl, st));
+        return L2Z_OK;
+    };
     if (half == 0) {
         L2Z_HIP(launch_prefill_rmsnorm(s->pf_xn, ldxn, s->pf_x, w->rms_att + (size_t)l * dim, dim, P, st));  // :305
-        const int sk_qkv = prefill_split_k((long long)dim + 2 * kvd_whole, P, dim64, false);
-        const float *wq = w->wq + (size_t)l * sh.dim_loc * dim, *wk = w->wk + (size_t)l * kvd * dim, *wv = w->wv + (size_t)l * kvd * dim;
-        const hipError_t qe = launch_prefill_gemm_qkv(s->pf_xn, ldxn, wq, wk, wv, s->pf_q, sh.dim_loc, kc, vc, kvd, P, sh.dim_loc, kvd,
-                                                      dim, pos0, s->rope, hs, st, kvh_stride, sh.world, sk_qkv, ws);
-        if (qe == hipErrorNotSupported) {
-            const long long n_qkv = (long long)dim + 2 * kvd_whole;
-            L2Z_HIP(launch_prefill_gemm(PG_ROPE, s->pf_xn, ldxn, wq, s->pf_q, sh.dim_loc, P, sh.dim_loc, dim, pos0, s->rope, hs, st,
-                                        nullptr, 0, sh.world, 0, sk_qkv, ws, 0, n_qkv));
-            L2Z_HIP(launch_prefill_gemm(PG_ROPE_CACHE, s->pf_xn, ldxn, wk, kc, kvd, P, kvd, dim, pos0, s->rope, hs, st, nullptr, 0,
-                                        sh.world, kvh_stride, sk_qkv, ws, 0, n_qkv, true));
-            L2Z_HIP(launch_prefill_gemm(PG_CACHE, s->pf_xn, ldxn, wv, vc, kvd, P, kvd, dim, pos0, s->rope, hs, st, nullptr, 0,
-                                        sh.world, kvh_stride, sk_qkv, ws, 0, n_qkv, true));
-        } else {
-            L2Z_HIP(qe);
-        }
+        const QkvProduct qp = {s->pf_xn, ldxn, dim, w->wq + (size_t)l * sh.dim_loc * dim, w->wk + (size_t)l * kvd * dim,
+                               w->wv + (size_t)l * kvd * dim, sh.dim_loc, kvd, s->pf_q, kc, vc, kvh_stride, n_qkv};
+        L2Z_TRY(launch_qkv(ch, qp, launch_of(ch, prefill_split_k(n_qkv, P, dim64, false)), false));
         L2Z_HIP(launch_prefill_attention(s->pf_q, sh.dim_loc, kc, vc, s->pf_att, ldatt, pos0, P, sh.heads_loc, hs, hs,
                                          kvh_stride, c.n_heads / c.n_kv_heads, c.seq_len, st, c.n_heads));   // :361-389
-        const int sk = prefill_split_k(dim, P, (sh.dimc_pad + 63) / 64 * 64, false);
-        L2Z_HIP(launch_prefill_gemm(epi, s->pf_att, ldatt, w->wo + (size_t)l * dim * sh.dimc_pad, s->pf_part, dim, P, dim,
-                                    sh.dimc_pad, pos0, s->rope, hs, st, s->pf_x, dim, 1, 0, sk, ws));        // :392-395
+        L2Z_TRY(partial(s->pf_att, ldatt, w->wo + (size_t)l * dim * sh.dimc_pad, sh.dimc_pad));
     } else {
         L2Z_HIP(launch_prefill_rmsnorm(s->pf_xn, ldxn, s->pf_x, w->rms_ffn + (size_t)l * dim, dim, P, st));  // :398
-        const int sk_h1 = prefill_split_k(c.hidden_dim, P, dim64, true);
-        const float *w1 = w->w1 + (size_t)l * sh.hid_loc * 2 * dim, *w3 = w->w3 + (size_t)l * sh.hid_loc * 2 * dim;
-        const hipError_t pe = launch_prefill_gemm_swiglu_pair(s->pf_xn, ldxn, w1, w3, s->pf_h1, ldh1, P, sh.hid_loc, dim, st,
-                                                              sh.world, sk_h1, ws, 2 * dim);
-        if (pe == hipErrorNotSupported) {
-            L2Z_HIP(launch_prefill_gemm(PG_STORE, s->pf_xn, ldxn, w1, s->pf_h1, ldh1, P, sh.hid_loc, dim, pos0, s->rope, hs, st,
-                                        nullptr, 0, sh.world, 0, sk_h1, ws, 2 * dim));                     // :405
-            L2Z_HIP(launch_prefill_gemm(PG_SWIGLU, s->pf_xn, ldxn, w3, s->pf_h1, ldh1, P, sh.hid_loc, dim, pos0, s->rope, hs,
-                                        st, nullptr, 0, sh.world, 0, sk_h1, ws, 2 * dim));                 // :408-416
-        } else {
-            L2Z_HIP(pe);
-        }
-        const int sk = prefill_split_k(dim, P, (sh.hidc_pad + 63) / 64 * 64, false);
-        L2Z_HIP(launch_prefill_gemm(epi, s->pf_h1, ldh1, w->w2 + (size_t)l * dim * sh.hidc_pad, s->pf_part, dim, P, dim,
-                                    sh.hidc_pad, pos0, s->rope, hs, st, s->pf_x, dim, 1, 0, sk, ws));        // :419-422
+        GemmArgs a = product(ch, s->pf_xn, ldxn, w->w1 + (size_t)l * sh.hid_loc * 2 * dim, 2 * dim, sh.hid_loc, dim);
+        a.w2 = w->w3 + (size_t)l * sh.hid_loc * 2 * dim; a.out = s->pf_h1; a.ldo = ldh1;
+        GemmLaunch gl = launch_of(ch, prefill_split_k(c.hidden_dim, P, dim64, true));
+        L2Z_TRY(launch_w13(ch, a, gl));
+        L2Z_TRY(partial(s->pf_h1, ldh1, w->w2 + (size_t)l * dim * sh.hidc_pad, sh.hidc_pad));
     }
     return L2Z_OK;
 }
@@ -525,11 +562,16 @@ int score_chunk(l2z_runstate *s, const l2z_weights *w, const ScoreCall *sc, int 
     a.part_i = (int *)(a.part_s + (size_t)s->sc_cap * nseg);
     a.tgt = (float *)(a.part_i + (size_t)s->sc_cap * nseg);
     a.targets = sc->d_targets ? sc->d_targets + done : nullptr;
+    const Chunk ch = chunk_of(s, P, 0);
+    GemmLaunch gl = launch_of(ch, sk);
+    gl.n_launch_whole = V;
     for (int col0 = 0; col0 < V; col0 += cols) {
         const int n = std::min(cols, V - col0);
         // (the first slab's launch cuts the rows into their planes of bf16 terms where the product runs on those cores; they stand for the rest)
-        L2Z_HIP(launch_prefill_gemm(PG_STORE, s->pf_xn, ldxn, w->wcls + (size_t)col0 * dim, slab, a.ld, P, n, dim, 0, s->rope,
-                                    s->sh.hs, st, nullptr, 0, 1, 0, sk, &s->pf_sk, 0, V, col0 == 0 ? PLANES_SPLIT : PLANES_READY));
+        GemmArgs g = product(ch, s->pf_xn, ldxn, w->wcls + (size_t)col0 * dim, dim, n, dim);
+        g.out = slab; g.ldo = a.ld;
+        L2Z_HIP(launch_prefill_gemm(GEMM_SINGLE, PG_STORE, g, gl, st));
+        gl.planes_ready = PLANES_READY;
         a.n = n; a.col0 = col0; a.seg0 = col0 / kScoreSeg;
         L2Z_HIP(launch_score_reduce(a, st));
     }

@@ -192,38 +192,32 @@ int skinny_k(const GemmArgs &a)
     return (a.ldx % 4) != 0 ? -1 : ke;
 }
 
-template <int EPI, int TMS>
+// The launch's 1-D grid for ntx feature groups x nty token tiles (the kernel's block -> tile comment): several token tiles,
+// or one and feature groups dealt to the XCDs (skinny_spread), pad the feature groups to whole windows of 8; else 2-D
+dim3 skinny_grid(const GemmArgs &a, unsigned ntx, unsigned nty, GemmArgs *args)
+{
+    args->ntx = 0; args->nty = 0;
+    if (nty == 1 && !skinny_spread(a)) return dim3(ntx, nty);
+    args->ntx = (int)ntx;
+    if (nty > 1) args->nty = (int)nty;
+    return dim3((ntx + 7) / 8 * 8 * nty);
+}
+
+// SW-deep ring of (16 NW + 16 TMS)-row stages; NW = 2: the paired form (a.w | a.w2)
+template <int EPI, int TMS, int SW, int NW = 1>
 hipError_t skinny_launch_t(const GemmArgs &a, hipStream_t st)
 {
     static_assert(TMS <= 2, "one or two token tiles (at 64 tokens the stage would take 83 KB)");
-    dim3 grid((a.N + 15) / 16, (a.P + 16 * TMS - 1) / (16 * TMS));
+    const size_t lds = (size_t)SW * (16 * NW + 16 * TMS) * kSkLD2 * sizeof(float);
+    const void *fn = (const void *)prefill_skinny_dma<EPI, TMS, SW, NW>;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
     GemmArgs args = a;
     args.K = skinny_k(a);
     if (args.K < 0) return hipErrorInvalidValue;
-    constexpr int SW = TMS == 1 ? 4 : 3;
-    const size_t lds = (size_t)SW * (16 + 16 * TMS) * kSkLD2 * sizeof(float);
-    const void *fn = (const void *)prefill_skinny_dma<EPI, TMS, SW>;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    dim3 g1 = grid;
-    args.ntx = 0; args.nty = 0;
-    if (grid.y == 1 && skinny_spread(a)) {
-        args.ntx = (int)grid.x;
-        g1 = dim3((grid.x + 7) / 8 * 8);
-    }
-    if (grid.y > 1) {
-        args.ntx = (int)grid.x; args.nty = (int)grid.y;
-        g1 = dim3((grid.x + 7) / 8 * 8 * grid.y);
-    }
+    const dim3 g1 = skinny_grid(a, (a.N + 15) / 16, (a.P + 16 * TMS - 1) / (16 * TMS), &args);
     void *params[] = {&args};
     return hipLaunchKernel(fn, g1, dim3(kPfBlock), params, lds, st);
-}
-
-// one token tile per block?  (see skinny_launch)
-bool skinny_one_tile(const GemmArgs &a)
-{
-    const bool cached = (size_t)a.N * (size_t)a.n_scale * (size_t)a.K * sizeof(float) <= ((size_t)16 << 20);
-    return a.P <= 16 || cached || (a.P > 32 && a.P <= 48);
 }
 
 template <int EPI>
@@ -235,41 +229,31 @@ hipError_t skinny_launch(const GemmArgs &a, hipStream_t st)
     // from 33 tokens several blocks per 16 rows of W, paired on one XCD by the 1-D grid (64 tokens: 17.4 ms
     // with four token tiles in registers -> 15.8; 40 tokens 15.4 -> 14.0: that form is gone).  The one-
     // and two-tile forms sum in the same order.
-    const bool one = skinny_one_tile(a);
-    return one ? skinny_launch_t<EPI, 1>(a, st) : skinny_launch_t<EPI, 2>(a, st);
+    const bool one = skinny_one_tile((long long)a.N * a.n_scale, a.K, a.P);
+    return one ? skinny_launch_t<EPI, 1, 4>(a, st) : skinny_launch_t<EPI, 2, 3>(a, st);
 }
 
 }  // namespace
+
+// one token tile per block?  (see skinny_launch)
+bool skinny_one_tile(long long n_whole, int K, int P)
+{
+    const bool cached = (size_t)n_whole * (size_t)K * sizeof(float) <= ((size_t)16 << 20);
+    return P <= 16 || cached || (P > 32 && P <= 48);
+}
 
 // a.w | a.w2 in one launch of the direct-to-LDS form (epi G_SWIGLU: out = silu(X w^T) * (X w2^T);
 // G_QKV: RoPE(X w^T) into a.outk's rows pos0 + token, X w2^T into a.outv's).  hipErrorNotSupported when
 // the shape takes another short-prompt form: the caller launches the two products separately.
 hipError_t launch_prefill_skinny_pair(int epi, const GemmArgs &a, hipStream_t st)
 {
-    if (!skinny_one_tile(a)) return hipErrorNotSupported;
-    constexpr int SW = 3;
-    const size_t lds = (size_t)SW * (32 + 16) * kSkLD2 * sizeof(float);
-    const void *fn = epi == G_SWIGLU   ? (const void *)prefill_skinny_dma<G_SWIGLU, 1, SW, 2>
-                   : epi == G_QKV      ? (const void *)prefill_skinny_dma<G_QKV, 1, SW, 2>
-                   : epi == G_QKV_ROWS ? (const void *)prefill_skinny_dma<G_QKV_ROWS, 1, SW, 2> : nullptr;
-    if (fn == nullptr) return hipErrorInvalidValue;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    GemmArgs args = a;
-    args.K = skinny_k(a);
-    if (args.K < 0) return hipErrorInvalidValue;
-    dim3 grid((a.N + 15) / 16, (a.P + 15) / 16), g1 = grid;
-    args.ntx = 0; args.nty = 0;
-    if (grid.y == 1 && skinny_spread(a)) {
-        args.ntx = (int)grid.x;
-        g1 = dim3((grid.x + 7) / 8 * 8);
+    if (!skinny_one_tile((long long)a.N * a.n_scale, a.K, a.P)) return hipErrorNotSupported;
+    switch (epi) {
+        case G_SWIGLU: return skinny_launch_t<G_SWIGLU, 1, 3, 2>(a, st);
+        case G_QKV: return skinny_launch_t<G_QKV, 1, 3, 2>(a, st);
+        case G_QKV_ROWS: return skinny_launch_t<G_QKV_ROWS, 1, 3, 2>(a, st);
     }
-    if (grid.y > 1) {
-        args.ntx = (int)grid.x; args.nty = (int)grid.y;
-        g1 = dim3((grid.x + 7) / 8 * 8 * grid.y);
-    }
-    void *params[] = {&args};
-    return hipLaunchKernel(fn, g1, dim3(kPfBlock), params, lds, st);
+    return hipErrorInvalidValue;
 }
 
 // The batched decode step (batch_host.cpp): P <= 16 rows, one token tile -- the form, the grid and the K order of every
@@ -279,10 +263,10 @@ hipError_t launch_batch_skinny(int epi, const GemmArgs &a, hipStream_t st)
 {
     if (a.P < 1 || a.P > 16) return hipErrorInvalidValue;
     switch (epi) {
-        case G_ROPE_ROWS: return skinny_launch_t<G_ROPE_ROWS, 1>(a, st);
-        case G_OUT_ROWS: return skinny_launch_t<G_OUT_ROWS, 1>(a, st);
+        case G_ROPE_ROWS: return skinny_launch_t<G_ROPE_ROWS, 1, 4>(a, st);
+        case G_OUT_ROWS: return skinny_launch_t<G_OUT_ROWS, 1, 4>(a, st);
         case G_QKV_ROWS: return launch_prefill_skinny_pair(G_QKV_ROWS, a, st);
-        case G_RESID: return skinny_launch_t<G_RESID, 1>(a, st);
+        case G_RESID: return skinny_launch_t<G_RESID, 1, 4>(a, st);
         case G_SWIGLU: return launch_prefill_skinny_pair(G_SWIGLU, a, st);
     }
     return hipErrorInvalidValue;

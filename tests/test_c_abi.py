@@ -138,3 +138,167 @@ def test_prefill_matrix_cores_and_stream_ranges_are_pinned(B):
              (2304, 100, 768): 0}
     for (n, p, k), want in cores.items():
         assert B.prefill_cores(n, p, k) == want, (n, p, k, B.prefill_cores(n, p, k))
+
+
+def test_prefill_gemm_plan_is_pinned(B):
+    """Which kernel form every product of the batched prefill takes (host logic, no device: 256 CUs assumed): what a
+    rocprofv3 kernel trace of the pass shows -- kernel family, tile, K ranges, the stream form's block width and ring depth --
+    as a function of numbers only.  The callers' split-K argument is l2z_prefill_split_k of the WHOLE product, as in
+    prefill_host.cpp."""
+    def plan(kind, p, n, k, n_sk=None, **kw):
+        world = kw.get("n_scale", 1)
+        kw.setdefault("sk", B.prefill_split_k((n_sk or n) * world, p, (k + 63) // 64 * 64))
+        return B.prefill_gemm_plan(kind, p, n, k, **kw)
+
+    def qkv(p, nq, nkv, k, **kw):
+        return plan("qkv", p, nq + 2 * nkv, k, nq=nq, nkv=nkv, **kw)
+
+    def stream(pl):
+        return (pl["family"], pl["x3"], pl["feat"], pl["sk"], pl["tm"], pl["nbuf"], pl["one_round"])
+
+    STORE, RESID, ROPE = 0, 1, 2
+    defaults = {"L2Z_PF_X3": 1, "L2Z_PF_X3_STREAM_MIN": 33}   # (csrc/tunables.h; what tests/conftest.py's options puts back)
+    for name, v in defaults.items():
+        B.option_set(name, v)
+    # tests/test_gpu_x3.py test_stream_form_tiles_of_every_width_equal_the_stepped_loop: dim 2048, hidden_dim 14336 -- its
+    # docstring's trace: prefill_x3_stream<6, 2, 4, 6> (q | k | v: 192 features, 8 ranges), <7, 2, 3, 8> (W1 | W3: 256 features on
+    # sixteen waves, 2 ranges), <1, 2, 5, 4> (W2: 128 features, 8 ranges); wo (16 MB: cache resident) on the f32 cores
+    for p in (40, 64):
+        assert stream(qkv(p, 2048, 2048, 2048)) == ("stream", 1, 192, 8, 2, 4, 1), p
+        assert qkv(p, 2048, 2048, 2048)["epi"] == 6
+        wo = plan("single", p, 2048, 2048, epi=RESID)
+        assert (wo["family"], wo["x3"], wo["tms"], wo["paired"]) == ("short", 0, 1, 0), p
+        w13 = plan("w13", p, 14336, 2048, w13_one_matrix=1)
+        assert stream(w13) == ("stream", 1, 256, 2, 2, 3, 1) and w13["epi"] == 7, p
+        assert stream(plan("single", p, 2048, 14336, epi=RESID)) == ("stream", 1, 128, 8, 2, 5, 1), p
+        # (W1 and W3 NOT in one slot: no stream form of the pair)
+        assert plan("w13", p, 14336, 2048)["family"] != "stream"
+    # the 7B figures of the stream form's comment (prefill_gemm.hip plan_stream), 64 tokens: q | k | v 192 features (256 blocks of
+    # 4 ranges), W1 | W3 192 (230 blocks of 2 ranges), wo / W2 128 (256 blocks of 8 ranges)
+    blocks = lambda pl, n: -(-n // pl["feat"]) * pl["sk"]
+    pl = qkv(64, 4096, 4096, 4096)
+    assert stream(pl)[:4] == ("stream", 1, 192, 4) and blocks(pl, 12288) == 256
+    pl = plan("w13", 64, 11008, 4096, w13_one_matrix=1)
+    assert stream(pl)[:4] == ("stream", 1, 192, 2) and blocks(pl, 22016) == 230
+    for k in (4096, 11008):
+        pl = plan("single", 64, 4096, k, epi=RESID)
+        assert stream(pl)[:4] == ("stream", 1, 128, 8) and blocks(pl, 4096) == 256
+    # the RoPE epilogues never run sixteen waves (128 registers per lane: they would spill); 100 tokens: 128 features, four token tiles
+    # (57344 features: 448 blocks of 128 or 299 of 192 do not fit one round, 224 of 256 do)
+    assert stream(plan("single", 40, 57344, 2048, epi=STORE))[2:4] == (256, 1)
+    assert stream(plan("single", 40, 57344, 2048, epi=ROPE))[2:4] == (128, 1)
+    assert stream(plan("single", 100, 4096, 4096, epi=RESID)) == ("stream", 1, 128, 8, 4, 4, 1)
+    # a stream launch whose K ranges' sums do not fit the workspace: hipErrorOutOfMemory
+    assert plan("single", 64, 4096, 4096, epi=RESID, part_floats=(1 << 20) - 1)["family"] == "no workspace"   # 32 tiles x 8 ranges x 2 x 32 x 128
+
+    # What is arithmetic (cores, K ranges, K as walked, kernel family up to the forms that give the same bits) is planned from the
+    # WHOLE model's matrix: a rank's share of the rows plans the same.  Tile and block width are grid fill: they may differ.
+    def arithmetic(pl):
+        fam = "tile" if pl["family"] in ("tile", "two-block") else pl["family"]   # (two-block: the unsplit family's bits)
+        return (fam, pl["epi"], pl["x3"], pl["sk"], pl["k"], pl["tms"], pl["paired"])
+
+    T0 = "-"   # (not a tile-kernel plan)
+
+    def form(pl):   # (the tile field means something in the tile kernel's families only)
+        return (pl["family"], pl["tile"] if pl["family"] in ("tile", "two-block", "split-k") else T0)
+
+    def sharded(kind, p, n, k, want, want_2=None, want_8=None, worlds=(2, 8), **kw):
+        whole = plan(kind, p, n, k, **kw)
+        assert form(whole) == want, (kind, p, n, k, whole)
+        for world, w in zip(worlds, (want_2 or want, want_8 or want)):
+            kw_r = dict(kw, n_scale=world, **{f: kw[f] // world for f in ("nq", "nkv") if f in kw})
+            part = plan(kind, p, n // world, k, **kw_r)
+            assert arithmetic(part) == arithmetic(whole), (kind, p, n, k, world, part, whole)
+            assert form(part) == w, (kind, p, n, k, world, part)
+        return whole
+
+    # 128 x 128 tiles at 1024 tokens on the bf16 cores (tests above: (4096, 1024) -> 128x128); a rank's 2048 / 512 rows fill
+    # the CUs with smaller tiles.  q | k | v fused is refused there (q alone gives every CU its resident block): three launches.
+    pl = sharded("single", 1024, 4096, 4096, ("tile", "128x128"), ("tile", "128x64"), ("tile", "32x64"), epi=ROPE, n_launch_whole=12288)
+    assert (pl["x3"], pl["sk"], pl["k"]) == (1, 1, 4096)
+    assert qkv(1024, 4096, 4096, 4096)["family"] == "not supported"
+    assert qkv(512, 4096, 4096, 4096)["family"] == "not supported"    # 128 x 64 tiles: the same
+    pl = qkv(256, 4096, 4096, 4096)                                   # 64 x 64: fused
+    assert (pl["family"], pl["tile"], pl["epi"], pl["x3"]) == ("tile", "64x64", 6, 1)
+    pl = plan("w13", 512, 11008, 4096, w13_one_matrix=1)              # (tests above: (11008, 512, paired) -> 128x64)
+    assert (pl["family"], pl["tile"], pl["epi"], pl["x3"]) == ("tile", "128x64", 0, 1)
+    B.option_set("L2Z_PF_X3", 0)   # the f32 cores
+    try:
+        # the short-prompt family at 16 tokens: one token tile of 16 per block; W1 | W3 and k | v paired; no fused q | k | v
+        pl = sharded("single", 16, 4096, 4096, ("short", T0), epi=RESID)
+        assert (pl["tms"], pl["paired"], pl["x3"], pl["k"]) == (1, 0, 0, 4096)
+        pl = sharded("w13", 16, 11008, 4096, ("short", T0), w13_one_matrix=1)
+        assert (pl["tms"], pl["paired"], pl["epi"]) == (1, 1, 5)
+        pl = sharded("kv", 16, 4096, 4096, ("short", T0), n_launch_whole=12288)
+        assert (pl["tms"], pl["paired"], pl["epi"]) == (1, 1, 6)
+        sharded("qkv", 16, 12288, 4096, ("not supported", T0), nq=4096, nkv=4096)
+        # ... two token tiles at 17 ... 32 and 49 ... 64 tokens of a matrix that streams from HBM: no paired form there
+        assert sharded("single", 24, 4096, 4096, ("short", T0), epi=RESID, sk=1)["tms"] == 2
+        sharded("w13", 24, 11008, 4096, ("not supported", T0), w13_one_matrix=1, sk=1)
+        sharded("kv", 24, 4096, 4096, ("not supported", T0), n_launch_whole=12288, sk=1)
+        assert sharded("single", 40, 4096, 4096, ("short", T0), epi=RESID)["tms"] == 1
+        assert plan("single", 24, 768, 768, epi=RESID)["tms"] == 1    # stories110M: cache resident
+        # split-K: 4 ranges at 64 tokens, 2 at 100 of the block-starved products (wo, W2); the pair and q | k | v fused at 64.
+        # The tile by the cost model, rounds of 256 blocks x tile area / ranges / efficiency: wo at 64 tokens 256 blocks of
+        # 64 x 64 (1 round x 4096 / 4 / 0.87) against 512 of 32 x 64 (2 x 2048 / 4 / 0.8); half the rows: 256 blocks of 32 x 64
+        pl = sharded("single", 64, 4096, 4096, ("split-k", "64x64"), ("split-k", "32x64"), ("split-k", "32x64"), epi=RESID)
+        assert (pl["sk"], pl["x3"]) == (4, 0)
+        pl = sharded("single", 100, 4096, 11008, ("split-k", "64x64"), ("split-k", "32x64"), ("split-k", "32x64"), epi=RESID)
+        assert (pl["sk"], pl["k"]) == (2, 11008)
+        pl = sharded("single", 100, 4096, 4096, ("split-k", "64x64"), ("split-k", "32x64"), ("split-k", "32x64"), epi=RESID)
+        assert pl["sk"] == 2
+        # ... while q | k | v and W1 | W3 have ~3 blocks per CU at 65 ... 128 tokens and stay unsplit, on the tile that fills the CUs:
+        # 768 blocks of 32 x 64 (3 rounds x 2048 / 0.8) beat 384 of 64 x 64 (2 x 4096 / 0.87); half the rows: 192 of 64 x 64 in one
+        sharded("qkv", 100, 12288, 4096, ("tile", "32x64"), ("tile", "64x64"), ("tile", "32x32"), nq=4096, nkv=4096)
+        sharded("w13", 100, 11008, 4096, ("tile", "32x64"), ("tile", "64x64"), ("tile", "32x32"), w13_one_matrix=1)
+        pl = sharded("w13", 64, 11008, 4096, ("split-k", "64x64"), ("split-k", "32x64"), ("split-k", "32x64"), w13_one_matrix=1)
+        assert (pl["sk"], pl["epi"]) == (4, 0)
+        pl = sharded("qkv", 64, 12288, 4096, ("split-k", "64x64"), ("split-k", "32x64"), ("split-k", "32x64"), nq=4096, nkv=4096)
+        assert (pl["sk"], pl["epi"]) == (4, 6)
+        assert plan("single", 64, 4096, 4096, epi=RESID, part_floats=(1 << 20) - 1)["family"] == "no workspace"   # 64 tiles x 4 ranges x 64 x 64
+        assert plan("single", 64, 4096, 4096, epi=RESID, part_floats=0)["family"] == "invalid"
+        # k-groups on two blocks: chunks of >= 512 tokens on the 128-token tile the unsplit family takes (the residual products,
+        # the pair, q | k | v), where the workspace holds the dump; a rank's 2048 rows take 64 x 64 tiles -- same bits
+        sharded("single", 512, 4096, 4096, ("two-block", "128x64"), ("tile", "64x64"), ("tile", "32x32"), epi=RESID)
+        assert plan("single", 512, 4096, 4096, epi=ROPE)["family"] == "tile"
+        assert plan("single", 511, 4096, 4096, epi=RESID)["family"] == "tile"
+        assert plan("single", 512, 4096, 4096, epi=RESID, part_floats=1 << 20)["family"] == "tile"
+        sharded("w13", 512, 11008, 4096, ("two-block", "128x64"), ("tile", "64x64"), ("tile", "64x64"), w13_one_matrix=1)
+        # (q | k | v, 1024 tokens: half the rows still fill the CUs with 128 x 64 tiles -- 768 blocks, 3 rounds -- an eighth with 32 x 64)
+        sharded("qkv", 1024, 12288, 4096, ("two-block", "128x128"), ("two-block", "128x64"), ("tile", "32x64"), nq=4096, nkv=4096)
+        assert (plan("single", 1024, 4096, 4096, epi=RESID)["family"], plan("single", 1024, 4096, 4096, epi=ROPE)["tile"]) == ("two-block", "128x128")
+    finally:
+        B.option_set("L2Z_PF_X3", defaults["L2Z_PF_X3"])
+    # K not a multiple of 64 (stories15M: dim 288, 6 heads -- ranks of 2 and of 6: six heads do not split eight ways): the kernels walk
+    # K rounded up -- the activation rows are padded with zeros that far (768 floats) -- on the f32 cores (cache resident); 32 x 32 tiles
+    pl = sharded("single", 100, 288, 288, ("tile", "32x32"), worlds=(2, 6), epi=RESID)
+    assert (pl["k"], pl["x3"], pl["sk"]) == (320, 0, 1)
+    # ... q | k | v fused; a rank's 144 or 48 rows are no whole 32-feature tiles: three launches there, the unsplit family's bits
+    pl = qkv(100, 288, 288, 288)
+    assert (pl["family"], pl["tile"], pl["k"], pl["epi"], pl["x3"], pl["sk"]) == ("tile", "32x32", 320, 6, 0, 1)
+    for world in (2, 6):
+        assert qkv(100, 288 // world, 288 // world, 288, n_scale=world)["family"] == "not supported", world
+        part = plan("single", 100, 288 // world, 288, epi=ROPE, n_scale=world, n_launch_whole=864)
+        assert (part["family"], part["k"], part["x3"], part["sk"]) == ("tile", 320, 0, 1), world
+    assert plan("single", 100, 288, 288, epi=RESID, ldx=288)["family"] == "invalid"   # rows not padded to the next stage
+    assert plan("single", 100, 144, 288, epi=RESID, ldx=288, n_scale=2)["family"] == "invalid"
+    assert plan("single", 100, 288, 290, epi=RESID)["family"] == "invalid"            # K % 4
+    # q | k | v refusals, whole and as a rank's share (nq, nkv divided by the ranks).  The stream form wants whole 128-feature
+    # blocks of each matrix; where a share refuses and the whole does not, the rank's three launches take the stream form with the
+    # WHOLE launch's K ranges (n_launch_whole)
+    sharded("qkv", 64, 3 * (4096 - 64), 4096, ("not supported", T0), nq=4096 - 64, nkv=4096 - 64)
+    whole = qkv(64, 4096 - 128, 4096 - 128, 4096)
+    assert whole["family"] == "stream"
+    for world in (2, 8):
+        n = (4096 - 128) // world   # 1984, 496: not multiples of 128
+        assert qkv(64, n, n, 4096, n_scale=world)["family"] == "not supported", world
+        part = plan("single", 64, n, 4096, epi=ROPE, n_scale=world, n_launch_whole=3 * (4096 - 128), sk=whole["sk"])
+        assert (part["family"], part["x3"], part["sk"], part["k"]) == ("stream", 1, whole["sk"], 4096), world
+    # ... and no tile may straddle two of the matrices: 64-feature tiles fall back to 32 x 32 where that divides, else three launches
+    # (a share of q's 4128 rows -- 2064, 516 -- divides by neither)
+    pl = qkv(300, 4096 + 32, 4096, 4096)
+    assert (pl["family"], pl["tile"]) == ("tile", "32x32")
+    for world in (2, 8):
+        assert qkv(300, (4096 + 32) // world, 4096 // world, 4096, n_scale=world)["family"] == "not supported", world
+    sharded("qkv", 300, 3 * 4096 + 16, 4096, ("not supported", T0), nq=4096 + 16, nkv=4096)
+    sharded("qkv", 300, 12288, 4096, ("tile", "64x64"), ("tile", "64x64"), ("tile", "32x64"), nq=4096, nkv=4096)

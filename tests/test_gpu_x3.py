@@ -102,7 +102,7 @@ def test_planes_written_by_the_producers_equal_the_split_launch(gpu, ck, options
 @pytest.mark.gpu
 @pytest.mark.parametrize("n", [40, 64])
 def test_stream_form_tiles_of_every_width_equal_the_stepped_loop(gpu, ck, options, n):
-    """Chunks of <= 64 tokens pick their tile by grid fill (prefill_gemm.hip launch_x3_stream: the narrowest of 128 / 192 / 256
+    """Chunks of <= 64 tokens pick their tile by grid fill (prefill_gemm.hip plan_stream: the narrowest of 128 / 192 / 256
     features -- eight / twelve / sixteen waves -- whose blocks fit one round of 256): a shape whose four products take all
     three.  dim 2048, hidden_dim 14336: q | k | v (6144 features, 8 K ranges) 32 tiles of 192 -- tiles lie across the three
     matrices; wo (16 MB: cache resident) stays on the f32 cores; W1 | W3 (28672 features, 2 ranges: 150 tiles of 192 would be
