@@ -122,6 +122,8 @@ __device__ __forceinline__ void attn_weighted_sum(const float *att, const float 
 // out[i] = part[0][i] + part[1][i] + ... + part[G-1][i], i < hs.  R = 1..16 adjacent lanes
 // share one output: lane r adds partials r, r+R, ... (increasing), then a DPP sum over the R
 // lanes.  R depends only on (G, hs, blockDim) -- fixed per model.
+// WT: the sums are stored write-through (one agent-scope store per value): a hand-off to another block
+template <bool WT = false>
 __device__ __forceinline__ void reduce_partials(const float *part, int G, int hs, float *out,
                                                 const P2pArgs *push = nullptr, int push_e = 0,
                                                 size_t push_idx0 = 0)
@@ -134,22 +136,13 @@ __device__ __forceinline__ void reduce_partials(const float *part, int G, int hs
         for (int gg = r; gg < G; gg += R) s += part[(size_t)gg * hs + i];
     s = lanes_sum(s, R);
     if (i < hs && r == 0) {
-        out[i] = s;
-        if (push) p2p_ll_push(push, push_e, push_idx0 + (size_t)i, s);
+        if constexpr (WT) {
+            __hip_atomic_store(out + i, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else {
+            out[i] = s;
+            if (push) p2p_ll_push(push, push_e, push_idx0 + (size_t)i, s);
+        }
     }
-}
-
-// the same sum, stored write-through (one agent-scope store per value): a hand-off to another block
-__device__ __forceinline__ void reduce_partials_wt(const float *part, int G, int hs, float *out)
-{
-    int R = 1;
-    while (R * 2 <= G && R * 2 * hs <= (int)blockDim.x && R < 16) R <<= 1;
-    const int i = threadIdx.x / R, r = threadIdx.x % R;
-    float s = 0.0f;
-    if (i < hs)
-        for (int gg = r; gg < G; gg += R) s += part[(size_t)gg * hs + i];
-    s = lanes_sum(s, R);
-    if (i < hs && r == 0) __hip_atomic_store(out + i, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // Fast path (head_size % 4 == 0, head_size <= 256).  The first kFastUB timesteps of
@@ -161,6 +154,81 @@ __device__ __forceinline__ void reduce_partials_wt(const float *part, int G, int
 // stories15M sizes this kernel's time is launch + instruction fetch, not data.
 constexpr int kFastUB = 8;
 constexpr int kAttnFastBlock = 1024;  // long contexts: 16 waves per head (32 groups at head_size 128)
+
+// What the one-block-per-head and the split kernel share.  Lane group g holds rows t0 + G * i, i < kFastUB, of its head's
+// K (V) rows in kr (vr): a ROUND; rows are indexed from `base`, row j's float4 column cc.  NT: non-temporal loads.
+struct AttnLane {
+    int g, c0, cc, G, TPR;  // group, lane in group, its float4 column (0 for idle lanes), groups per block, lanes per row
+    size_t stride;          // floats between rows
+};
+
+// the round starting at row t0, rows clamped to bound - 1 (duplicates hit the L1)
+template <bool NT>
+__device__ __forceinline__ void attn_load_round(const float *base, const AttnLane &ln, int t0, int bound, v4f (&r)[kFastUB])
+{
+#pragma unroll
+    for (int i = 0; i < kFastUB; i++) {
+        int t = t0 + ln.G * i;
+        t = t < bound ? t : bound - 1;
+        const v4f *p = (const v4f *)(base + (size_t)t * ln.stride) + ln.cc;
+        if constexpr (NT) r[i] = ldg_nt(p);
+        else r[i] = *p;
+    }
+}
+
+// scores (:367-375) of rows 0 .. T - 1 into att[]; kr holds the first round on entry
+template <bool NT>
+__device__ __forceinline__ void attn_score_rounds(const float *kbase, const AttnLane &ln, v4f qv, v4f (&kr)[kFastUB], int T,
+                                                  float div, float *att)
+{
+    const v4f zero = {0.f, 0.f, 0.f, 0.f};
+    for (int t0 = ln.g;;) {
+#pragma unroll
+        for (int i = 0; i < kFastUB; i++) {
+            float p = hsum4(fma4(qv, kr[i], zero));
+            p = lanes_sum(p, ln.TPR);
+            const int t = t0 + ln.G * i;
+            if (ln.c0 == 0 && t < T) att[t] = p / div;  // :372 divide
+        }
+        t0 += ln.G * kFastUB;
+        if (t0 >= T) break;
+        attn_load_round<NT>(kbase, ln, t0, T, kr);
+    }
+}
+
+// att . V (:381-388) over rows 0 .. T - 1 with weights w[], increasing t within the group; vr holds the first round on entry
+template <bool NT>
+__device__ __forceinline__ v4f attn_wsum_rounds(const float *vbase, const AttnLane &ln, v4f (&vr)[kFastUB], int T, const float *w_)
+{
+    v4f acc = {0.f, 0.f, 0.f, 0.f};
+    for (int t0 = ln.g;;) {
+#pragma unroll
+        for (int i = 0; i < kFastUB; i++) {
+            const int t = t0 + ln.G * i;
+            const float w = t < T ? w_[t] : 0.0f;
+            acc.x = fmaf(vr[i].x, w, acc.x);
+            acc.y = fmaf(vr[i].y, w, acc.y);
+            acc.z = fmaf(vr[i].z, w, acc.z);
+            acc.w = fmaf(vr[i].w, w, acc.w);
+        }
+        t0 += ln.G * kFastUB;
+        if (t0 >= T) break;
+        attn_load_round<NT>(vbase, ln, t0, T, vr);
+    }
+    return acc;
+}
+
+__device__ __forceinline__ AttnLane attn_lane(const AttnGeom &ge, size_t stride)
+{
+    AttnLane ln;
+    ln.g = threadIdx.x / ge.TPR;
+    ln.c0 = threadIdx.x % ge.TPR;
+    ln.cc = ln.c0 < ge.E ? ln.c0 : 0;
+    ln.G = ge.G;
+    ln.TPR = ge.TPR;
+    ln.stride = stride;
+    return ln;
+}
 
 // NT = 256 for short contexts (seq_len <= 512: launch latency matters most),
 // NT = 1024 for long ones (more rows in flight per head).
@@ -177,11 +245,8 @@ __global__ __launch_bounds__(NT) void attention_fast_kernel(const AttnArgs a)
     const int kvh = h / a.kv_mul;                      // :369 (h / kv_mul) * head_size
     const float *kbase = a.kcache + (size_t)kvh * a.kv_head;  // head-major cache: this head's rows are contiguous
     const float *vbase = a.vcache + (size_t)kvh * a.kv_head;
-    const size_t stride = (size_t)a.kv_row;
-    const int g = threadIdx.x / ge.TPR, c0 = threadIdx.x % ge.TPR;
-    const bool active = c0 < ge.E;
-    const int cc = active ? c0 : 0;
-    const int step = ge.G * kFastUB;
+    const AttnLane ln = attn_lane(ge, (size_t)a.kv_row);
+    const bool active = ln.c0 < ge.E;
     const v4f zero = {0.f, 0.f, 0.f, 0.f};
 
     // SPEC (small models, latency-bound): the first round is requested without waiting for
@@ -190,61 +255,15 @@ __global__ __launch_bounds__(NT) void attention_fast_kernel(const AttnArgs a)
     // extra dependent read of pos, so rows are clamped to pos (duplicates hit the L1).
     const int T = *a.pos_ptr + 1;  // timesteps 0..pos inclusive (:367)
     const int lim = SPEC ? a.seq_len : T;
-    const v4f qv = active ? ((const v4f *)(a.q + (size_t)h * hs))[cc] : zero;
+    const v4f qv = active ? ((const v4f *)(a.q + (size_t)h * hs))[ln.cc] : zero;
     v4f kr[kFastUB], vr[kFastUB];
-#pragma unroll
-    for (int i = 0; i < kFastUB; i++) {
-        int t = g + ge.G * i;
-        t = t < lim ? t : lim - 1;
-        kr[i] = ((const v4f *)(kbase + (size_t)t * stride))[cc];
-    }
-#pragma unroll
-    for (int i = 0; i < kFastUB; i++) {
-        int t = g + ge.G * i;
-        t = t < lim ? t : lim - 1;
-        vr[i] = ((const v4f *)(vbase + (size_t)t * stride))[cc];
-    }
-    const float div = sqrtf((float)hs);
-    for (int t0 = g;;) {  // scores (:367-375)
-#pragma unroll
-        for (int i = 0; i < kFastUB; i++) {
-            float p = hsum4(fma4(qv, kr[i], zero));
-            p = lanes_sum(p, ge.TPR);
-            const int t = t0 + ge.G * i;
-            if (c0 == 0 && t < T) att[t] = p / div;  // :372 divide
-        }
-        t0 += step;
-        if (t0 >= T) break;
-#pragma unroll
-        for (int i = 0; i < kFastUB; i++) {
-            int t = t0 + ge.G * i;
-            t = t < T ? t : T - 1;
-            kr[i] = ((const v4f *)(kbase + (size_t)t * stride))[cc];
-        }
-    }
+    attn_load_round<false>(kbase, ln, ln.g, lim, kr);
+    attn_load_round<false>(vbase, ln, ln.g, lim, vr);
+    attn_score_rounds<false>(kbase, ln, qv, kr, T, sqrtf((float)hs), att);
     __syncthreads();
     wave_softmax(att, prob, T);  // :378
-    v4f acc = zero;
-    for (int t0 = g;;) {  // att . V (:381-388), increasing t within the group
-#pragma unroll
-        for (int i = 0; i < kFastUB; i++) {
-            const int t = t0 + ge.G * i;
-            const float w = t < T ? prob[t] : 0.0f;
-            acc.x = fmaf(vr[i].x, w, acc.x);
-            acc.y = fmaf(vr[i].y, w, acc.y);
-            acc.z = fmaf(vr[i].z, w, acc.z);
-            acc.w = fmaf(vr[i].w, w, acc.w);
-        }
-        t0 += step;
-        if (t0 >= T) break;
-#pragma unroll
-        for (int i = 0; i < kFastUB; i++) {
-            int t = t0 + ge.G * i;
-            t = t < T ? t : T - 1;
-            vr[i] = ((const v4f *)(vbase + (size_t)t * stride))[cc];
-        }
-    }
-    if (active) ((v4f *)(part + (size_t)g * hs))[cc] = acc;
+    const v4f acc = attn_wsum_rounds<false>(vbase, ln, vr, T, prob);
+    if (active) ((v4f *)(part + (size_t)ln.g * hs))[ln.cc] = acc;
     __syncthreads();
     // sharded: a.xb already points at this rank's slice, head h of it starts at h * hs
     reduce_partials(part, ge.G, hs, a.xb + (size_t)h * hs, a.push,
@@ -342,10 +361,8 @@ __global__ __launch_bounds__(NT) void attention_split_kernel(const AttnArgs a, i
     const int h = blockIdx.x / nch, c = blockIdx.x % nch;
     const int kvh = h / a.kv_mul;                      // :369
     const size_t stride = (size_t)a.kv_row;
-    const int g = threadIdx.x / ge.TPR, c0 = threadIdx.x % ge.TPR;
-    const bool active = c0 < ge.E;
-    const int cc = active ? c0 : 0;
-    const int step = ge.G * kFastUB;
+    const AttnLane ln = attn_lane(ge, stride);
+    const bool active = ln.c0 < ge.E;
     const v4f zero = {0.f, 0.f, 0.f, 0.f};
 
     // (pos as a kernel ARGUMENT instead of this dependent read -- what a per-replay hipGraphExecKernelNodeSetParams would
@@ -367,41 +384,14 @@ __global__ __launch_bounds__(NT) void attention_split_kernel(const AttnArgs a, i
         for (int i = threadIdx.x; i < hs; i += blockDim.x)
             __hip_atomic_store(po + i, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     } else {
-        const v4f qv = active ? ((const v4f *)(a.q + (size_t)h * hs))[cc] : zero;
+        const v4f qv = active ? ((const v4f *)(a.q + (size_t)h * hs))[ln.cc] : zero;
         v4f kr[kFastUB], vr[kFastUB];
         // K and V rows are read once per token and the long-context cache does not fit the on-die
-        // caches: non-temporal, like the weight stream
-#pragma unroll
-        for (int i = 0; i < kFastUB; i++) {  // rows clamped to the chunk's last one (duplicates hit L1)
-            int j = g + ge.G * i;
-            j = j < Tc ? j : Tc - 1;
-            kr[i] = ldg_nt((const v4f *)(kbase + (size_t)j * stride) + cc);
-        }
-#pragma unroll
-        for (int i = 0; i < kFastUB; i++) {
-            int j = g + ge.G * i;
-            j = j < Tc ? j : Tc - 1;
-            vr[i] = ldg_nt((const v4f *)(vbase + (size_t)j * stride) + cc);
-        }
+        // caches: non-temporal, like the weight stream.  Rows clamped to the chunk's last one.
+        attn_load_round<true>(kbase, ln, ln.g, Tc, kr);
+        attn_load_round<true>(vbase, ln, ln.g, Tc, vr);
         L2Z_ATL(1);
-        const float div = sqrtf((float)hs);
-        for (int j0 = g;;) {  // scores (:367-375), local index j <-> t = t_lo + j
-#pragma unroll
-            for (int i = 0; i < kFastUB; i++) {
-                float p = hsum4(fma4(qv, kr[i], zero));
-                p = lanes_sum(p, ge.TPR);
-                const int j = j0 + ge.G * i;
-                if (c0 == 0 && j < Tc) sc[j] = p / div;  // :372
-            }
-            j0 += step;
-            if (j0 >= Tc) break;
-#pragma unroll
-            for (int i = 0; i < kFastUB; i++) {
-                int j = j0 + ge.G * i;
-                j = j < Tc ? j : Tc - 1;
-                kr[i] = ldg_nt((const v4f *)(kbase + (size_t)j * stride) + cc);
-            }
-        }
+        attn_score_rounds<true>(kbase, ln, qv, kr, Tc, sqrtf((float)hs), sc);  // local index j <-> t = t_lo + j
         __syncthreads();
         L2Z_ATL(2);
         // chunk-local max and sum of exponentials, redundantly per wave (identical in every wave)
@@ -413,29 +403,10 @@ __global__ __launch_bounds__(NT) void attention_split_kernel(const AttnArgs a, i
         for (int j = wave * kWave + lane; j < Tc; j += NT) wt[j] = expf(sc[j] - m);  // unnormalised
         __syncthreads();
         L2Z_ATL(3);
-        v4f acc = zero;
-        for (int j0 = g;;) {  // weighted V (:381-388), increasing t within the group
-#pragma unroll
-            for (int i = 0; i < kFastUB; i++) {
-                const int j = j0 + ge.G * i;
-                const float w = j < Tc ? wt[j] : 0.0f;
-                acc.x = fmaf(vr[i].x, w, acc.x);
-                acc.y = fmaf(vr[i].y, w, acc.y);
-                acc.z = fmaf(vr[i].z, w, acc.z);
-                acc.w = fmaf(vr[i].w, w, acc.w);
-            }
-            j0 += step;
-            if (j0 >= Tc) break;
-#pragma unroll
-            for (int i = 0; i < kFastUB; i++) {
-                int j = j0 + ge.G * i;
-                j = j < Tc ? j : Tc - 1;
-                vr[i] = ldg_nt((const v4f *)(vbase + (size_t)j * stride) + cc);
-            }
-        }
-        if (active) ((v4f *)(part + (size_t)g * hs))[cc] = acc;
+        const v4f acc = attn_wsum_rounds<true>(vbase, ln, vr, Tc, wt);
+        if (active) ((v4f *)(part + (size_t)ln.g * hs))[ln.cc] = acc;
         __syncthreads();
-        reduce_partials_wt(part, ge.G, hs, po);
+        reduce_partials<true>(part, ge.G, hs, po);
     }
     L2Z_ATL(4);
     if (threadIdx.x == 0) {
@@ -578,77 +549,49 @@ int attention_split_wide_pos(int seq_len)
     return seq_len > 512 ? 1024 : seq_len;  // small contexts: 256 threads throughout (as before)
 }
 
+// the vector kernels' shape: float4 rows, 16-byte aligned operands ...
+static bool attn_vec_shape(const AttnArgs &a)
+{
+    return (a.head_size % 4) == 0 && (a.kv_row % 4) == 0 && (a.kv_head % 4) == 0 && aligned16(a.q) && aligned16(a.kcache) &&
+           aligned16(a.vcache);
+}
+// ... and the fast / split kernels' (not the generic one): a head row in one trip of the lane group
+static bool attn_fast_shape(const AttnArgs &a) { return attn_vec_shape(a) && a.head_size <= 256; }
+
+bool attention_push_supported(const AttnArgs &a) { return attn_fast_shape(a); }
+
+bool attention_split_supported(const AttnArgs &a) { return attn_fast_shape(a); }
+
 // small: 256 threads per block (the position is below attention_split_wide_pos)
-hipError_t launch_attention_split(const AttnArgs &a_in, int n_heads_local, int nch, float *part,
+hipError_t launch_attention_split(const AttnArgs &a, int n_heads_local, int nch, float *part,
                                   int *arrivals, hipStream_t st, bool small)
 {
-    const AttnArgs &a = a_in;
     const int nt = small ? kBlock : kAttnFastBlock;
     const AttnGeom ge = attn_geom(a.head_size, true, nt);
     const int max_local = attn_split_per(a.seq_len, nch);  // the kernel's own bound on a chunk's length
     const size_t lds = (size_t)(2 * ((max_local + 3) & ~3) + ge.G * a.head_size) * sizeof(float);
-    if (nt == kAttnFastBlock) {
-        hipError_t e = ensure_lds(attention_split_kernel<kAttnFastBlock>, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(attention_split_kernel<kAttnFastBlock>, dim3(n_heads_local * nch),
-                           dim3(kAttnFastBlock), lds, st, a, nch, part, arrivals);
-    } else {
-        hipError_t e = ensure_lds(attention_split_kernel<kBlock>, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(attention_split_kernel<kBlock>, dim3(n_heads_local * nch), dim3(kBlock), lds,
-                           st, a, nch, part, arrivals);
-    }
-    return hipGetLastError();
-}
-
-bool attention_push_supported(const AttnArgs &a)
-{
-    return (a.head_size % 4) == 0 && (a.kv_row % 4) == 0 && (a.kv_head % 4) == 0 && a.head_size <= 256 && aligned16(a.q) &&
-           aligned16(a.kcache) && aligned16(a.vcache);  // the fast / split kernels, not the generic one
-}
-
-bool attention_split_supported(const AttnArgs &a)
-{
-    return (a.head_size % 4) == 0 && a.head_size <= 256 && (a.kv_row % 4) == 0 && (a.kv_head % 4) == 0 && aligned16(a.q) &&
-           aligned16(a.kcache) && aligned16(a.vcache);
+    const dim3 grid(n_heads_local * nch);
+    return small ? launch_lds(attention_split_kernel<kBlock>, grid, dim3(kBlock), lds, st, a, nch, part, arrivals)
+                 : launch_lds(attention_split_kernel<kAttnFastBlock>, grid, dim3(kAttnFastBlock), lds, st, a, nch, part, arrivals);
 }
 
 // form: 0 = by shape (1024 threads per head for seq_len > 512, else 256 speculative), 1 / 2 force the
 // 256- / 1024-thread fast kernel, 4 forces the generic kernel (tests drive every form directly)
-hipError_t launch_attention(const AttnArgs &a_in, int n_heads_local, hipStream_t st, int form)
+hipError_t launch_attention(const AttnArgs &a, int n_heads_local, hipStream_t st, int form)
 {
-    const AttnArgs &a = a_in;
-    const bool vec = (a.head_size % 4) == 0 && (a.kv_row % 4) == 0 && (a.kv_head % 4) == 0 && aligned16(a.q) &&
-                     aligned16(a.kcache) && aligned16(a.vcache);
-    const size_t lds = attention_lds_bytes(a.head_size, a.seq_len, vec);
-    if (vec && a.head_size <= 256 && form != 4) {
+    const bool vec = attn_vec_shape(a);
+    const dim3 grid(n_heads_local);
+    if (attn_fast_shape(a) && form != 4) {
         const int forced = form == 1 ? kBlock : form == 2 ? kAttnFastBlock : 0;
         const int nt = forced ? forced : (a.seq_len > 512 ? kAttnFastBlock : kBlock);
         const AttnGeom gf = attn_geom(a.head_size, true, nt);
         const size_t lds_fast = (size_t)(2 * ((a.seq_len + 3) & ~3) + gf.G * a.head_size) * sizeof(float);
-        if (nt == kAttnFastBlock) {
-            hipError_t e = ensure_lds(attention_fast_kernel<kAttnFastBlock, false>, lds_fast);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((attention_fast_kernel<kAttnFastBlock, false>), dim3(n_heads_local),
-                               dim3(kAttnFastBlock), lds_fast, st, a);
-        } else {
-            hipError_t e = ensure_lds(attention_fast_kernel<kBlock, true>, lds_fast);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((attention_fast_kernel<kBlock, true>), dim3(n_heads_local),
-                               dim3(kBlock), lds_fast, st, a);
-        }
-        return hipGetLastError();
+        return nt == kAttnFastBlock ? launch_lds(attention_fast_kernel<kAttnFastBlock, false>, grid, dim3(kAttnFastBlock), lds_fast, st, a)
+                                    : launch_lds(attention_fast_kernel<kBlock, true>, grid, dim3(kBlock), lds_fast, st, a);
     }
-    if (vec) {
-        hipError_t e = ensure_lds(attention_kernel<true>, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((attention_kernel<true>), dim3(n_heads_local), dim3(kBlock), lds, st, a);
-    } else {
-        hipError_t e = ensure_lds(attention_kernel<false>, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((attention_kernel<false>), dim3(n_heads_local), dim3(kBlock), lds, st, a);
-    }
-    return hipGetLastError();
+    const size_t lds = attention_lds_bytes(a.head_size, a.seq_len, vec);
+    return vec ? launch_lds(attention_kernel<true>, grid, dim3(kBlock), lds, st, a)
+               : launch_lds(attention_kernel<false>, grid, dim3(kBlock), lds, st, a);
 }
 
 hipError_t launch_dot(float *out, const float *x, const float *y, int n, hipStream_t st)

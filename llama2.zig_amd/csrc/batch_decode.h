@@ -9,6 +9,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "argmax_rule.h"
+
 namespace l2z {
 
 constexpr int kBatchMax = 16;  // L2Z_BATCH_MAX
@@ -49,27 +51,13 @@ hipError_t launch_batch_argmax(const BatchTable *tab, int vocab, int *out, int n
 __device__ inline int block_argmax_1024(const float *lg, int vocab, float *s_val, int *s_idx)
 {
     const int tid = threadIdx.x;
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = tid; i < vocab; i += 1024) {
-        const float v = lg[i];
-        if (bi == 0x7fffffff || v > best) { best = v; bi = i; }
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float ov = __shfl_xor(best, off, 64);
-        const int oi = __shfl_xor(bi, off, 64);
-        if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > best || (ov == best && oi < bi))) { best = ov; bi = oi; }
-    }
-    if ((tid & 63) == 0) { s_val[tid >> 6] = best; s_idx[tid >> 6] = bi; }
+    ArgmaxCand c;
+    for (int i = tid; i < vocab; i += 1024) argmax_take(c, lg[i], i);
+    argmax_wave_fold(c);
+    if ((tid & 63) == 0) { s_val[tid >> 6] = c.v; s_idx[tid >> 6] = c.i; }
     __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < 16; w++) {
-            const float ov = s_val[w];
-            const int oi = s_idx[w];
-            if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > best || (ov == best && oi < bi))) { best = ov; bi = oi; }
-        }
-    }
-    return bi == 0x7fffffff ? 0 : bi;
+    if (tid == 0) argmax_fold_waves(c, s_val, s_idx, 16);
+    return c.i == kNoCandidate ? 0 : c.i;
 }
 
 // l2z_sample_batch (sample_batch.hip): row b draws one token from tab->logits[b] with tab->temperature[b],

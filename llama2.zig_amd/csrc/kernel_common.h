@@ -324,6 +324,33 @@ __device__ __forceinline__ void xstage_finish_ll(const LLPoll &p, const float *_
     });
 }
 
+// The two halves as the mat-vec kernels use them: the registers that live between issue() and finish() -- x (plain: xr,
+// LL: the raw words xl and the poll state) and the rmsnorm weights gr -- and the choice of form.  The arrays are
+// fixed-size members indexed by unrolled constants only, so they stay in registers.
+template <int PRO, int XC, bool LL>
+struct XStage {
+    v4f xr[LL ? 1 : XC], gr[XC];
+    v4u xl[LL ? 2 * XC : 2];
+    LLPoll poll;
+
+    __device__ __forceinline__ void issue(const float *x, const LLIn &xin, const float *rms_w, int n4)
+    {
+        if constexpr (LL) {
+            poll = ll_poll_init(xin);
+            xload_issue_ll<PRO, XC>(poll, rms_w, n4, xl, gr);
+        } else {
+            xload_issue<PRO, XC>(x, rms_w, n4, xr, gr);
+        }
+    }
+    __device__ __forceinline__ void finish(const float *x, const float *rms_w, int n, int n4_pad, float *xs, float *scratch)
+    {
+        if constexpr (LL)
+            xstage_finish_ll<PRO, XC>(poll, rms_w, n, n4_pad, xl, gr, xs, scratch);
+        else
+            xstage_finish<PRO, XC>(x, rms_w, n, n4_pad, xr, gr, xs, scratch);
+    }
+};
+
 // in-place softmax over att[0..T)  (main.zig:687-706)
 __device__ __forceinline__ void block_softmax(float *att, int T, float *scratch)
 {
@@ -393,6 +420,16 @@ hipError_t ensure_lds(K kernel, size_t bytes)
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// ensure_lds + launch, for a kernel whose dynamic LDS may pass 64 KiB
+template <typename K, typename... Args>
+hipError_t launch_lds(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args)
+{
+    hipError_t e = ensure_lds(kernel, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+    return hipGetLastError();
 }
 
 }  // namespace

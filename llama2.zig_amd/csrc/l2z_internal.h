@@ -178,7 +178,7 @@ hipError_t launch_fused_qkv_attn(const FusedQkvAttnArgs &a, int n_heads, hipStre
 
 // Launchers (matvec.hip, attention.hip, misc_kernels.hip).  All return a hipError_t from the launch.
 // pushed: set to whether a.push was honoured (row kernel only)
-// (a.push / a.xin are all-or-nothing: matvec_ll_supported tells beforehand whether they will be)
+// (a.push / a.xin are all-or-nothing: matvec_vector_width tells beforehand whether they will be)
 // packed_w.hip: the 29-bit weight copy -- exponent stats of a matrix (stats: max e, min e, bad; preset 0, 255, 0), its
 // packing (rows x n, row-major; pk: (rows / 2) * pk::pair_dw(n / 4) dwords), and the decode back to f32 (tests)
 hipError_t launch_pk_stats(const float *m, size_t count, uint32_t *stats, hipStream_t st);
@@ -186,11 +186,10 @@ hipError_t launch_pk_pack(const float *m, int rows, int n, int e_base, uint32_t 
 hipError_t launch_pk_unpack(const uint32_t *pk, int rows, int n, int e_base, float *out, hipStream_t st);
 hipError_t launch_matvec(const MatvecArgs &a, int pro, int epi, int max_blocks_per_cu, int n_cus,
                          hipStream_t st, int *out_grid = nullptr, bool *pushed = nullptr);
-// true if a launch with this width takes the vector kernels, which honour push and xin
-bool matvec_ll_supported(int n);
 // true if launch_attention / launch_attention_split will honour a.push (vector kernels only)
 bool attention_push_supported(const AttnArgs &a);
 int matvec_max_grid(int n_cus);
+// true if a launch with this width takes the vector kernels, which honour push and xin
 bool matvec_vector_width(int n);
 // out: >= 8 * n_cus floats of scratch (never written in practice)
 hipError_t launch_stream_read(const float *p, size_t n_floats, float *out, int n_cus, hipStream_t st);  // upper bound of the grid launch_matvec picks

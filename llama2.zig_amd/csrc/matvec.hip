@@ -17,6 +17,9 @@
 //  * token and position live in device memory so one captured hipGraph per
 //    step can be replayed without host involvement.
 // matvec.hip: the fused mat-vec kernels (narrow rows, wide rows, generic scalar) and their launcher.
+#include <type_traits>
+
+#include "argmax_rule.h"
 #include "matvec_device.h"
 #include "packed_w.h"
 
@@ -75,7 +78,7 @@ struct MvGeom {
 // the row end are clamped to its last float4: the matching x entries in LDS are the
 // zero padding, so they add exactly 0 (weights are finite) -- no predicated loads.
 template <int LPR>
-__device__ __forceinline__ void mv_load(const float *pa, const float *pb, int c0, int cb, int n4,
+__device__ __forceinline__ void mv_load(const float *pa, const float *pb, int c0, int n4,
                                         v4f (&wa)[MvGeom<LPR>::U], v4f (&wb)[MvGeom<LPR>::U])
 {
     constexpr int U = MvGeom<LPR>::U;
@@ -83,7 +86,6 @@ __device__ __forceinline__ void mv_load(const float *pa, const float *pb, int c0
     // Per lane: n4 need not be a multiple of the lane count -- the last step of a row like hidden_dim 1376
     // (n4 = 344 = 5 * 64 + 24) is a partial one, the vector form of the reference's scalar tail
     // (main.zig:589-594).
-    (void)cb;
 #pragma unroll
     for (int k = 0; k < U; k++) {
         int c = c0 + LPR * k;
@@ -106,10 +108,21 @@ __device__ __forceinline__ void mv_consume(const v4f *xs4, int c0, const v4f (&w
     }
 }
 
-template <int LPR>
-__device__ __forceinline__ float group_sum(float v)
+// One step of the flat (unit, batch) loop of both vector kernels: after batch b of unit u comes batch b + 1 of the same
+// unit, or batch 0 of the unit ustride further on; `more` = there is such a batch.
+struct MvStep {
+    bool unit_done, more;
+    int u_next, b_next;
+};
+
+__device__ __forceinline__ MvStep mv_step(int u, int b, int n_batches, int ustride, int n_units)
 {
-    return lanes_sum(v, LPR);
+    MvStep s;
+    s.unit_done = (b + 1 == n_batches);
+    s.u_next = s.unit_done ? u + ustride : u;
+    s.b_next = s.unit_done ? 0 : b + 1;
+    s.more = s.u_next < n_units;
+    return s;
 }
 
 template <int PRO, int EPI, int LPR, int XC, bool LL>
@@ -132,15 +145,8 @@ __global__ __launch_bounds__(kBlock) void matvec_kernel(const MatvecArgs a)
     const int ustride = gridDim.x * kWaves;
 
     // 1. issue x loads (they return first), 2. issue the first weight batch, 3. stage x
-    v4f xr[LL ? 1 : XC], gr[XC];
-    v4u xl[LL ? 2 * XC : 2];
-    LLPoll poll;
-    if constexpr (LL) {
-        poll = ll_poll_init(a.xin);
-        xload_issue_ll<PRO, XC>(poll, a.rms_w, n4, xl, gr);
-    } else {
-        xload_issue<PRO, XC>(a.x, a.rms_w, n4, xr, gr);
-    }
+    XStage<PRO, XC, LL> xst;
+    xst.issue(a.x, a.xin, a.rms_w, n4);
     int u = blockIdx.x * kWaves + wave;
     const bool has_unit = u < n_units;
     const float *pa, *pb;
@@ -148,94 +154,60 @@ __global__ __launch_bounds__(kBlock) void matvec_kernel(const MatvecArgs a)
     v4f wa[U], wb[U];
     EpiIn ein = epi_prefetch<EPI>(m, (has_unit ? u : 0) * RW + grp, cl == 0 && has_unit);
     EpiIn ein_next = ein;
-    mv_load<LPR>(pa, pb, cl, 0, n4, wa, wb);
-    if constexpr (LL)
-        xstage_finish_ll<PRO, XC>(poll, a.rms_w, m.n, n4_pad, xl, gr, xs, scratch);
-    else
-        xstage_finish<PRO, XC>(a.x, a.rms_w, m.n, n4_pad, xr, gr, xs, scratch);
+    mv_load<LPR>(pa, pb, cl, n4, wa, wb);
+    xst.finish(a.x, a.rms_w, m.n, n4_pad, xs, scratch);
     if (EPI != EPI_ARGMAX && !has_unit) return;
 
     // flat loop over (unit, batch): consume the batch in registers, then immediately
     // issue the next one -- the next unit's first batch included -- before reducing
     v4f acc_a = {0.f, 0.f, 0.f, 0.f}, acc_b = {0.f, 0.f, 0.f, 0.f};
-    float best_v = -INFINITY;  // EPI_ARGMAX: running (max, first index) of this lane's rows
-    int best_i = 0x7fffffff;
+    ArgmaxCand best;  // EPI_ARGMAX: running (max, first index) of this lane's rows
     int b = 0;
     while (has_unit) {
         mv_consume<LPR>(xs4, cl + b * (LPR * U), wa, wb, acc_a, acc_b);
-        const bool unit_done = (b + 1 == n_batches);
-        const int u_next = unit_done ? u + ustride : u;
-        const int b_next = unit_done ? 0 : b + 1;
-        const bool more = u_next < n_units;
-        if (more) {
-            if (unit_done) {
-                pair_rows<EPI>(m, u_next * RW + grp, pa, pb);
-                ein_next = epi_prefetch<EPI>(m, u_next * RW + grp, cl == 0);
+        const MvStep s = mv_step(u, b, n_batches, ustride, n_units);
+        if (s.more) {
+            if (s.unit_done) {
+                pair_rows<EPI>(m, s.u_next * RW + grp, pa, pb);
+                ein_next = epi_prefetch<EPI>(m, s.u_next * RW + grp, cl == 0);
             }
-            mv_load<LPR>(pa, pb, cl + b_next * (LPR * U), b_next * (LPR * U), n4, wa, wb);
+            mv_load<LPR>(pa, pb, cl + s.b_next * (LPR * U), n4, wa, wb);
         }
-        if (unit_done) {
-            const float sa = group_sum<LPR>(hsum4(acc_a));
-            const float sb = group_sum<LPR>(hsum4(acc_b));
+        if (s.unit_done) {
+            const float sa = lanes_sum(hsum4(acc_a), LPR);
+            const float sb = lanes_sum(hsum4(acc_b), LPR);
             pair_epilogue<EPI>(m, u * RW + grp, sa, sb, cl == 0, ein);
             ein = ein_next;
-            if (EPI == EPI_ARGMAX) {  // single segment: pair p = rows 2p, 2p+1
+            if (EPI == EPI_ARGMAX) {  // single segment: pair p = rows 2p, 2p+1, taken in increasing order
                 const int ra_ = 2 * (u * RW + grp), rb_ = ra_ + 1;
-                if (ra_ < m.total_rows && (sa > best_v || best_i == 0x7fffffff)) {
-                    best_v = sa; best_i = ra_ + a.row_offset;
-                }
-                if (rb_ < m.total_rows && sb > best_v) {  // strict '>' : first index wins ties
-                    best_v = sb; best_i = rb_ + a.row_offset;
-                }
+                if (ra_ < m.total_rows) argmax_take(best, sa, ra_ + a.row_offset);
+                if (rb_ < m.total_rows) argmax_take(best, sb, rb_ + a.row_offset);
             }
             acc_a = v4f{0.f, 0.f, 0.f, 0.f};
             acc_b = v4f{0.f, 0.f, 0.f, 0.f};
         }
-        if (!more) break;
-        u = u_next;
-        b = b_next;
+        if (!s.more) break;
+        u = s.u_next;
+        b = s.b_next;
     }
     if (EPI == EPI_ARGMAX) {
         // block candidate: larger value wins, equal values -> lower index (main.zig:720)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(best_v, o, 64);
-            const int oi = __shfl_xor(best_i, o, 64);
-            if (oi != 0x7fffffff && (best_i == 0x7fffffff || ov > best_v || (ov == best_v && oi < best_i))) {
-                best_v = ov; best_i = oi;
-            }
-        }
+        argmax_wave_fold(best);
         __syncthreads();
         if (lane == 0) {
-            scratch[wave] = best_v;
-            scratch[kWaves + wave] = __int_as_float(best_i);
+            scratch[wave] = best.v;
+            scratch[kWaves + wave] = __int_as_float(best.i);
         }
         __syncthreads();
         if (threadIdx.x == 0) {
-            float bv = scratch[0];
-            int bi = __float_as_int(scratch[kWaves]);
-            for (int w = 1; w < kWaves; w++) {
-                const float ov = scratch[w];
-                const int oi = __float_as_int(scratch[kWaves + w]);
-                if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > bv || (ov == bv && oi < bi))) {
-                    bv = ov; bi = oi;
-                }
-            }
-            a.part_val[blockIdx.x] = bv;
-            a.part_idx[blockIdx.x] = bi;
+            ArgmaxCand c = {scratch[0], __float_as_int(scratch[kWaves])};
+            for (int w = 1; w < kWaves; w++) argmax_merge(c, scratch[w], __float_as_int(scratch[kWaves + w]));
+            a.part_val[blockIdx.x] = c.v;
+            a.part_idx[blockIdx.x] = c.i;
         }
     }
 }
 
-// ---------------------------------------------------------------------------
-// Wide rows (n >= 4096, n/4 a multiple of 64: the 7B shapes): the WHOLE BLOCK works on
-// one pair.  Rows 2p and 2p+1 are adjacent in memory, so a block reads one contiguous
-// 8n-byte run per unit and consecutive blocks read consecutive runs -- the chip sweeps
-// the matrix linearly, like a plain streaming read (DRAM page locality: +10 % over
-// giving every wave its own row pair, measured).  Thread t takes float4 columns
-// t, t+256, ...; per-thread component accumulators, (x+y)+(z+w), wave xor-shuffle,
-// then the 4 wave partials are added in wave order.  Still a function of n only.
-// ---------------------------------------------------------------------------
 // Packed weights (PK, packed_w.h): the raw dwords of one lane's chunk of a batch.  Plane q of 16 bytes per lane lands
 // in q4[q], single-dword plane r in q1[r]: fixed registers whatever the step count S, so a chunk of a runtime S is
 // loaded with wave-uniform predicates and no register is indexed at run time
@@ -285,60 +257,95 @@ __device__ __forceinline__ void pk_decode_lane(const PkRaw &r, int e31, v4f (&wa
     }
 }
 
-// ---------------------------------------------------------------------------
-// Wide rows (n >= 4096, n/4 a multiple of 64: the 7B shapes): the WHOLE BLOCK works on
-// one pair.  Rows 2p and 2p+1 are adjacent in memory, so a block reads one contiguous
-// 8n-byte run per unit and consecutive blocks read consecutive runs -- the chip sweeps
-// the matrix linearly, like a plain streaming read (DRAM page locality: +10 % over
-// giving every wave its own row pair, measured).  Thread t takes float4 columns
-// t, t+256, ...; per-thread component accumulators, (x+y)+(z+w), wave xor-shuffle,
-// then the 4 wave partials are added in wave order.  Still a function of n only.
-// ---------------------------------------------------------------------------
-typedef unsigned v2u_ __attribute__((ext_vector_type(2)));
-typedef unsigned v3u_ __attribute__((ext_vector_type(3)));
+// Where matvec_row_kernel's (unit, batch) loop gets a batch's wa[] / wb[] from.  A source offers
+//   point(m, u)  aim at unit u's pair,
+//   issue(b)     request batch b of that pair,
+//   deliver()    wa[] / wb[] hold the CURRENT batch for the FMAs,
+// and kAhead says when the loop issues the next batch: after the current one's FMAs, into the same registers (fp32), or
+// before them, into a second set of raw words that rotate() makes the current one (packed).
+constexpr int kRowU = 4;  // float4 per row per thread per batch
 
-// Packed weights (PK, packed_w.h): one lane's S-step chunk of a batch -- lane_dw(S) dwords in planes of 16 bytes per
-// lane and one plane of the rest, each a linear sweep of the wave -- into raw[0 .. lane_dw(S))
-template <int S>
-__device__ __forceinline__ void pk_load_lane(const uint32_t *src, int lane, uint32_t (&raw)[pk::kMaxLaneDw])
-{
-    constexpr int N = pk::lane_dw(S), Q = N / 4, R = N % 4;
-#pragma unroll
-    for (int q = 0; q < Q; q++) {
-        const v4u t = __builtin_nontemporal_load((const v4u *)(src + q * 256 + lane * 4));
-        raw[4 * q] = t.x; raw[4 * q + 1] = t.y; raw[4 * q + 2] = t.z; raw[4 * q + 3] = t.w;
-    }
-    const uint32_t *r = src + Q * 256 + lane * R;
-    if constexpr (R == 3) {
-        const v3u_ t = __builtin_nontemporal_load((const v3u_ *)r);
-        raw[4 * Q] = t.x; raw[4 * Q + 1] = t.y; raw[4 * Q + 2] = t.z;
-    } else if constexpr (R == 2) {
-        const v2u_ t = __builtin_nontemporal_load((const v2u_ *)r);
-        raw[4 * Q] = t.x; raw[4 * Q + 1] = t.y;
-    } else if constexpr (R == 1) {
-        raw[4 * Q] = __builtin_nontemporal_load(r);
-    }
-}
+template <int EPI, int XC>
+struct RowF32 {
+    static constexpr bool kAhead = false;
+    v4f wa[kRowU], wb[kRowU];
+    const float *pa, *pb;
+    int n4;
 
-// ... and its values, exactly the f32 bits, into the fp32 kernel's registers; steps past the row end are zero there too
-template <int S>
-__device__ __forceinline__ void pk_decode_lane(const uint32_t (&raw)[pk::kMaxLaneDw], int e31, v4f (&wa)[4], v4f (&wb)[4])
-{
-    uint32_t t[8 * S > 0 ? 8 * S : 1];
-    pk::decode_lane_t<S>(raw, t);
+    __device__ __forceinline__ void init(const MvLocals &, int n4_, int) { n4 = n4_; }
+    __device__ __forceinline__ void point(const MvLocals &m, int u) { pair_rows<EPI>(m, u, pa, pb); }
+    __device__ __forceinline__ void issue(int b)
+    {
+        // columns cb + tid + 256k; validity is wave-uniform (n4 % 64 == 0)
+        const int tid = threadIdx.x, cb = b * (kBlock * kRowU);
+        const v4f *a4 = (const v4f *)pa + cb + tid, *b4 = (const v4f *)pb + cb + tid;
+        const int wbase = cb + (tid & ~63);
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-        if (k < S) {
-            wa[k] = v4f{__builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k]), e31), __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 1]), e31),
-                        __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 2]), e31), __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 3]), e31)};
-            wb[k] = v4f{__builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 4]), e31), __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 5]), e31),
-                        __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 6]), e31), __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 7]), e31)};
-        } else {
-            wa[k] = v4f{0.f, 0.f, 0.f, 0.f};
-            wb[k] = v4f{0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < kRowU; k++) {
+            const bool in_row = wbase + kBlock * k < n4;  // wave-uniform
+            if (XC == 12 && !in_row) {
+                // rows that do not fill their last batch (n = 11008: 704 of 1024 float4): the out-of-row steps
+                // load NOTHING (their x is the zero padding) -- the re-reads of the row start were 11.6 % of
+                // W2's load instructions and, the nt lines long evicted, 2.7 % extra HBM traffic (PMC 1.027x)
+                wa[k] = v4f{0.f, 0.f, 0.f, 0.f};
+                wb[k] = v4f{0.f, 0.f, 0.f, 0.f};
+                continue;
+            }
+            const int off = in_row ? kBlock * k : -(cb + (tid & ~63));
+            wa[k] = ldg_nt(a4 + off);  // out-of-row steps re-read the row start; their x is 0
+            wb[k] = ldg_nt(b4 + off);
         }
     }
-}
+    __device__ __forceinline__ void deliver() {}
+};
+
+template <int XC>
+struct RowPacked {
+    static constexpr bool kAhead = true;
+    v4f wa[kRowU], wb[kRowU];
+    PkRaw raw, nraw;  // raw words of the batch being decoded and of the next one, and their in-row steps
+    int s_cur, s_nxt;
+    const uint32_t *pp;
+    size_t pdw, last_off;
+    int e31, s_last, wave_u, n_batches;
+
+    __device__ __forceinline__ void init(const MvLocals &m, int n4, int n_batches_)
+    {
+        n_batches = n_batches_;
+        e31 = m.pk_e - 31;
+        wave_u = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        pdw = pk::pair_dw(n4);
+        last_off = pk::chunk_off(n4, n_batches - 1, wave_u);
+        s_last = pk::steps(n4, n_batches - 1, wave_u);
+    }
+    __device__ __forceinline__ void point(const MvLocals &m, int u) { pp = pair_packed(m, u, pdw); }
+    __device__ __forceinline__ void issue(int b)
+    {
+        const bool last = b + 1 == n_batches;
+        const uint32_t *src = pp + (last ? last_off : (size_t)b * (4 * 64 * pk::kMaxLaneDw) + (size_t)wave_u * (64 * pk::kMaxLaneDw));
+        s_nxt = (XC == 4 || !last) ? 4 : s_last;  // n = 4096: one full batch
+        pk_load_raw(src, threadIdx.x & 63, XC == 4 ? 4 : s_nxt, nraw);
+    }
+    __device__ __forceinline__ void rotate()
+    {
+        raw = nraw;
+        s_cur = s_nxt;
+    }
+    __device__ __forceinline__ void deliver()
+    {
+        if constexpr (XC == 4) {
+            pk_decode_lane<4>(raw, e31, wa, wb);
+        } else {
+            switch (s_cur) {  // wave-uniform
+                case 4: pk_decode_lane<4>(raw, e31, wa, wb); break;
+                case 3: pk_decode_lane<3>(raw, e31, wa, wb); break;
+                case 2: pk_decode_lane<2>(raw, e31, wa, wb); break;
+                case 1: pk_decode_lane<1>(raw, e31, wa, wb); break;
+                default: pk_decode_lane<0>(raw, e31, wa, wb); break;
+            }
+        }
+    }
+};
 
 // ---------------------------------------------------------------------------
 // Wide rows (n >= 4096, n/4 a multiple of 64: the 7B shapes): the WHOLE BLOCK works on
@@ -358,7 +365,8 @@ __device__ __forceinline__ void pk_decode_lane(const uint32_t (&raw)[pk::kMaxLan
 template <int PRO, int EPI, int XC, bool LL, bool PK = false>
 __global__ __launch_bounds__(kBlock) void matvec_row_kernel(const MatvecArgs a)
 {
-    constexpr int U = 4;
+    constexpr int U = kRowU;
+    using Src = typename std::conditional<PK, RowPacked<XC>, RowF32<EPI, XC>>::type;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const MvLocals m = mv_locals<EPI>(a);
     const int n4 = m.n >> 2;
@@ -372,121 +380,42 @@ __global__ __launch_bounds__(kBlock) void matvec_row_kernel(const MatvecArgs a)
     const int n_units = m.n_pairs;
     const int ustride = gridDim.x;
 
-    v4f xr[LL ? 1 : XC], gr[XC];
-    v4u xl[LL ? 2 * XC : 2];
-    LLPoll poll;
-    if constexpr (LL) {
-        poll = ll_poll_init(a.xin);
-        xload_issue_ll<PRO, XC>(poll, a.rms_w, n4, xl, gr);
-    } else {
-        xload_issue<PRO, XC>(a.x, a.rms_w, n4, xr, gr);
-    }
+    XStage<PRO, XC, LL> xst;
+    xst.issue(a.x, a.xin, a.rms_w, n4);
     int u = blockIdx.x;  // grid <= n_units
-    const float *pa, *pb;
-    if constexpr (!PK) pair_rows<EPI>(m, u, pa, pb);
-    v4f wa[U], wb[U];
-    auto load = [&](int cb) {  // columns cb + tid + 256k; validity is wave-uniform (n4 % 64 == 0)
-        const v4f *a4 = (const v4f *)pa + cb + tid, *b4 = (const v4f *)pb + cb + tid;
-        const int wbase = cb + (tid & ~63);
-#pragma unroll
-        for (int k = 0; k < U; k++) {
-            const bool in_row = wbase + kBlock * k < n4;  // wave-uniform
-            if (XC == 12 && !in_row) {
-                // rows that do not fill their last batch (n = 11008: 704 of 1024 float4): the out-of-row steps
-                // load NOTHING (their x is the zero padding) -- the re-reads of the row start were 11.6 % of
-                // W2's load instructions and, the nt lines long evicted, 2.7 % extra HBM traffic (PMC 1.027x)
-                wa[k] = v4f{0.f, 0.f, 0.f, 0.f};
-                wb[k] = v4f{0.f, 0.f, 0.f, 0.f};
-                continue;
-            }
-            const int off = in_row ? kBlock * k : -(cb + (tid & ~63));
-            wa[k] = ldg_nt(a4 + off);  // out-of-row steps re-read the row start; their x is 0
-            wb[k] = ldg_nt(b4 + off);
-        }
-    };
-    // PK: raw words of the batch being decoded and of the next one, and their in-row steps
-    PkRaw raw, nraw;
-    int s_cur = 4, s_nxt = 4;
-    const int e31 = m.pk_e - 31;
-    const uint32_t *pp = nullptr;
-    size_t pdw = 0, last_off = 0;
-    int s_last = 4;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    auto pk_load = [&](int b_, PkRaw &dst, int &s_out) __attribute__((always_inline)) {
-        if constexpr (PK) {
-            const bool last = b_ + 1 == n_batches;
-            const uint32_t *src = pp + (last ? last_off : (size_t)b_ * (4 * 64 * pk::kMaxLaneDw) + (size_t)wave_u * (64 * pk::kMaxLaneDw));
-            s_out = (XC == 4 || !last) ? 4 : s_last;  // n = 4096: one full batch
-            pk_load_raw(src, lane, XC == 4 ? 4 : s_out, dst);
-        }
-    };
-    auto pk_decode = [&]() __attribute__((always_inline)) {
-        if constexpr (PK) {
-            if constexpr (XC == 4) {
-                pk_decode_lane<4>(raw, e31, wa, wb);
-            } else {
-                switch (s_cur) {  // wave-uniform
-                    case 4: pk_decode_lane<4>(raw, e31, wa, wb); break;
-                    case 3: pk_decode_lane<3>(raw, e31, wa, wb); break;
-                    case 2: pk_decode_lane<2>(raw, e31, wa, wb); break;
-                    case 1: pk_decode_lane<1>(raw, e31, wa, wb); break;
-                    default: pk_decode_lane<0>(raw, e31, wa, wb); break;
-                }
-            }
-        }
-    };
+    Src src;
+    src.init(m, n4, n_batches);
+    src.point(m, u);
     EpiIn ein = epi_prefetch<EPI>(m, u, tid == 0);
     EpiIn ein_next = ein;
-    if constexpr (PK) {
-        pdw = pk::pair_dw(n4);
-        last_off = pk::chunk_off(n4, n_batches - 1, wave_u);
-        s_last = pk::steps(n4, n_batches - 1, wave_u);
-        pp = pair_packed(m, u, pdw);
-        pk_load(0, raw, s_cur);
-    } else {
-        load(0);
-    }
-    if constexpr (LL)
-        xstage_finish_ll<PRO, XC>(poll, a.rms_w, m.n, n4_pad, xl, gr, xs, scratch);
-    else
-        xstage_finish<PRO, XC>(a.x, a.rms_w, m.n, n4_pad, xr, gr, xs, scratch);
+    src.issue(0);
+    if constexpr (Src::kAhead) src.rotate();
+    xst.finish(a.x, a.rms_w, m.n, n4_pad, xs, scratch);
 
     v4f acc_a = {0.f, 0.f, 0.f, 0.f}, acc_b = {0.f, 0.f, 0.f, 0.f};
-    float best_v = -INFINITY;
-    int best_i = 0x7fffffff;
+    ArgmaxCand best;
     int b = 0, parity = 0;
     while (true) {
-        if constexpr (PK) {
-            const bool unit_done = (b + 1 == n_batches);
-            const int u_next = unit_done ? u + ustride : u;
-            const int b_next = unit_done ? 0 : b + 1;
-            if (u_next < n_units) {
-                if (unit_done) {
-                    pp = pair_packed(m, u_next, pdw);
-                    ein_next = epi_prefetch<EPI>(m, u_next, tid == 0);
+        const MvStep s = mv_step(u, b, n_batches, ustride, n_units);
+        auto issue_next = [&]() __attribute__((always_inline)) {  // the next batch, the next unit's first one included
+            if (s.more) {
+                if (s.unit_done) {
+                    src.point(m, s.u_next);
+                    ein_next = epi_prefetch<EPI>(m, s.u_next, tid == 0);
                 }
-                pk_load(b_next, nraw, s_nxt);
+                src.issue(s.b_next);
             }
-            pk_decode();
-        }
+        };
+        if constexpr (Src::kAhead) issue_next();
+        src.deliver();
 #pragma unroll
         for (int k = 0; k < U; k++) {
             const v4f xv = xs4[b * (kBlock * U) + tid + kBlock * k];
-            acc_a = fma4(wa[k], xv, acc_a);
-            acc_b = fma4(wb[k], xv, acc_b);
+            acc_a = fma4(src.wa[k], xv, acc_a);
+            acc_b = fma4(src.wb[k], xv, acc_b);
         }
-        const bool unit_done = (b + 1 == n_batches);
-        const int u_next = unit_done ? u + ustride : u;
-        const int b_next = unit_done ? 0 : b + 1;
-        const bool more = u_next < n_units;
-        if (!PK && more) {
-            if (unit_done) {
-                pair_rows<EPI>(m, u_next, pa, pb);
-                ein_next = epi_prefetch<EPI>(m, u_next, tid == 0);
-            }
-            load(b_next * (kBlock * U));
-        }
-        if (unit_done) {
+        if constexpr (!Src::kAhead) issue_next();
+        if (s.unit_done) {
             const float sa = wave_sum(hsum4(acc_a));
             const float sb = wave_sum(hsum4(acc_b));
             float *pp_ = part + parity * (2 * kWaves);
@@ -501,8 +430,8 @@ __global__ __launch_bounds__(kBlock) void matvec_row_kernel(const MatvecArgs a)
                 pair_epilogue<EPI>(m, u, ta, tb, true, ein);
                 if (EPI == EPI_ARGMAX) {
                     const int ra_ = 2 * u, rb_ = ra_ + 1;
-                    if (ta > best_v || best_i == 0x7fffffff) { best_v = ta; best_i = ra_ + a.row_offset; }
-                    if (rb_ < m.total_rows && tb > best_v) { best_v = tb; best_i = rb_ + a.row_offset; }
+                    argmax_take(best, ta, ra_ + a.row_offset);
+                    if (rb_ < m.total_rows) argmax_take(best, tb, rb_ + a.row_offset);
                 }
             }
             ein = ein_next;
@@ -510,17 +439,14 @@ __global__ __launch_bounds__(kBlock) void matvec_row_kernel(const MatvecArgs a)
             acc_a = v4f{0.f, 0.f, 0.f, 0.f};
             acc_b = v4f{0.f, 0.f, 0.f, 0.f};
         }
-        if (!more) break;
-        if constexpr (PK) {
-            raw = nraw;
-            s_cur = s_nxt;
-        }
-        u = u_next;
-        b = b_next;
+        if (!s.more) break;
+        if constexpr (Src::kAhead) src.rotate();
+        u = s.u_next;
+        b = s.b_next;
     }
     if (EPI == EPI_ARGMAX && tid == 0) {  // units ascend within a block: first index kept
-        a.part_val[blockIdx.x] = best_v;
-        a.part_idx[blockIdx.x] = best_i;
+        a.part_val[blockIdx.x] = best.v;
+        a.part_idx[blockIdx.x] = best.i;
     }
 }
 
@@ -581,57 +507,53 @@ const void *mv_row_fn(bool big_x)
                  : reinterpret_cast<const void *>(&matvec_row_kernel<PRO, EPI, 4, LL, PK>);
 }
 
-// packed weights: ffn13 (rmsnorm + W1 | W3 + SwiGLU), the one decode launch they pay off on
+// The (prologue, epilogue) pairs that exist, and in which further forms: LL = x read as LL words from the landing slot
+// (sharded runs: only the pairs the forward pass launches on a gathered vector; EPI_ARGMAX there is a shard's classifier,
+// the candidate exchange of greedy steps), SCALAR = the generic kernel (it has no fused-argmax epilogue), PACKED = the row
+// kernel on the 29-bit copy: ffn13 (rmsnorm + W1 | W3 + SwiGLU), the one decode launch it pays off on.
+//                    PRO       EPI         LL SCALAR PACKED
+#define L2Z_MV_COMBOS(X)                     \
+    X(PRO_NONE, EPI_STORE,  0, 1, 0)         \
+    X(PRO_NONE, EPI_RESID,  1, 1, 0)         \
+    X(PRO_RMS,  EPI_STORE,  1, 1, 0)         \
+    X(PRO_RMS,  EPI_ROPE,   1, 1, 0)         \
+    X(PRO_RMS,  EPI_SWIGLU, 1, 1, 1)         \
+    X(PRO_RMS,  EPI_ARGMAX, 1, 0, 0)
+#define L2Z_IF_1(...) __VA_ARGS__
+#define L2Z_IF_0(...)
+
 const void *mv_row_pick_packed(int pro, int epi, bool big_x)
 {
-    if (pro == PRO_RMS && epi == EPI_SWIGLU) return mv_row_fn<PRO_RMS, EPI_SWIGLU, false, true>(big_x);
+#define X(P, E, LL, SC, PK) L2Z_IF_##PK(if (pro == P && epi == E) return mv_row_fn<P, E, false, true>(big_x);)
+    L2Z_MV_COMBOS(X)
+#undef X
     return nullptr;
 }
 
-// ll: x is read as LL words from the landing slot (sharded runs).  Only the (prologue, epilogue)
-// pairs the forward pass launches on a gathered vector exist in that form.
 const void *mv_row_pick(int pro, int epi, bool big_x, bool ll)
 {
-#define L2Z_MVR(P, E) if (pro == P && epi == E && !ll) return mv_row_fn<P, E, false>(big_x);
-#define L2Z_MVR_LL(P, E) if (pro == P && epi == E && ll) return mv_row_fn<P, E, true>(big_x);
-    L2Z_MVR(PRO_NONE, EPI_STORE)
-    L2Z_MVR(PRO_NONE, EPI_RESID)
-    L2Z_MVR(PRO_RMS, EPI_STORE)
-    L2Z_MVR(PRO_RMS, EPI_ROPE)
-    L2Z_MVR(PRO_RMS, EPI_SWIGLU)
-    L2Z_MVR(PRO_RMS, EPI_ARGMAX)
-    L2Z_MVR_LL(PRO_NONE, EPI_RESID)
-    L2Z_MVR_LL(PRO_RMS, EPI_STORE)
-    L2Z_MVR_LL(PRO_RMS, EPI_ROPE)
-    L2Z_MVR_LL(PRO_RMS, EPI_SWIGLU)
-    L2Z_MVR_LL(PRO_RMS, EPI_ARGMAX)   // a shard's classifier on a gathered x: the candidate exchange of greedy steps
-#undef L2Z_MVR
-#undef L2Z_MVR_LL
+#define X(P, E, LL, SC, PK)                                           \
+    if (pro == P && epi == E && !ll) return mv_row_fn<P, E, false>(big_x); \
+    L2Z_IF_##LL(if (pro == P && epi == E && ll) return mv_row_fn<P, E, true>(big_x);)
+    L2Z_MV_COMBOS(X)
+#undef X
     return nullptr;
 }
 
 MvLaunch mv_pick_pe(int pro, int epi, int lpr, bool big_x, bool vec, bool ll)
 {
-#define L2Z_MV(P, E)                                                                      \
-    if (pro == P && epi == E && !ll)                                                      \
-        return vec ? mv_pick<P, E, false>(lpr, big_x)                                     \
-                   : MvLaunch{reinterpret_cast<const void *>(&matvec_scalar_kernel<P, E>), 0, 0};
-#define L2Z_MV_LL(P, E) if (pro == P && epi == E && ll && vec) return mv_pick<P, E, true>(lpr, big_x);
-    L2Z_MV(PRO_NONE, EPI_STORE)
-    L2Z_MV(PRO_NONE, EPI_RESID)
-    L2Z_MV(PRO_RMS, EPI_STORE)
-    L2Z_MV(PRO_RMS, EPI_ROPE)
-    L2Z_MV(PRO_RMS, EPI_SWIGLU)
-    L2Z_MV_LL(PRO_NONE, EPI_RESID)
-    L2Z_MV_LL(PRO_RMS, EPI_STORE)
-    L2Z_MV_LL(PRO_RMS, EPI_ROPE)
-    L2Z_MV_LL(PRO_RMS, EPI_SWIGLU)
-#undef L2Z_MV
-#undef L2Z_MV_LL
-    if (pro == PRO_RMS && epi == EPI_ARGMAX && vec && !ll) return mv_pick<PRO_RMS, EPI_ARGMAX, false>(lpr, big_x);
-    if (pro == PRO_RMS && epi == EPI_ARGMAX && vec && ll) return mv_pick<PRO_RMS, EPI_ARGMAX, true>(lpr, big_x);
+#define X(P, E, LL, SC, PK)                                                                \
+    if (pro == P && epi == E && vec && !ll) return mv_pick<P, E, false>(lpr, big_x);       \
+    L2Z_IF_##LL(if (pro == P && epi == E && vec && ll) return mv_pick<P, E, true>(lpr, big_x);) \
+    L2Z_IF_##SC(if (pro == P && epi == E && !vec && !ll)                                   \
+                    return MvLaunch{reinterpret_cast<const void *>(&matvec_scalar_kernel<P, E>), 0, 0};)
+    L2Z_MV_COMBOS(X)
+#undef X
     return {nullptr, 0, 0};
 }
+#undef L2Z_MV_COMBOS
+#undef L2Z_IF_1
+#undef L2Z_IF_0
 
 // Pure streaming read (non-temporal float4 loads, 8 in flight per lane, sum kept out of DCE's
 // reach): the rate the memory system gives a kernel that does nothing else -- the measured
@@ -665,9 +587,6 @@ int matvec_max_grid(int n_cus) { return n_cus * 8; }
 // reference's 3x3 / 2x12 known-answer tests) goes to the generic scalar kernel, which has no fused-argmax epilogue
 bool matvec_vector_width(int n) { return n > 0 && (n % 4) == 0; }
 
-// vector kernels (16-byte aligned operands assumed: every buffer here is a hipMalloc or a row of one)
-bool matvec_ll_supported(int n) { return matvec_vector_width(n); }
-
 hipError_t launch_stream_read(const float *p, size_t n_floats, float *out, int n_cus, hipStream_t st)
 {
     hipLaunchKernelGGL(stream_read_kernel, dim3(n_cus * 8), dim3(256), 0, st, (const v4f *)p, n_floats / 4, out);
@@ -693,31 +612,30 @@ hipError_t launch_matvec(const MatvecArgs &a_in, int pro, int epi, int max_block
     const Tunables &tn = tunables();
     const bool use_row = vec && n4 >= 1024 && (n4 % 64) == 0;
     const bool ll = a.xin.slots != nullptr;
-    if (ll && !vec) return hipErrorNotSupported;  // callers ask matvec_ll_supported() first
-    MvLaunch k = mv_pick_pe(pro, epi, lpr, a.n > 4096, vec, ll);
-    if (use_row) k.fn = mv_row_pick(pro, epi, a.n > 4096, ll);
-    if (a.pk != nullptr) {  // packed weights: the row kernel's packed form or nothing (no quiet f32 fall-back)
-        if (!use_row || ll || !pk::width_ok(a.n)) return hipErrorInvalidValue;
-        k.fn = mv_row_pick_packed(pro, epi, a.n > 4096);
-    }
-    if (k.fn == nullptr) return hipErrorInvalidValue;
+    if (ll && !vec) return hipErrorNotSupported;  // callers ask matvec_vector_width() first
+    // packed weights: the row kernel's packed form or nothing (no quiet f32 fall-back)
+    if (a.pk != nullptr && (!use_row || ll || !pk::width_ok(a.n))) return hipErrorInvalidValue;
+    // the kernel form, with the LDS it carves (x padded to whole batches + scratch) and its units of work
+    MvLaunch k = {nullptr, 0, 0};
     size_t lds;
     int n_units;
-    if (use_row) {
-        const int batch = kBlock * 4;
-        const int n4_pad = ((n4 + batch - 1) / batch) * batch;
-        lds = (size_t)(4 * n4_pad + kScratch + 4 * kWaves) * sizeof(float);
+    const auto padded = [n4](int batch) { return ((n4 + batch - 1) / batch) * batch; };
+    if (use_row) {  // the whole block on one pair
+        k.fn = a.pk != nullptr ? mv_row_pick_packed(pro, epi, a.n > 4096) : mv_row_pick(pro, epi, a.n > 4096, ll);
+        lds = (size_t)(4 * padded(kBlock * kRowU) + kScratch + 4 * kWaves) * sizeof(float);
         n_units = n_pairs;
-    } else if (vec) {
-        const int batch = k.lpr * k.u;
-        const int n4_pad = ((n4 + batch - 1) / batch) * batch;
-        lds = (size_t)(4 * n4_pad + kScratch) * sizeof(float);
+    } else if (vec) {  // 64 / lpr pairs per wave
+        k = mv_pick_pe(pro, epi, lpr, a.n > 4096, true, ll);
+        if (k.fn == nullptr) return hipErrorInvalidValue;
+        lds = (size_t)(4 * padded(k.lpr * k.u) + kScratch) * sizeof(float);
         const int rw = kWave / k.lpr;
         n_units = (n_pairs + rw - 1) / rw;
-    } else {
+    } else {  // generic scalar kernel: a pair per wave
+        k = mv_pick_pe(pro, epi, lpr, a.n > 4096, false, ll);
         lds = (size_t)(((a.n + 3) & ~3) + kScratch) * sizeof(float);
         n_units = n_pairs;
     }
+    if (k.fn == nullptr) return hipErrorInvalidValue;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;

@@ -44,6 +44,30 @@ __device__ __forceinline__ MvLocals mv_locals(const MatvecArgs &a)
     return m;
 }
 
+// Global row g of the concatenated row space -> the segment (0 / 1 / 2: w0 / w1 / w2, out0 / out1 / out2) it lies in
+// and its row within that segment
+struct SegRow {
+    bool past0, past1;  // at or past the end of segment 0 / of segment 1: the segment as the two compares that find it
+    int row;
+    __device__ __forceinline__ int seg() const { return past1 ? 2 : (past0 ? 1 : 0); }
+    // one of three per-segment values, as two selects
+    template <typename T>
+    __device__ __forceinline__ T pick(T v0, T v1, T v2) const
+    {
+        const T v = past0 ? v1 : v0;
+        return past1 ? v2 : v;
+    }
+};
+
+__device__ __forceinline__ SegRow seg_row(const MvLocals &m, int g)
+{
+    SegRow r;
+    r.past0 = g >= m.rows0;
+    r.past1 = g >= m.r01;
+    r.row = g - (r.past1 ? m.r01 : (r.past0 ? m.rows0 : 0));
+    return r;
+}
+
 // the two weight rows of pair p (clamped to the last pair for idle lane groups)
 template <int EPI>
 __device__ __forceinline__ void pair_rows(const MvLocals &m, int p, const float *&pa, const float *&pb)
@@ -55,16 +79,9 @@ __device__ __forceinline__ void pair_rows(const MvLocals &m, int p, const float 
     } else {
         const int ga = 2 * p;
         const int gb = (ga + 1 < m.total_rows) ? ga + 1 : ga;
-        const bool a1 = ga >= m.rows0, a2 = ga >= m.r01;
-        const bool b1 = gb >= m.rows0, b2 = gb >= m.r01;
-        const int row_a = ga - (a2 ? m.r01 : (a1 ? m.rows0 : 0));
-        const int row_b = gb - (b2 ? m.r01 : (b1 ? m.rows0 : 0));
-        const float *wa = a1 ? m.w1 : m.w0;
-        wa = a2 ? m.w2 : wa;
-        const float *wb = b1 ? m.w1 : m.w0;
-        wb = b2 ? m.w2 : wb;
-        pa = wa + (size_t)row_a * (size_t)m.n;
-        pb = wb + (size_t)row_b * (size_t)m.n;
+        const SegRow ra = seg_row(m, ga), rb = seg_row(m, gb);
+        pa = ra.pick(m.w0, m.w1, m.w2) + (size_t)ra.row * (size_t)m.n;
+        pb = rb.pick(m.w0, m.w1, m.w2) + (size_t)rb.row * (size_t)m.n;
     }
 }
 
@@ -95,13 +112,10 @@ __device__ __forceinline__ EpiIn epi_prefetch(const MvLocals &m, int p, bool wri
         e.ra = m.resid[ga];
         if (gb < m.total_rows) e.rb = m.resid[gb];
     } else if (EPI == EPI_ROPE) {
-        const int ga = 2 * p;
-        const bool a1 = ga >= m.rows0, a2 = ga >= m.r01;
-        const int seg_a = a2 ? 2 : (a1 ? 1 : 0);
-        const int row_a = ga - (a2 ? m.r01 : (a1 ? m.rows0 : 0));
-        if (seg_a < m.rope_segs) {
+        const SegRow ra = seg_row(m, 2 * p);
+        if (ra.seg() < m.rope_segs) {
             const int hs = m.head_size;
-            e.cs = m.rope[(size_t)m.pos * (size_t)(hs >> 1) + (size_t)((row_a % hs) >> 1)];
+            e.cs = m.rope[(size_t)m.pos * (size_t)(hs >> 1) + (size_t)((ra.row % hs) >> 1)];
         }
     }
     return e;
@@ -123,19 +137,14 @@ __device__ __forceinline__ void pair_epilogue(const MvLocals &m, int p, float sa
     }
     const int ga = 2 * p, gb = ga + 1;
     const bool valid_b = valid_a && gb < m.total_rows;
-    const bool a1 = ga >= m.rows0, a2 = ga >= m.r01;
-    const bool b1 = gb >= m.rows0, b2 = gb >= m.r01;
-    const int row_a = ga - (a2 ? m.r01 : (a1 ? m.rows0 : 0));
-    const int row_b = gb - (b2 ? m.r01 : (b1 ? m.rows0 : 0));
-    float *oa = a1 ? m.out1 + m.ps1 : m.out0;
-    oa = a2 ? m.out2 + m.ps2 : oa;
-    float *ob = b1 ? m.out1 + m.ps1 : m.out0;
-    ob = b2 ? m.out2 + m.ps2 : ob;
+    const SegRow ra = seg_row(m, ga), rb = seg_row(m, gb);
+    const int row_a = ra.row, row_b = rb.row;
+    float *oa = ra.pick(m.out0, m.out1 + m.ps1, m.out2 + m.ps2);
+    float *ob = rb.pick(m.out0, m.out1 + m.ps1, m.out2 + m.ps2);
     if (EPI == EPI_ROPE) {
         // rows (row_a, row_a+1) of one segment: the pair (i, i+1) of :346-349
         float o0 = sa, o1 = sb;
-        const int seg_a = a2 ? 2 : (a1 ? 1 : 0);
-        if (seg_a < m.rope_segs) {
+        if (ra.seg() < m.rope_segs) {
             const float2 cs = in.cs;     // rope[pos][(row_a % head_size)/2], prefetched
             o0 = sa * cs.x - sb * cs.y;  // :348
             o1 = sa * cs.y + sb * cs.x;  // :349
@@ -144,8 +153,8 @@ __device__ __forceinline__ void pair_epilogue(const MvLocals &m, int p, float sa
             size_t ia = (size_t)row_a, ib = (size_t)row_b;
             if (m.kv_head_stride) {  // head-major cache: [kv head][pos][i]; ps1 / ps2 = pos * head_size
                 const int hs = m.head_size;
-                if (a1) ia = (size_t)(row_a / hs) * m.kv_head_stride + (size_t)(row_a % hs);
-                if (b1) ib = (size_t)(row_b / hs) * m.kv_head_stride + (size_t)(row_b % hs);
+                if (ra.past0) ia = (size_t)(row_a / hs) * m.kv_head_stride + (size_t)(row_a % hs);
+                if (rb.past0) ib = (size_t)(row_b / hs) * m.kv_head_stride + (size_t)(row_b % hs);
             }
             oa[ia] = o0;
             if (valid_b) ob[ib] = o1;

@@ -1,5 +1,6 @@
 // misc_kernels.hip -- argmax + loop hand-over, state set-up, the stand-alone kernels behind the
 // test hooks (rmsnorm, softmax, dot, weighted row sum) and the synthetic-checkpoint generator.
+#include "argmax_rule.h"
 #include "kernel_common.h"
 
 namespace l2z {
@@ -16,17 +17,9 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const ArgmaxArgs a)
     __shared__ int s_idx[16];
     __shared__ int s_next;
     const int tid = threadIdx.x;
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
+    ArgmaxCand c;
     if (a.part_val != nullptr) {  // per-block candidates left by the classifier launch
-        for (int i = tid; i < a.n_part; i += blockDim.x) {
-            const float v = a.part_val[i];
-            const int id = a.part_idx[i];
-            if (id != 0x7fffffff && (bi == 0x7fffffff || v > best || (v == best && id < bi))) {
-                best = v;
-                bi = id;
-            }
-        }
+        for (int i = tid; i < a.n_part; i += blockDim.x) argmax_merge(c, a.part_val[i], a.part_idx[i]);
     } else if ((a.vocab & 3) == 0 && ((unsigned long long)a.logits & 15ull) == 0) {
         // the whole vocabulary in flight at once where it fits (32000 logits = 8 x 16 bytes per thread): the scan of a
         // gathered logits vector -- every sharded token -- took 11 us as 32 dependent rounds of 4-byte loads
@@ -45,50 +38,26 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const ArgmaxArgs a)
                 if (j < n4) {
                     const float e[4] = {r[k].x, r[k].y, r[k].z, r[k].w};
 #pragma unroll
-                    for (int q = 0; q < 4; q++)
-                        if (e[q] > best || bi == 0x7fffffff) {
-                            best = e[q];
-                            bi = 4 * j + q;
-                        }
+                    for (int q = 0; q < 4; q++) argmax_take(c, e[q], 4 * j + q);
                 }
             }
         }
     } else {
-        for (int i = tid; i < a.vocab; i += blockDim.x) {
-            const float v = a.logits[i];
-            if (v > best || bi == 0x7fffffff) {  // strict '>' keeps the lowest index (:720)
-                best = v;
-                bi = i;
-            }
-        }
+        for (int i = tid; i < a.vocab; i += blockDim.x) argmax_take(c, a.logits[i], i);  // strict '>' keeps the lowest index (:720)
     }
-    // wave reduce: larger value wins, equal values -> lower index
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > best || (ov == best && oi < bi))) {
-            best = ov;
-            bi = oi;
-        }
-    }
+    argmax_wave_fold(c);
     if ((tid & 63) == 0) {
-        s_val[tid >> 6] = best;
-        s_idx[tid >> 6] = bi;
+        s_val[tid >> 6] = c.v;
+        s_idx[tid >> 6] = c.i;
     }
     __syncthreads();
+    int bi = c.i;  // what thread 0 hands over below (the block's, then the group's candidate, or kArgmaxFailed)
     if (tid < kWave) {
         // every lane of the first wave forms the block's candidate (<= 16 wave candidates, in wave order)
-        const int nw = blockDim.x >> 6;
-        best = s_val[0];
-        bi = s_idx[0];
-        for (int w = 1; w < nw; w++) {
-            if (s_idx[w] != 0x7fffffff &&
-                (bi == 0x7fffffff || s_val[w] > best || (s_val[w] == best && s_idx[w] < bi))) {
-                best = s_val[w];
-                bi = s_idx[w];
-            }
-        }
+        c.v = s_val[0];
+        c.i = s_idx[0];
+        argmax_fold_waves(c, s_val, s_idx, blockDim.x >> 6);
+        bi = c.i;
         if (a.xchg != nullptr) {
             // The ranks' candidates: lane p sends this rank's pair to rank p -- two LL words {bits, epoch}, each valid by
             // itself -- and waits for rank p's pair in this rank's own slot; then the wave reduces the N pairs by the
@@ -98,17 +67,15 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const ArgmaxArgs a)
             const unsigned e = (unsigned)(x->ctl[kCtlEpoch] + a.xchg_gi);
             const unsigned long long tag = (unsigned long long)e << 32;
             const size_t off = (size_t)(e & 1u) * x->slot_floats;
-            float cv = -INFINITY;
-            int ci = 0x7fffffff;
+            ArgmaxCand rc;  // lane p: rank p's candidate
             bool late = false;
             const bool dead = __hip_atomic_load(x->ctl + kCtlErr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
             if (tid == rank) {
-                cv = best;
-                ci = bi;
+                rc = c;
             } else if (tid < world && !dead) {
                 unsigned long long *dst = (unsigned long long *)(x->peer_arena[tid] + kP2pFlagBytes) + off + 2 * (size_t)rank;
-                __hip_atomic_store(dst, tag | (unsigned long long)__float_as_uint(best), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __hip_atomic_store(dst + 1, tag | (unsigned long long)(unsigned)bi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                __hip_atomic_store(dst, tag | (unsigned long long)__float_as_uint(c.v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                __hip_atomic_store(dst + 1, tag | (unsigned long long)(unsigned)c.i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 const unsigned long long *src = (const unsigned long long *)(x->peer_arena[rank] + kP2pFlagBytes) + off + 2 * (size_t)tid;
                 const long long t0 = wall_clock64();
                 unsigned long long wv, wi;
@@ -124,24 +91,15 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const ArgmaxArgs a)
                     __builtin_amdgcn_s_sleep(1);
                 }
                 if (!late) {
-                    cv = __uint_as_float((unsigned)wv);
-                    ci = (int)(unsigned)wi;
+                    rc.v = __uint_as_float((unsigned)wv);
+                    rc.i = (int)(unsigned)wi;
                 } else {
                     __hip_atomic_store(x->ctl + kCtlErr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     *x->err = 1 + tid;
                 }
             }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(cv, o, 64);
-                const int oi = __shfl_xor(ci, o, 64);
-                if (oi != 0x7fffffff && (ci == 0x7fffffff || ov > cv || (ov == cv && oi < ci))) {
-                    cv = ov;
-                    ci = oi;
-                }
-            }
-            best = cv;
-            bi = ci;
+            argmax_wave_fold(rc);
+            bi = rc.i;
             // a candidate that never arrived (or a group already marked dead): the N pairs are not what the other ranks
             // see, so this rank must not hand a token over as if they were -- mark the step invalid instead of diverging
             if (__any(late ? 1 : 0) || dead) bi = kArgmaxFailed;
@@ -157,7 +115,7 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const ArgmaxArgs a)
     } else if (tid == 0) {
         // (an index outside the vocabulary can only come from a corrupted exchange -- a solo rank's collapsed epochs, a
         // peer that died mid-word: never let it address the embedding table)
-        if (bi == 0x7fffffff || (unsigned)bi >= (unsigned)a.vocab) bi = 0;
+        if (bi == kNoCandidate || (unsigned)bi >= (unsigned)a.vocab) bi = 0;
         if (a.epoch_ctl) a.epoch_ctl[0] += a.epoch_add;  // every launch of the pass has read its epoch long ago
         if (a.argmax_out) *a.argmax_out = bi;
         int next = bi;
@@ -290,16 +248,8 @@ hipError_t launch_rmsnorm(float *o, const float *x, const float *w, int n, hipSt
 {
     const bool vec = (n % 4) == 0 && aligned16(x) && aligned16(w);
     const size_t lds = matvec_lds_bytes(n);
-    if (vec) {
-        hipError_t e = ensure_lds(rmsnorm_kernel<true>, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((rmsnorm_kernel<true>), dim3(1), dim3(kBlock), lds, st, o, x, w, n);
-    } else {
-        hipError_t e = ensure_lds(rmsnorm_kernel<false>, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((rmsnorm_kernel<false>), dim3(1), dim3(kBlock), lds, st, o, x, w, n);
-    }
-    return hipGetLastError();
+    return vec ? launch_lds(rmsnorm_kernel<true>, dim3(1), dim3(kBlock), lds, st, o, x, w, n)
+               : launch_lds(rmsnorm_kernel<false>, dim3(1), dim3(kBlock), lds, st, o, x, w, n);
 }
 
 hipError_t launch_probs(float *probs, const float *logits, int n, float temperature, hipStream_t st)

@@ -1,0 +1,61 @@
+#!/usr/bin/env python3
+"""Per-kernel device-code comparison of one HIP source between two trees, without a GPU: both copies are compiled for
+gfx950 with the Makefile's flags and `--cuda-device-only -S`, the assembly is cut per kernel symbol, assembler comments,
+the __hip_cuid symbol and the function ordinal of local labels are dropped, and the instruction text is compared.  For
+kernels whose text differs, the counts of the arithmetic and memory opcodes a refactor must not move are printed side by side.
+usage: python scripts/kernel_asm_diff.py <parent csrc dir> <head csrc dir> matvec.hip [attention.hip ...]"""
+import collections, os, re, subprocess, sys
+
+FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off"]
+GROUPS = [("v_fma*", r"v_(pk_)?fma"), ("v_mul_f32", r"v_(pk_)?mul_f32"), ("v_add_f32", r"v_(pk_)?add_f32"), ("v_exp*", r"v_exp"),
+          ("v_rcp* / v_div*", r"v_(rcp|div_)"), ("global_load*", r"global_load"), ("global_store* / atomic", r"global_(store|atomic)"),
+          ("ds_*", r"ds_")]
+
+
+def kernels(csrc, src):
+    asm = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", *FLAGS, "--cuda-device-only", "-S", src, "-o", "-"],
+                         cwd=csrc, capture_output=True, text=True, check=True).stdout
+    out, cur = {}, None
+    for line in asm.splitlines():
+        line = line.split(";")[0].rstrip()
+        m = re.match(r"^(_Z\w+):", line)
+        if m:
+            cur = out.setdefault(m.group(1), [])
+            continue
+        if cur is None or not line.strip():
+            continue
+        s = line.strip()
+        if s.startswith(".Lfunc_end"):
+            cur = None
+            continue
+        if "__hip_cuid" in s:
+            continue
+        cur.append(re.sub(r"\.LBB\d+_", ".LBB_", s))
+    return out
+
+
+def counts(text):
+    c = collections.OrderedDict((g, 0) for g, _ in GROUPS)
+    for s in text:
+        op = s.split()[0]
+        for g, pat in GROUPS:
+            if re.match(pat, op):
+                c[g] += 1
+    return c
+
+
+if __name__ == "__main__":
+    parent, head = sys.argv[1], sys.argv[2]
+    for src in sys.argv[3:]:
+        a, b = kernels(parent, src), kernels(head, src)
+        differ = [k for k in a if k in b and a[k] != b[k]]
+        print(f"{src}: kernels parent {len(a)} head {len(b)}; only in parent {sorted(set(a) - set(b))}; only in head {sorted(set(b) - set(a))}; "
+              f"instruction text differs in {len(differ)}")
+        dem = subprocess.run(["c++filt"], input="\n".join(differ), capture_output=True, text=True).stdout.splitlines()
+        for k, d in zip(differ, dem):
+            d = re.sub(r"l2z::\(anonymous namespace\)::", "", d)
+            d = re.sub(r"\(.*", "", d).replace("void ", "")
+            ca, cb = counts(a[k]), counts(b[k])
+            moved = ", ".join(f"{g} {ca[g]} -> {cb[g]} (!)" for g in ca if ca[g] != cb[g])
+            print(f"  {d}: instructions {len([s for s in a[k] if not s.endswith(':')])} -> {len([s for s in b[k] if not s.endswith(':')])}; "
+                  + (moved or "counts equal: " + ", ".join(f"{g} {ca[g]}" for g in ca)))

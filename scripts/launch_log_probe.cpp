@@ -1,4 +1,4 @@
-// launch_log_probe.cpp -- every launch of the batched prompt pass, logged WITHOUT a GPU.
+// launch_log_probe.cpp -- every launch of the batched prompt pass, and of the decode launchers, logged WITHOUT a GPU.
 //
 // csrc/prefill_host.cpp is compiled into this program and driven with a fake runstate; every HIP entry point is a stub:
 // __hipRegisterFunction keeps the kernels' names, hipMalloc hands out fake aligned addresses, hipLaunchKernel prints the
@@ -8,11 +8,19 @@
 // library launch the same kernels the same way if and only if their logs are equal: build this file against each tree
 // (after `make` in its csrc/) and diff (profiles/prefill_launchers_refactor.md).
 //
+// `launch_log_probe decode` drives the decode launchers of matvec.o, attention.o and misc_kernels.o directly instead:
+// launch_matvec over 11 widths x 6 row counts x every (prologue, epilogue) x one and three segments x LL on / off x
+// packed or not x an unaligned x x L2Z_GRID_CAP 0 / 64, with the occupancy query answering 1, 2, 4, 8 in turn;
+// launch_attention / launch_attention_split over head sizes, context lengths, forms and chunk counts; launch_argmax.
+// Every call logs its launch (or none) and its return code (profiles/decode_kernels_refactor.md).  The same program
+// built with -Xarch_host -fsanitize=address,undefined on both lines is the host-side sanitizer run of those launchers.
+//
 //   C=llama2.zig_amd/csrc
 //   hipcc --offload-arch=gfx950 -O1 -std=c++17 -fPIC -ffp-contract=off -w -I$C -Iinclude -c scripts/launch_log_probe.cpp -o /tmp/llp.o
 //   /opt/rocm/llvm/bin/clang++ /tmp/llp.o $C/prefill_gemm.o $C/prefill_skinny.o $C/prefill_panel.o $C/prefill_attention.o \
-//       $C/prefill_ragged.o $C/score.o $C/tunables.o -o scripts/launch_log_probe
+//       $C/prefill_ragged.o $C/score.o $C/tunables.o $C/matvec.o $C/attention.o $C/misc_kernels.o -o scripts/launch_log_probe
 //   scripts/launch_log_probe [L2Z_PF_PANEL L2Z_PF_FUSE_PLANES [L2Z_PF_X3_STREAM_MIN]] > launches.log
+//   scripts/launch_log_probe decode > decode_launches.log
 #include "prefill_host.cpp"
 #include "prefill_common.h"
 #include <cstdarg>
@@ -33,7 +41,9 @@ hipError_t __hipPushCallConfiguration(dim3 g, dim3 b, size_t s, hipStream_t st) 
 hipError_t __hipPopCallConfiguration(dim3 *g, dim3 *b, size_t *s, hipStream_t *st) { *g = g_cfg_grid; *b = g_cfg_block; *s = g_cfg_shmem; *st = g_cfg_stream; return hipSuccess; }
 hipError_t hipGetDevice(int *) { return hipErrorNoDevice; }
 hipError_t hipDeviceGetAttribute(int *, hipDeviceAttribute_t, int) { return hipErrorNoDevice; }
-hipError_t hipFuncSetAttribute(const void *, hipFuncAttribute, int) { return hipSuccess; }
+static int g_occ = 2, g_log_attr = 0;
+hipError_t hipFuncSetAttribute(const void *, hipFuncAttribute, int v) { if (g_log_attr) printf("  max dynamic LDS %d\n", v); return hipSuccess; }
+hipError_t hipOccupancyMaxActiveBlocksPerMultiprocessor(int *n, const void *, int, size_t) { *n = g_occ; return hipSuccess; }
 hipError_t hipGetLastError() { return hipSuccess; }
 hipError_t hipDeviceSynchronize() { return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
@@ -73,13 +83,10 @@ void set_error(const char *f, ...) { va_list ap; va_start(ap, f); printf("  ERRO
 int check_pair(const l2z_config *, const l2z_runstate *, const l2z_weights *) { return 0; }
 int comm_check(const l2z_comm *) { return 0; }
 bool comm_bulk_ok(const l2z_comm *, size_t) { return true; }
-hipError_t launch_matvec(const MatvecArgs &, int, int, int, int, hipStream_t, int *, bool *) { return hipSuccess; }
-hipError_t launch_sum_parts(float *, const float *const *, int, int, hipStream_t) { return hipSuccess; }
 hipError_t launch_bulk_unpack(const BulkArgs &, unsigned long long, int, float *, int, hipStream_t) { return hipSuccess; }
 int comm_bulk_allgather(const l2z_comm *, float *, int, int, float *, int, hipStream_t) { return 0; }
 int comm_bulk_allreduce(const l2z_comm *, float *, int, int, float *, float *, int, hipStream_t) { return 0; }
 int comm_allgather_inplace(const l2z_comm *, float *, size_t, int, int, bool, hipStream_t) { return 0; }
-bool matvec_vector_width(int) { return true; }
 }
 static int pad_cols_(int n) { return n > 768 ? (n + 255) / 256 * 256 : (n + 3) / 4 * 4; }
 
@@ -124,8 +131,71 @@ static void run(const char *name, l2z_config c, int world, int rank, bool scheme
     }
 }
 
+// ---- the decode launchers, driven directly ----
+static void decode_sweep()
+{
+    g_log_attr = 1;
+    float *const base = (float *)0x200000000ull;  // fake, 16-byte aligned; nothing is dereferenced
+    static const int ns[] = {3, 5, 64, 172, 288, 512, 768, 1376, 4096, 11008, 5632}, rows[] = {1, 2, 33, 288, 4096, 32000};
+    for (int cap : {0, 64}) {
+        tunables_set("L2Z_GRID_CAP", cap);
+        for (int n : ns) for (int r : rows) for (int pro = 0; pro <= 1; pro++) for (int epi = 0; epi <= 4; epi++)
+            for (int segs : {1, 3}) for (int ll = 0; ll <= 1; ll++) for (int pk = 0; pk <= 1; pk++) for (int mis = 0; mis <= 1; mis++)
+                for (int occ : {1, 2, 4, 8}) {
+                    if (mis && (ll || pk || occ != 2)) continue;  // the unaligned x: once per shape
+                    g_occ = occ;
+                    MatvecArgs a = {};
+                    a.n = n; a.x = base + mis; a.rms_w = base + (1 << 20); a.resid = base + (2 << 20);
+                    a.w0 = base + (16 << 20); a.out0 = base + (3 << 20); a.rows0 = r;
+                    if (epi == EPI_SWIGLU) a.rows1 = r;
+                    if (segs == 3) {
+                        a.w1 = base + (64 << 20); a.out1 = base + (4 << 20); a.rows1 = epi == EPI_SWIGLU ? r : (r + 1) / 2;
+                        if (epi != EPI_SWIGLU) { a.w2 = base + (96 << 20); a.out2 = base + (5 << 20); a.rows2 = (r + 1) / 2; }
+                    }
+                    a.pos_ptr = (const int *)(base + (6 << 20)); a.rope = (const float2 *)(base + (7 << 20)); a.head_size = 64; a.rope_segs = 2;
+                    a.part_val = base + (8 << 20); a.part_idx = (int *)(base + (9 << 20));
+                    a.push = (const P2pArgs *)(base + (10 << 20)); a.push_ctl = (const int *)(base + (11 << 20));
+                    if (ll) { a.xin.slots = (const unsigned long long *)(base + (12 << 20)); a.xin.ctl = (int *)(base + (11 << 20)); }
+                    if (pk) a.pk = (const uint32_t *)(base + (128 << 20));
+                    int grid = -1; bool pushed = false;
+                    printf("mv cap %d n %d rows %d pro %d epi %d segs %d ll %d pk %d mis %d occ %d\n", cap, n, r, pro, epi, segs, ll, pk, mis, occ);
+                    const hipError_t e = launch_matvec(a, pro, epi, 8, g_cus, nullptr, &grid, &pushed);
+                    printf("  -> %d grid %d pushed %d\n", (int)e, grid, (int)pushed);
+                }
+    }
+    tunables_set("L2Z_GRID_CAP", 0);
+    for (int hs : {11, 48, 64, 128}) for (int S : {256, 512, 1024, 2048}) for (int mis = 0; mis <= 1; mis++) {
+        AttnArgs a = {};
+        a.q = base + mis; a.kcache = base + (16 << 20); a.vcache = base + (64 << 20); a.xb = base + (3 << 20);
+        a.pos_ptr = (const int *)(base + (6 << 20)); a.head_size = hs; a.kv_row = hs; a.kv_head = (size_t)S * hs; a.kv_mul = 1; a.seq_len = S;
+        printf("attn hs %d seq_len %d mis %d: push_supported %d split_supported %d short_pos %d wide_pos %d lds %zu %zu\n", hs, S, mis,
+               (int)attention_push_supported(a), (int)attention_split_supported(a), attention_short_pos(hs, S), attention_split_wide_pos(S),
+               attention_lds_bytes(hs, S, true), attention_lds_bytes(hs, S, false));
+        for (int form = 0; form <= 4; form++) {
+            printf(" form %d\n", form);
+            printf("  -> %d\n", (int)launch_attention(a, 32, nullptr, form));
+        }
+        if (!attention_split_supported(a)) continue;  // the callers' own guard: the split kernel has no scalar form
+        for (int nch : {1, 2, 3, 8}) for (int small = 0; small <= 1; small++) {
+            printf(" split nch %d small %d part_floats %zu\n", nch, small, attention_split_part_floats(32, hs, nch));
+            printf("  -> %d\n", (int)launch_attention_split(a, 32, nch, base + (8 << 20), (int *)(base + (9 << 20)), nullptr, small != 0));
+        }
+    }
+    for (int heads : {1, 6, 12, 32, 64, 300}) printf("split_chunks heads %d -> %d\n", heads, attention_split_chunks(heads, g_cus));
+    for (int vocab : {1, 1000, 32000}) for (int parts : {0, 16}) {
+        ArgmaxArgs a = {};
+        a.logits = base; a.vocab = vocab; a.argmax_out = (int *)(base + (9 << 20));
+        if (parts) { a.part_val = base + (8 << 20); a.part_idx = (int *)(base + (9 << 20)); a.n_part = parts; }
+        printf("argmax vocab %d parts %d\n", vocab, parts);
+        printf("  -> %d\n", (int)launch_argmax(a, nullptr));
+    }
+    for (int n : ns) printf("n %d: vector_width %d lds_bytes %zu\n", n, (int)matvec_vector_width(n), matvec_lds_bytes(n));
+    printf("max_grid %d\n", matvec_max_grid(g_cus));
+}
+
 int main(int argc, char **argv)
 {
+    if (argc > 1 && std::string(argv[1]) == "decode") { decode_sweep(); return 0; }
     if (argc > 2) { tunables_set("L2Z_PF_PANEL", atoi(argv[1])); tunables_set("L2Z_PF_FUSE_PLANES", atoi(argv[2])); }
     if (argc > 3) tunables_set("L2Z_PF_X3_STREAM_MIN", atoi(argv[3]));
     const l2z_config a = {2048, 5632, 2, 16, 16, 4096, 1024}, b = {4096, 11008, 2, 32, 32, 32000, 1024}, c = {288, 768, 2, 6, 6, 4096, 1024},

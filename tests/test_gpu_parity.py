@@ -302,6 +302,65 @@ def test_argmax_tie_rule(gpu, orc):
         assert gpu.argmax(y) == orc.argmax(y)
 
 
+# rows of 1000 logits whose maximum is not unique; the expected index is numpy's FIRST maximum, which is what the
+# reference's strict-'>' loop (main.zig:715-726) returns -- never what a kernel returned
+TIE_ROWS = {
+    "all_equal": {},
+    "first_and_last": {0: 2.0, 999: 2.0},
+    # dim 64 puts 16 classifier rows in a wave and 64 in a block of the fused mat-vec; argmax_kernel's float4 scan has 256
+    # logits per wave, the batched rows' block 64: indices in one lane group, one wave, two waves, several blocks
+    "across_waves_and_blocks": {70: 2.0, 75: 2.0, 90: 2.0, 500: 2.0, 997: 2.0},
+    "all_minus_inf": None,
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", list(TIE_ROWS))
+def test_argmax_tie_rule_on_every_path(gpu, ck, orc, case):
+    """One rule, three kernels: the fused classifier epilogue of the mat-vec with argmax_kernel's merge of its per-block
+    candidates (l2z_transformer + l2z_argmax, and a greedy step), argmax_kernel's own scan of a logits vector, and the
+    batched rows' block_argmax_1024 (l2z_argmax_batch) must all return the first maximum.  The classifier's rows are
+    constants, so equal rows give bit-equal logits: row i = v[i] everywhere, x = rmsnorm of an all-ones embedding
+    row (wo and w2 are zero: the layer leaves x alone).  -inf comes from finite weights: -3e38 * x overflows in
+    every partial sum."""
+    cfg = ck.Config(dim=64, hidden_dim=172, n_layers=1, n_heads=4, n_kv_heads=4, vocab_size=1000, seq_len=16)
+    blob = ck.synth_blob(cfg, False, 21)
+    t = {d.name: d for d in ck.tensor_table(cfg, False)}
+
+    def fill(name, value):
+        blob[t[name].offset:t[name].offset + t[name].count] = value
+
+    fill("token_embedding_table", 1.0); fill("wo", 0.0); fill("w2", 0.0); fill("rms_final_weight", 1.0)
+    v = np.ones(cfg.vocab_size, np.float32)
+    if TIE_ROWS[case] is None:
+        v[:] = -3e38
+    else:
+        for i, val in TIE_ROWS[case].items():
+            v[i] = val
+    fill("wcls", np.repeat(v, cfg.dim))
+    w, s, s2 = gpu.Weights(cfg, blob, False), gpu.RunState(cfg), gpu.RunState(cfg)
+    s.transformer(1, 0, w)
+    lg = s.logits()
+    # the rows are what the case says they are
+    if TIE_ROWS[case] is None:
+        assert np.all(np.isneginf(lg))
+    else:
+        dup = sorted(TIE_ROWS[case]) or list(range(cfg.vocab_size))
+        assert np.all(lg[dup] == lg.max()) and int((lg == lg.max()).sum()) == len(dup)
+    want = int(np.argmax(lg))
+    assert want == orc.argmax(lg) == (min(TIE_ROWS[case]) if TIE_ROWS[case] else 0)
+    assert s.argmax() == want                          # fused classifier candidates -> argmax_kernel's merge
+    s.greedy_begin([])
+    assert set(s.greedy_run(w, 2).tolist()) == {want}  # the same pair inside a greedy step
+    assert gpu.argmax(lg) == want                      # argmax_kernel's scan
+    s2.write_logits(lg)
+    assert s2.argmax() == want                         # ... on a runstate's logits, no candidates
+    s.write_logits(lg)
+    assert gpu.argmax_batch([s, s2]).tolist() == [want, want]  # block_argmax_1024
+    for o in (s, s2, w):
+        o.close()
+
+
 # ---------------------------------------------------------------- synthetic generator
 def test_synth_generator_device_matches_host(gpu, ck, orc):
     cfg = ck.Config(**TOY)
