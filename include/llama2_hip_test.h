@@ -325,6 +325,33 @@ int l2z_verify_tree_time(const int32_t *tokens, const int32_t *parent, int n_nod
                          float temperature, float top_p, const float *coins,
                          const l2z_config *config, l2z_runstate *s, const l2z_weights *w, int iters, double *out_ms);
 
+/* The sampled generation loop on the device: l2z_greedy_run with the argmax replaced by the sampler's draw -- main.zig:987-1042
+ * at any temperature, one replay of a captured step graph per position (forward pass, draw, prompt override, hand-over of
+ * token and position, embedding row of the next token), no host round trip per token.
+ * It follows l2z_greedy_begin (there is no second "begin") and shares the greedy loop's state -- the prompt, the ids, the next
+ * position, the BOS flag -- so a sequence may alternate l2z_greedy_run and l2z_sample_run calls, and temperature and top_p may
+ * change from call to call.
+ * Step i of the call is position next + i.  Below the prompt's length the next token is prompt[pos] (main.zig:999-1000) and
+ * coins[i] is not used; otherwise it is the token l2z_sample_batch draws from that step's logits with (temperature, top_p,
+ * coins[i]) -- the same device code, so the same bits.  temperature == 0 takes the argmax (l2z_argmax's rule) and coins may be
+ * NULL.  coins holds n_steps entries.
+ * The call stops after a BOS and at seq_len, as l2z_greedy_run does: the host looks for BOS once per chunk of 64 steps (the
+ * chunk's steps behind a BOS have run and are discarded), *out_n counts up to and including the BOS, and further calls return
+ * 0 tokens until the next l2z_greedy_begin.  The prompt positions run as one batched pass under exactly l2z_greedy_run's
+ * conditions.  The logits are not modified: l2z_logits_read afterwards returns the last step's.
+ * The scratch (5 x vocab_size floats, one l2z_sample_batch row's) and one coin slot per position are allocated on the
+ * runstate's first call and freed with it; the sampled step's graphs are captured on first use, so a runstate that only ever
+ * runs greedy pays nothing.
+ * A refusal enqueues nothing and changes no state.  L2Z_ERR_INVALID: a NULL argument, n_steps < 0, a sharded runstate,
+ * l2z_greedy_run's refusals (config / runstate / weights that do not belong together), a temperature that is not finite and
+ * >= 0, a top_p outside [0, 1], coins == NULL with temperature > 0, a coins[i] outside [0, 1) (NaN included; all n_steps
+ * entries are checked, at temperature > 0).  L2Z_ERR_NO_DEVICE without a device.
+ * Out of scope: sharded runstates (a shard's logits are its own vocabulary rows only), several sequences per call
+ * (l2z_transformer_batch + l2z_sample_batch), and the CLI, which links the product library. */
+int l2z_sample_run(const l2z_config *config, l2z_runstate *s, const l2z_weights *w, int n_steps,
+                   float temperature, float top_p, const float *coins,
+                   int32_t *out_tokens, int *out_n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,8 @@ def lib():
         L.l2z_verify_tree.argtypes = [i32p, i32p, C.c_int, C.c_int, C.c_float, C.c_float, fp, cfgp, vp, vp, i32p, i32p, ip]
         L.l2z_verify_tree_time.argtypes = [i32p, i32p, C.c_int, C.c_int, C.c_float, C.c_float, fp, cfgp, vp, vp, C.c_int,
                                            C.POINTER(C.c_double)]
+    if hasattr(L, "l2z_sample_run"):
+        L.l2z_sample_run.argtypes = [cfgp, vp, vp, C.c_int, C.c_float, C.c_float, fp, i32p, ip]
     L.l2z_logits_write.argtypes = [vp, fp]
     L.l2z_sample_time.argtypes = [C.c_int, C.POINTER(vp), fp, fp, fp, C.c_int, C.POINTER(C.c_double)]
     L.l2z_greedy_begin.argtypes = [vp, i32p, C.c_int]
@@ -475,6 +477,22 @@ class RunState:
                                   out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)))
         return out[: n.value].copy()
 
+    def sample_run(self, w: Weights, n_steps: int, temperature: float, top_p: float, coins=None) -> np.ndarray:
+        """l2z_sample_run (a preview entry point of the test library: include/llama2_hip_test.h): greedy_run with every
+        generated token DRAWN on the device, after greedy_begin.  coins[i] is the coin of the call's step i (unused at a
+        prompt step); None at temperature 0.  Returns the ids of the steps that ran."""
+        out = np.zeros(max(n_steps, 1), np.int32)
+        n = C.c_int(0)
+        cp = None
+        if coins is not None:
+            coins = np.ascontiguousarray(coins, np.float32).reshape(-1)
+            if coins.size < n_steps:
+                raise ValueError(f"{coins.size} coins for {n_steps} steps")
+            cp = _fp(coins)
+        _chk(lib().l2z_sample_run(C.byref(self.cfg), self.h, w.h, n_steps, C.c_float(temperature), C.c_float(top_p), cp,
+                                  out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)))
+        return out[: n.value].copy()
+
     def profile_forward(self, token: int, pos: int, w: Weights):
         ms = (C.c_double * len(KINDS))()
         cnt = (C.c_int * len(KINDS))()
@@ -755,6 +773,25 @@ def coin_stream(seed: int, n: int) -> np.ndarray:
     out = np.zeros(max(int(n), 1), np.float32)
     host_lib().l2zh_prng_floats(C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _fp(out), int(n))
     return out[: int(n)].copy()
+
+
+def generate_sample(s: RunState, w: Weights, prompt, n_steps: int, temperature: float, top_p: float, coins) -> np.ndarray:
+    """The loop of `llama2 -t temperature -p top_p` on the device: n_steps positions (0 = seq_len) from BOS + prompt in one
+    RunState.sample_run call.  coins[g] is the coin of the g-th generated token (speculate_sample's convention, coin_stream's
+    order); prompt steps get a coin of 0, which is not read.  Returns the `next` of every position from 0 as l2z_greedy_run
+    reports them; a BOS ends the run and is the last id.  ValueError if `coins` is too short for n_steps."""
+    seq_len = s.cfg.seq_len
+    steps = seq_len if n_steps == 0 else max(1, min(int(n_steps), seq_len))
+    prompt = [int(t) for t in prompt]
+    n_gen = max(0, steps - len(prompt))
+    per_step = np.zeros(steps, np.float32)
+    if temperature > 0 and n_gen > 0:
+        coins = np.ascontiguousarray(coins, np.float32).reshape(-1)
+        if coins.size < n_gen:
+            raise ValueError(f"{coins.size} coins for {n_gen} generated positions")
+        per_step[len(prompt):] = coins[:n_gen]
+    s.greedy_begin(prompt)
+    return s.sample_run(w, steps, temperature, top_p, per_step)
 
 
 def speculate_sample(s: RunState, w: Weights, prompt, n_steps: int, k: int, temperature: float, top_p: float, coins,

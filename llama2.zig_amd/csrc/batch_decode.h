@@ -73,6 +73,31 @@ struct SampleArgs {
 inline size_t sample_scratch_floats(int vocab) { return 5 * (((size_t)vocab + 63) / 64 * 64); }
 hipError_t launch_sample_batch(const SampleArgs &a, int n, hipStream_t st);
 
+// l2z_sample_run (sample_step.hip): the last node of a sampled step graph, one block of 1024 threads -- argmax_kernel's
+// hand-over (main.zig:999-1003, :1036) with the argmax replaced by the row body's draw from the runstate's logits.  What
+// changes from step to step or from call to call is read from device memory, never from the arguments, which a captured
+// graph freezes: pos from *pos_ptr, temperature and top_p from *params, the coin from coins[pos].
+struct SampleStepParams {
+    float temperature, top_p;
+};
+struct SampleStepArgs {
+    const float *logits;             // read only: the step's logits stay as the classifier left them
+    int vocab;
+    const SampleStepParams *params;
+    const float *coins;              // [seq_len], indexed by position; not read at a prompt position
+    int seq_len;                     // a position outside [0, seq_len) is left alone: nothing is read or written
+    float *scratch;                  // sample_scratch_floats(vocab) floats
+    int *token_ptr;                  // out: the next step's token
+    int *pos_ptr;                    // in/out
+    const int *prompt;               // forced tokens (n_prompt)
+    const int *n_prompt_ptr;
+    int *out_tokens;                 // out_tokens[pos] = next
+    const float *tok_emb;            // (vocab, dim): next step's embedding row -> x
+    float *x;
+    int dim;
+};
+hipError_t launch_sample_step(const SampleStepArgs &a, hipStream_t st);
+
 // The verify family (verify.hip, verify_batch.hip, verify_tree.hip; host side: verify_host.cpp): the rows of a step are
 // guessed positions, attention is multi-query, causal and split over positions.  A block owns (head, segment), the
 // segments are kVerifySeg ABSOLUTE positions each -- segment s = positions [s * kVerifySeg, (s + 1) * kVerifySeg) whatever

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <mutex>
 
+#include "batch_host.h"
 #include "l2z_state.h"
 
 namespace l2z {
@@ -47,7 +48,7 @@ int check_pair(const l2z_config *config, const l2z_runstate *s, const l2z_weight
 }
 
 // The forward pass (main.zig:285-430) as 5 launches per layer + classifier
-// (+ argmax/hand-over).  Token and pos are read from device memory.
+// (+ the step's last node: argmax or draw, and the hand-over).  Token and pos are read from device memory.
 // `only_stage` >= 0 runs just the launches between two gather points (and no collective):
 // the single-process multi-rank emulation (l2z_emu_transformer) interleaves the ranks
 // stage by stage and performs the gathers itself.  Stages: 4 per layer (after attention,
@@ -65,9 +66,10 @@ int check_pair(const l2z_config *config, const l2z_runstate *s, const l2z_weight
 // of 4; stages between collectives: [qkv, attention, wo], [w1|w3, w2] per layer, then the classifier.  The sum over a row
 // is split differently than in the unsharded pass: logits agree at the tolerance of the parity tests, not bit for bit
 // (ranks agree with each other exactly: same partials, same order).
-int enqueue_forward(l2z_runstate *s, const l2z_weights *w, bool with_step, Prof *prof,
+int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *prof,
                     int only_stage, int variant, int only_kind)
 {
+    const bool with_step = step != STEP_NONE;
     const bool split = variant == ATTN_SPLIT || variant == ATTN_SPLIT_S;
     const l2z_config &c = s->cfg;
     const Shard &sh = s->sh;
@@ -92,7 +94,7 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, bool with_step, Prof 
     // greedy step of a shard group on the peer-write transport: the classifier leaves this rank's argmax candidates and
     // the hand-over launch exchanges one pair per rank instead of the logits gather + 32000-logit scan (main.zig:715-726
     // over the whole vocabulary all the same: larger value, then lower index)
-    const bool xchg = with_step && p2p && s->xchg_steps;
+    const bool xchg = step == STEP_GREEDY && p2p && s->xchg_steps;
     const int n_g = s->n_gathers;
     int gi = 0;           // gathers issued so far in this pass
     bool pushed = false;  // the launch just made pushed its outputs itself
@@ -292,7 +294,7 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, bool with_step, Prof 
     } else {
         L2Z_TRY(gather(s->logits, sh.v_loc));
     }
-    if (with_step && want() && kind(KIND_ARGMAX)) {
+    if (step == STEP_GREEDY && want() && kind(KIND_ARGMAX)) {
         ArgmaxArgs a = {};
         a.logits = s->logits; a.vocab = c.vocab_size; a.token_ptr = s->d_token;
         if (s->n_part > 0) { a.part_val = s->d_part_val; a.part_idx = s->d_part_idx; a.n_part = s->n_part; }
@@ -307,6 +309,16 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, bool with_step, Prof 
         }
         L2Z_LAUNCH(KIND_ARGMAX, launch_argmax(a, st));
     }
+    if (step == STEP_SAMPLE && want() && kind(KIND_ARGMAX)) {   // the draw (main.zig:1005-1010) + the same hand-over
+        L2Z_CHECK(sh.world == 1 && s->d_smp_ctl != nullptr && s->d_smp_scratch != nullptr, L2Z_ERR_STATE,
+                  "sampled step on a runstate l2z_sample_run has not prepared");
+        SampleStepArgs a = {};
+        a.logits = s->logits; a.vocab = c.vocab_size; a.seq_len = c.seq_len;
+        a.params = (const SampleStepParams *)s->d_smp_ctl; a.coins = s->d_smp_ctl + 2; a.scratch = s->d_smp_scratch;
+        a.token_ptr = s->d_token; a.pos_ptr = s->d_pos; a.prompt = s->d_prompt; a.n_prompt_ptr = s->d_n_prompt;
+        a.out_tokens = s->d_out_tokens; a.tok_emb = w->tok_emb; a.x = s->x; a.dim = c.dim;
+        L2Z_LAUNCH(KIND_ARGMAX, launch_sample_step(a, st));
+    }
     return L2Z_OK;
 }
 
@@ -316,12 +328,12 @@ int attn_variant(const l2z_runstate *s, int pos)
     return pos < s->attn_short_pos ? ATTN_SHORT : ATTN_HEAD;
 }
 
-int build_graph(l2z_runstate *s, const l2z_weights *w, bool with_step, int variant,
+int build_graph(l2z_runstate *s, const l2z_weights *w, StepKind step, int variant,
                 hipGraphExec_t *out)
 {
     hipGraph_t graph = nullptr;
     L2Z_HIP(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
-    int rc = enqueue_forward(s, w, with_step, nullptr, -1, variant);
+    int rc = enqueue_forward(s, w, step, nullptr, -1, variant);
     hipError_t e = hipStreamEndCapture(s->stream, &graph);
     if (rc != L2Z_OK) {
         if (graph) (void)hipGraphDestroy(graph);
@@ -339,13 +351,20 @@ void drop_graphs(l2z_runstate *s)
     for (int v = 0; v < ATTN_VARIANTS; v++) {
         if (s->g_forward[v]) { (void)hipGraphExecDestroy(s->g_forward[v]); s->g_forward[v] = nullptr; }
         if (s->g_step[v]) { (void)hipGraphExecDestroy(s->g_step[v]); s->g_step[v] = nullptr; }
+        if (s->g_sample[v]) { (void)hipGraphExecDestroy(s->g_sample[v]); s->g_sample[v] = nullptr; }
     }
     s->graph_w_uid = 0;
 }
 
-// the captured graph of one attention variant (with or without the loop hand-over); a model only ever pays for the
-// variants its positions take (attn_variant)
-int ensure_graph(l2z_runstate *s, const l2z_weights *w, int variant, bool with_step)
+hipGraphExec_t *graph_slot(l2z_runstate *s, StepKind step, int variant)
+{
+    return step == STEP_SAMPLE ? &s->g_sample[variant] : step == STEP_GREEDY ? &s->g_step[variant] : &s->g_forward[variant];
+}
+
+// the captured graph of one attention variant (without a last node, with the greedy or with the sampled one); a model only
+// ever pays for the variants its positions take (attn_variant), and for the sampled step's graphs only once it samples in
+// the loop: those are captured one by one, each on the first sampled step of its variant
+int ensure_graph(l2z_runstate *s, const l2z_weights *w, int variant, StepKind step)
 {
     if (!s->use_graphs) return L2Z_OK;
     int rc = L2Z_OK;
@@ -361,13 +380,13 @@ int ensure_graph(l2z_runstate *s, const l2z_weights *w, int variant, bool with_s
                 if (p >= 0 && p < s->cfg.seq_len) reach[attn_variant(s, p)] = true;
         for (int v = 0; v < ATTN_VARIANTS && rc == L2Z_OK; v++) {
             if (!reach[v]) continue;
-            rc = build_graph(s, w, false, v, &s->g_forward[v]);
-            if (rc == L2Z_OK) rc = build_graph(s, w, true, v, &s->g_step[v]);
+            rc = build_graph(s, w, STEP_NONE, v, &s->g_forward[v]);
+            if (rc == L2Z_OK) rc = build_graph(s, w, STEP_GREEDY, v, &s->g_step[v]);
         }
     }
-    hipGraphExec_t *slot = with_step ? &s->g_step[variant] : &s->g_forward[variant];
+    hipGraphExec_t *slot = graph_slot(s, step, variant);
     if (rc == L2Z_OK && *slot) return L2Z_OK;
-    if (rc != L2Z_OK || build_graph(s, w, with_step, variant, slot) != L2Z_OK) {
+    if (rc != L2Z_OK || build_graph(s, w, step, variant, slot) != L2Z_OK) {
         // capture is an optimisation, not a requirement: run the same launches eagerly
         fprintf(stderr, "llama2_hip: hipGraph capture failed (%s); launching eagerly\n", l2z_last_error());
         drop_graphs(s);
@@ -378,21 +397,22 @@ int ensure_graph(l2z_runstate *s, const l2z_weights *w, int variant, bool with_s
 }
 
 // one forward pass at position `pos` (the host mirrors the device-side pos)
-int run_forward(l2z_runstate *s, const l2z_weights *w, bool with_step, int pos)
+int run_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, int pos)
 {
+    const bool with_step = step != STEP_NONE;
     const int variant = attn_variant(s, pos);
     L2Z_CHECK(s->sh.world == 1 || (s->comm && (s->comm->nccl || s->comm->p2p)), L2Z_ERR_STATE,
               "sharded runstate without a transport: connect the group (RCCL id or "
               "l2z_comm_p2p_export/_connect), or drive emulated ranks with l2z_emu_transformer");
     L2Z_TRY(comm_check(s->comm));
-    L2Z_TRY(ensure_graph(s, w, variant, with_step));
-    s->logits_partial = with_step && s->xchg_steps && s->d_push != nullptr && s->sh.world > 1;  // enqueue_forward's `xchg`
+    L2Z_TRY(ensure_graph(s, w, variant, step));
+    s->logits_partial = step == STEP_GREEDY && s->xchg_steps && s->d_push != nullptr && s->sh.world > 1;  // enqueue_forward's `xchg`
     if (s->use_graphs) {
         s->n_part = with_step ? s->n_part_step : s->n_part_fwd;
-        L2Z_HIP(hipGraphLaunch(with_step ? s->g_step[variant] : s->g_forward[variant], s->stream));
+        L2Z_HIP(hipGraphLaunch(*graph_slot(s, step, variant), s->stream));
         return L2Z_OK;
     }
-    return enqueue_forward(s, w, with_step, nullptr, -1, variant);
+    return enqueue_forward(s, w, step, nullptr, -1, variant);
 }
 
 // After a greedy step that ended in the candidate exchange `logits` holds this rank's rows only: gather the rest, as a
@@ -422,7 +442,7 @@ extern "C" int l2z_transformer(int token, int pos, const l2z_config *config, l2z
     L2Z_HIP(hipSetDevice(s->device));
     L2Z_HIP(launch_set_state(token, pos, s->d_token, s->d_pos, w->tok_emb, s->x, config->dim,
                              s->stream));
-    L2Z_TRY(run_forward(s, w, false, pos));
+    L2Z_TRY(run_forward(s, w, STEP_NONE, pos));
     s->host_pos = pos + 1;
     return L2Z_OK;
 }
@@ -493,11 +513,15 @@ extern "C" int l2z_greedy_begin(l2z_runstate *s, const int32_t *prompt, int n_pr
     return L2Z_OK;
 }
 
-extern "C" int l2z_greedy_run(const l2z_config *config, l2z_runstate *s, const l2z_weights *w,
-                              int n_steps, int32_t *out_tokens, int *out_n)
+namespace l2z {
+namespace {
+
+// The loop of main.zig:987-1042 on the device, shared by l2z_greedy_run and l2z_sample_run: up to n_steps positions from
+// host_pos, each one replay of the step graph whose last node is `step`'s (the argmax, or the draw), the ids copied back
+// and searched for BOS once per chunk.  The caller has made its checks.
+int step_loop(const l2z_config *config, l2z_runstate *s, const l2z_weights *w, int n_steps, StepKind step,
+              int32_t *out_tokens, int *out_n)
 {
-    L2Z_TRY(check_pair(config, s, w));
-    L2Z_CHECK(out_tokens && out_n && n_steps >= 0, L2Z_ERR_INVALID, "l2z_greedy_run: bad arguments");
     *out_n = 0;
     L2Z_HIP(hipSetDevice(s->device));
     if (s->done) return L2Z_OK;
@@ -534,12 +558,12 @@ extern "C" int l2z_greedy_run(const l2z_config *config, l2z_runstate *s, const l
     }
     while (remaining > 0 && !s->done) {
         const int n = remaining < kChunk ? remaining : kChunk;
-        for (int i = 0; i < n; i++) L2Z_TRY(run_forward(s, w, true, s->host_pos + i));
+        for (int i = 0; i < n; i++) L2Z_TRY(run_forward(s, w, step, s->host_pos + i));
         L2Z_HIP(hipMemcpyAsync(out_tokens + produced, s->d_out_tokens + s->host_pos,
                                (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s->stream));
         L2Z_HIP(hipStreamSynchronize(s->stream));
         L2Z_TRY(comm_check(s->comm));
-            int got = n;
+        int got = n;
         for (int i = 0; i < n; i++) {
             if (out_tokens[produced + i] == 1) {  // BOS ends the sequence
                 got = i + 1;
@@ -553,6 +577,63 @@ extern "C" int l2z_greedy_run(const l2z_config *config, l2z_runstate *s, const l
     }
     *out_n = produced;
     return L2Z_OK;
+}
+
+}  // namespace
+}  // namespace l2z
+
+extern "C" int l2z_greedy_run(const l2z_config *config, l2z_runstate *s, const l2z_weights *w,
+                              int n_steps, int32_t *out_tokens, int *out_n)
+{
+    L2Z_TRY(check_pair(config, s, w));
+    L2Z_CHECK(out_tokens && out_n && n_steps >= 0, L2Z_ERR_INVALID, "l2z_greedy_run: bad arguments");
+    return step_loop(config, s, w, n_steps, STEP_GREEDY, out_tokens, out_n);
+}
+
+// l2z_greedy_run with the argmax replaced by the sampler's draw (include/llama2_hip_test.h)
+extern "C" int l2z_sample_run(const l2z_config *config, l2z_runstate *s, const l2z_weights *w, int n_steps,
+                              float temperature, float top_p, const float *coins, int32_t *out_tokens, int *out_n)
+{
+    L2Z_TRY(no_device_check());
+    L2Z_CHECK(out_tokens && out_n && n_steps >= 0, L2Z_ERR_INVALID, "l2z_sample_run: bad arguments");
+    L2Z_TRY(check_pair(config, s, w));
+    L2Z_CHECK(s->comm == nullptr && s->sh.world == 1, L2Z_ERR_INVALID,
+              "l2z_sample_run: the runstate is a shard (a shard holds its own rows of the logits only)");
+    // l2z_sample_batch's rules
+    L2Z_CHECK(std::isfinite(temperature) && temperature >= 0.0f, L2Z_ERR_INVALID, "l2z_sample_run: temperature = %g (finite, >= 0)",
+              (double)temperature);
+    L2Z_CHECK(top_p >= 0.0f && top_p <= 1.0f, L2Z_ERR_INVALID, "l2z_sample_run: top_p = %g outside [0, 1]", (double)top_p);
+    L2Z_CHECK(temperature == 0.0f || coins != nullptr, L2Z_ERR_INVALID, "l2z_sample_run: coins is NULL at temperature %g",
+              (double)temperature);
+    if (temperature > 0.0f)
+        for (int i = 0; i < n_steps; i++)
+            L2Z_CHECK(coins[i] >= 0.0f && coins[i] < 1.0f, L2Z_ERR_INVALID, "l2z_sample_run: coins[%d] = %g outside [0, 1)", i,
+                      (double)coins[i]);
+    *out_n = 0;
+    const int left = config->seq_len - s->host_pos;
+    const int n = n_steps < left ? n_steps : left;
+    if (s->done || n <= 0) return L2Z_OK;
+    L2Z_HIP(hipSetDevice(s->device));
+    const size_t ctl_bytes = (2 + (size_t)config->seq_len) * sizeof(float);
+    if (s->d_smp_ctl == nullptr) {
+        L2Z_HIP(hipMalloc((void **)&s->d_smp_ctl, ctl_bytes));
+        L2Z_HIP(hipMemset(s->d_smp_ctl, 0, ctl_bytes));
+    }
+    if (s->h_smp_ctl == nullptr) L2Z_HIP(hipHostMalloc((void **)&s->h_smp_ctl, ctl_bytes, hipHostMallocDefault));
+    if (s->d_smp_scratch == nullptr)
+        L2Z_HIP(hipMalloc((void **)&s->d_smp_scratch, sample_scratch_floats(config->vocab_size) * sizeof(float)));
+    // this call's temperature, top_p and coins (at the positions its steps take) -> the device, behind everything queued.
+    // The pinned twin is free to rewrite: only these copies read it, and no call returns with them in flight (at least one
+    // step is left, so step_loop syncs the stream behind them -- after the prompt's pass or after the first chunk)
+    s->h_smp_ctl[0] = temperature;
+    s->h_smp_ctl[1] = top_p;
+    L2Z_HIP(hipMemcpyAsync(s->d_smp_ctl, s->h_smp_ctl, 2 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    if (temperature > 0.0f) {
+        float *h = s->h_smp_ctl + 2 + s->host_pos;
+        memcpy(h, coins, (size_t)n * sizeof(float));
+        L2Z_HIP(hipMemcpyAsync(s->d_smp_ctl + 2 + s->host_pos, h, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    }
+    return step_loop(config, s, w, n_steps, STEP_SAMPLE, out_tokens, out_n);
 }
 
 // ---------------------------------------------------------------------------
@@ -571,7 +652,7 @@ extern "C" int l2z_profile_forward(int token, int pos, const l2z_config *config,
     L2Z_HIP(launch_set_state(token, pos, s->d_token, s->d_pos, w->tok_emb, s->x, config->dim,
                              s->stream));
     Prof prof;
-    int rc = enqueue_forward(s, w, true, &prof, -1, attn_variant(s, pos));
+    int rc = enqueue_forward(s, w, STEP_GREEDY, &prof, -1, attn_variant(s, pos));
     hipError_t e = hipStreamSynchronize(s->stream);
     for (int k = 0; k < n_kinds; k++) { ms_by_kind[k] = 0.0; launches_by_kind[k] = 0; }
     if (rc == L2Z_OK && e == hipSuccess) {
@@ -612,9 +693,9 @@ extern "C" int l2z_time_kind(int kind, int pos, const l2z_config *config, l2z_ru
     L2Z_HIP(hipEventCreate(&e0));
     L2Z_HIP(hipEventCreate(&e1));
     const int per_pass = kind == KIND_CLS || kind == KIND_ARGMAX ? 1 : config->n_layers;
-    int rc = enqueue_forward(s, w, true, nullptr, -1, attn_variant(s, pos), kind);  // warm-up pass
+    int rc = enqueue_forward(s, w, STEP_GREEDY, nullptr, -1, attn_variant(s, pos), kind);  // warm-up pass
     hipError_t e = hipEventRecord(e0, s->stream);
-    for (int r = 0; r < reps && rc == L2Z_OK; r++) rc = enqueue_forward(s, w, true, nullptr, -1, attn_variant(s, pos), kind);
+    for (int r = 0; r < reps && rc == L2Z_OK; r++) rc = enqueue_forward(s, w, STEP_GREEDY, nullptr, -1, attn_variant(s, pos), kind);
     if (e == hipSuccess) e = hipEventRecord(e1, s->stream);
     if (e == hipSuccess) e = hipEventSynchronize(e1);
     float ms = 0.0f;
@@ -654,7 +735,7 @@ extern "C" int l2z_emu_transformer(int n_ranks, l2z_runstate *const *ss,
     const int n_stages = (sb ? 2 : 4) * c.n_layers + 1;
     for (int stage = 0; stage < n_stages; stage++) {
         for (int r = 0; r < n_ranks; r++)
-            L2Z_TRY(enqueue_forward(ss[r], ws[r], false, nullptr, stage, attn_variant(ss[r], pos)));
+            L2Z_TRY(enqueue_forward(ss[r], ws[r], STEP_NONE, nullptr, stage, attn_variant(ss[r], pos)));
         for (int r = 0; r < n_ranks; r++) L2Z_HIP(hipStreamSynchronize(ss[r]->stream));
         if (sb && stage < n_stages - 1) {
             // scheme B: the all-reduce -- every rank's x = the partials summed in rank order

@@ -120,6 +120,10 @@ struct l2z_runstate {
     int sc_slab_force = 0;           // l2z_score_slab_set (tests): columns per slab, 0: by the workspace budget
     float *d_probs = nullptr;     // l2z_probs_read: softmax(logits / temperature), allocated on first use
     float *h_stage = nullptr;     // ... and its pinned host landing buffer
+    // l2z_sample_run (allocated on the first call, a runstate that never samples in the loop holds none of it): what the
+    // sampled step's last node reads -- {temperature, top_p}, then one coin per position (2 + seq_len floats) --, its pinned
+    // host twin, and the row body's scratch (sample_scratch_floats(vocab))
+    float *d_smp_ctl = nullptr, *h_smp_ctl = nullptr, *d_smp_scratch = nullptr;
     float *d_part_val = nullptr;  // classifier launch's per-block argmax candidates
     int *d_part_idx = nullptr;
     int n_part = 0;               // 0: argmax scans the logits instead
@@ -134,6 +138,7 @@ struct l2z_runstate {
     // is commonly handed to the next one)
     uint64_t graph_w_uid = 0;
     hipGraphExec_t g_forward[4] = {nullptr, nullptr, nullptr, nullptr}, g_step[4] = {nullptr, nullptr, nullptr, nullptr};  // [attention variant]
+    hipGraphExec_t g_sample[4] = {nullptr, nullptr, nullptr, nullptr};  // the sampled step's, each captured on its first sampled step (forward.cpp ensure_graph)
     bool use_graphs = true;
     int host_pos = 0;   // next position the greedy loop will run
     bool done = false;  // greedy loop saw BOS
@@ -171,10 +176,14 @@ int check_pair(const l2z_config *config, const l2z_runstate *s, const l2z_weight
 // 0 short context (256-thread speculative form), 1 one block per head as the shape picks, 2 split with 256
 // threads per block, 3 split with 1024
 enum { ATTN_SHORT = 0, ATTN_HEAD = 1, ATTN_SPLIT_S = 2, ATTN_SPLIT = 3, ATTN_VARIANTS = 4 };
-int enqueue_forward(l2z_runstate *s, const l2z_weights *w, bool with_step, Prof *prof, int only_stage,
+// what follows the classifier in a pass: nothing (the logits are the result), the greedy loop's argmax + hand-over
+// (argmax_kernel), or the sampled loop's draw + hand-over (sample_step_kernel; unsharded runstates, after l2z_sample_run
+// has allocated what it reads)
+enum StepKind { STEP_NONE = 0, STEP_GREEDY = 1, STEP_SAMPLE = 2 };
+int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *prof, int only_stage,
                     int variant, int only_kind = -1);
 int attn_variant(const l2z_runstate *s, int pos);
-int run_forward(l2z_runstate *s, const l2z_weights *w, bool with_step, int pos);
+int run_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, int pos);
 int ensure_logits(l2z_runstate *s);  // gathers the logits if the last pass left only this rank's rows (see xchg_steps)
 void drop_graphs(l2z_runstate *s);
 

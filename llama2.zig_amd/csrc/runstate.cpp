@@ -169,15 +169,17 @@ extern "C" void l2z_runstate_free(l2z_runstate *s)
     for (int v = 0; v < l2z::ATTN_VARIANTS; v++) {
         if (s->g_forward[v]) (void)hipGraphExecDestroy(s->g_forward[v]);
         if (s->g_step[v]) (void)hipGraphExecDestroy(s->g_step[v]);
+        if (s->g_sample[v]) (void)hipGraphExecDestroy(s->g_sample[v]);
     }
     void *ptrs[] = {s->x, s->xb, s->hb, s->q, s->logits, s->key_cache, s->value_cache, s->rope,
                     s->d_token, s->d_pos, s->d_prompt, s->d_n_prompt, s->d_out_tokens, s->d_argmax,
                     s->d_probs, s->d_part_val, s->d_part_idx, s->d_attn_part, s->d_attn_cnt, s->pf_x, s->pf_xn, s->pf_q,
                     s->pf_att, s->pf_h1, s->pf_stage, s->pf_part, s->pf_tokens, s->d_push, s->pf_sk.part, s->pf_sk.cnt, s->pf_sk.x3, s->pf_sk.x3b, s->part, s->sc_ws, s->sc_seq,
-                    s->rg_k, s->rg_v, s->rg_tab};
+                    s->rg_k, s->rg_v, s->rg_tab, s->d_smp_ctl, s->d_smp_scratch};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (s->h_stage) (void)hipHostFree(s->h_stage);
+    if (s->h_smp_ctl) (void)hipHostFree(s->h_smp_ctl);
     l2z::batch_free(s);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
