@@ -81,12 +81,52 @@ struct GemmArgs {
 };
 
 
-// where feature f of position pos lives in a cache whose flat form has rows of ld floats
+// where feature f of position pos lives in a cache whose flat form has rows of ld floats (kv_head_stride != 0: head-major,
+// see GemmArgs)
+__device__ __forceinline__ size_t kv_index(size_t kv_head_stride, int head_size, int ld, int pos, int f)
+{
+    return kv_head_stride ? (size_t)(f / head_size) * kv_head_stride + (size_t)pos * (size_t)head_size + (size_t)(f % head_size)
+                          : (size_t)pos * (size_t)ld + (size_t)f;
+}
 __device__ __forceinline__ size_t kv_index(const GemmArgs &a, int ld, int pos, int f)
 {
-    return a.kv_head_stride ? (size_t)(f / a.head_size) * a.kv_head_stride + (size_t)pos * (size_t)a.head_size +
-                                  (size_t)(f % a.head_size)
-                            : (size_t)pos * (size_t)ld + (size_t)f;
+    return kv_index(a.kv_head_stride, a.head_size, ld, pos, f);
+}
+
+// The q | k | v segment of feature f of a launch whose features are q's a.nq, then k's a.nkv, then v's a.nkv (A: GemmArgs, or
+// the panel kernel's arguments): which of the three, the segment's first feature in the launch, its feature count, and one of
+// three members of `a` by segment.  Everything is read from `a` inside the arm that needs it, as the kernels wrote it out
+// before: the compiler then sees the compares and the loads it saw there (a form that took nq and nkv by value cost the
+// q | k | v kernels other epilogue code: fewer, shared stores and loads).
+template <class A>
+struct QkvSeg {
+    const A &a;
+    int seg;   // 0 q, 1 k, 2 v
+    __device__ __forceinline__ int first() const { return seg == 2 ? a.nq + a.nkv : seg == 1 ? a.nq : 0; }
+    __device__ __forceinline__ int rows() const { return seg == 0 ? a.nq : a.nkv; }
+    template <typename T>
+    __device__ __forceinline__ T pick(T A::*q, T A::*k, T A::*v) const { return seg == 0 ? a.*q : seg == 1 ? a.*k : a.*v; }
+};
+template <class A>
+__device__ __forceinline__ QkvSeg<A> qkv_seg(const A &a, int f)
+{
+    return {a, f >= a.nq + a.nkv ? 2 : f >= a.nq ? 1 : 0};
+}
+
+// MFMA 32x32 accumulators: the row (token) that register r of lane `lane` holds in a 32 x 32 tile whose first row is row0; its
+// column is lane & 31
+__device__ __forceinline__ int mfma32_row(int row0, int r, int lane) { return row0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
+
+// Block -> tile of a 1-D grid of a.ntx feature tiles x a.nty token tiles (a.nty > 0): ids are dispatched in order and
+// round-robin over the 8 XCDs, so consecutive groups of 8 nty ids take 8 feature tiles x all nty token tiles with
+// id % 8 = feature tile % 8: the nty blocks that read the same W tile run on ONE XCD (one L2 fill) and at the same time.
+// false: a padding block of the last group.
+__device__ __forceinline__ bool block_tile_1d(const GemmArgs &a, int &bx, int &by)
+{
+    const int group = 8 * a.nty, g = bx / group, local = bx - g * group;
+    by = local >> 3;
+    bx = g * 8 + (local & 7);
+    return bx < a.ntx;
 }
 
 // One direct-to-LDS load: 16 bytes per lane from `g` (per lane) to lds + 16 * lane (`lds` wave-uniform).

@@ -71,9 +71,7 @@ int x3_stream_sk(long long n_whole, int P, int K)
     }
     return best;
 }
-}  // namespace l2z
 
-namespace l2z {
 namespace {
 
 // compute units of the current device (tile choice: does the larger tile still give every CU a block?)
@@ -93,7 +91,7 @@ static int g_cus_hint()
 
 // Output tile of the direct-to-LDS kernel for a [P, N] product.  All forms split and order k the same
 // way (two k-groups per 64-k stage, MFMA pairing (8s+t, 8s+4+t)), so the choice never changes a bit of
-// the result (tests: sharded == unsharded, L2Z_PF_TILE forms equal) -- it is purely a question of
+// the result (tests: sharded == unsharded) -- it is purely a question of
 // filling 256 CUs:  cost = tiles in sequence on the busiest CU x tile area / efficiency of the form,
 // efficiencies from interleaved A/B runs on the 7B and 110M shapes (larger tiles bring
 // fewer bytes per flop into the CU).  The 7B shape at 512 tokens keeps 128 x 64; 65..128-token prompts,
@@ -147,10 +145,11 @@ __device__ __forceinline__ void epi_values(const GemmArgs &a, float (&v)[NV], co
     if constexpr (EPI == G_QKV) {
         // a wave's 32 columns lie in ONE of the three ranges (launchers: nq and nkv are multiples of 32; a block's tile may
         // lie across two of them -- the stream form's 192-feature tiles)
-        seg = nb >= a.nq + a.nkv ? 2 : nb >= a.nq ? 1 : 0;
-        j -= seg == 2 ? a.nq + a.nkv : seg == 1 ? a.nq : 0;
-        nseg = seg == 0 ? a.nq : a.nkv;
-        o = seg == 0 ? a.out : seg == 1 ? a.outk : a.outv;
+        const QkvSeg<GemmArgs> sg = qkv_seg(a, nb);
+        seg = sg.seg;
+        j -= sg.first();
+        nseg = sg.rows();
+        o = sg.pick(&GemmArgs::out, &GemmArgs::outk, &GemmArgs::outv);
         ld = seg == 0 ? a.ldo : a.ldkv;
     }
     const bool inr = j < nseg;
@@ -225,11 +224,114 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &a, v16f (&acc)[TM]
 #pragma unroll
             for (int r = 0; r < 16; r++) {
                 v[r] = acc[i][jt][r];
-                tok[r] = m0 + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                tok[r] = mfma32_row(m0 + (wm * TM + i) * 32, r, lane);
                 on[r] = tok[r] < a.P && i * 16 + r >= lo && i * 16 + r < hi;
             }
             epi_values<EPI, 16>(a, v, tok, on, n0 + (wn * TN + jt) * 32, lane);
         }
+}
+
+// ---- a lane's accumulators, and the ways they pass from one wave or block to another ----
+// The one walk over acc[TM][TN][16]: acc[i][j][r] = f(acc[i][j][r], flat) in the fixed order flat = (i TN + j) 16 + r.
+// (By value: an element of an ext_vector_type does not bind to a reference.)
+template <int TM, int TN, class F>
+__device__ __forceinline__ void acc_each(v16f (&acc)[TM][TN], F &&f)
+{
+#pragma unroll
+    for (int i = 0; i < TM; i++)
+#pragma unroll
+        for (int j = 0; j < TN; j++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[i][j][r] = f(acc[i][j][r], (i * TN + j) * 16 + r);
+}
+// Where the accumulators live outside the registers -- the k-groups' sums in LDS, the dumps and partial sums in the split-K
+// workspace, the deferred sums the next rmsnorm launch reads (DeferredSum): wave w's value `flat` of lane l is float
+// (w TM TN 16 + flat) 64 + l of the tile's block of 32 TM x 32 TN x waves floats = the tile's outputs, which is what the
+// plan's part_floats arithmetic counts per tile and range (prefill_gemm_plan, plan_stream).  A wave's part, from its lane on:
+template <int TM, int TN>
+__device__ __forceinline__ float *acc_part(float *tile, int w, int lane) { return tile + (w * (TM * TN * 16 * 64) + lane); }
+constexpr int acc_slot(int flat) { return flat * 64; }
+
+template <int TM, int TN>
+__device__ __forceinline__ void acc_store(v16f (&acc)[TM][TN], float *p)
+{
+    acc_each(acc, [&](float v, int k) { p[acc_slot(k)] = v; return v; });
+}
+template <int TM, int TN>   // write-through: past this CU's caches, for another block to read
+__device__ __forceinline__ void acc_store_through(v16f (&acc)[TM][TN], float *p)
+{
+    acc_each(acc, [&](float v, int k) { __hip_atomic_store(p + acc_slot(k), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return v; });
+}
+template <int TM, int TN>
+__device__ __forceinline__ void acc_add(v16f (&acc)[TM][TN], const float *p)
+{
+    acc_each(acc, [&](float v, int k) { return v + p[acc_slot(k)]; });
+}
+
+// The two k-groups of ONE block: group 1 leaves its sums in LDS (red: [NWG waves], acc_part) and ENDS (false); group 0 adds
+// them.  Every wave of the block calls it (wg: its place among its group's waves); the stage buffers red reuses must be dead.
+template <int TM, int TN>
+__device__ __forceinline__ bool kgroup_sum(v16f (&acc)[TM][TN], float *red, int kg, int wg, int lane)
+{
+    float *part = acc_part<TM, TN>(red, wg, lane);
+    if (kg > 0) acc_store(acc, part);
+    __syncthreads();
+    if (kg > 0) return false;
+    acc_add(acc, part);
+    return true;
+}
+
+// The sk blocks of a tile that each hold ONE K range's sums, nobody waiting for anybody (the split-K family; the stream
+// form's launches of several rounds): a block leaves its sums in the workspace with write-through stores, drains them
+// and bumps the tile's counter; every block but the one that arrives last ENDS (false); the last adds the sk partials IN
+// RANGE ORDER -- its own read back like the others: one fixed order -- and leaves the counter at zero for the next launch.
+// part: the tile's sk partials of pt floats each; z: this block's range; w: this wave's part of a partial (acc_part);
+// flag: an int of dead LDS.  How the last block reads what other CUs wrote is the caller's recipe, kept as measured:
+//   SCOPED false (the tile kernel): the last block acquires ONCE (a fence: this CU's stale lines of the partials -- the
+//     hand-off recipe of attention.hip's split kernel), then plain loads, a value's sk ranges one after the other;
+//   SCOPED true (the stream form): no fence (an acquire fence per block would drop the whole L2) but device-scope loads,
+//     served past this XCD's caches, a range's values requested together (one round trip per range; two ranges in
+//     flight cost 64 more registers and spilled).
+template <bool SCOPED, int TM, int TN>
+__device__ __forceinline__ bool split_k_last_sum(v16f (&acc)[TM][TN], float *part, int pt, int z, int sk, int w, int lane, int *cnt, int *flag, int tid)
+{
+    acc_store_through(acc, acc_part<TM, TN>(part + (size_t)z * pt, w, lane));
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its partial
+    __syncthreads();   // (the live waves: k-group 0)
+    if (tid == 0) {
+        const int prev = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = prev == sk - 1;
+        if (last) {
+            __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // for the next launch
+            if constexpr (!SCOPED) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // this CU's stale lines of the partials
+        }
+        *flag = last;
+    }
+    __syncthreads();
+    if (!*flag) return false;
+    const float *p0 = acc_part<TM, TN>(part, w, lane);
+    if constexpr (SCOPED) {
+        float t[TM * TN * 16];
+        auto fetch = [&](int zz) {
+            acc_each(acc, [&](float v, int k) {
+                t[k] = __hip_atomic_load(p0 + (size_t)zz * pt + acc_slot(k), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                return v;
+            });
+        };
+        fetch(0);
+        acc_each(acc, [&](float, int k) { return t[k]; });
+        for (int zz = 1; zz < sk; zz++) {
+            fetch(zz);
+            acc_each(acc, [&](float v, int k) { return v + t[k]; });
+        }
+    } else {
+        acc_each(acc, [&](float, int k) {
+            float v = p0[acc_slot(k)];  // range 0, then 1, ... in order
+            for (int zz = 1; zz < sk; zz++) v += p0[(size_t)zz * pt + acc_slot(k)];
+            return v;
+        });
+    }
+    return true;
 }
 
 // MFMA 32x32x2 f32: D[i][j] += A[i][k] B[k][j] with
@@ -241,9 +343,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &a, v16f (&acc)[TM]
 // whole stages against zero-padded activation rows: pad_k, prefill_common.h.)
 
 // The tile product with the operands brought in by DIRECT-TO-LDS loads
-// (global_load_lds_dwordx4, gfx950): no VGPR round trip and no LDS-write instructions -- in the
-// register-staged kernel above the copy (6 float4 loads -> 24 ds_write_b32 per thread and stage,
-// the row padding forbids wider writes) costs 13 % of the run time (ablation).
+// (global_load_lds_dwordx4, gfx950): no VGPR round trip and no LDS-write instructions -- in a
+// register-staged form the copy (6 float4 loads -> 24 ds_write_b32 per thread and stage,
+// the row padding forbids wider writes) cost 13 % of the run time (ablation).
 //  * LDS tile rows are unpadded (BK = 64 floats = 256 B = 16 float4 slots); a wave-wide load writes
 //    1 KB = 4 whole rows, lane L -> row L / 16, physical slot L % 16.
 //  * Operands are read with ds_read_b128: lane l of an MFMA 32x32x2 operand holds row l & 31 and
@@ -327,18 +429,11 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void prefill_gemm_dma(const Gemm
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wg = KGS ? wave : wave % NWG, kg = KGS ? (int)blockIdx.z : wave / NWG, wm = wg / WN, wn = wg % WN;
     const int kslot0 = KGS ? kg * SLOTS : 0;         // first slot of the 64-k stage this block's LDS rows hold
-    // Block -> tile.  2-D grid: x = feature tile, y = token tile.  1-D grid (a.nty > 0, dma_grid): ids are
-    // dispatched in order and round-robin over the 8 XCDs, so consecutive groups of 8 nty ids take 8
-    // feature tiles x all nty token tiles with id % 8 = feature tile % 8: the nty blocks that read the
-    // same W tile run on ONE XCD (one L2 fill) and at the same time -- also in grids of several waves,
-    // where the 2-D order lets them drift a whole wave apart.
+    // Block -> tile.  2-D grid: x = feature tile, y = token tile.  1-D grid (a.nty > 0, dma_grid): block_tile_1d -- the
+    // blocks that read the same W tile run on one XCD and at the same time, also in grids of several waves, where the
+    // 2-D order lets them drift a whole wave apart.
     int bx = blockIdx.x, by = blockIdx.y;
-    if (a.nty > 0) {
-        const int group = 8 * a.nty, g = bx / group, local = bx - g * group;
-        by = local >> 3;
-        bx = g * 8 + (local & 7);
-        if (bx >= a.ntx) return;  // padding of the last group
-    }
+    if (a.nty > 0 && !block_tile_1d(a, bx, by)) return;
     const int n0 = bx * (PAIR ? BNt / 2 : BNt), m0 = by * BMt;
     // SPLIT == 1: this block's K range (launcher: K % (64 sk) == 0)
     // (whole 64-k stages, as even as they come: range z takes stages [S z / sk, S (z + 1) / sk) of the S = K / 64)
@@ -368,14 +463,17 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void prefill_gemm_dma(const Gemm
             const int f = n0 + (r >> 6) * 32 + (r & 31);
             wsrc[j] = m + (size_t)min(f, a.N - 1) * a.ldw + 4 * (kslot0 + (pslot ^ swz(r)));
         } else if (EPI == G_QKV) {  // the matrix of the block's column range
-            const int seg = n0 >= a.nq + a.nkv ? 2 : n0 >= a.nq ? 1 : 0;
-            const float *m = seg == 0 ? a.w : seg == 1 ? a.wk : a.wv;
-            const int f0 = n0 - (seg == 2 ? a.nq + a.nkv : seg == 1 ? a.nq : 0), nseg = seg == 0 ? a.nq : a.nkv;
+            const QkvSeg<GemmArgs> sg = qkv_seg(a, n0);
+            const float *m = sg.pick(&GemmArgs::w, &GemmArgs::wk, &GemmArgs::wv);
+            const int f0 = n0 - sg.first(), nseg = sg.rows();
             wsrc[j] = m + (size_t)min(f0 + r, nseg - 1) * a.ldw + 4 * (kslot0 + (pslot ^ swz(r)));
         } else {
             wsrc[j] = a.w + (size_t)min(n0 + r, a.N - 1) * a.ldw + 4 * (kslot0 + (pslot ^ swz(r)));
         }
     }
+    // The f32 form's stage bodies stay macros, and the two-block hand-over below the kernel's own loops: as lambdas (plain or
+    // always_inline) and as a function over acc_each they move the f32 two-block kernels across an occupancy step and the 7B
+    // prefill of 512 tokens on the f32 cores by +0.5 % (profiles/prefill_kernels_refactor.md).
 #define L2Z_DMA_ISSUE(k0_, buf_)                                                                          \
     do {                                                                                                  \
         float *xs_ = smem + (buf_) * STAGE, *ws_ = xs_ + XSTG;                                            \
@@ -385,13 +483,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void prefill_gemm_dma(const Gemm
             lds_dma16(wsrc[j] + (k0_), ws_ + (wave * WI + j) * 256);                                       \
     } while (0)
 
-    v16f acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; i++)
-#pragma unroll
-        for (int j = 0; j < TN; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.0f;
+    v16f acc[TM][TN] = {};
 
     // operand addresses (float4 units) of super-step s: row base + ((logical slot) ^ (row & 15))
     const int hl = lane >> 5, il = lane & 31;
@@ -556,6 +648,9 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void prefill_gemm_dma(const Gemm
     }
     }
 #undef L2Z_MULTIPLY_STAGE
+    // The k-groups' sums through LDS, in acc_part's layout.  Written out here, not kgroup_sum (the stream form's): with the
+    // shared function the bf16 instantiations of 1024-token chunks came out with other code -- the RoPE epilogue's multiplies
+    // in both arms, 15 % more instructions -- and 0.26 % slower (profiles/prefill_kernels_refactor.md).
     if (KS > 1 && !KGS) {
         float *red = smem;  // [KS-1][NWG waves][TM*TN*16][64 lanes]
         if (kg > 0) {
@@ -620,45 +715,13 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void prefill_gemm_dma(const Gemm
                 for (int r = 0; r < 16; r++) acc[i][j][r] += dump[((i * TN + j) * 16 + r) * 64];  // kg0 + kg1 (a + b == b + a)
     }
     if constexpr (SPLIT == 1) {
-        // the k-group-0 waves hold the block's sums (the others have left; a barrier only counts live waves)
         constexpr int PT = NWG * TM * TN * 16 * 64;  // floats per partial = the tile's outputs
-        const int ntx_all = a.nty > 0 ? a.ntx : (int)gridDim.x;
-        const size_t tile = (size_t)by * ntx_all + bx;
-        float *part = a.sk_part + tile * (size_t)a.sk * PT;
-        float *mine = part + (size_t)blockIdx.z * PT + (size_t)wg * (TM * TN * 16 * 64) + lane;
-#pragma unroll
-        for (int i = 0; i < TM; i++)
-#pragma unroll
-            for (int j = 0; j < TN; j++)
-#pragma unroll
-                for (int r = 0; r < 16; r++)
-                    __hip_atomic_store(mine + ((i * TN + j) * 16 + r) * 64, acc[i][j][r], __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);  // write-through
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its partial
-        __syncthreads();
-        int *flag = (int *)smem;  // stage buffers and the k-group sums are dead
-        if (tid == 0) {
-            const int prev = __hip_atomic_fetch_add(a.sk_cnt + tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int last = prev == a.sk - 1;
-            if (last) {
-                __hip_atomic_store(a.sk_cnt + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // for the next launch
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // this CU's stale lines of the partials
-            }
-            *flag = last;
-        }
-        __syncthreads();
-        if (!*flag) return;
-        const float *p0 = part + (size_t)wg * (TM * TN * 16 * 64) + lane;
-#pragma unroll
-        for (int i = 0; i < TM; i++)
-#pragma unroll
-            for (int j = 0; j < TN; j++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    float v = p0[((i * TN + j) * 16 + r) * 64];  // range 0, then 1, ... in order
-                    for (int z = 1; z < a.sk; z++) v += p0[(size_t)z * PT + ((i * TN + j) * 16 + r) * 64];
-                    acc[i][j][r] = v;
-                }
+        const size_t tile = (size_t)by * (a.nty > 0 ? a.ntx : (int)gridDim.x) + bx;
+        // the k-group-0 waves hold the block's sums (the others have left; a barrier only counts live waves); the flag:
+        // stage buffers and the k-group sums are dead
+        if (!split_k_last_sum<false>(acc, a.sk_part + tile * (size_t)a.sk * PT, PT, (int)blockIdx.z, a.sk, wg, lane,
+                                     a.sk_cnt + tile, (int *)smem, tid))
+            return;
     }
     if constexpr (PAIR) {
         const int j = n0 + wn * 32 + (lane & 31);
@@ -666,7 +729,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void prefill_gemm_dma(const Gemm
         for (int i = 0; i < TM; i++)
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const int tok = m0 + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const int tok = mfma32_row(m0 + (wm * TM + i) * 32, r, lane);
                 if (tok < a.P && j < a.N) {
                     const float g = swiglu_merge(acc[i][0][r], acc[i][1][r]);  // :411-416
                     a.out[(size_t)tok * a.ldo + j] = g;
@@ -705,6 +768,20 @@ template <int N_> __device__ __forceinline__ void wait_vmcnt()
 {
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N_) : "memory");
 }
+// Wait until at most `ahead` stages of a ring of NBUF (NL loads of this wave each) are still in flight, and for this wave's
+// LDS reads.  The counter takes an immediate: a literal per case, and `ahead` a constant wherever the call is inlined.
+// (ahead <= NBUF - 1: that many stages can be in flight behind the one awaited.)
+template <int NBUF, int NL> __device__ __forceinline__ void wait_stages(int ahead)
+{
+    static_assert(NBUF <= 7 && NL * (NBUF - 1) <= 63, "vmcnt");
+    if (ahead <= 0) wait_vmcnt<0>();
+    else if (ahead == 1) wait_vmcnt<NL>();
+    else if (ahead == 2) wait_vmcnt<(NBUF > 2 ? 2 : 0) * NL>();
+    else if (ahead == 3) wait_vmcnt<(NBUF > 3 ? 3 : 0) * NL>();
+    else if (ahead == 4) wait_vmcnt<(NBUF > 4 ? 4 : 0) * NL>();
+    else if (ahead == 5) wait_vmcnt<(NBUF > 5 ? 5 : 0) * NL>();
+    else wait_vmcnt<(NBUF > 6 ? 6 : 0) * NL>();
+}
 
 template <int EPI, int TM, int NBUF, int WN>
 __global__ __launch_bounds__(128 * WN) void prefill_x3_stream(const GemmArgs a)
@@ -714,7 +791,6 @@ __global__ __launch_bounds__(128 * WN) void prefill_x3_stream(const GemmArgs a)
     // per wave and stage (X: the last waves repeat a load); experiment builds 32 / 64: no X / no W loads at all
     constexpr int XI = (L2Z_X3_EXP & 32) ? 0 : (XLOADS + NW - 1) / NW, WI = (L2Z_X3_EXP & 64) ? 0 : BNt * 128 / 1024 / NW, NL = XI + WI;
     constexpr int XSTG = 3 * BMt * 16, WSTG = BNt * 32, STAGE = XSTG + WSTG;                 // floats
-    static_assert(NL * (NBUF - 1) <= 63, "vmcnt");
     extern __shared__ __attribute__((aligned(16))) float smem[];
 #ifdef L2Z_X3_TIMELINE
     long long tl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -754,7 +830,9 @@ __global__ __launch_bounds__(128 * WN) void prefill_x3_stream(const GemmArgs a)
         const float *m = a.w;
         int f = n0 + r, nseg = a.N;
         if constexpr (EPI == G_QKV) {
-            const int seg = f >= a.nq + a.nkv ? 2 : f >= a.nq ? 1 : 0;   // (per row: a tile may lie across two of the matrices)
+            // (per row: a tile may lie across two of the matrices.  Written out, not qkv_seg: with the helper here the eight
+            // q | k | v stream kernels came out with four more global loads each)
+            const int seg = f >= a.nq + a.nkv ? 2 : f >= a.nq ? 1 : 0;
             m = seg == 0 ? a.w : seg == 1 ? a.wk : a.wv;
             f -= seg == 2 ? a.nq + a.nkv : seg == 1 ? a.nq : 0;
             nseg = seg == 0 ? a.nq : a.nkv;
@@ -791,11 +869,7 @@ __global__ __launch_bounds__(128 * WN) void prefill_x3_stream(const GemmArgs a)
         lo = wr[brow + (sb ^ bsw)];
         hi = wr[brow + ((sb + 1) ^ bsw)];
     };
-    v16f acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; i++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[i][0][r] = 0.0f;
+    v16f acc[TM][TN] = {};
 
     // prologue: the first NBUF stages requested; stage 0 awaited
 #pragma unroll
@@ -804,17 +878,7 @@ __global__ __launch_bounds__(128 * WN) void prefill_x3_stream(const GemmArgs a)
 #pragma unroll
             for (int q = 0; q < NL; q++) issue_one(b, q);
         }
-    {
-        const int ahead = (nstage < NBUF ? nstage : NBUF) - 1;   // stages that may still be in flight
-        // (a literal per case: the counter takes an immediate)
-        if (ahead <= 0) wait_vmcnt<0>();
-        else if (ahead == 1) wait_vmcnt<NL>();
-        else if (ahead == 2) wait_vmcnt<2 * NL>();
-        else if (ahead == 3) wait_vmcnt<(NBUF > 3 ? 3 : 0) * NL>();
-        else if (ahead == 4) wait_vmcnt<(NBUF > 4 ? 4 : 0) * NL>();
-        else if (ahead == 5) wait_vmcnt<(NBUF > 5 ? 5 : 0) * NL>();
-        else wait_vmcnt<(NBUF > 6 ? 6 : 0) * NL>();
-    }
+    wait_stages<NBUF, NL>((nstage < NBUF ? nstage : NBUF) - 1);   // the stages behind stage 0 may still be in flight
     __syncthreads();
     L2Z_XTL(1);
     Bf3 av[TM], bcur;
@@ -825,12 +889,12 @@ __global__ __launch_bounds__(128 * WN) void prefill_x3_stream(const GemmArgs a)
     for (int i = 0; i < TM; i++) av[i] = read_a(0, i);
 
     // step s: MFMAs of stage s (operands in registers); behind them the loads of stage s + NBUF and the operands of s + 1.
-    // AHEAD: stages beyond s + 1 that may still be in flight at the top of the step (steady state NBUF - 2)
-    auto step = [&](auto ahead_c, auto has_next_c, auto issue_c, int s) {
-        constexpr int ahead = decltype(ahead_c)::value;
+    // ahead: stages beyond s + 1 that may still be in flight at the top of the step (steady state NBUF - 2); a constant at
+    // every call once the step is inlined there (wait_stages)
+    auto step = [&](int ahead, auto has_next_c, auto issue_c, int s) __attribute__((always_inline)) {
         constexpr bool has_next = decltype(has_next_c)::value, issue = decltype(issue_c)::value;
         if constexpr (has_next) {
-            wait_vmcnt<ahead * NL>();   // stage s + 1 has landed (this wave's part) and this wave's reads of stage s are done ...
+            wait_stages<NBUF, NL>(ahead);   // stage s + 1 has landed (this wave's part) and this wave's reads of stage s are done ...
             // ... for every wave: stage s's buffer takes the loads of stage s + NBUF.  (The bare barrier: behind __syncthreads()
             // the compiler drains vmcnt to 0 in the steps that issue nothing -- the tail -- and the last stages then land with
             // nothing multiplying beside them.)
@@ -858,49 +922,28 @@ __global__ __launch_bounds__(128 * WN) void prefill_x3_stream(const GemmArgs a)
     using T = std::true_type;
     using F = std::false_type;
     int s = 0;
-    for (; s + NBUF < nstage; s++) step(std::integral_constant<int, NBUF - 2>{}, T{}, T{}, s);
+    for (; s + NBUF < nstage; s++) step(NBUF - 2, T{}, T{}, s);
     // the tail: nothing left to request; fewer and fewer stages in flight
 #pragma unroll
     for (int t = NBUF - 1; t >= 1; t--)
         if (nstage - 1 - s == t) {
             // stages s + 1 .. s + t are the last ones: t - 1 of them beyond s + 1
-            if (t - 1 >= NBUF - 2) step(std::integral_constant<int, NBUF - 2>{}, T{}, F{}, s);
-            else if (t - 1 == 4) step(std::integral_constant<int, (NBUF > 6 ? 4 : 0)>{}, T{}, F{}, s);
-            else if (t - 1 == 3) step(std::integral_constant<int, (NBUF > 5 ? 3 : 0)>{}, T{}, F{}, s);
-            else if (t - 1 == 2) step(std::integral_constant<int, (NBUF > 4 ? 2 : 0)>{}, T{}, F{}, s);
-            else if (t - 1 == 1) step(std::integral_constant<int, (NBUF > 3 ? 1 : 0)>{}, T{}, F{}, s);
-            else step(std::integral_constant<int, 0>{}, T{}, F{}, s);
+            step(t - 1 < NBUF - 2 ? t - 1 : NBUF - 2, T{}, F{}, s);
             s++;
         }
-    step(std::integral_constant<int, 0>{}, F{}, F{}, s);
+    step(0, F{}, F{}, s);
     __syncthreads();   // every wave is done with the ring (the k-groups' sums reuse it)
     L2Z_XTL(2);
 
     // the two k-groups' sums, then (sk > 1) the ranges' through the workspace, then the epilogue -- as in the tile forms
-    {
-        float *red = smem;  // [WN waves][TM * 16][64 lanes]
-        if (kg > 0) {
-#pragma unroll
-            for (int i = 0; i < TM; i++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) red[((wn * TM + i) * 16 + r) * 64 + lane] = acc[i][0][r];
-        }
-        __syncthreads();
-        if (kg > 0) return;
-#pragma unroll
-        for (int i = 0; i < TM; i++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[i][0][r] += red[((wn * TM + i) * 16 + r) * 64 + lane];
-    }
+    if (!kgroup_sum(acc, smem, kg, wn, lane)) return;
     L2Z_XTL(3);
+    constexpr int PT = WN * TM * 16 * 64;   // floats per partial = the tile's outputs
+    float *part = a.sk_part + (size_t)bx * (size_t)sk * PT;   // the tile's sk partials
     if constexpr (EPI == G_RESID) {
         if (sk > 1 && a.defer) {
             // the sums stay as they are: the next rmsnorm launch adds the ranges in order and the residual (DeferredSum)
-            float *mine = a.sk_part + ((size_t)bx * (size_t)sk + (size_t)bz) * (WN * TM * 16 * 64) + (size_t)wn * (TM * 16 * 64) + lane;
-#pragma unroll
-            for (int i = 0; i < TM; i++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) mine[(i * 16 + r) * 64] = acc[i][0][r];
+            acc_store(acc, acc_part<TM, TN>(part + (size_t)bz * PT, wn, lane));
             tl_store();
             return;
         }
@@ -908,62 +951,15 @@ __global__ __launch_bounds__(128 * WN) void prefill_x3_stream(const GemmArgs a)
     if (sk > 1 && !coop) {
         // A launch of several rounds of blocks: whichever block of a tile arrives last adds the sk partials in range order
         // (nobody waits: a waiting block would hold a CU its not-yet-resident siblings need) and runs the epilogue.
-        constexpr int PT = WN * TM * 16 * 64;   // floats per partial = the tile's outputs
-        float *part = a.sk_part + (size_t)bx * (size_t)sk * PT;
-        float *mine = part + (size_t)bz * PT + (size_t)wn * (TM * 16 * 64) + lane;
-#pragma unroll
-        for (int i = 0; i < TM; i++)
-#pragma unroll
-            for (int r = 0; r < 16; r++)
-                __hip_atomic_store(mine + (i * 16 + r) * 64, acc[i][0][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // write-through
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();   // (the live waves: k-group 0)
-        int *flag = (int *)smem + WN * TM * 16 * 64;   // past the k-groups' sums
-        if (tid == 0) {
-            const int prev = __hip_atomic_fetch_add(a.sk_cnt + 2 * bx, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int last = prev == sk - 1;
-            if (last) __hip_atomic_store(a.sk_cnt + 2 * bx, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // for the next launch
-            *flag = last;
-        }
-        __syncthreads();
-        if (!*flag) return;
-        // range 0, then 1, ... in order; a range's TM x 16 values are requested together (device-scope loads: served past this
-        // XCD's caches)
-        const float *p0 = part + (size_t)wn * (TM * 16 * 64) + lane;
-        auto fetch = [&](int z, v16f (&d)[TM]) {
-#pragma unroll
-            for (int i = 0; i < TM; i++)
-#pragma unroll
-                for (int r = 0; r < 16; r++)
-                    d[i][r] = __hip_atomic_load(p0 + (size_t)z * PT + (i * 16 + r) * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        };
-        {
-            v16f t[TM];
-            fetch(0, t);
-#pragma unroll
-            for (int i = 0; i < TM; i++) acc[i][0] = t[i];
-            for (int z = 1; z < sk; z++) {   // (one round trip per range; two ranges in flight cost 64 more registers and spilled)
-                fetch(z, t);
-#pragma unroll
-                for (int i = 0; i < TM; i++)
-#pragma unroll
-                    for (int r = 0; r < 16; r++) acc[i][0][r] += t[i][r];
-            }
-        }
+        // (the flag: past the k-groups' sums)
+        if (!split_k_last_sum<true>(acc, part, PT, bz, sk, wn, lane, a.sk_cnt + 2 * bx, (int *)smem + PT, tid)) return;
     } else if (sk > 1) {
         // The tile's K ranges: every block leaves its sums in the workspace (write-through), arrives, and waits for its sk - 1
         // siblings (consecutive block ids: resident with it or about to be -- see the block -> tile map); then EVERY block
         // finishes 1 / sk of the tile: values [lo, lo + PER) of each lane's TM x 16 (flat index i * 16 + r), the ranges added
         // IN RANGE ORDER -- a range's PER values requested together, one round trip per range -- and their epilogue.
         // (The last-arriver form: one block re-read all sk partials of the tile with its 7 siblings' CUs idle.)
-        constexpr int PT = WN * TM * 16 * 64;   // floats per partial = the tile's outputs
-        float *part = a.sk_part + (size_t)bx * (size_t)sk * PT;
-        float *mine = part + (size_t)bz * PT + (size_t)wn * (TM * 16 * 64) + lane;
-#pragma unroll
-        for (int i = 0; i < TM; i++)
-#pragma unroll
-            for (int r = 0; r < 16; r++)
-                __hip_atomic_store(mine + (i * 16 + r) * 64, acc[i][0][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // write-through
+        acc_store_through(acc, acc_part<TM, TN>(part + (size_t)bz * PT, wn, lane));
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();   // (the live waves: k-group 0) every wave's part has left
         L2Z_XTL(4);
@@ -976,7 +972,7 @@ __global__ __launch_bounds__(128 * WN) void prefill_x3_stream(const GemmArgs a)
         }
         __syncthreads();
         L2Z_XTL(5);
-        const float *p0 = part + (size_t)wn * (TM * 16 * 64) + lane;
+        const float *p0 = acc_part<TM, TN>(part, wn, lane);
         auto finish = [&](auto sk_c) {
             constexpr int SK = decltype(sk_c)::value, PER = TM * 16 / SK;   // values per block
             const int lo = bz * PER;
@@ -988,7 +984,7 @@ __global__ __launch_bounds__(128 * WN) void prefill_x3_stream(const GemmArgs a)
             for (int z = 0; z < SK; z++)
 #pragma unroll
                 for (int k = 0; k < PER; k++)
-                    t[z][k] = __hip_atomic_load(p0 + (size_t)z * PT + (size_t)(lo + k) * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    t[z][k] = __hip_atomic_load(p0 + (size_t)z * PT + acc_slot(lo + k), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
             for (int z = 1; z < SK; z++)
 #pragma unroll
@@ -1006,7 +1002,7 @@ __global__ __launch_bounds__(128 * WN) void prefill_x3_stream(const GemmArgs a)
 #pragma unroll
             for (int k = 0; k < PER; k++) {
                 const int idx = lo + k, i = idx >> 4, r = idx & 15;
-                tok[k] = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                tok[k] = mfma32_row(i * 32, r, lane);
                 on[k] = tok[k] < a.P;
             }
             epi_values<EPI, PER>(a, t[0], tok, on, n0 + wn * 32, lane);

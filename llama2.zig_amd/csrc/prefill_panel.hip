@@ -238,17 +238,16 @@ __global__ __launch_bounds__(64 * NW) void prefill_panel(const PanelArgs a)
     }
 }
 
-// ---- second launch: ranges added in range order + the product's epilogue ----
-enum PanelMode { PN_STORE = 0, PN_RESID = 1, PN_SWIGLU = 2, PN_QKV = 3 };
+// ---- second launch: ranges added in range order + the product's epilogue (MODE: PanelEpi) ----
 
 struct PanelReduceArgs {
     const float *part;   // [ranges][P16][N]
     int n_ranges, P16, N, P;
-    float *out;          // PN_STORE / PN_RESID: [P, ldo]; PN_SWIGLU: [P, ldo] of N / 2 gated values; PN_QKV: q [P, ldo]
+    float *out;          // PANEL_STORE / PANEL_RESID: [P, ldo]; PANEL_SWIGLU: [P, ldo] of N / 2 gated values; PANEL_QKV: q [P, ldo]
     int ldo;
-    const float *res;    // PN_RESID: out = res + product
+    const float *res;    // PANEL_RESID: out = res + product
     int ldres;
-    // PN_QKV: features [0, nq) -> RoPE -> out; [nq, nq + nkv) -> RoPE -> key-cache row pos0 + token; then the value cache
+    // PANEL_QKV: features [0, nq) -> RoPE -> out; [nq, nq + nkv) -> RoPE -> key-cache row pos0 + token; then the value cache
     int nq, nkv, ldkv, head_size, pos0;
     float *outk, *outv;
     size_t kv_head_stride;
@@ -275,12 +274,6 @@ __device__ __forceinline__ v4f pn_sum_ranges(const PanelReduceArgs &a, int t, in
     return v;
 }
 
-__device__ __forceinline__ size_t pn_kv_index(const PanelReduceArgs &a, int pos, int f)
-{
-    return a.kv_head_stride ? (size_t)(f / a.head_size) * a.kv_head_stride + (size_t)pos * (size_t)a.head_size + (size_t)(f % a.head_size)
-                            : (size_t)pos * (size_t)a.ldkv + (size_t)f;
-}
-
 template <int MODE>
 __global__ __launch_bounds__(256) void panel_reduce(const PanelReduceArgs a)
 {
@@ -288,22 +281,22 @@ __global__ __launch_bounds__(256) void panel_reduce(const PanelReduceArgs a)
     const int f = 4 * (blockIdx.x * 256 + threadIdx.x);
     if (f >= a.N) return;
     const v4f v = pn_sum_ranges(a, t, f);
-    if (MODE == PN_STORE) {
+    if (MODE == PANEL_STORE) {
         *(v4f *)(a.out + (size_t)t * a.ldo + f) = v;
-    } else if (MODE == PN_RESID) {
+    } else if (MODE == PANEL_RESID) {
         const v4f r = *(const v4f *)(a.res + (size_t)t * a.ldres + f);
         v4f o;
         o.x = r.x + v.x; o.y = r.y + v.y; o.z = r.z + v.z; o.w = r.w + v.w;   // main.zig:711
         *(v4f *)(a.out + (size_t)t * a.ldo + f) = o;
-    } else if (MODE == PN_SWIGLU) {
+    } else if (MODE == PANEL_SWIGLU) {
         // rows 2p, 2p + 1 = W1 row p, W3 row p (main.zig:405-416)
         float2 o;
         o.x = swiglu_merge(v.x, v.y);
         o.y = swiglu_merge(v.z, v.w);
         *(float2 *)(a.out + (size_t)t * a.ldo + (f >> 1)) = o;
     } else {
-        const int seg = f >= a.nq + a.nkv ? 2 : f >= a.nq ? 1 : 0;
-        const int fl = f - (seg == 2 ? a.nq + a.nkv : seg == 1 ? a.nq : 0);
+        const QkvSeg<PanelReduceArgs> sg = qkv_seg(a, f);
+        const int seg = sg.seg, fl = f - sg.first();
         v4f o = v;
         if (seg < 2) {  // RoPE on the pairs (fl, fl + 1), (fl + 2, fl + 3)  (main.zig:346-349)
             const int hs = a.head_size, pos = a.pos0 + t;
@@ -318,7 +311,7 @@ __global__ __launch_bounds__(256) void panel_reduce(const PanelReduceArgs a)
             *(v4f *)(a.out + (size_t)t * a.ldo + fl) = o;
         } else {  // :354-358 (four consecutive features of one head: head_size % 4 == 0)
             float *c = seg == 1 ? a.outk : a.outv;
-            *(v4f *)(c + pn_kv_index(a, a.pos0 + t, fl)) = o;
+            *(v4f *)(c + kv_index(a.kv_head_stride, a.head_size, a.ldkv, a.pos0 + t, fl)) = o;
         }
     }
 }
@@ -419,12 +412,12 @@ hipError_t launch_prefill_panel(const PanelProduct &p, int n_cus, const SplitKWs
     r.outk = p.outk; r.outv = p.outv; r.kv_head_stride = p.kv_head_stride; r.rope = p.rope;
     const dim3 g2((unsigned)((N / 4 + 255) / 256), (unsigned)p.P);
     switch (p.mode) {
-    case PANEL_STORE: hipLaunchKernelGGL(panel_reduce<PN_STORE>, g2, dim3(256), 0, st, r); break;
-    case PANEL_RESID: hipLaunchKernelGGL(panel_reduce<PN_RESID>, g2, dim3(256), 0, st, r); break;
-    case PANEL_SWIGLU: hipLaunchKernelGGL(panel_reduce<PN_SWIGLU>, g2, dim3(256), 0, st, r); break;
+    case PANEL_STORE: hipLaunchKernelGGL(panel_reduce<PANEL_STORE>, g2, dim3(256), 0, st, r); break;
+    case PANEL_RESID: hipLaunchKernelGGL(panel_reduce<PANEL_RESID>, g2, dim3(256), 0, st, r); break;
+    case PANEL_SWIGLU: hipLaunchKernelGGL(panel_reduce<PANEL_SWIGLU>, g2, dim3(256), 0, st, r); break;
     case PANEL_QKV:
         if ((p.head_size % 4) != 0) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(panel_reduce<PN_QKV>, g2, dim3(256), 0, st, r);
+        hipLaunchKernelGGL(panel_reduce<PANEL_QKV>, g2, dim3(256), 0, st, r);
         break;
     default: return hipErrorInvalidValue;
     }

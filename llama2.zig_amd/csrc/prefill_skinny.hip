@@ -50,14 +50,10 @@ __global__ __launch_bounds__(kPfBlock) void prefill_skinny_dma(const GemmArgs a)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 15, q = lane >> 4;
     // 1-D grid when there are several token tiles (a.nty > 0): the blocks that read the same 16 rows of W
-    // get ids 8 apart -- one XCD, the same moment -- so that W comes from HBM once (prefill_gemm.hip,
-    // block -> tile)
+    // get ids 8 apart -- one XCD, the same moment -- so that W comes from HBM once (block_tile_1d)
     int bx = blockIdx.x, by = blockIdx.y;
     if (a.nty > 0) {
-        const int group = 8 * a.nty, g = bx / group, local = bx - g * group;
-        by = local >> 3;
-        bx = g * 8 + (local & 7);
-        if (bx >= a.ntx) return;
+        if (!block_tile_1d(a, bx, by)) return;
     } else if (a.ntx > 0) {
         // one token tile, a matrix that streams: block ids go round-robin over the 8 XCDs, so id b takes group
         // (b % 8) * per + b / 8 -- every XCD sweeps its own eighth of the rows linearly instead of all of them
