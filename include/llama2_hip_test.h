@@ -352,6 +352,37 @@ int l2z_sample_run(const l2z_config *config, l2z_runstate *s, const l2z_weights 
                    float temperature, float top_p, const float *coins,
                    int32_t *out_tokens, int *out_n);
 
+/* ---- wide batched decode (preview) ----
+ * One decode step for up to L2Z_WIDE_MAX independent sequences, one runstate each, with one sweep of the weights on the
+ * matrix cores: the n rows are ONE chunk of n rows of the ragged prompt pass (l2z_prefill_batch's) on states[0]'s prefill
+ * scratch, so every product takes the whole model's GEMM form at that row count, and the attention is a position-split
+ * decode kernel in which a block reads a kv head's K / V rows of one segment once for all the query heads that share them.
+ * The state change is l2z_transformer_batch's, for 1 <= n <= L2Z_WIDE_MAX: KV row pos[i] of every layer of states[i] is
+ * written -- and NO other cache row of any runstate --, states[i]'s logits hold its result, and every runstate's host
+ * bookkeeping is left as l2z_transformer_batch leaves it (next position pos[i] + 1, whole logits, no per-block argmax
+ * candidates): l2z_argmax, l2z_logits_read, l2z_probs_read, l2z_sample_batch, l2z_transformer_batch, l2z_verify* and
+ * l2z_runstate_fork go on from there.
+ * out_next != NULL: out_next[i] = the argmax of row i by l2z_argmax's rule (strict '>', the lowest index wins), taken on
+ * the device by the launch that hands out the logits; the call returns after one copy and one sync.  out_next == NULL: the
+ * call is asynchronous, as l2z_transformer_batch is.
+ * Streams: l2z_transformer_batch's rule -- the pass runs on states[0]'s stream after everything queued on every runstate's
+ * stream, and every runstate's stream waits for it; no device-wide sync.  The scratch is states[0]'s (freed with it).
+ * INVARIANCE.  For a fixed n and a fixed place i in the batch, row i's logits and KV row are bit-identical whatever the
+ * other rows' tokens, positions and caches hold and whatever stale rows lie beyond pos[i] in its own cache, and from run
+ * to run: the GEMMs compute each row from that row alone in an order fixed by the shape and n, no block of the step's own
+ * kernels touches two sequences, and the attention's orders depend on head_size, the segment and the row's own position
+ * only.  Nothing more is promised: n selects the GEMM form, so values across different n, and against
+ * l2z_transformer_batch / l2z_transformer, agree at the fp32 parity bar, not bit for bit.  l2z_transformer_batch stays the
+ * form for n <= L2Z_BATCH_MAX whenever bit-invariance across n matters.
+ * Sampled wide batches are out of scope: draw with l2z_sample_batch in groups of L2Z_BATCH_MAX runstates after the call.
+ * A refusal enqueues nothing and changes no state.  L2Z_ERR_INVALID: a NULL argument other than out_next, n outside
+ * [1, L2Z_WIDE_MAX], runstates that are not pairwise distinct, unsharded, on one device and made with *config, weights of
+ * another config, dims l2z_prefill refuses.  L2Z_ERR_STATE: a pos[i] outside [0, seq_len), a token outside the vocabulary.
+ * L2Z_ERR_NO_DEVICE without a device. */
+#define L2Z_WIDE_MAX 128
+int l2z_transformer_wide(int n, const int32_t *tokens, const int32_t *pos, const l2z_config *config,
+                         l2z_runstate *const *states, const l2z_weights *w, int32_t *out_next /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,6 +105,8 @@ def lib():
     L.l2z_runstate_fork.argtypes = [vp, vp, C.c_int]
     if hasattr(L, "l2z_prefill_batch"):
         L.l2z_prefill_batch.argtypes = [C.c_int, i32p, i32p, i32p, cfgp, C.POINTER(vp), vp]
+    if hasattr(L, "l2z_transformer_wide"):
+        L.l2z_transformer_wide.argtypes = [C.c_int, i32p, i32p, cfgp, C.POINTER(vp), vp, i32p]
     if hasattr(L, "l2z_verify_batch"):
         L.l2z_verify_batch.argtypes = [C.c_int, i32p, i32p, i32p, fp, fp, fp, cfgp, C.POINTER(vp), vp, i32p, i32p]
     if hasattr(L, "l2z_verify_tree"):
@@ -621,6 +623,36 @@ def prefill_batch(states, token_lists, pos0s, w: Weights) -> None:
     i32p = C.POINTER(C.c_int32)
     _chk(lib().l2z_prefill_batch(n, t.ctypes.data_as(i32p), nt.ctypes.data_as(i32p), p0.ctypes.data_as(i32p),
                                  C.byref(cfg), ss, w.h))
+
+
+WIDE_MAX = 128  # L2Z_WIDE_MAX
+
+
+def transformer_wide(states, tokens, pos, w: Weights, want_next: bool = True):
+    """l2z_transformer_wide: transformer(tokens[i], pos[i]) on states[i] for every i of up to WIDE_MAX runstates, one sweep
+    of the weights on the matrix cores (a preview entry point of the test library: include/llama2_hip_test.h).
+    want_next: returns every row's argmax (taken on the device; the call is synchronous); otherwise None, and the call is
+    asynchronous as transformer_batch is."""
+    n, ss, t, p = _batch_args(states, tokens, pos)
+    cfg = states[0].cfg if n else L2ZConfig()
+    i32p = C.POINTER(C.c_int32)
+    nxt = np.zeros(max(n, 1), np.int32) if want_next else None
+    _chk(lib().l2z_transformer_wide(n, t.ctypes.data_as(i32p), p.ctypes.data_as(i32p), C.byref(cfg), ss, w.h,
+                                    nxt.ctypes.data_as(i32p) if want_next else None))
+    return nxt[:n].copy() if want_next else None
+
+
+def generate_wide(states, first_tokens, pos0s, w: Weights, n_steps: int) -> np.ndarray:
+    """The greedy loop over transformer_wide: states[i] is fed first_tokens[i] at pos0s[i], then its own argmax, for n_steps
+    steps -- one call per step, no host argmax.  Returns the ids [n_steps, n] (row k = the tokens step k chose)."""
+    n = len(states)
+    tok = np.array(np.broadcast_to(np.asarray(first_tokens, np.int32), (n,)), np.int32)
+    pos = np.array(np.broadcast_to(np.asarray(pos0s, np.int32), (n,)), np.int32)
+    out = np.zeros((n_steps, n), np.int32)
+    for k in range(n_steps):
+        tok = transformer_wide(states, tok, pos + k, w)
+        out[k] = tok
+    return out
 
 
 def verify_batch(states, token_lists, pos0s, w: Weights, temperature=None, top_p=None, coin_lists=None):

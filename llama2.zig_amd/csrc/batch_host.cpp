@@ -134,9 +134,9 @@ int no_device_check()
     return L2Z_OK;
 }
 
-int check_states(const char *fn, int n, l2z_runstate *const *states, const l2z_config *c)
+int check_states(const char *fn, int n, l2z_runstate *const *states, const l2z_config *c, int n_max)
 {
-    L2Z_CHECK(n >= 1 && n <= kBatchMax, L2Z_ERR_INVALID, "%s: n = %d outside [1, %d]", fn, n, kBatchMax);
+    L2Z_CHECK(n >= 1 && n <= n_max, L2Z_ERR_INVALID, "%s: n = %d outside [1, %d]", fn, n, n_max);
     L2Z_CHECK(states != nullptr, L2Z_ERR_INVALID, "%s: null runstate array", fn);
     for (int i = 0; i < n; i++) {
         const l2z_runstate *s = states[i];

@@ -38,8 +38,8 @@ int verify_alloc(l2z_runstate *s);
 
 int no_device_check();
 // the runstates of one call: non-null, pairwise distinct, unsharded, on one device, all made with *c (c: states[0]'s
-// when the call names no config)
-int check_states(const char *fn, int n, l2z_runstate *const *states, const l2z_config *c);
+// when the call names no config), 1 <= n <= n_max
+int check_states(const char *fn, int n, l2z_runstate *const *states, const l2z_config *c, int n_max = kBatchMax);
 // the pass on states[0]'s stream waits for everything already queued on every runstate's stream ...
 int join_streams(BatchScratch *b, int n, l2z_runstate *const *states);
 // ... and every runstate's stream waits for the pass

@@ -319,6 +319,7 @@ hipError_t launch_prefill_attention(const float *q, int ldq, const float *kcache
                                     bool *planes_written = nullptr);  // ... if the form that ran writes them (the flash form does)
 // ---- prefill_ragged.hip: a chunk whose rows belong to SEVERAL sequences (l2z_prefill_batch; prefill_batch_host.cpp) ----
 constexpr int kRaggedMaxSeq = 16;   // L2Z_BATCH_MAX
+struct WideAttn;                    // wide_decode.h
 struct RaggedSeq {     // one sequence's rows of a chunk
     float *kc, *vc;    // its runstate's key / value caches (layer 0): [layer][kv head][seq_len][head_size]
     int row0, rows;    // its first row in the chunk, how many
@@ -335,6 +336,8 @@ struct RaggedChunk {
     const int2 *tiles;      // [n_tiles]
     int n_seq, n_tiles;
     float *k, *v;           // scratch: the chunk's key / value rows [P, kv_dim] between the product and the scatter
+    const WideAttn *wide;   // != null (l2z_transformer_wide): every row is a sequence of its own at one position -- the
+                            // attention is launch_wide_attention (wide_decode.h) on this table; tiles and n_tiles are not read
 };
 // q [P, dim] rotated in place, k rotated, and k / v stored into row row_pos[r] of sequence row_seq[r]'s caches: the
 // arithmetic of the q | k | v product's own epilogue (prefill_gemm.hip), one launch

@@ -12,6 +12,7 @@
 namespace l2z {
 
 struct BatchScratch;  // batch_host.h
+struct WideScratch;   // wide_host.cpp
 
 // ----- shard geometry (DESIGN.md "Sharding"; world == 1 -> everything local) -----
 struct Shard {
@@ -165,6 +166,7 @@ struct l2z_runstate {
     float *rg_k = nullptr, *rg_v = nullptr;
     void *rg_tab = nullptr;
     int rg_cap = 0;
+    l2z::WideScratch *wd = nullptr;   // l2z_transformer_wide scratch of the calls that name this runstate first (wide_host.cpp)
 };
 
 namespace l2z {
@@ -202,8 +204,12 @@ int prefill_tokens(l2z_runstate *s, const l2z_weights *w, const int32_t *tokens,
 int prefill_scratch(l2z_runstate *s, int need);
 int prefill_ragged_chunk(l2z_runstate *s, const l2z_weights *w, const int32_t *tokens, int P, const RaggedChunk &rg);
 int prefill_last_logits(l2z_runstate *s, const l2z_weights *w);
+// ... and with l2z_transformer_wide (wide_host.cpp): the classifier over all P rows of the chunk just run -> out [P, ldo]
+int prefill_rows_logits(l2z_runstate *s, const l2z_weights *w, int P, float *out, int ldo);
 
 // batch_host.cpp
 void batch_free(l2z_runstate *s);
+// wide_host.cpp
+void wide_free(l2z_runstate *s);
 
 }  // namespace l2z

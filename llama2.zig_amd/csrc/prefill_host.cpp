@@ -7,6 +7,7 @@
 
 #include "l2z_state.h"
 #include "prefill_common.h"
+#include "wide_decode.h"
 
 using namespace l2z;
 
@@ -208,8 +209,8 @@ int launch_w13(const Chunk &c, GemmArgs a, GemmLaunch &l)
 // The launches of stage k of layer l.  One rank: straight into the destination matrix.  Sharded: this
 // rank's [P, n_loc] block, contiguous, at pf_stage + rank * P * n_loc; the exchange and the unpack
 // into the destination follow (comm_bulk_allgather, or the emulated-rank driver's copies).
-// rg != null (l2z_prefill_batch): the rows belong to several sequences, which only the q | k | v epilogue and the attention
-// see (below); pos0 is not read.
+// rg != null (l2z_prefill_batch; l2z_transformer_wide with rg->wide set): the rows belong to several sequences, which only the
+// q | k | v epilogue and the attention see (below); pos0 is not read.
 int prefill_stage(l2z_runstate *s, const l2z_weights *w, int l, int k, int P, int pos0, const RaggedChunk *rg = nullptr)
 {
     const l2z_config &c = s->cfg;
@@ -318,8 +319,12 @@ int prefill_stage(l2z_runstate *s, const l2z_weights *w, int l, int k, int P, in
         L2Z_HIP(launch_ragged_rope_scatter(s->pf_q, dim, *rg, P, dim, kvd, hs, s->rope, layer_off, kvh_stride, st));
         bool att_planes = false;
         const bool want = planes_for(dim, dim, sk_wo);
-        L2Z_HIP(launch_ragged_attention(s->pf_q, dim, out, ldo, *rg, P, c.n_heads, hs, layer_off, kvh_stride,
-                                        c.n_heads / c.n_kv_heads, c.seq_len, st, want ? ws->x3 : nullptr, dim, &att_planes));
+        if (rg->wide != nullptr)   // one row per sequence: the position-split decode attention (wide_decode.hip)
+            L2Z_HIP(launch_wide_attention(s->pf_q, dim, out, ldo, *rg->wide, P, c.n_heads, hs, layer_off, kvh_stride,
+                                          c.n_heads / c.n_kv_heads, st, want ? ws->x3 : nullptr, dim, &att_planes));
+        else
+            L2Z_HIP(launch_ragged_attention(s->pf_q, dim, out, ldo, *rg, P, c.n_heads, hs, layer_off, kvh_stride,
+                                            c.n_heads / c.n_kv_heads, c.seq_len, st, want ? ws->x3 : nullptr, dim, &att_planes));
         s->pf_planes_att = att_planes ? PLANES_READY : PLANES_SPLIT;
     } else if (k == PF_ATT) {
         const QkvProduct qp = {s->pf_xn, ldxn, dim, w->wq + (size_t)l * sh.dim_loc * dim, w->wk + (size_t)l * kvd * dim,
@@ -537,6 +542,18 @@ int score_alloc(l2z_runstate *s, int need)
     return L2Z_OK;
 }
 
+// Vocabulary columns per slab of the classifier product of a chunk of P rows, at most `cols` (a multiple of kScoreSeg): chunks
+// the split forms take must fit a slab's K ranges' sums into the split-K workspace (sized for the layers' launches)
+int slab_cols_that_fit(const l2z_runstate *s, int P, int sk, int kp, int cols)
+{
+    if (P > kSplitKMaxTokens) return cols;
+    const int V = s->cfg.vocab_size;
+    const size_t ranges = (size_t)std::max(sk, x3_stream_shape(V, P, kp) ? x3_stream_sk(V, P, kp) : 1);
+    const size_t rows = (size_t)(P + 127) / 128 * 128;
+    while (cols > kScoreSeg && ((size_t)cols + 256) * ranges * rows > s->pf_sk.part_floats) cols -= kScoreSeg;
+    return cols;
+}
+
 int score_chunk(l2z_runstate *s, const l2z_weights *w, const ScoreCall *sc, int done, int P)
 {
     const l2z_config &c = s->cfg;
@@ -547,13 +564,7 @@ int score_chunk(l2z_runstate *s, const l2z_weights *w, const ScoreCall *sc, int 
     L2Z_HIP(launch_prefill_rmsnorm(s->pf_xn, ldxn, s->pf_x, w->rms_final, dim, P, st));   // :426, all rows
     const int kp = (dim + 63) / 64 * 64;
     const int sk = prefill_split_k(V, P, kp, false);
-    // chunks the split forms take: a slab's K ranges' sums must fit the split-K workspace (sized for the layers' launches)
-    int cols = s->sc_slab_n;
-    if (P <= kSplitKMaxTokens) {
-        const size_t ranges = (size_t)std::max(sk, x3_stream_shape(V, P, kp) ? x3_stream_sk(V, P, kp) : 1);
-        const size_t rows = (size_t)(P + 127) / 128 * 128;
-        while (cols > kScoreSeg && ((size_t)cols + 256) * ranges * rows > s->pf_sk.part_floats) cols -= kScoreSeg;
-    }
+    const int cols = slab_cols_that_fit(s, P, sk, kp, s->sc_slab_n);
     float *slab = (float *)s->sc_ws;
     ScoreArgs a = {};
     a.slab = slab; a.ld = s->sc_slab_n; a.P = P; a.nseg = nseg;
@@ -583,6 +594,31 @@ int score_chunk(l2z_runstate *s, const l2z_weights *w, const ScoreCall *sc, int 
 }  // namespace
 
 namespace l2z {
+
+// l2z_transformer_wide: the logits of ALL P rows of the chunk the layers just finished, as score_chunk's step 1 and 2 --
+// final rmsnorm into pf_xn, then the classifier by launch_prefill_gemm(PG_STORE) with the whole vocabulary as
+// n_launch_whole -- into out [P, ldo], in as few vocabulary slabs as the split-K workspace allows (score_chunk's rule).
+int prefill_rows_logits(l2z_runstate *s, const l2z_weights *w, int P, float *out, int ldo)
+{
+    const l2z_config &c = s->cfg;
+    hipStream_t st = s->stream;
+    const int dim = c.dim, V = c.vocab_size, ldxn = s->pf_ld_xn;
+    L2Z_CHECK(!s->pf_pending.valid, L2Z_ERR_INVALID, "l2z_transformer_wide: the last layer left its residual product's sums behind");
+    L2Z_HIP(launch_prefill_rmsnorm(s->pf_xn, ldxn, s->pf_x, w->rms_final, dim, P, st));   // :426, all rows
+    const int kp = (dim + 63) / 64 * 64;
+    const int sk = prefill_split_k(V, P, kp, false);
+    const int cols = slab_cols_that_fit(s, P, sk, kp, score_nseg(c) * kScoreSeg);
+    const Chunk ch = chunk_of(s, P, 0);
+    GemmLaunch gl = launch_of(ch, sk);
+    gl.n_launch_whole = V;
+    for (int col0 = 0; col0 < V; col0 += cols) {
+        GemmArgs g = product(ch, s->pf_xn, ldxn, w->wcls + (size_t)col0 * dim, dim, std::min(cols, V - col0), dim);
+        g.out = out + col0; g.ldo = ldo;
+        L2Z_HIP(launch_prefill_gemm(GEMM_SINGLE, PG_STORE, g, gl, st));
+        gl.planes_ready = PLANES_READY;   // (the first slab's launch cut the rows into their planes)
+    }
+    return L2Z_OK;
+}
 
 // Row-sharded == unsharded bit for bit needs every rank to take the kernel -- the summation order -- the unsharded
 // pass takes.  The one kernel with a per-rank shape condition is the K-range panel kernel (a wave's 16 rows lie in one

@@ -181,6 +181,7 @@ extern "C" void l2z_runstate_free(l2z_runstate *s)
     if (s->h_stage) (void)hipHostFree(s->h_stage);
     if (s->h_smp_ctl) (void)hipHostFree(s->h_smp_ctl);
     l2z::batch_free(s);
+    l2z::wide_free(s);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }

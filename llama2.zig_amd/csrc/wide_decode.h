@@ -1,0 +1,61 @@
+// wide_decode.h -- the kernels l2z_transformer_wide adds to the ragged prompt pass (wide_decode.hip; host side
+// wide_host.cpp, prefill_host.cpp): decode attention for up to kWideMax one-query sequences, each on its own cache, and
+// the launch that hands the [n, vocab] logits matrix back to the runstates.  Every row's token, position, caches and
+// logits come from one device table.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "batch_decode.h"
+#include "l2z_internal.h"
+
+namespace l2z {
+
+constexpr int kWideMax = 128;  // L2Z_WIDE_MAX
+
+// What the host uploads before a step, in one copy from a pinned buffer.  The first three arrays are the table
+// launch_ragged_rope_scatter reads (RaggedChunk: kWideMax sequence slots of one row each, row i = slot i); cache bases are
+// layer 0's.
+struct WideTable {
+    RaggedSeq seq[kWideMax];      // kc, vc of row i's runstate; row0 = i, rows = 1, pos0 = pos[i]
+    int32_t row_seq[kWideMax];    // i
+    int32_t pos[kWideMax];
+    int32_t tokens[kWideMax];
+    float *logits[kWideMax];
+};
+
+// Segments of kVerifySeg ABSOLUTE positions, the verify family's scheme: segment s = positions [s * kVerifySeg,
+// (s + 1) * kVerifySeg) whatever n and the positions are.
+// Partials of one step: [kWideMax, n_heads, seg_cap, head_size] sums, then [kWideMax, n_heads, seg_cap, 2] (max, sum e),
+// in one allocation of kWideMax * n_heads * seg_cap * (head_size + 2) floats.
+inline size_t wide_part_floats(int n_heads, int seg_cap, int head_size)
+{
+    return (size_t)kWideMax * n_heads * seg_cap * ((size_t)head_size + 2);
+}
+struct WideAttn {
+    const WideTable *tab;  // device
+    float *part;           // wide_part_floats
+    int seg_cap;           // verify_segments(seq_len)
+    int n_seg;             // segments of the deepest row of this step: the grid's extent
+};
+
+// Decode attention (main.zig:361-389) of rows 0 .. n - 1 of q [n, ldq] (RoPE applied) into out [n, ldo], two launches:
+//   wide_attention: block (kv head, segment, row) reads the segment's K and V rows of that kv head ONCE and serves all
+//     kv_mul query heads of it (up to 4 per block; beyond, blocks of 4); a block past its row's last segment returns.  It
+//     leaves the flash partials (max, sum e, sum e v) per (row, head, segment).
+//   wide_combine: block (head, row) folds the row's segments in segment order, divides, and writes out -- and, x3 != null,
+//     out's planes of bf16 terms x3[row][3][kp] (the Wo product's operand; *planes_written says whether it did).
+// head_size: a multiple of 4 up to 256.  Every summation order is a function of head_size, the segment and the row's own
+// position only; no block touches two sequences.  Keys beyond pos[i] are never read.
+hipError_t launch_wide_attention(const float *q, int ldq, float *out, int ldo, const WideAttn &wa, int n, int n_heads,
+                                 int head_size, size_t layer_off, size_t kv_head_stride, int kv_mul, hipStream_t st,
+                                 void *x3 = nullptr, int kp = 0, bool *planes_written = nullptr);
+
+// Row i of logits [n, ld] -> tab->logits[i][0 .. vocab) (float4 where both sides are 16-byte aligned), and, next != null,
+// next[i] = the row's argmax by argmax_rule.h (strict '>', lowest index wins).  One launch, one block per row.
+hipError_t launch_wide_logits_out(const float *logits, int ld, const WideTable *tab, int vocab, int *next, int n,
+                                  hipStream_t st);
+
+}  // namespace l2z
