@@ -374,7 +374,8 @@ int l2z_sample_run(const l2z_config *config, l2z_runstate *s, const l2z_weights 
  * only.  Nothing more is promised: n selects the GEMM form, so values across different n, and against
  * l2z_transformer_batch / l2z_transformer, agree at the fp32 parity bar, not bit for bit.  l2z_transformer_batch stays the
  * form for n <= L2Z_BATCH_MAX whenever bit-invariance across n matters.
- * Sampled wide batches are out of scope: draw with l2z_sample_batch in groups of L2Z_BATCH_MAX runstates after the call.
+ * The step itself draws nothing but the argmax: draw with l2z_sample_batch in groups of L2Z_BATCH_MAX runstates after the
+ * call, or run the steps and their draws on the device with l2z_wide_run (below).
  * A refusal enqueues nothing and changes no state.  L2Z_ERR_INVALID: a NULL argument other than out_next, n outside
  * [1, L2Z_WIDE_MAX], runstates that are not pairwise distinct, unsharded, on one device and made with *config, weights of
  * another config, dims l2z_prefill refuses.  L2Z_ERR_STATE: a pos[i] outside [0, seq_len), a token outside the vocabulary.
@@ -382,6 +383,38 @@ int l2z_sample_run(const l2z_config *config, l2z_runstate *s, const l2z_weights 
 #define L2Z_WIDE_MAX 128
 int l2z_transformer_wide(int n, const int32_t *tokens, const int32_t *pos, const l2z_config *config,
                          l2z_runstate *const *states, const l2z_weights *w, int32_t *out_next /* may be NULL */);
+
+/* ---- wide generation loop on the device (preview) ----
+ * n_steps consecutive l2z_transformer_wide steps of the same n runstates in ONE call, every row's token drawn on the
+ * device and handed to the next step there.  Step k (k = 0 .. n_steps - 1) runs transformer(tok_k[i], pos0[i] + k) on
+ * states[i] exactly as l2z_transformer_wide runs it at that n; tok_0 = first_tokens, tok_{k+1}[i] = out_tokens[k * n + i],
+ * and out_tokens[k * n + i] is the token l2z_sample_batch draws from that row's logits with (temperature[i], top_p[i],
+ * coins[k * n + i]) -- the same device code, so the host samplers' bits.  Where temperature[i] == 0, or temperature ==
+ * NULL (every row greedy; top_p and coins are not read), it is the argmax by l2z_argmax's rule and the coin is not read.
+ * THE DEFINING PROPERTY: the ids, every row's final logits and every cache row are bit-identical to the step loop on the
+ * same states -- l2z_transformer_wide(n, tok_k, pos0 + k, ..., NULL), then l2z_sample_batch over the runstates in groups
+ * of L2Z_BATCH_MAX, for each k: the run issues each step's own launches, its attention grid sized by that step's own
+ * deepest position.
+ * On return KV rows pos0[i] .. pos0[i] + n_steps - 1 of every layer of states[i] are written -- and NO other cache row of
+ * any runstate --, states[i]'s logits are its last step's, and the host bookkeeping is as l2z_transformer_wide leaves it
+ * after the last step (next position pos0[i] + n_steps, whole logits, no per-block argmax candidates): every other entry
+ * point can go on from there.
+ * Nothing stops a row on the device: a row that draws BOS keeps running and the caller discards what follows it, as
+ * l2z_sample_run's caller does within a chunk; the context limit is the caller's to keep (below).
+ * The call is synchronous: the run waits for every runstate's stream once at its start, every runstate's stream waits
+ * for it once at its end, and the call returns after one copy of the ids and one sync; no device-wide sync.  The scratch
+ * is states[0]'s (freed with it); the sampler's (5 * vocab floats for each of L2Z_WIDE_MAX rows) is allocated on the
+ * first call with a positive temperature -- runs that are all greedy allocate none.
+ * A refusal enqueues nothing and changes no state.  L2Z_ERR_INVALID: everything l2z_transformer_wide refuses so,
+ * n_steps < 1, NULL first_tokens, pos0 or out_tokens, a temperature that is not finite and >= 0, a top_p outside [0, 1]
+ * or top_p == NULL beside temperature, coins == NULL with any temperature[i] > 0, a coin of such a row (all n_steps of
+ * them) outside [0, 1).  L2Z_ERR_STATE: a pos0[i] < 0 or pos0[i] + n_steps > seq_len, a first token outside the
+ * vocabulary.  L2Z_ERR_NO_DEVICE without a device. */
+int l2z_wide_run(int n, const int32_t *first_tokens, const int32_t *pos0, int n_steps,
+                 const float *temperature /* [n], or NULL: all greedy */, const float *top_p /* [n] */,
+                 const float *coins /* [n_steps, n], row-major by step */,
+                 const l2z_config *config, l2z_runstate *const *states, const l2z_weights *w,
+                 int32_t *out_tokens /* [n_steps, n] */);
 
 #ifdef __cplusplus
 }

@@ -107,6 +107,8 @@ def lib():
         L.l2z_prefill_batch.argtypes = [C.c_int, i32p, i32p, i32p, cfgp, C.POINTER(vp), vp]
     if hasattr(L, "l2z_transformer_wide"):
         L.l2z_transformer_wide.argtypes = [C.c_int, i32p, i32p, cfgp, C.POINTER(vp), vp, i32p]
+    if hasattr(L, "l2z_wide_run"):
+        L.l2z_wide_run.argtypes = [C.c_int, i32p, i32p, C.c_int, fp, fp, fp, cfgp, C.POINTER(vp), vp, i32p]
     if hasattr(L, "l2z_verify_batch"):
         L.l2z_verify_batch.argtypes = [C.c_int, i32p, i32p, i32p, fp, fp, fp, cfgp, C.POINTER(vp), vp, i32p, i32p]
     if hasattr(L, "l2z_verify_tree"):
@@ -652,6 +654,53 @@ def generate_wide(states, first_tokens, pos0s, w: Weights, n_steps: int) -> np.n
     for k in range(n_steps):
         tok = transformer_wide(states, tok, pos + k, w)
         out[k] = tok
+    return out
+
+
+def wide_run(states, first_tokens, pos0s, w: Weights, n_steps: int, temperature=None, top_p=None, coins=None) -> np.ndarray:
+    """l2z_wide_run: n_steps transformer_wide steps of the same runstates in ONE call, every row's token drawn on the device
+    as sample_batch draws it and fed to the next step there (a preview entry point of the test library:
+    include/llama2_hip_test.h).  states[i] is fed first_tokens[i] at pos0s[i].  temperature=None: every row takes its
+    argmax; otherwise temperature and top_p are one value per row (or a scalar for all) and coins is [n_steps, n] (or a
+    scalar, or one row per step broadcast over the rows; None where every temperature is 0).
+    Returns the ids [n_steps, n] (row k = the tokens step k drew), bit for bit those of the loop of transformer_wide and
+    sample_batch calls."""
+    n = len(states)
+    ss = (C.c_void_p * max(n, 1))(*[s.h for s in states])
+    steps = max(int(n_steps), 0)
+
+    def per_row(v, dtype):
+        a = np.zeros(max(n, 1), dtype)
+        a[:n] = np.broadcast_to(np.asarray(v, dtype), (n,)) if n else []
+        return a
+    tok, pos = per_row(first_tokens, np.int32), per_row(pos0s, np.int32)
+    t = p = c = None
+    if temperature is not None:
+        t = per_row(temperature, np.float32)
+        p = per_row(top_p, np.float32) if top_p is not None else None
+        if coins is not None:
+            c = np.zeros((max(steps, 1), max(n, 1)), np.float32)
+            c[:steps, :n] = np.broadcast_to(np.asarray(coins, np.float32), (steps, n))
+    out = np.zeros((max(steps, 1), max(n, 1)), np.int32)
+    cfg = states[0].cfg if n else L2ZConfig()
+    i32p = C.POINTER(C.c_int32)
+    _chk(lib().l2z_wide_run(n, tok.ctypes.data_as(i32p), pos.ctypes.data_as(i32p), int(n_steps),
+                            _fp(t) if t is not None else None, _fp(p) if p is not None else None,
+                            _fp(c) if c is not None else None, C.byref(cfg), ss, w.h, out.ctypes.data_as(i32p)))
+    return out[:steps, :n].copy()   # (n >= 1 here: the rows are n wide, as the call wrote them)
+
+
+def generate_wide_sample(states, first_tokens, pos0s, w: Weights, n_steps: int, temperature=None, top_p=None, coins=None,
+                         bos: int = 1):
+    """The convenience loop over wide_run: one call, then every column cut after its first BOS (main.zig:1038-1040; the
+    device stops no row, what a row drew after its BOS is discarded here).  Returns a list of n int32 arrays, sequence
+    i's tokens up to and including its BOS if it drew one."""
+    ids = wide_run(states, first_tokens, pos0s, w, n_steps, temperature, top_p, coins)
+    out = []
+    for i in range(ids.shape[1]):
+        col = ids[:, i]
+        hit = np.flatnonzero(col == bos)
+        out.append(col[:hit[0] + 1].copy() if hit.size else col.copy())
     return out
 
 

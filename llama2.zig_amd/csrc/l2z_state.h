@@ -166,7 +166,7 @@ struct l2z_runstate {
     float *rg_k = nullptr, *rg_v = nullptr;
     void *rg_tab = nullptr;
     int rg_cap = 0;
-    l2z::WideScratch *wd = nullptr;   // l2z_transformer_wide scratch of the calls that name this runstate first (wide_host.cpp)
+    l2z::WideScratch *wd = nullptr;   // l2z_transformer_wide / l2z_wide_run scratch of the calls that name this runstate first (wide_host.cpp)
 };
 
 namespace l2z {
@@ -200,7 +200,9 @@ int prefill_tokens(l2z_runstate *s, const l2z_weights *w, const int32_t *tokens,
                    const ScoreCall *score = nullptr);
 
 // ... what l2z_prefill_batch shares with l2z_prefill (prefill_batch_host.cpp): the chunk scratch, one chunk's layers with
-// the rows' sequences given by the table (every stage but q | k | v + attention is l2z_prefill's own), the classifier launch
+// the rows' sequences given by the table (every stage but q | k | v + attention is l2z_prefill's own), the classifier launch.
+// tokens: the chunk's ids on the host, copied into pf_tokens first; null (l2z_wide_run from its second step on): they
+// already stand in pf_tokens on the device, and the chunk makes no host-to-device copy
 int prefill_scratch(l2z_runstate *s, int need);
 int prefill_ragged_chunk(l2z_runstate *s, const l2z_weights *w, const int32_t *tokens, int P, const RaggedChunk &rg);
 int prefill_last_logits(l2z_runstate *s, const l2z_weights *w);

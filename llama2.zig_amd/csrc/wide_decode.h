@@ -1,7 +1,8 @@
 // wide_decode.h -- the kernels l2z_transformer_wide adds to the ragged prompt pass (wide_decode.hip; host side
 // wide_host.cpp, prefill_host.cpp): decode attention for up to kWideMax one-query sequences, each on its own cache, and
 // the launch that hands the [n, vocab] logits matrix back to the runstates.  Every row's token, position, caches and
-// logits come from one device table.
+// logits come from one device table.  And the last launch of a step inside l2z_wide_run (wide_sample.hip): every row's
+// draw, and the hand-over of token and position to the next step on the device.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -57,5 +58,25 @@ hipError_t launch_wide_attention(const float *q, int ldq, float *out, int ldo, c
 // next[i] = the row's argmax by argmax_rule.h (strict '>', lowest index wins).  One launch, one block per row.
 hipError_t launch_wide_logits_out(const float *logits, int ld, const WideTable *tab, int vocab, int *next, int n,
                                   hipStream_t st);
+
+// The last launch of one step of l2z_wide_run (wide_sample.hip), one block of 1024 threads per row: row i's token is drawn
+// from row i of logits [n, ld] by the sampler's row body (sample_device.h: the token l2z_sample_batch draws from the same
+// logits with temperature[i], top_p[i], coins[i]; the argmax by argmax_rule.h at temperature 0, the coin not read), stored
+// in ids[i], and the row is handed to the next step on the device: the token into tokens[i] (the embed launch's array),
+// tab->pos[i] and tab->seq[i].pos0 moved on by one.  logits_out (the run's last step): the row goes to tab->logits[i] as
+// launch_wide_logits_out copies it.
+struct WideDraw {
+    const float *logits;
+    int ld, vocab;
+    WideTable *tab;
+    const float *temperature, *top_p;  // [n]; temperature null: every row takes the argmax
+    const float *coins;                // [n], this step's; read where temperature[i] > 0
+    float *scratch;                    // row_stride floats per row, sample_scratch_floats(vocab) at least; null: all greedy
+    size_t row_stride;
+    int *ids;                          // [n], this step's
+    int *tokens;                       // [n]
+    bool logits_out;
+};
+hipError_t launch_wide_draw_advance(const WideDraw &d, int n, hipStream_t st);
 
 }  // namespace l2z

@@ -1,8 +1,11 @@
-// wide_host.cpp -- host side of l2z_transformer_wide (include/llama2_hip_test.h): up to L2Z_WIDE_MAX independent sequences
-// advanced by one token with one sweep of the weights.  The rows are ONE chunk of P = n rows of the ragged prompt pass
-// (prefill_host.cpp) on states[0]'s prefill scratch and stream, so every product takes the whole model's form at that row
-// count (short-prompt / panel / stream / tile, f32 or bf16 cores); what the step adds is the table with one sequence slot
-// per row, the position-split decode attention and the launch that hands the [n, vocab] logits back (wide_decode.hip).
+// wide_host.cpp -- host side of l2z_transformer_wide and l2z_wide_run (include/llama2_hip_test.h): up to L2Z_WIDE_MAX
+// independent sequences advanced by one token with one sweep of the weights, and the loop of such steps kept on the device.
+// The rows are ONE chunk of P = n rows of the ragged prompt pass (prefill_host.cpp) on states[0]'s prefill scratch and
+// stream, so every product takes the whole model's form at that row count (short-prompt / panel / stream / tile, f32 or
+// bf16 cores); what the step adds is the table with one sequence slot per row, the position-split decode attention and its
+// last launch: the one that hands the [n, vocab] logits back (wide_decode.hip), or, inside a run, the one that draws every
+// row's token and hands the row to the next step (wide_sample.hip).
+#include <cmath>
 #include <cstring>
 
 #include "batch_host.h"
@@ -27,17 +30,24 @@ struct WideScratch {
     hipEvent_t ev_in[kWideMax] = {};
     hipEvent_t ev_done = nullptr;
     hipEvent_t ev_upload = nullptr;     // the last table copy: the pinned table may be rewritten once it has completed
+    // l2z_wide_run (each on the first call that needs it): a call's temperature | top_p ([kWideMax] each) | coins and its
+    // ids, [n_steps, n] both, on the device and pinned, sized on demand; the sampler's scratch of kWideMax rows
+    float *d_ctl = nullptr, *h_ctl = nullptr;
+    int *d_ids = nullptr, *h_ids = nullptr;
+    size_t run_cap = 0;                 // entries of coins / ids the four buffers hold
+    float *smp = nullptr;               // kWideMax rows of sample_scratch_floats(vocab)
 };
 
 void wide_free(l2z_runstate *s)
 {
     WideScratch *b = s->wd;
     if (b == nullptr) return;
-    void *ptrs[] = {b->k, b->v, b->logits, b->part, b->d_next, b->d_tab};
+    void *ptrs[] = {b->k, b->v, b->logits, b->part, b->d_next, b->d_tab, b->d_ctl, b->d_ids, b->smp};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
-    if (b->h_next) (void)hipHostFree(b->h_next);
-    if (b->h_tab) (void)hipHostFree(b->h_tab);
+    void *pinned[] = {b->h_next, b->h_tab, b->h_ctl, b->h_ids};
+    for (void *p : pinned)
+        if (p) (void)hipHostFree(p);
     for (hipEvent_t e : b->ev_in)
         if (e) (void)hipEventDestroy(e);
     if (b->ev_done) (void)hipEventDestroy(b->ev_done);
@@ -86,6 +96,121 @@ int wide_alloc(l2z_runstate *s)
     return rc;
 }
 
+
+// what an l2z_wide_run call of `entries` = n_steps * n ids needs beyond the step's own; sampled: the row body's scratch too
+int run_alloc(l2z_runstate *s, size_t entries, bool sampled)
+{
+    WideScratch *b = s->wd;
+    auto fail = [](const char *what, size_t bytes, hipError_t e) {
+        set_error("l2z_wide_run %s allocation (%zu bytes) failed: %s", what, bytes, hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
+    };
+    if (entries > b->run_cap) {
+        // (every earlier run has completed: the call is synchronous)
+        if (b->d_ctl) (void)hipFree(b->d_ctl);
+        if (b->d_ids) (void)hipFree(b->d_ids);
+        if (b->h_ctl) (void)hipHostFree(b->h_ctl);
+        if (b->h_ids) (void)hipHostFree(b->h_ids);
+        b->d_ctl = b->h_ctl = nullptr;
+        b->d_ids = b->h_ids = nullptr;
+        b->run_cap = 0;
+        const size_t cap = (entries + 4095) / 4096 * 4096, ctl = (2 * (size_t)kWideMax + cap) * 4;
+        hipError_t e = hipMalloc((void **)&b->d_ctl, ctl);
+        if (e == hipSuccess) e = hipMalloc((void **)&b->d_ids, cap * 4);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_ctl, ctl, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_ids, cap * 4, hipHostMallocDefault);
+        if (e != hipSuccess) return fail("coins / ids", ctl + cap * 4, e);  // (what was allocated is freed on the next attempt)
+        b->run_cap = cap;
+    }
+    if (sampled && b->smp == nullptr) {
+        const size_t bytes = (size_t)kWideMax * sample_scratch_floats(s->cfg.vocab_size) * 4;
+        const hipError_t e = hipMalloc((void **)&b->smp, bytes);
+        if (e != hipSuccess) {
+            b->smp = nullptr;
+            return fail("sampler scratch", bytes, e);
+        }
+    }
+    return L2Z_OK;
+}
+
+// The checks both entry points share: the runstates, the weights, and every row's first token and its positions
+// pos[i] .. pos[i] + n_steps - 1.  *deepest: the deepest first position.
+int wide_checks(const char *fn, int n, const int32_t *tokens, const int32_t *pos, int n_steps, const l2z_config *config,
+                l2z_runstate *const *states, const l2z_weights *w, int *deepest)
+{
+    L2Z_CHECK(tokens != nullptr && pos != nullptr && config != nullptr && w != nullptr, L2Z_ERR_INVALID, "%s: null argument", fn);
+    L2Z_TRY(check_states(fn, n, states, config, kWideMax));
+    *deepest = 0;
+    for (int i = 0; i < n; i++) {
+        L2Z_TRY(check_pair(config, states[i], w));
+        L2Z_CHECK(pos[i] >= 0 && pos[i] <= config->seq_len - n_steps, L2Z_ERR_STATE, "%s: pos[%d] = %d, %d step(s) outside [0,%d)",
+                  fn, i, pos[i], n_steps, config->seq_len);
+        L2Z_CHECK(tokens[i] >= 0 && tokens[i] < config->vocab_size, L2Z_ERR_STATE, "%s: tokens[%d] = %d out of vocabulary", fn, i,
+                  tokens[i]);
+        if (pos[i] > *deepest) *deepest = pos[i];
+    }
+    return prefill_check(config, states[0]);
+}
+
+// the pass on states[0]'s stream waits for every runstate's stream ...
+int wide_join(WideScratch *b, int n, l2z_runstate *const *states)
+{
+    for (int i = 1; i < n; i++) {
+        L2Z_HIP(hipEventRecord(b->ev_in[i], states[i]->stream));
+        L2Z_HIP(hipStreamWaitEvent(states[0]->stream, b->ev_in[i], 0));
+    }
+    return L2Z_OK;
+}
+
+// ... and every runstate's stream waits for the pass; the host bookkeeping of a runstate whose next position is pos[i] + steps
+int wide_release(WideScratch *b, int n, l2z_runstate *const *states, const int32_t *pos, int steps)
+{
+    L2Z_HIP(hipEventRecord(b->ev_done, states[0]->stream));
+    for (int i = 1; i < n; i++) L2Z_HIP(hipStreamWaitEvent(states[i]->stream, b->ev_done, 0));
+    for (int i = 0; i < n; i++) {
+        l2z_runstate *s = states[i];
+        s->n_part = 0;  // l2z_argmax scans the logits: the classifier left no per-block candidates
+        s->logits_partial = false;
+        s->host_pos = pos[i] + steps;
+    }
+    return L2Z_OK;
+}
+
+// the table of a step (a run: of its first step), one copy from the pinned buffer (rewritten only once the last copy is done)
+int wide_upload_table(WideScratch *b, int n, const int32_t *tokens, const int32_t *pos, l2z_runstate *const *states)
+{
+    L2Z_HIP(hipEventSynchronize(b->ev_upload));
+    WideTable *t = b->h_tab;
+    for (int i = 0; i < n; i++) {
+        t->seq[i] = {states[i]->key_cache, states[i]->value_cache, i, 1, pos[i], 0};
+        t->row_seq[i] = i;
+        t->pos[i] = pos[i];
+        t->tokens[i] = tokens[i];
+        t->logits[i] = states[i]->logits;
+    }
+    L2Z_HIP(hipMemcpyAsync(b->d_tab, t, sizeof(WideTable), hipMemcpyHostToDevice, states[0]->stream));
+    return L2Z_OK;
+}
+
+// The launches of ONE step of n rows on s0's stream, the same for both entry points: the rows as one chunk of the ragged
+// prompt pass driven by the device table (deepest: the step's deepest position, the attention grid's segment extent),
+// the classifier over all rows into b->logits, then the step's last launch.  from_table: the rows' ids go up from the
+// pinned table (the caller's array is free on return); otherwise they stand in pf_tokens, written by the step before.
+int wide_step(l2z_runstate *s0, const l2z_weights *w, int n, int deepest, bool from_table, FnRef<int()> last)
+{
+    WideScratch *b = s0->wd;
+    WideAttn wa = {b->d_tab, b->part, b->seg_cap, deepest / kVerifySeg + 1};
+    RaggedChunk rg = {};
+    rg.seq = b->d_tab->seq; rg.row_seq = b->d_tab->row_seq; rg.row_pos = b->d_tab->pos;
+    rg.n_seq = n;
+    rg.k = b->k; rg.v = b->v;
+    rg.wide = &wa;
+    L2Z_TRY(prefill_ragged_chunk(s0, w, from_table ? b->h_tab->tokens : nullptr, n, rg));
+    if (from_table) L2Z_HIP(hipEventRecord(b->ev_upload, s0->stream));
+    L2Z_TRY(prefill_rows_logits(s0, w, n, b->logits, b->ld_logits));
+    return last();
+}
+
 }  // namespace
 }  // namespace l2z
 
@@ -96,67 +221,96 @@ extern "C" int l2z_transformer_wide(int n, const int32_t *tokens, const int32_t 
 {
     // ---- checks: a refusal enqueues nothing and changes no state ----
     L2Z_TRY(no_device_check());
-    L2Z_CHECK(tokens != nullptr && pos != nullptr && config != nullptr && w != nullptr, L2Z_ERR_INVALID,
-              "l2z_transformer_wide: null argument");
-    L2Z_TRY(check_states("l2z_transformer_wide", n, states, config, kWideMax));
     int deepest = 0;
-    for (int i = 0; i < n; i++) {
-        L2Z_TRY(check_pair(config, states[i], w));
-        L2Z_CHECK(pos[i] >= 0 && pos[i] < config->seq_len, L2Z_ERR_STATE, "l2z_transformer_wide: pos[%d] = %d outside [0,%d)", i,
-                  pos[i], config->seq_len);
-        L2Z_CHECK(tokens[i] >= 0 && tokens[i] < config->vocab_size, L2Z_ERR_STATE,
-                  "l2z_transformer_wide: tokens[%d] = %d out of vocabulary", i, tokens[i]);
-        if (pos[i] > deepest) deepest = pos[i];
-    }
-    L2Z_TRY(prefill_check(config, states[0]));
+    L2Z_TRY(wide_checks("l2z_transformer_wide", n, tokens, pos, 1, config, states, w, &deepest));
     l2z_runstate *s0 = states[0];
     hipStream_t st = s0->stream;
-    const l2z_config &c = *config;
     L2Z_HIP(hipSetDevice(s0->device));
     L2Z_TRY(prefill_scratch(s0, n));
     L2Z_TRY(wide_alloc(s0));
     WideScratch *b = s0->wd;
 
-    // ---- the pass, on states[0]'s stream: it waits for every runstate's stream ... ----
-    for (int i = 1; i < n; i++) {
-        L2Z_HIP(hipEventRecord(b->ev_in[i], states[i]->stream));
-        L2Z_HIP(hipStreamWaitEvent(st, b->ev_in[i], 0));
-    }
-    // the step's table, one copy from the pinned buffer (rewritten only once the last copy is done)
-    L2Z_HIP(hipEventSynchronize(b->ev_upload));
-    WideTable *t = b->h_tab;
-    for (int i = 0; i < n; i++) {
-        t->seq[i] = {states[i]->key_cache, states[i]->value_cache, i, 1, pos[i], 0};
-        t->row_seq[i] = i;
-        t->pos[i] = pos[i];
-        t->tokens[i] = tokens[i];
-        t->logits[i] = states[i]->logits;
-    }
-    L2Z_HIP(hipMemcpyAsync(b->d_tab, t, sizeof(WideTable), hipMemcpyHostToDevice, st));
-    WideAttn wa = {b->d_tab, b->part, b->seg_cap, deepest / kVerifySeg + 1};
-    RaggedChunk rg = {};
-    rg.seq = b->d_tab->seq; rg.row_seq = b->d_tab->row_seq; rg.row_pos = b->d_tab->pos;
-    rg.n_seq = n;
-    rg.k = b->k; rg.v = b->v;
-    rg.wide = &wa;
-    // (the chunk's tokens go up from the pinned table too: the caller's array is free on return)
-    L2Z_TRY(prefill_ragged_chunk(s0, w, t->tokens, n, rg));
-    L2Z_HIP(hipEventRecord(b->ev_upload, st));
-    L2Z_TRY(prefill_rows_logits(s0, w, n, b->logits, b->ld_logits));
-    L2Z_HIP(launch_wide_logits_out(b->logits, b->ld_logits, b->d_tab, c.vocab_size, out_next ? b->d_next : nullptr, n, st));
+    L2Z_TRY(wide_join(b, n, states));
+    L2Z_TRY(wide_upload_table(b, n, tokens, pos, states));
+    L2Z_TRY(wide_step(s0, w, n, deepest, true, [&]() -> int {
+        L2Z_HIP(launch_wide_logits_out(b->logits, b->ld_logits, b->d_tab, config->vocab_size, out_next ? b->d_next : nullptr, n, st));
+        return L2Z_OK;
+    }));
     if (out_next) L2Z_HIP(hipMemcpyAsync(b->h_next, b->d_next, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    // ---- ... and every runstate's stream waits for the pass ----
-    L2Z_HIP(hipEventRecord(b->ev_done, st));
-    for (int i = 1; i < n; i++) L2Z_HIP(hipStreamWaitEvent(states[i]->stream, b->ev_done, 0));
-    for (int i = 0; i < n; i++) {
-        l2z_runstate *s = states[i];
-        s->n_part = 0;  // l2z_argmax scans the logits: the classifier left no per-block candidates
-        s->logits_partial = false;
-        s->host_pos = pos[i] + 1;
-    }
+    L2Z_TRY(wide_release(b, n, states, pos, 1));
     if (out_next) {
         L2Z_HIP(hipStreamSynchronize(st));
         memcpy(out_next, b->h_next, (size_t)n * 4);
     }
+    return L2Z_OK;
+}
+
+extern "C" int l2z_wide_run(int n, const int32_t *first_tokens, const int32_t *pos0, int n_steps, const float *temperature,
+                            const float *top_p, const float *coins, const l2z_config *config, l2z_runstate *const *states,
+                            const l2z_weights *w, int32_t *out_tokens)
+{
+    // ---- checks: a refusal enqueues nothing and changes no state ----
+    L2Z_TRY(no_device_check());
+    L2Z_CHECK(out_tokens != nullptr, L2Z_ERR_INVALID, "l2z_wide_run: null argument");
+    L2Z_CHECK(n_steps >= 1, L2Z_ERR_INVALID, "l2z_wide_run: n_steps = %d", n_steps);
+    int deepest = 0;
+    L2Z_TRY(wide_checks("l2z_wide_run", n, first_tokens, pos0, n_steps, config, states, w, &deepest));
+    bool sampled = false;  // some row draws: l2z_sample_batch's rules for it
+    if (temperature != nullptr) {
+        L2Z_CHECK(top_p != nullptr, L2Z_ERR_INVALID, "l2z_wide_run: top_p is NULL beside temperature");
+        for (int i = 0; i < n; i++) {
+            L2Z_CHECK(std::isfinite(temperature[i]) && temperature[i] >= 0.0f, L2Z_ERR_INVALID,
+                      "l2z_wide_run: temperature[%d] = %g (finite, >= 0)", i, (double)temperature[i]);
+            L2Z_CHECK(top_p[i] >= 0.0f && top_p[i] <= 1.0f, L2Z_ERR_INVALID, "l2z_wide_run: top_p[%d] = %g outside [0, 1]", i,
+                      (double)top_p[i]);
+            if (temperature[i] == 0.0f) continue;
+            sampled = true;
+            L2Z_CHECK(coins != nullptr, L2Z_ERR_INVALID, "l2z_wide_run: coins is NULL at temperature[%d] = %g", i,
+                      (double)temperature[i]);
+            for (int k = 0; k < n_steps; k++) {
+                const float coin = coins[(size_t)k * n + i];
+                L2Z_CHECK(coin >= 0.0f && coin < 1.0f, L2Z_ERR_INVALID, "l2z_wide_run: coins[%d][%d] = %g outside [0, 1)", k, i,
+                          (double)coin);
+            }
+        }
+    }
+    l2z_runstate *s0 = states[0];
+    hipStream_t st = s0->stream;
+    const size_t entries = (size_t)n_steps * n;
+    L2Z_HIP(hipSetDevice(s0->device));
+    L2Z_TRY(prefill_scratch(s0, n));
+    L2Z_TRY(wide_alloc(s0));
+    L2Z_TRY(run_alloc(s0, entries, sampled));
+    WideScratch *b = s0->wd;
+
+    // ---- the run, on states[0]'s stream: one join, the first step's table and the coins, n_steps steps back to back ----
+    L2Z_TRY(wide_join(b, n, states));
+    L2Z_TRY(wide_upload_table(b, n, first_tokens, pos0, states));
+    WideDraw d = {};
+    d.logits = b->logits; d.ld = b->ld_logits; d.vocab = config->vocab_size;
+    d.tab = b->d_tab;
+    d.tokens = s0->pf_tokens;
+    if (sampled) {  // (the pinned twin is free: the run before has completed)
+        memcpy(b->h_ctl, temperature, (size_t)n * 4);
+        memcpy(b->h_ctl + kWideMax, top_p, (size_t)n * 4);
+        memcpy(b->h_ctl + 2 * kWideMax, coins, entries * 4);
+        L2Z_HIP(hipMemcpyAsync(b->d_ctl, b->h_ctl, (2 * (size_t)kWideMax + entries) * 4, hipMemcpyHostToDevice, st));
+        d.temperature = b->d_ctl; d.top_p = b->d_ctl + kWideMax;
+        d.scratch = b->smp; d.row_stride = sample_scratch_floats(config->vocab_size);
+    }
+    for (int k = 0; k < n_steps; k++) {
+        // the step's own launches: its grids take the step's own deepest position, as the single call computes it
+        if (sampled) d.coins = b->d_ctl + 2 * kWideMax + (size_t)k * n;
+        d.ids = b->d_ids + (size_t)k * n;
+        d.logits_out = k == n_steps - 1;
+        L2Z_TRY(wide_step(s0, w, n, deepest + k, k == 0, [&]() -> int {
+            L2Z_HIP(launch_wide_draw_advance(d, n, st));
+            return L2Z_OK;
+        }));
+    }
+    L2Z_HIP(hipMemcpyAsync(b->h_ids, b->d_ids, entries * 4, hipMemcpyDeviceToHost, st));
+    L2Z_TRY(wide_release(b, n, states, pos0, n_steps));
+    L2Z_HIP(hipStreamSynchronize(st));
+    memcpy(out_tokens, b->h_ids, entries * 4);
     return L2Z_OK;
 }
