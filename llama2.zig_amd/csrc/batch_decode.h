@@ -103,7 +103,9 @@ hipError_t launch_sample_step(const SampleStepArgs &a, hipStream_t st);
 // segments are kVerifySeg ABSOLUTE positions each -- segment s = positions [s * kVerifySeg, (s + 1) * kVerifySeg) whatever
 // the call's first position and row count are -- loads each K and V row of its segment once and uses it for every row; it
 // leaves per (row, head, segment) the flash partials (max, sum e^(s - max), sum e^(s - max) v).  The combine folds a row's
-// segments in segment order and divides.  Every order is a function of head_size, the segment and the row's position alone.
+// segments in segment order and divides.  Every order is a function of head_size, the segment and the row's position alone:
+// the kernels are wrappers around the segment bodies of verify_device.h, which the wide step (wide_decode.h) runs too,
+// there with the query heads of one row where these have the rows of one head.
 constexpr int kVerifySeg = 64;
 inline int verify_segments(int seq_len) { return (seq_len + kVerifySeg - 1) / kVerifySeg; }
 // What the three attention forms share: the rows' queries, outputs and partials

@@ -3,9 +3,11 @@
 // GEMM forms with per-row epilogues (prefill_skinny.hip, G_*_ROWS) and batch_decode.hip.  Also what a batch of samples
 // needs around the step: the on-device sampler l2z_sample_batch (sample_batch.hip) and the prompt copy
 // l2z_runstate_fork.  The step itself (batch_step) takes a layer's attention from its caller: the verify family
-// (verify_host.cpp) runs it with attention forms of its own.  batch_host.h: what the three host files of the step share.
+// (verify_host.cpp) runs it with attention forms of its own.  batch_host.h: what the host files share -- its argument
+// rules, stream hand-overs and allocation helper are defined here.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 
 #include "batch_host.h"
@@ -57,19 +59,11 @@ int batch_alloc(l2z_runstate *s)
     s->bt = b;  // freed with the runstate whatever happens below
     b->ld_xn = bt_ld(c.dim); b->ld_att = bt_ld(c.dim); b->ld_h1 = bt_ld(c.hidden_dim);
     const size_t R = kBatchMax;
-    struct { void **p; size_t bytes; } want[] = {
-        {(void **)&b->x, R * c.dim * 4}, {(void **)&b->xn, R * b->ld_xn * 4}, {(void **)&b->q, R * c.dim * 4},
-        {(void **)&b->att, R * b->ld_att * 4}, {(void **)&b->h1, R * b->ld_h1 * 4},
-        {(void **)&b->scores, R * (size_t)c.n_heads * c.seq_len * 4},
-        {(void **)&b->d_tab, sizeof(BatchTable) + kTabExtra}, {(void **)&b->d_tokens_out, R * 4}};
-    for (auto &w : want) {
-        const hipError_t e = hipMalloc(w.p, w.bytes);
-        if (e != hipSuccess) {
-            *w.p = nullptr;
-            set_error("batched step scratch allocation (%zu bytes) failed: %s", w.bytes, hipGetErrorString(e));
-            return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
-        }
-    }
+    L2Z_TRY(alloc_all("batched step scratch",
+                      {{(void **)&b->x, R * c.dim * 4}, {(void **)&b->xn, R * b->ld_xn * 4}, {(void **)&b->q, R * c.dim * 4},
+                       {(void **)&b->att, R * b->ld_att * 4}, {(void **)&b->h1, R * b->ld_h1 * 4},
+                       {(void **)&b->scores, R * (size_t)c.n_heads * c.seq_len * 4},
+                       {(void **)&b->d_tab, sizeof(BatchTable) + kTabExtra}, {(void **)&b->d_tokens_out, R * 4}}));
     L2Z_HIP(hipHostMalloc((void **)&b->h_tab, sizeof(BatchTable) + kTabExtra, hipHostMallocDefault));
     b->d_behind = b->d_tab + 1;
     b->h_behind = b->h_tab + 1;
@@ -88,13 +82,8 @@ int sample_alloc(l2z_runstate *s)
 {
     BatchScratch *b = s->bt;
     if (b->smp != nullptr) return L2Z_OK;
-    const size_t stride = sample_scratch_floats(s->cfg.vocab_size), bytes = kBatchMax * stride * 4;
-    const hipError_t e = hipMalloc(&b->smp, bytes);
-    if (e != hipSuccess) {
-        b->smp = nullptr;
-        set_error("l2z_sample_batch scratch allocation (%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
-    }
+    const size_t stride = sample_scratch_floats(s->cfg.vocab_size);
+    L2Z_TRY(alloc_all("l2z_sample_batch scratch", {{(void **)&b->smp, kBatchMax * stride * 4}}));
     b->smp_stride = stride;
     return L2Z_OK;
 }
@@ -107,22 +96,27 @@ int verify_alloc(l2z_runstate *s)
         return L2Z_OK;
     const l2z_config &c = s->cfg;
     const size_t R = kBatchMax, segs = (size_t)verify_segments(c.seq_len), hs = (size_t)c.dim / c.n_heads;
-    struct { void **p; size_t bytes; } want[] = {
-        {(void **)&b->v_logits, R * (size_t)c.vocab_size * 4},
-        {(void **)&b->v_part_o, R * c.n_heads * segs * hs * 4},
-        {(void **)&b->v_part_ml, R * c.n_heads * segs * 2 * 4},
-        {(void **)&b->d_vout, 3 * R * 4}};
-    for (auto &w : want) {
-        if (*w.p != nullptr) continue;
+    // (a call that failed part of the way left some of them: those stay)
+    L2Z_TRY(alloc_all("l2z_verify scratch", {{(void **)&b->v_logits, R * (size_t)c.vocab_size * 4},
+                                             {(void **)&b->v_part_o, R * c.n_heads * segs * hs * 4},
+                                             {(void **)&b->v_part_ml, R * c.n_heads * segs * 2 * 4},
+                                             {(void **)&b->d_vout, 3 * R * 4}}));
+    if (b->h_vout == nullptr) L2Z_HIP(hipHostMalloc((void **)&b->h_vout, 3 * R * 4, hipHostMallocDefault));
+    b->v_seg_cap = (int)segs;
+    return L2Z_OK;
+}
+
+int alloc_all(const char *what, std::initializer_list<DeviceBuf> want)
+{
+    for (const DeviceBuf &w : want) {
+        if (*w.p != nullptr || w.bytes == 0) continue;
         const hipError_t e = hipMalloc(w.p, w.bytes);
         if (e != hipSuccess) {
             *w.p = nullptr;
-            set_error("l2z_verify scratch allocation (%zu bytes) failed: %s", w.bytes, hipGetErrorString(e));
+            set_error("%s allocation (%zu bytes) failed: %s", what, w.bytes, hipGetErrorString(e));
             return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
         }
     }
-    if (b->h_vout == nullptr) L2Z_HIP(hipHostMalloc((void **)&b->h_vout, 3 * R * 4, hipHostMallocDefault));
-    b->v_seg_cap = (int)segs;
     return L2Z_OK;
 }
 
@@ -152,20 +146,45 @@ int check_states(const char *fn, int n, l2z_runstate *const *states, const l2z_c
     return L2Z_OK;
 }
 
-int join_streams(BatchScratch *b, int n, l2z_runstate *const *states)
+int check_positions(const char *fn, const char *where, const char *what, int pos0, int n, int seq_len)
 {
-    hipStream_t st = states[0]->stream;
-    for (int i = 1; i < n; i++) {
-        L2Z_HIP(hipEventRecord(b->ev_in[i], states[i]->stream));
-        L2Z_HIP(hipStreamWaitEvent(st, b->ev_in[i], 0));
-    }
+    L2Z_CHECK(pos0 >= 0 && pos0 <= seq_len - n, L2Z_ERR_STATE, "%s: %s%s %d .. %lld outside [0, %d)", fn, where, what, pos0,
+              (long long)pos0 + n - 1, seq_len);
     return L2Z_OK;
 }
 
-int release_streams(BatchScratch *b, int n, l2z_runstate *const *states)
+int check_tokens(const char *fn, const char *where, const int32_t *tokens, int n, int vocab, int first)
 {
-    L2Z_HIP(hipEventRecord(b->ev_done, states[0]->stream));
-    for (int i = 1; i < n; i++) L2Z_HIP(hipStreamWaitEvent(states[i]->stream, b->ev_done, 0));
+    for (int i = 0; i < n; i++)
+        L2Z_CHECK(tokens[i] >= 0 && tokens[i] < vocab, L2Z_ERR_STATE, "%s: %stokens[%d] = %d out of vocabulary", fn, where,
+                  first + i, tokens[i]);
+    return L2Z_OK;
+}
+
+int check_row(const char *fn, int i, int32_t token, int32_t pos, int n_pos, const l2z_config &c)
+{
+    char what[24];
+    snprintf(what, sizeof what, "pos[%d] =", i);
+    L2Z_TRY(check_positions(fn, "", what, pos, n_pos, c.seq_len));
+    return check_tokens(fn, "", &token, 1, c.vocab_size, i);
+}
+
+int check_draw(const char *fn, int seq, float temperature, float top_p, const float *coins)
+{
+    char idx[16] = "";
+    if (seq >= 0) snprintf(idx, sizeof idx, "[%d]", seq);
+    L2Z_CHECK(std::isfinite(temperature) && temperature >= 0.0f, L2Z_ERR_INVALID, "%s: temperature%s = %g (finite, >= 0)", fn, idx,
+              (double)temperature);
+    L2Z_CHECK(top_p >= 0.0f && top_p <= 1.0f, L2Z_ERR_INVALID, "%s: top_p%s = %g outside [0, 1]", fn, idx, (double)top_p);
+    L2Z_CHECK(temperature == 0.0f || coins != nullptr, L2Z_ERR_INVALID, "%s: coins is NULL at temperature%s%s%g", fn, idx,
+              seq >= 0 ? " = " : " ", (double)temperature);
+    return L2Z_OK;
+}
+
+int check_coins(const char *fn, const float *coins, int first, int count, int stride)
+{
+    for (long long i = first; i < first + (long long)count * stride; i += stride)
+        L2Z_CHECK(coins[i] >= 0.0f && coins[i] < 1.0f, L2Z_ERR_INVALID, "%s: coins[%lld] = %g outside [0, 1)", fn, i, (double)coins[i]);
     return L2Z_OK;
 }
 
@@ -268,10 +287,7 @@ extern "C" int l2z_transformer_batch(int n, const int32_t *tokens, const int32_t
     L2Z_TRY(check_states("l2z_transformer_batch", n, states, config));
     for (int i = 0; i < n; i++) {
         L2Z_TRY(check_pair(config, states[i], w));
-        L2Z_CHECK(pos[i] >= 0 && pos[i] < config->seq_len, L2Z_ERR_STATE, "l2z_transformer_batch: pos[%d] = %d outside [0,%d)", i,
-                  pos[i], config->seq_len);
-        L2Z_CHECK(tokens[i] >= 0 && tokens[i] < config->vocab_size, L2Z_ERR_STATE,
-                  "l2z_transformer_batch: tokens[%d] = %d out of vocabulary", i, tokens[i]);
+        L2Z_TRY(check_row("l2z_transformer_batch", i, tokens[i], pos[i], 1, *config));
     }
     L2Z_TRY(prefill_check(config, states[0]));
     L2Z_CHECK(states[0]->sh.hs <= 256, L2Z_ERR_INVALID, "l2z_transformer_batch: head_size above 256");
@@ -297,12 +313,7 @@ extern "C" int l2z_transformer_batch(int n, const int32_t *tokens, const int32_t
         return L2Z_OK;
     }));
     L2Z_TRY(release_streams(b, n, states));
-    for (int i = 0; i < n; i++) {
-        l2z_runstate *s = states[i];
-        s->n_part = 0;  // l2z_argmax scans the logits: the classifier left no per-block candidates
-        s->logits_partial = false;
-        s->host_pos = pos[i] + 1;
-    }
+    for (int i = 0; i < n; i++) logits_whole(states[i], pos[i] + 1);
     return L2Z_OK;
 }
 
@@ -336,13 +347,9 @@ int sample_enqueue(int n, l2z_runstate *const *states, const float *temperature,
     L2Z_CHECK(temperature != nullptr && top_p != nullptr && coins != nullptr, L2Z_ERR_INVALID,
               "l2z_sample_batch: null argument");
     L2Z_TRY(check_states("l2z_sample_batch", n, states, nullptr));
-    for (int i = 0; i < n; i++) {
-        L2Z_CHECK(std::isfinite(temperature[i]) && temperature[i] >= 0.0f, L2Z_ERR_INVALID,
-                  "l2z_sample_batch: temperature[%d] = %g (finite, >= 0)", i, (double)temperature[i]);
-        L2Z_CHECK(top_p[i] >= 0.0f && top_p[i] <= 1.0f, L2Z_ERR_INVALID, "l2z_sample_batch: top_p[%d] = %g outside [0, 1]", i,
-                  (double)top_p[i]);
-        L2Z_CHECK(coins[i] >= 0.0f && coins[i] < 1.0f, L2Z_ERR_INVALID, "l2z_sample_batch: coins[%d] = %g outside [0, 1)", i,
-                  (double)coins[i]);
+    for (int i = 0; i < n; i++) {   // (a row at temperature 0 answers for its coin too)
+        L2Z_TRY(check_draw("l2z_sample_batch", i, temperature[i], top_p[i], coins));
+        L2Z_TRY(check_coins("l2z_sample_batch", coins, i, 1));
     }
     L2Z_HIP(hipSetDevice(states[0]->device));
     L2Z_TRY(batch_alloc(states[0]));
@@ -427,9 +434,7 @@ extern "C" int l2z_runstate_fork(l2z_runstate *dst, const l2z_runstate *src, int
     (void)hipEventDestroy(ev_src);  // released by the runtime once the streams are past them
     if (ev_dst) (void)hipEventDestroy(ev_dst);
     if (rc != L2Z_OK) return rc;
-    dst->n_part = 0;  // l2z_argmax scans the copied logits, not dst's own classifier candidates
-    dst->logits_partial = false;
-    dst->host_pos = n_pos;
+    logits_whole(dst, n_pos);  // (the copied logits, not dst's own classifier candidates)
     return L2Z_OK;
 }
 
@@ -442,8 +447,7 @@ extern "C" int l2z_logits_write(l2z_runstate *s, const float *logits)
     L2Z_HIP(hipSetDevice(s->device));
     L2Z_HIP(hipMemcpyAsync(s->logits, logits, (size_t)s->cfg.vocab_size * 4, hipMemcpyHostToDevice, s->stream));
     L2Z_HIP(hipStreamSynchronize(s->stream));
-    s->n_part = 0;
-    s->logits_partial = false;
+    logits_whole(s, s->host_pos);
     return L2Z_OK;
 }
 

@@ -1,6 +1,10 @@
-// batch_host.h -- what the host files that run on the batched step share (batch_host.cpp: the step and what stands around
-// it; verify_host.cpp: the verify family; prefill_batch_host.cpp: the rules of a call that names several runstates).
+// batch_host.h -- what the host files of a call that names several runstates, or draws tokens, share (batch_host.cpp: the
+// batched step and what stands around it; verify_host.cpp: the verify family; wide_host.cpp: the wide step and its run;
+// prefill_batch_host.cpp, prefill_host.cpp, forward.cpp): the rules for the runstates and for the arguments of a draw, the
+// stream hand-overs, the scratch allocation and the batched step itself.
 #pragma once
+#include <initializer_list>
+
 #include "batch_decode.h"
 #include "l2z_state.h"
 
@@ -36,14 +40,57 @@ int batch_alloc(l2z_runstate *s);
 int sample_alloc(l2z_runstate *s);
 int verify_alloc(l2z_runstate *s);
 
+// hipMalloc of every buffer of the list that has a size and is not there yet.  A failure leaves that pointer null, names
+// `what` and the size in the error, and is L2Z_ERR_OOM where the device is out of memory; what was allocated before it
+// stays with its owner, whose clean-up rule is the caller's.
+struct DeviceBuf {
+    void **p;
+    size_t bytes;
+};
+int alloc_all(const char *what, std::initializer_list<DeviceBuf> want);
+
 int no_device_check();
 // the runstates of one call: non-null, pairwise distinct, unsharded, on one device, all made with *c (c: states[0]'s
 // when the call names no config), 1 <= n <= n_max
 int check_states(const char *fn, int n, l2z_runstate *const *states, const l2z_config *c, int n_max = kBatchMax);
-// the pass on states[0]'s stream waits for everything already queued on every runstate's stream ...
-int join_streams(BatchScratch *b, int n, l2z_runstate *const *states);
+// The preconditions of a call's rows; fn: the entry point a message names, where: "" or "sequence j: ".
+// n rows from pos0 on lie in the cache; what: what the rows are to the caller
+int check_positions(const char *fn, const char *where, const char *what, int pos0, int n, int seq_len);
+// tokens[0 .. n) are in the vocabulary; a message names index first + i
+int check_tokens(const char *fn, const char *where, const int32_t *tokens, int n, int vocab, int first = 0);
+// row i of a call that takes a token and a position per runstate: its n_pos positions from pos on, then its token
+int check_row(const char *fn, int i, int32_t token, int32_t pos, int n_pos, const l2z_config &c);
+// l2z_sample_batch's rules for one temperature and top_p (seq >= 0: those of row or sequence seq) and the coins' presence ...
+int check_draw(const char *fn, int seq, float temperature, float top_p, const float *coins);
+// ... and for the `count` coins a sampled row reads, `stride` apart from coins[first] on
+int check_coins(const char *fn, const float *coins, int first, int count, int stride = 1);
+
+// the pass on states[0]'s stream waits for everything already queued on every runstate's stream ... (b: a scratch with
+// an event per runstate, ev_in[], and ev_done)
+template <class Scratch> int join_streams(Scratch *b, int n, l2z_runstate *const *states)
+{
+    for (int i = 1; i < n; i++) {
+        L2Z_HIP(hipEventRecord(b->ev_in[i], states[i]->stream));
+        L2Z_HIP(hipStreamWaitEvent(states[0]->stream, b->ev_in[i], 0));
+    }
+    return L2Z_OK;
+}
 // ... and every runstate's stream waits for the pass
-int release_streams(BatchScratch *b, int n, l2z_runstate *const *states);
+template <class Scratch> int release_streams(Scratch *b, int n, l2z_runstate *const *states)
+{
+    L2Z_HIP(hipEventRecord(b->ev_done, states[0]->stream));
+    for (int i = 1; i < n; i++) L2Z_HIP(hipStreamWaitEvent(states[i]->stream, b->ev_done, 0));
+    return L2Z_OK;
+}
+
+// The call left WHOLE logits in s, not a classifier's per-block candidates (l2z_argmax scans them), and s's next position
+// is next_pos
+inline void logits_whole(l2z_runstate *s, int next_pos)
+{
+    s->n_part = 0;
+    s->logits_partial = false;
+    s->host_pos = next_pos;
+}
 
 // the table of this call, and behind_bytes of what sits behind it, -> the device: one copy from the pinned buffer
 // (rewritten only once the last copy is done)

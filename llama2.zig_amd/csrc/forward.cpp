@@ -599,16 +599,8 @@ extern "C" int l2z_sample_run(const l2z_config *config, l2z_runstate *s, const l
     L2Z_TRY(check_pair(config, s, w));
     L2Z_CHECK(s->comm == nullptr && s->sh.world == 1, L2Z_ERR_INVALID,
               "l2z_sample_run: the runstate is a shard (a shard holds its own rows of the logits only)");
-    // l2z_sample_batch's rules
-    L2Z_CHECK(std::isfinite(temperature) && temperature >= 0.0f, L2Z_ERR_INVALID, "l2z_sample_run: temperature = %g (finite, >= 0)",
-              (double)temperature);
-    L2Z_CHECK(top_p >= 0.0f && top_p <= 1.0f, L2Z_ERR_INVALID, "l2z_sample_run: top_p = %g outside [0, 1]", (double)top_p);
-    L2Z_CHECK(temperature == 0.0f || coins != nullptr, L2Z_ERR_INVALID, "l2z_sample_run: coins is NULL at temperature %g",
-              (double)temperature);
-    if (temperature > 0.0f)
-        for (int i = 0; i < n_steps; i++)
-            L2Z_CHECK(coins[i] >= 0.0f && coins[i] < 1.0f, L2Z_ERR_INVALID, "l2z_sample_run: coins[%d] = %g outside [0, 1)", i,
-                      (double)coins[i]);
+    L2Z_TRY(check_draw("l2z_sample_run", -1, temperature, top_p, coins));  // l2z_sample_batch's rules
+    if (temperature > 0.0f) L2Z_TRY(check_coins("l2z_sample_run", coins, 0, n_steps));
     *out_n = 0;
     const int left = config->seq_len - s->host_pos;
     const int n = n_steps < left ? n_steps : left;

@@ -18,6 +18,7 @@ constexpr int kWaves = kBlock / kWave;
 constexpr int kScratch = 32;  // floats of LDS scratch for block reductions
 
 typedef float v4f __attribute__((ext_vector_type(4)));
+typedef float v2f __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ v4f ldg_nt(const v4f *p) { return __builtin_nontemporal_load(p); }
 

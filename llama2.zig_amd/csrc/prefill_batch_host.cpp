@@ -27,15 +27,9 @@ int ragged_alloc(l2z_runstate *s, int need)
     for (void **b : bufs)
         if (*b) { (void)hipFree(*b); *b = nullptr; }
     s->rg_cap = 0;
-    struct { void **p; size_t bytes; } want[] = {{(void **)&s->rg_k, P * kvd * 4}, {(void **)&s->rg_v, P * kvd * 4}, {&s->rg_tab, tab_bytes((int)P)}};
-    for (auto &b : want) {
-        const hipError_t e = hipMalloc(b.p, b.bytes);
-        if (e != hipSuccess) {
-            *b.p = nullptr;
-            set_error("l2z_prefill_batch scratch allocation (%zu bytes) failed: %s", b.bytes, hipGetErrorString(e));
-            return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;   // what was allocated is freed with the runstate
-        }
-    }
+    // (after a failure, what was allocated is freed with the runstate)
+    L2Z_TRY(alloc_all("l2z_prefill_batch scratch",
+                      {{(void **)&s->rg_k, P * kvd * 4}, {(void **)&s->rg_v, P * kvd * 4}, {&s->rg_tab, tab_bytes((int)P)}}));
     s->rg_cap = (int)P;
     return L2Z_OK;
 }

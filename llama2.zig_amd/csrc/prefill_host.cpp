@@ -5,6 +5,7 @@
 #include <cstring>
 #include <mutex>
 
+#include "batch_host.h"
 #include "l2z_state.h"
 #include "prefill_common.h"
 #include "wide_decode.h"
@@ -52,7 +53,8 @@ int prefill_alloc(l2z_runstate *s, int need)
     const size_t h1_w = (size_t)pf_ld(std::max(c.hidden_dim, s->sh.scheme_b ? s->sh.hidc_pad : 0));
     const size_t xn_w = (size_t)pf_ld(c.dim);
     s->pf_ld_xn = (int)xn_w; s->pf_ld_att = (int)att_w; s->pf_ld_h1 = (int)h1_w;
-    struct { void **p; size_t bytes; } want[] = {
+    // (after a failure, what was allocated is freed with the runstate, or on the next attempt)
+    L2Z_TRY(alloc_all("prefill scratch", {
         {(void **)&s->pf_x, P * c.dim * 4},   {(void **)&s->pf_xn, P * xn_w * 4},
         {(void **)&s->pf_q, P * c.dim * 4},   {(void **)&s->pf_att, P * att_w * 4},
         {(void **)&s->pf_h1, P * h1_w * 4},
@@ -64,16 +66,7 @@ int prefill_alloc(l2z_runstate *s, int need)
         // the tile GEMM on the bf16 matrix cores: one launch's activation matrix as three planes of bf16 terms
         {(void **)&s->pf_sk.x3, P * 3 * std::max(std::max(xn_w, att_w), h1_w) * 2},
         // ... and the gated hidden rows' planes, written by the W1 | W3 launch while it reads its own (unsharded pass)
-        {(void **)&s->pf_sk.x3b, s->sh.world > 1 ? 0 : P * 3 * h1_w * 2}};
-    for (auto &b : want) {
-        if (b.bytes == 0) continue;
-        hipError_t e = hipMalloc(b.p, b.bytes);
-        if (e != hipSuccess) {
-            *b.p = nullptr;
-            set_error("prefill scratch allocation (%zu bytes) failed: %s", b.bytes, hipGetErrorString(e));
-            return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;  // what was allocated is freed with the runstate, or on the next attempt
-        }
-    }
+        {(void **)&s->pf_sk.x3b, s->sh.world > 1 ? 0 : P * 3 * h1_w * 2}}));
     s->pf_cap = (int)P;
     s->pf_sk.x3_bytes = P * 3 * std::max(std::max(xn_w, att_w), h1_w) * 2;
     s->pf_sk.x3b_bytes = s->sh.world > 1 ? 0 : P * 3 * h1_w * 2;

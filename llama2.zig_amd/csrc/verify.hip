@@ -18,16 +18,15 @@ namespace {
 // Block (h, seg): head h over the keys t of segment seg that the call's rows see (verify_device.h)
 __global__ __launch_bounds__(kVaBlock) void verify_attention_kernel(const VerifyAttnArgs a, const int n)
 {
-    __shared__ __attribute__((aligned(16))) float sc[kVaLds];  // scores [row][key], then the groups' V sums (4 rows a round)
+    __shared__ __attribute__((aligned(16))) float sc[seg_lds_floats<kBatchMax>];  // scores [row][key], then the groups' V sums
     verify_attention_body(a, n, blockIdx.x, blockIdx.y, sc);
 }
 
 // Block (h, i): row i's segments 0 .. (pos0 + i) / kVerifySeg folded in segment order, then the divide (verify_device.h)
 __global__ __launch_bounds__(64) void verify_combine_kernel(const VerifyAttnArgs a)
 {
-    const int h = blockIdx.x, i = blockIdx.y;
-    verify_combine_body(a.part_o, a.part_ml, ((size_t)i * a.n_heads + h) * a.seg_cap, (a.pos0 + i) / kVerifySeg + 1, a.head_size,
-                        a.out + (size_t)i * a.ldo + (size_t)h * a.head_size);
+    const int i = blockIdx.y;
+    verify_combine_store(a, blockIdx.x, i, (a.pos0 + i) / kVerifySeg + 1);
 }
 
 __global__ __launch_bounds__(1024) void verify_argmax_kernel(const float *logits, int vocab, int *out)

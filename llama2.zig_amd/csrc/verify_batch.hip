@@ -16,7 +16,7 @@ namespace {
 // segment has no key to look at and returns (uniformly, before any barrier).
 __global__ __launch_bounds__(kVaBlock) void verify_batch_attention_kernel(const VerifyBatchAttnArgs b)
 {
-    __shared__ __attribute__((aligned(16))) float sc[kVaLds];
+    __shared__ __attribute__((aligned(16))) float sc[seg_lds_floats<kBatchMax>];
     const int grp = blockIdx.z, seg = blockIdx.y;
     const VerifyGroupTable *gt = b.groups;
     const int first = gt->first[grp], n = gt->count[grp], pos0 = gt->pos0[grp];
@@ -35,9 +35,8 @@ __global__ __launch_bounds__(kVaBlock) void verify_batch_attention_kernel(const 
 // Block (h, row): the row's segments 0 .. pos / kVerifySeg, pos = the row's own position in the step's table
 __global__ __launch_bounds__(64) void verify_batch_combine_kernel(const VerifyBatchAttnArgs b)
 {
-    const int h = blockIdx.x, i = blockIdx.y;
-    verify_combine_body(b.part_o, b.part_ml, ((size_t)i * b.n_heads + h) * b.seg_cap, b.tab->pos[i] / kVerifySeg + 1, b.head_size,
-                        b.out + (size_t)i * b.ldo + (size_t)h * b.head_size);
+    const int i = blockIdx.y;
+    verify_combine_store(b, blockIdx.x, i, b.tab->pos[i] / kVerifySeg + 1);
 }
 
 // Block (x, group): verify_accept_kernel per group.  Every block finds its group's accept length itself over the group's

@@ -5,7 +5,6 @@
 // path (verify_tree.hip).  Every path reads the same way: checks (a refusal enqueues nothing and changes no state), scratch,
 // table, the step with the path's attention, the rows' next ids (verify_ids), the path's accept kernel, the copy back.
 #include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <cstring>
 
@@ -41,43 +40,6 @@ int check_target(const char *fn, const l2z_config *config, l2z_runstate *s, cons
     return check_targets(fn, config, 1, &s, w);
 }
 
-// n rows from pos0 on lie in the cache; where: "" or "sequence j: ", what: what the rows are to the caller
-int check_positions(const char *fn, const char *where, const char *what, int pos0, int n, int seq_len)
-{
-    L2Z_CHECK(pos0 >= 0 && pos0 <= seq_len - n, L2Z_ERR_STATE, "%s: %s%s %d .. %lld outside [0, %d)", fn, where, what, pos0,
-              (long long)pos0 + n - 1, seq_len);
-    return L2Z_OK;
-}
-
-int check_tokens(const char *fn, const char *where, const int32_t *tokens, int n, int vocab)
-{
-    for (int i = 0; i < n; i++)
-        L2Z_CHECK(tokens[i] >= 0 && tokens[i] < vocab, L2Z_ERR_STATE, "%s: %stokens[%d] = %d out of vocabulary", fn, where, i,
-                  tokens[i]);
-    return L2Z_OK;
-}
-
-// l2z_sample_batch's rules for one temperature and top_p (seq >= 0: those of sequence seq) and the coins' presence ...
-int check_draw(const char *fn, int seq, float temperature, float top_p, const float *coins)
-{
-    char idx[16] = "";
-    if (seq >= 0) snprintf(idx, sizeof idx, "[%d]", seq);
-    L2Z_CHECK(std::isfinite(temperature) && temperature >= 0.0f, L2Z_ERR_INVALID, "%s: temperature%s = %g (finite, >= 0)", fn, idx,
-              (double)temperature);
-    L2Z_CHECK(top_p >= 0.0f && top_p <= 1.0f, L2Z_ERR_INVALID, "%s: top_p%s = %g outside [0, 1]", fn, idx, (double)top_p);
-    L2Z_CHECK(temperature == 0.0f || coins != nullptr, L2Z_ERR_INVALID, "%s: coins is NULL at temperature%s%s%g", fn, idx,
-              seq >= 0 ? " = " : " ", (double)temperature);
-    return L2Z_OK;
-}
-
-// ... and for the coins first .. first + count - 1 a sampled pass reads
-int check_coins(const char *fn, const float *coins, int first, int count)
-{
-    for (int i = first; i < first + count; i++)
-        L2Z_CHECK(coins[i] >= 0.0f && coins[i] < 1.0f, L2Z_ERR_INVALID, "%s: coins[%d] = %g outside [0, 1)", fn, i, (double)coins[i]);
-    return L2Z_OK;
-}
-
 // ---- what the paths share after the checks ----
 
 int verify_scratch(l2z_runstate *s0, bool sampled)
@@ -110,8 +72,7 @@ int verify_ids(BatchScratch *b, bool sampled, int vocab, int rows, hipStream_t s
 // l2z_verify_logits_read
 void verify_done(l2z_runstate *s, int rows)
 {
-    s->n_part = 0;
-    s->logits_partial = false;
+    logits_whole(s, s->host_pos);  // (the caller moves the position once it has read the verdict)
     if (s->bt != nullptr) s->bt->v_rows = rows;
 }
 

@@ -25,7 +25,7 @@ constexpr int kVvUB = 8;  // the tree's V rows a lane has in flight (those of it
 // Position pos0 + d is a tree slot: one K / V row per node of depth d, used by the rows below that node.
 __global__ __launch_bounds__(kVaBlock) void verify_tree_attention_kernel(const VerifyTreeAttnArgs a, const int n, const int max_depth)
 {
-    __shared__ __attribute__((aligned(16))) float sc[kVaLds];  // scores [row][slot], then the groups' V sums (4 rows a round)
+    __shared__ __attribute__((aligned(16))) float sc[seg_lds_floats<kBatchMax>];  // scores [row][slot], then the groups' V sums
     const VerifyTreeTable *tt = a.tree;
     const int h = blockIdx.x, seg = blockIdx.y;
     const int tid = threadIdx.x;
@@ -106,7 +106,8 @@ __global__ __launch_bounds__(kVaBlock) void verify_tree_attention_kernel(const V
         }
     }
     __syncthreads();
-    verify_softmax_sweep(a, h, seg, act, nk, sc);
+    const SegSlots s = verify_slots(a, h, act);  // (the sweep and the fold: where the rows' partials go)
+    segment_softmax_sweep<kBatchMax>(s, seg, nk, sc);
     __syncthreads();
     // acc_i = sum over slots of e[i][slot] v: group g takes slots g, g + G, ... in increasing slot -- its context slots ...
     v4f acc[kBatchMax];
@@ -165,15 +166,14 @@ __global__ __launch_bounds__(kVaBlock) void verify_tree_attention_kernel(const V
             }
     }
     __syncthreads();
-    verify_group_fold(a, h, seg, act, acc, TPR, sc);
+    segment_group_fold<kBatchMax>(s, seg, hs, acc, TPR, sc);
 }
 
 // Block (h, i): row i's segments 0 .. (pos0 + depth_i) / kVerifySeg folded in segment order, then the divide
 __global__ __launch_bounds__(64) void verify_tree_combine_kernel(const VerifyTreeAttnArgs a)
 {
-    const int h = blockIdx.x, i = blockIdx.y;
-    verify_combine_body(a.part_o, a.part_ml, ((size_t)i * a.n_heads + h) * a.seg_cap, (a.pos0 + a.tree->depth[i]) / kVerifySeg + 1,
-                        a.head_size, a.out + (size_t)i * a.ldo + (size_t)h * a.head_size);
+    const int i = blockIdx.y;
+    verify_combine_store(a, blockIdx.x, i, (a.pos0 + a.tree->depth[i]) / kVerifySeg + 1);
 }
 
 // out[0 .. n) = the rows' next ids.  Every block walks the tree itself (cur = 0; while cur has a child whose token is

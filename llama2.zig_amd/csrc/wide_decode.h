@@ -1,6 +1,7 @@
 // wide_decode.h -- the kernels l2z_transformer_wide adds to the ragged prompt pass (wide_decode.hip; host side
-// wide_host.cpp, prefill_host.cpp): decode attention for up to kWideMax one-query sequences, each on its own cache, and
-// the launch that hands the [n, vocab] logits matrix back to the runstates.  Every row's token, position, caches and
+// wide_host.cpp, prefill_host.cpp): decode attention for up to kWideMax one-query sequences, each on its own cache (the
+// verify family's segment body, verify_device.h, with a kv head's query heads as a block's slots), and the launch that
+// hands the [n, vocab] logits matrix back to the runstates.  Every row's token, position, caches and
 // logits come from one device table.  And the last launch of a step inside l2z_wide_run (wide_sample.hip): every row's
 // draw, and the hand-over of token and position to the next step on the device.
 #pragma once
@@ -44,12 +45,12 @@ struct WideAttn {
 
 // Decode attention (main.zig:361-389) of rows 0 .. n - 1 of q [n, ldq] (RoPE applied) into out [n, ldo], two launches:
 //   wide_attention: block (kv head, segment, row) reads the segment's K and V rows of that kv head ONCE and serves all
-//     kv_mul query heads of it (up to 4 per block; beyond, blocks of 4); a block past its row's last segment returns.  It
-//     leaves the flash partials (max, sum e, sum e v) per (row, head, segment).
+//     kv_mul query heads of it (up to 4 per block; beyond, blocks of 4, the last one with the heads that are left); a block
+//     past its row's last segment returns.  It leaves the flash partials (max, sum e, sum e v) per (row, head, segment).
 //   wide_combine: block (head, row) folds the row's segments in segment order, divides, and writes out -- and, x3 != null,
 //     out's planes of bf16 terms x3[row][3][kp] (the Wo product's operand; *planes_written says whether it did).
-// head_size: a multiple of 4 up to 256.  Every summation order is a function of head_size, the segment and the row's own
-// position only; no block touches two sequences.  Keys beyond pos[i] are never read.
+// head_size: a multiple of 4 up to 256.  Every summation order is verify_device.h's: a function of head_size, the segment
+// and the row's own position only; no block touches two sequences.  Keys beyond pos[i] are never read.
 hipError_t launch_wide_attention(const float *q, int ldq, float *out, int ldo, const WideAttn &wa, int n, int n_heads,
                                  int head_size, size_t layer_off, size_t kv_head_stride, int kv_mul, hipStream_t st,
                                  void *x3 = nullptr, int kp = 0, bool *planes_written = nullptr);

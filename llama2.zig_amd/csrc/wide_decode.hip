@@ -2,23 +2,21 @@
 // wide_host.cpp): decode attention for many one-query sequences, each on its own cache, split over positions in the verify
 // family's fixed segments of absolute positions, and the launch that hands the logits matrix back to the runstates.
 //
-// A row's results depend on that row's q, its own cache rows 0 .. pos and its own position only: no block touches two
-// sequences, and every order below (the lanes' partial dots, a wave's max and sum over the segment, a group's V rows in
-// increasing t, the groups in g order, the segments in segment order) is a function of head_size, the segment and the
-// row's position.  Vector loads and stores only; every FMA is an explicit fmaf.
+// The attention is the verify family's segment body (verify_device.h) with a block's query slots being the query heads
+// of one kv head of ONE row, so the summation orders are that file's.  A row's results depend on that row's q, its own
+// cache rows 0 .. pos and its own position only: no block touches two sequences.  Vector loads and stores only; every
+// FMA is an explicit fmaf.
 #include "wide_decode.h"
 
 #include "kernel_common.h"
 #include "prefill_common.h"
+#include "verify_device.h"
 
 namespace l2z {
 namespace {
 
-constexpr int kWaBlock = 256;
-constexpr int kWaUB = 4;        // K / V rows a lane has in flight
-constexpr int kWcUB = 4;        // combine: segments' partials a thread has in flight
+constexpr int kWcUB = 4;        // combine: segments' partials a lane has in flight
 constexpr int kWaHeadsMax = 4;  // query heads of one kv head a block serves (8: 256 VGPRs, one wave per SIMD)
-static_assert(kVerifySeg == 64, "a wave sweeps a head's scores of one segment in one 64-lane step");
 
 struct WideAttnArgs {
     const float *q;
@@ -32,16 +30,12 @@ struct WideAttnArgs {
 };
 
 // Block (kv head x part, segment, row); MQ = query heads per block (a part = MQ consecutive heads of the kv head: one part
-// while kv_mul <= kWaHeadsMax).  A K row is read by TPR lanes (float4 each) ONCE and dotted with every head's q slice
-// (registers); the segment's scores sit in LDS ([head][key]); a wave owns heads w, w + 4 for max / exp / sum; then each V
-// row is read once and added into every head's accumulator; the lane groups' sums are combined in g order through LDS.
-// Keys behind the row's position are not part of the segment (nk): they are neither read nor summed.
+// while kv_mul <= kWaHeadsMax).  The part's heads are the slots of segment_attention_body: every head sees the keys up to
+// the row's position, which is where the segment ends for the block.
 template <int MQ>
-__global__ __launch_bounds__(kWaBlock) void wide_attention(const WideAttnArgs a)
+__global__ __launch_bounds__(kVaBlock) void wide_attention(const WideAttnArgs a)
 {
-    constexpr int FH = MQ < 4 ? MQ : 4;  // heads per round of the group fold
-    __shared__ __attribute__((aligned(16))) float sc[FH * 4 * kWaBlock];
-    static_assert(MQ * kVerifySeg <= FH * 4 * kWaBlock && MQ % FH == 0, "scores and fold rounds share the buffer");
+    __shared__ __attribute__((aligned(16))) float sc[seg_lds_floats<MQ>];
     const int row = blockIdx.z, seg = blockIdx.y;
     const int pos = a.tab->pos[row];
     const int seg0 = seg * kVerifySeg;
@@ -50,133 +44,24 @@ __global__ __launch_bounds__(kWaBlock) void wide_attention(const WideAttnArgs a)
     const int kvh = blockIdx.x / parts, hq0 = (blockIdx.x % parts) * MQ;
     const int h0 = kvh * a.kv_mul + hq0;
     const int nq = min(MQ, a.kv_mul - hq0);
-    const int tid = threadIdx.x, hs = a.head_size, E = hs >> 2;
-    int TPR = 1;
-    while (TPR < E) TPR <<= 1;
-    const int G = kWaBlock / TPR, g = tid / TPR, c = tid % TPR;
-    const int nk = min(kVerifySeg, pos - seg0 + 1);  // keys seg0 .. seg0 + nk - 1
-    const int last = seg0 + nk - 1;
+    SegSlots s = {};
+    s.q = a.q + (size_t)row * a.ldq + (size_t)h0 * a.head_size; s.q_step = (size_t)a.head_size;
+    s.see0 = pos; s.see_step = 0;
+    s.idx0 = (size_t)row * a.n_heads + h0; s.part_step = 1;
+    s.act = (1u << nq) - 1u;
+    s.part_o = a.part_o; s.part_ml = a.part_ml; s.seg_cap = a.seg_cap;
     const RaggedSeq sq = a.tab->seq[row];
     const size_t head_off = a.layer_off + (size_t)kvh * a.kv_head_stride;
-    const float *kbase = sq.kc + head_off, *vbase = sq.vc + head_off;
-    const v4f zero = {0.f, 0.f, 0.f, 0.f};
-    const float div = sqrtf((float)hs);
-    v4f qv[MQ];
-#pragma unroll
-    for (int m = 0; m < MQ; m++)
-        qv[m] = m < nq && c < E ? *(const v4f *)(a.q + (size_t)row * a.ldq + (size_t)(h0 + m) * hs + 4 * c) : zero;
-    // scores sc[m][t - seg0] = q_m . k_t / sqrt(head_size)
-    for (int tl0 = g; tl0 < nk; tl0 += G * kWaUB) {
-        v4f kv[kWaUB];
-#pragma unroll
-        for (int u = 0; u < kWaUB; u++) {
-            const int t = min(seg0 + tl0 + G * u, last);  // clamped: dropped below
-            kv[u] = c < E ? *(const v4f *)(kbase + (size_t)t * hs + 4 * c) : zero;
-        }
-#pragma unroll
-        for (int u = 0; u < kWaUB; u++) {
-            const int tl = tl0 + G * u;
-#pragma unroll
-            for (int m = 0; m < MQ; m++)
-                if (m < nq) {
-                    const float p = lanes_sum(hsum4(fma4(qv[m], kv[u], zero)), TPR);
-                    if (c == 0 && tl < nk) sc[m * kVerifySeg + tl] = p / div;
-                }
-        }
-    }
-    __syncthreads();
-    {   // per head: m = max, e = exp(s - m) in place, l = sum e (wave_sum's fixed order) -> part_ml
-        const int lane = tid & 63;
-        for (int m = tid >> 6; m < nq; m += kWaBlock / 64) {
-            float *r = sc + m * kVerifySeg;
-            const float s = lane < nk ? r[lane] : -INFINITY;
-            const float mx = wave_max(s);  // finite: key seg0 is at or below the row's position
-            const float e = expf(s - mx);  // a lane without a key: exactly 0
-            if (lane < nk) r[lane] = e;
-            const float l = wave_sum(e);
-            if (lane == 0) {
-                const v2f ml = {mx, l};
-                *(v2f *)(a.part_ml + (((size_t)row * a.n_heads + h0 + m) * a.seg_cap + seg) * 2) = ml;
-            }
-        }
-    }
-    __syncthreads();
-    // acc_m = sum_t e[m][t] v_t: group g takes t = seg0 + g, + G, ... in increasing t
-    v4f acc[MQ];
-#pragma unroll
-    for (int m = 0; m < MQ; m++) acc[m] = zero;
-    for (int tl0 = g; tl0 < nk; tl0 += G * kWaUB) {
-        v4f vv[kWaUB];
-#pragma unroll
-        for (int u = 0; u < kWaUB; u++) {
-            const int t = min(seg0 + tl0 + G * u, last);
-            vv[u] = c < E ? *(const v4f *)(vbase + (size_t)t * hs + 4 * c) : zero;
-        }
-#pragma unroll
-        for (int u = 0; u < kWaUB; u++) {
-            const int tl = tl0 + G * u;
-            if (tl < nk) {
-#pragma unroll
-                for (int m = 0; m < MQ; m++)
-                    if (m < nq) {
-                        const float wt = sc[m * kVerifySeg + tl];
-                        const v4f w4 = {wt, wt, wt, wt};
-                        acc[m] = fma4(w4, vv[u], acc[m]);
-                    }
-            }
-        }
-    }
-    __syncthreads();  // the scores are dead: the buffer takes the groups' sums, FH heads per round
-    v4f *buf = (v4f *)sc;
-#pragma unroll
-    for (int r = 0; r < MQ; r += FH)
-        if (r < nq) {
-#pragma unroll
-            for (int j = 0; j < FH; j++) buf[j * kWaBlock + tid] = acc[r + j];
-            __syncthreads();
-            if (tid < FH * TPR) {
-                const int j = tid / TPR, cc = tid % TPR, m = r + j;
-                if (cc < E && m < nq) {
-                    v4f o = buf[j * kWaBlock + cc];
-                    for (int gg = 1; gg < G; gg++) o += buf[j * kWaBlock + gg * TPR + cc];
-                    *(v4f *)(a.part_o + (((size_t)row * a.n_heads + h0 + m) * a.seg_cap + seg) * hs + 4 * cc) = o;
-                }
-            }
-            __syncthreads();
-        }
+    segment_attention_body<MQ>(s, sq.kc + head_off, sq.vc + head_off, a.head_size, seg, min(seg0 + kVerifySeg - 1, pos), sc);
 }
 
-// Block (head, row), lane c = four features: the row's segments 0 .. pos / kVerifySeg folded in segment order (online
-// rescale from max = -inf, sum = 0, so one segment goes through the same arithmetic as many), then the divide.
+// Block (head, row), lane c = four features: the row's segments 0 .. pos / kVerifySeg through segment_combine_body
 __global__ __launch_bounds__(64) void wide_combine(const WideAttnArgs a)
 {
     const int h = blockIdx.x, row = blockIdx.y, c = threadIdx.x, hs = a.head_size;
     if (c >= (hs >> 2)) return;
-    const int ns = a.tab->pos[row] / kVerifySeg + 1;
-    const size_t base = ((size_t)row * a.n_heads + h) * a.seg_cap;
-    const v4f zero = {0.f, 0.f, 0.f, 0.f};
-    float M = -INFINITY, L = 0.0f;
-    v4f O = zero;
-    for (int s0 = 0; s0 < ns; s0 += kWcUB) {
-        v2f ml[kWcUB];
-        v4f o[kWcUB];
-#pragma unroll
-        for (int u = 0; u < kWcUB; u++) {
-            const size_t s = base + min(s0 + u, ns - 1);  // clamped: dropped below
-            ml[u] = *(const v2f *)(a.part_ml + s * 2);
-            o[u] = *(const v4f *)(a.part_o + s * hs + 4 * c);
-        }
-#pragma unroll
-        for (int u = 0; u < kWcUB; u++)
-            if (s0 + u < ns) {
-                const float mn = fmaxf(M, ml[u].x);
-                const float ea = expf(M - mn), eb = expf(ml[u].x - mn);
-                L = L * ea + ml[u].y * eb;
-                O = O * ea + o[u] * eb;
-                M = mn;
-            }
-    }
-    const v4f r = {O.x / L, O.y / L, O.z / L, O.w / L};  // main.zig:704
+    const v4f r = segment_combine_body<kWcUB>(a.part_o, a.part_ml, ((size_t)row * a.n_heads + h) * a.seg_cap,
+                                              a.tab->pos[row] / kVerifySeg + 1, hs, c);
     *(v4f *)(a.out + (size_t)row * a.ldo + (size_t)h * hs + 4 * c) = r;
     if (a.x3) planes_store4(a.x3, a.kp, row, h * hs + 4 * c, r);
 }
@@ -237,9 +122,9 @@ hipError_t launch_wide_attention(const float *q, int ldq, float *out, int ldo, c
     const int mq = kv_mul == 1 ? 1 : kv_mul == 2 ? 2 : kWaHeadsMax;
     const dim3 grid(n_heads / kv_mul * ((kv_mul + mq - 1) / mq), wa.n_seg, n);
     switch (mq) {
-        case 1: hipLaunchKernelGGL(wide_attention<1>, grid, dim3(kWaBlock), 0, st, a); break;
-        case 2: hipLaunchKernelGGL(wide_attention<2>, grid, dim3(kWaBlock), 0, st, a); break;
-        default: hipLaunchKernelGGL(wide_attention<kWaHeadsMax>, grid, dim3(kWaBlock), 0, st, a); break;
+        case 1: hipLaunchKernelGGL(wide_attention<1>, grid, dim3(kVaBlock), 0, st, a); break;
+        case 2: hipLaunchKernelGGL(wide_attention<2>, grid, dim3(kVaBlock), 0, st, a); break;
+        default: hipLaunchKernelGGL(wide_attention<kWaHeadsMax>, grid, dim3(kVaBlock), 0, st, a); break;
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -5,7 +5,6 @@
 // bf16 cores); what the step adds is the table with one sequence slot per row, the position-split decode attention and its
 // last launch: the one that hands the [n, vocab] logits back (wide_decode.hip), or, inside a run, the one that draws every
 // row's token and hands the row to the next step (wide_sample.hip).
-#include <cmath>
 #include <cstring>
 
 #include "batch_host.h"
@@ -67,20 +66,10 @@ int wide_alloc(l2z_runstate *s)
     const size_t R = kWideMax, kvd = (size_t)s->sh.kvd_loc;
     b->ld_logits = (c.vocab_size + 3) / 4 * 4;
     b->seg_cap = verify_segments(c.seq_len);
-    struct { void **p; size_t bytes; } want[] = {
-        {(void **)&b->k, R * kvd * 4}, {(void **)&b->v, R * kvd * 4}, {(void **)&b->logits, R * b->ld_logits * 4},
-        {(void **)&b->part, wide_part_floats(c.n_heads, b->seg_cap, s->sh.hs) * 4},
-        {(void **)&b->d_next, R * 4}, {(void **)&b->d_tab, sizeof(WideTable)}};
-    for (auto &w : want) {
-        const hipError_t e = hipMalloc(w.p, w.bytes);
-        if (e != hipSuccess) {
-            *w.p = nullptr;
-            wide_free(s);  // the next call starts over
-            set_error("l2z_transformer_wide scratch allocation (%zu bytes) failed: %s", w.bytes, hipGetErrorString(e));
-            return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
-        }
-    }
-    int rc = L2Z_OK;
+    int rc = alloc_all("l2z_transformer_wide scratch",
+                       {{(void **)&b->k, R * kvd * 4}, {(void **)&b->v, R * kvd * 4}, {(void **)&b->logits, R * b->ld_logits * 4},
+                        {(void **)&b->part, wide_part_floats(c.n_heads, b->seg_cap, s->sh.hs) * 4},
+                        {(void **)&b->d_next, R * 4}, {(void **)&b->d_tab, sizeof(WideTable)}});
     auto hip = [&rc](hipError_t e) {
         if (rc == L2Z_OK && e != hipSuccess) {
             set_error("l2z_transformer_wide scratch: %s", hipGetErrorString(e));
@@ -92,19 +81,14 @@ int wide_alloc(l2z_runstate *s)
     for (hipEvent_t &e : b->ev_in) hip(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     hip(hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
     hip(hipEventCreateWithFlags(&b->ev_upload, hipEventDisableTiming));
-    if (rc != L2Z_OK) wide_free(s);
+    if (rc != L2Z_OK) wide_free(s);  // the next call starts over
     return rc;
 }
-
 
 // what an l2z_wide_run call of `entries` = n_steps * n ids needs beyond the step's own; sampled: the row body's scratch too
 int run_alloc(l2z_runstate *s, size_t entries, bool sampled)
 {
     WideScratch *b = s->wd;
-    auto fail = [](const char *what, size_t bytes, hipError_t e) {
-        set_error("l2z_wide_run %s allocation (%zu bytes) failed: %s", what, bytes, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
-    };
     if (entries > b->run_cap) {
         // (every earlier run has completed: the call is synchronous)
         if (b->d_ctl) (void)hipFree(b->d_ctl);
@@ -119,17 +103,15 @@ int run_alloc(l2z_runstate *s, size_t entries, bool sampled)
         if (e == hipSuccess) e = hipMalloc((void **)&b->d_ids, cap * 4);
         if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_ctl, ctl, hipHostMallocDefault);
         if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_ids, cap * 4, hipHostMallocDefault);
-        if (e != hipSuccess) return fail("coins / ids", ctl + cap * 4, e);  // (what was allocated is freed on the next attempt)
+        if (e != hipSuccess) {  // (what was allocated is freed on the next attempt)
+            set_error("l2z_wide_run coins / ids allocation (%zu bytes) failed: %s", ctl + cap * 4, hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
+        }
         b->run_cap = cap;
     }
-    if (sampled && b->smp == nullptr) {
-        const size_t bytes = (size_t)kWideMax * sample_scratch_floats(s->cfg.vocab_size) * 4;
-        const hipError_t e = hipMalloc((void **)&b->smp, bytes);
-        if (e != hipSuccess) {
-            b->smp = nullptr;
-            return fail("sampler scratch", bytes, e);
-        }
-    }
+    if (sampled)
+        L2Z_TRY(alloc_all("l2z_wide_run sampler scratch",
+                          {{(void **)&b->smp, (size_t)kWideMax * sample_scratch_floats(s->cfg.vocab_size) * 4}}));
     return L2Z_OK;
 }
 
@@ -143,36 +125,17 @@ int wide_checks(const char *fn, int n, const int32_t *tokens, const int32_t *pos
     *deepest = 0;
     for (int i = 0; i < n; i++) {
         L2Z_TRY(check_pair(config, states[i], w));
-        L2Z_CHECK(pos[i] >= 0 && pos[i] <= config->seq_len - n_steps, L2Z_ERR_STATE, "%s: pos[%d] = %d, %d step(s) outside [0,%d)",
-                  fn, i, pos[i], n_steps, config->seq_len);
-        L2Z_CHECK(tokens[i] >= 0 && tokens[i] < config->vocab_size, L2Z_ERR_STATE, "%s: tokens[%d] = %d out of vocabulary", fn, i,
-                  tokens[i]);
+        L2Z_TRY(check_row(fn, i, tokens[i], pos[i], n_steps, *config));
         if (pos[i] > *deepest) *deepest = pos[i];
     }
     return prefill_check(config, states[0]);
 }
 
-// the pass on states[0]'s stream waits for every runstate's stream ...
-int wide_join(WideScratch *b, int n, l2z_runstate *const *states)
-{
-    for (int i = 1; i < n; i++) {
-        L2Z_HIP(hipEventRecord(b->ev_in[i], states[i]->stream));
-        L2Z_HIP(hipStreamWaitEvent(states[0]->stream, b->ev_in[i], 0));
-    }
-    return L2Z_OK;
-}
-
-// ... and every runstate's stream waits for the pass; the host bookkeeping of a runstate whose next position is pos[i] + steps
+// every runstate's stream waits for the pass; the host bookkeeping of a runstate whose next position is pos[i] + steps
 int wide_release(WideScratch *b, int n, l2z_runstate *const *states, const int32_t *pos, int steps)
 {
-    L2Z_HIP(hipEventRecord(b->ev_done, states[0]->stream));
-    for (int i = 1; i < n; i++) L2Z_HIP(hipStreamWaitEvent(states[i]->stream, b->ev_done, 0));
-    for (int i = 0; i < n; i++) {
-        l2z_runstate *s = states[i];
-        s->n_part = 0;  // l2z_argmax scans the logits: the classifier left no per-block candidates
-        s->logits_partial = false;
-        s->host_pos = pos[i] + steps;
-    }
+    L2Z_TRY(release_streams(b, n, states));
+    for (int i = 0; i < n; i++) logits_whole(states[i], pos[i] + steps);
     return L2Z_OK;
 }
 
@@ -230,7 +193,7 @@ extern "C" int l2z_transformer_wide(int n, const int32_t *tokens, const int32_t 
     L2Z_TRY(wide_alloc(s0));
     WideScratch *b = s0->wd;
 
-    L2Z_TRY(wide_join(b, n, states));
+    L2Z_TRY(join_streams(b, n, states));
     L2Z_TRY(wide_upload_table(b, n, tokens, pos, states));
     L2Z_TRY(wide_step(s0, w, n, deepest, true, [&]() -> int {
         L2Z_HIP(launch_wide_logits_out(b->logits, b->ld_logits, b->d_tab, config->vocab_size, out_next ? b->d_next : nullptr, n, st));
@@ -259,19 +222,10 @@ extern "C" int l2z_wide_run(int n, const int32_t *first_tokens, const int32_t *p
     if (temperature != nullptr) {
         L2Z_CHECK(top_p != nullptr, L2Z_ERR_INVALID, "l2z_wide_run: top_p is NULL beside temperature");
         for (int i = 0; i < n; i++) {
-            L2Z_CHECK(std::isfinite(temperature[i]) && temperature[i] >= 0.0f, L2Z_ERR_INVALID,
-                      "l2z_wide_run: temperature[%d] = %g (finite, >= 0)", i, (double)temperature[i]);
-            L2Z_CHECK(top_p[i] >= 0.0f && top_p[i] <= 1.0f, L2Z_ERR_INVALID, "l2z_wide_run: top_p[%d] = %g outside [0, 1]", i,
-                      (double)top_p[i]);
+            L2Z_TRY(check_draw("l2z_wide_run", i, temperature[i], top_p[i], coins));
             if (temperature[i] == 0.0f) continue;
             sampled = true;
-            L2Z_CHECK(coins != nullptr, L2Z_ERR_INVALID, "l2z_wide_run: coins is NULL at temperature[%d] = %g", i,
-                      (double)temperature[i]);
-            for (int k = 0; k < n_steps; k++) {
-                const float coin = coins[(size_t)k * n + i];
-                L2Z_CHECK(coin >= 0.0f && coin < 1.0f, L2Z_ERR_INVALID, "l2z_wide_run: coins[%d][%d] = %g outside [0, 1)", k, i,
-                          (double)coin);
-            }
+            L2Z_TRY(check_coins("l2z_wide_run", coins, i, n_steps, n));  // the row's coin of every step: coins[k * n + i]
         }
     }
     l2z_runstate *s0 = states[0];
@@ -284,7 +238,7 @@ extern "C" int l2z_wide_run(int n, const int32_t *first_tokens, const int32_t *p
     WideScratch *b = s0->wd;
 
     // ---- the run, on states[0]'s stream: one join, the first step's table and the coins, n_steps steps back to back ----
-    L2Z_TRY(wide_join(b, n, states));
+    L2Z_TRY(join_streams(b, n, states));
     L2Z_TRY(wide_upload_table(b, n, first_tokens, pos0, states));
     WideDraw d = {};
     d.logits = b->logits; d.ld = b->ld_logits; d.vocab = config->vocab_size;

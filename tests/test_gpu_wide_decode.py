@@ -22,18 +22,23 @@ import numpy as np
 import pytest
 
 from test_gpu_parity import LOGIT_ATOL, LOGIT_RTOL
-from test_gpu_prefill_batch import SHAPES, bits, caches
+from test_gpu_prefill_batch import SHAPES as PROMPT_SHAPES, bits, caches
 
 pytestmark = pytest.mark.gpu
 
 KV_TOL = 2e-5   # a KV row against l2z_transformer_batch's
 WIDE = 128
+# The partial parts of the wide attention, which no prompt-pass shape reaches: a block serves up to 4 query heads of one kv
+# head.  `small`'s widths (every GEMM form takes them) with 6 heads on 2 kv heads -- kv_mul 3: one part of 3 heads in a
+# block made for 4 -- and on 1 kv head -- kv_mul 6: two parts, 4 + 2.
+PARTS = dict(dim=288, hidden_dim=768, n_layers=2, n_heads=6, vocab_size=1024, seq_len=160)
+SHAPES = dict(PROMPT_SHAPES, **{"kvmul3": dict(PARTS, n_kv_heads=2), "kvmul6": dict(PARTS, n_kv_heads=1)})
 # seeds picked on the CPU with the oracle alone: at most 5 % of a case's rows have a top-2 margin under the bar
-SEED = {"small": 23, "gqa": 23, "hs64": 23, "mqa-256": 23, "streams-2048": 23}
+SEED = {"small": 23, "gqa": 23, "hs64": 23, "mqa-256": 23, "streams-2048": 23, "kvmul3": 23, "kvmul6": 23}
 
 # (shape, n, L2Z_PF_X3): both sides of every GEMM-form switch-over on `small`, 33 and 128 on every other shape
 PARITY = ([("small", n, 1) for n in (1, 16, 17, 32, 33, 64, 65, 128)] +
-          [(s, n, 1) for s in ("gqa", "hs64", "mqa-256") for n in (33, 128)] +
+          [(s, n, 1) for s in ("gqa", "hs64", "mqa-256", "kvmul3", "kvmul6") for n in (33, 128)] +
           [("streams-2048", n, x3) for x3 in (1, 2) for n in (33, 128)])
 
 
@@ -224,7 +229,7 @@ def test_three_steps_against_oracles_of_their_own_and_the_batched_step(gpu, ck, 
         s.close()
 
 
-@pytest.mark.parametrize("shape,n", [("small", 33), ("small", 128), ("hs64", 33)])
+@pytest.mark.parametrize("shape,n", [("small", 33), ("small", 128), ("hs64", 33), ("kvmul3", 33), ("kvmul6", 33)])
 def test_neighbour_invariance_and_run_to_run(gpu, ck, worlds, shape, n):
     """a fixed n and a fixed place: row i's logits and KV row are the same bits whatever tokens, depths and prefixes the
     other rows hold, whatever stale rows its own cache holds beyond pos[i] -- and from run to run"""
