@@ -214,7 +214,8 @@ int l2z_sample_time(int n, l2z_runstate *const *states, const float *temperature
 int l2z_score_slab_set(l2z_runstate *s, int slab_cols);
 /* Row `row` (0 .. n_tokens - 1) of the logits matrix of this runstate's last l2z_verify or l2z_verify_sample call: every z_i, not only the
  * accepted z_a the runstate keeps (vocab_size floats).  L2Z_ERR_STATE when there is no such row.  Synchronous.  After
- * l2z_verify_batch the matrix is states[0]'s: row r of the concatenated rows; the call's other runstates have no row. */
+ * l2z_verify_batch and l2z_verify_wide the matrix is states[0]'s: row r of the concatenated rows; the call's other runstates
+ * have no row. */
 int l2z_verify_logits_read(l2z_runstate *s, int row, float *out);
 /* Measurement (scripts/verify_bench.py): one l2z_verify call, then `iters` passes back to back (verdict launches and
  * their copy included, no sync), timed by device events on the runstate's stream; *out_ms = milliseconds per pass.  The
@@ -415,6 +416,53 @@ int l2z_wide_run(int n, const int32_t *first_tokens, const int32_t *pos0, int n_
                  const float *coins /* [n_steps, n], row-major by step */,
                  const l2z_config *config, l2z_runstate *const *states, const l2z_weights *w,
                  int32_t *out_tokens /* [n_steps, n] */);
+
+/* ---- wide speculative decoding (preview) ----
+ * The verify pass of l2z_verify_batch for up to L2Z_WIDE_MAX rows in ONE sweep of the weights on the matrix cores: the rows
+ * are one chunk of R rows of the ragged prompt pass on states[0]'s prefill scratch, as l2z_transformer_wide's are, with
+ * several rows per sequence.  The arguments have l2z_verify_batch's meaning throughout: sequence j contributes n_tokens[j]
+ * consecutive positions from pos0[j], its first token known and the rest guesses; tokens, coins and out_next are the
+ * sequences' rows concatenated in order; temperature and top_p are per sequence (temperature == NULL: every sequence greedy,
+ * top_p and coins not read; a sequence at temperature 0 is arg-maxed and its coins are not read); out_accepted has n entries.
+ * 1 <= n <= L2Z_WIDE_MAX, 1 <= n_tokens[j] <= L2Z_BATCH_MAX, R = the sum of n_tokens[] <= L2Z_WIDE_MAX.
+ * Row r: z_r = the logits of its position given its sequence's tokens up to it on top of cache rows < pos0[j]; out_next[r] =
+ * the argmax of z_r, or the sampler's draw; out_accepted[j] = a_j, the number of leading guesses that equal the row before's
+ * out_next (found on the device).  State on return, per sequence, l2z_verify's: KV rows pos0[j] .. pos0[j] + n_tokens[j] - 1
+ * of every layer written -- and NO other cache row of any runstate --, the runstate's logits z_a, the next position
+ * pos0[j] + a_j + 1, and the host bookkeeping as l2z_transformer_wide leaves it (whole logits, no per-block argmax
+ * candidates): every other entry point goes on from there.
+ * The call is synchronous (one copy back, one sync).  Streams: l2z_transformer_batch's rule.  The scratch is states[0]'s wide
+ * scratch (freed with it); the sampler's is allocated on the first call with a positive temperature.  Afterwards
+ * l2z_verify_logits_read(states[0], r, ...) returns concatenated row r, r < R; on the call's other runstates it refuses with
+ * L2Z_ERR_STATE until that runstate's next verify call of its own.
+ * WHAT IS PROMISED.  The products take the whole model's GEMM form at R rows, so a row's bits depend on the total row count
+ * and possibly on the row's place: this call does NOT inherit the bit-for-bit DRAFT INVARIANCE across calls that l2z_verify,
+ * l2z_verify_sample, l2z_verify_batch and l2z_verify_tree have.  It promises:
+ *   ONE-ROW IDENTITY.  With every n_tokens[j] == 1 and all greedy, each runstate's logits, every cache row and out_next are
+ *     bit-identical to l2z_transformer_wide on the same states, tokens, positions and order: the same chunk of the same R
+ *     rows, and a slot's bits in the segment attention do not depend on how many slots a block has or on what a slot is.
+ *   NEIGHBOUR INVARIANCE.  For a fixed layout -- the same n, n_tokens[], pos0[] and order -- sequence j's out_next,
+ *     out_accepted[j], logits and KV rows are bit-identical whatever the other sequences' tokens and caches hold, whatever
+ *     stale rows lie beyond its own rows, and from run to run.
+ *   CAUSALITY within a call.  Row i of a sequence is a function of that sequence's tokens 0 .. i and the cache rows below
+ *     pos0 alone: changing the guesses behind row i leaves logits row i and KV row pos0 + i bit-identical.
+ *   PARITY.  Values against l2z_verify / l2z_verify_batch, and against the CPU oracle, agree at the fp32 parity bar, not bit
+ *     for bit.
+ *   THE DRAW.  Given row r's logits, out_next[r] is bit for bit the token l2z_sample_batch draws from them with the same
+ *     temperature, top_p and coin (the argmax by l2z_argmax's rule at temperature 0).
+ * l2z_verify_batch stays the form for R <= L2Z_BATCH_MAX and wherever the text must not depend on the drafter bit for bit.
+ * A refusal enqueues nothing and changes no state.  L2Z_ERR_INVALID: a NULL required argument, n outside [1, L2Z_WIDE_MAX],
+ * an n_tokens[j] outside [1, L2Z_BATCH_MAX], R > L2Z_WIDE_MAX, runstates that are not pairwise distinct, unsharded, on one
+ * device and made with *config, weights of another config, dims l2z_prefill refuses, a temperature[j] that is not finite and
+ * >= 0, a top_p[j] outside [0, 1] (or top_p == NULL beside temperature), coins == NULL with any temperature[j] > 0, a coin
+ * of such a sequence outside [0, 1).  L2Z_ERR_STATE: pos0[j] < 0, pos0[j] + n_tokens[j] > seq_len, a token outside the
+ * vocabulary.  L2Z_ERR_NO_DEVICE without a device.
+ * Out of scope: the product header, map, Zig shim and CLI (ABI version 3); sharded runstates; trees; the loop on the
+ * device; sharing a kv head's K / V rows between its query heads in the multi-row attention; hipGraph replay. */
+int l2z_verify_wide(int n, const int32_t *tokens, const int32_t *n_tokens, const int32_t *pos0,
+                    const float *temperature, const float *top_p, const float *coins,
+                    const l2z_config *config, l2z_runstate *const *states, const l2z_weights *w,
+                    int32_t *out_next, int32_t *out_accepted);
 
 #ifdef __cplusplus
 }

@@ -111,6 +111,8 @@ def lib():
         L.l2z_wide_run.argtypes = [C.c_int, i32p, i32p, C.c_int, fp, fp, fp, cfgp, C.POINTER(vp), vp, i32p]
     if hasattr(L, "l2z_verify_batch"):
         L.l2z_verify_batch.argtypes = [C.c_int, i32p, i32p, i32p, fp, fp, fp, cfgp, C.POINTER(vp), vp, i32p, i32p]
+    if hasattr(L, "l2z_verify_wide"):
+        L.l2z_verify_wide.argtypes = [C.c_int, i32p, i32p, i32p, fp, fp, fp, cfgp, C.POINTER(vp), vp, i32p, i32p]
     if hasattr(L, "l2z_verify_tree"):
         L.l2z_verify_tree.argtypes = [i32p, i32p, C.c_int, C.c_int, C.c_float, C.c_float, fp, cfgp, vp, vp, i32p, i32p, ip]
         L.l2z_verify_tree_time.argtypes = [i32p, i32p, C.c_int, C.c_int, C.c_float, C.c_float, fp, cfgp, vp, vp, C.c_int,
@@ -710,6 +712,18 @@ def verify_batch(states, token_lists, pos0s, w: Weights, temperature=None, top_p
     temperature and top_p are one value per sequence (or a scalar for all) and coin_lists[j] holds a coin per row of
     sequence j (None, or a None entry, where the temperature is 0): RunState.verify_sample per sequence.
     Returns (list of next arrays, accepted array).  states[0].verify_logits(r) then reads concatenated row r."""
+    return _verify_rows(lib().l2z_verify_batch, states, token_lists, pos0s, w, temperature, top_p, coin_lists)
+
+
+def verify_wide(states, token_lists, pos0s, w: Weights, temperature=None, top_p=None, coin_lists=None):
+    """l2z_verify_wide: verify_batch's call for up to WIDE_MAX rows in all (each sequence up to BATCH_MAX) in ONE sweep of the
+    weights on the matrix cores (a preview entry point of the test library: include/llama2_hip_test.h).  The arguments and
+    the return are verify_batch's; the values agree with RunState.verify's at the fp32 parity bar, not bit for bit."""
+    return _verify_rows(lib().l2z_verify_wide, states, token_lists, pos0s, w, temperature, top_p, coin_lists)
+
+
+def _verify_rows(call, states, token_lists, pos0s, w, temperature, top_p, coin_lists):
+    """the arguments l2z_verify_batch and l2z_verify_wide share, the call, and its outputs cut per sequence"""
     n = len(states)
     ss = (C.c_void_p * max(n, 1))(*[s.h for s in states])
     lists = [np.ascontiguousarray(t, np.int32).reshape(-1) for t in token_lists]
@@ -742,10 +756,10 @@ def verify_batch(states, token_lists, pos0s, w: Weights, temperature=None, top_p
     acc = np.zeros(max(n, 1), np.int32)
     cfg = states[0].cfg if n else L2ZConfig()
     i32p = C.POINTER(C.c_int32)
-    _chk(lib().l2z_verify_batch(n, t.ctypes.data_as(i32p), nt.ctypes.data_as(i32p), p0.ctypes.data_as(i32p),
-                                None if tp is None else _fp(tp), None if pp is None else _fp(pp),
-                                None if cp is None else _fp(cp), C.byref(cfg), ss, w.h, nxt.ctypes.data_as(i32p),
-                                acc.ctypes.data_as(i32p)))
+    _chk(call(n, t.ctypes.data_as(i32p), nt.ctypes.data_as(i32p), p0.ctypes.data_as(i32p),
+              None if tp is None else _fp(tp), None if pp is None else _fp(pp),
+              None if cp is None else _fp(cp), C.byref(cfg), ss, w.h, nxt.ctypes.data_as(i32p),
+              acc.ctypes.data_as(i32p)))
     ends = np.cumsum(nt[:n])
     return [nxt[e - m: e].copy() for e, m in zip(ends, nt[:n])], acc[:n].copy()
 
@@ -1007,11 +1021,29 @@ def speculate_batch(states, w: Weights, prompts, n_steps: int, k: int, drafter=N
     speculate_sample's on a fresh runstate, bit for bit, whatever the other sequences are).
     Returns (list of token arrays, stats): per sequence the return convention of speculate_greedy; stats is per call:
     speculate_greedy's keys plus "rows" (rows of all verify_batch calls) and "rows_per_call" (a list)."""
+    return _speculate_rows(verify_batch, BATCH_MAX, False, states, w, prompts, n_steps, k, drafter, temperature, top_p, coins,
+                           batched_prefill)
+
+
+def speculate_wide(states, w: Weights, prompts, n_steps: int, k: int, drafter=None, *, temperature=None, top_p=None,
+                   coins=None):
+    """speculate_batch's loop over verify_wide, for up to WIDE_MAX sequences: every round ONE verify_wide call advances all
+    the sequences still running.  Each asks for min(k + 1, 16) rows -- its last token and the drafter's guesses; when the
+    rows asked for exceed WIDE_MAX the guesses are trimmed evenly (every sequence gets WIDE_MAX // live rows, the first
+    WIDE_MAX % live one more).  The drafter, the position-indexed coins, the cut at BOS and the return convention are
+    speculate_batch's; the prompts go through prefill_batch in groups of BATCH_MAX sequences.  The ids agree with
+    speculate_batch's up to the fp32 parity bar: a verify_wide row's bits depend on the call's layout."""
+    return _speculate_rows(verify_wide, WIDE_MAX, True, states, w, prompts, n_steps, k, drafter, temperature, top_p, coins, True)
+
+
+def _speculate_rows(verify, n_max, spread, states, w, prompts, n_steps, k, drafter, temperature, top_p, coins, batched_prefill):
+    """the loop speculate_batch and speculate_wide share; verify: verify_batch or verify_wide, for up to n_max sequences
+    and as many rows a call; spread: the rows that n_max leaves over an even share go to the first sequences"""
     if not 0 <= k <= BATCH_MAX - 1:
         raise ValueError(f"k = {k} outside [0, {BATCH_MAX - 1}]")
     n = len(states)
-    if not 1 <= n <= BATCH_MAX or len(prompts) != n:
-        raise ValueError(f"{n} runstates and {len(prompts)} prompts (1 .. {BATCH_MAX}, one prompt each)")
+    if not 1 <= n <= n_max or len(prompts) != n:
+        raise ValueError(f"{n} runstates and {len(prompts)} prompts (1 .. {n_max}, one prompt each)")
     if drafter is None:
         drafter = lookup_draft
     sampled = temperature is not None
@@ -1043,14 +1075,19 @@ def speculate_batch(states, w: Weights, prompts, n_steps: int, k: int, drafter=N
     first = [j for j in range(n) if alive[j] and pos[j] < steps]
     if first:
         if batched_prefill:
-            prefill_batch([states[j] for j in first], [np.array(hist[j], np.int32) for j in first], 0, w)
+            for g in range(0, len(first), BATCH_MAX):
+                grp = first[g: g + BATCH_MAX]
+                prefill_batch([states[j] for j in grp], [np.array(hist[j], np.int32) for j in grp], 0, w)
         else:
             for j in first:
                 states[j].prefill(np.array(hist[j], np.int32), 0, w)
-        if sampled:
-            ids = sample_batch([states[j] for j in first], temps[first], tops[first], [coins[j][0] for j in first])
-        else:
-            ids = argmax_batch([states[j] for j in first])
+        ids = []
+        for g in range(0, len(first), BATCH_MAX):
+            grp = first[g: g + BATCH_MAX]
+            if sampled:
+                ids.extend(sample_batch([states[j] for j in grp], temps[grp], tops[grp], [coins[j][0] for j in grp]))
+            else:
+                ids.extend(argmax_batch([states[j] for j in grp]))
         for j, t in zip(first, ids):
             emit(j, t)
             gen[j] += 1
@@ -1058,9 +1095,10 @@ def speculate_batch(states, w: Weights, prompts, n_steps: int, k: int, drafter=N
         live = [j for j in range(n) if alive[j] and pos[j] < steps]
         if not live:
             break
-        rows_each = min(k + 1, BATCH_MAX // len(live))
         lists, clists = [], []
-        for j in live:
+        share, over = divmod(n_max, len(live))
+        for i, j in enumerate(live):
+            rows_each = min(k + 1, BATCH_MAX, share + (spread and i < over))
             kk = min(rows_each - 1, steps - pos[j] - 1)
             guesses = [int(g) for g in drafter(np.array(hist[j], np.int32), kk)][:kk] if kk > 0 else []
             lists.append([hist[j][-1]] + guesses)
@@ -1068,9 +1106,9 @@ def speculate_batch(states, w: Weights, prompts, n_steps: int, k: int, drafter=N
                 clists.append(coins[j][gen[j]: gen[j] + 1 + len(guesses)])
             stats["offered"] += len(guesses)
         if sampled:
-            nxts, accs = verify_batch([states[j] for j in live], lists, [pos[j] for j in live], w, temps[live], tops[live], clists)
+            nxts, accs = verify([states[j] for j in live], lists, [pos[j] for j in live], w, temps[live], tops[live], clists)
         else:
-            nxts, accs = verify_batch([states[j] for j in live], lists, [pos[j] for j in live], w)
+            nxts, accs = verify([states[j] for j in live], lists, [pos[j] for j in live], w)
         stats["calls"] += 1
         stats["rows"] += sum(len(t) for t in lists)
         stats["rows_per_call"].append(sum(len(t) for t in lists))

@@ -338,6 +338,7 @@ struct RaggedChunk {
     float *k, *v;           // scratch: the chunk's key / value rows [P, kv_dim] between the product and the scatter
     const WideAttn *wide;   // != null (l2z_transformer_wide): every row is a sequence of its own at one position -- the
                             // attention is launch_wide_attention (wide_decode.h) on this table; tiles and n_tiles are not read
+                            // (wide->verify_m != 0, l2z_verify_wide: sequences of several rows, launch_wide_verify_attention)
 };
 // q [P, dim] rotated in place, k rotated, and k / v stored into row row_pos[r] of sequence row_seq[r]'s caches: the
 // arithmetic of the q | k | v product's own epilogue (prefill_gemm.hip), one launch

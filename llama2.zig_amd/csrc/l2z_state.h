@@ -213,5 +213,9 @@ int prefill_rows_logits(l2z_runstate *s, const l2z_weights *w, int P, float *out
 void batch_free(l2z_runstate *s);
 // wide_host.cpp
 void wide_free(l2z_runstate *s);
+// l2z_verify_logits_read: row `row` of the logits matrix of s's last l2z_verify_wide call as states[0] (null: s's last verify
+// call was not that, or the matrix has no such row); and the end of that: another call has taken the matrix or s's turn
+const float *wide_verify_row(const l2z_runstate *s, int row);
+void wide_verify_forget(l2z_runstate *s);
 
 }  // namespace l2z

@@ -312,7 +312,11 @@ int prefill_stage(l2z_runstate *s, const l2z_weights *w, int l, int k, int P, in
         L2Z_HIP(launch_ragged_rope_scatter(s->pf_q, dim, *rg, P, dim, kvd, hs, s->rope, layer_off, kvh_stride, st));
         bool att_planes = false;
         const bool want = planes_for(dim, dim, sk_wo);
-        if (rg->wide != nullptr)   // one row per sequence: the position-split decode attention (wide_decode.hip)
+        if (rg->wide != nullptr && rg->wide->verify_m != 0)   // l2z_verify_wide: a sequence's rows are a block's slots (wide_verify.hip)
+            L2Z_HIP(launch_wide_verify_attention(s->pf_q, dim, out, ldo, *rg->wide, rg->n_seq, P, c.n_heads, hs, layer_off,
+                                                 kvh_stride, c.n_heads / c.n_kv_heads, st, want ? ws->x3 : nullptr, dim,
+                                                 &att_planes));
+        else if (rg->wide != nullptr)   // one row per sequence: the position-split decode attention (wide_decode.hip)
             L2Z_HIP(launch_wide_attention(s->pf_q, dim, out, ldo, *rg->wide, P, c.n_heads, hs, layer_off, kvh_stride,
                                           c.n_heads / c.n_kv_heads, st, want ? ws->x3 : nullptr, dim, &att_planes));
         else

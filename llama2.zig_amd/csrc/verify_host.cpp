@@ -74,6 +74,7 @@ void verify_done(l2z_runstate *s, int rows)
 {
     logits_whole(s, s->host_pos);  // (the caller moves the position once it has read the verdict)
     if (s->bt != nullptr) s->bt->v_rows = rows;
+    wide_verify_forget(s);
 }
 
 // ---- l2z_verify, l2z_verify_sample: n consecutive positions of ONE sequence in one sweep ----
@@ -191,6 +192,12 @@ extern "C" int l2z_verify_logits_read(l2z_runstate *s, int row, float *out)
 {
     L2Z_TRY(no_device_check());
     L2Z_CHECK(s != nullptr && out != nullptr, L2Z_ERR_INVALID, "l2z_verify_logits_read: null argument");
+    if (const float *wide = wide_verify_row(s, row)) {  // the last verify call was l2z_verify_wide with s as states[0]
+        L2Z_HIP(hipSetDevice(s->device));
+        L2Z_HIP(hipMemcpyAsync(out, wide, (size_t)s->cfg.vocab_size * 4, hipMemcpyDeviceToHost, s->stream));
+        L2Z_HIP(hipStreamSynchronize(s->stream));
+        return L2Z_OK;
+    }
     L2Z_CHECK(s->bt != nullptr && s->bt->v_logits != nullptr && row >= 0 && row < s->bt->v_rows, L2Z_ERR_STATE,
               "l2z_verify_logits_read: row %d is not a row of this runstate's last l2z_verify call", row);
     L2Z_HIP(hipSetDevice(s->device));

@@ -3,7 +3,8 @@
 // verify family's segment body, verify_device.h, with a kv head's query heads as a block's slots), and the launch that
 // hands the [n, vocab] logits matrix back to the runstates.  Every row's token, position, caches and
 // logits come from one device table.  And the last launch of a step inside l2z_wide_run (wide_sample.hip): every row's
-// draw, and the hand-over of token and position to the next step on the device.
+// draw, and the hand-over of token and position to the next step on the device.  And what l2z_verify_wide puts in their
+// place (wide_verify.hip): attention whose slots are the rows of ONE sequence, and the verdict per sequence.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -41,6 +42,8 @@ struct WideAttn {
     float *part;           // wide_part_floats
     int seg_cap;           // verify_segments(seq_len)
     int n_seg;             // segments of the deepest row of this step: the grid's extent
+    int verify_m;          // 0: one row per sequence (launch_wide_attention); l2z_verify_wide: the slots of a block, the
+                           // smallest of 1, 2, 4, 8, 16 that holds the call's longest sequence (launch_wide_verify_attention)
 };
 
 // Decode attention (main.zig:361-389) of rows 0 .. n - 1 of q [n, ldq] (RoPE applied) into out [n, ldo], two launches:
@@ -54,6 +57,9 @@ struct WideAttn {
 hipError_t launch_wide_attention(const float *q, int ldq, float *out, int ldo, const WideAttn &wa, int n, int n_heads,
                                  int head_size, size_t layer_off, size_t kv_head_stride, int kv_mul, hipStream_t st,
                                  void *x3 = nullptr, int kp = 0, bool *planes_written = nullptr);
+// wide_combine alone, over the partials some attention launch left for rows 0 .. n - 1 (tab->pos[row] = the row's position)
+hipError_t launch_wide_combine(float *out, int ldo, const WideAttn &wa, int n, int n_heads, int head_size, hipStream_t st,
+                               void *x3 = nullptr, int kp = 0, bool *planes_written = nullptr);
 
 // Row i of logits [n, ld] -> tab->logits[i][0 .. vocab) (float4 where both sides are 16-byte aligned), and, next != null,
 // next[i] = the row's argmax by argmax_rule.h (strict '>', lowest index wins).  One launch, one block per row.
@@ -79,5 +85,44 @@ struct WideDraw {
     bool logits_out;
 };
 hipError_t launch_wide_draw_advance(const WideDraw &d, int n, hipStream_t st);
+
+// ---- l2z_verify_wide (wide_verify.hip): the table's sequence slot j is ONE sequence's seq[j].rows <= kBatchMax consecutive
+// positions from seq[j].pos0 on, rows seq[j].row0 .. of the chunk; row_seq[r], pos[r] and tokens[r] are per row, logits[j]
+// is per SEQUENCE: the runstate's logits the verdict fills ----
+
+// Causal attention of rows 0 .. n_rows - 1 of q [n_rows, ldq] (RoPE applied) into out [n_rows, ldo], two launches:
+//   wide_verify_attention<M>: block (head, segment, sequence), M = wa.verify_m; its slots are the sequence's rows of that
+//     head as verify_attention_body sets them up (row i sees the keys t <= pos0 + i; the rows that end before the segment
+//     are out of use), the q slices and partials addressed through the wide step's row-indexed layout.  A block past its
+//     own sequence's last segment returns.  A kv head's K / V rows are read once per QUERY head here: sharing them between
+//     the query heads of a kv head, as wide_attention does, needs slot strides in two dimensions.
+//   wide_combine, as it stands: a row's segments 0 .. pos[row] / kVerifySeg, and the bf16 planes.
+// Every summation order is verify_device.h's; no block touches two sequences.  wa.n_seg: the segments of the deepest
+// sequence's last position.
+hipError_t launch_wide_verify_attention(const float *q, int ldq, float *out, int ldo, const WideAttn &wa, int n_seq, int n_rows,
+                                        int n_heads, int head_size, size_t layer_off, size_t kv_head_stride, int kv_mul,
+                                        hipStream_t st, void *x3 = nullptr, int kp = 0, bool *planes_written = nullptr);
+
+// The per-sequence controls of a sampled call, behind the WideTable in the same allocations and the same copy
+struct WideVerdictCtl {
+    float temperature[kWideMax], top_p[kWideMax];  // per sequence
+    float coins[kWideMax];                         // per row
+};
+// The verdict of l2z_verify_wide, two launches.  The draw: one block of 1024 threads per row, next[r] = the token the
+// sampler's row body (sample_device.h) draws from row r of logits [n_rows, ld] with its sequence's temperature and top_p and
+// coins[r] -- the argmax at temperature 0 or ctl == null, where neither coin nor scratch is read.  The accept: one block per
+// sequence, a = the number of leading guesses tokens[row0 + i + 1] == next[row0 + i] (verify_batch_accept_kernel's scan over
+// the sequence's own rows) -> accepted[j], and row row0 + a of the matrix -> tab->logits[j] (wide_logits_out's copy).
+struct WideVerdict {
+    const float *logits;
+    int ld, vocab;
+    const WideTable *tab;
+    const WideVerdictCtl *ctl;  // null: every sequence greedy
+    float *scratch;             // row_stride floats per row, sample_scratch_floats(vocab) at least; null: no sequence draws
+    size_t row_stride;
+    int *next;                  // [n_rows]
+    int *accepted;              // [n_seq]
+};
+hipError_t launch_wide_verdict(const WideVerdict &d, int n_seq, int n_rows, hipStream_t st);
 
 }  // namespace l2z

@@ -102,23 +102,40 @@ __global__ __launch_bounds__(1024) void wide_logits_out(const float *logits, int
 
 }  // namespace
 
+// what both launchers ask of the partials and the output, and the arguments the combine reads
+static bool wide_out_args(WideAttnArgs &a, float *out, int ldo, const WideAttn &wa, int n, int n_heads, int head_size, void *x3,
+                          int kp)
+{
+    if (n < 1 || n > kWideMax || head_size < 4 || head_size > 256 || (head_size & 3) || n_heads < 1 || wa.tab == nullptr ||
+        wa.part == nullptr || wa.n_seg < 1 || wa.n_seg > wa.seg_cap || (ldo & 3) || (((uintptr_t)out | (uintptr_t)wa.part) & 15))
+        return false;
+    a.out = out; a.tab = wa.tab;
+    a.part_o = wa.part;
+    a.part_ml = wa.part + (size_t)kWideMax * n_heads * wa.seg_cap * head_size;
+    a.ldo = ldo; a.n_heads = n_heads; a.head_size = head_size; a.seg_cap = wa.seg_cap;
+    if (x3 != nullptr && (kp & 3) == 0 && (((uintptr_t)x3) & 7) == 0) { a.x3 = (__bf16 *)x3; a.kp = kp; }
+    return true;
+}
+
+static hipError_t combine_launch(const WideAttnArgs &a, int n, hipStream_t st, bool *planes_written)
+{
+    hipLaunchKernelGGL(wide_combine, dim3(a.n_heads, n), dim3(64), 0, st, a);
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess && planes_written) *planes_written = a.x3 != nullptr;
+    return e;
+}
+
 hipError_t launch_wide_attention(const float *q, int ldq, float *out, int ldo, const WideAttn &wa, int n, int n_heads,
                                  int head_size, size_t layer_off, size_t kv_head_stride, int kv_mul, hipStream_t st, void *x3,
                                  int kp, bool *planes_written)
 {
     if (planes_written) *planes_written = false;
-    if (n < 1 || n > kWideMax || head_size < 4 || head_size > 256 || (head_size & 3) || kv_mul < 1 || n_heads < 1 ||
-        n_heads % kv_mul != 0 || wa.tab == nullptr || wa.part == nullptr || wa.n_seg < 1 || wa.n_seg > wa.seg_cap ||
-        (ldq & 3) || (ldo & 3) || (((uintptr_t)q | (uintptr_t)out | (uintptr_t)wa.part) & 15) || (layer_off & 3) ||
-        (kv_head_stride & 3))
-        return hipErrorInvalidValue;
     WideAttnArgs a = {};
-    a.q = q; a.out = out; a.tab = wa.tab;
-    a.part_o = wa.part;
-    a.part_ml = wa.part + (size_t)kWideMax * n_heads * wa.seg_cap * head_size;
+    if (!wide_out_args(a, out, ldo, wa, n, n_heads, head_size, x3, kp) || kv_mul < 1 || n_heads % kv_mul != 0 || (ldq & 3) ||
+        (((uintptr_t)q) & 15) || (layer_off & 3) || (kv_head_stride & 3))
+        return hipErrorInvalidValue;
+    a.q = q; a.ldq = ldq; a.kv_mul = kv_mul;
     a.layer_off = layer_off; a.kv_head_stride = kv_head_stride;
-    a.ldq = ldq; a.ldo = ldo; a.n_heads = n_heads; a.kv_mul = kv_mul; a.head_size = head_size; a.seg_cap = wa.seg_cap;
-    if (x3 != nullptr && (kp & 3) == 0 && (((uintptr_t)x3) & 7) == 0) { a.x3 = (__bf16 *)x3; a.kp = kp; }
     const int mq = kv_mul == 1 ? 1 : kv_mul == 2 ? 2 : kWaHeadsMax;
     const dim3 grid(n_heads / kv_mul * ((kv_mul + mq - 1) / mq), wa.n_seg, n);
     switch (mq) {
@@ -126,12 +143,18 @@ hipError_t launch_wide_attention(const float *q, int ldq, float *out, int ldo, c
         case 2: hipLaunchKernelGGL(wide_attention<2>, grid, dim3(kVaBlock), 0, st, a); break;
         default: hipLaunchKernelGGL(wide_attention<kWaHeadsMax>, grid, dim3(kVaBlock), 0, st, a); break;
     }
-    hipError_t e = hipGetLastError();
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(wide_combine, dim3(n_heads, n), dim3(64), 0, st, a);
-    e = hipGetLastError();
-    if (e == hipSuccess && planes_written) *planes_written = a.x3 != nullptr;
-    return e;
+    return combine_launch(a, n, st, planes_written);
+}
+
+hipError_t launch_wide_combine(float *out, int ldo, const WideAttn &wa, int n, int n_heads, int head_size, hipStream_t st,
+                               void *x3, int kp, bool *planes_written)
+{
+    if (planes_written) *planes_written = false;
+    WideAttnArgs a = {};
+    if (!wide_out_args(a, out, ldo, wa, n, n_heads, head_size, x3, kp)) return hipErrorInvalidValue;
+    return combine_launch(a, n, st, planes_written);
 }
 
 hipError_t launch_wide_logits_out(const float *logits, int ld, const WideTable *tab, int vocab, int *next, int n, hipStream_t st)

@@ -1,10 +1,15 @@
-// wide_host.cpp -- host side of l2z_transformer_wide and l2z_wide_run (include/llama2_hip_test.h): up to L2Z_WIDE_MAX
-// independent sequences advanced by one token with one sweep of the weights, and the loop of such steps kept on the device.
+// wide_host.cpp -- host side of l2z_transformer_wide, l2z_wide_run and l2z_verify_wide (include/llama2_hip_test.h): up to
+// L2Z_WIDE_MAX independent sequences advanced by one token with one sweep of the weights, the loop of such steps kept on the
+// device, and the verify pass over up to L2Z_WIDE_MAX rows of many sequences.
 // The rows are ONE chunk of P = n rows of the ragged prompt pass (prefill_host.cpp) on states[0]'s prefill scratch and
 // stream, so every product takes the whole model's form at that row count (short-prompt / panel / stream / tile, f32 or
 // bf16 cores); what the step adds is the table with one sequence slot per row, the position-split decode attention and its
 // last launch: the one that hands the [n, vocab] logits back (wide_decode.hip), or, inside a run, the one that draws every
-// row's token and hands the row to the next step (wide_sample.hip).
+// row's token and hands the row to the next step (wide_sample.hip).  l2z_verify_wide is the same chunk with sequences of
+// several rows: the table's slots are sequences, the attention takes a sequence's rows as a block's slots, and the last
+// launches are the verdict (wide_verify.hip).
+#include <algorithm>
+#include <cstdio>
 #include <cstring>
 
 #include "batch_host.h"
@@ -24,8 +29,9 @@ struct WideScratch {
     int ld_logits = 0;                  // vocab_size rounded up to 4: every row 16-byte aligned
     float *part = nullptr;              // wide_part_floats
     int seg_cap = 0;
-    int *d_next = nullptr, *h_next = nullptr;
-    WideTable *d_tab = nullptr, *h_tab = nullptr;
+    int *d_next = nullptr, *h_next = nullptr;   // [2 kWideMax]: the rows' ids; l2z_verify_wide: next[0 .. R) | accepted[0 .. n)
+    WideTable *d_tab = nullptr, *h_tab = nullptr;   // with room for l2z_verify_wide's WideVerdictCtl behind
+    int v_rows = 0;                     // rows of the logits matrix l2z_verify_logits_read may read: the last call was l2z_verify_wide
     hipEvent_t ev_in[kWideMax] = {};
     hipEvent_t ev_done = nullptr;
     hipEvent_t ev_upload = nullptr;     // the last table copy: the pinned table may be rewritten once it has completed
@@ -55,7 +61,21 @@ void wide_free(l2z_runstate *s)
     s->wd = nullptr;
 }
 
+const float *wide_verify_row(const l2z_runstate *s, int row)
+{
+    const WideScratch *b = s->wd;
+    return b != nullptr && row >= 0 && row < b->v_rows ? b->logits + (size_t)row * b->ld_logits : nullptr;
+}
+
+void wide_verify_forget(l2z_runstate *s)
+{
+    if (s->wd != nullptr) s->wd->v_rows = 0;
+}
+
 namespace {
+
+constexpr size_t kTabBytes = sizeof(WideTable) + sizeof(WideVerdictCtl);
+static_assert(sizeof(WideTable) % alignof(WideVerdictCtl) == 0, "the controls sit right behind the table");
 
 int wide_alloc(l2z_runstate *s)
 {
@@ -69,15 +89,15 @@ int wide_alloc(l2z_runstate *s)
     int rc = alloc_all("l2z_transformer_wide scratch",
                        {{(void **)&b->k, R * kvd * 4}, {(void **)&b->v, R * kvd * 4}, {(void **)&b->logits, R * b->ld_logits * 4},
                         {(void **)&b->part, wide_part_floats(c.n_heads, b->seg_cap, s->sh.hs) * 4},
-                        {(void **)&b->d_next, R * 4}, {(void **)&b->d_tab, sizeof(WideTable)}});
+                        {(void **)&b->d_next, 2 * R * 4}, {(void **)&b->d_tab, kTabBytes}});
     auto hip = [&rc](hipError_t e) {
         if (rc == L2Z_OK && e != hipSuccess) {
             set_error("l2z_transformer_wide scratch: %s", hipGetErrorString(e));
             rc = L2Z_ERR_HIP;
         }
     };
-    hip(hipHostMalloc((void **)&b->h_tab, sizeof(WideTable), hipHostMallocDefault));
-    hip(hipHostMalloc((void **)&b->h_next, R * 4, hipHostMallocDefault));
+    hip(hipHostMalloc((void **)&b->h_tab, kTabBytes, hipHostMallocDefault));
+    hip(hipHostMalloc((void **)&b->h_next, 2 * R * 4, hipHostMallocDefault));
     for (hipEvent_t &e : b->ev_in) hip(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     hip(hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
     hip(hipEventCreateWithFlags(&b->ev_upload, hipEventDisableTiming));
@@ -135,37 +155,57 @@ int wide_checks(const char *fn, int n, const int32_t *tokens, const int32_t *pos
 int wide_release(WideScratch *b, int n, l2z_runstate *const *states, const int32_t *pos, int steps)
 {
     L2Z_TRY(release_streams(b, n, states));
-    for (int i = 0; i < n; i++) logits_whole(states[i], pos[i] + steps);
+    for (int i = 0; i < n; i++) {
+        logits_whole(states[i], pos[i] + steps);
+        wide_verify_forget(states[i]);  // (states[0]'s matrix is this call's now)
+    }
     return L2Z_OK;
 }
 
-// the table of a step (a run: of its first step), one copy from the pinned buffer (rewritten only once the last copy is done)
-int wide_upload_table(WideScratch *b, int n, const int32_t *tokens, const int32_t *pos, l2z_runstate *const *states)
+// the table of a step (a run: of its first step), one copy from the pinned buffer (rewritten only once the last copy is done).
+// n_tokens == null: a row per sequence, at pos[i].  l2z_verify_wide: sequence i's n_tokens[i] rows stand behind one another
+// from pos[i] on, tokens is per row, and, temperature != null, the sequences' controls and the rows' coins go up behind the
+// table in the same copy (a greedy sequence's coins are not read: 0 in their place).
+int wide_upload_table(WideScratch *b, int n, const int32_t *tokens, const int32_t *pos, l2z_runstate *const *states,
+                      const int32_t *n_tokens = nullptr, const float *temperature = nullptr, const float *top_p = nullptr,
+                      const float *coins = nullptr)
 {
     L2Z_HIP(hipEventSynchronize(b->ev_upload));
     WideTable *t = b->h_tab;
-    for (int i = 0; i < n; i++) {
-        t->seq[i] = {states[i]->key_cache, states[i]->value_cache, i, 1, pos[i], 0};
-        t->row_seq[i] = i;
-        t->pos[i] = pos[i];
-        t->tokens[i] = tokens[i];
+    WideVerdictCtl *ctl = (WideVerdictCtl *)(t + 1);
+    for (int i = 0, r = 0; i < n; i++) {
+        const int rows = n_tokens ? n_tokens[i] : 1;
+        t->seq[i] = {states[i]->key_cache, states[i]->value_cache, r, rows, pos[i], 0};
         t->logits[i] = states[i]->logits;
+        if (temperature) {
+            ctl->temperature[i] = temperature[i];
+            ctl->top_p[i] = top_p[i];
+        }
+        for (int k = 0; k < rows; k++, r++) {
+            t->row_seq[r] = i;
+            t->pos[r] = pos[i] + k;
+            t->tokens[r] = tokens[r];
+            if (temperature) ctl->coins[r] = temperature[i] > 0.0f ? coins[r] : 0.0f;
+        }
     }
-    L2Z_HIP(hipMemcpyAsync(b->d_tab, t, sizeof(WideTable), hipMemcpyHostToDevice, states[0]->stream));
+    L2Z_HIP(hipMemcpyAsync(b->d_tab, t, temperature ? kTabBytes : sizeof(WideTable), hipMemcpyHostToDevice, states[0]->stream));
     return L2Z_OK;
 }
 
-// The launches of ONE step of n rows on s0's stream, the same for both entry points: the rows as one chunk of the ragged
+// The launches of ONE step of n rows on s0's stream, the same for every entry point: the rows as one chunk of the ragged
 // prompt pass driven by the device table (deepest: the step's deepest position, the attention grid's segment extent),
 // the classifier over all rows into b->logits, then the step's last launch.  from_table: the rows' ids go up from the
 // pinned table (the caller's array is free on return); otherwise they stand in pf_tokens, written by the step before.
-int wide_step(l2z_runstate *s0, const l2z_weights *w, int n, int deepest, bool from_table, FnRef<int()> last)
+// n_seq, verify_m: the step's own are n and 0, a sequence per row; l2z_verify_wide's are its sequences and the slots of
+// an attention block.
+int wide_step(l2z_runstate *s0, const l2z_weights *w, int n, int deepest, bool from_table, FnRef<int()> last, int n_seq = 0,
+              int verify_m = 0)
 {
     WideScratch *b = s0->wd;
-    WideAttn wa = {b->d_tab, b->part, b->seg_cap, deepest / kVerifySeg + 1};
+    WideAttn wa = {b->d_tab, b->part, b->seg_cap, deepest / kVerifySeg + 1, verify_m};
     RaggedChunk rg = {};
     rg.seq = b->d_tab->seq; rg.row_seq = b->d_tab->row_seq; rg.row_pos = b->d_tab->pos;
-    rg.n_seq = n;
+    rg.n_seq = verify_m ? n_seq : n;
     rg.k = b->k; rg.v = b->v;
     rg.wide = &wa;
     L2Z_TRY(prefill_ragged_chunk(s0, w, from_table ? b->h_tab->tokens : nullptr, n, rg));
@@ -266,5 +306,91 @@ extern "C" int l2z_wide_run(int n, const int32_t *first_tokens, const int32_t *p
     L2Z_TRY(wide_release(b, n, states, pos0, n_steps));
     L2Z_HIP(hipStreamSynchronize(st));
     memcpy(out_tokens, b->h_ids, entries * 4);
+    return L2Z_OK;
+}
+
+// ---- l2z_verify_wide: the verify pass for up to kWideMax rows of many sequences in one sweep (include/llama2_hip_test.h) ----
+extern "C" int l2z_verify_wide(int n, const int32_t *tokens, const int32_t *n_tokens, const int32_t *pos0,
+                               const float *temperature, const float *top_p, const float *coins, const l2z_config *config,
+                               l2z_runstate *const *states, const l2z_weights *w, int32_t *out_next, int32_t *out_accepted)
+{
+    const char *fn = "l2z_verify_wide";
+    // ---- checks: a refusal enqueues nothing and changes no state (l2z_verify_batch's, with the wide limits) ----
+    L2Z_TRY(no_device_check());
+    L2Z_CHECK(tokens != nullptr && n_tokens != nullptr && pos0 != nullptr && config != nullptr && w != nullptr &&
+                  out_next != nullptr && out_accepted != nullptr,
+              L2Z_ERR_INVALID, "%s: null argument", fn);
+    L2Z_TRY(check_states(fn, n, states, config, kWideMax));
+    int R = 0, longest = 0, deepest = 0;
+    for (int j = 0; j < n; j++) {
+        L2Z_CHECK(n_tokens[j] >= 1 && n_tokens[j] <= kBatchMax, L2Z_ERR_INVALID, "%s: n_tokens[%d] = %d outside [1, %d]", fn, j,
+                  n_tokens[j], kBatchMax);
+        R += n_tokens[j];
+        longest = std::max(longest, n_tokens[j]);
+    }
+    L2Z_CHECK(R <= kWideMax, L2Z_ERR_INVALID, "%s: %d rows in all, above %d", fn, R, kWideMax);
+    for (int j = 0; j < n; j++) L2Z_TRY(check_pair(config, states[j], w));
+    L2Z_TRY(prefill_check(config, states[0]));
+    L2Z_CHECK(states[0]->sh.hs <= 256, L2Z_ERR_INVALID, "%s: head_size above 256", fn);
+    bool sampled = false;  // some sequence draws: l2z_sample_batch's rules for it
+    if (temperature != nullptr) {
+        L2Z_CHECK(top_p != nullptr, L2Z_ERR_INVALID, "%s: top_p is NULL beside a temperature array", fn);
+        for (int j = 0, r = 0; j < n; r += n_tokens[j], j++) {
+            L2Z_TRY(check_draw(fn, j, temperature[j], top_p[j], coins));
+            if (temperature[j] == 0.0f) continue;
+            sampled = true;
+            L2Z_TRY(check_coins(fn, coins, r, n_tokens[j]));
+        }
+    }
+    for (int j = 0, r = 0; j < n; r += n_tokens[j], j++) {
+        char where[32];
+        snprintf(where, sizeof where, "sequence %d: ", j);
+        L2Z_TRY(check_positions(fn, where, "positions", pos0[j], n_tokens[j], config->seq_len));
+        L2Z_TRY(check_tokens(fn, where, tokens + r, n_tokens[j], config->vocab_size));
+        deepest = std::max(deepest, pos0[j] + n_tokens[j] - 1);
+    }
+    l2z_runstate *s0 = states[0];
+    hipStream_t st = s0->stream;
+    L2Z_HIP(hipSetDevice(s0->device));
+    L2Z_TRY(prefill_scratch(s0, R));
+    L2Z_TRY(wide_alloc(s0));
+    WideScratch *b = s0->wd;
+    if (sampled)
+        L2Z_TRY(alloc_all("l2z_verify_wide sampler scratch",
+                          {{(void **)&b->smp, (size_t)kWideMax * sample_scratch_floats(config->vocab_size) * 4}}));
+    int m = 1;  // the smallest instantiation that holds the longest sequence
+    while (m < longest) m <<= 1;
+
+    // ---- the pass, on states[0]'s stream: the table (a slot per sequence, its rows behind one another), the chunk of R
+    // rows, the classifier over all of them, the verdict, one copy back ----
+    // (a failure from here on returns without release_streams, as in l2z_transformer_wide and l2z_wide_run: the other
+    // runstates' streams are then not ordered behind what was enqueued.  "A refusal changes no state" covers the checks.)
+    L2Z_TRY(join_streams(b, n, states));
+    L2Z_TRY(wide_upload_table(b, n, tokens, pos0, states, n_tokens, sampled ? temperature : nullptr, top_p, coins));
+    WideVerdict d = {};
+    d.logits = b->logits; d.ld = b->ld_logits; d.vocab = config->vocab_size;
+    d.tab = b->d_tab;
+    d.next = b->d_next; d.accepted = b->d_next + R;
+    if (sampled) {
+        d.ctl = (const WideVerdictCtl *)(b->d_tab + 1);
+        d.scratch = b->smp; d.row_stride = sample_scratch_floats(config->vocab_size);
+    }
+    L2Z_TRY(wide_step(s0, w, R, deepest, true, [&]() -> int {
+        L2Z_HIP(launch_wide_verdict(d, n, R, st));
+        return L2Z_OK;
+    }, n, m));
+    L2Z_HIP(hipMemcpyAsync(b->h_next, b->d_next, (size_t)(R + n) * 4, hipMemcpyDeviceToHost, st));
+    L2Z_TRY(release_streams(b, n, states));
+    for (int j = 0; j < n; j++) {  // the matrix is states[0]'s: l2z_verify_logits_read finds it there and nowhere else
+        if (states[j]->bt != nullptr) states[j]->bt->v_rows = 0;
+        wide_verify_forget(states[j]);
+    }
+    L2Z_HIP(hipStreamSynchronize(st));
+    b->v_rows = R;  // (only a pass that completed leaves the hook a matrix)
+    memcpy(out_next, b->h_next, (size_t)R * 4);
+    for (int j = 0; j < n; j++) {
+        out_accepted[j] = b->h_next[R + j];
+        logits_whole(states[j], pos0[j] + out_accepted[j] + 1);
+    }
     return L2Z_OK;
 }
