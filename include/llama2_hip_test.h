@@ -464,6 +464,60 @@ int l2z_verify_wide(int n, const int32_t *tokens, const int32_t *n_tokens, const
                     const l2z_config *config, l2z_runstate *const *states, const l2z_weights *w,
                     int32_t *out_next, int32_t *out_accepted);
 
+/* ---- paged KV cache: a shared page pool for the wide family (preview) ----
+ * A contiguous runstate reserves seq_len rows of K and V in every layer whatever its sequence's length.  A PAGED runstate
+ * reserves none: it draws pages of L2Z_KV_PAGE consecutive positions from a pool, on demand, and gives them back.  One page
+ * holds, for every layer and kv head, 64 positions of K and the same of V -- [layer][kv head][64][head_size], the
+ * contiguous cache's layout with seq_len replaced by 64 --; page p of a sequence covers positions 64 p .. 64 p + 63 (a
+ * seq_len that is no multiple of 64 leaves the last page partly used).  The pool's memory is zeroed once at creation;
+ * recycled pages are NOT cleared (stale finite rows beyond a sequence's position are covered by the wide family's
+ * invariance promises).
+ * WHO TAKES THEM.  l2z_prefill_batch, l2z_transformer_wide, l2z_wide_run and l2z_verify_wide, whose kernels touch a cache
+ * in units of 64 absolute positions anyway: a page changes where a block finds its rows and no summation order, so a paged
+ * sequence's ids, accepted counts, logits and KV rows are BIT-IDENTICAL to a contiguous one's under the same calls.  All
+ * runstates of a call are of one kind -- all contiguous, or all paged from one pool --, else L2Z_ERR_INVALID.  Every other
+ * entry point that reads or writes KV rows (l2z_transformer, l2z_prefill, l2z_score, l2z_greedy_begin / _run,
+ * l2z_sample_run, l2z_transformer_batch, the l2z_verify family other than l2z_verify_wide, the timing / profile and
+ * emulated-rank hooks) refuses a paged runstate with L2Z_ERR_INVALID before it enqueues anything; the logits-only calls
+ * (l2z_argmax*, l2z_logits_read / _write, l2z_probs_read, l2z_sample_batch, l2z_synchronize) work unchanged.
+ * ATTACHING.  On the host, before anything is enqueued: a call knows every position it writes (pos0[j] .. + rows - 1; every
+ * step's for l2z_wide_run), counts the pages still missing, and returns L2Z_ERR_OOM -- nothing enqueued, no page attached,
+ * no state changed -- if the pool's free pages fall short; otherwise it attaches them and makes the page tables visible to
+ * the device in stream order.  There is no device-side allocation.  After l2z_verify_wide, pages that hold only rejected
+ * rows stay attached until a trim.
+ * SHARING.  l2z_runstate_fork(dst, src, n_pos) with dst paged: dst first gives back all its pages; with src paged from the
+ * same pool the n_pos / 64 whole pages are SHARED (reference counts, no copy) and, if n_pos % 64 != 0, dst gets one private
+ * page holding a copy of the rows of the last, partial one; with src contiguous dst attaches ceil(n_pos / 64) pages and the
+ * rows are copied in; src paged and dst contiguous: copied out.  Stream ordering and the logits copy are l2z_runstate_fork's
+ * own; L2Z_ERR_OOM with nothing changed if pages are short, L2Z_ERR_STATE if a paged src holds no page for a position
+ * below n_pos -- as is a call of the wide family whose pos0[j] lies above a page the runstate does not hold (a pass never
+ * reads through a missing entry; rows below pos0[j] in pos0[j]'s own page are whatever the page holds).  A call that would WRITE a position inside a page held by more than one runstate is refused with
+ * L2Z_ERR_STATE and nothing enqueued (a caller that rewinds below a fork point, a src forked beyond its own position):
+ * copy-on-write is out of scope.
+ * GIVING BACK.  l2z_runstate_trim, l2z_runstate_free and the dst side of a fork synchronise the runstate's own stream
+ * before pages return to the free list -- sufficient, since every pass that read a runstate's pages made that runstate's
+ * stream wait for it.  A page is free again when its last holder lets go.
+ * l2z_runstate_read("key_cache" / "value_cache") on a paged runstate returns the logical [layer][seq_len][kv_dim] view;
+ * unattached positions read as 0.
+ * Out of scope: the product header, map, Zig shim and CLI; paged runstates in the single-sequence, batched-16, verify /
+ * tree and score paths; sharded runstates; copy-on-write; device-side allocation; eviction or swapping; a scheduler; page
+ * sizes other than 64. */
+#define L2Z_KV_PAGE 64                      /* positions per page; == the segment of the verify / wide attention */
+typedef struct l2z_kvpool l2z_kvpool;
+/* n_pages pages for runstates of *config on the current device.  L2Z_ERR_OOM where the device cannot hold them */
+int l2z_kvpool_init(const l2z_config *config, int n_pages, l2z_kvpool **out);
+/* L2Z_ERR_STATE while a runstate made from it is alive (NULL: nothing to do) */
+int l2z_kvpool_free(l2z_kvpool *p);
+/* any of the three may be NULL; page_bytes: K and V of one page */
+int l2z_kvpool_info(const l2z_kvpool *p, int *n_pages, int *n_free, uint64_t *page_bytes);
+/* l2z_runstate_init without key / value caches; L2Z_ERR_INVALID if the pool was made with another config.  Freed by
+ * l2z_runstate_free, which gives its pages back */
+int l2z_runstate_init_paged(const l2z_config *config, l2z_kvpool *pool, l2z_runstate **out);
+/* the page table: page_ids[p] for p < cap = the pool's page that holds positions 64 p .., -1: none */
+int l2z_runstate_pages(const l2z_runstate *s, int *n_attached, int32_t *page_ids /* [cap], -1: none */, int cap);
+/* give back every page that lies wholly at or above n_pos */
+int l2z_runstate_trim(l2z_runstate *s, int n_pos);
+
 #ifdef __cplusplus
 }
 #endif

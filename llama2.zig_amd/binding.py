@@ -113,6 +113,13 @@ def lib():
         L.l2z_verify_batch.argtypes = [C.c_int, i32p, i32p, i32p, fp, fp, fp, cfgp, C.POINTER(vp), vp, i32p, i32p]
     if hasattr(L, "l2z_verify_wide"):
         L.l2z_verify_wide.argtypes = [C.c_int, i32p, i32p, i32p, fp, fp, fp, cfgp, C.POINTER(vp), vp, i32p, i32p]
+    if hasattr(L, "l2z_kvpool_init"):
+        L.l2z_kvpool_init.argtypes = [cfgp, C.c_int, C.POINTER(vp)]
+        L.l2z_kvpool_free.argtypes = [vp]
+        L.l2z_kvpool_info.argtypes = [vp, ip, ip, C.POINTER(C.c_uint64)]
+        L.l2z_runstate_init_paged.argtypes = [cfgp, vp, C.POINTER(vp)]
+        L.l2z_runstate_pages.argtypes = [vp, ip, i32p, C.c_int]
+        L.l2z_runstate_trim.argtypes = [vp, C.c_int]
     if hasattr(L, "l2z_verify_tree"):
         L.l2z_verify_tree.argtypes = [i32p, i32p, C.c_int, C.c_int, C.c_float, C.c_float, fp, cfgp, vp, vp, i32p, i32p, ip]
         L.l2z_verify_tree_time.argtypes = [i32p, i32p, C.c_int, C.c_int, C.c_float, C.c_float, fp, cfgp, vp, vp, C.c_int,
@@ -317,14 +324,62 @@ class Weights:
             pass
 
 
-class RunState:
-    """src/main.zig:119 RunState, device resident."""
+KV_PAGE = 64  # L2Z_KV_PAGE
 
-    def __init__(self, cfg, comm: Comm | None = None):
+
+class KvPool:
+    """l2z_kvpool: n_pages pages of KV_PAGE positions that paged runstates (RunState(cfg, pool=pool)) draw from on demand
+    (a preview surface of the test library: include/llama2_hip_test.h)."""
+
+    def __init__(self, cfg, n_pages: int):
         self.cfg = _cfg(cfg)
         self.h = C.c_void_p()
+        _chk(lib().l2z_kvpool_init(C.byref(self.cfg), int(n_pages), C.byref(self.h)))
+
+    def info(self) -> dict:
+        n, f, b = C.c_int(0), C.c_int(0), C.c_uint64(0)
+        _chk(lib().l2z_kvpool_info(self.h, C.byref(n), C.byref(f), C.byref(b)))
+        return {"n_pages": n.value, "n_free": f.value, "page_bytes": b.value}
+
+    def close(self):
+        """Raises L2ZError (ERR_STATE) while a runstate made from the pool is alive; the pool then stays usable."""
+        if self.h:
+            _chk(lib().l2z_kvpool_free(self.h))
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RunState:
+    """src/main.zig:119 RunState, device resident.  pool: a paged runstate (l2z_runstate_init_paged), which holds no KV
+    caches of its own and is taken by the wide family only."""
+
+    def __init__(self, cfg, comm: Comm | None = None, pool: KvPool | None = None):
+        self.cfg = _cfg(cfg)
+        self.h = C.c_void_p()
+        self.pool = pool   # (kept alive: the pool outlives its runstates)
+        if pool is not None:
+            assert comm is None, "a paged runstate is unsharded"
+            _chk(lib().l2z_runstate_init_paged(C.byref(self.cfg), pool.h, C.byref(self.h)))
+            return
         _chk(lib().l2z_runstate_init(C.byref(self.cfg), comm.h if comm is not None else None,
                                      C.byref(self.h)))
+
+    def pages(self) -> np.ndarray:
+        """l2z_runstate_pages: the page table, one pool page id per KV_PAGE positions of seq_len, -1 where none is attached."""
+        cap = (self.cfg.seq_len + KV_PAGE - 1) // KV_PAGE
+        ids = np.full(max(cap, 1), -1, np.int32)
+        n = C.c_int(0)
+        _chk(lib().l2z_runstate_pages(self.h, C.byref(n), ids.ctypes.data_as(C.POINTER(C.c_int32)), cap))
+        return ids[:cap].copy()
+
+    def trim(self, n_pos: int) -> None:
+        """l2z_runstate_trim: give back every page that lies wholly at or above n_pos."""
+        _chk(lib().l2z_runstate_trim(self.h, int(n_pos)))
 
     def transformer(self, token: int, pos: int, w: Weights) -> None:
         """src/main.zig:285"""

@@ -401,6 +401,25 @@ extern "C" int l2z_runstate_fork(l2z_runstate *dst, const l2z_runstate *src, int
     L2Z_CHECK(n_pos >= 0 && n_pos <= c.seq_len, L2Z_ERR_STATE, "l2z_runstate_fork: n_pos = %d outside [0, %d]", n_pos,
               c.seq_len);
     L2Z_HIP(hipSetDevice(src->device));
+    // ---- a paged side (include/llama2_hip_test.h l2z_kvpool): dst gives back its pages, then shares src's whole pages
+    // where both draw from one pool, and attaches private ones for the rows that are copied ----
+    const bool paged = dst->pool != nullptr || src->pool != nullptr;
+    const int whole = dst->pool != nullptr && dst->pool == src->pool ? n_pos / kKvPage : 0;   // pages shared, not copied
+    if (src->pool != nullptr)
+        L2Z_CHECK(src->pool->alloc.missing(src->pg, 0, n_pos) == 0, L2Z_ERR_STATE,
+                  "l2z_runstate_fork: src holds no page for some position below n_pos = %d", n_pos);
+    if (dst->pool != nullptr) {
+        KvPages &al = dst->pool->alloc;
+        int back = 0;   // pages dst's release sets free
+        for (int32_t id : dst->pg.pages) back += id >= 0 && al.refs(id) == 1;
+        const int need = kv_pages_for(n_pos) - whole;
+        L2Z_CHECK(need <= al.n_free() + back, L2Z_ERR_OOM, "l2z_runstate_fork: dst needs %d KV pages, the pool has %d free of %d",
+                  need, al.n_free() + back, al.n_pages());
+        L2Z_TRY(kv_release(dst, 0));
+        al.share(dst->pg, src->pg, whole);
+        (void)al.attach(dst->pg, whole * kKvPage, n_pos);   // (cannot fall short: counted above)
+        dst->pages_dirty = true;
+    }
     hipEvent_t ev_src = nullptr, ev_dst = nullptr;
     L2Z_HIP(hipEventCreateWithFlags(&ev_src, hipEventDisableTiming));
     int rc = L2Z_OK;
@@ -418,7 +437,9 @@ extern "C" int l2z_runstate_fork(l2z_runstate *dst, const l2z_runstate *src, int
     // run of n_pos * head_size floats per (layer, kv head), seq_len * head_size floats apart
     const size_t hs = (size_t)c.dim / c.n_heads, pitch = (size_t)c.seq_len * hs * 4, width = (size_t)n_pos * hs * 4;
     const size_t rows = (size_t)c.n_layers * c.n_kv_heads;
-    if (n_pos > 0 && rc == L2Z_OK) {
+    if (paged) {
+        if (rc == L2Z_OK) rc = kv_copy_rows(dst, src, whole * kKvPage, n_pos);
+    } else if (n_pos > 0 && rc == L2Z_OK) {
         hip(hipMemcpy2DAsync(dst->key_cache, pitch, src->key_cache, pitch, width, rows, hipMemcpyDeviceToDevice, dst->stream),
             "key cache copy");
         hip(hipMemcpy2DAsync(dst->value_cache, pitch, src->value_cache, pitch, width, rows, hipMemcpyDeviceToDevice,

@@ -34,9 +34,12 @@ struct Prof {
         }                                                                                 \
     } while (0)
 
-int check_pair(const l2z_config *config, const l2z_runstate *s, const l2z_weights *w)
+int check_pair(const l2z_config *config, const l2z_runstate *s, const l2z_weights *w, bool paged_ok)
 {
     L2Z_CHECK(config && s && w, L2Z_ERR_INVALID, "null config / runstate / weights");
+    L2Z_CHECK(paged_ok || s->pool == nullptr, L2Z_ERR_INVALID,
+              "a paged runstate (l2z_runstate_init_paged) is taken by the wide family only: l2z_prefill_batch, "
+              "l2z_transformer_wide, l2z_wide_run, l2z_verify_wide");
     L2Z_CHECK(memcmp(config, &s->cfg, sizeof *config) == 0 &&
                   memcmp(config, &w->cfg, sizeof *config) == 0,
               L2Z_ERR_INVALID, "config does not match the one RunState / Weights were built with");
@@ -499,6 +502,7 @@ extern "C" int l2z_greedy_begin(l2z_runstate *s, const int32_t *prompt, int n_pr
     L2Z_CHECK(s != nullptr && n_prompt >= 0 && (n_prompt == 0 || prompt != nullptr),
               L2Z_ERR_INVALID, "l2z_greedy_begin: bad arguments");
     L2Z_CHECK(n_prompt <= s->cfg.seq_len, L2Z_ERR_INVALID, "prompt longer than seq_len");
+    L2Z_CHECK(s->pool == nullptr, L2Z_ERR_INVALID, "l2z_greedy_begin: a paged runstate is taken by the wide family only");
     for (int i = 0; i < n_prompt; i++)
         L2Z_CHECK(prompt[i] >= 0 && prompt[i] < s->cfg.vocab_size, L2Z_ERR_INVALID,
                   "prompt[%d] = %d out of vocabulary", i, prompt[i]);

@@ -325,7 +325,19 @@ struct RaggedSeq {     // one sequence's rows of a chunk
     int row0, rows;    // its first row in the chunk, how many
     int pos0;          // position of row0
     int pad;
+    // Paged runstate (kv_pages.h): its page table on the device, [ceil(seq_len / 64)] page ids; kc / vc
+    // are then the POOL's key / value arrays, page p of which starts RaggedChunk::page_floats * p floats in, laid out
+    // [layer][kv head][64][head_size], and position t is row t & 63 of page pages[t >> 6].  null: contiguous caches
+    const int32_t *pages;
 };
+// Entry i of a page table, read as CONSTANT memory: no launch that reads a table writes one (the host uploads it in stream
+// order before the pass), so at a wave-uniform index the read is a scalar load wherever it stands -- outside the vector memory
+// counter, which the flash form's direct-to-LDS ring counts on.  (The pointer comes out of a table in memory: left generic,
+// the compiler reads through it with a flat VECTOR load.)
+__device__ __forceinline__ int kv_page_id(const int32_t *pages, int i)
+{
+    return ((const __attribute__((address_space(4))) int32_t *)pages)[i];
+}
 // The table of one chunk (device pointers; built on the host and uploaded with the tokens).  tiles: the flash attention's
 // blocks -- .x the sequence slot, .y the first of its (up to 64) queries as a row of that sequence's segment --, the
 // ones with the most key rows first.
@@ -336,6 +348,8 @@ struct RaggedChunk {
     const int2 *tiles;      // [n_tiles]
     int n_seq, n_tiles;
     float *k, *v;           // scratch: the chunk's key / value rows [P, kv_dim] between the product and the scatter
+    size_t page_floats;     // != 0: every sequence of the table is paged (RaggedSeq::pages), a page is this many floats of the
+                            // key pool and as many of the value pool; the launchers' layer_off / kv_head_stride are a PAGE's
     const WideAttn *wide;   // != null (l2z_transformer_wide): every row is a sequence of its own at one position -- the
                             // attention is launch_wide_attention (wide_decode.h) on this table; tiles and n_tiles are not read
                             // (wide->verify_m != 0, l2z_verify_wide: sequences of several rows, launch_wide_verify_attention)

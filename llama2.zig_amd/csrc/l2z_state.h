@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "kv_pages.h"
 #include "l2z_comm.h"
 #include "l2z_internal.h"
 #include "tunables.h"
@@ -82,6 +83,17 @@ struct l2z_weights {
     int pk_packed = 0, pk_candidates = 0;
 };
 
+// The KV page pool (include/llama2_hip_test.h; kv_pool.cpp): n_pages pages of the key array and as many of
+// the value array, page p of either page_floats * p floats in, [layer][kv head][kKvPage][head_size]; zero-filled once
+struct l2z_kvpool {
+    l2z_config cfg;
+    int device = 0;
+    l2z::KvPages alloc;
+    float *k = nullptr, *v = nullptr;
+    size_t page_floats = 0;
+    int live = 0;   // runstates made from it and not freed yet
+};
+
 enum { KIND_QKV = 0, KIND_ATTN, KIND_WO, KIND_FFN13, KIND_FFN2, KIND_CLS, KIND_ARGMAX, KIND_GATHER, KIND_COUNT };
 static const char *const kKindNames[KIND_COUNT] = {"qkv", "attn", "wo", "ffn13", "ffn2", "cls", "argmax", "gather"};
 static_assert(KIND_COUNT == L2Z_N_KINDS, "include/llama2_hip_test.h L2Z_N_KINDS");
@@ -96,7 +108,13 @@ struct l2z_runstate {
     // k/v go straight into the cache rows, xb2/hb2 are fused away)
     float *x = nullptr, *xb = nullptr, *hb = nullptr, *q = nullptr, *logits = nullptr;
     float *part = nullptr;    // scheme B: this rank's partial [dim] output of wo / w2 (rank 0's includes the residual), summed by the all-reduce
-    float *key_cache = nullptr, *value_cache = nullptr;
+    float *key_cache = nullptr, *value_cache = nullptr;   // (a paged runstate has neither)
+    // l2z_runstate_init_paged: the pool the KV rows live in, this sequence's page table on the host, and its device
+    // copy with the pinned twin the copy is made from (pages_dirty: the table changed since the last copy was enqueued)
+    l2z_kvpool *pool = nullptr;
+    l2z::KvSeq pg;
+    int32_t *d_pages = nullptr, *h_pages = nullptr;
+    bool pages_dirty = false;
     float2 *rope = nullptr;  // (seq_len, head_size/2) {cos, sin}
     // loop state on the device
     int *d_token = nullptr, *d_pos = nullptr, *d_prompt = nullptr, *d_n_prompt = nullptr;
@@ -173,7 +191,9 @@ namespace l2z {
 
 // forward.cpp
 struct Prof;
-int check_pair(const l2z_config *config, const l2z_runstate *s, const l2z_weights *w);
+// paged_ok: the entry point takes paged runstates (the wide family); every other one that touches a KV cache through
+// s->key_cache refuses them here with L2Z_ERR_INVALID
+int check_pair(const l2z_config *config, const l2z_runstate *s, const l2z_weights *w, bool paged_ok = false);
 // attention variant of a position (the host knows pos and replays the graph captured for its variant):
 // 0 short context (256-thread speculative form), 1 one block per head as the shape picks, 2 split with 256
 // threads per block, 3 split with 1024
@@ -208,6 +228,25 @@ int prefill_ragged_chunk(l2z_runstate *s, const l2z_weights *w, const int32_t *t
 int prefill_last_logits(l2z_runstate *s, const l2z_weights *w);
 // ... and with l2z_transformer_wide (wide_host.cpp): the classifier over all P rows of the chunk just run -> out [P, ldo]
 int prefill_rows_logits(l2z_runstate *s, const l2z_weights *w, int P, float *out, int ldo);
+
+// kv_pool.cpp: paged runstates in a call of the wide family (a call without them passes through all of these untouched)
+// The runstates are of one kind -- all contiguous, or all paged from one pool made with their config --, else L2Z_ERR_INVALID
+int kv_check_kind(const char *fn, int n, l2z_runstate *const *states);
+// Before anything is enqueued: sequence j will write positions pos0[j] .. pos0[j] + (counts ? counts[j] : count) - 1.
+// L2Z_ERR_STATE if one of them lies in a page shared with another sequence or a page below pos0[j] is not attached, L2Z_ERR_OOM if the pool's free pages do not cover
+// what is missing -- nothing attached, nothing changed --, else every page is attached
+int kv_attach(const char *fn, int n, l2z_runstate *const *states, const int32_t *pos0, const int32_t *counts, int count);
+// the page tables that changed -> the device, on st (the pass's stream, after it has joined the runstates' streams)
+int kv_upload(int n, l2z_runstate *const *states, hipStream_t st);
+// s's entry of a RaggedSeq table: the caches, or the pool's arrays and the page table
+void kv_seq_base(const l2z_runstate *s, RaggedSeq *q);
+inline size_t kv_page_floats(const l2z_runstate *s) { return s->pool != nullptr ? s->pool->page_floats : 0; }
+// s gives back every page wholly at or above n_pos, after its own stream has drained (every pass that read s's pages made
+// that stream wait for it)
+int kv_release(l2z_runstate *s, int n_pos);
+// rows 0 .. n_pos - 1 of src's caches -> dst's, on dst's stream, either of them paged (both paged: rows r0 .. only)
+int kv_copy_rows(l2z_runstate *dst, const l2z_runstate *src, int r0, int n_pos);
+void kv_runstate_free(l2z_runstate *s);   // l2z_runstate_free's part: pages back, tables freed, the pool's count down
 
 // batch_host.cpp
 void batch_free(l2z_runstate *s);

@@ -44,9 +44,10 @@ extern "C" int l2z_prefill_batch(int n, const int32_t *tokens, const int32_t *n_
     L2Z_CHECK(tokens != nullptr && n_tokens != nullptr && pos0 != nullptr && config != nullptr && w != nullptr, L2Z_ERR_INVALID,
               "l2z_prefill_batch: null argument");
     L2Z_TRY(check_states("l2z_prefill_batch", n, states, config));
+    L2Z_TRY(kv_check_kind("l2z_prefill_batch", n, states));
     long long total_ll = 0;
     for (int j = 0; j < n; j++) {
-        L2Z_TRY(check_pair(config, states[j], w));
+        L2Z_TRY(check_pair(config, states[j], w, true));
         L2Z_CHECK(n_tokens[j] >= 1, L2Z_ERR_INVALID, "l2z_prefill_batch: n_tokens[%d] = %d (at least 1)", j, n_tokens[j]);
         total_ll += n_tokens[j];
     }
@@ -75,7 +76,9 @@ extern "C" int l2z_prefill_batch(int n, const int32_t *tokens, const int32_t *n_
 
     // ---- the pass, on states[0]'s stream: it waits for every runstate's stream ... ----
     L2Z_TRY(batch_alloc(s0));  // (the events)
+    L2Z_TRY(kv_attach("l2z_prefill_batch", n, states, pos0, n_tokens, 0));   // (paged runstates: the last refusal)
     L2Z_TRY(join_streams(s0->bt, n, states));
+    L2Z_TRY(kv_upload(n, states, st));
     int first[kRaggedMaxSeq];   // a sequence's first row among the concatenated rows
     for (int j = 0, g = 0; j < n; g += n_tokens[j], j++) first[j] = g;
     std::vector<unsigned char> h_tab(tab_bytes(s0->rg_cap));
@@ -96,7 +99,7 @@ extern "C" int l2z_prefill_batch(int n, const int32_t *tokens, const int32_t *n_
             const int lo = std::max(first[j], done), hi = std::min(first[j] + n_tokens[j], done + P);
             if (lo >= hi) continue;
             RaggedSeq &q = h_seq[n_seq];
-            q.kc = states[j]->key_cache; q.vc = states[j]->value_cache;
+            kv_seq_base(states[j], &q);
             q.row0 = lo - done; q.rows = hi - lo; q.pos0 = pos0[j] + (lo - first[j]);
             for (int r = 0; r < q.rows; r++) { h_row_seq[q.row0 + r] = n_seq; h_row_pos[q.row0 + r] = q.pos0 + r; }
             for (int q0 = 0; q0 < q.rows; q0 += 64) tiles.push_back({n_seq, q0, q.pos0 + std::min(q0 + 63, q.rows - 1)});
@@ -115,6 +118,7 @@ extern "C" int l2z_prefill_batch(int n, const int32_t *tokens, const int32_t *n_
         rg.tiles = (const int2 *)(d_tab + ((unsigned char *)h_tiles - h_tab.data()));
         rg.n_seq = n_seq; rg.n_tiles = (int)tiles.size();
         rg.k = s0->rg_k; rg.v = s0->rg_v;
+        rg.page_floats = kv_page_floats(s0);
         L2Z_HIP(hipMemcpyAsync(d_tab, h_tab.data(), h_tab.size(), hipMemcpyHostToDevice, st));
         L2Z_TRY(prefill_ragged_chunk(s0, w, tokens + done, P, rg));
         // the last residual row of every sequence that ends here is that runstate's x

@@ -297,7 +297,9 @@ int prefill_stage(l2z_runstate *s, const l2z_weights *w, int l, int k, int P, in
         // then ONE launch that rotates q and k at each row's own position and stores k / v into each row's own caches,
         // then ONE attention launch in which a row sees its own sequence's cache only (prefill_ragged.hip).
         L2Z_CHECK(!sharded, L2Z_ERR_INVALID, "batched prefill: rows of several sequences on a shard");
-        const size_t layer_off = (size_t)l * c.seq_len * kvd;
+        // (paged sequences: a layer and a kv head of a PAGE, l2z_internal.h RaggedSeq::pages)
+        const size_t kvh_stride = rg->page_floats ? (size_t)kKvPage * hs : (size_t)c.seq_len * hs;
+        const size_t layer_off = (size_t)l * c.n_kv_heads * kvh_stride;
         GemmLaunch gl = launch_of(ch, sk_qkv, xn_planes);
         gl.n_launch_whole = n_qkv;
         struct { const float *w; float *out; int n; } qkv[3] = {{w->wq + (size_t)l * dim * dim, s->pf_q, dim},

@@ -16,12 +16,16 @@ namespace {
 __global__ __launch_bounds__(kPfBlock) void ragged_rope_scatter(float *q, int ldq, const float *k, const float *v,
                                                                 const RaggedSeq *seq, const int *row_seq, const int *row_pos,
                                                                 int dim, int kvd, int hs, const float2 *rope,
-                                                                size_t layer_off, size_t kv_head_stride)
+                                                                size_t layer_off, size_t kv_head_stride, size_t page_floats)
 {
     const int row = blockIdx.x;
     const int n4 = (dim + 2 * kvd) >> 2;
     const int pos = row_pos[row];
     const RaggedSeq sq = seq[row_seq[row]];
+    // where the row's position stands in a (layer, kv head) run of its sequence: row pos of the cache, or (paged) row
+    // pos & 63 of the page that holds it
+    size_t cache_off = layer_off + (size_t)pos * (size_t)hs;
+    if (sq.pages != nullptr) cache_off = (size_t)kv_page_id(sq.pages, pos >> 6) * page_floats + layer_off + (size_t)(pos & 63) * (size_t)hs;
     for (int i = blockIdx.y * kPfBlock + threadIdx.x; i < n4; i += gridDim.y * kPfBlock) {
         int f = 4 * i;
         if (f < dim) {
@@ -46,7 +50,7 @@ __global__ __launch_bounds__(kPfBlock) void ragged_rope_scatter(float *q, int ld
             x = r;
         }
         // head-major cache [kv head][seq_len][head_size]
-        float *dst = (is_k ? sq.kc : sq.vc) + layer_off + (size_t)(f / hs) * kv_head_stride + (size_t)pos * (size_t)hs + (size_t)(f % hs);
+        float *dst = (is_k ? sq.kc : sq.vc) + cache_off + (size_t)(f / hs) * kv_head_stride + (size_t)(f % hs);
         *(v4f *)dst = x;
     }
 }
@@ -57,7 +61,8 @@ struct RaggedAttnArgs {
     const RaggedSeq *seq;
     const int *row_seq, *row_pos;
     const int2 *tiles;
-    size_t layer_off, kv_head;   // floats to this layer in a cache; between kv heads
+    size_t layer_off, kv_head;   // floats to this layer in a cache; between kv heads (paged: in a page)
+    size_t page_floats;          // paged sequences: floats per page of the pool
     int ldq, ldo, kv_mul, seq_len, head_size;
     __bf16 *x3;                  // != null: out's planes of bf16 terms too (the Wo product's operand)
     int kp;
@@ -81,6 +86,10 @@ __global__ __launch_bounds__(kPfBlock) void ragged_attention_rows(const RaggedAt
     const int T = a.row_pos[row] + 1;
     const int kvh = h / a.kv_mul;
     const float *kbase = sq.kc + a.layer_off + (size_t)kvh * a.kv_head, *vbase = sq.vc + a.layer_off + (size_t)kvh * a.kv_head;
+    // key / value row t of this kv head, as floats from kbase / vbase: paged, row t & 63 of the page that holds t
+    auto row_off = [&](int t) -> size_t {
+        return sq.pages != nullptr ? (size_t)kv_page_id(sq.pages, t >> 6) * a.page_floats + (size_t)(t & 63) * hs : (size_t)t * hs;
+    };
     const int g = threadIdx.x / TPR, c0 = threadIdx.x % TPR;
     const bool active = c0 < E;
     const int cc = active ? c0 : 0;
@@ -88,7 +97,7 @@ __global__ __launch_bounds__(kPfBlock) void ragged_attention_rows(const RaggedAt
     const v4f qv = active ? ((const v4f *)(a.q + (size_t)row * a.ldq + (size_t)h * hs))[cc] : zero;
     const float div = sqrtf((float)hs);
     for (int t = g; t < T; t += G) {
-        const v4f kv = ((const v4f *)(kbase + (size_t)t * hs))[cc];
+        const v4f kv = ((const v4f *)(kbase + row_off(t)))[cc];
         float p = fmaf(qv.x, kv.x, 0.0f);
         p = fmaf(qv.y, kv.y, p); p = fmaf(qv.z, kv.z, p); p = fmaf(qv.w, kv.w, p);
         for (int o = TPR >> 1; o > 0; o >>= 1) p += __shfl_xor(p, o, 64);
@@ -114,7 +123,7 @@ __global__ __launch_bounds__(kPfBlock) void ragged_attention_rows(const RaggedAt
     s = ((red[4] + red[5]) + red[6]) + red[7];
     v4f acc = zero;
     for (int t = g; t < T; t += G) {
-        const v4f vv = ((const v4f *)(vbase + (size_t)t * hs))[cc];
+        const v4f vv = ((const v4f *)(vbase + row_off(t)))[cc];
         const float w = att[t] / s;  // main.zig:704
         acc.x = fmaf(vv.x, w, acc.x); acc.y = fmaf(vv.y, w, acc.y);
         acc.z = fmaf(vv.z, w, acc.z); acc.w = fmaf(vv.w, w, acc.w);
@@ -135,7 +144,10 @@ __global__ __launch_bounds__(kPfBlock) void ragged_attention_rows(const RaggedAt
 // the registers, K / V tiles arrive by direct-to-LDS loads into two buffers.  What differs is where a block finds its
 // rows: the segment's first row in the chunk (q, out and the planes), its first position, its row count and its caches
 // come from the table.  Masked scores are -inf; key 0 of a sequence is live for every one of its queries.
-template <int NDT>
+// PAGED: a key tile is ONE page of the sequence (both are 64 absolute positions): `issue` takes the tile's page id, a
+// wave-uniform value read one tile ahead through the scalar path, so no load of the vmcnt-counted ring waits for it;
+// the rows, their order in LDS and every sum are the contiguous form's.
+template <int NDT, bool PAGED>
 __global__ __launch_bounds__(512) void ragged_attention_flash(const RaggedAttnArgs a)
 {
     constexpr int KH = 2;
@@ -169,24 +181,34 @@ __global__ __launch_bounds__(512) void ragged_attention_flash(const RaggedAttnAr
     const int n_kt = (pos0 + last_q) / 64 + 1;              // key tiles of the block
     const int last_live = pos0 + q0 + 16 * qg + 15;         // last key position live for one of this wave's queries
     const float div = sqrtf((float)HS);
-    auto issue = [&](int kt, int buf) {
+    auto issue = [&](int kt, int buf, int page) {
         const int t0 = kt * 64;
         float *kd = lds + buf * (2 * 64 * HS), *vd = kd + 64 * HS;
+        // paged: the tile's rows are rows 0 .. 63 of its page (t0 is a multiple of 64, and seq_len - 1 >= t0 lies in it)
+        const float *kt_base = PAGED ? kbase + (size_t)page * a.page_floats - (size_t)t0 * HS : kbase;
+        const float *vt_base = PAGED ? vbase + (size_t)page * a.page_floats - (size_t)t0 * HS : vbase;
 #pragma unroll
         for (int i = 0; i < LPW; i++) {
             const int f = (wave * LPW + i) * 64 + lane, row = f / E, cp = f % E;
             int t = t0 + row;
             t = t < seq_len ? t : seq_len - 1;  // rows past the context are masked below
-            lds_dma16(kbase + (size_t)t * HS + 4 * (cp ^ (row & 15)), kd + (wave * LPW + i) * 256);
-            lds_dma16(vbase + (size_t)t * HS + 4 * cp, vd + (wave * LPW + i) * 256);
+            lds_dma16(kt_base + (size_t)t * HS + 4 * (cp ^ (row & 15)), kd + (wave * LPW + i) * 256);
+            lds_dma16(vt_base + (size_t)t * HS + 4 * cp, vd + (wave * LPW + i) * 256);
         }
     };
-    issue(0, 0);
+    const int32_t *pages = PAGED ? sq.pages : nullptr;
+    int page_next = 0;   // the page of the tile `issue` takes next
+    if (PAGED) page_next = kv_page_id(pages, 0);
+    issue(0, 0, page_next);
+    if (PAGED && n_kt > 1) page_next = kv_page_id(pages, 1);
     for (int kt = 0; kt < n_kt; kt++) {
         const int t0 = kt * 64;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's part of tile kt has landed
         __syncthreads();  // everyone's has; and every wave is done with tile kt - 1: its buffer is free
-        if (kt + 1 < n_kt) issue(kt + 1, (kt + 1) & 1);
+        if (kt + 1 < n_kt) {
+            issue(kt + 1, (kt + 1) & 1, page_next);
+            if (PAGED && kt + 2 < n_kt) page_next = kv_page_id(pages, kt + 2);
+        }
         const float *ks = lds + (kt & 1) * (2 * 64 * HS), *vs = ks + 64 * HS;
         const int r0 = (64 / KH) * kh;                 // this wave's rows of the tile
         if (t0 + r0 > last_live) continue;             // nothing live for this wave (wave-uniform)
@@ -288,13 +310,14 @@ __global__ __launch_bounds__(512) void ragged_attention_flash(const RaggedAttnAr
 hipError_t launch_ragged_rope_scatter(float *q, int ldq, const RaggedChunk &rg, int P, int dim, int kv_dim, int head_size,
                                       const float2 *rope, size_t layer_off, size_t kv_head_stride, hipStream_t st)
 {
+    if (rg.page_floats & 3) return hipErrorInvalidValue;
     if (P <= 0 || (head_size & 3) || (dim % head_size) || (kv_dim % head_size) || (ldq & 3) ||
         (((uintptr_t)q | (uintptr_t)rg.k | (uintptr_t)rg.v | (uintptr_t)rope) & 15) || (layer_off & 3) || (kv_head_stride & 3))
         return hipErrorInvalidValue;
     const int n4 = (dim + 2 * kv_dim) >> 2;
     const dim3 grid(P, (n4 + 4 * kPfBlock - 1) / (4 * kPfBlock));   // up to four float4 per thread
     hipLaunchKernelGGL(ragged_rope_scatter, grid, dim3(kPfBlock), 0, st, q, ldq, (const float *)rg.k, (const float *)rg.v, rg.seq,
-                       rg.row_seq, rg.row_pos, dim, kv_dim, head_size, rope, layer_off, kv_head_stride);
+                       rg.row_seq, rg.row_pos, dim, kv_dim, head_size, rope, layer_off, kv_head_stride, rg.page_floats);
     return hipGetLastError();
 }
 
@@ -307,12 +330,15 @@ hipError_t launch_ragged_attention(const float *q, int ldq, float *out, int ldo,
     RaggedAttnArgs a = {};
     a.q = q; a.out = out; a.seq = rg.seq; a.row_seq = rg.row_seq; a.row_pos = rg.row_pos; a.tiles = rg.tiles;
     a.layer_off = layer_off; a.kv_head = kv_head_stride; a.ldq = ldq; a.ldo = ldo; a.kv_mul = kv_mul; a.seq_len = seq_len;
-    a.head_size = head_size;
+    a.head_size = head_size; a.page_floats = rg.page_floats;
     // (the caches come from hipMalloc and a layer / a kv head is a multiple of head_size floats: 16-byte aligned rows)
     if ((head_size == 64 || head_size == 128) && (ldq % 4) == 0 && (ldo % 4) == 0 && rg.n_tiles > 0 &&
         (((uintptr_t)q | (uintptr_t)out) & 15) == 0) {
         const size_t lds_f = (size_t)2 * 2 * 64 * head_size * sizeof(float);  // two buffers of a K and a V tile
-        const void *fn = head_size == 128 ? (const void *)ragged_attention_flash<8> : (const void *)ragged_attention_flash<4>;
+        const bool paged = rg.page_floats != 0;
+        const void *fn = head_size == 128
+                             ? (paged ? (const void *)ragged_attention_flash<8, true> : (const void *)ragged_attention_flash<8, false>)
+                             : (paged ? (const void *)ragged_attention_flash<4, true> : (const void *)ragged_attention_flash<4, false>);
         if (lds_f > 48 * 1024) {
             const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f);
             if (e != hipSuccess) return e;

@@ -12,8 +12,8 @@
 using namespace l2z;
 
 // ---------------------------------------------------------------------------
-// src/main.zig:137 RunState.init
-extern "C" int l2z_runstate_init(const l2z_config *config, const l2z_comm *comm, l2z_runstate **out)
+// src/main.zig:137 RunState.init; pool != null (l2z_runstate_init_paged): no caches, a page table instead
+static int runstate_make(const l2z_config *config, const l2z_comm *comm, l2z_kvpool *pool, l2z_runstate **out)
 {
     L2Z_CHECK(config != nullptr && out != nullptr, L2Z_ERR_INVALID, "runstate_init: null argument");
     const int dev = current_device_for(comm);
@@ -73,8 +73,15 @@ extern "C" int l2z_runstate_init(const l2z_config *config, const l2z_comm *comm,
     if (sh.scheme_b) alloc((void **)&s->part, (size_t)c.dim * 4);
     alloc((void **)&s->q, (size_t)c.dim * 4);
     alloc((void **)&s->logits, (size_t)c.vocab_size * 4);
-    alloc((void **)&s->key_cache, kv * 4);
-    alloc((void **)&s->value_cache, kv * 4);
+    if (pool == nullptr) {
+        alloc((void **)&s->key_cache, kv * 4);
+        alloc((void **)&s->value_cache, kv * 4);
+    } else {
+        s->pg.init(c.seq_len);
+        alloc((void **)&s->d_pages, s->pg.pages.size() * 4);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&s->h_pages, s->pg.pages.size() * 4, hipHostMallocDefault);
+        s->pages_dirty = true;   // (the first pass uploads the table whatever it attaches)
+    }
     alloc((void **)&s->rope, (size_t)c.seq_len * (sh.hs / 2) * sizeof(float2));
     alloc((void **)&s->d_token, 4);
     alloc((void **)&s->d_pos, 4);
@@ -157,8 +164,27 @@ extern "C" int l2z_runstate_init(const l2z_config *config, const l2z_comm *comm,
             return L2Z_ERR_HIP;
         }
     }
+    if (pool != nullptr) {   // (from here on l2z_runstate_free gives the pages back and counts the pool down)
+        s->pool = pool;
+        pool->live++;
+    }
     *out = s;
     return L2Z_OK;
+}
+
+extern "C" int l2z_runstate_init(const l2z_config *config, const l2z_comm *comm, l2z_runstate **out)
+{
+    return runstate_make(config, comm, nullptr, out);
+}
+
+extern "C" int l2z_runstate_init_paged(const l2z_config *config, l2z_kvpool *pool, l2z_runstate **out)
+{
+    L2Z_CHECK(config != nullptr && pool != nullptr && out != nullptr, L2Z_ERR_INVALID, "l2z_runstate_init_paged: null argument");
+    L2Z_CHECK(memcmp(config, &pool->cfg, sizeof *config) == 0, L2Z_ERR_INVALID,
+              "l2z_runstate_init_paged: the pool was made with another config");
+    L2Z_CHECK(current_device_for(nullptr) == pool->device, L2Z_ERR_INVALID,
+              "l2z_runstate_init_paged: the pool lives on device %d, the current device is another", pool->device);
+    return runstate_make(config, nullptr, pool, out);
 }
 
 extern "C" void l2z_runstate_free(l2z_runstate *s)
@@ -180,6 +206,11 @@ extern "C" void l2z_runstate_free(l2z_runstate *s)
         if (p) (void)hipFree(p);
     if (s->h_stage) (void)hipHostFree(s->h_stage);
     if (s->h_smp_ctl) (void)hipHostFree(s->h_smp_ctl);
+    if (s->pool == nullptr) {   // (a paged runstate whose allocation failed half way: the pool does not know it yet)
+        if (s->d_pages) (void)hipFree(s->d_pages);
+        if (s->h_pages) (void)hipHostFree(s->h_pages);
+    }
+    l2z::kv_runstate_free(s);
     l2z::batch_free(s);
     l2z::wide_free(s);
     if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -212,6 +243,8 @@ extern "C" int l2z_runstate_read(l2z_runstate *s, const char *name, size_t offse
     else if (k == "logits") { p = s->logits; n = c.vocab_size; }
     else if (k == "key_cache") { p = s->key_cache; n = kv; }
     else if (k == "value_cache") { p = s->value_cache; n = kv; }
+    const bool paged_kv = s->pool != nullptr && (k == "key_cache" || k == "value_cache");
+    if (paged_kv) p = k == "key_cache" ? s->pool->k : s->pool->v;   // (the pages are gathered below)
     L2Z_CHECK(p != nullptr, L2Z_ERR_INVALID, "l2z_runstate_read: unknown buffer '%s'", name);
     L2Z_CHECK(offset + count <= n, L2Z_ERR_INVALID, "l2z_runstate_read: out of range");
     L2Z_HIP(hipSetDevice(s->device));
@@ -223,7 +256,19 @@ extern "C" int l2z_runstate_read(l2z_runstate *s, const char *name, size_t offse
         const size_t S = (size_t)c.seq_len, kvd = (size_t)s->sh.kvd_loc, hs = (size_t)s->sh.hs, layer = S * kvd;
         std::vector<float> host(layer);
         for (size_t l = offset / layer; l * layer < offset + count; l++) {
-            L2Z_HIP(hipMemcpy(host.data(), p + l * layer, layer * sizeof(float), hipMemcpyDeviceToHost));
+            if (paged_kv) {
+                // the logical layer: every attached page's rows of this layer to their place, unattached positions 0
+                std::fill(host.begin(), host.end(), 0.0f);
+                const size_t P = (size_t)l2z::kKvPage, run = P * hs;
+                for (size_t pg = 0; pg < s->pg.pages.size(); pg++) {
+                    if (s->pg.pages[pg] < 0) continue;
+                    const size_t rows = std::min(P, S - pg * P);
+                    L2Z_HIP(hipMemcpy2D(host.data() + pg * run, S * hs * 4,
+                                        p + (size_t)s->pg.pages[pg] * s->pool->page_floats + l * (kvd / hs) * run, run * 4,
+                                        rows * hs * 4, kvd / hs, hipMemcpyDeviceToHost));
+                }
+            } else
+                L2Z_HIP(hipMemcpy(host.data(), p + l * layer, layer * sizeof(float), hipMemcpyDeviceToHost));
             const size_t lo = std::max(offset, l * layer), hi = std::min(offset + count, (l + 1) * layer);
             for (size_t i = lo; i < hi; i++) {
                 const size_t r = i - l * layer, t = r / kvd, f = r % kvd;

@@ -44,6 +44,7 @@ struct WideAttn {
     int n_seg;             // segments of the deepest row of this step: the grid's extent
     int verify_m;          // 0: one row per sequence (launch_wide_attention); l2z_verify_wide: the slots of a block, the
                            // smallest of 1, 2, 4, 8, 16 that holds the call's longest sequence (launch_wide_verify_attention)
+    size_t page_floats;    // RaggedChunk::page_floats of the step (0: contiguous caches)
 };
 
 // Decode attention (main.zig:361-389) of rows 0 .. n - 1 of q [n, ldq] (RoPE applied) into out [n, ldo], two launches:

@@ -24,6 +24,7 @@ struct WideAttnArgs {
     const WideTable *tab;
     float *part_o, *part_ml;  // [kWideMax, n_heads, seg_cap, head_size] and [..., 2]
     size_t layer_off, kv_head_stride;
+    size_t page_floats;       // paged sequences (RaggedSeq::pages): floats per page of the pool
     int ldq, ldo, n_heads, kv_mul, head_size, seg_cap;
     __bf16 *x3;  // != null: out's planes of bf16 terms too
     int kp;
@@ -51,7 +52,10 @@ __global__ __launch_bounds__(kVaBlock) void wide_attention(const WideAttnArgs a)
     s.act = (1u << nq) - 1u;
     s.part_o = a.part_o; s.part_ml = a.part_ml; s.seg_cap = a.seg_cap;
     const RaggedSeq sq = a.tab->seq[row];
-    const size_t head_off = a.layer_off + (size_t)kvh * a.kv_head_stride;
+    size_t head_off = a.layer_off + (size_t)kvh * a.kv_head_stride;
+    // paged: the block's segment is ONE page; the body addresses key t at base + t * head_size, so the base takes the
+    // page's start less the segment's first row (one dependent 4-byte read per block, uniform)
+    if (sq.pages != nullptr) head_off += (size_t)kv_page_id(sq.pages, seg) * a.page_floats - (size_t)seg0 * a.head_size;
     segment_attention_body<MQ>(s, sq.kc + head_off, sq.vc + head_off, a.head_size, seg, min(seg0 + kVerifySeg - 1, pos), sc);
 }
 
@@ -132,10 +136,10 @@ hipError_t launch_wide_attention(const float *q, int ldq, float *out, int ldo, c
     if (planes_written) *planes_written = false;
     WideAttnArgs a = {};
     if (!wide_out_args(a, out, ldo, wa, n, n_heads, head_size, x3, kp) || kv_mul < 1 || n_heads % kv_mul != 0 || (ldq & 3) ||
-        (((uintptr_t)q) & 15) || (layer_off & 3) || (kv_head_stride & 3))
+        (((uintptr_t)q) & 15) || (layer_off & 3) || (kv_head_stride & 3) || (wa.page_floats & 3))
         return hipErrorInvalidValue;
     a.q = q; a.ldq = ldq; a.kv_mul = kv_mul;
-    a.layer_off = layer_off; a.kv_head_stride = kv_head_stride;
+    a.layer_off = layer_off; a.kv_head_stride = kv_head_stride; a.page_floats = wa.page_floats;
     const int mq = kv_mul == 1 ? 1 : kv_mul == 2 ? 2 : kWaHeadsMax;
     const dim3 grid(n_heads / kv_mul * ((kv_mul + mq - 1) / mq), wa.n_seg, n);
     switch (mq) {

@@ -142,9 +142,10 @@ int wide_checks(const char *fn, int n, const int32_t *tokens, const int32_t *pos
 {
     L2Z_CHECK(tokens != nullptr && pos != nullptr && config != nullptr && w != nullptr, L2Z_ERR_INVALID, "%s: null argument", fn);
     L2Z_TRY(check_states(fn, n, states, config, kWideMax));
+    L2Z_TRY(kv_check_kind(fn, n, states));
     *deepest = 0;
     for (int i = 0; i < n; i++) {
-        L2Z_TRY(check_pair(config, states[i], w));
+        L2Z_TRY(check_pair(config, states[i], w, true));
         L2Z_TRY(check_row(fn, i, tokens[i], pos[i], n_steps, *config));
         if (pos[i] > *deepest) *deepest = pos[i];
     }
@@ -175,7 +176,8 @@ int wide_upload_table(WideScratch *b, int n, const int32_t *tokens, const int32_
     WideVerdictCtl *ctl = (WideVerdictCtl *)(t + 1);
     for (int i = 0, r = 0; i < n; i++) {
         const int rows = n_tokens ? n_tokens[i] : 1;
-        t->seq[i] = {states[i]->key_cache, states[i]->value_cache, r, rows, pos[i], 0};
+        t->seq[i] = {nullptr, nullptr, r, rows, pos[i], 0, nullptr};
+        kv_seq_base(states[i], &t->seq[i]);
         t->logits[i] = states[i]->logits;
         if (temperature) {
             ctl->temperature[i] = temperature[i];
@@ -202,11 +204,12 @@ int wide_step(l2z_runstate *s0, const l2z_weights *w, int n, int deepest, bool f
               int verify_m = 0)
 {
     WideScratch *b = s0->wd;
-    WideAttn wa = {b->d_tab, b->part, b->seg_cap, deepest / kVerifySeg + 1, verify_m};
+    WideAttn wa = {b->d_tab, b->part, b->seg_cap, deepest / kVerifySeg + 1, verify_m, kv_page_floats(s0)};
     RaggedChunk rg = {};
     rg.seq = b->d_tab->seq; rg.row_seq = b->d_tab->row_seq; rg.row_pos = b->d_tab->pos;
     rg.n_seq = verify_m ? n_seq : n;
     rg.k = b->k; rg.v = b->v;
+    rg.page_floats = wa.page_floats;
     rg.wide = &wa;
     L2Z_TRY(prefill_ragged_chunk(s0, w, from_table ? b->h_tab->tokens : nullptr, n, rg));
     if (from_table) L2Z_HIP(hipEventRecord(b->ev_upload, s0->stream));
@@ -232,8 +235,10 @@ extern "C" int l2z_transformer_wide(int n, const int32_t *tokens, const int32_t 
     L2Z_TRY(prefill_scratch(s0, n));
     L2Z_TRY(wide_alloc(s0));
     WideScratch *b = s0->wd;
+    L2Z_TRY(kv_attach("l2z_transformer_wide", n, states, pos, nullptr, 1));   // (paged runstates: the last refusal)
 
     L2Z_TRY(join_streams(b, n, states));
+    L2Z_TRY(kv_upload(n, states, st));
     L2Z_TRY(wide_upload_table(b, n, tokens, pos, states));
     L2Z_TRY(wide_step(s0, w, n, deepest, true, [&]() -> int {
         L2Z_HIP(launch_wide_logits_out(b->logits, b->ld_logits, b->d_tab, config->vocab_size, out_next ? b->d_next : nullptr, n, st));
@@ -276,9 +281,11 @@ extern "C" int l2z_wide_run(int n, const int32_t *first_tokens, const int32_t *p
     L2Z_TRY(wide_alloc(s0));
     L2Z_TRY(run_alloc(s0, entries, sampled));
     WideScratch *b = s0->wd;
+    L2Z_TRY(kv_attach("l2z_wide_run", n, states, pos0, nullptr, n_steps));   // (paged runstates: every step's pages, up front)
 
     // ---- the run, on states[0]'s stream: one join, the first step's table and the coins, n_steps steps back to back ----
     L2Z_TRY(join_streams(b, n, states));
+    L2Z_TRY(kv_upload(n, states, st));
     L2Z_TRY(wide_upload_table(b, n, first_tokens, pos0, states));
     WideDraw d = {};
     d.logits = b->logits; d.ld = b->ld_logits; d.vocab = config->vocab_size;
@@ -321,6 +328,7 @@ extern "C" int l2z_verify_wide(int n, const int32_t *tokens, const int32_t *n_to
                   out_next != nullptr && out_accepted != nullptr,
               L2Z_ERR_INVALID, "%s: null argument", fn);
     L2Z_TRY(check_states(fn, n, states, config, kWideMax));
+    L2Z_TRY(kv_check_kind(fn, n, states));
     int R = 0, longest = 0, deepest = 0;
     for (int j = 0; j < n; j++) {
         L2Z_CHECK(n_tokens[j] >= 1 && n_tokens[j] <= kBatchMax, L2Z_ERR_INVALID, "%s: n_tokens[%d] = %d outside [1, %d]", fn, j,
@@ -329,7 +337,7 @@ extern "C" int l2z_verify_wide(int n, const int32_t *tokens, const int32_t *n_to
         longest = std::max(longest, n_tokens[j]);
     }
     L2Z_CHECK(R <= kWideMax, L2Z_ERR_INVALID, "%s: %d rows in all, above %d", fn, R, kWideMax);
-    for (int j = 0; j < n; j++) L2Z_TRY(check_pair(config, states[j], w));
+    for (int j = 0; j < n; j++) L2Z_TRY(check_pair(config, states[j], w, true));
     L2Z_TRY(prefill_check(config, states[0]));
     L2Z_CHECK(states[0]->sh.hs <= 256, L2Z_ERR_INVALID, "%s: head_size above 256", fn);
     bool sampled = false;  // some sequence draws: l2z_sample_batch's rules for it
@@ -360,12 +368,14 @@ extern "C" int l2z_verify_wide(int n, const int32_t *tokens, const int32_t *n_to
                           {{(void **)&b->smp, (size_t)kWideMax * sample_scratch_floats(config->vocab_size) * 4}}));
     int m = 1;  // the smallest instantiation that holds the longest sequence
     while (m < longest) m <<= 1;
+    L2Z_TRY(kv_attach(fn, n, states, pos0, n_tokens, 0));   // (paged runstates: the last refusal)
 
     // ---- the pass, on states[0]'s stream: the table (a slot per sequence, its rows behind one another), the chunk of R
     // rows, the classifier over all of them, the verdict, one copy back ----
     // (a failure from here on returns without release_streams, as in l2z_transformer_wide and l2z_wide_run: the other
     // runstates' streams are then not ordered behind what was enqueued.  "A refusal changes no state" covers the checks.)
     L2Z_TRY(join_streams(b, n, states));
+    L2Z_TRY(kv_upload(n, states, st));
     L2Z_TRY(wide_upload_table(b, n, tokens, pos0, states, n_tokens, sampled ? temperature : nullptr, top_p, coins));
     WideVerdict d = {};
     d.logits = b->logits; d.ld = b->ld_logits; d.vocab = config->vocab_size;

@@ -22,6 +22,7 @@ struct WideVerifyAttnArgs {
     const WideTable *tab;
     float *part_o, *part_ml;  // [kWideMax, n_heads, seg_cap, head_size] and [..., 2]
     size_t layer_off, kv_head_stride;
+    size_t page_floats;       // paged sequences (RaggedSeq::pages): floats per page of the pool
     int ldq, n_heads, kv_mul, head_size, seg_cap;
 };
 
@@ -43,7 +44,9 @@ __global__ __launch_bounds__(kVaBlock) void wide_verify_attention(const WideVeri
     s.idx0 = (size_t)sq.row0 * a.n_heads + h; s.part_step = (size_t)a.n_heads;
     s.act = ((1u << sq.rows) - 1u) & (0xFFFFFFFFu << i0);
     s.part_o = a.part_o; s.part_ml = a.part_ml; s.seg_cap = a.seg_cap;
-    const size_t head_off = a.layer_off + (size_t)(h / a.kv_mul) * a.kv_head_stride;
+    size_t head_off = a.layer_off + (size_t)(h / a.kv_mul) * a.kv_head_stride;
+    // paged: the segment is ONE page, the base takes its start less the segment's first row (as wide_attention)
+    if (sq.pages != nullptr) head_off += (size_t)kv_page_id(sq.pages, seg) * a.page_floats - (size_t)seg0 * a.head_size;
     segment_attention_body<M>(s, sq.kc + head_off, sq.vc + head_off, a.head_size, seg, last, sc);
 }
 
@@ -95,13 +98,13 @@ hipError_t launch_wide_verify_attention(const float *q, int ldq, float *out, int
     if (planes_written) *planes_written = false;
     if (n_seq < 1 || n_seq > n_rows || n_rows > kWideMax || head_size < 4 || head_size > 256 || (head_size & 3) || kv_mul < 1 ||
         n_heads < 1 || n_heads % kv_mul != 0 || wa.tab == nullptr || wa.part == nullptr || wa.n_seg < 1 || wa.n_seg > wa.seg_cap ||
-        (ldq & 3) || (((uintptr_t)q | (uintptr_t)wa.part) & 15) || (layer_off & 3) || (kv_head_stride & 3))
+        (ldq & 3) || (((uintptr_t)q | (uintptr_t)wa.part) & 15) || (layer_off & 3) || (kv_head_stride & 3) || (wa.page_floats & 3))
         return hipErrorInvalidValue;
     WideVerifyAttnArgs a = {};
     a.q = q; a.tab = wa.tab;
     a.part_o = wa.part;
     a.part_ml = wa.part + (size_t)kWideMax * n_heads * wa.seg_cap * head_size;
-    a.layer_off = layer_off; a.kv_head_stride = kv_head_stride;
+    a.layer_off = layer_off; a.kv_head_stride = kv_head_stride; a.page_floats = wa.page_floats;
     a.ldq = ldq; a.n_heads = n_heads; a.kv_mul = kv_mul; a.head_size = head_size; a.seg_cap = wa.seg_cap;
     const dim3 grid(n_heads, wa.n_seg, n_seq);
     switch (wa.verify_m) {

@@ -1,0 +1,37 @@
+"""The paged KV cache's host bookkeeping (llama2.zig_amd/csrc/kv_pages.h: free list, reference counts, pages missing for a
+position range, share, release, the shared-page write check) without a GPU: tests/kv_pages_check.cpp, a stand-alone program
+with its own main over that header alone, built with -fsanitize=address,undefined and run.  Nothing is loaded into Python."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CASES = ["pages missing for a position range", "attach, then release restores the free count",
+         "share and release by reference count in either order", "the shared-page write refusal",
+         "exhaustion is reported with nothing attached", "seq_len not a multiple of 64"]
+
+
+@pytest.fixture(scope="module")
+def report(tmp_path_factory):
+    cxx = next((c for c in (os.environ.get("CXX"), "g++", "clang++", "/opt/rocm/llvm/bin/clang++") if c and shutil.which(c)), None)
+    assert cxx is not None, "no host C++ compiler found"
+    exe = str(tmp_path_factory.mktemp("kv_pages") / "kv_pages_check")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "llama2.zig_amd", "csrc"),
+                    os.path.join(HERE, "kv_pages_check.cpp"), "-o", exe], check=True, timeout=300)
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    return run.returncode, run.stdout + run.stderr
+
+
+def test_the_program_ran_clean_under_the_sanitizers(report):
+    code, out = report
+    assert code == 0, out
+    assert "ERROR" not in out and "runtime error" not in out, out
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_case(report, case):
+    assert f"ok: {case}" in report[1].splitlines(), report[1]
