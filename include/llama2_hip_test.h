@@ -464,6 +464,50 @@ int l2z_verify_wide(int n, const int32_t *tokens, const int32_t *n_tokens, const
                     const l2z_config *config, l2z_runstate *const *states, const l2z_weights *w,
                     int32_t *out_next, int32_t *out_accepted);
 
+/* ---- mixed step: prompt chunks and decode rows in one sweep of the weights (preview) ----
+ * What a server does when a request arrives while others decode: n sequences, one runstate each, of which sequence j brings
+ * n_tokens[j] consecutive positions pos0[j] .. pos0[j] + n_tokens[j] - 1.  A sequence of ONE row is a decode step; a sequence
+ * of two or more rows is a prompt chunk -- a whole prompt, or a slice of one that starts at pos0[j] > 0 (chunked prefill).
+ * tokens is the sequences' rows concatenated.  1 <= n <= L2Z_WIDE_MAX, n_tokens[j] >= 1, R = the sum of n_tokens[] <=
+ * L2Z_MIXED_ROWS_MAX.  The R rows run as ONE chunk of the ragged prompt pass on states[0]'s prefill scratch, as
+ * l2z_transformer_wide's n rows do: every weight matrix is read once per call.  Per layer the multi-row sequences take the
+ * prompt attention of l2z_prefill_batch, the one-row sequences the position-split decode attention of l2z_transformer_wide;
+ * the classifier runs on the n LAST rows only.
+ * State on return, per sequence: KV rows pos0[j] .. pos0[j] + n_tokens[j] - 1 of every layer written -- and NO other cache
+ * row of any runstate --, the runstate's logits those of its last row, the next position pos0[j] + n_tokens[j], the host
+ * bookkeeping as l2z_transformer_wide leaves it (whole logits, no per-block argmax candidates): every other entry point goes
+ * on from there.  out_next[j] = the token the sampler draws from those logits with (temperature[j], top_p[j], coins[j]) --
+ * ONE coin per sequence --; at temperature 0, or temperature == NULL (top_p and coins not read), the argmax by l2z_argmax's
+ * rule.  A caller in the middle of a prompt ignores the id.
+ * The call is synchronous (one copy back, one sync).  Streams: l2z_transformer_batch's rule.  Paged runstates are taken as
+ * the wide family takes them (all of one kind; pages attached on the host before anything is enqueued; L2Z_ERR_OOM leaves
+ * nothing attached; a write into a shared page is L2Z_ERR_STATE).
+ * WHAT IS PROMISED.
+ *   ALL-ONE-ROW IDENTITY.  With every n_tokens[j] == 1, each runstate's logits and every cache row are bit-identical to
+ *     l2z_transformer_wide on the same states, tokens, positions and order.
+ *   PROMPTS-ONLY IDENTITY.  With n <= L2Z_BATCH_MAX and every n_tokens[j] >= 2, every cache row is bit-identical to
+ *     l2z_prefill_batch on the same layout (while that call runs it as one chunk); the logits agree at the parity bar (that
+ *     call takes them by the mat-vec classifier).
+ *   NEIGHBOUR INVARIANCE.  For a fixed layout, sequence j's id, logits and KV rows are bit-identical whatever the other
+ *     sequences' tokens and caches hold, whatever stale rows lie beyond its own, and from run to run.
+ *   THE DRAW.  Given a sequence's logits, out_next[j] is bit for bit l2z_sample_batch's token for the same controls.
+ *   PARITY.  Against the CPU oracle and against l2z_prefill_batch followed by l2z_transformer_wide: the fp32 parity bar.
+ *   PAGED == contiguous, bit for bit.
+ * A refusal enqueues nothing and changes no state.  L2Z_ERR_INVALID: a NULL required argument, n outside [1, L2Z_WIDE_MAX],
+ * an n_tokens[j] < 1, R > L2Z_MIXED_ROWS_MAX, runstates that are not pairwise distinct, unsharded, of one kind, on one device
+ * and made with *config, weights of another config, dims l2z_prefill refuses, the sampler's controls as l2z_verify_wide
+ * refuses them.  L2Z_ERR_STATE: pos0[j] < 0, pos0[j] + n_tokens[j] > seq_len, a token outside the vocabulary.
+ * L2Z_ERR_NO_DEVICE without a device.
+ * Out of scope: the product header, map, Zig shim and CLI (ABI version 3); sharded runstates; more than one chunk per call;
+ * guesses and verdicts inside a mixed call (l2z_verify_wide); a loop on the device; hipGraph capture; the two attention
+ * launches on parallel streams. */
+#define L2Z_MIXED_ROWS_MAX 512
+int l2z_step_mixed(int n, const int32_t *tokens, const int32_t *n_tokens, const int32_t *pos0,
+                   const float *temperature /* [n] or NULL: all greedy */, const float *top_p /* [n] */,
+                   const float *coins /* [n]: one per SEQUENCE */,
+                   const l2z_config *config, l2z_runstate *const *states, const l2z_weights *w,
+                   int32_t *out_next /* [n] */);
+
 /* ---- paged KV cache: a shared page pool for the wide family (preview) ----
  * A contiguous runstate reserves seq_len rows of K and V in every layer whatever its sequence's length.  A PAGED runstate
  * reserves none: it draws pages of L2Z_KV_PAGE consecutive positions from a pool, on demand, and gives them back.  One page
@@ -472,7 +516,7 @@ int l2z_verify_wide(int n, const int32_t *tokens, const int32_t *n_tokens, const
  * seq_len that is no multiple of 64 leaves the last page partly used).  The pool's memory is zeroed once at creation;
  * recycled pages are NOT cleared (stale finite rows beyond a sequence's position are covered by the wide family's
  * invariance promises).
- * WHO TAKES THEM.  l2z_prefill_batch, l2z_transformer_wide, l2z_wide_run and l2z_verify_wide, whose kernels touch a cache
+ * WHO TAKES THEM.  l2z_prefill_batch, l2z_transformer_wide, l2z_wide_run, l2z_verify_wide and l2z_step_mixed, whose kernels touch a cache
  * in units of 64 absolute positions anyway: a page changes where a block finds its rows and no summation order, so a paged
  * sequence's ids, accepted counts, logits and KV rows are BIT-IDENTICAL to a contiguous one's under the same calls.  All
  * runstates of a call are of one kind -- all contiguous, or all paged from one pool --, else L2Z_ERR_INVALID.  Every other

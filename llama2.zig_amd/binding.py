@@ -113,6 +113,8 @@ def lib():
         L.l2z_verify_batch.argtypes = [C.c_int, i32p, i32p, i32p, fp, fp, fp, cfgp, C.POINTER(vp), vp, i32p, i32p]
     if hasattr(L, "l2z_verify_wide"):
         L.l2z_verify_wide.argtypes = [C.c_int, i32p, i32p, i32p, fp, fp, fp, cfgp, C.POINTER(vp), vp, i32p, i32p]
+    if hasattr(L, "l2z_step_mixed"):
+        L.l2z_step_mixed.argtypes = [C.c_int, i32p, i32p, i32p, fp, fp, fp, cfgp, C.POINTER(vp), vp, i32p]
     if hasattr(L, "l2z_kvpool_init"):
         L.l2z_kvpool_init.argtypes = [cfgp, C.c_int, C.POINTER(vp)]
         L.l2z_kvpool_free.argtypes = [vp]
@@ -817,6 +819,129 @@ def _verify_rows(call, states, token_lists, pos0s, w, temperature, top_p, coin_l
               acc.ctypes.data_as(i32p)))
     ends = np.cumsum(nt[:n])
     return [nxt[e - m: e].copy() for e, m in zip(ends, nt[:n])], acc[:n].copy()
+
+
+MIXED_ROWS_MAX = 512  # L2Z_MIXED_ROWS_MAX
+
+
+def step_mixed(states, token_lists, pos0s, w: Weights, temperature=None, top_p=None, coins=None) -> np.ndarray:
+    """l2z_step_mixed: states[j] runs token_lists[j] at positions pos0s[j] .. in ONE sweep of the weights -- a list of one
+    token is a decode step, a longer one a prompt chunk (a preview entry point of the test library:
+    include/llama2_hip_test.h).  Up to WIDE_MAX sequences and MIXED_ROWS_MAX rows in all.  temperature=None: greedy;
+    otherwise temperature and top_p are one value per sequence (or a scalar for all) and coins holds ONE coin per sequence
+    (None where every temperature is 0).  Returns the n ids drawn from the sequences' last rows; every runstate's logits
+    are its last row's."""
+    n = len(states)
+    ss = (C.c_void_p * max(n, 1))(*[s.h for s in states])
+    lists = [np.ascontiguousarray(t, np.int32).reshape(-1) for t in token_lists]
+    assert len(lists) == n, "one token list per runstate"
+    nt = np.zeros(max(n, 1), np.int32)
+    nt[:n] = [t.size for t in lists]
+    p0 = np.zeros(max(n, 1), np.int32)
+    p0[:n] = np.broadcast_to(np.asarray(pos0s, np.int32), (n,)) if n else []
+    t = np.ascontiguousarray(np.concatenate(lists + [np.zeros(1, np.int32)]), np.int32)  # (never empty)
+    tp = pp = cp = None
+    if temperature is not None:
+        tp, pp = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float32)
+        tp[:n] = np.broadcast_to(np.asarray(temperature, np.float32), (n,)) if n else []
+        pp[:n] = np.broadcast_to(np.asarray(1.0 if top_p is None else top_p, np.float32), (n,)) if n else []
+        if coins is not None:
+            cp = np.zeros(max(n, 1), np.float32)
+            cp[:n] = np.broadcast_to(np.asarray(coins, np.float32), (n,)) if n else []
+    nxt = np.zeros(max(n, 1), np.int32)
+    cfg = states[0].cfg if n else L2ZConfig()
+    i32p = C.POINTER(C.c_int32)
+    _chk(lib().l2z_step_mixed(n, t.ctypes.data_as(i32p), nt.ctypes.data_as(i32p), p0.ctypes.data_as(i32p),
+                              None if tp is None else _fp(tp), None if pp is None else _fp(pp),
+                              None if cp is None else _fp(cp), C.byref(cfg), ss, w.h, nxt.ctypes.data_as(i32p)))
+    return nxt[:n].copy()
+
+
+def serve(requests, w: Weights, pool: KvPool, *, max_seqs: int = WIDE_MAX, row_budget: int = MIXED_ROWS_MAX,
+          chunk: int | None = None, temperature=None, top_p=None, coins=None, bos: int = 1):
+    """Continuous batching over paged runstates: a queue of requests turned into step_mixed calls.  requests[i] =
+    (tokens, max_new): the tokens fed from position 0 on (the caller's BOS included) and how many ids to draw at most.
+    Every step gives each sequence that is decoding its one row, then fills what is left of row_budget with slices (of at
+    most `chunk` rows; None: whatever fits) of partly prefilled or waiting requests in arrival order.  A waiting request is
+    admitted only while fewer than max_seqs are in flight -- fewer than row_budget too: every sequence in flight may need a
+    row of every step, so no step runs more than row_budget rows -- and the pool's free pages, less what the requests in
+    flight may still take, hold its whole prompt plus max_new; nothing is preempted.  A sequence retires at `bos`, at max_new ids, or
+    at seq_len; its pages go back (trim) and its runstate serves the next request.
+    temperature / top_p: None (greedy), a scalar, or one value per request; coins: per request, the coin of its g-th id
+    (generate_sample's convention; None where greedy).
+    Returns (ids, trace): ids[i] = request i's ids (its BOS, if drawn, the last), trace[k] = step k's layout: a dict of
+    "ids" (the requests, in call order), "n_tokens", "pos0" and "pages" (the pool pages each of them holds after the step,
+    as RunState.pages() lists them).  The scheduler is host code; it adds nothing on the device."""
+    cfg = pool.cfg
+    n_req = len(requests)
+    max_seqs = max(1, min(int(max_seqs), WIDE_MAX))
+    row_budget = max(1, min(int(row_budget), MIXED_ROWS_MAX))
+    max_seqs = min(max_seqs, row_budget)
+    chunk = row_budget if chunk is None else max(1, int(chunk))
+    prompts = [np.ascontiguousarray(r[0], np.int32).reshape(-1) for r in requests]
+    max_new = [int(r[1]) for r in requests]
+    for i in range(n_req):
+        if not 1 <= prompts[i].size <= cfg.seq_len or max_new[i] < 1:
+            raise ValueError(f"request {i}: {prompts[i].size} tokens (1 .. seq_len), max_new {max_new[i]} (at least 1)")
+    temp = None if temperature is None else np.broadcast_to(np.asarray(temperature, np.float32), (n_req,))
+    topp = np.broadcast_to(np.asarray(1.0 if top_p is None else top_p, np.float32), (n_req,))
+    pages_of = [(min(prompts[i].size + max_new[i], cfg.seq_len) + KV_PAGE - 1) // KV_PAGE for i in range(n_req)]
+    pages_free = pool.info()["n_free"]   # less what the requests in flight have been promised
+    if any(p > pages_free for p in pages_of):
+        raise ValueError("a request needs more pages than the pool has free")
+    idle, flight, waiting = [], [], list(range(n_req))   # runstates; requests in flight, in arrival order; the queue
+    fed = [0] * n_req            # rows of the request already run = its next position
+    out = [[] for _ in range(n_req)]
+    state_of = {}
+    trace = []
+    try:
+        while flight or waiting:
+            rows = {i: 1 for i in flight if fed[i] >= prompts[i].size}   # the decoders' rows first
+            left = row_budget - len(rows)
+            for i in flight:
+                if i not in rows and left > 0:
+                    rows[i] = min(chunk, left, prompts[i].size - fed[i])
+                    left -= rows[i]
+            while waiting and left > 0 and len(flight) < max_seqs and pages_of[waiting[0]] <= pages_free:
+                i = waiting.pop(0)
+                pages_free -= pages_of[i]
+                if not idle:
+                    idle.append(RunState(cfg, pool=pool))
+                state_of[i] = idle.pop()
+                flight.append(i)
+                rows[i] = min(chunk, left, prompts[i].size)
+                left -= rows[i]
+            call = [i for i in flight if i in rows]   # (never empty: a decoder has its row, and an empty flight admits)
+            lists, p0 = [], []
+            for i in call:
+                if fed[i] >= prompts[i].size:
+                    lists.append([out[i][-1]])
+                else:
+                    lists.append(prompts[i][fed[i]: fed[i] + rows[i]])
+                p0.append(fed[i])
+            tp = pp = cp = None
+            if temp is not None:
+                tp, pp = [temp[i] for i in call], [topp[i] for i in call]
+                cp = [float(coins[i][len(out[i])]) if tp[k] > 0 else 0.0 for k, i in enumerate(call)]
+            nxt = step_mixed([state_of[i] for i in call], lists, p0, w, tp, pp, cp)
+            held = [state_of[i].pages() for i in call]
+            trace.append({"ids": list(call), "n_tokens": [int(rows[i]) for i in call], "pos0": list(p0),
+                          "pages": [[int(p) for p in h[h >= 0]] for h in held]})
+            for k, i in enumerate(call):
+                fed[i] += rows[i]
+                if fed[i] < prompts[i].size:
+                    continue   # still in its prompt: the id is ignored
+                out[i].append(int(nxt[k]))
+                if out[i][-1] == bos or len(out[i]) >= max_new[i] or fed[i] >= cfg.seq_len:
+                    s = state_of.pop(i)
+                    s.trim(0)
+                    idle.append(s)
+                    flight.remove(i)
+                    pages_free += pages_of[i]
+    finally:
+        for s in list(state_of.values()) + idle:
+            s.close()
+    return [np.asarray(o, np.int32) for o in out], trace
 
 
 def runstate_fork(dst: RunState, src: RunState, n_pos: int) -> None:

@@ -22,6 +22,15 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ v4f ldg_nt(const v4f *p) { return __builtin_nontemporal_load(p); }
 
+// src[0 .. n) -> dst by a block of n_threads threads (tid: the caller's): float4 where both sides are 16-byte aligned.  The
+// copy that hands a row of a logits matrix to its runstate (wide_sample.hip, wide_verify.hip, mixed_step.hip).
+__device__ __forceinline__ void block_copy_row(float *dst, const float *src, const int n, const int tid, const int n_threads)
+{
+    const int n4 = ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0) ? n >> 2 : 0;
+    for (int i = tid; i < n4; i += n_threads) ((v4f *)dst)[i] = ((const v4f *)src)[i];
+    for (int i = 4 * n4 + tid; i < n; i += n_threads) dst[i] = src[i];
+}
+
 // Cross-lane reductions.  Inside a 16-lane row the exchange is a DPP modifier on a VALU op
 // (a few cycles); ds_bpermute-based __shfl_xor (~100 cycles each, and the five steps of one
 // sum are a dependent chain) is kept only for the 16- and 32-lane hops.  s_memtime showed the

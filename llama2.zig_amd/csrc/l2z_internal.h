@@ -306,7 +306,8 @@ GemmPlan prefill_gemm_plan(const GemmShape &s);
 hipError_t launch_prefill_rmsnorm(float *o, int ldo, const float *x, const float *w, int n, int P,
                                   hipStream_t st,    // o: rows of ldo floats (the pad columns are left alone)
                                   void *x3 = nullptr, int kp = 0,    // != null: o's planes of bf16 terms too (x3[token][3][kp], kp == n)
-                                  const DeferredSum *pending = nullptr);   // valid: x += the ranges' sums first (x is written back)
+                                  const DeferredSum *pending = nullptr,    // valid: x += the ranges' sums first (x is written back)
+                                  const int *rows = nullptr);   // != null (device): o's row t is the norm of x's row rows[t] (no pending sums)
 hipError_t launch_prefill_embed(float *x, const float *tok_emb, const int *tokens, int dim, int P,
                                 hipStream_t st);
 // kv_row / kv_head: floats between timesteps of one kv head / between kv heads (AttnArgs)
@@ -320,6 +321,7 @@ hipError_t launch_prefill_attention(const float *q, int ldq, const float *kcache
 // ---- prefill_ragged.hip: a chunk whose rows belong to SEVERAL sequences (l2z_prefill_batch; prefill_batch_host.cpp) ----
 constexpr int kRaggedMaxSeq = 16;   // L2Z_BATCH_MAX
 struct WideAttn;                    // wide_decode.h
+struct MixedAttn;                   // mixed_step.h
 struct RaggedSeq {     // one sequence's rows of a chunk
     float *kc, *vc;    // its runstate's key / value caches (layer 0): [layer][kv head][seq_len][head_size]
     int row0, rows;    // its first row in the chunk, how many
@@ -353,6 +355,11 @@ struct RaggedChunk {
     const WideAttn *wide;   // != null (l2z_transformer_wide): every row is a sequence of its own at one position -- the
                             // attention is launch_wide_attention (wide_decode.h) on this table; tiles and n_tiles are not read
                             // (wide->verify_m != 0, l2z_verify_wide: sequences of several rows, launch_wide_verify_attention)
+    const MixedAttn *mixed; // != null (l2z_step_mixed): sequences of one row and of several in one chunk -- the attention is
+                            // launch_mixed_attention (mixed_step.h); n_seq may reach kMixedSeqMax, tiles name the sequences of
+                            // several rows only
+    const int *att_rows;    // != null: the n_att_rows rows launch_ragged_attention's block-per-(head, row) form serves (the
+    int n_att_rows;         // flash form's are the tile list's); null: all P
 };
 // q [P, dim] rotated in place, k rotated, and k / v stored into row row_pos[r] of sequence row_seq[r]'s caches: the
 // arithmetic of the q | k | v product's own epilogue (prefill_gemm.hip), one launch

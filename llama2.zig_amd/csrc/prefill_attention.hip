@@ -22,11 +22,12 @@ __device__ __forceinline__ const float *deferred_at(const DeferredSum &d, int t,
 }
 
 __global__ __launch_bounds__(kPfBlock) void prefill_rmsnorm(float *o, int ldo, float *x, const float *w,
-                                                            int n, int P, __bf16 *x3, int kp, const DeferredSum pend)
+                                                            int n, int P, __bf16 *x3, int kp, const DeferredSum pend,
+                                                            const int *rows)
 {
     __shared__ float red[8];
     const int t = blockIdx.x;
-    float *xr = x + (size_t)t * n;
+    float *xr = x + (size_t)(rows ? rows[t] : t) * n;   // (rows: a gather, l2z_step_mixed's last rows; the host passes no pend with it)
     const int n4 = n >> 2;  // n % 4 == 0 on this path
     constexpr int R = 8;    // float4 kept in registers per lane: one round trip up to n = 8192
     const bool in_regs = n4 <= R * kPfBlock;
@@ -488,16 +489,17 @@ __global__ __launch_bounds__(kPfBlock) void prefill_attention_tiled(const float 
 }  // namespace
 
 hipError_t launch_prefill_rmsnorm(float *o, int ldo, const float *x, const float *w, int n, int P,
-                                  hipStream_t st, void *x3, int kp, const DeferredSum *pending)
+                                  hipStream_t st, void *x3, int kp, const DeferredSum *pending, const int *rows)
 {
     if (x3 != nullptr && (kp != n || (n & 3))) return hipErrorInvalidValue;   // (pad columns: the split launch writes their zeros)
     DeferredSum pend = {nullptr, 1, 128, 1, false};
     if (pending != nullptr && pending->valid) {
+        if (rows != nullptr) return hipErrorInvalidValue;   // (the sums are laid out by the chunk's own rows)
         if (pending->part == nullptr || (pending->sk != 2 && pending->sk != 4 && pending->sk != 8) || (pending->feat & 31) || pending->tm * 32 < P)
             return hipErrorInvalidValue;
         pend = *pending;
     }
-    hipLaunchKernelGGL(prefill_rmsnorm, dim3(P), dim3(kPfBlock), 0, st, o, ldo, const_cast<float *>(x), w, n, P, (__bf16 *)x3, kp, pend);
+    hipLaunchKernelGGL(prefill_rmsnorm, dim3(P), dim3(kPfBlock), 0, st, o, ldo, const_cast<float *>(x), w, n, P, (__bf16 *)x3, kp, pend, rows);
     return hipGetLastError();
 }
 

@@ -17,7 +17,10 @@ namespace {
 size_t tab_tiles_max(int cap) { return (size_t)cap / 64 + kRaggedMaxSeq; }
 size_t tab_bytes(int cap) { return kRaggedMaxSeq * sizeof(RaggedSeq) + (size_t)cap * 8 + tab_tiles_max(cap) * sizeof(int2); }
 
-int ragged_alloc(l2z_runstate *s, int need)
+}  // namespace
+
+// (l2z_step_mixed takes rg_k / rg_v from here too: wide_host.cpp)
+int l2z::ragged_alloc(l2z_runstate *s, int need)
 {
     if (s->rg_cap >= need) return L2Z_OK;
     const size_t P = (size_t)(need + 511) / 512 * 512;   // as prefill_alloc
@@ -33,8 +36,6 @@ int ragged_alloc(l2z_runstate *s, int need)
     s->rg_cap = (int)P;
     return L2Z_OK;
 }
-
-}  // namespace
 
 extern "C" int l2z_prefill_batch(int n, const int32_t *tokens, const int32_t *n_tokens, const int32_t *pos0,
                                  const l2z_config *config, l2z_runstate *const *states, const l2z_weights *w)

@@ -7,6 +7,7 @@
 
 #include "batch_host.h"
 #include "l2z_state.h"
+#include "mixed_step.h"
 #include "prefill_common.h"
 #include "wide_decode.h"
 
@@ -314,7 +315,10 @@ int prefill_stage(l2z_runstate *s, const l2z_weights *w, int l, int k, int P, in
         L2Z_HIP(launch_ragged_rope_scatter(s->pf_q, dim, *rg, P, dim, kvd, hs, s->rope, layer_off, kvh_stride, st));
         bool att_planes = false;
         const bool want = planes_for(dim, dim, sk_wo);
-        if (rg->wide != nullptr && rg->wide->verify_m != 0)   // l2z_verify_wide: a sequence's rows are a block's slots (wide_verify.hip)
+        if (rg->mixed != nullptr)   // l2z_step_mixed: prompt attention for the sequences of several rows, decode attention for the rest (mixed_step.hip)
+            L2Z_HIP(launch_mixed_attention(s->pf_q, dim, out, ldo, *rg, P, c.n_heads, hs, layer_off, kvh_stride,
+                                           c.n_heads / c.n_kv_heads, c.seq_len, st, want ? ws->x3 : nullptr, dim, &att_planes));
+        else if (rg->wide != nullptr && rg->wide->verify_m != 0)   // l2z_verify_wide: a sequence's rows are a block's slots (wide_verify.hip)
             L2Z_HIP(launch_wide_verify_attention(s->pf_q, dim, out, ldo, *rg->wide, rg->n_seq, P, c.n_heads, hs, layer_off,
                                                  kvh_stride, c.n_heads / c.n_kv_heads, st, want ? ws->x3 : nullptr, dim,
                                                  &att_planes));
@@ -599,13 +603,15 @@ namespace l2z {
 // l2z_transformer_wide: the logits of ALL P rows of the chunk the layers just finished, as score_chunk's step 1 and 2 --
 // final rmsnorm into pf_xn, then the classifier by launch_prefill_gemm(PG_STORE) with the whole vocabulary as
 // n_launch_whole -- into out [P, ldo], in as few vocabulary slabs as the split-K workspace allows (score_chunk's rule).
-int prefill_rows_logits(l2z_runstate *s, const l2z_weights *w, int P, float *out, int ldo)
+// rows != null (l2z_step_mixed; a device list): the P rows are rows[0 .. P) of the chunk, gathered by the norm launch into the
+// first P rows of pf_xn -- the classifier runs at P rows, whatever the chunk held.
+int prefill_rows_logits(l2z_runstate *s, const l2z_weights *w, int P, float *out, int ldo, const int *rows)
 {
     const l2z_config &c = s->cfg;
     hipStream_t st = s->stream;
     const int dim = c.dim, V = c.vocab_size, ldxn = s->pf_ld_xn;
     L2Z_CHECK(!s->pf_pending.valid, L2Z_ERR_INVALID, "l2z_transformer_wide: the last layer left its residual product's sums behind");
-    L2Z_HIP(launch_prefill_rmsnorm(s->pf_xn, ldxn, s->pf_x, w->rms_final, dim, P, st));   // :426, all rows
+    L2Z_HIP(launch_prefill_rmsnorm(s->pf_xn, ldxn, s->pf_x, w->rms_final, dim, P, st, nullptr, 0, nullptr, rows));   // :426: all P rows, or the P listed ones
     const int kp = (dim + 63) / 64 * 64;
     const int sk = prefill_split_k(V, P, kp, false);
     const int cols = slab_cols_that_fit(s, P, sk, kp, score_nseg(c) * kScoreSeg);

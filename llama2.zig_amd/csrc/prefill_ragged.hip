@@ -4,6 +4,7 @@
 // the pass treats the rows of a chunk independently and is l2z_prefill's own.
 // A row's results depend on its own sequence's rows and caches and on the chunk's table -- never on what the other
 // sequences hold (no reduction here crosses a sequence, no block shares state between two).
+#include "mixed_plan.h"
 #include "prefill_common.h"
 
 namespace l2z {
@@ -61,6 +62,7 @@ struct RaggedAttnArgs {
     const RaggedSeq *seq;
     const int *row_seq, *row_pos;
     const int2 *tiles;
+    const int *rows;             // the block-per-(head, row) form: != null, block y serves row rows[y] (null: row y)
     size_t layer_off, kv_head;   // floats to this layer in a cache; between kv heads (paged: in a page)
     size_t page_floats;          // paged sequences: floats per page of the pool
     int ldq, ldo, kv_mul, seq_len, head_size;
@@ -81,7 +83,7 @@ __global__ __launch_bounds__(kPfBlock) void ragged_attention_rows(const RaggedAt
     float *att = lds;                                   // seq_len
     float *part = att + ((a.seq_len + 3) & ~3);         // G*hs
     float *red = part + (size_t)G * hs;                 // 8
-    const int h = blockIdx.x, row = blockIdx.y;
+    const int h = blockIdx.x, row = a.rows ? a.rows[blockIdx.y] : blockIdx.y;
     const RaggedSeq sq = a.seq[a.row_seq[row]];
     const int T = a.row_pos[row] + 1;
     const int kvh = h / a.kv_mul;
@@ -326,11 +328,13 @@ hipError_t launch_ragged_attention(const float *q, int ldq, float *out, int ldo,
                                    hipStream_t st, void *x3, int kp, bool *planes_written)
 {
     if (planes_written) *planes_written = false;
-    if (P <= 0 || (head_size & 3) || head_size > 256 || rg.n_seq < 1 || rg.n_seq > kRaggedMaxSeq) return hipErrorInvalidValue;
+    if (P <= 0 || (head_size & 3) || head_size > 256 || rg.n_seq < 1 || rg.n_seq > (rg.mixed != nullptr ? kMixedSeqMax : kRaggedMaxSeq) ||
+        (rg.att_rows != nullptr && (rg.n_att_rows < 1 || rg.n_att_rows > P)))
+        return hipErrorInvalidValue;
     RaggedAttnArgs a = {};
     a.q = q; a.out = out; a.seq = rg.seq; a.row_seq = rg.row_seq; a.row_pos = rg.row_pos; a.tiles = rg.tiles;
     a.layer_off = layer_off; a.kv_head = kv_head_stride; a.ldq = ldq; a.ldo = ldo; a.kv_mul = kv_mul; a.seq_len = seq_len;
-    a.head_size = head_size; a.page_floats = rg.page_floats;
+    a.head_size = head_size; a.page_floats = rg.page_floats; a.rows = rg.att_rows;
     // (the caches come from hipMalloc and a layer / a kv head is a multiple of head_size floats: 16-byte aligned rows)
     if ((head_size == 64 || head_size == 128) && (ldq % 4) == 0 && (ldo % 4) == 0 && rg.n_tiles > 0 &&
         (((uintptr_t)q | (uintptr_t)out) & 15) == 0) {
@@ -357,7 +361,7 @@ hipError_t launch_ragged_attention(const float *q, int ldq, float *out, int ldo,
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(ragged_attention_rows, dim3(n_heads, P), dim3(kPfBlock), lds, st, a);
+    hipLaunchKernelGGL(ragged_attention_rows, dim3(n_heads, rg.att_rows != nullptr ? rg.n_att_rows : P), dim3(kPfBlock), lds, st, a);
     return hipGetLastError();
 }
 

@@ -58,6 +58,22 @@ struct WideAttn {
 hipError_t launch_wide_attention(const float *q, int ldq, float *out, int ldo, const WideAttn &wa, int n, int n_heads,
                                  int head_size, size_t layer_off, size_t kv_head_stride, int kv_mul, hipStream_t st,
                                  void *x3 = nullptr, int kp = 0, bool *planes_written = nullptr);
+// The same two launches over rows named one by one (l2z_step_mixed, mixed_step.hip: the one-row sequences of a chunk that
+// holds prompt rows too): block ordinal i of either launch serves row list[i].x of the chunk -- q, out, the planes, pos[] --
+// on sequence slot list[i].y of seq[]; the partials stand at the ORDINAL, n <= kWideMax of them.  list == null: row = slot =
+// ordinal, which is launch_wide_attention -- one kernel body for both, so the bits of a row do not depend on how it is named.
+struct WideRows {
+    const int32_t *pos;      // device: [rows of the chunk]
+    const RaggedSeq *seq;    // device: [sequence slots]
+    const int2 *list;        // device: [n], or null
+    int n;
+    float *part;             // wide_part_floats
+    int seg_cap, n_seg;      // as WideAttn's; n_seg: segments of the deepest listed row
+    size_t page_floats;
+};
+hipError_t launch_wide_attention_rows(const float *q, int ldq, float *out, int ldo, const WideRows &wr, int n_heads, int head_size,
+                                      size_t layer_off, size_t kv_head_stride, int kv_mul, hipStream_t st, void *x3 = nullptr,
+                                      int kp = 0, bool *planes_written = nullptr);
 // wide_combine alone, over the partials some attention launch left for rows 0 .. n - 1 (tab->pos[row] = the row's position)
 hipError_t launch_wide_combine(float *out, int ldo, const WideAttn &wa, int n, int n_heads, int head_size, hipStream_t st,
                                void *x3 = nullptr, int kp = 0, bool *planes_written = nullptr);

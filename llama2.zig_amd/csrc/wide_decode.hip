@@ -21,8 +21,11 @@ constexpr int kWaHeadsMax = 4;  // query heads of one kv head a block serves (8:
 struct WideAttnArgs {
     const float *q;
     float *out;
-    const WideTable *tab;
-    float *part_o, *part_ml;  // [kWideMax, n_heads, seg_cap, head_size] and [..., 2]
+    const int32_t *pos;       // [rows of the chunk] a row's position
+    const RaggedSeq *seq;     // [sequence slots] the caches (and pages) of a slot
+    const int2 *list;         // != null (l2z_step_mixed): block ordinal i serves row list[i].x of sequence slot list[i].y;
+                              // null: row = slot = ordinal
+    float *part_o, *part_ml;  // [kWideMax, n_heads, seg_cap, head_size] and [..., 2], by ORDINAL
     size_t layer_off, kv_head_stride;
     size_t page_floats;       // paged sequences (RaggedSeq::pages): floats per page of the pool
     int ldq, ldo, n_heads, kv_mul, head_size, seg_cap;
@@ -30,15 +33,17 @@ struct WideAttnArgs {
     int kp;
 };
 
-// Block (kv head x part, segment, row); MQ = query heads per block (a part = MQ consecutive heads of the kv head: one part
+// Block (kv head x part, segment, ordinal); MQ = query heads per block (a part = MQ consecutive heads of the kv head: one part
 // while kv_mul <= kWaHeadsMax).  The part's heads are the slots of segment_attention_body: every head sees the keys up to
 // the row's position, which is where the segment ends for the block.
 template <int MQ>
 __global__ __launch_bounds__(kVaBlock) void wide_attention(const WideAttnArgs a)
 {
     __shared__ __attribute__((aligned(16))) float sc[seg_lds_floats<MQ>];
-    const int row = blockIdx.z, seg = blockIdx.y;
-    const int pos = a.tab->pos[row];
+    const int ord = blockIdx.z, seg = blockIdx.y;
+    int row = ord, slot = ord;
+    if (a.list != nullptr) { const int2 d = a.list[ord]; row = d.x; slot = d.y; }   // (uniform)
+    const int pos = a.pos[row];
     const int seg0 = seg * kVerifySeg;
     if (seg0 > pos) return;  // past this row's last segment (uniform, before any barrier)
     const int parts = (a.kv_mul + MQ - 1) / MQ;
@@ -48,10 +53,10 @@ __global__ __launch_bounds__(kVaBlock) void wide_attention(const WideAttnArgs a)
     SegSlots s = {};
     s.q = a.q + (size_t)row * a.ldq + (size_t)h0 * a.head_size; s.q_step = (size_t)a.head_size;
     s.see0 = pos; s.see_step = 0;
-    s.idx0 = (size_t)row * a.n_heads + h0; s.part_step = 1;
+    s.idx0 = (size_t)ord * a.n_heads + h0; s.part_step = 1;
     s.act = (1u << nq) - 1u;
     s.part_o = a.part_o; s.part_ml = a.part_ml; s.seg_cap = a.seg_cap;
-    const RaggedSeq sq = a.tab->seq[row];
+    const RaggedSeq sq = a.seq[slot];
     size_t head_off = a.layer_off + (size_t)kvh * a.kv_head_stride;
     // paged: the block's segment is ONE page; the body addresses key t at base + t * head_size, so the base takes the
     // page's start less the segment's first row (one dependent 4-byte read per block, uniform)
@@ -59,13 +64,14 @@ __global__ __launch_bounds__(kVaBlock) void wide_attention(const WideAttnArgs a)
     segment_attention_body<MQ>(s, sq.kc + head_off, sq.vc + head_off, a.head_size, seg, min(seg0 + kVerifySeg - 1, pos), sc);
 }
 
-// Block (head, row), lane c = four features: the row's segments 0 .. pos / kVerifySeg through segment_combine_body
+// Block (head, ordinal), lane c = four features: the row's segments 0 .. pos / kVerifySeg through segment_combine_body
 __global__ __launch_bounds__(64) void wide_combine(const WideAttnArgs a)
 {
-    const int h = blockIdx.x, row = blockIdx.y, c = threadIdx.x, hs = a.head_size;
+    const int h = blockIdx.x, ord = blockIdx.y, c = threadIdx.x, hs = a.head_size;
     if (c >= (hs >> 2)) return;
-    const v4f r = segment_combine_body<kWcUB>(a.part_o, a.part_ml, ((size_t)row * a.n_heads + h) * a.seg_cap,
-                                              a.tab->pos[row] / kVerifySeg + 1, hs, c);
+    const int row = a.list != nullptr ? a.list[ord].x : ord;
+    const v4f r = segment_combine_body<kWcUB>(a.part_o, a.part_ml, ((size_t)ord * a.n_heads + h) * a.seg_cap,
+                                              a.pos[row] / kVerifySeg + 1, hs, c);
     *(v4f *)(a.out + (size_t)row * a.ldo + (size_t)h * hs + 4 * c) = r;
     if (a.x3) planes_store4(a.x3, a.kp, row, h * hs + 4 * c, r);
 }
@@ -106,19 +112,28 @@ __global__ __launch_bounds__(1024) void wide_logits_out(const float *logits, int
 
 }  // namespace
 
-// what both launchers ask of the partials and the output, and the arguments the combine reads
-static bool wide_out_args(WideAttnArgs &a, float *out, int ldo, const WideAttn &wa, int n, int n_heads, int head_size, void *x3,
-                          int kp)
+// what the launchers ask of the partials and the output, and the arguments the combine reads
+static bool wide_out_args(WideAttnArgs &a, float *out, int ldo, const WideRows &wr, int n_heads, int head_size, void *x3, int kp)
 {
-    if (n < 1 || n > kWideMax || head_size < 4 || head_size > 256 || (head_size & 3) || n_heads < 1 || wa.tab == nullptr ||
-        wa.part == nullptr || wa.n_seg < 1 || wa.n_seg > wa.seg_cap || (ldo & 3) || (((uintptr_t)out | (uintptr_t)wa.part) & 15))
+    if (wr.n < 1 || wr.n > kWideMax || head_size < 4 || head_size > 256 || (head_size & 3) || n_heads < 1 || wr.pos == nullptr ||
+        wr.seq == nullptr || wr.part == nullptr || wr.n_seg < 1 || wr.n_seg > wr.seg_cap || (ldo & 3) ||
+        (((uintptr_t)out | (uintptr_t)wr.part) & 15))
         return false;
-    a.out = out; a.tab = wa.tab;
-    a.part_o = wa.part;
-    a.part_ml = wa.part + (size_t)kWideMax * n_heads * wa.seg_cap * head_size;
-    a.ldo = ldo; a.n_heads = n_heads; a.head_size = head_size; a.seg_cap = wa.seg_cap;
+    a.out = out; a.pos = wr.pos; a.seq = wr.seq; a.list = wr.list;
+    a.part_o = wr.part;
+    a.part_ml = wr.part + (size_t)kWideMax * n_heads * wr.seg_cap * head_size;
+    a.ldo = ldo; a.n_heads = n_heads; a.head_size = head_size; a.seg_cap = wr.seg_cap;
     if (x3 != nullptr && (kp & 3) == 0 && (((uintptr_t)x3) & 7) == 0) { a.x3 = (__bf16 *)x3; a.kp = kp; }
     return true;
+}
+
+// the wide step's rows: row i of the chunk = sequence slot i of the table
+static WideRows rows_of(const WideAttn &wa, int n)
+{
+    WideRows wr = {};
+    if (wa.tab != nullptr) { wr.pos = wa.tab->pos; wr.seq = wa.tab->seq; }
+    wr.n = n; wr.part = wa.part; wr.seg_cap = wa.seg_cap; wr.n_seg = wa.n_seg; wr.page_floats = wa.page_floats;
+    return wr;
 }
 
 static hipError_t combine_launch(const WideAttnArgs &a, int n, hipStream_t st, bool *planes_written)
@@ -129,19 +144,19 @@ static hipError_t combine_launch(const WideAttnArgs &a, int n, hipStream_t st, b
     return e;
 }
 
-hipError_t launch_wide_attention(const float *q, int ldq, float *out, int ldo, const WideAttn &wa, int n, int n_heads,
-                                 int head_size, size_t layer_off, size_t kv_head_stride, int kv_mul, hipStream_t st, void *x3,
-                                 int kp, bool *planes_written)
+hipError_t launch_wide_attention_rows(const float *q, int ldq, float *out, int ldo, const WideRows &wr, int n_heads, int head_size,
+                                      size_t layer_off, size_t kv_head_stride, int kv_mul, hipStream_t st, void *x3, int kp,
+                                      bool *planes_written)
 {
     if (planes_written) *planes_written = false;
     WideAttnArgs a = {};
-    if (!wide_out_args(a, out, ldo, wa, n, n_heads, head_size, x3, kp) || kv_mul < 1 || n_heads % kv_mul != 0 || (ldq & 3) ||
-        (((uintptr_t)q) & 15) || (layer_off & 3) || (kv_head_stride & 3) || (wa.page_floats & 3))
+    if (!wide_out_args(a, out, ldo, wr, n_heads, head_size, x3, kp) || kv_mul < 1 || n_heads % kv_mul != 0 || (ldq & 3) ||
+        (((uintptr_t)q) & 15) || (layer_off & 3) || (kv_head_stride & 3) || (wr.page_floats & 3))
         return hipErrorInvalidValue;
     a.q = q; a.ldq = ldq; a.kv_mul = kv_mul;
-    a.layer_off = layer_off; a.kv_head_stride = kv_head_stride; a.page_floats = wa.page_floats;
+    a.layer_off = layer_off; a.kv_head_stride = kv_head_stride; a.page_floats = wr.page_floats;
     const int mq = kv_mul == 1 ? 1 : kv_mul == 2 ? 2 : kWaHeadsMax;
-    const dim3 grid(n_heads / kv_mul * ((kv_mul + mq - 1) / mq), wa.n_seg, n);
+    const dim3 grid(n_heads / kv_mul * ((kv_mul + mq - 1) / mq), wr.n_seg, wr.n);
     switch (mq) {
         case 1: hipLaunchKernelGGL(wide_attention<1>, grid, dim3(kVaBlock), 0, st, a); break;
         case 2: hipLaunchKernelGGL(wide_attention<2>, grid, dim3(kVaBlock), 0, st, a); break;
@@ -149,7 +164,15 @@ hipError_t launch_wide_attention(const float *q, int ldq, float *out, int ldo, c
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    return combine_launch(a, n, st, planes_written);
+    return combine_launch(a, wr.n, st, planes_written);
+}
+
+hipError_t launch_wide_attention(const float *q, int ldq, float *out, int ldo, const WideAttn &wa, int n, int n_heads,
+                                 int head_size, size_t layer_off, size_t kv_head_stride, int kv_mul, hipStream_t st, void *x3,
+                                 int kp, bool *planes_written)
+{
+    return launch_wide_attention_rows(q, ldq, out, ldo, rows_of(wa, n), n_heads, head_size, layer_off, kv_head_stride, kv_mul, st,
+                                      x3, kp, planes_written);
 }
 
 hipError_t launch_wide_combine(float *out, int ldo, const WideAttn &wa, int n, int n_heads, int head_size, hipStream_t st,
@@ -157,7 +180,7 @@ hipError_t launch_wide_combine(float *out, int ldo, const WideAttn &wa, int n, i
 {
     if (planes_written) *planes_written = false;
     WideAttnArgs a = {};
-    if (!wide_out_args(a, out, ldo, wa, n, n_heads, head_size, x3, kp)) return hipErrorInvalidValue;
+    if (!wide_out_args(a, out, ldo, rows_of(wa, n), n_heads, head_size, x3, kp)) return hipErrorInvalidValue;
     return combine_launch(a, n, st, planes_written);
 }
 

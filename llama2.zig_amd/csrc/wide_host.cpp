@@ -7,15 +7,20 @@
 // last launch: the one that hands the [n, vocab] logits back (wide_decode.hip), or, inside a run, the one that draws every
 // row's token and hands the row to the next step (wide_sample.hip).  l2z_verify_wide is the same chunk with sequences of
 // several rows: the table's slots are sequences, the attention takes a sequence's rows as a block's slots, and the last
-// launches are the verdict (wide_verify.hip).
+// launches are the verdict (wide_verify.hip).  l2z_step_mixed (at the end of the file) is the chunk with sequences of one row
+// AND sequences of many, up to kMixedRowsMax rows: its own table (mixed_plan.h, mixed_step.h), prompt attention for the
+// multi-row sequences and the wide step's decode attention through a (row, slot) list for the rest, the classifier on the
+// last rows only.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
 
 #include "batch_host.h"
+#include "mixed_step.h"
 #include "wide_decode.h"
 
 static_assert(l2z::kWideMax == L2Z_WIDE_MAX, "include/llama2_hip_test.h L2Z_WIDE_MAX");
+static_assert(l2z::kMixedSeqMax == L2Z_WIDE_MAX && l2z::kMixedRowsMax == L2Z_MIXED_ROWS_MAX, "include/llama2_hip_test.h L2Z_MIXED_ROWS_MAX");
 
 namespace l2z {
 
@@ -41,16 +46,18 @@ struct WideScratch {
     int *d_ids = nullptr, *h_ids = nullptr;
     size_t run_cap = 0;                 // entries of coins / ids the four buffers hold
     float *smp = nullptr;               // kWideMax rows of sample_scratch_floats(vocab)
+    // l2z_step_mixed (on the first such call): its own table, kMixedSeqMax sequences and kMixedRowsMax rows, and the pinned twin
+    MixedTable *d_mtab = nullptr, *h_mtab = nullptr;
 };
 
 void wide_free(l2z_runstate *s)
 {
     WideScratch *b = s->wd;
     if (b == nullptr) return;
-    void *ptrs[] = {b->k, b->v, b->logits, b->part, b->d_next, b->d_tab, b->d_ctl, b->d_ids, b->smp};
+    void *ptrs[] = {b->k, b->v, b->logits, b->part, b->d_next, b->d_tab, b->d_ctl, b->d_ids, b->smp, b->d_mtab};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
-    void *pinned[] = {b->h_next, b->h_tab, b->h_ctl, b->h_ids};
+    void *pinned[] = {b->h_next, b->h_tab, b->h_ctl, b->h_ids, b->h_mtab};
     for (void *p : pinned)
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : b->ev_in)
@@ -402,5 +409,135 @@ extern "C" int l2z_verify_wide(int n, const int32_t *tokens, const int32_t *n_to
         out_accepted[j] = b->h_next[R + j];
         logits_whole(states[j], pos0[j] + out_accepted[j] + 1);
     }
+    return L2Z_OK;
+}
+
+// ---- l2z_step_mixed: prompt chunks and decode rows in ONE chunk of the ragged prompt pass (include/llama2_hip_test.h) ----
+namespace l2z {
+namespace {
+
+int mixed_alloc(l2z_runstate *s)
+{
+    WideScratch *b = s->wd;
+    if (b->d_mtab != nullptr && b->h_mtab != nullptr) return L2Z_OK;
+    L2Z_TRY(alloc_all("l2z_step_mixed table", {{(void **)&b->d_mtab, sizeof(MixedTable)}}));
+    if (b->h_mtab == nullptr) L2Z_HIP(hipHostMalloc((void **)&b->h_mtab, sizeof(MixedTable), hipHostMallocDefault));
+    return L2Z_OK;
+}
+
+// the plan and the call's arguments -> the pinned table (rewritten only once the last copy is done), one copy
+int mixed_upload_table(WideScratch *b, const MixedPlan &p, const int32_t *tokens, const int32_t *n_tokens, const int32_t *pos0,
+                       l2z_runstate *const *states, const float *temperature, const float *top_p, const float *coins)
+{
+    L2Z_HIP(hipEventSynchronize(b->ev_upload));
+    MixedTable *t = b->h_mtab;
+    for (int j = 0; j < p.n; j++) {
+        t->seq[j] = {nullptr, nullptr, p.seq_row0[j], n_tokens[j], pos0[j], 0, nullptr};
+        kv_seq_base(states[j], &t->seq[j]);
+        t->logits[j] = states[j]->logits;
+        t->last_row[j] = p.last_row[j];
+        t->temperature[j] = temperature ? temperature[j] : 0.0f;
+        t->top_p[j] = temperature ? top_p[j] : 0.0f;
+        t->coins[j] = temperature && temperature[j] > 0.0f ? coins[j] : 0.0f;   // (a greedy sequence's coin is not read)
+    }
+    memcpy(t->row_seq, p.row_seq, (size_t)p.R * 4);
+    memcpy(t->pos, p.row_pos, (size_t)p.R * 4);
+    memcpy(t->tokens, tokens, (size_t)p.R * 4);
+    memcpy(t->prompt_rows, p.prompt_rows, (size_t)p.n_prompt_rows * 4);
+    for (int i = 0; i < p.n_dec; i++) t->dec[i] = make_int2(p.dec_row[i], p.dec_seq[i]);
+    for (int i = 0; i < p.n_tiles; i++) t->tiles[i] = make_int2(p.tile_seq[i], p.tile_q0[i]);
+    L2Z_HIP(hipMemcpyAsync(b->d_mtab, t, sizeof(MixedTable), hipMemcpyHostToDevice, states[0]->stream));
+    return L2Z_OK;
+}
+
+}  // namespace
+}  // namespace l2z
+
+extern "C" int l2z_step_mixed(int n, const int32_t *tokens, const int32_t *n_tokens, const int32_t *pos0,
+                              const float *temperature, const float *top_p, const float *coins, const l2z_config *config,
+                              l2z_runstate *const *states, const l2z_weights *w, int32_t *out_next)
+{
+    const char *fn = "l2z_step_mixed";
+    // ---- checks: a refusal enqueues nothing and changes no state (l2z_verify_wide's, with this call's limits) ----
+    L2Z_TRY(no_device_check());
+    L2Z_CHECK(tokens != nullptr && n_tokens != nullptr && pos0 != nullptr && config != nullptr && w != nullptr && out_next != nullptr,
+              L2Z_ERR_INVALID, "%s: null argument", fn);
+    L2Z_TRY(check_states(fn, n, states, config, kWideMax));
+    L2Z_TRY(kv_check_kind(fn, n, states));
+    long long rows = 0;
+    for (int j = 0; j < n; j++) {
+        L2Z_CHECK(n_tokens[j] >= 1, L2Z_ERR_INVALID, "%s: n_tokens[%d] = %d (at least 1)", fn, j, n_tokens[j]);
+        rows += n_tokens[j];
+        L2Z_CHECK(rows <= kMixedRowsMax, L2Z_ERR_INVALID, "%s: more than %d rows in all", fn, kMixedRowsMax);
+    }
+    const int R = (int)rows;
+    for (int j = 0; j < n; j++) L2Z_TRY(check_pair(config, states[j], w, true));
+    L2Z_TRY(prefill_check(config, states[0]));
+    L2Z_CHECK(states[0]->sh.hs <= 256, L2Z_ERR_INVALID, "%s: head_size above 256", fn);
+    bool sampled = false;  // some sequence draws: l2z_sample_batch's rules for it
+    if (temperature != nullptr) {
+        L2Z_CHECK(top_p != nullptr, L2Z_ERR_INVALID, "%s: top_p is NULL beside a temperature array", fn);
+        for (int j = 0; j < n; j++) {
+            L2Z_TRY(check_draw(fn, j, temperature[j], top_p[j], coins));
+            if (temperature[j] == 0.0f) continue;
+            sampled = true;
+            L2Z_TRY(check_coins(fn, coins, j, 1));
+        }
+    }
+    for (int j = 0, r = 0; j < n; r += n_tokens[j], j++) {
+        char where[32];
+        snprintf(where, sizeof where, "sequence %d: ", j);
+        L2Z_TRY(check_positions(fn, where, "positions", pos0[j], n_tokens[j], config->seq_len));
+        L2Z_TRY(check_tokens(fn, where, tokens + r, n_tokens[j], config->vocab_size));
+    }
+    MixedPlan plan;
+    L2Z_CHECK(mixed_plan(n, n_tokens, pos0, &plan) && plan.R == R, L2Z_ERR_INVALID, "%s: no plan for this layout", fn);
+    l2z_runstate *s0 = states[0];
+    hipStream_t st = s0->stream;
+    L2Z_HIP(hipSetDevice(s0->device));
+    L2Z_TRY(prefill_scratch(s0, R));
+    L2Z_TRY(ragged_alloc(s0, R));   // (the chunk's key / value rows before the scatter: WideScratch's hold kWideMax rows only)
+    L2Z_TRY(wide_alloc(s0));
+    L2Z_TRY(mixed_alloc(s0));
+    WideScratch *b = s0->wd;
+    if (sampled)
+        L2Z_TRY(alloc_all("l2z_step_mixed sampler scratch",
+                          {{(void **)&b->smp, (size_t)kWideMax * sample_scratch_floats(config->vocab_size) * 4}}));
+    L2Z_TRY(kv_attach(fn, n, states, pos0, n_tokens, 0));   // (paged runstates: the last refusal)
+
+    // ---- the pass, on states[0]'s stream: the table, ONE chunk of R rows, the classifier over the n last rows, the draw
+    // and the hand-out, one copy back ----
+    L2Z_TRY(join_streams(b, n, states));
+    L2Z_TRY(kv_upload(n, states, st));
+    L2Z_TRY(mixed_upload_table(b, plan, tokens, n_tokens, pos0, states, sampled ? temperature : nullptr, top_p, coins));
+    MixedAttn ma = {b->d_mtab, b->part, b->seg_cap, std::max(plan.deepest_dec, 0) / kVerifySeg + 1, plan.n_dec,
+                    plan.n_prompt_rows, kv_page_floats(s0)};
+    RaggedChunk rg = {};
+    rg.seq = b->d_mtab->seq; rg.row_seq = b->d_mtab->row_seq; rg.row_pos = b->d_mtab->pos;
+    rg.tiles = b->d_mtab->tiles;
+    rg.n_seq = n; rg.n_tiles = plan.n_tiles;
+    rg.k = s0->rg_k; rg.v = s0->rg_v;
+    rg.page_floats = ma.page_floats;
+    rg.mixed = &ma;
+    rg.att_rows = b->d_mtab->prompt_rows; rg.n_att_rows = plan.n_prompt_rows;
+    L2Z_TRY(prefill_ragged_chunk(s0, w, b->h_mtab->tokens, R, rg));
+    L2Z_HIP(hipEventRecord(b->ev_upload, st));
+    // the classifier on the n LAST rows only: gathered and normed into a compact [n, dim] matrix, the product at n rows
+    L2Z_TRY(prefill_rows_logits(s0, w, n, b->logits, b->ld_logits, b->d_mtab->last_row));
+    MixedDraw d = {};
+    d.logits = b->logits; d.ld = b->ld_logits; d.vocab = config->vocab_size;
+    d.tab = b->d_mtab;
+    d.sampled = sampled;
+    d.next = b->d_next;
+    if (sampled) { d.scratch = b->smp; d.row_stride = sample_scratch_floats(config->vocab_size); }
+    L2Z_HIP(launch_mixed_draw_out(d, n, st));
+    L2Z_HIP(hipMemcpyAsync(b->h_next, b->d_next, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    L2Z_TRY(release_streams(b, n, states));
+    for (int j = 0; j < n; j++) {
+        logits_whole(states[j], pos0[j] + n_tokens[j]);
+        wide_verify_forget(states[j]);  // (states[0]'s matrix is this call's now)
+    }
+    L2Z_HIP(hipStreamSynchronize(st));
+    memcpy(out_next, b->h_next, (size_t)n * 4);
     return L2Z_OK;
 }

@@ -19,12 +19,7 @@ __global__ __launch_bounds__(kSbThreads) void wide_draw_advance(const WideDraw a
     const bool greedy = temperature == 0.0f;
     int next = sample_row(L, lg, a.vocab, temperature, greedy ? 0.0f : a.top_p[row], greedy ? 0.0f : a.coins[row],
                           greedy ? nullptr : a.scratch + (size_t)row * a.row_stride);
-    if (a.logits_out) {  // wide_logits_out's copy: float4 where both sides are 16-byte aligned
-        float *dst = a.tab->logits[row];
-        const int n4 = ((((uintptr_t)lg | (uintptr_t)dst) & 15) == 0) ? a.vocab >> 2 : 0;
-        for (int i = tid; i < n4; i += kSbThreads) ((v4f *)dst)[i] = ((const v4f *)lg)[i];
-        for (int i = 4 * n4 + tid; i < a.vocab; i += kSbThreads) dst[i] = lg[i];
-    }
+    if (a.logits_out) block_copy_row(a.tab->logits[row], lg, a.vocab, tid, kSbThreads);  // wide_logits_out's copy
     if (tid == 0) {
         // Unreachable by construction (sample_row returns an index it scanned or a candidate's id); kept, as
         // sample_step_kernel keeps its own, so that no id can ever address past the embedding table

@@ -82,11 +82,7 @@ __global__ __launch_bounds__(1024) void wide_verify_accept(const WideVerdict a)
         a.accepted[j] = acc;
     }
     __syncthreads();
-    const float *src = a.logits + (size_t)(first + s_a) * a.ld;
-    float *dst = a.tab->logits[j];
-    const int n4 = ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0) ? a.vocab >> 2 : 0;
-    for (int i = tid; i < n4; i += 1024) ((v4f *)dst)[i] = ((const v4f *)src)[i];
-    for (int i = 4 * n4 + tid; i < a.vocab; i += 1024) dst[i] = src[i];
+    block_copy_row(a.tab->logits[j], a.logits + (size_t)(first + s_a) * a.ld, a.vocab, tid, 1024);
 }
 
 }  // namespace
