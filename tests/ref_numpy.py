@@ -11,8 +11,11 @@ import numpy as np
 
 
 class NumpyModel:
-    def __init__(self, ck, cfg, blob, shared):
+    def __init__(self, ck, cfg, blob, shared, probe=None):
+        """probe: None, or a callable probe(layer, head, pos, spread, weights) that sees every softmax of the pass: the
+        spread max - min of its scores and the weights it produced (a view: copy what is kept)"""
         self.c = cfg
+        self.probe = probe
         self.w = {k: v.astype(np.float64) for k, v in ck.carve(cfg, blob, shared).items()}
         L, S, kvd = cfg.n_layers, cfg.seq_len, cfg.kv_dim
         self.kc = np.zeros((L, S, kvd))
@@ -46,8 +49,11 @@ class NumpyModel:
                 K = self.kc[l, : pos + 1, kh : kh + hs]
                 V = self.vc[l, : pos + 1, kh : kh + hs]
                 att = (K @ q[h * hs : (h + 1) * hs]) / np.sqrt(hs)
+                spread = att.max() - att.min()
                 att = np.exp(att - att.max())
                 att /= att.sum()
+                if self.probe is not None:
+                    self.probe(l, h, pos, float(spread), att)
                 out[h * hs : (h + 1) * hs] = att @ V
             x = x + w["wo"][l] @ out
             xb = self.rmsnorm(x, w["rms_ffn_weight"][l])
