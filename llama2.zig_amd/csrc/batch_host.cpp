@@ -188,6 +188,46 @@ int check_coins(const char *fn, const float *coins, int first, int count, int st
     return L2Z_OK;
 }
 
+int check_ragged_call(const RaggedCall &c, RaggedTotals *t)
+{
+    const char *fn = c.fn;
+    L2Z_TRY(no_device_check());
+    L2Z_CHECK(c.tokens != nullptr && c.pos0 != nullptr && c.config != nullptr && c.w != nullptr, L2Z_ERR_INVALID, "%s: null argument", fn);
+    L2Z_TRY(check_states(fn, c.n, c.states, c.config, c.max_seq));
+    L2Z_TRY(kv_check_kind(fn, c.n, c.states));
+    auto rows_of = [&c](int j) { return c.n_tokens != nullptr ? c.n_tokens[j] : 1; };
+    long long rows = 0;   // (no sum of n counts overflows it)
+    *t = {};
+    for (int j = 0; j < c.n; j++) {
+        L2Z_CHECK(rows_of(j) >= 1, L2Z_ERR_INVALID, "%s: n_tokens[%d] = %d (at least 1)", fn, j, rows_of(j));
+        L2Z_CHECK(c.max_seq_rows == 0 || rows_of(j) <= c.max_seq_rows, L2Z_ERR_INVALID, "%s: n_tokens[%d] = %d above %d", fn, j,
+                  rows_of(j), c.max_seq_rows);
+        rows += rows_of(j);
+        L2Z_CHECK(c.max_rows == 0 || rows <= c.max_rows, L2Z_ERR_INVALID, "%s: more than %d rows in all", fn, c.max_rows);
+        t->longest = std::max(t->longest, rows_of(j));
+    }
+    for (int j = 0; j < c.n; j++) L2Z_TRY(check_pair(c.config, c.states[j], c.w, true));
+    L2Z_TRY(prefill_check(c.config, c.states[0]));
+    if (c.temperature != nullptr) {   // l2z_sample_batch's rules for every sequence; a greedy one's coins are not read
+        L2Z_CHECK(c.top_p != nullptr, L2Z_ERR_INVALID, "%s: top_p is NULL beside a temperature array", fn);
+        for (int j = 0, r = 0; j < c.n; r += rows_of(j), j++) {
+            L2Z_TRY(check_draw(fn, j, c.temperature[j], c.top_p[j], c.coins));
+            if (c.temperature[j] == 0.0f) continue;
+            t->sampled = true;
+            L2Z_TRY(c.coins_per_step ? check_coins(fn, c.coins, j, c.n_steps, c.n) : check_coins(fn, c.coins, r, rows_of(j)));
+        }
+    }
+    for (int j = 0, r = 0; j < c.n; r += rows_of(j), j++) {   // (a sequence that passed fits the cache: r cannot overflow)
+        char where[32];
+        snprintf(where, sizeof where, "sequence %d: ", j);
+        L2Z_TRY(check_positions(fn, where, "positions", c.pos0[j], rows_of(j) + c.n_steps - 1, c.config->seq_len));
+        L2Z_TRY(check_tokens(fn, where, c.tokens + r, rows_of(j), c.config->vocab_size));
+        t->deepest = std::max(t->deepest, c.pos0[j] + rows_of(j) - 1);
+    }
+    t->R = (int)rows;
+    return L2Z_OK;
+}
+
 int upload_table(BatchScratch *b, const BatchTable &t, hipStream_t st, const void *behind, size_t behind_bytes)
 {
     L2Z_HIP(hipEventSynchronize(b->ev_upload));

@@ -1,7 +1,8 @@
 // batch_host.h -- what the host files of a call that names several runstates, or draws tokens, share (batch_host.cpp: the
 // batched step and what stands around it; verify_host.cpp: the verify family; wide_host.cpp: the wide step and its run;
 // prefill_batch_host.cpp, prefill_host.cpp, forward.cpp): the rules for the runstates and for the arguments of a draw, the
-// stream hand-overs, the scratch allocation and the batched step itself.
+// front of a call of the ragged family made of them (check_ragged_call), the stream hand-overs, the scratch allocation and
+// the batched step itself.
 #pragma once
 #include <initializer_list>
 
@@ -65,6 +66,37 @@ int check_draw(const char *fn, int seq, float temperature, float top_p, const fl
 // ... and for the `count` coins a sampled row reads, `stride` apart from coins[first] on
 int check_coins(const char *fn, const float *coins, int first, int count, int stride = 1);
 
+// A call of the ragged family (l2z_prefill_batch, l2z_transformer_wide, l2z_wide_run, l2z_verify_wide, l2z_step_mixed) as its
+// arguments describe it: n sequences, one runstate each; sequence j brings n_tokens[j] rows (n_tokens null: one) at
+// consecutive positions from pos0[j] on, the rows of all sequences behind one another in tokens; n_steps: the positions
+// a sequence takes from its last row on (1; l2z_wide_run: its steps).
+struct RaggedCall {
+    const char *fn;          // the entry point a message names
+    int n;
+    const int32_t *tokens, *n_tokens, *pos0;
+    int n_steps;
+    // the draws: temperature null, none; else per sequence, and a sampled sequence's coins one per row (coins[row]), or --
+    // coins_per_step -- one per step (coins[k * n + j])
+    const float *temperature, *top_p, *coins;
+    bool coins_per_step;
+    const l2z_config *config;
+    l2z_runstate *const *states;
+    const l2z_weights *w;
+    // the entry's limits: sequences, rows in all, rows of one sequence (0: as many as the cache holds)
+    int max_seq, max_rows, max_seq_rows;
+};
+struct RaggedTotals {
+    int R;          // rows in all
+    int longest;    // rows of the longest sequence
+    int deepest;    // the deepest position of a row
+    bool sampled;   // some sequence draws
+};
+// The front of such a call; a refusal enqueues nothing and changes no state.  In this order: no device, null arguments, the
+// runstates (check_states), one kind of cache (kv_check_kind), the row counts, every runstate against config and w
+// (check_pair), states[0] on the prompt pass (prefill_check), the draws and their coins, then positions and tokens sequence
+// by sequence.
+int check_ragged_call(const RaggedCall &c, RaggedTotals *t);
+
 // the pass on states[0]'s stream waits for everything already queued on every runstate's stream ... (b: a scratch with
 // an event per runstate, ev_in[], and ev_done)
 template <class Scratch> int join_streams(Scratch *b, int n, l2z_runstate *const *states)
@@ -95,19 +127,6 @@ inline void logits_whole(l2z_runstate *s, int next_pos)
 // the table of this call, and behind_bytes of what sits behind it, -> the device: one copy from the pinned buffer
 // (rewritten only once the last copy is done)
 int upload_table(BatchScratch *b, const BatchTable &t, hipStream_t st, const void *behind = nullptr, size_t behind_bytes = 0);
-
-// A reference to a caller's callable (Args...) -> L2Z code, alive for the call it is passed to
-template <class Sig> class FnRef;
-template <class... Args> class FnRef<int(Args...)> {
-  public:
-    template <class F>
-    FnRef(const F &f) : f_(&f), call_([](const void *p, Args... args) -> int { return (*(const F *)p)(args...); }) {}
-    int operator()(Args... args) const { return call_(f_, args...); }
-
-  private:
-    const void *f_;
-    int (*call_)(const void *, Args...);
-};
 
 // A layer's attention as batch_step sees it: (layer_off) enqueues the launches that turn b->q into b->att for the layer
 // whose caches start layer_off floats into each cache.

@@ -59,6 +59,19 @@ void set_error(const char *fmt, ...);
         if (_s != L2Z_OK) return _s; \
     } while (0)
 
+// A reference to a caller's callable (Args...) -> R, alive for the call it is passed to
+template <class Sig> class FnRef;
+template <class R, class... Args> class FnRef<R(Args...)> {
+  public:
+    template <class F>
+    FnRef(const F &f) : f_(&f), call_([](const void *p, Args... args) -> R { return (*(const F *)p)(args...); }) {}
+    R operator()(Args... args) const { return call_(f_, args...); }
+
+  private:
+    const void *f_;
+    R (*call_)(const void *, Args...);
+};
+
 // ---------------------------------------------------------------------------
 // Kernel argument blocks (passed by value; all pointers are device pointers)
 // ---------------------------------------------------------------------------
@@ -320,8 +333,6 @@ hipError_t launch_prefill_attention(const float *q, int ldq, const float *kcache
                                     bool *planes_written = nullptr);  // ... if the form that ran writes them (the flash form does)
 // ---- prefill_ragged.hip: a chunk whose rows belong to SEVERAL sequences (l2z_prefill_batch; prefill_batch_host.cpp) ----
 constexpr int kRaggedMaxSeq = 16;   // L2Z_BATCH_MAX
-struct WideAttn;                    // wide_decode.h
-struct MixedAttn;                   // mixed_step.h
 struct RaggedSeq {     // one sequence's rows of a chunk
     float *kc, *vc;    // its runstate's key / value caches (layer 0): [layer][kv head][seq_len][head_size]
     int row0, rows;    // its first row in the chunk, how many
@@ -340,24 +351,39 @@ __device__ __forceinline__ int kv_page_id(const int32_t *pages, int i)
 {
     return ((const __attribute__((address_space(4))) int32_t *)pages)[i];
 }
+// What every attention launcher of the ragged pass is told about a layer: rows of q [P, ldq] (RoPE applied) into out
+// [P, ldo]; layer_off / kv_head_stride: the layer's and a kv head's place in a cache (paged: in a PAGE); x3 != null: out's
+// planes of bf16 terms too (x3[row][3][kp]), where the form that runs writes them (it says so in *planes_written).
+struct RaggedLayer {
+    const float *q;
+    int ldq;
+    float *out;
+    int ldo;
+    int P, n_heads, head_size, kv_mul, seq_len;
+    size_t layer_off, kv_head_stride;
+    hipStream_t st;
+    void *x3;
+    int kp;
+};
+// A chunk's attention as the layer loop sees it (prefill_host.cpp prefill_stage): the owner of the chunk's table binds its
+// own launcher and that launcher's table to it
+using RaggedAttention = FnRef<hipError_t(const RaggedLayer &, bool *planes_written)>;
 // The table of one chunk (device pointers; built on the host and uploaded with the tokens).  tiles: the flash attention's
 // blocks -- .x the sequence slot, .y the first of its (up to 64) queries as a row of that sequence's segment --, the
-// ones with the most key rows first.
+// ones with the most key rows first.  The layer loop knows no caller: whoever owns the table says how many sequence slots
+// it has and, where the rows are not plain prompt rows, brings the attention.
 struct RaggedChunk {
     const RaggedSeq *seq;   // [n_seq]
     const int *row_seq;     // [P] slot of each row
     const int *row_pos;     // [P] position of each row
     const int2 *tiles;      // [n_tiles]
     int n_seq, n_tiles;
+    int seq_max;            // sequence slots the table has (kRaggedMaxSeq, kWideMax, kMixedSeqMax): launch_ragged_attention's bound on n_seq
     float *k, *v;           // scratch: the chunk's key / value rows [P, kv_dim] between the product and the scatter
     size_t page_floats;     // != 0: every sequence of the table is paged (RaggedSeq::pages), a page is this many floats of the
                             // key pool and as many of the value pool; the launchers' layer_off / kv_head_stride are a PAGE's
-    const WideAttn *wide;   // != null (l2z_transformer_wide): every row is a sequence of its own at one position -- the
-                            // attention is launch_wide_attention (wide_decode.h) on this table; tiles and n_tiles are not read
-                            // (wide->verify_m != 0, l2z_verify_wide: sequences of several rows, launch_wide_verify_attention)
-    const MixedAttn *mixed; // != null (l2z_step_mixed): sequences of one row and of several in one chunk -- the attention is
-                            // launch_mixed_attention (mixed_step.h); n_seq may reach kMixedSeqMax, tiles name the sequences of
-                            // several rows only
+    const RaggedAttention *attention;   // null: launch_ragged_attention on this table (l2z_prefill_batch); else the layer's
+                            // attention launches, alive for the pass (the wide step's, the wide verify's, the mixed chunk's)
     const int *att_rows;    // != null: the n_att_rows rows launch_ragged_attention's block-per-(head, row) form serves (the
     int n_att_rows;         // flash form's are the tile list's); null: all P
 };
@@ -367,10 +393,8 @@ hipError_t launch_ragged_rope_scatter(float *q, int ldq, const RaggedChunk &rg, 
                                       const float2 *rope, size_t layer_off, size_t kv_head_stride, hipStream_t st);
 // causal attention of every row over rows 0 .. row_pos[r] of its OWN sequence's cache, one launch: the MFMA flash form at
 // head sizes 64 and 128 (one block per (tile, head)), else one block per (head, row) with the decode kernel's arithmetic.
-// x3 / kp / planes_written: as launch_prefill_attention.  A function of the shape and the table only.
-hipError_t launch_ragged_attention(const float *q, int ldq, float *out, int ldo, const RaggedChunk &rg, int P, int n_heads,
-                                   int head_size, size_t layer_off, size_t kv_head_stride, int kv_mul, int seq_len,
-                                   hipStream_t st, void *x3 = nullptr, int kp = 0, bool *planes_written = nullptr);
+// A function of the shape and the table only.
+hipError_t launch_ragged_attention(const RaggedLayer &L, const RaggedChunk &rg, bool *planes_written = nullptr);
 // ---- prefill_panel.hip: chunks of <= 32 tokens of matrices that stream from HBM (K ranges with a resident X panel) ----
 enum PanelEpi { PANEL_STORE = 0, PANEL_RESID = 1, PANEL_SWIGLU = 2, PANEL_QKV = 3 };
 struct PanelProduct {

@@ -226,7 +226,8 @@ int prefill_tokens(l2z_runstate *s, const l2z_weights *w, const int32_t *tokens,
 int prefill_scratch(l2z_runstate *s, int need);
 int prefill_ragged_chunk(l2z_runstate *s, const l2z_weights *w, const int32_t *tokens, int P, const RaggedChunk &rg);
 int prefill_last_logits(l2z_runstate *s, const l2z_weights *w);
-// ... and with l2z_transformer_wide (wide_host.cpp): the classifier over all P rows of the chunk just run -> out [P, ldo]
+// ... and with the wide and mixed calls (wide_host.cpp): the classifier over P rows of the chunk just run -- all of it, or
+// the rows a device list names -- -> out [P, ldo]
 int prefill_rows_logits(l2z_runstate *s, const l2z_weights *w, int P, float *out, int ldo, const int *rows = nullptr);
 // prefill_batch_host.cpp: s's rg_k / rg_v (and l2z_prefill_batch's own table) for chunks of up to `need` rows
 int ragged_alloc(l2z_runstate *s, int need);

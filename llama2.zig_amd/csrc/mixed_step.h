@@ -1,6 +1,7 @@
-// mixed_step.h -- what l2z_step_mixed adds to the ragged prompt pass (mixed_step.hip; host side wide_host.cpp,
-// prefill_host.cpp; the layout: mixed_plan.h): the device table of a chunk that holds sequences of ONE row (decode steps)
-// and sequences of several rows (prompt chunks), the attention dispatch for such a chunk, and the last launch of the call:
+// mixed_step.h -- what l2z_step_mixed adds to the ragged prompt pass (mixed_step.hip; host side wide_host.cpp; the layout:
+// mixed_plan.h): the device table of a chunk that holds sequences of ONE row (decode steps) and sequences of several rows
+// (prompt chunks), the attention dispatch for such a chunk -- which wide_host.cpp hands to the pass as the chunk's
+// attention (RaggedChunk::attention); the layer loop itself does not know this file -- and the last launch of the call:
 // every sequence's draw from its LAST row's logits and the hand-out of that row to the runstate.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -38,18 +39,17 @@ struct MixedAttn {
     size_t page_floats;      // RaggedChunk::page_floats
 };
 
-// The attention of a mixed chunk, rows of q [P, ldq] (RoPE applied) into out [P, ldo]; rg.mixed != null.
+// The attention of a mixed chunk, rows of q [P, ldq] (RoPE applied) into out [P, ldo]: the layer as the ragged pass
+// describes it (RaggedLayer), this call's MixedAttn, and the chunk's table as the pass holds it.
 //   the sequences of several rows: launch_ragged_attention (prefill_ragged.hip) over rg.tiles (head sizes 64 / 128) or over
 //     the rows rg.att_rows names (every other head size);
 //   the sequences of one row: launch_wide_attention_rows (wide_decode.h) with tab->dec as the list -- block (kv head x part,
 //     segment, ordinal) takes its row and its sequence slot from tab->dec[ordinal], reads the segment's K / V rows of that kv
 //     head ONCE for its query heads (one page per block when paged) and leaves the partials at the ORDINAL; the combine,
 //     block (head, ordinal), folds them in segment order into the row.
-// No block is launched for a row of the other class.  x3 / kp / planes_written as launch_ragged_attention: the planes of
+// No block is launched for a row of the other class.  L.x3 / L.kp / planes_written as launch_ragged_attention: the planes of
 // bf16 terms of out are written by BOTH classes' launches (the flash form and the combine) or by neither.
-hipError_t launch_mixed_attention(const float *q, int ldq, float *out, int ldo, const RaggedChunk &rg, int P, int n_heads,
-                                  int head_size, size_t layer_off, size_t kv_head_stride, int kv_mul, int seq_len,
-                                  hipStream_t st, void *x3 = nullptr, int kp = 0, bool *planes_written = nullptr);
+hipError_t launch_mixed_attention(const RaggedLayer &L, const MixedAttn &m, const RaggedChunk &rg, bool *planes_written = nullptr);
 
 // The last launch, one block of 1024 threads per SEQUENCE: next[j] = the token the sampler's row body (sample_device.h)
 // draws from row j of logits [n, ld] with tab->temperature[j], top_p[j], coins[j] -- the argmax by argmax_rule.h at

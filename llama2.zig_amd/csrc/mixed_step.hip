@@ -38,28 +38,26 @@ __global__ __launch_bounds__(kSbThreads) void mixed_draw_out(const MixedDraw a)
 
 }  // namespace
 
-hipError_t launch_mixed_attention(const float *q, int ldq, float *out, int ldo, const RaggedChunk &rg, int P, int n_heads,
-                                  int head_size, size_t layer_off, size_t kv_head_stride, int kv_mul, int seq_len,
-                                  hipStream_t st, void *x3, int kp, bool *planes_written)
+hipError_t launch_mixed_attention(const RaggedLayer &L, const MixedAttn &m, const RaggedChunk &rg, bool *planes_written)
 {
     if (planes_written) *planes_written = false;
-    if (rg.mixed == nullptr) return hipErrorInvalidValue;
-    const MixedAttn &m = *rg.mixed;
-    if (P < 1 || P > kMixedRowsMax || m.n_dec < 0 || m.n_dec > kMixedSeqMax || m.n_prompt_rows < 0 || m.n_dec + m.n_prompt_rows != P ||
-        head_size < 4 || head_size > 256 || (head_size & 3) || n_heads < 1 || kv_mul < 1 || n_heads % kv_mul != 0 ||
-        m.tab == nullptr || (ldq & 3) || (ldo & 3) || (((uintptr_t)q | (uintptr_t)out) & 15) || (layer_off & 3) ||
-        (kv_head_stride & 3) || (m.page_floats & 3))
+    const int head_size = L.head_size;
+    if (L.P < 1 || L.P > kMixedRowsMax || m.n_dec < 0 || m.n_dec > kMixedSeqMax || m.n_prompt_rows < 0 || m.n_dec + m.n_prompt_rows != L.P ||
+        head_size < 4 || head_size > 256 || (head_size & 3) || L.n_heads < 1 || L.kv_mul < 1 || L.n_heads % L.kv_mul != 0 ||
+        m.tab == nullptr || (L.ldq & 3) || (L.ldo & 3) || (((uintptr_t)L.q | (uintptr_t)L.out) & 15) || (L.layer_off & 3) ||
+        (L.kv_head_stride & 3) || (m.page_floats & 3))
         return hipErrorInvalidValue;
     if (m.n_dec > 0 && (m.part == nullptr || (((uintptr_t)m.part) & 15) || m.n_seg < 1 || m.n_seg > m.seg_cap))
         return hipErrorInvalidValue;
     // The planes of out: the flash form writes its rows' (launch_ragged_attention), the block-per-(head, row) form does not --
     // so with rows of several-row sequences at another head size NEITHER class writes them and the chunk splits out itself.
     const bool flash = head_size == 64 || head_size == 128;
-    const bool planes = x3 != nullptr && (kp & 3) == 0 && (((uintptr_t)x3) & 7) == 0 && (flash || m.n_prompt_rows == 0);
+    const bool planes = L.x3 != nullptr && (L.kp & 3) == 0 && (((uintptr_t)L.x3) & 7) == 0 && (flash || m.n_prompt_rows == 0);
+    RaggedLayer each = L;   // both classes' launches: with the planes, or without
+    if (!planes) each.x3 = nullptr;
     if (m.n_prompt_rows > 0) {
         bool pw = false;
-        const hipError_t e = launch_ragged_attention(q, ldq, out, ldo, rg, P, n_heads, head_size, layer_off, kv_head_stride, kv_mul,
-                                                     seq_len, st, planes ? x3 : nullptr, kp, &pw);
+        const hipError_t e = launch_ragged_attention(each, rg, &pw);
         if (e != hipSuccess) return e;
         if (pw != planes) return hipErrorInvalidValue;   // (never a mixture)
     }
@@ -68,8 +66,7 @@ hipError_t launch_mixed_attention(const float *q, int ldq, float *out, int ldo, 
         wr.pos = m.tab->pos; wr.seq = m.tab->seq; wr.list = m.tab->dec;
         wr.n = m.n_dec; wr.part = m.part; wr.seg_cap = m.seg_cap; wr.n_seg = m.n_seg; wr.page_floats = m.page_floats;
         bool pw = false;
-        const hipError_t e = launch_wide_attention_rows(q, ldq, out, ldo, wr, n_heads, head_size, layer_off, kv_head_stride, kv_mul,
-                                                        st, planes ? x3 : nullptr, kp, &pw);
+        const hipError_t e = launch_wide_attention_rows(each, wr, &pw);
         if (e != hipSuccess) return e;
         if (pw != planes) return hipErrorInvalidValue;
     }

@@ -42,26 +42,12 @@ extern "C" int l2z_prefill_batch(int n, const int32_t *tokens, const int32_t *n_
 {
     // ---- checks: a refusal enqueues nothing and changes no state ----
     L2Z_TRY(no_device_check());
-    L2Z_CHECK(tokens != nullptr && n_tokens != nullptr && pos0 != nullptr && config != nullptr && w != nullptr, L2Z_ERR_INVALID,
-              "l2z_prefill_batch: null argument");
-    L2Z_TRY(check_states("l2z_prefill_batch", n, states, config));
-    L2Z_TRY(kv_check_kind("l2z_prefill_batch", n, states));
-    long long total_ll = 0;
-    for (int j = 0; j < n; j++) {
-        L2Z_TRY(check_pair(config, states[j], w, true));
-        L2Z_CHECK(n_tokens[j] >= 1, L2Z_ERR_INVALID, "l2z_prefill_batch: n_tokens[%d] = %d (at least 1)", j, n_tokens[j]);
-        total_ll += n_tokens[j];
-    }
-    L2Z_TRY(prefill_check(config, states[0]));
-    for (int j = 0, g = 0; j < n; g += n_tokens[j], j++) {
-        L2Z_CHECK(pos0[j] >= 0 && (long long)pos0[j] + n_tokens[j] <= config->seq_len, L2Z_ERR_STATE,
-                  "l2z_prefill_batch: sequence %d: positions %d..%lld outside [0,%d)", j, pos0[j],
-                  (long long)pos0[j] + n_tokens[j] - 1, config->seq_len);
-        for (int i = 0; i < n_tokens[j]; i++)   // (n_tokens[j] <= seq_len from here on: g cannot overflow)
-            L2Z_CHECK(tokens[g + i] >= 0 && tokens[g + i] < config->vocab_size, L2Z_ERR_STATE,
-                      "l2z_prefill_batch: sequence %d: tokens[%d] = %d out of vocabulary", j, i, tokens[g + i]);
-    }
-    const int total = (int)total_ll;
+    L2Z_CHECK(n_tokens != nullptr, L2Z_ERR_INVALID, "l2z_prefill_batch: null argument");
+    const RaggedCall call = {"l2z_prefill_batch", n, tokens, n_tokens, pos0, 1, nullptr, nullptr, nullptr, false,
+                             config, states, w, kRaggedMaxSeq, 0, 0};
+    RaggedTotals t;
+    L2Z_TRY(check_ragged_call(call, &t));
+    const int total = t.R;
     l2z_runstate *s0 = states[0];
     hipStream_t st = s0->stream;
     const l2z_config &c = *config;
@@ -118,6 +104,7 @@ extern "C" int l2z_prefill_batch(int n, const int32_t *tokens, const int32_t *n_
         rg.row_pos = (const int *)(d_tab + ((unsigned char *)h_row_pos - h_tab.data()));
         rg.tiles = (const int2 *)(d_tab + ((unsigned char *)h_tiles - h_tab.data()));
         rg.n_seq = n_seq; rg.n_tiles = (int)tiles.size();
+        rg.seq_max = kRaggedMaxSeq;
         rg.k = s0->rg_k; rg.v = s0->rg_v;
         rg.page_floats = kv_page_floats(s0);
         L2Z_HIP(hipMemcpyAsync(d_tab, h_tab.data(), h_tab.size(), hipMemcpyHostToDevice, st));

@@ -1,4 +1,9 @@
 // prefill_host.cpp -- host side of the batched prompt prefill (kernels: prefill_gemm.hip, prefill_skinny.hip, prefill_attention.hip).
+// The layer loop (prefill_stage) serves l2z_prefill's chunks and, handed a RaggedChunk, chunks whose rows belong to several
+// sequences (prefill_ragged_chunk: l2z_prefill_batch and the wide and mixed calls of wide_host.cpp).  It knows none of those
+// callers: the chunk's table says how its rows lie, and its owner brings the layers' attention as a callable of the
+// RaggedLayer built here once per layer (RaggedChunk::attention; none: the prompt form, launch_ragged_attention).
+// The classifier over a chunk's rows is one slab loop (classifier_slabs) for l2z_score and for those calls.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -7,9 +12,7 @@
 
 #include "batch_host.h"
 #include "l2z_state.h"
-#include "mixed_step.h"
 #include "prefill_common.h"
-#include "wide_decode.h"
 
 using namespace l2z;
 
@@ -203,8 +206,8 @@ int launch_w13(const Chunk &c, GemmArgs a, GemmLaunch &l)
 // The launches of stage k of layer l.  One rank: straight into the destination matrix.  Sharded: this
 // rank's [P, n_loc] block, contiguous, at pf_stage + rank * P * n_loc; the exchange and the unpack
 // into the destination follow (comm_bulk_allgather, or the emulated-rank driver's copies).
-// rg != null (l2z_prefill_batch; l2z_transformer_wide with rg->wide set): the rows belong to several sequences, which only the
-// q | k | v epilogue and the attention see (below); pos0 is not read.
+// rg != null (the ragged pass: l2z_prefill_batch, and the wide and mixed calls of wide_host.cpp): the rows belong to several
+// sequences, which only the q | k | v epilogue and the attention see (below); pos0 is not read.
 int prefill_stage(l2z_runstate *s, const l2z_weights *w, int l, int k, int P, int pos0, const RaggedChunk *rg = nullptr)
 {
     const l2z_config &c = s->cfg;
@@ -296,7 +299,8 @@ int prefill_stage(l2z_runstate *s, const l2z_weights *w, int l, int k, int P, in
         // Rows of several sequences: the three products with the plain-store epilogue into scratch (the forms of the
         // whole model's q | k | v launch at this chunk length, as where the single-sequence pass launches them apart),
         // then ONE launch that rotates q and k at each row's own position and stores k / v into each row's own caches,
-        // then ONE attention launch in which a row sees its own sequence's cache only (prefill_ragged.hip).
+        // then the chunk's attention, in which a row sees its own sequence's cache only: the one its owner brought
+        // (RaggedChunk::attention), else the prompt form's ONE launch (prefill_ragged.hip).
         L2Z_CHECK(!sharded, L2Z_ERR_INVALID, "batched prefill: rows of several sequences on a shard");
         // (paged sequences: a layer and a kv head of a PAGE, l2z_internal.h RaggedSeq::pages)
         const size_t kvh_stride = rg->page_floats ? (size_t)kKvPage * hs : (size_t)c.seq_len * hs;
@@ -315,19 +319,9 @@ int prefill_stage(l2z_runstate *s, const l2z_weights *w, int l, int k, int P, in
         L2Z_HIP(launch_ragged_rope_scatter(s->pf_q, dim, *rg, P, dim, kvd, hs, s->rope, layer_off, kvh_stride, st));
         bool att_planes = false;
         const bool want = planes_for(dim, dim, sk_wo);
-        if (rg->mixed != nullptr)   // l2z_step_mixed: prompt attention for the sequences of several rows, decode attention for the rest (mixed_step.hip)
-            L2Z_HIP(launch_mixed_attention(s->pf_q, dim, out, ldo, *rg, P, c.n_heads, hs, layer_off, kvh_stride,
-                                           c.n_heads / c.n_kv_heads, c.seq_len, st, want ? ws->x3 : nullptr, dim, &att_planes));
-        else if (rg->wide != nullptr && rg->wide->verify_m != 0)   // l2z_verify_wide: a sequence's rows are a block's slots (wide_verify.hip)
-            L2Z_HIP(launch_wide_verify_attention(s->pf_q, dim, out, ldo, *rg->wide, rg->n_seq, P, c.n_heads, hs, layer_off,
-                                                 kvh_stride, c.n_heads / c.n_kv_heads, st, want ? ws->x3 : nullptr, dim,
-                                                 &att_planes));
-        else if (rg->wide != nullptr)   // one row per sequence: the position-split decode attention (wide_decode.hip)
-            L2Z_HIP(launch_wide_attention(s->pf_q, dim, out, ldo, *rg->wide, P, c.n_heads, hs, layer_off, kvh_stride,
-                                          c.n_heads / c.n_kv_heads, st, want ? ws->x3 : nullptr, dim, &att_planes));
-        else
-            L2Z_HIP(launch_ragged_attention(s->pf_q, dim, out, ldo, *rg, P, c.n_heads, hs, layer_off, kvh_stride,
-                                            c.n_heads / c.n_kv_heads, c.seq_len, st, want ? ws->x3 : nullptr, dim, &att_planes));
+        const RaggedLayer L = {s->pf_q, dim, out, ldo, P, c.n_heads, hs, c.n_heads / c.n_kv_heads, c.seq_len,
+                               layer_off, kvh_stride, st, want ? ws->x3 : nullptr, dim};
+        L2Z_HIP(rg->attention != nullptr ? (*rg->attention)(L, &att_planes) : launch_ragged_attention(L, *rg, &att_planes));
         s->pf_planes_att = att_planes ? PLANES_READY : PLANES_SPLIT;
     } else if (k == PF_ATT) {
         const QkvProduct qp = {s->pf_xn, ldxn, dim, w->wq + (size_t)l * sh.dim_loc * dim, w->wk + (size_t)l * kvd * dim,
@@ -559,17 +553,43 @@ int slab_cols_that_fit(const l2z_runstate *s, int P, int sk, int kp, int cols)
     return cols;
 }
 
-int score_chunk(l2z_runstate *s, const l2z_weights *w, const ScoreCall *sc, int done, int P)
+// Steps 1 and 2 above, for l2z_score and for the wide and mixed calls (prefill_rows_logits): the norm of all P rows -- rows !=
+// null (a device list): of rows[0 .. P) of the chunk, gathered -- into the first P rows of pf_xn, then the slabs, at most
+// max_cols vocabulary columns wide (a multiple of kScoreSeg) and as few as the split-K workspace allows.  The first slab's
+// launch cuts the rows into their planes of bf16 terms where the product runs on those cores; they stand for the rest.  A
+// slab goes to dst [P, ldd]: side_by_side at its own columns of a whole [P, vocab] matrix, else at column 0 of a buffer one
+// slab wide, which `each` (col0, n) -- called once the product is enqueued -- uses up before the next.
+using SlabDone = FnRef<int(int, int)>;
+int classifier_slabs(l2z_runstate *s, const l2z_weights *w, int P, const int *rows, float *dst, int ldd, bool side_by_side,
+                     int max_cols, const SlabDone *each = nullptr)
 {
     const l2z_config &c = s->cfg;
     hipStream_t st = s->stream;
-    const int dim = c.dim, V = c.vocab_size, ldxn = s->pf_ld_xn, nseg = score_nseg(c);
-    L2Z_CHECK(s->sc_ws != nullptr && P <= s->sc_cap, L2Z_ERR_INVALID, "l2z_score: no workspace for a chunk of %d tokens", P);
-    L2Z_CHECK(!s->pf_pending.valid, L2Z_ERR_INVALID, "l2z_score: the last layer left its residual product's sums behind");
-    L2Z_HIP(launch_prefill_rmsnorm(s->pf_xn, ldxn, s->pf_x, w->rms_final, dim, P, st));   // :426, all rows
+    const int dim = c.dim, V = c.vocab_size, ldxn = s->pf_ld_xn;
+    L2Z_CHECK(!s->pf_pending.valid, L2Z_ERR_INVALID, "classifier over a chunk: the last layer left its residual product's sums behind");
+    L2Z_HIP(launch_prefill_rmsnorm(s->pf_xn, ldxn, s->pf_x, w->rms_final, dim, P, st, nullptr, 0, nullptr, rows));   // :426
     const int kp = (dim + 63) / 64 * 64;
     const int sk = prefill_split_k(V, P, kp, false);
-    const int cols = slab_cols_that_fit(s, P, sk, kp, s->sc_slab_n);
+    const int cols = slab_cols_that_fit(s, P, sk, kp, max_cols);
+    const Chunk ch = chunk_of(s, P, 0);
+    GemmLaunch gl = launch_of(ch, sk);
+    gl.n_launch_whole = V;
+    for (int col0 = 0; col0 < V; col0 += cols) {
+        const int n = std::min(cols, V - col0);
+        GemmArgs g = product(ch, s->pf_xn, ldxn, w->wcls + (size_t)col0 * dim, dim, n, dim);
+        g.out = side_by_side ? dst + col0 : dst; g.ldo = ldd;
+        L2Z_HIP(launch_prefill_gemm(GEMM_SINGLE, PG_STORE, g, gl, st));
+        gl.planes_ready = PLANES_READY;
+        if (each != nullptr) L2Z_TRY((*each)(col0, n));
+    }
+    return L2Z_OK;
+}
+
+int score_chunk(l2z_runstate *s, const l2z_weights *w, const ScoreCall *sc, int done, int P)
+{
+    hipStream_t st = s->stream;
+    const int nseg = score_nseg(s->cfg);
+    L2Z_CHECK(s->sc_ws != nullptr && P <= s->sc_cap, L2Z_ERR_INVALID, "l2z_score: no workspace for a chunk of %d tokens", P);
     float *slab = (float *)s->sc_ws;
     ScoreArgs a = {};
     a.slab = slab; a.ld = s->sc_slab_n; a.P = P; a.nseg = nseg;
@@ -578,19 +598,13 @@ int score_chunk(l2z_runstate *s, const l2z_weights *w, const ScoreCall *sc, int 
     a.part_i = (int *)(a.part_s + (size_t)s->sc_cap * nseg);
     a.tgt = (float *)(a.part_i + (size_t)s->sc_cap * nseg);
     a.targets = sc->d_targets ? sc->d_targets + done : nullptr;
-    const Chunk ch = chunk_of(s, P, 0);
-    GemmLaunch gl = launch_of(ch, sk);
-    gl.n_launch_whole = V;
-    for (int col0 = 0; col0 < V; col0 += cols) {
-        const int n = std::min(cols, V - col0);
-        // (the first slab's launch cuts the rows into their planes of bf16 terms where the product runs on those cores; they stand for the rest)
-        GemmArgs g = product(ch, s->pf_xn, ldxn, w->wcls + (size_t)col0 * dim, dim, n, dim);
-        g.out = slab; g.ldo = a.ld;
-        L2Z_HIP(launch_prefill_gemm(GEMM_SINGLE, PG_STORE, g, gl, st));
-        gl.planes_ready = PLANES_READY;
+    const auto reduce = [&](int col0, int n) -> int {
         a.n = n; a.col0 = col0; a.seg0 = col0 / kScoreSeg;
         L2Z_HIP(launch_score_reduce(a, st));
-    }
+        return L2Z_OK;
+    };
+    const SlabDone each = reduce;
+    L2Z_TRY(classifier_slabs(s, w, P, nullptr, slab, a.ld, false, s->sc_slab_n, &each));
     a.out_logprob = sc->d_logprob ? sc->d_logprob + done : nullptr;
     a.out_top1 = sc->d_top1 ? sc->d_top1 + done : nullptr;
     L2Z_HIP(launch_score_finish(a, st));
@@ -600,31 +614,11 @@ int score_chunk(l2z_runstate *s, const l2z_weights *w, const ScoreCall *sc, int 
 
 namespace l2z {
 
-// l2z_transformer_wide: the logits of ALL P rows of the chunk the layers just finished, as score_chunk's step 1 and 2 --
-// final rmsnorm into pf_xn, then the classifier by launch_prefill_gemm(PG_STORE) with the whole vocabulary as
-// n_launch_whole -- into out [P, ldo], in as few vocabulary slabs as the split-K workspace allows (score_chunk's rule).
-// rows != null (l2z_step_mixed; a device list): the P rows are rows[0 .. P) of the chunk, gathered by the norm launch into the
-// first P rows of pf_xn -- the classifier runs at P rows, whatever the chunk held.
+// The wide and mixed calls (wide_host.cpp): the logits of P rows of the chunk the layers just finished -- all of it, or the
+// rows a device list names (l2z_step_mixed: the classifier runs at P rows, whatever the chunk held) -- into out [P, ldo].
 int prefill_rows_logits(l2z_runstate *s, const l2z_weights *w, int P, float *out, int ldo, const int *rows)
 {
-    const l2z_config &c = s->cfg;
-    hipStream_t st = s->stream;
-    const int dim = c.dim, V = c.vocab_size, ldxn = s->pf_ld_xn;
-    L2Z_CHECK(!s->pf_pending.valid, L2Z_ERR_INVALID, "l2z_transformer_wide: the last layer left its residual product's sums behind");
-    L2Z_HIP(launch_prefill_rmsnorm(s->pf_xn, ldxn, s->pf_x, w->rms_final, dim, P, st, nullptr, 0, nullptr, rows));   // :426: all P rows, or the P listed ones
-    const int kp = (dim + 63) / 64 * 64;
-    const int sk = prefill_split_k(V, P, kp, false);
-    const int cols = slab_cols_that_fit(s, P, sk, kp, score_nseg(c) * kScoreSeg);
-    const Chunk ch = chunk_of(s, P, 0);
-    GemmLaunch gl = launch_of(ch, sk);
-    gl.n_launch_whole = V;
-    for (int col0 = 0; col0 < V; col0 += cols) {
-        GemmArgs g = product(ch, s->pf_xn, ldxn, w->wcls + (size_t)col0 * dim, dim, std::min(cols, V - col0), dim);
-        g.out = out + col0; g.ldo = ldo;
-        L2Z_HIP(launch_prefill_gemm(GEMM_SINGLE, PG_STORE, g, gl, st));
-        gl.planes_ready = PLANES_READY;   // (the first slab's launch cut the rows into their planes)
-    }
-    return L2Z_OK;
+    return classifier_slabs(s, w, P, rows, out, ldo, true, score_nseg(s->cfg) * kScoreSeg);
 }
 
 // Row-sharded == unsharded bit for bit needs every rank to take the kernel -- the summation order -- the unsharded
@@ -768,11 +762,8 @@ extern "C" int l2z_prefill(const int32_t *tokens, int n_tokens, int pos0, const 
 {
     L2Z_TRY(check_pair(config, s, w));
     L2Z_CHECK(tokens != nullptr && n_tokens >= 1, L2Z_ERR_INVALID, "l2z_prefill: no tokens");
-    L2Z_CHECK(pos0 >= 0 && pos0 + n_tokens <= config->seq_len, L2Z_ERR_STATE,
-              "l2z_prefill: positions %d..%d outside [0,%d)", pos0, pos0 + n_tokens - 1, config->seq_len);
-    for (int i = 0; i < n_tokens; i++)
-        L2Z_CHECK(tokens[i] >= 0 && tokens[i] < config->vocab_size, L2Z_ERR_STATE,
-                  "l2z_prefill: tokens[%d] = %d out of vocabulary", i, tokens[i]);
+    L2Z_TRY(check_positions("l2z_prefill", "", "positions", pos0, n_tokens, config->seq_len));
+    L2Z_TRY(check_tokens("l2z_prefill", "", tokens, n_tokens, config->vocab_size));
     L2Z_TRY(prefill_check(config, s));
     L2Z_HIP(hipSetDevice(s->device));
     return prefill_pass(tokens, n_tokens, pos0, config, s, w, nullptr);
@@ -790,14 +781,11 @@ extern "C" int l2z_score(const int32_t *tokens, int n_tokens, int pos0, const in
     L2Z_CHECK(s->comm == nullptr && s->sh.world == 1, L2Z_ERR_INVALID,
               "l2z_score: sharded runstates are not supported (the vocabulary rows are sharded there)");
     L2Z_TRY(prefill_check(config, s));
-    L2Z_CHECK(pos0 >= 0 && pos0 + n_tokens <= config->seq_len, L2Z_ERR_STATE,
-              "l2z_score: positions %d..%d outside [0,%d)", pos0, pos0 + n_tokens - 1, config->seq_len);
-    for (int i = 0; i < n_tokens; i++) {
-        L2Z_CHECK(tokens[i] >= 0 && tokens[i] < config->vocab_size, L2Z_ERR_STATE,
-                  "l2z_score: tokens[%d] = %d out of vocabulary", i, tokens[i]);
-        L2Z_CHECK(targets == nullptr || (targets[i] >= -1 && targets[i] < config->vocab_size), L2Z_ERR_STATE,
+    L2Z_TRY(check_positions("l2z_score", "", "positions", pos0, n_tokens, config->seq_len));
+    L2Z_TRY(check_tokens("l2z_score", "", tokens, n_tokens, config->vocab_size));
+    for (int i = 0; targets != nullptr && i < n_tokens; i++)
+        L2Z_CHECK(targets[i] >= -1 && targets[i] < config->vocab_size, L2Z_ERR_STATE,
                   "l2z_score: targets[%d] = %d is neither -1 nor in the vocabulary", i, targets[i]);
-    }
     L2Z_HIP(hipSetDevice(s->device));
     int longest = 0;   // the plan's longest chunk sizes the workspace before anything is enqueued
     for (int done = 0; done < n_tokens;) {

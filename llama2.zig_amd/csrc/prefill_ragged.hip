@@ -4,7 +4,6 @@
 // the pass treats the rows of a chunk independently and is l2z_prefill's own.
 // A row's results depend on its own sequence's rows and caches and on the chunk's table -- never on what the other
 // sequences hold (no reduction here crosses a sequence, no block shares state between two).
-#include "mixed_plan.h"
 #include "prefill_common.h"
 
 namespace l2z {
@@ -323,21 +322,20 @@ hipError_t launch_ragged_rope_scatter(float *q, int ldq, const RaggedChunk &rg, 
     return hipGetLastError();
 }
 
-hipError_t launch_ragged_attention(const float *q, int ldq, float *out, int ldo, const RaggedChunk &rg, int P, int n_heads,
-                                   int head_size, size_t layer_off, size_t kv_head_stride, int kv_mul, int seq_len,
-                                   hipStream_t st, void *x3, int kp, bool *planes_written)
+hipError_t launch_ragged_attention(const RaggedLayer &L, const RaggedChunk &rg, bool *planes_written)
 {
+    const int P = L.P, head_size = L.head_size;
     if (planes_written) *planes_written = false;
-    if (P <= 0 || (head_size & 3) || head_size > 256 || rg.n_seq < 1 || rg.n_seq > (rg.mixed != nullptr ? kMixedSeqMax : kRaggedMaxSeq) ||
+    if (P <= 0 || (head_size & 3) || head_size > 256 || rg.n_seq < 1 || rg.n_seq > rg.seq_max ||
         (rg.att_rows != nullptr && (rg.n_att_rows < 1 || rg.n_att_rows > P)))
         return hipErrorInvalidValue;
     RaggedAttnArgs a = {};
-    a.q = q; a.out = out; a.seq = rg.seq; a.row_seq = rg.row_seq; a.row_pos = rg.row_pos; a.tiles = rg.tiles;
-    a.layer_off = layer_off; a.kv_head = kv_head_stride; a.ldq = ldq; a.ldo = ldo; a.kv_mul = kv_mul; a.seq_len = seq_len;
+    a.q = L.q; a.out = L.out; a.seq = rg.seq; a.row_seq = rg.row_seq; a.row_pos = rg.row_pos; a.tiles = rg.tiles;
+    a.layer_off = L.layer_off; a.kv_head = L.kv_head_stride; a.ldq = L.ldq; a.ldo = L.ldo; a.kv_mul = L.kv_mul; a.seq_len = L.seq_len;
     a.head_size = head_size; a.page_floats = rg.page_floats; a.rows = rg.att_rows;
     // (the caches come from hipMalloc and a layer / a kv head is a multiple of head_size floats: 16-byte aligned rows)
-    if ((head_size == 64 || head_size == 128) && (ldq % 4) == 0 && (ldo % 4) == 0 && rg.n_tiles > 0 &&
-        (((uintptr_t)q | (uintptr_t)out) & 15) == 0) {
+    if ((head_size == 64 || head_size == 128) && (L.ldq % 4) == 0 && (L.ldo % 4) == 0 && rg.n_tiles > 0 &&
+        (((uintptr_t)L.q | (uintptr_t)L.out) & 15) == 0) {
         const size_t lds_f = (size_t)2 * 2 * 64 * head_size * sizeof(float);  // two buffers of a K and a V tile
         const bool paged = rg.page_floats != 0;
         const void *fn = head_size == 128
@@ -347,21 +345,21 @@ hipError_t launch_ragged_attention(const float *q, int ldq, float *out, int ldo,
             const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f);
             if (e != hipSuccess) return e;
         }
-        if (x3 != nullptr && (kp & 3) == 0) { a.x3 = (__bf16 *)x3; a.kp = kp; }
+        if (L.x3 != nullptr && (L.kp & 3) == 0) { a.x3 = (__bf16 *)L.x3; a.kp = L.kp; }
         if (planes_written) *planes_written = a.x3 != nullptr;
         void *params[] = {(void *)&a};
-        return hipLaunchKernel(fn, dim3(n_heads, rg.n_tiles), dim3(512), params, lds_f, st);
+        return hipLaunchKernel(fn, dim3(L.n_heads, rg.n_tiles), dim3(512), params, lds_f, L.st);
     }
     int E = head_size >> 2, TPR = 1;
     while (TPR < E && TPR < 64) TPR <<= 1;
     const int G = kPfBlock / TPR;
-    const size_t lds = (size_t)(((seq_len + 3) & ~3) + G * head_size + 8) * sizeof(float);
+    const size_t lds = (size_t)(((L.seq_len + 3) & ~3) + G * head_size + 8) * sizeof(float);
     if (lds > 64 * 1024) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ragged_attention_rows),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(ragged_attention_rows, dim3(n_heads, rg.att_rows != nullptr ? rg.n_att_rows : P), dim3(kPfBlock), lds, st, a);
+    hipLaunchKernelGGL(ragged_attention_rows, dim3(L.n_heads, rg.att_rows != nullptr ? rg.n_att_rows : P), dim3(kPfBlock), lds, L.st, a);
     return hipGetLastError();
 }
 

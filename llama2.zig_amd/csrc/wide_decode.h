@@ -44,10 +44,13 @@ struct WideAttn {
     int n_seg;             // segments of the deepest row of this step: the grid's extent
     int verify_m;          // 0: one row per sequence (launch_wide_attention); l2z_verify_wide: the slots of a block, the
                            // smallest of 1, 2, 4, 8, 16 that holds the call's longest sequence (launch_wide_verify_attention)
+    int n_seq;             // l2z_verify_wide: the table's sequences
     size_t page_floats;    // RaggedChunk::page_floats of the step (0: contiguous caches)
 };
 
-// Decode attention (main.zig:361-389) of rows 0 .. n - 1 of q [n, ldq] (RoPE applied) into out [n, ldo], two launches:
+// Every attention launcher here takes the layer's q, out, shape, cache offsets, stream and planes as the ragged pass's
+// RaggedLayer (l2z_internal.h), then its own table, then planes_written.
+// Decode attention (main.zig:361-389) of rows 0 .. n - 1 of q [n, ldq] (RoPE applied) into out [n, ldo], n = L.P, two launches:
 //   wide_attention: block (kv head, segment, row) reads the segment's K and V rows of that kv head ONCE and serves all
 //     kv_mul query heads of it (up to 4 per block; beyond, blocks of 4, the last one with the heads that are left); a block
 //     past its row's last segment returns.  It leaves the flash partials (max, sum e, sum e v) per (row, head, segment).
@@ -55,9 +58,7 @@ struct WideAttn {
 //     out's planes of bf16 terms x3[row][3][kp] (the Wo product's operand; *planes_written says whether it did).
 // head_size: a multiple of 4 up to 256.  Every summation order is verify_device.h's: a function of head_size, the segment
 // and the row's own position only; no block touches two sequences.  Keys beyond pos[i] are never read.
-hipError_t launch_wide_attention(const float *q, int ldq, float *out, int ldo, const WideAttn &wa, int n, int n_heads,
-                                 int head_size, size_t layer_off, size_t kv_head_stride, int kv_mul, hipStream_t st,
-                                 void *x3 = nullptr, int kp = 0, bool *planes_written = nullptr);
+hipError_t launch_wide_attention(const RaggedLayer &L, const WideAttn &wa, bool *planes_written = nullptr);
 // The same two launches over rows named one by one (l2z_step_mixed, mixed_step.hip: the one-row sequences of a chunk that
 // holds prompt rows too): block ordinal i of either launch serves row list[i].x of the chunk -- q, out, the planes, pos[] --
 // on sequence slot list[i].y of seq[]; the partials stand at the ORDINAL, n <= kWideMax of them.  list == null: row = slot =
@@ -71,9 +72,7 @@ struct WideRows {
     int seg_cap, n_seg;      // as WideAttn's; n_seg: segments of the deepest listed row
     size_t page_floats;
 };
-hipError_t launch_wide_attention_rows(const float *q, int ldq, float *out, int ldo, const WideRows &wr, int n_heads, int head_size,
-                                      size_t layer_off, size_t kv_head_stride, int kv_mul, hipStream_t st, void *x3 = nullptr,
-                                      int kp = 0, bool *planes_written = nullptr);
+hipError_t launch_wide_attention_rows(const RaggedLayer &L, const WideRows &wr, bool *planes_written = nullptr);   // (wr.n rows, not L.P)
 // wide_combine alone, over the partials some attention launch left for rows 0 .. n - 1 (tab->pos[row] = the row's position)
 hipError_t launch_wide_combine(float *out, int ldo, const WideAttn &wa, int n, int n_heads, int head_size, hipStream_t st,
                                void *x3 = nullptr, int kp = 0, bool *planes_written = nullptr);
@@ -107,7 +106,8 @@ hipError_t launch_wide_draw_advance(const WideDraw &d, int n, hipStream_t st);
 // positions from seq[j].pos0 on, rows seq[j].row0 .. of the chunk; row_seq[r], pos[r] and tokens[r] are per row, logits[j]
 // is per SEQUENCE: the runstate's logits the verdict fills ----
 
-// Causal attention of rows 0 .. n_rows - 1 of q [n_rows, ldq] (RoPE applied) into out [n_rows, ldo], two launches:
+// Causal attention of rows 0 .. n_rows - 1 of q [n_rows, ldq] (RoPE applied) into out [n_rows, ldo], n_rows = L.P rows of
+// wa.n_seq sequences, two launches:
 //   wide_verify_attention<M>: block (head, segment, sequence), M = wa.verify_m; its slots are the sequence's rows of that
 //     head as verify_attention_body sets them up (row i sees the keys t <= pos0 + i; the rows that end before the segment
 //     are out of use), the q slices and partials addressed through the wide step's row-indexed layout.  A block past its
@@ -116,9 +116,7 @@ hipError_t launch_wide_draw_advance(const WideDraw &d, int n, hipStream_t st);
 //   wide_combine, as it stands: a row's segments 0 .. pos[row] / kVerifySeg, and the bf16 planes.
 // Every summation order is verify_device.h's; no block touches two sequences.  wa.n_seg: the segments of the deepest
 // sequence's last position.
-hipError_t launch_wide_verify_attention(const float *q, int ldq, float *out, int ldo, const WideAttn &wa, int n_seq, int n_rows,
-                                        int n_heads, int head_size, size_t layer_off, size_t kv_head_stride, int kv_mul,
-                                        hipStream_t st, void *x3 = nullptr, int kp = 0, bool *planes_written = nullptr);
+hipError_t launch_wide_verify_attention(const RaggedLayer &L, const WideAttn &wa, bool *planes_written = nullptr);
 
 // The per-sequence controls of a sampled call, behind the WideTable in the same allocations and the same copy
 struct WideVerdictCtl {

@@ -144,35 +144,31 @@ static hipError_t combine_launch(const WideAttnArgs &a, int n, hipStream_t st, b
     return e;
 }
 
-hipError_t launch_wide_attention_rows(const float *q, int ldq, float *out, int ldo, const WideRows &wr, int n_heads, int head_size,
-                                      size_t layer_off, size_t kv_head_stride, int kv_mul, hipStream_t st, void *x3, int kp,
-                                      bool *planes_written)
+hipError_t launch_wide_attention_rows(const RaggedLayer &L, const WideRows &wr, bool *planes_written)
 {
     if (planes_written) *planes_written = false;
+    const int kv_mul = L.kv_mul;
     WideAttnArgs a = {};
-    if (!wide_out_args(a, out, ldo, wr, n_heads, head_size, x3, kp) || kv_mul < 1 || n_heads % kv_mul != 0 || (ldq & 3) ||
-        (((uintptr_t)q) & 15) || (layer_off & 3) || (kv_head_stride & 3) || (wr.page_floats & 3))
+    if (!wide_out_args(a, L.out, L.ldo, wr, L.n_heads, L.head_size, L.x3, L.kp) || kv_mul < 1 || L.n_heads % kv_mul != 0 || (L.ldq & 3) ||
+        (((uintptr_t)L.q) & 15) || (L.layer_off & 3) || (L.kv_head_stride & 3) || (wr.page_floats & 3))
         return hipErrorInvalidValue;
-    a.q = q; a.ldq = ldq; a.kv_mul = kv_mul;
-    a.layer_off = layer_off; a.kv_head_stride = kv_head_stride; a.page_floats = wr.page_floats;
+    a.q = L.q; a.ldq = L.ldq; a.kv_mul = kv_mul;
+    a.layer_off = L.layer_off; a.kv_head_stride = L.kv_head_stride; a.page_floats = wr.page_floats;
     const int mq = kv_mul == 1 ? 1 : kv_mul == 2 ? 2 : kWaHeadsMax;
-    const dim3 grid(n_heads / kv_mul * ((kv_mul + mq - 1) / mq), wr.n_seg, wr.n);
+    const dim3 grid(L.n_heads / kv_mul * ((kv_mul + mq - 1) / mq), wr.n_seg, wr.n);
     switch (mq) {
-        case 1: hipLaunchKernelGGL(wide_attention<1>, grid, dim3(kVaBlock), 0, st, a); break;
-        case 2: hipLaunchKernelGGL(wide_attention<2>, grid, dim3(kVaBlock), 0, st, a); break;
-        default: hipLaunchKernelGGL(wide_attention<kWaHeadsMax>, grid, dim3(kVaBlock), 0, st, a); break;
+        case 1: hipLaunchKernelGGL(wide_attention<1>, grid, dim3(kVaBlock), 0, L.st, a); break;
+        case 2: hipLaunchKernelGGL(wide_attention<2>, grid, dim3(kVaBlock), 0, L.st, a); break;
+        default: hipLaunchKernelGGL(wide_attention<kWaHeadsMax>, grid, dim3(kVaBlock), 0, L.st, a); break;
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    return combine_launch(a, wr.n, st, planes_written);
+    return combine_launch(a, wr.n, L.st, planes_written);
 }
 
-hipError_t launch_wide_attention(const float *q, int ldq, float *out, int ldo, const WideAttn &wa, int n, int n_heads,
-                                 int head_size, size_t layer_off, size_t kv_head_stride, int kv_mul, hipStream_t st, void *x3,
-                                 int kp, bool *planes_written)
+hipError_t launch_wide_attention(const RaggedLayer &L, const WideAttn &wa, bool *planes_written)
 {
-    return launch_wide_attention_rows(q, ldq, out, ldo, rows_of(wa, n), n_heads, head_size, layer_off, kv_head_stride, kv_mul, st,
-                                      x3, kp, planes_written);
+    return launch_wide_attention_rows(L, rows_of(wa, L.P), planes_written);
 }
 
 hipError_t launch_wide_combine(float *out, int ldo, const WideAttn &wa, int n, int n_heads, int head_size, hipStream_t st,

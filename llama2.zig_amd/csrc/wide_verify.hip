@@ -87,33 +87,33 @@ __global__ __launch_bounds__(1024) void wide_verify_accept(const WideVerdict a)
 
 }  // namespace
 
-hipError_t launch_wide_verify_attention(const float *q, int ldq, float *out, int ldo, const WideAttn &wa, int n_seq, int n_rows,
-                                        int n_heads, int head_size, size_t layer_off, size_t kv_head_stride, int kv_mul,
-                                        hipStream_t st, void *x3, int kp, bool *planes_written)
+hipError_t launch_wide_verify_attention(const RaggedLayer &L, const WideAttn &wa, bool *planes_written)
 {
     if (planes_written) *planes_written = false;
+    const int n_seq = wa.n_seq, n_rows = L.P, n_heads = L.n_heads, head_size = L.head_size, kv_mul = L.kv_mul;
     if (n_seq < 1 || n_seq > n_rows || n_rows > kWideMax || head_size < 4 || head_size > 256 || (head_size & 3) || kv_mul < 1 ||
         n_heads < 1 || n_heads % kv_mul != 0 || wa.tab == nullptr || wa.part == nullptr || wa.n_seg < 1 || wa.n_seg > wa.seg_cap ||
-        (ldq & 3) || (((uintptr_t)q | (uintptr_t)wa.part) & 15) || (layer_off & 3) || (kv_head_stride & 3) || (wa.page_floats & 3))
+        (L.ldq & 3) || (((uintptr_t)L.q | (uintptr_t)wa.part) & 15) || (L.layer_off & 3) || (L.kv_head_stride & 3) ||
+        (wa.page_floats & 3))
         return hipErrorInvalidValue;
     WideVerifyAttnArgs a = {};
-    a.q = q; a.tab = wa.tab;
+    a.q = L.q; a.tab = wa.tab;
     a.part_o = wa.part;
     a.part_ml = wa.part + (size_t)kWideMax * n_heads * wa.seg_cap * head_size;
-    a.layer_off = layer_off; a.kv_head_stride = kv_head_stride; a.page_floats = wa.page_floats;
-    a.ldq = ldq; a.n_heads = n_heads; a.kv_mul = kv_mul; a.head_size = head_size; a.seg_cap = wa.seg_cap;
+    a.layer_off = L.layer_off; a.kv_head_stride = L.kv_head_stride; a.page_floats = wa.page_floats;
+    a.ldq = L.ldq; a.n_heads = n_heads; a.kv_mul = kv_mul; a.head_size = head_size; a.seg_cap = wa.seg_cap;
     const dim3 grid(n_heads, wa.n_seg, n_seq);
     switch (wa.verify_m) {
-        case 1: hipLaunchKernelGGL(wide_verify_attention<1>, grid, dim3(kVaBlock), 0, st, a); break;
-        case 2: hipLaunchKernelGGL(wide_verify_attention<2>, grid, dim3(kVaBlock), 0, st, a); break;
-        case 4: hipLaunchKernelGGL(wide_verify_attention<4>, grid, dim3(kVaBlock), 0, st, a); break;
-        case 8: hipLaunchKernelGGL(wide_verify_attention<8>, grid, dim3(kVaBlock), 0, st, a); break;
-        case 16: hipLaunchKernelGGL(wide_verify_attention<16>, grid, dim3(kVaBlock), 0, st, a); break;
+        case 1: hipLaunchKernelGGL(wide_verify_attention<1>, grid, dim3(kVaBlock), 0, L.st, a); break;
+        case 2: hipLaunchKernelGGL(wide_verify_attention<2>, grid, dim3(kVaBlock), 0, L.st, a); break;
+        case 4: hipLaunchKernelGGL(wide_verify_attention<4>, grid, dim3(kVaBlock), 0, L.st, a); break;
+        case 8: hipLaunchKernelGGL(wide_verify_attention<8>, grid, dim3(kVaBlock), 0, L.st, a); break;
+        case 16: hipLaunchKernelGGL(wide_verify_attention<16>, grid, dim3(kVaBlock), 0, L.st, a); break;
         default: return hipErrorInvalidValue;
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    return launch_wide_combine(out, ldo, wa, n_rows, n_heads, head_size, st, x3, kp, planes_written);
+    return launch_wide_combine(L.out, L.ldo, wa, n_rows, n_heads, head_size, L.st, L.x3, L.kp, planes_written);
 }
 
 hipError_t launch_wide_verdict(const WideVerdict &d, int n_seq, int n_rows, hipStream_t st)

@@ -120,7 +120,7 @@ static void run(const char *name, l2z_config c, int world, int rank, bool scheme
         s.pf_pending.valid = false;
         if (world == 1 && !scheme_b) {
             RaggedChunk rg = {};
-            hipMalloc(&p, 1 << 24); rg.k = (float *)p; hipMalloc(&p, 1 << 24); rg.v = (float *)p; rg.n_seq = 2; rg.n_tiles = 2;
+            hipMalloc(&p, 1 << 24); rg.k = (float *)p; hipMalloc(&p, 1 << 24); rg.v = (float *)p; rg.n_seq = 2; rg.n_tiles = 2; rg.seq_max = kRaggedMaxSeq;
             for (int k = 0; k < PF_STAGES; k++) { printf("  ragged stage %d\n", k); int rc = prefill_stage(&s, &w, 1, k, P, 0, &rg); if (rc) printf("  rc %d\n", rc); }
             s.pf_pending.valid = false;
             if (score_alloc(&s, P) == 0) {
