@@ -38,6 +38,13 @@ int l2z_weights_packed_count(const l2z_weights *w, int *n_packed, int *n_candida
 /* Decode the packed slot of `layer` ON THE DEVICE back to f32: 2 * hidden_dim rows (row 2r = W1 row r, row 2r + 1 = W3
  * row r) x dim, row-major, into out (n_floats >= that).  L2Z_ERR_STATE if that slot is not packed. */
 int l2z_weights_packed_read(const l2z_weights *w, int layer, float *out, size_t n_floats);
+/* The same two for the packed copy of any kind of decode launch (`kind`: the index l2z_time_kind takes).  Slots per layer:
+ * qkv 3 (0 Wq, 1 Wk, 2 Wv: rows x dim each, every slot with its own base exponent; the launch streams the copy only if
+ * all three of its layer are packed), wo 1 (dim x dim), ffn13 1 (the W1 | W3 slot above), ffn2 1 (dim x hidden_dim), cls
+ * 1 for the model, at layer 0 (vocab_size x dim; with shared embeddings a copy of the embedding table).  A slot with an
+ * odd number of rows is a candidate that stays f32.  Kinds without a packed form report (0, 0). */
+int l2z_weights_packed_count_kind(const l2z_weights *w, int kind, int *n_packed, int *n_candidates);
+int l2z_weights_packed_read_kind(const l2z_weights *w, int kind, int layer, int slot, float *out, size_t n_floats);
 
 /* copy a named RunState buffer to the host: "x","xb","hb","q","att","logits",
  * "key_cache","value_cache" (tests only) */

@@ -173,8 +173,12 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *
         *epi = sh.rank == 0 ? EPI_RESID : EPI_STORE;
         push_to(a, 1);
     };
-    // packed weights: ffn13 streams the 29-bit copy of its W1 | W3 slot where the weights have one
-    const bool pk = s->packed_w && w->pk_blob != nullptr && !sb && sh.world == 1 && !consume;
+    // packed weights: a row launch streams the 29-bit copy of its slot(s) where the weights have one and
+    // the runstate's mask of kinds (L2Z_PACKED_KINDS) lets it
+    const bool pk = s->packed_w && !sb && sh.world == 1 && !consume;
+    const auto pk_slot = [&](int k, int l, int j = 0) -> const l2z_weights::PkMat * {
+        return pk && ((s->packed_kinds >> k) & 1) ? w->pk_slot(k, l, j) : nullptr;
+    };
     for (int l = 0; l < c.n_layers; l++) {
         // :354 loff; inside a layer the device cache is head-major, [kv heads][seq_len][head_size]: the rows
         // one head's attention reads are one contiguous run
@@ -204,6 +208,12 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *
             a.n = c.dim; a.rms_w = w->rms_att + (size_t)l * dim;
             x_in(a, s->x, gi, sh.dim_loc);  // layer 0: the embedding row, a plain buffer (gi == 0)
             a.pos_ptr = s->d_pos; a.rope = s->rope; a.head_size = sh.hs; a.rope_segs = 2;
+            const auto *pq = pk_slot(KIND_QKV, l, 0), *pkk = pk_slot(KIND_QKV, l, 1), *pv = pk_slot(KIND_QKV, l, 2);
+            if (pq && pkk && pv) {  // all three slots or none
+                a.pk = pq->p; a.pk_e = pq->e;
+                a.pk1 = pkk->p; a.pk_e1 = pkk->e;
+                a.pk2 = pv->p; a.pk_e2 = pv->e;
+            }
             L2Z_LAUNCH(KIND_QKV, launch_matvec(a, PRO_RMS, EPI_ROPE, mb, g_cus, st));
         }
         if (!fused && want() && kind(KIND_ATTN)) {   // attention (:361-389) over the local heads
@@ -236,6 +246,7 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *
                 a.rows0 = sh.dim_loc; a.n = c.dim;
                 x_in(a, s->xb, gi, sh.dim_loc);
                 push_to(a, 1);
+                if (const auto *p = pk_slot(KIND_WO, l)) { a.pk = p->p; a.pk_e = p->e; }
             }
             L2Z_LAUNCH(KIND_WO, launch_matvec(a, PRO_NONE, epi, mb, g_cus, st, nullptr, &pushed));
         }
@@ -250,7 +261,7 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *
             a.rms_w = w->rms_ffn + (size_t)l * dim;
             x_in(a, s->x, gi, sh.dim_loc);
             if (!sb) push_to(a, 2);
-            if (pk && w->pk[l].p != nullptr) { a.pk = w->pk[l].p; a.pk_e = w->pk[l].e; }
+            if (const auto *p = pk_slot(KIND_FFN13, l)) { a.pk = p->p; a.pk_e = p->e; }
             L2Z_LAUNCH(KIND_FFN13, launch_matvec(a, PRO_RMS, EPI_SWIGLU, mb, g_cus, st, nullptr, &pushed));
         }
         if (!sb) L2Z_TRY(gather(s->hb, sh.hid_loc));
@@ -265,6 +276,7 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *
                 a.rows0 = sh.dim_loc; a.n = c.hidden_dim;
                 x_in(a, s->hb, gi, sh.hid_loc);
                 push_to(a, 1);
+                if (const auto *p = pk_slot(KIND_FFN2, l)) { a.pk = p->p; a.pk_e = p->e; }
             }
             L2Z_LAUNCH(KIND_FFN2, launch_matvec(a, PRO_NONE, epi, mb, g_cus, st, nullptr, &pushed));
         }
@@ -283,6 +295,7 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *
                           matvec_vector_width(c.dim);
         int grid = 0;
         if (!xchg) push_to(a, 3);
+        if (const auto *p = fuse ? pk_slot(KIND_CLS, 0) : nullptr) { a.pk = p->p; a.pk_e = p->e; }
         L2Z_LAUNCH(KIND_CLS, launch_matvec(a, PRO_RMS, fuse ? EPI_ARGMAX : EPI_STORE, mb, g_cus, st,
                                            &grid, &pushed));
         s->n_part = fuse ? grid : 0;

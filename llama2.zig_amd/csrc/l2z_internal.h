@@ -147,9 +147,11 @@ struct MatvecArgs {
     // x is a gathered vector that is read as LL words from this rank's landing slot (xin.slots != null)
     LLIn xin;
     // Packed weights (packed_w.h): pk != null -> the row kernel streams the 29-bit copy of w0 (base
-    // exponent pk_e) instead of its f32 rows.  EPI_SWIGLU on the W1 | W3 slot of unsharded weights only (ffn13)
-    const uint32_t *pk;
-    int pk_e;
+    // exponent pk_e) instead of its f32 rows, and with three segments (q | k | v) those of w1 and w2 as well (pk1 / pk2,
+    // pk_e1 / pk_e2: every slot has its own base exponent; all three or none).  Unsharded weights only
+    const uint32_t *pk, *pk1, *pk2;
+    int pk_e, pk_e1, pk_e2;
+    int tl_slot;              // measurement builds only (L2Z_TIMELINE): where the launch's blocks leave their stamps
 };
 
 // main.zig:361-389: scores, softmax, att.V for the local heads of one layer

@@ -54,6 +54,9 @@ int current_device_for(const l2z_comm *comm);
 
 }  // namespace l2z
 
+// the kinds of launch of the decode pass (l2z_time_kind, l2z_profile_forward; the packed copy and its mask are per kind)
+enum { KIND_QKV = 0, KIND_ATTN, KIND_WO, KIND_FFN13, KIND_FFN2, KIND_CLS, KIND_ARGMAX, KIND_GATHER, KIND_COUNT };
+
 struct l2z_weights {
     uint64_t uid = 0;  // unique per object for the life of the process: keys a runstate's captured graphs
     l2z_config cfg;
@@ -72,15 +75,30 @@ struct l2z_weights {
     const float *wq = nullptr, *wk = nullptr, *wv = nullptr, *wo = nullptr;
     // w1 / w3: row 0 of W1 / of W3 in the shared slot; consecutive rows of either are 2 * dim floats apart
     const float *w1 = nullptr, *w2 = nullptr, *w3 = nullptr, *wcls = nullptr;
-    // the 29-bit packed copy of each layer's W1 | W3 slot that ffn13 streams in decode (packed_w.h, DESIGN.md 4.9;
-    // unsharded weights, L2Z_PACKED_W); pk[layer].p == null: that slot stays f32 only
+    // the 29-bit packed copy of the decode's row mat-vec weights (packed_w.h; unsharded weights,
+    // L2Z_PACKED_W), per kind of launch: ffn13 one W1 | W3 slot per layer, q|k|v three slots per layer (Wq, Wk, Wv, each
+    // with its own base exponent), wo and ffn2 one per layer, cls one per model.  A kind has its own allocation (one that
+    // fails costs that kind only); slots[i].p == null: that slot stays f32 only
     struct PkMat {
         const uint32_t *p = nullptr;
         int e = 0;          // base exponent E
+        const float *src = nullptr;  // the f32 rows it stands for
+        int rows = 0, cols = 0;
     };
-    uint32_t *pk_blob = nullptr;
-    std::vector<PkMat> pk;
-    int pk_packed = 0, pk_candidates = 0;
+    struct PkKind {
+        uint32_t *blob = nullptr;
+        std::vector<PkMat> slots;  // [layer][slot of the kind]
+        int per_layer = 0;         // slots per layer (cls: 1, layer 0 only)
+        int packed = 0;            // slots with a copy
+    };
+    PkKind pk[KIND_COUNT];
+    // slot j of `layer` of a kind, or null where the kind has no copy of it
+    const PkMat *pk_slot(int kind, int layer, int j = 0) const
+    {
+        const PkKind &k = pk[kind];
+        const size_t i = (size_t)layer * k.per_layer + j;
+        return k.blob != nullptr && i < k.slots.size() && k.slots[i].p != nullptr ? &k.slots[i] : nullptr;
+    }
 };
 
 // The KV page pool (include/llama2_hip_test.h; kv_pool.cpp): n_pages pages of the key array and as many of
@@ -94,7 +112,6 @@ struct l2z_kvpool {
     int live = 0;   // runstates made from it and not freed yet
 };
 
-enum { KIND_QKV = 0, KIND_ATTN, KIND_WO, KIND_FFN13, KIND_FFN2, KIND_CLS, KIND_ARGMAX, KIND_GATHER, KIND_COUNT };
 static const char *const kKindNames[KIND_COUNT] = {"qkv", "attn", "wo", "ffn13", "ffn2", "cls", "argmax", "gather"};
 static_assert(KIND_COUNT == L2Z_N_KINDS, "include/llama2_hip_test.h L2Z_N_KINDS");
 
@@ -177,6 +194,7 @@ struct l2z_runstate {
     bool fused_qkv_attn = false;  // small models: qkv + RoPE + KV write + attention in one launch
     int max_blocks = 0;
     bool packed_w = true;          // L2Z_PACKED_W at creation: decode mat-vecs stream the weights' packed copy where it exists
+    int packed_kinds = -1;         // L2Z_PACKED_KINDS at creation: bit k = launches of kind k may take it
     int tl_attn_seq = 0;           // attention launches enqueued so far (AttnArgs::tl_seq, measurement builds)
     l2z::BatchScratch *bt = nullptr;  // batched decode scratch of the calls that name this runstate first (batch_host.cpp)
     // l2z_prefill_batch scratch of the calls that name this runstate first (prefill_batch_host.cpp): a chunk's key / value

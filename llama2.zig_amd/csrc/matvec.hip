@@ -258,22 +258,24 @@ __device__ __forceinline__ void pk_decode_lane(const PkRaw &r, int e31, v4f (&wa
 }
 
 // Where matvec_row_kernel's (unit, batch) loop gets a batch's wa[] / wb[] from.  A source offers
-//   point(m, u)  aim at unit u's pair,
-//   issue(b)     request batch b of that pair,
-//   deliver()    wa[] / wb[] hold the CURRENT batch for the FMAs,
-// and kAhead says when the loop issues the next batch: after the current one's FMAs, into the same registers (fp32), or
-// before them, into a second set of raw words that rotate() makes the current one (packed).
+//   point(m, u)   aim at unit u's pair,
+//   issue<P>(b)   request batch b of that pair into register set P,
+//   deliver<P>()  wa[] / wb[] hold the batch of set P for the FMAs,
+// and kSets says when the loop requests the next batch: 1 = after the current batch's FMAs, into the same registers
+// (fp32); 2 = before the current batch is decoded, into the other of two FIXED sets of raw words that the loop, unrolled
+// twice, takes in turn (packed): no set is ever copied into the other, so a request never waits for an earlier batch.
 constexpr int kRowU = 4;  // float4 per row per thread per batch
 
 template <int EPI, int XC>
 struct RowF32 {
-    static constexpr bool kAhead = false;
+    static constexpr int kSets = 1;
     v4f wa[kRowU], wb[kRowU];
     const float *pa, *pb;
     int n4;
 
     __device__ __forceinline__ void init(const MvLocals &, int n4_, int) { n4 = n4_; }
     __device__ __forceinline__ void point(const MvLocals &m, int u) { pair_rows<EPI>(m, u, pa, pb); }
+    template <int P>
     __device__ __forceinline__ void issue(int b)
     {
         // columns cb + tid + 256k; validity is wave-uniform (n4 % 64 == 0)
@@ -296,56 +298,72 @@ struct RowF32 {
             wb[k] = ldg_nt(b4 + off);
         }
     }
+    template <int P>
     __device__ __forceinline__ void deliver() {}
 };
 
-template <int XC>
+template <int EPI, int XC>
 struct RowPacked {
-    static constexpr bool kAhead = true;
+    static constexpr int kSets = 2;
     v4f wa[kRowU], wb[kRowU];
-    PkRaw raw, nraw;  // raw words of the batch being decoded and of the next one, and their in-row steps
-    int s_cur, s_nxt;
+    // per set: the raw words of a batch, its in-row steps and its slot's exponent offset (both wave-uniform)
+    PkRaw raw[kSets];
+    int s_in[kSets], e31[kSets];
     const uint32_t *pp;
     size_t pdw, last_off;
-    int e31, s_last, wave_u, n_batches;
+    int e_pt, s_last, wave_u, n_batches;
 
-    __device__ __forceinline__ void init(const MvLocals &m, int n4, int n_batches_)
+    __device__ __forceinline__ void init(const MvLocals &, int n4, int n_batches_)
     {
         n_batches = n_batches_;
-        e31 = m.pk_e - 31;
         wave_u = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
         pdw = pk::pair_dw(n4);
         last_off = pk::chunk_off(n4, n_batches - 1, wave_u);
         s_last = pk::steps(n4, n_batches - 1, wave_u);
     }
-    __device__ __forceinline__ void point(const MvLocals &m, int u) { pp = pair_packed(m, u, pdw); }
+    __device__ __forceinline__ void point(const MvLocals &m, int u)
+    {
+        int e;
+        pp = pair_packed<EPI>(m, u, pdw, e);
+        e_pt = e - 31;
+    }
+    template <int P>
     __device__ __forceinline__ void issue(int b)
     {
         const bool last = b + 1 == n_batches;
         const uint32_t *src = pp + (last ? last_off : (size_t)b * (4 * 64 * pk::kMaxLaneDw) + (size_t)wave_u * (64 * pk::kMaxLaneDw));
-        s_nxt = (XC == 4 || !last) ? 4 : s_last;  // n = 4096: one full batch
-        pk_load_raw(src, threadIdx.x & 63, XC == 4 ? 4 : s_nxt, nraw);
+        s_in[P] = (XC == 4 || !last) ? 4 : s_last;  // n = 4096: one full batch
+        e31[P] = e_pt;
+        pk_load_raw(src, threadIdx.x & 63, XC == 4 ? 4 : s_in[P], raw[P]);
     }
-    __device__ __forceinline__ void rotate()
-    {
-        raw = nraw;
-        s_cur = s_nxt;
-    }
+    template <int P>
     __device__ __forceinline__ void deliver()
     {
         if constexpr (XC == 4) {
-            pk_decode_lane<4>(raw, e31, wa, wb);
+            pk_decode_lane<4>(raw[P], e31[P], wa, wb);
         } else {
-            switch (s_cur) {  // wave-uniform
-                case 4: pk_decode_lane<4>(raw, e31, wa, wb); break;
-                case 3: pk_decode_lane<3>(raw, e31, wa, wb); break;
-                case 2: pk_decode_lane<2>(raw, e31, wa, wb); break;
-                case 1: pk_decode_lane<1>(raw, e31, wa, wb); break;
-                default: pk_decode_lane<0>(raw, e31, wa, wb); break;
+            switch (s_in[P]) {  // wave-uniform
+                case 4: pk_decode_lane<4>(raw[P], e31[P], wa, wb); break;
+                case 3: pk_decode_lane<3>(raw[P], e31[P], wa, wb); break;
+                case 2: pk_decode_lane<2>(raw[P], e31[P], wa, wb); break;
+                case 1: pk_decode_lane<1>(raw[P], e31[P], wa, wb); break;
+                default: pk_decode_lane<0>(raw[P], e31[P], wa, wb); break;
             }
         }
     }
 };
+
+#ifdef L2Z_TIMELINE
+// measurement build (scripts/timeline_build.sh): wall-clock stamps (100 MHz) of every block of the row kernel, kept in
+// registers and stored at the block's end.  Per (slot, block): [0] entry, [1] first weight batch requested, [2] x staged,
+// [3] first unit done, [4] last unit done, [5] exit, [6] batches consumed, [7] units done
+constexpr int kMtlSlots = 256, kMtlBlocks = 512;
+__device__ long long g_mtl[kMtlSlots * kMtlBlocks * 8];
+unsigned long long g_mtl_launches = 0;  // row-kernel launches so far: launch i stamps slot i % kMtlSlots
+#define L2Z_MTL(i) tl[i] = wall_clock64()
+#else
+#define L2Z_MTL(i) do { } while (0)
+#endif
 
 // ---------------------------------------------------------------------------
 // Wide rows (n >= 4096, n/4 a multiple of 64: the 7B shapes): the WHOLE BLOCK works on
@@ -358,17 +376,26 @@ struct RowPacked {
 //
 // PK: the same kernel streaming the 29-bit packed copy of the weights (packed_w.h): the pair's chunks
 // are read in the same (unit, batch) order, 116 instead of 128 bytes per lane and batch, and decoded into the same
-// wa[] / wb[] right before the FMAs, so every sum is the fp32 kernel's bit for bit.  The next batch's loads are issued
-// before the current one is decoded (the raw words are double-buffered): the decode never stands between a batch's
-// arrival and the next request.
+// wa[] / wb[] right before the FMAs, so every sum is the fp32 kernel's bit for bit.  The raw words live in two fixed
+// register sets taken in turn by a loop unrolled twice: the next batch is requested before the current one is decoded,
+// no request waits on a copy of an earlier batch's words, and the decode waits for the current batch's words only.
 // ---------------------------------------------------------------------------
 template <int PRO, int EPI, int XC, bool LL, bool PK = false>
 __global__ __launch_bounds__(kBlock) void matvec_row_kernel(const MatvecArgs a)
 {
     constexpr int U = kRowU;
-    using Src = typename std::conditional<PK, RowPacked<XC>, RowF32<EPI, XC>>::type;
+    using Src = typename std::conditional<PK, RowPacked<EPI, XC>, RowF32<EPI, XC>>::type;
+    constexpr int NS = Src::kSets;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const MvLocals m = mv_locals<EPI>(a);
+#ifdef L2Z_TIMELINE
+    long long tl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+    L2Z_MTL(0);
+    MvLocals m_ = mv_locals<EPI>(a);
+    // packed weights are unsharded weights: no peer to push to.  Compiled out, not just never taken: the push path is a
+    // loop with loads of its own, and behind it hipcc no longer counts the outstanding weight loads (vmcnt(0) again)
+    if constexpr (PK) m_.push = nullptr;
+    const MvLocals m = m_;
     const int n4 = m.n >> 2;
     const int n_batches = (n4 + kBlock * U - 1) / (kBlock * U);
     const int n4_pad = n_batches * (kBlock * U);
@@ -388,33 +415,69 @@ __global__ __launch_bounds__(kBlock) void matvec_row_kernel(const MatvecArgs a)
     src.point(m, u);
     EpiIn ein = epi_prefetch<EPI>(m, u, tid == 0);
     EpiIn ein_next = ein;
-    src.issue(0);
-    if constexpr (Src::kAhead) src.rotate();
+    src.template issue<0>(0);
+    L2Z_MTL(1);
     xst.finish(a.x, a.rms_w, m.n, n4_pad, xs, scratch);
+    L2Z_MTL(2);
+
+    // the request cursor: the batch the loop issues next (fp32: one past the batch in the registers; packed: one past
+    // the batch in flight)
+    int iu = u, ib = 0;
+    bool imore = true;
+    auto advance = [&]() __attribute__((always_inline)) {
+        const MvStep s = mv_step(iu, ib, n_batches, ustride, n_units);
+        imore = s.more;
+        if (s.more) {
+            if (s.unit_done) src.point(m, s.u_next);
+            iu = s.u_next;
+            ib = s.b_next;
+        }
+    };
+    advance();  // past batch 0 (requested above)
 
     v4f acc_a = {0.f, 0.f, 0.f, 0.f}, acc_b = {0.f, 0.f, 0.f, 0.f};
     ArgmaxCand best;
     int b = 0, parity = 0;
-    while (true) {
+    // one (unit, batch) step on register set P; true = that was the last one.  Packed: whether the step requests a
+    // further batch is decided by its caller (`ahead`), not inside -- a request under a branch that joins again before
+    // the decode makes hipcc wait there for EVERY outstanding load (s_waitcnt vmcnt(0)), the batch just requested
+    // included, and the decode no longer overlaps anything
+    auto step = [&](auto set, auto ahead) __attribute__((always_inline)) -> bool {
+        constexpr int P = decltype(set)::value;
         const MvStep s = mv_step(u, b, n_batches, ustride, n_units);
-        auto issue_next = [&]() __attribute__((always_inline)) {  // the next batch, the next unit's first one included
-            if (s.more) {
-                if (s.unit_done) {
-                    src.point(m, s.u_next);
-                    ein_next = epi_prefetch<EPI>(m, s.u_next, tid == 0);
-                }
-                src.issue(s.b_next);
-            }
+        // what the next unit's epilogue reads: with its first batch's request (fp32), or ahead of the packed requests,
+        // which run further ahead (the epilogue's wait then covers no younger batch)
+        auto prefetch_next = [&]() __attribute__((always_inline)) {
+            if (s.more && s.unit_done) ein_next = epi_prefetch<EPI>(m, s.u_next, tid == 0);
         };
-        if constexpr (Src::kAhead) issue_next();
-        src.deliver();
+        if constexpr (NS > 1) {
+            prefetch_next();
+            if constexpr (decltype(ahead)::value) {
+                // ffn13 alone runs faster when a wave requests the next batch only once the current one is in (one
+                // batch in flight per wave, not up to two: 51.4 against 52.3 us; q|k|v the other way round, 31.5
+                // against 30.6; the other kinds within noise -- profiles/packed_all_kinds.md)
+                if constexpr (EPI == EPI_SWIGLU) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                src.template issue<(P + 1) % NS>(ib);
+                advance();
+            }
+        }
+        src.template deliver<P>();
 #pragma unroll
         for (int k = 0; k < U; k++) {
             const v4f xv = xs4[b * (kBlock * U) + tid + kBlock * k];
             acc_a = fma4(src.wa[k], xv, acc_a);
             acc_b = fma4(src.wb[k], xv, acc_b);
         }
-        if constexpr (!Src::kAhead) issue_next();
+        if constexpr (NS == 1) {  // the next batch, the next unit's first one included
+            prefetch_next();
+            if (imore) {
+                src.template issue<0>(ib);
+                advance();
+            }
+        }
+#ifdef L2Z_TIMELINE
+        tl[6]++;
+#endif
         if (s.unit_done) {
             const float sa = wave_sum(hsum4(acc_a));
             const float sb = wave_sum(hsum4(acc_b));
@@ -438,16 +501,40 @@ __global__ __launch_bounds__(kBlock) void matvec_row_kernel(const MatvecArgs a)
             parity ^= 1;
             acc_a = v4f{0.f, 0.f, 0.f, 0.f};
             acc_b = v4f{0.f, 0.f, 0.f, 0.f};
+#ifdef L2Z_TIMELINE
+            if (tl[7]++ == 0) L2Z_MTL(3);
+            L2Z_MTL(4);
+#endif
         }
-        if (!s.more) break;
-        if constexpr (Src::kAhead) src.rotate();
         u = s.u_next;
         b = s.b_next;
+        return !s.more;
+    };
+    using Set0 = std::integral_constant<int, 0>;
+    using Set1 = std::integral_constant<int, 1>;
+    static_assert(NS == 1 || NS == 2, "register sets of a source");
+    if constexpr (NS == 1) {
+        while (!step(Set0{}, std::false_type{})) {}
+    } else {
+        // the request cursor is one batch past the consumed one: no batch left to request = the last step
+        while (true) {
+            if (!imore) { step(Set0{}, std::false_type{}); break; }
+            step(Set0{}, std::true_type{});
+            if (!imore) { step(Set1{}, std::false_type{}); break; }
+            step(Set1{}, std::true_type{});
+        }
     }
     if (EPI == EPI_ARGMAX && tid == 0) {  // units ascend within a block: first index kept
         a.part_val[blockIdx.x] = best.v;
         a.part_idx[blockIdx.x] = best.i;
     }
+#ifdef L2Z_TIMELINE
+    L2Z_MTL(5);
+    if (tid == 0 && (unsigned)a.tl_slot < (unsigned)kMtlSlots && blockIdx.x < kMtlBlocks) {
+        long long *o = g_mtl + ((size_t)a.tl_slot * kMtlBlocks + blockIdx.x) * 8;
+        for (int i = 0; i < 8; i++) o[i] = tl[i];
+    }
+#endif
 }
 
 // Generic form: any n, any alignment (the reference's 3x3 / 2x12 known-answer
@@ -510,15 +597,15 @@ const void *mv_row_fn(bool big_x)
 // The (prologue, epilogue) pairs that exist, and in which further forms: LL = x read as LL words from the landing slot
 // (sharded runs: only the pairs the forward pass launches on a gathered vector; EPI_ARGMAX there is a shard's classifier,
 // the candidate exchange of greedy steps), SCALAR = the generic kernel (it has no fused-argmax epilogue), PACKED = the row
-// kernel on the 29-bit copy: ffn13 (rmsnorm + W1 | W3 + SwiGLU), the one decode launch it pays off on.
+// kernel on the 29-bit copy: the decode's five row launches -- q|k|v, Wo and W2, ffn13, the classifier.
 //                    PRO       EPI         LL SCALAR PACKED
 #define L2Z_MV_COMBOS(X)                     \
     X(PRO_NONE, EPI_STORE,  0, 1, 0)         \
-    X(PRO_NONE, EPI_RESID,  1, 1, 0)         \
+    X(PRO_NONE, EPI_RESID,  1, 1, 1)         \
     X(PRO_RMS,  EPI_STORE,  1, 1, 0)         \
-    X(PRO_RMS,  EPI_ROPE,   1, 1, 0)         \
+    X(PRO_RMS,  EPI_ROPE,   1, 1, 1)         \
     X(PRO_RMS,  EPI_SWIGLU, 1, 1, 1)         \
-    X(PRO_RMS,  EPI_ARGMAX, 1, 0, 0)
+    X(PRO_RMS,  EPI_ARGMAX, 1, 0, 1)
 #define L2Z_IF_1(...) __VA_ARGS__
 #define L2Z_IF_0(...)
 
@@ -615,6 +702,11 @@ hipError_t launch_matvec(const MatvecArgs &a_in, int pro, int epi, int max_block
     if (ll && !vec) return hipErrorNotSupported;  // callers ask matvec_vector_width() first
     // packed weights: the row kernel's packed form or nothing (no quiet f32 fall-back)
     if (a.pk != nullptr && (!use_row || ll || !pk::width_ok(a.n))) return hipErrorInvalidValue;
+    if (a.pk != nullptr) a.push = nullptr;  // (unsharded: nothing to push to; the packed kernels have no push path)
+    // ... of every segment, pairs inside one slot
+    if (a.pk != nullptr && epi != EPI_SWIGLU &&
+        ((a.rows1 > 0 && a.pk1 == nullptr) || (a.rows2 > 0 && a.pk2 == nullptr) || a.rows0 % 2 || a.rows1 % 2 || a.rows2 % 2))
+        return hipErrorInvalidValue;
     // the kernel form, with the LDS it carves (x padded to whole batches + scratch) and its units of work
     MvLaunch k = {nullptr, 0, 0};
     size_t lds;
@@ -674,8 +766,22 @@ hipError_t launch_matvec(const MatvecArgs &a_in, int pro, int epi, int max_block
     // only single-segment epilogues of the vector kernels push (wo, ffn13, ffn2, classifier)
     if (!vec || epi == EPI_ROPE || a.rows2 != 0 || (epi != EPI_SWIGLU && a.rows1 != 0)) a.push = nullptr;
     if (pushed) *pushed = a.push != nullptr;
+#ifdef L2Z_TIMELINE
+    a.tl_slot = use_row ? (int)(g_mtl_launches++ % kMtlSlots) : -1;
+#endif
     void *args[] = {&a};
     return hipLaunchKernel(k.fn, dim3(grid), dim3(kBlock), args, lds, st);
 }
 
 }  // namespace l2z
+
+#ifdef L2Z_TIMELINE
+// the stamps of all slots, and how many row-kernel launches there have been
+extern "C" int l2z_matvec_timeline_dump(long long *out, unsigned long long *n_launches)
+{
+    if (hipDeviceSynchronize() != hipSuccess) return 1;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(l2z::g_mtl), sizeof(long long) * l2z::kMtlSlots * l2z::kMtlBlocks * 8) != hipSuccess) return 1;
+    *n_launches = l2z::g_mtl_launches;
+    return 0;
+}
+#endif

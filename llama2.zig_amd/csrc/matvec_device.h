@@ -19,8 +19,8 @@ struct MvLocals {
     const P2pArgs *push;  // sharded: LL words of the outputs go straight to the peers
     int push_e;
     size_t push_base;     // index of out0[0] in the gathered vector
-    const uint32_t *pk;  // packed W1 | W3 slot (MatvecArgs::pk; packed row kernel only)
-    int pk_e;
+    const uint32_t *pk, *pk1, *pk2;  // packed slots of w0 / w1 / w2 (MatvecArgs::pk...; packed row kernel only)
+    int pk_e, pk_e1, pk_e2;
 };
 
 template <int EPI>
@@ -40,7 +40,8 @@ __device__ __forceinline__ MvLocals mv_locals(const MatvecArgs &a)
     m.push = a.push;
     m.push_e = m.push ? a.push_ctl[kCtlEpoch] + a.push_gi : 0;
     m.push_base = m.push ? (size_t)m.push->rank * m.push->count : 0;
-    m.pk = a.pk; m.pk_e = a.pk_e;
+    m.pk = a.pk; m.pk1 = a.pk1; m.pk2 = a.pk2;
+    m.pk_e = a.pk_e; m.pk_e1 = a.pk_e1; m.pk_e2 = a.pk_e2;
     return m;
 }
 
@@ -85,11 +86,18 @@ __device__ __forceinline__ void pair_rows(const MvLocals &m, int p, const float 
     }
 }
 
-// packed form of pair_rows (EPI_SWIGLU: pair p = rows 2p, 2p + 1 of the slot): the pair's 29-bit chunks (pair_dw
-// dwords, packed_w.h)
-__device__ __forceinline__ const uint32_t *pair_packed(const MvLocals &m, int p, size_t pair_dw)
+// packed form of pair_rows: the 29-bit chunks of pair p (pair_dw dwords, packed_w.h) and its slot's base exponent.  A
+// pair is rows 2q, 2q + 1 of ONE slot (packed slots have an even number of rows); only q | k | v has three slots
+template <int EPI>
+__device__ __forceinline__ const uint32_t *pair_packed(const MvLocals &m, int p, size_t pair_dw, int &e_base)
 {
     if (p >= m.n_pairs) p = m.n_pairs - 1;
+    if (EPI == EPI_ROPE) {
+        const SegRow r = seg_row(m, 2 * p);
+        e_base = r.pick(m.pk_e, m.pk_e1, m.pk_e2);
+        return r.pick(m.pk, m.pk1, m.pk2) + (size_t)(r.row >> 1) * pair_dw;
+    }
+    e_base = m.pk_e;
     return m.pk + (size_t)p * pair_dw;
 }
 

@@ -38,6 +38,7 @@ static int runstate_make(const l2z_config *config, const l2z_comm *comm, l2z_kvp
     s->max_blocks = tn.max_blocks_per_cu;  // per CU; the launcher also caps at the occupancy query
     s->use_graphs = tn.no_graph == 0;
     s->packed_w = tn.packed_w != 0;
+    s->packed_kinds = tn.packed_kinds;
     // Peer-write gathers are plain kernels (or no launch at all): captured with the rest of the
     // step.  RCCL collectives are captured too (stream capture of ncclAllGather; if the capture
     // fails the step is launched eagerly, ensure_graph).

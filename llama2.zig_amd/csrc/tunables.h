@@ -57,6 +57,10 @@ struct Tunables {
     int packed_w = 1;          // L2Z_PACKED_W        0: no packed weight copy is built and runstates stream the f32 weights in decode (the A/B
                                //                     switch and the escape hatch of DESIGN.md 4.9; same bits either way).  Read when Weights
                                //                     objects (build the copy) and RunState objects (take it) are created
+    int packed_kinds = -1;     // L2Z_PACKED_KINDS    mask over the kinds of decode launch (bit = the kind's index in l2z_time_kind: qkv 1,
+                               //                     wo 4, ffn13 8, ffn2 16, cls 32) that stream the packed copy where the weights have one;
+                               //                     default: every kind that has one.  Read when a RunState is created (the per-kind A/B of
+                               //                     DESIGN.md 4.9; same bits whatever the mask)
     int pf_panel_max = -1;     // L2Z_PF_PANEL_MAX    longest chunk that takes the panel kernel (default and maximum 96 tokens): tests of both sides
                                //                     of the switch-over
 

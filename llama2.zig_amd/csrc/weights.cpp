@@ -258,56 +258,94 @@ int weights_alloc(const l2z_config *config, int shared_weights, const l2z_comm *
     return L2Z_OK;
 }
 
-// The packed copy of each layer's W1 | W3 slot (packed_w.h), built on the device from the complete f32
-// blob: a stats pass per slot, one host read of the stats, one allocation, a packing pass per encodable slot.  Unsharded
-// weights of a width the row kernel runs only; everything else (prefill, batched decode, shards, l2z_weights_read)
-// keeps reading the f32 blob.  Best effort: a failed allocation or launch leaves the weights without a packed copy (f32
-// decode), never failing init.
-void build_packed(l2z_weights *w)
+// The packed copy of one kind's slots (packed_w.h), built on the device from the complete f32 blob: a
+// stats pass per slot, one host read of the stats, one allocation for the kind, a packing pass per encodable slot.  A
+// slot with an odd number of rows has no pairs to pack and stays f32 like one outside the format.  Best effort: a failed
+// allocation or launch leaves this kind without a copy (f32 decode), never failing init.
+void build_packed_kind(l2z_weights *w, int kind, int per_layer, std::vector<l2z_weights::PkMat> slots)
 {
-    if (tunables().packed_w == 0 || !w->file_layout) return;
-    const l2z_config &c = w->cfg;
-    const size_t dim = c.dim, hid = c.hidden_dim;
-    const int rows = 2 * c.hidden_dim, cols = c.dim, L = c.n_layers;
-    if (!pk::width_ok(cols)) return;
-    w->pk.assign(L, l2z_weights::PkMat{});
-    w->pk_candidates = L;
-    auto slot = [&](int l) { return w->w1 + (size_t)l * hid * 2 * dim; };
-    std::vector<uint32_t> stats(3 * (size_t)L);
-    for (int l = 0; l < L; l++) {
-        stats[3 * l] = 0;
-        stats[3 * l + 1] = 255;
-        stats[3 * l + 2] = 0;
+    l2z_weights::PkKind &k = w->pk[kind];
+    k.per_layer = per_layer;
+    k.slots = std::move(slots);
+    const size_t n = k.slots.size();
+    std::vector<uint32_t> stats(3 * n);
+    for (size_t i = 0; i < n; i++) {
+        stats[3 * i] = 0;
+        stats[3 * i + 1] = 255;
+        stats[3 * i + 2] = 0;
     }
     uint32_t *d_stats = nullptr;
     hipError_t e = hipMalloc((void **)&d_stats, stats.size() * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemcpy(d_stats, stats.data(), stats.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    for (int l = 0; l < L && e == hipSuccess; l++) e = launch_pk_stats(slot(l), (size_t)rows * cols, d_stats + 3 * l, nullptr);
+    for (size_t i = 0; i < n && e == hipSuccess; i++)
+        e = launch_pk_stats(k.slots[i].src, (size_t)k.slots[i].rows * k.slots[i].cols, d_stats + 3 * i, nullptr);
     if (e == hipSuccess) e = hipMemcpy(stats.data(), d_stats, stats.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
     if (d_stats) (void)hipFree(d_stats);
-    const size_t per = (size_t)(rows / 2) * pk::pair_dw(cols / 4);
+    const auto dwords = [&](size_t i) -> size_t {
+        const auto &m = k.slots[i];
+        if (m.rows % 2 || !pk::encodable(stats[3 * i], stats[3 * i + 1], stats[3 * i + 2])) return 0;
+        return (size_t)(m.rows / 2) * pk::pair_dw(m.cols / 4);
+    };
     size_t total = 0;
-    for (int l = 0; l < L; l++) total += pk::encodable(stats[3 * l], stats[3 * l + 1], stats[3 * l + 2]) ? per : 0;
+    for (size_t i = 0; i < n; i++) total += dwords(i);
     if (e == hipSuccess && total > 0) {
-        e = hipMalloc((void **)&w->pk_blob, total * sizeof(uint32_t));
-        if (e != hipSuccess) w->pk_blob = nullptr;  // no room for the copy: decode streams the f32 weights
+        e = hipMalloc((void **)&k.blob, total * sizeof(uint32_t));
+        if (e != hipSuccess) k.blob = nullptr;  // no room for the copy: this kind streams the f32 weights
     }
     size_t off = 0;
-    for (int l = 0; l < L && e == hipSuccess && w->pk_blob; l++) {
-        if (!pk::encodable(stats[3 * l], stats[3 * l + 1], stats[3 * l + 2])) continue;
-        e = launch_pk_pack(slot(l), rows, cols, (int)stats[3 * l], w->pk_blob + off, nullptr);
-        w->pk[l].p = w->pk_blob + off;
-        w->pk[l].e = (int)stats[3 * l];
-        w->pk_packed++;
-        off += per;
+    for (size_t i = 0; i < n && e == hipSuccess && k.blob; i++) {
+        auto &m = k.slots[i];
+        if (dwords(i) == 0) continue;
+        e = launch_pk_pack(m.src, m.rows, m.cols, (int)stats[3 * i], k.blob + off, nullptr);
+        m.p = k.blob + off;
+        m.e = (int)stats[3 * i];
+        k.packed++;
+        off += dwords(i);
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        if (w->pk_blob) (void)hipFree(w->pk_blob);
-        w->pk_blob = nullptr;
-        w->pk.assign(L, l2z_weights::PkMat{});
-        w->pk_packed = 0;
+        if (k.blob) (void)hipFree(k.blob);
+        k.blob = nullptr;
+        for (auto &m : k.slots) m.p = nullptr;
+        k.packed = 0;
+    }
+}
+
+// ... of every kind of row launch of the decode, in the order of what each saves per token (a device short of memory
+// keeps the kinds that pay most).  Unsharded weights of widths the row kernel runs only; everything else (prefill, the
+// batched / wide / verify families, shards, l2z_weights_read, the embedding-row lookup) keeps reading the f32 blob.
+void build_packed(l2z_weights *w)
+{
+    if (tunables().packed_w == 0 || !w->file_layout) return;
+    const l2z_config &c = w->cfg;
+    const size_t dim = c.dim, hid = c.hidden_dim, kvd = (size_t)c.dim / c.n_heads * c.n_kv_heads;
+    const int L = c.n_layers;
+    using Slots = std::vector<l2z_weights::PkMat>;
+    const auto mat = [](const float *src, size_t rows, size_t cols) {
+        l2z_weights::PkMat m;
+        m.src = src; m.rows = (int)rows; m.cols = (int)cols;
+        return m;
+    };
+    if (pk::width_ok(c.dim)) {
+        Slots s13, sqkv, so, scls;
+        for (int l = 0; l < L; l++) {
+            s13.push_back(mat(w->w1 + (size_t)l * hid * 2 * dim, 2 * hid, dim));
+            sqkv.push_back(mat(w->wq + (size_t)l * dim * dim, dim, dim));
+            sqkv.push_back(mat(w->wk + (size_t)l * kvd * dim, kvd, dim));
+            sqkv.push_back(mat(w->wv + (size_t)l * kvd * dim, kvd, dim));
+            so.push_back(mat(w->wo + (size_t)l * dim * dim, dim, dim));
+        }
+        scls.push_back(mat(w->wcls, c.vocab_size, dim));  // shared embeddings: a copy of the embedding table
+        build_packed_kind(w, KIND_FFN13, 1, std::move(s13));
+        build_packed_kind(w, KIND_QKV, 3, std::move(sqkv));
+        build_packed_kind(w, KIND_WO, 1, std::move(so));
+        build_packed_kind(w, KIND_CLS, 1, std::move(scls));
+    }
+    if (pk::width_ok(c.hidden_dim)) {
+        Slots s2;
+        for (int l = 0; l < L; l++) s2.push_back(mat(w->w2 + (size_t)l * dim * hid, dim, hid));
+        build_packed_kind(w, KIND_FFN2, 1, std::move(s2));
     }
 }
 
@@ -488,34 +526,59 @@ extern "C" void l2z_weights_free(l2z_weights *w)
 {
     if (!w) return;
     if (w->blob) (void)hipFree(w->blob);
-    if (w->pk_blob) (void)hipFree(w->pk_blob);
+    for (auto &k : w->pk)
+        if (k.blob) (void)hipFree(k.blob);
     delete w;
 }
 
+namespace {
+
+int packed_read_slot(const l2z_weights *w, int kind, int layer, int j, float *out, size_t n_floats)
+{
+    const l2z_weights::PkKind &k = w->pk[kind];
+    L2Z_CHECK(layer >= 0 && j >= 0 && j < k.per_layer && (size_t)layer * k.per_layer + j < k.slots.size(), L2Z_ERR_INVALID,
+              "l2z_weights_packed_read: no packed slot %d of layer %d of kind %s", j, layer, kKindNames[kind]);
+    const l2z_weights::PkMat *pm = w->pk_slot(kind, layer, j);
+    L2Z_CHECK(pm != nullptr, L2Z_ERR_STATE, "l2z_weights_packed_read: slot %d of layer %d of kind %s is not packed", j, layer,
+              kKindNames[kind]);
+    const size_t count = (size_t)pm->rows * pm->cols;
+    L2Z_CHECK(n_floats >= count, L2Z_ERR_INVALID, "l2z_weights_packed_read: need %zu floats", count);
+    L2Z_HIP(hipSetDevice(w->device));
+    float *d = nullptr;
+    L2Z_HIP(hipMalloc((void **)&d, count * sizeof(float)));
+    hipError_t e = launch_pk_unpack(pm->p, pm->rows, pm->cols, pm->e, d, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(out, d, count * sizeof(float), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    L2Z_HIP(e);
+    return L2Z_OK;
+}
+
+}  // namespace
+
 extern "C" int l2z_weights_packed_count(const l2z_weights *w, int *n_packed, int *n_candidates)
 {
-    L2Z_CHECK(w != nullptr && n_packed != nullptr && n_candidates != nullptr, L2Z_ERR_INVALID,
-              "l2z_weights_packed_count: null argument");
-    *n_packed = w->pk_packed;
-    *n_candidates = w->pk_candidates;
-    return L2Z_OK;
+    return l2z_weights_packed_count_kind(w, KIND_FFN13, n_packed, n_candidates);
 }
 
 extern "C" int l2z_weights_packed_read(const l2z_weights *w, int layer, float *out, size_t n_floats)
 {
     L2Z_CHECK(w != nullptr && out != nullptr, L2Z_ERR_INVALID, "l2z_weights_packed_read: null argument");
-    L2Z_CHECK(layer >= 0 && (size_t)layer < w->pk.size(), L2Z_ERR_INVALID, "l2z_weights_packed_read: no packed layer %d", layer);
-    const auto &pm = w->pk[layer];
-    L2Z_CHECK(pm.p != nullptr, L2Z_ERR_STATE, "l2z_weights_packed_read: layer %d is not packed", layer);
-    const int rows = 2 * w->cfg.hidden_dim, cols = w->cfg.dim;
-    const size_t count = (size_t)rows * cols;
-    L2Z_CHECK(n_floats >= count, L2Z_ERR_INVALID, "l2z_weights_packed_read: need %zu floats", count);
-    L2Z_HIP(hipSetDevice(w->device));
-    float *d = nullptr;
-    L2Z_HIP(hipMalloc((void **)&d, count * sizeof(float)));
-    hipError_t e = launch_pk_unpack(pm.p, rows, cols, pm.e, d, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(out, d, count * sizeof(float), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    L2Z_HIP(e);
+    return packed_read_slot(w, KIND_FFN13, layer, 0, out, n_floats);
+}
+
+extern "C" int l2z_weights_packed_count_kind(const l2z_weights *w, int kind, int *n_packed, int *n_candidates)
+{
+    L2Z_CHECK(w != nullptr && n_packed != nullptr && n_candidates != nullptr, L2Z_ERR_INVALID,
+              "l2z_weights_packed_count: null argument");
+    L2Z_CHECK(kind >= 0 && kind < KIND_COUNT, L2Z_ERR_INVALID, "l2z_weights_packed_count_kind: bad kind %d", kind);
+    *n_packed = w->pk[kind].packed;
+    *n_candidates = (int)w->pk[kind].slots.size();
     return L2Z_OK;
+}
+
+extern "C" int l2z_weights_packed_read_kind(const l2z_weights *w, int kind, int layer, int slot, float *out, size_t n_floats)
+{
+    L2Z_CHECK(w != nullptr && out != nullptr, L2Z_ERR_INVALID, "l2z_weights_packed_read: null argument");
+    L2Z_CHECK(kind >= 0 && kind < KIND_COUNT, L2Z_ERR_INVALID, "l2z_weights_packed_read_kind: bad kind %d", kind);
+    return packed_read_slot(w, kind, layer, slot, out, n_floats);
 }
