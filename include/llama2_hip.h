@@ -107,7 +107,15 @@ void l2z_runstate_free(l2z_runstate *s);
  * Asynchronous on the runstate's stream; l2z_argmax / l2z_logits_read sync. */
 int l2z_transformer(int token, int pos, const l2z_config *config, l2z_runstate *s,
                     const l2z_weights *w);
-/* src/main.zig:715 argmax over s.logits, on device (strict '>' : lowest index wins ties).
+/* src/main.zig:715 argmax over s.logits, on device.  THE RULE, for every call of this header that returns a token id from
+ * a row of logits at temperature 0 (l2z_argmax, l2z_greedy_run, l2z_argmax_batch, l2z_sample_batch, l2z_verify*) and for
+ * l2z_score's top-1: what the reference's scan (max = x[0], then strict '>') returns on the row's f32 values --
+ *   index 0 if x[0] is a NaN; otherwise the lowest index of the largest non-NaN value (a NaN behind index 0 never wins,
+ *   the first of equal maxima does; +-inf, signed zeros and denormals compare as IEEE values); index 0 if the row holds
+ *   no non-NaN value.
+ * At a temperature the id is the host sampler's on l2z_probs_read's probabilities with no tolerance, all-NaN
+ * probabilities included (a NaN or +inf among the logits, or nothing but -inf): sample returns vocab_size - 1,
+ * sample_top_p the argmax of the probabilities, 0.
  * SHARDED runstates: l2z_argmax, l2z_logits_read and l2z_probs_read are COLLECTIVE after greedy steps
  * (l2z_greedy_run) on the peer-write transport -- those steps exchange one argmax candidate per rank instead of
  * gathering the logits, so the first call that needs the whole vector gathers it, and every rank of the group

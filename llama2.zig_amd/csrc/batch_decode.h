@@ -41,11 +41,13 @@ struct BatchAttnArgs {
 };
 hipError_t launch_batch_attention(const BatchAttnArgs &a, int n, hipStream_t st);
 
-// out[b] = argmax of tab->logits[b][0 .. vocab) (main.zig:715-726: strict '>', lowest index wins), one block per row
+// out[b] = argmax of tab->logits[b][0 .. vocab) by argmax_rule.h (main.zig:715-726: what the strict-'>' scan returns,
+// NaN rows included), one block per row
 hipError_t launch_batch_argmax(const BatchTable *tab, int vocab, int *out, int n, hipStream_t st);
 
 // The argmax of lg[0 .. vocab) for a block of 1024 threads, valid in thread 0: each thread scans its indices in
-// increasing order (strict '>' keeps the lowest, :720), the candidates combine by (value, then lower index).
+// increasing order (strict '>' keeps the lowest, :720; a NaN counts only as element 0), the candidates combine by
+// argmax_merge (value, then lower index; the NaN at index 0 above all); no non-NaN value: index 0.
 // s_val / s_idx: 16 entries of LDS each.  Shared by the argmax of the batched step and l2z_sample_batch's rows at
 // temperature 0, which must pick the same token.
 __device__ inline int block_argmax_1024(const float *lg, int vocab, float *s_val, int *s_idx)
@@ -57,7 +59,7 @@ __device__ inline int block_argmax_1024(const float *lg, int vocab, float *s_val
     if ((tid & 63) == 0) { s_val[tid >> 6] = c.v; s_idx[tid >> 6] = c.i; }
     __syncthreads();
     if (tid == 0) argmax_fold_waves(c, s_val, s_idx, 16);
-    return c.i == kNoCandidate ? 0 : c.i;
+    return argmax_token(c);
 }
 
 // l2z_sample_batch (sample_batch.hip): row b draws one token from tab->logits[b] with tab->temperature[b],

@@ -191,7 +191,7 @@ __global__ __launch_bounds__(kBlock) void matvec_kernel(const MatvecArgs a)
         b = s.b_next;
     }
     if (EPI == EPI_ARGMAX) {
-        // block candidate: larger value wins, equal values -> lower index (main.zig:720)
+        // block candidate: larger value wins, equal values -> lower index, the NaN at row 0 above all (argmax_rule.h)
         argmax_wave_fold(best);
         __syncthreads();
         if (lane == 0) {

@@ -113,9 +113,10 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const ArgmaxArgs a)
         if (a.advance) a.out_tokens[*a.pos_ptr] = -1;
         s_next = -1;
     } else if (tid == 0) {
-        // (an index outside the vocabulary can only come from a corrupted exchange -- a solo rank's collapsed epochs, a
-        // peer that died mid-word: never let it address the embedding table)
-        if (bi == kNoCandidate || (unsigned)bi >= (unsigned)a.vocab) bi = 0;
+        // kNanFirst (a NaN in logit 0) and kNoCandidate (no non-NaN logit) are token 0: argmax_rule.h.  (Any other index
+        // outside the vocabulary can only come from a corrupted exchange -- a solo rank's collapsed epochs, a peer that
+        // died mid-word: never let it address the embedding table)
+        if ((unsigned)bi >= (unsigned)a.vocab) bi = 0;
         if (a.epoch_ctl) a.epoch_ctl[0] += a.epoch_add;  // every launch of the pass has read its epoch long ago
         if (a.argmax_out) *a.argmax_out = bi;
         int next = bi;

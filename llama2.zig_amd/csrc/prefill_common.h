@@ -39,6 +39,7 @@ struct GemmArgs {
     float *out;          // [P, ldo]; G_*CACHE: cache base, row = pos0 + token
     const float *res;    // G_RESID: out = res + product ([P, ldres]; the unsharded pass has res == out)
     int P, N, K, ldx, ldo, ldres;
+    int kw;              // short-prompt forms (set by their launcher): the product's own K where the kernel walks K rounded up
     int pos0;            // position of token 0 (RoPE angle, cache row)
     const float2 *rope;  // (seq_len, head_size/2) {cos, sin}
     int head_size;
@@ -235,8 +236,10 @@ __device__ __forceinline__ v16f x3_mfma(const Bf3 &a, const Bf3 &b, v16f acc)
 // Loop bound of a kernel that multiplies whole `granule`-k stages (round 6): the product's K rounded up.  The columns
 // past K are ZEROS in every activation matrix of the batched pass (prefill_host.cpp pf_ld: rows padded to a multiple of
 // 256 floats, >= 768), and whatever follows the row in W -- the next row, the next tensor, the zeroed slack behind the
-// blob (weights.cpp kBlobSlackFloats) -- is finite: the extra products are exact zeros.  -1: the activation rows are
-// not padded that far (a caller that did not come through prefill_host.cpp).
+// blob (weights.cpp kBlobSlackFloats) -- is finite in a sound checkpoint: the extra products are exact zeros.  (A NaN or
+// an infinite weight there makes them NaN.  The short-prompt forms, which every batched, wide, verify and mixed step
+// runs, zero W past the row's end themselves: prefill_skinny.hip PADK; the panel, tile and planes forms rely on finite
+// weights.)  -1: the activation rows are not padded that far (a caller that did not come through prefill_host.cpp).
 inline int pad_k(int K, int granule, int ldx)
 {
     const int ke = (K + granule - 1) / granule * granule;

@@ -12,7 +12,10 @@ namespace {
 //   D: lane l, reg r holds D[i = 4 (l >> 4) + r][j = l & 15]
 // (Rounds 1-5 carried three forms: no LDS, a register-staged LDS form, and the direct-to-LDS ring below, the first two
 // as fallbacks for K that is not whole 256-k stages.  Since round 6 every product runs the ring over K rounded up to
-// whole stages -- at least three -- against zero-padded activation rows: pad_k, prefill_common.h.)
+// whole stages -- at least three -- against zero-padded activation rows: pad_k, prefill_common.h.  Where K is rounded
+// up -- PADK -- the W operand is zeroed past the row's own K columns (a.kw) as it leaves LDS: what stands there is the
+// next rows of W, and 0 x NaN or 0 x inf is a NaN, which put a NaN weight of row r into the outputs of the rows before
+// it: up to 11 of them at K = 64.)
 constexpr int kSkBK = 256;
 
 // The operands are brought in by direct-to-LDS loads through a ring of SW stages.  (The register-staged form of
@@ -39,7 +42,7 @@ constexpr int kSkLD2 = kSkBK + 8;
 // NW = 2: TWO weight matrices share the X stage -- w1 | w3 with silu(a) * b as the epilogue (EPI =
 // G_SWIGLU, main.zig:405-416) or wk | wv into the two caches (EPI = G_QKV, :354-358): X is a third of
 // the bytes brought into the CU instead of half, one launch instead of two.
-template <int EPI, int TMS, int SW, int NW = 1>
+template <int EPI, int TMS, int SW, int NW, bool PADK>
 __global__ __launch_bounds__(kPfBlock) void prefill_skinny_dma(const GemmArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -113,6 +116,10 @@ __global__ __launch_bounds__(kPfBlock) void prefill_skinny_dma(const GemmArgs a)
             v4f b[NW], xa[TMS];
 #pragma unroll
             for (int m = 0; m < NW; m++) b[m] = *(const v4f *)(wr + m * WST + 16 * u);
+            if (PADK && st * kSkBK + 64 * wave + 16 * u + 4 * q >= a.kw) {  // (K is a multiple of 4: a whole float4)
+#pragma unroll
+                for (int m = 0; m < NW; m++) b[m] = zero;
+            }
 #pragma unroll
             for (int tm = 0; tm < TMS; tm++) xa[tm] = *(const v4f *)(xr + 16 * tm * kSkLD2 + 16 * u);
 #pragma unroll
@@ -205,12 +212,15 @@ hipError_t skinny_launch_t(const GemmArgs &a, hipStream_t st)
 {
     static_assert(TMS <= 2, "one or two token tiles (at 64 tokens the stage would take 83 KB)");
     const size_t lds = (size_t)SW * (16 * NW + 16 * TMS) * kSkLD2 * sizeof(float);
-    const void *fn = (const void *)prefill_skinny_dma<EPI, TMS, SW, NW>;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
     GemmArgs args = a;
     args.K = skinny_k(a);
     if (args.K < 0) return hipErrorInvalidValue;
+    args.kw = a.K;
+    // K rounded up: the form that zeroes W past the row's end; whole stages (the 7B widths) run the plain one
+    const void *fn = args.K != a.K ? (const void *)prefill_skinny_dma<EPI, TMS, SW, NW, true>
+                                   : (const void *)prefill_skinny_dma<EPI, TMS, SW, NW, false>;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
     const dim3 g1 = skinny_grid(a, (a.N + 15) / 16, (a.P + 16 * TMS - 1) / (16 * TMS), &args);
     void *params[] = {&args};
     return hipLaunchKernel(fn, g1, dim3(kPfBlock), params, lds, st);

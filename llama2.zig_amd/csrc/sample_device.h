@@ -12,8 +12,11 @@
 //                                              exceeds p; r = coin * cumulative; the first candidate whose cdf exceeds r
 // The f32 sums run in the host's order on one chain (every lane of wave 0 computes it, identically): no tree sum can
 // give the host's bits.  Every sum is kept, and because adding a non-negative float never lowers a sum, "the first
-// index whose sum exceeds t" is then the count of sums <= t -- a parallel count, so the pick needs no second walk.
-// temperature 0: the argmax of the logits, the same code as l2z_argmax_batch.
+// index whose sum exceeds t" is then the count of sums that do NOT exceed t -- a parallel count, so the pick needs no
+// second walk.  Counted as !(sum > t), which holds for a NaN sum too: on all-NaN probabilities (a NaN or a +inf in the
+// logits, or nothing but -inf) no sum exceeds anything, the count is the whole chain, and the pick is the host's last
+// index (:740), where `coin < cdf` never held either.
+// temperature 0: the argmax of the logits, the same code as l2z_argmax_batch (argmax_rule.h).
 #pragma once
 #include "batch_decode.h"
 #include "kernel_common.h"
@@ -214,11 +217,12 @@ __device__ int prefix_walk(SampleLds &L, int len, float t, Val val, float *pre)
     return done;
 }
 
-// how many of pre[0 .. len) are <= t; pre is non-decreasing, so when this is < len it is the first index above t
+// how many of pre[0 .. len) do not exceed t (a NaN sum does not).  pre is non-decreasing, so when this is < len it is the
+// first index above t -- or all NaN (a softmax is NaN everywhere or nowhere), and then this is len
 __device__ int count_le(SampleLds &L, const float *pre, int len, float t)
 {
     unsigned c = 0;
-    for (int j = threadIdx.x; j < len; j += kSbThreads) c += pre[j] <= t ? 1u : 0u;
+    for (int j = threadIdx.x; j < len; j += kSbThreads) c += !(pre[j] > t) ? 1u : 0u;
     return (int)block_reduce_u32(L, c, [](unsigned x, unsigned y) { return x + y; });
 }
 

@@ -12,9 +12,12 @@
 //                         The block whose segment holds the row's target column keeps that logit.
 //   score_finish_kernel   one thread per token row folds the segments' triples in segment order (online log-sum-exp:
 //                         a larger max rescales the running sum) and writes logprob = z[target] - (max + log(sum)), top1.
-// Ties: a later column / lane / wave / segment replaces the running best only when strictly greater, and equal maxima
-// across lanes resolve to the lowest index: l2z_argmax's rule (main.zig:720).  exp is expf, as in block_softmax behind
-// l2z_probs_read.  Compiled with -ffp-contract=off: every sum is a plain f32 add in the order written.
+// Top-1 is l2z_argmax's rule (argmax_rule.h: what the scan of main.zig:715-726 returns).  A later column / lane / wave /
+// segment replaces the running best only when strictly greater, equal maxima across lanes resolve to the lowest index,
+// and a NaN is never greater than anything: the lowest index of the largest non-NaN value, index 0 if there is none.
+// Column 0 of the vocabulary is the scan's first element and wins outright when it is a NaN: the block that owns it
+// leaves kScoreNanFirst as its segment's index, which outlives every fold.  (The max and the sum behind the log-prob skip
+// nothing: a row with a NaN has a NaN log-prob.)  exp is expf, as in block_softmax behind l2z_probs_read.  Compiled with -ffp-contract=off: every sum is a plain f32 add in the order written.
 #include <climits>
 
 #include "kernel_common.h"
@@ -25,6 +28,7 @@ namespace {
 constexpr int kSegWaveCols = kScoreSeg / kWaves;       // 1024 columns per wave
 constexpr int kSegLoads = kSegWaveCols / (4 * kWave);  // four 16-byte loads per lane
 static_assert(kSegLoads * 4 * kWave * kWaves == kScoreSeg, "a segment is whole 16-byte loads of four waves");
+constexpr int kScoreNanFirst = -1;  // part_i of the vocabulary's first segment: column 0 is a NaN, top-1 is 0
 
 __device__ __forceinline__ int wave_min_int(int v)
 {
@@ -57,6 +61,8 @@ __global__ __launch_bounds__(kBlock) void score_reduce_kernel(const ScoreArgs a)
     v4f v[kSegLoads];
 #pragma unroll
     for (int j = 0; j < kSegLoads; j++) v[j] = *(const v4f *)(z + c0 + 4 * (lane + kWave * j));
+    // thread 0 holds the segment's first column in v[0][0]: column 0 of the vocabulary in the first segment of the first slab
+    const bool nan_first = a.col0 + seg * kScoreSeg == 0 && v[0][0] != v[0][0];
     float m = -INFINITY;
     int mi = INT_MAX;
 #pragma unroll
@@ -87,7 +93,7 @@ __global__ __launch_bounds__(kBlock) void score_reduce_kernel(const ScoreArgs a)
     const size_t at = (size_t)row * a.nseg + a.seg0 + seg;
     a.part_m[at] = bm;
     a.part_s[at] = bs;
-    a.part_i[at] = bi == INT_MAX ? 0 : a.col0 + bi;
+    a.part_i[at] = nan_first ? kScoreNanFirst : bi == INT_MAX ? 0 : a.col0 + bi;
     if (a.targets != nullptr) {
         const int t = a.targets[row] - a.col0;   // (no target: -1 - col0 < 0)
         const int end = min((seg + 1) * kScoreSeg, a.n);
@@ -105,6 +111,7 @@ __global__ __launch_bounds__(kBlock) void score_finish_kernel(const ScoreArgs a)
         const size_t at = (size_t)row * a.nseg + g;
         fold(m, s, i, a.part_m[at], a.part_s[at], a.part_i[at]);
     }
+    if (a.part_i[(size_t)row * a.nseg] == kScoreNanFirst) i = 0;
     if (a.out_top1 != nullptr) a.out_top1[row] = i;
     if (a.out_logprob != nullptr) {
         const bool has = a.targets != nullptr && a.targets[row] >= 0;

@@ -77,7 +77,8 @@ __global__ __launch_bounds__(64) void wide_combine(const WideAttnArgs a)
 }
 
 // Block = row, 1024 threads: the copy, and the argmax of what was copied.  A thread takes its elements in increasing
-// index order (strict '>' keeps the lowest index of equal values); the candidates combine by (value, then lower index).
+// index order (strict '>' keeps the lowest index of equal values; a NaN counts only as element 0); the candidates
+// combine by argmax_merge (value, then lower index; the NaN at index 0 above all): argmax_rule.h, NaN rows included.
 __global__ __launch_bounds__(1024) void wide_logits_out(const float *logits, int ld, const WideTable *tab, int vocab, int *next)
 {
     __shared__ float s_val[16];
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(1024) void wide_logits_out(const float *logits, int
     __syncthreads();
     if (tid == 0 && next != nullptr) {
         argmax_fold_waves(cand, s_val, s_idx, 16);
-        next[row] = cand.i == kNoCandidate ? 0 : cand.i;
+        next[row] = argmax_token(cand);
     }
 }
 
