@@ -569,6 +569,49 @@ int l2z_runstate_pages(const l2z_runstate *s, int *n_attached, int32_t *page_ids
 /* give back every page that lies wholly at or above n_pos */
 int l2z_runstate_trim(l2z_runstate *s, int n_pos);
 
+/* ---- decode from int8 group-quantized weights: llama2.c version-2 checkpoints (PREVIEW) ----
+ * The reference has no quantized path, so nothing here is part of the drop-in boundary: ABI version 2, its 31 functions,
+ * the version script, the Zig shim and the CLI are unchanged.
+ * GROUP QUANTIZATION of a vector v, per group of `group_size` (32 or 64) consecutive elements: m = max |v_i|,
+ * s = m / 127.0f (one correctly rounded f32 division), q_i = round(v_i / s) as int8 (the quotient one correctly rounded f32
+ * division, never a multiplication by a reciprocal).  A group with m == 0 -- or with an m so small that s rounds to 0 --
+ * has all q_i = 0.  WEIGHTS round half to even (export.py's torch.round), ACTIVATIONS at run time half away from zero
+ * (runq.c's round: roundf of the f32 quotient).  Non-finite inputs are UNSPECIFIED.
+ * PRODUCT of d rows by n columns: out[i] = sum over groups g of f32(I[i][g]) * ws[i * n / gs + g] * xs[g], with
+ * I[i][g] the exact int32 sum over the group of wq * xq; the f32 sum over groups runs in a fixed order that depends on
+ * n and gs only (the same bits from run to run).
+ * THE PASS is l2z_transformer's with five differences: the embedding row is f32(q) * s of the quantized table's row; the
+ * rmsnorm output that feeds q | k | v is quantized over dim and the three products are quantized; the attention output is
+ * quantized over dim before Wo; the ffn rmsnorm output over dim before W1 and W3 and the SwiGLU output over hidden_dim
+ * before W2; the final rmsnorm output over dim before the classifier, which is the quantized embedding table where the
+ * file shares them.  Everything else -- rmsnorm, RoPE, the head-major KV cache, attention, SwiGLU, the residual adds, the
+ * argmax rule -- is the f32 pass's.
+ * WHO TAKES SUCH WEIGHTS: l2z_transformer, l2z_greedy_begin / _run, l2z_sample_run (prompt positions always step, as under
+ * L2Z_PREFILL=0), l2z_time_kind, l2z_profile_forward, with an unsharded, contiguous runstate; the logits-only calls work
+ * unchanged.  Every other entry point that takes weights -- l2z_prefill, l2z_score, l2z_transformer_batch, the verify
+ * family, l2z_prefill_batch, the wide family, l2z_step_mixed, the emulated-rank hooks, l2z_weights_read -- refuses them with
+ * L2Z_ERR_INVALID before anything is enqueued or changed.  Such weights are unsharded, hold no f32 matrix and no packed
+ * copy.
+ *
+ * l2z_weights_init_q8: `body` is a version-2 file from byte 256 on (the header -- magic 0x616b3432, version 2, the seven
+ * config ints, u8 shared_classifier at 36, i32 group_size at 37 -- is the caller's to parse): f32 rms_att_weight [L, dim],
+ * rms_ffn_weight [L, dim], rms_final_weight [dim], then each quantized tensor as its int8 values followed by its f32
+ * scales: the token embedding, wq, wk, wv, wo, w1, w2, w3 (each layer by layer), wcls unless shared.  L2Z_ERR_INVALID for
+ * a group size other than 32 / 64, dim or hidden_dim no multiple of it, a body shorter than the config needs, a non-null
+ * comm.
+ * l2z_weights_init_q8_from: quantizes an unsharded f32 weights object ON THE DEVICE (the weight rule); the result is
+ * independent of the source.
+ * l2z_weights_q8_read: tensor `tensor_name` ("token_embedding_table", "wq", "wk", "wv", "wo", "w1", "w2", "w3", "wcls") of
+ * `layer` in the FILE's row order: rows * cols int8 into out_q, rows * cols / group_size scales into out_s.
+ * l2z_q8_quantize: the activation rule on its own (n a multiple of gs).  l2z_q8_matmul: the product on its own, through
+ * the kernel body the pass launches (host pointers; xq [n], xs [n / gs], wq [d * n], ws [d * n / gs]). */
+int l2z_weights_init_q8(const l2z_config *config, const void *body, size_t n_bytes, int shared_classifier, int group_size,
+                        const l2z_comm *comm, l2z_weights **out);
+int l2z_weights_init_q8_from(const l2z_weights *w_f32, int group_size, l2z_weights **out);
+int l2z_weights_q8_read(const l2z_weights *w, const char *tensor_name, int layer, int8_t *out_q, float *out_s);
+int l2z_q8_quantize(const float *x, size_t n, int gs, int8_t *out_q, float *out_s);
+int l2z_q8_matmul(float *out, const int8_t *xq, const float *xs, const int8_t *wq, const float *ws, size_t n, size_t d, int gs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -128,6 +128,13 @@ def lib():
                                            C.POINTER(C.c_double)]
     if hasattr(L, "l2z_sample_run"):
         L.l2z_sample_run.argtypes = [cfgp, vp, vp, C.c_int, C.c_float, C.c_float, fp, i32p, ip]
+    if hasattr(L, "l2z_weights_init_q8"):  # int8 group-quantized weights (PREVIEW; include/llama2_hip_test.h)
+        i8p = C.POINTER(C.c_int8)
+        L.l2z_weights_init_q8.argtypes = [cfgp, vp, sz, C.c_int, C.c_int, vp, C.POINTER(vp)]
+        L.l2z_weights_init_q8_from.argtypes = [vp, C.c_int, C.POINTER(vp)]
+        L.l2z_weights_q8_read.argtypes = [vp, C.c_char_p, C.c_int, i8p, fp]
+        L.l2z_q8_quantize.argtypes = [fp, sz, C.c_int, i8p, fp]
+        L.l2z_q8_matmul.argtypes = [fp, i8p, fp, i8p, fp, sz, sz, C.c_int]
     L.l2z_logits_write.argtypes = [vp, fp]
     L.l2z_sample_time.argtypes = [C.c_int, C.POINTER(vp), fp, fp, fp, C.c_int, C.POINTER(C.c_double)]
     L.l2z_greedy_begin.argtypes = [vp, i32p, C.c_int]
@@ -308,6 +315,41 @@ class Weights:
             assert seed is not None
             _chk(lib().l2z_weights_init_synthetic(C.byref(self.cfg), int(shared), seed, ch,
                                                   C.byref(self.h)))
+
+    @classmethod
+    def from_q8(cls, cfg, body, shared: bool, gs: int, *, comm: Comm | None = None) -> "Weights":
+        """int8 group-quantized weights from the body of a llama2.c version-2 checkpoint (the file from byte 256 on:
+        checkpoint.read_checkpoint_v2).  Only the single-sequence decode takes them (l2z_weights_init_q8)."""
+        self = cls.__new__(cls)
+        self.cfg = _cfg(cfg)
+        self.h = C.c_void_p()
+        self.gs = int(gs)
+        b = np.ascontiguousarray(np.asarray(body).view(np.uint8).reshape(-1))
+        _chk(lib().l2z_weights_init_q8(C.byref(self.cfg), b.ctypes.data_as(C.c_void_p), b.size, int(shared), int(gs),
+                                       comm.h if comm is not None else None, C.byref(self.h)))
+        return self
+
+    @classmethod
+    def quantized(cls, w_f32: "Weights", gs: int) -> "Weights":
+        """w_f32 (unsharded f32 weights) quantized ON THE DEVICE by the weight rule; independent of w_f32 afterwards."""
+        self = cls.__new__(cls)
+        self.cfg = w_f32.cfg
+        self.h = C.c_void_p()
+        self.gs = int(gs)
+        _chk(lib().l2z_weights_init_q8_from(w_f32.h, int(gs), C.byref(self.h)))
+        return self
+
+    def q8_read(self, name: str, layer: int = 0):
+        """(q int8 [rows, cols], s f32 [rows, cols // gs]) of one layer of a quantized tensor, in the file's row order."""
+        c = self.cfg
+        kvd = c.dim // c.n_heads * c.n_kv_heads
+        rows, cols = {"token_embedding_table": (c.vocab_size, c.dim), "wcls": (c.vocab_size, c.dim), "wq": (c.dim, c.dim),
+                      "wk": (kvd, c.dim), "wv": (kvd, c.dim), "wo": (c.dim, c.dim), "w1": (c.hidden_dim, c.dim),
+                      "w2": (c.dim, c.hidden_dim), "w3": (c.hidden_dim, c.dim)}[name]
+        q = np.empty((rows, cols), np.int8)
+        s = np.empty((rows, cols // self.gs), np.float32)
+        _chk(lib().l2z_weights_q8_read(self.h, name.encode(), layer, q.ctypes.data_as(C.POINTER(C.c_int8)), _fp(s)))
+        return q, s
 
     def read(self, offset: int, count: int) -> np.ndarray:
         out = np.empty(count, np.float32)
@@ -1476,6 +1518,28 @@ def attention_decode(q, kcache, vcache, pos: int, n_heads: int, n_kv_heads: int,
     out = np.empty(n_heads * head_size, np.float32)
     _chk(lib().l2z_attention_decode(ATTN_FORMS[form], nch, _fp(out), _fp(q), _fp(kcache), _fp(vcache),
                                     pos, n_heads, n_kv_heads, head_size, seq_len))
+    return out
+
+
+def q8_quantize(x, gs: int):
+    """The activation rule of the int8 group quantization on the device: (q int8 [n], s f32 [n // gs])."""
+    x = _f32(x).reshape(-1)
+    q = np.empty(x.size, np.int8)
+    s = np.empty(x.size // gs, np.float32)
+    _chk(lib().l2z_q8_quantize(_fp(x), x.size, gs, q.ctypes.data_as(C.POINTER(C.c_int8)), _fp(s)))
+    return q, s
+
+
+def q8_matmul(xq, xs, wq, ws, gs: int) -> np.ndarray:
+    """The quantized product on its own, through the pass's kernel body: wq [d, n] int8, ws [d, n // gs], xq [n], xs [n // gs]."""
+    wq = np.ascontiguousarray(wq, dtype=np.int8)
+    d, n = wq.shape
+    xq = np.ascontiguousarray(xq, dtype=np.int8).reshape(-1)
+    xs, ws = _f32(xs).reshape(-1), _f32(ws).reshape(-1)
+    assert xq.size == n and xs.size == n // gs and ws.size == d * (n // gs)
+    out = np.empty(d, np.float32)
+    i8p = C.POINTER(C.c_int8)
+    _chk(lib().l2z_q8_matmul(_fp(out), xq.ctypes.data_as(i8p), _fp(xs), wq.ctypes.data_as(i8p), _fp(ws), n, d, gs))
     return out
 
 

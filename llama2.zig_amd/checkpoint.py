@@ -187,3 +187,141 @@ def iter_configs() -> Iterator[tuple[str, Config, bool]]:
     yield "stories110M", STORIES110M, True
     yield "stories42M", STORIES42M, True
     yield "llama2-7b", LLAMA2_7B, False
+
+
+# ---------------------------------------------------------------------------
+# llama2.c "version 2" checkpoints: int8 group-quantized weights
+#
+# 256-byte header, little endian: u32 magic 0x616b3432, i32 version 2, the seven config ints, u8 shared_classifier at
+# byte 36, i32 group_size at byte 37 (unaligned), zero padding.  Body: f32 rms_att_weight [L, dim], rms_ffn_weight
+# [L, dim], rms_final_weight [dim], then every quantized tensor as its int8 values followed by its f32 scales (one per
+# group): the token embedding, wq, wk, wv, wo, w1, w2, w3 (each layer by layer), wcls unless shared.
+V2_MAGIC = 0x616B3432
+V2_HEADER_BYTES = 256
+V2_QUANTIZED = ("token_embedding_table", "wq", "wk", "wv", "wo", "w1", "w2", "w3", "wcls")
+V2_GROUP_SIZES = (32, 64)
+
+
+def quantize_q80(w, gs: int):
+    """Group quantization by the WEIGHT rule: per group of gs consecutive elements s = max|v| / 127 (one f32 division),
+    q = round-half-to-even(v / s) (one f32 division, then np.rint) as int8; a group whose scale is 0 has all q = 0.
+    Returns (q int8 of w's shape, s f32 [w.size // gs]).  Non-finite inputs are unspecified."""
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    assert w.size % gs == 0
+    g = w.reshape(-1, gs)
+    s = (np.abs(g).max(axis=1) / np.float32(127.0)).astype(np.float32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        quot = (g / s[:, None]).astype(np.float32)
+    q = np.where(s[:, None] > 0, np.rint(quot), np.float32(0)).astype(np.int8)
+    return q.reshape(w.shape), s
+
+
+class V2Tensor(NamedTuple):
+    name: str
+    shape: tuple     # (layers, rows, cols)
+    q_offset: int    # bytes from the start of the body
+    s_offset: int
+
+    @property
+    def count(self) -> int:
+        return self.shape[0] * self.shape[1] * self.shape[2]
+
+
+class V2Layout(NamedTuple):
+    gs: int
+    norms: dict      # name -> (byte offset, shape) of the three f32 tensors
+    tensors: dict    # name -> V2Tensor
+    total: int       # bytes of the body
+
+
+def v2_layout(c: Config, shared: bool, gs: int) -> V2Layout:
+    """Byte offsets of everything in a version-2 body (csrc/q8_layout.h computes the same)."""
+    if gs not in V2_GROUP_SIZES:
+        raise ValueError(f"group size {gs}: 32 or 64")
+    if c.dim % gs or c.hidden_dim % gs:
+        raise ValueError(f"dim {c.dim} and hidden_dim {c.hidden_dim} must be multiples of the group size {gs}")
+    L, dim, hid, V, kvd = c.n_layers, c.dim, c.hidden_dim, c.vocab_size, c.kv_dim
+    off = 0
+    norms = {}
+    for name, shape in (("rms_att_weight", (L, dim)), ("rms_ffn_weight", (L, dim)), ("rms_final_weight", (dim,))):
+        norms[name] = (off, shape)
+        off += 4 * int(np.prod(shape))
+    shapes = {"token_embedding_table": (1, V, dim), "wq": (L, dim, dim), "wk": (L, kvd, dim), "wv": (L, kvd, dim),
+              "wo": (L, dim, dim), "w1": (L, hid, dim), "w2": (L, dim, hid), "w3": (L, hid, dim), "wcls": (1, V, dim)}
+    tensors = {}
+    for name in V2_QUANTIZED:
+        if name == "wcls" and shared:
+            continue
+        n = shapes[name][0] * shapes[name][1] * shapes[name][2]
+        tensors[name] = V2Tensor(name, shapes[name], off, off + n)
+        off += n + 4 * (n // gs)
+    return V2Layout(gs, norms, tensors, off)
+
+
+def v2_header(c: Config, shared: bool, gs: int) -> bytes:
+    hdr = struct.pack("<Ii7i", V2_MAGIC, 2, *dataclasses.astuple(c)) + struct.pack("<B", 1 if shared else 0) + struct.pack("<i", gs)
+    return hdr + bytes(V2_HEADER_BYTES - len(hdr))
+
+
+def v2_body_from_f32(c: Config, blob: np.ndarray, shared: bool, gs: int) -> np.ndarray:
+    """The version-2 body (uint8) of an f32 blob in the version-0 order: the norms copied, the matrices quantized."""
+    lay = v2_layout(c, shared, gs)
+    t = carve(c, np.ascontiguousarray(blob, dtype=np.float32), shared)
+    body = np.zeros(lay.total, np.uint8)
+    for name, (off, shape) in lay.norms.items():
+        body[off : off + 4 * int(np.prod(shape))] = np.ascontiguousarray(t[name], dtype="<f4").reshape(-1).view(np.uint8)
+    for name, vt in lay.tensors.items():
+        q, s = quantize_q80(t[name], gs)
+        body[vt.q_offset : vt.q_offset + vt.count] = q.reshape(-1).view(np.uint8)
+        body[vt.s_offset : vt.s_offset + 4 * s.size] = s.astype("<f4").view(np.uint8)
+    return body
+
+
+def v2_carve(c: Config, body: np.ndarray, shared: bool, gs: int) -> dict:
+    """Views into a version-2 body: the three norms as f32 arrays, every quantized tensor as (q int8 [L, rows, cols],
+    s f32 [L, rows, cols // gs]); "wcls" is the embedding table's pair where the file shares them."""
+    lay = v2_layout(c, shared, gs)
+    body = np.asarray(body).view(np.uint8).reshape(-1)
+    if body.size < lay.total:
+        raise ValueError(f"version-2 body too small: {body.size} bytes < {lay.total}")
+    out = {}
+    for name, (off, shape) in lay.norms.items():
+        out[name] = body[off : off + 4 * int(np.prod(shape))].view("<f4").reshape(shape)
+    for name, vt in lay.tensors.items():
+        L, rows, cols = vt.shape
+        out[name] = (body[vt.q_offset : vt.q_offset + vt.count].view(np.int8).reshape(vt.shape),
+                     body[vt.s_offset : vt.s_offset + 4 * (vt.count // gs)].view("<f4").reshape(L, rows, cols // gs))
+    if shared:
+        out["wcls"] = out["token_embedding_table"]
+    return out
+
+
+def write_checkpoint_v2(path, c: Config, body: np.ndarray, shared: bool, gs: int) -> None:
+    lay = v2_layout(c, shared, gs)
+    body = np.asarray(body).view(np.uint8).reshape(-1)
+    assert body.size == lay.total
+    with open(path, "wb") as f:
+        f.write(v2_header(c, shared, gs))
+        f.write(body.tobytes())
+
+
+def read_checkpoint_v2(path, mmap: bool = True):
+    """Returns (Config, shared_classifier, group_size, body[uint8])."""
+    with open(path, "rb") as f:
+        hdr = f.read(V2_HEADER_BYTES)
+    if len(hdr) < V2_HEADER_BYTES:
+        raise ValueError("version-2 checkpoint: header too short")
+    magic, version = struct.unpack_from("<Ii", hdr, 0)
+    if magic != V2_MAGIC or version != 2:
+        raise ValueError(f"not a version-2 checkpoint (magic {magic:#x}, version {version})")
+    c = Config(*struct.unpack_from("<7i", hdr, 8))
+    shared = hdr[36] != 0
+    (gs,) = struct.unpack_from("<i", hdr, 37)
+    lay = v2_layout(c, shared, gs)
+    if mmap:
+        body = np.memmap(path, dtype=np.uint8, mode="r", offset=V2_HEADER_BYTES)
+    else:
+        body = np.fromfile(path, dtype=np.uint8, offset=V2_HEADER_BYTES)
+    if body.size < lay.total:
+        raise ValueError(f"version-2 checkpoint too small: body has {body.size} bytes, config needs {lay.total}")
+    return c, shared, gs, body[: lay.total]

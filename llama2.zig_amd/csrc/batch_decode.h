@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "argmax_rule.h"
+#include "l2z_internal.h"
 
 namespace l2z {
 
@@ -97,6 +98,7 @@ struct SampleStepArgs {
     const float *tok_emb;            // (vocab, dim): next step's embedding row -> x
     float *x;
     int dim;
+    Q8Emb emb_q8;                    // q != null: the embedding table is the quantized one, tok_emb is not read
 };
 hipError_t launch_sample_step(const SampleStepArgs &a, hipStream_t st);
 

@@ -34,9 +34,14 @@ struct Prof {
         }                                                                                 \
     } while (0)
 
-int check_pair(const l2z_config *config, const l2z_runstate *s, const l2z_weights *w, bool paged_ok)
+int check_pair(const l2z_config *config, const l2z_runstate *s, const l2z_weights *w, bool paged_ok, bool q8_ok)
 {
     L2Z_CHECK(config && s && w, L2Z_ERR_INVALID, "null config / runstate / weights");
+    L2Z_CHECK(q8_ok || !w->is_q8(), L2Z_ERR_INVALID,
+              "int8 group-quantized weights (l2z_weights_init_q8) are taken by the single-sequence decode only: "
+              "l2z_transformer, l2z_greedy_run, l2z_sample_run, l2z_time_kind, l2z_profile_forward");
+    L2Z_CHECK(!w->is_q8() || (s->comm == nullptr && s->sh.world == 1), L2Z_ERR_INVALID,
+              "int8 group-quantized weights are unsharded: the runstate belongs to a shard group");
     L2Z_CHECK(paged_ok || s->pool == nullptr, L2Z_ERR_INVALID,
               "a paged runstate (l2z_runstate_init_paged) is taken by the wide family only: l2z_prefill_batch, "
               "l2z_transformer_wide, l2z_wide_run, l2z_verify_wide");
@@ -49,6 +54,119 @@ int check_pair(const l2z_config *config, const l2z_runstate *s, const l2z_weight
               "RunState and Weights were built under different sharding schemes (L2Z_SCHEME_B changed in between)");
     return L2Z_OK;
 }
+
+namespace {
+
+// token / pos from the host + the embedding row of the weights' table, f32 or quantized (main.zig:295-296)
+hipError_t set_state(l2z_runstate *s, const l2z_weights *w, int token, int pos)
+{
+    if (w->is_q8()) return launch_set_state_q8(token, pos, s->d_token, s->d_pos, w->q8_emb(), s->x, s->cfg.dim, s->stream);
+    return launch_set_state(token, pos, s->d_token, s->d_pos, w->tok_emb, s->x, s->cfg.dim, s->stream);
+}
+
+// The pass on int8 group-quantized weights: the same five launches a layer, the classifier and the
+// step's last node, every row mat-vec the q8 kernel -- its prologue quantizes the launch's input per group, after the
+// rmsnorm where the f32 launch has one -- and attention, the epilogues and the hand-over the f32 pass's own.  Unsharded;
+// the one-launch q | k | v + attention form of small models is not taken.
+int enqueue_forward_q8(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *prof, int only_stage, int variant,
+                       int only_kind)
+{
+    L2Z_CHECK(only_stage < 0 && s->sh.world == 1, L2Z_ERR_INVALID, "int8 group-quantized weights: unsharded passes only");
+    const bool with_step = step != STEP_NONE;
+    const bool split = variant == ATTN_SPLIT || variant == ATTN_SPLIT_S;
+    const l2z_config &c = s->cfg;
+    const Shard &sh = s->sh;
+    hipStream_t st = s->stream;
+    const size_t dim = c.dim, hid = c.hidden_dim, kvd = sh.kvd_loc;
+    const int mb = s->max_blocks, gs = w->q8_gs;
+    const size_t gd = dim / gs, gh = hid / gs;   // groups of a row of dim / of hidden_dim values
+    auto kind = [&](int k) { return only_kind < 0 || only_kind == k; };
+    for (int l = 0; l < c.n_layers; l++) {
+        float *kc = s->key_cache + (size_t)l * c.seq_len * kvd;
+        float *vc = s->value_cache + (size_t)l * c.seq_len * kvd;
+        const size_t kvh_stride = (size_t)c.seq_len * sh.hs;
+        if (kind(KIND_QKV)) {   // rmsnorm + quantize, q | k | v, RoPE, KV write
+            Q8MatvecArgs a = {};
+            a.gs = gs;
+            a.q0 = w->q_wq.q + (size_t)l * dim * dim; a.s0 = w->q_wq.s + (size_t)l * dim * gd;
+            a.q1 = w->q_wk.q + (size_t)l * kvd * dim; a.s1 = w->q_wk.s + (size_t)l * kvd * gd;
+            a.q2 = w->q_wv.q + (size_t)l * kvd * dim; a.s2 = w->q_wv.s + (size_t)l * kvd * gd;
+            a.b.out0 = s->q; a.b.out1 = kc; a.b.out2 = vc;
+            a.b.rows0 = c.dim; a.b.rows1 = sh.kvd_loc; a.b.rows2 = sh.kvd_loc;
+            a.b.pos_stride1 = sh.hs; a.b.pos_stride2 = sh.hs; a.b.kv_head_stride = kvh_stride;
+            a.b.n = c.dim; a.b.x = s->x; a.b.rms_w = w->rms_att + (size_t)l * dim;
+            a.b.pos_ptr = s->d_pos; a.b.rope = s->rope; a.b.head_size = sh.hs; a.b.rope_segs = 2;
+            L2Z_LAUNCH(KIND_QKV, launch_q8_matvec(a, EPI_ROPE, mb, g_cus, st));
+        }
+        if (kind(KIND_ATTN)) {   // attention, as the f32 pass launches it
+            AttnArgs a = {};
+            a.q = s->q; a.kcache = kc; a.vcache = vc; a.xb = s->xb;
+            a.pos_ptr = s->d_pos; a.head_size = sh.hs; a.kv_row = sh.hs; a.kv_head = kvh_stride;
+            a.kv_mul = c.n_heads / c.n_kv_heads; a.seq_len = c.seq_len;
+            a.tl_seq = s->tl_attn_seq++;
+            if (split && s->attn_nch > 1 && attention_split_supported(a))
+                L2Z_LAUNCH(KIND_ATTN, launch_attention_split(a, sh.heads_loc, s->attn_nch, s->d_attn_part, s->d_attn_cnt, st,
+                                                             variant == ATTN_SPLIT_S));
+            else
+                L2Z_LAUNCH(KIND_ATTN, launch_attention(a, sh.heads_loc, st, variant == ATTN_SHORT ? 1 : 0));
+        }
+        if (kind(KIND_WO)) {   // quantize, wo, residual
+            Q8MatvecArgs a = {};
+            a.gs = gs;
+            a.q0 = w->q_wo.q + (size_t)l * dim * dim; a.s0 = w->q_wo.s + (size_t)l * dim * gd;
+            a.b.out0 = s->x; a.b.resid = s->x; a.b.rows0 = c.dim; a.b.n = c.dim; a.b.x = s->xb;
+            L2Z_LAUNCH(KIND_WO, launch_q8_matvec(a, EPI_RESID, mb, g_cus, st));
+        }
+        if (kind(KIND_FFN13)) {   // rmsnorm + quantize, w1 | w3, SiLU * mul
+            Q8MatvecArgs a = {};
+            a.gs = gs;
+            a.q0 = w->q_w13.q + (size_t)l * 2 * hid * dim; a.s0 = w->q_w13.s + (size_t)l * 2 * hid * gd;
+            a.b.out0 = s->hb; a.b.rows0 = c.hidden_dim; a.b.rows1 = c.hidden_dim; a.b.n = c.dim; a.b.x = s->x;
+            a.b.rms_w = w->rms_ffn + (size_t)l * dim;
+            L2Z_LAUNCH(KIND_FFN13, launch_q8_matvec(a, EPI_SWIGLU, mb, g_cus, st));
+        }
+        if (kind(KIND_FFN2)) {   // quantize, w2, residual
+            Q8MatvecArgs a = {};
+            a.gs = gs;
+            a.q0 = w->q_w2.q + (size_t)l * dim * hid; a.s0 = w->q_w2.s + (size_t)l * dim * gh;
+            a.b.out0 = s->x; a.b.resid = s->x; a.b.rows0 = c.dim; a.b.n = c.hidden_dim; a.b.x = s->hb;
+            L2Z_LAUNCH(KIND_FFN2, launch_q8_matvec(a, EPI_RESID, mb, g_cus, st));
+        }
+    }
+    if (kind(KIND_CLS)) {   // final rmsnorm + quantize, classifier, one argmax candidate a block
+        Q8MatvecArgs a = {};
+        a.gs = gs;
+        a.q0 = w->q_cls.q; a.s0 = w->q_cls.s;
+        a.b.out0 = s->logits; a.b.rows0 = c.vocab_size; a.b.n = c.dim; a.b.x = s->x; a.b.rms_w = w->rms_final;
+        a.b.part_val = s->d_part_val; a.b.part_idx = s->d_part_idx;
+        int grid = 0;
+        L2Z_LAUNCH(KIND_CLS, launch_q8_matvec(a, EPI_ARGMAX, mb, g_cus, st, &grid));
+        s->n_part = grid;
+        if (only_kind < 0) (with_step ? s->n_part_step : s->n_part_fwd) = s->n_part;
+    }
+    if (step == STEP_GREEDY && kind(KIND_ARGMAX)) {
+        ArgmaxArgs a = {};
+        a.logits = s->logits; a.vocab = c.vocab_size; a.token_ptr = s->d_token;
+        if (s->n_part > 0) { a.part_val = s->d_part_val; a.part_idx = s->d_part_idx; a.n_part = s->n_part; }
+        a.pos_ptr = s->d_pos; a.prompt = s->d_prompt; a.n_prompt_ptr = s->d_n_prompt;
+        a.out_tokens = s->d_out_tokens; a.argmax_out = s->d_argmax; a.emb_q8 = w->q8_emb();
+        a.x = s->x; a.dim = c.dim; a.advance = 1;
+        L2Z_LAUNCH(KIND_ARGMAX, launch_argmax(a, st));
+    }
+    if (step == STEP_SAMPLE && kind(KIND_ARGMAX)) {
+        L2Z_CHECK(s->d_smp_ctl != nullptr && s->d_smp_scratch != nullptr, L2Z_ERR_STATE,
+                  "sampled step on a runstate l2z_sample_run has not prepared");
+        SampleStepArgs a = {};
+        a.logits = s->logits; a.vocab = c.vocab_size; a.seq_len = c.seq_len;
+        a.params = (const SampleStepParams *)s->d_smp_ctl; a.coins = s->d_smp_ctl + 2; a.scratch = s->d_smp_scratch;
+        a.token_ptr = s->d_token; a.pos_ptr = s->d_pos; a.prompt = s->d_prompt; a.n_prompt_ptr = s->d_n_prompt;
+        a.out_tokens = s->d_out_tokens; a.emb_q8 = w->q8_emb(); a.x = s->x; a.dim = c.dim;
+        L2Z_LAUNCH(KIND_ARGMAX, launch_sample_step(a, st));
+    }
+    return L2Z_OK;
+}
+
+}  // namespace
 
 // The forward pass (main.zig:285-430) as 5 launches per layer + classifier
 // (+ the step's last node: argmax or draw, and the hand-over).  Token and pos are read from device memory.
@@ -72,6 +190,7 @@ int check_pair(const l2z_config *config, const l2z_runstate *s, const l2z_weight
 int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *prof,
                     int only_stage, int variant, int only_kind)
 {
+    if (w->is_q8()) return enqueue_forward_q8(s, w, step, prof, only_stage, variant, only_kind);
     const bool with_step = step != STEP_NONE;
     const bool split = variant == ATTN_SPLIT || variant == ATTN_SPLIT_S;
     const l2z_config &c = s->cfg;
@@ -451,13 +570,12 @@ using namespace l2z;
 extern "C" int l2z_transformer(int token, int pos, const l2z_config *config, l2z_runstate *s,
                                const l2z_weights *w)
 {
-    L2Z_TRY(check_pair(config, s, w));
+    L2Z_TRY(check_pair(config, s, w, false, true));
     L2Z_CHECK(token >= 0 && token < config->vocab_size, L2Z_ERR_STATE, "token %d out of range", token);
     L2Z_CHECK(pos >= 0 && pos < config->seq_len, L2Z_ERR_STATE, "pos %d out of range [0,%d)", pos,
               config->seq_len);
     L2Z_HIP(hipSetDevice(s->device));
-    L2Z_HIP(launch_set_state(token, pos, s->d_token, s->d_pos, w->tok_emb, s->x, config->dim,
-                             s->stream));
+    L2Z_HIP(set_state(s, w, token, pos));
     L2Z_TRY(run_forward(s, w, STEP_NONE, pos));
     s->host_pos = pos + 1;
     return L2Z_OK;
@@ -547,8 +665,7 @@ int step_loop(const l2z_config *config, l2z_runstate *s, const l2z_weights *w, i
     if (remaining <= 0) return L2Z_OK;
     if (s->host_pos == 0) {
         // token = 1 (BOS, main.zig:988), pos = 0, x = embedding row of BOS
-        L2Z_HIP(launch_set_state(1, 0, s->d_token, s->d_pos, w->tok_emb, s->x, config->dim,
-                                 s->stream));
+        L2Z_HIP(set_state(s, w, 1, 0));
     }
     const int kChunk = 64;  // host looks for BOS (main.zig:1017) once per chunk
     int produced = 0;
@@ -557,7 +674,7 @@ int step_loop(const l2z_config *config, l2z_runstate *s, const l2z_weights *w, i
     // the loop resumes at pos = n with token = prompt[n-1].  Only when this call covers the whole
     // prompt, no prompt token is BOS (the loop would stop there, :1017) and L2Z_PREFILL != 0.
     const int np = (int)s->h_prompt.size();
-    if (s->host_pos == 0 && np >= kPrefillMinPrompt && remaining >= np && prefill_enabled() &&
+    if (s->host_pos == 0 && np >= kPrefillMinPrompt && remaining >= np && prefill_enabled() && !w->is_q8() &&
         prefill_usable(s) &&
         std::find(s->h_prompt.begin(), s->h_prompt.end(), 1) == s->h_prompt.end()) {
         std::vector<int32_t> in((size_t)np);
@@ -602,7 +719,7 @@ int step_loop(const l2z_config *config, l2z_runstate *s, const l2z_weights *w, i
 extern "C" int l2z_greedy_run(const l2z_config *config, l2z_runstate *s, const l2z_weights *w,
                               int n_steps, int32_t *out_tokens, int *out_n)
 {
-    L2Z_TRY(check_pair(config, s, w));
+    L2Z_TRY(check_pair(config, s, w, false, true));
     L2Z_CHECK(out_tokens && out_n && n_steps >= 0, L2Z_ERR_INVALID, "l2z_greedy_run: bad arguments");
     return step_loop(config, s, w, n_steps, STEP_GREEDY, out_tokens, out_n);
 }
@@ -613,7 +730,7 @@ extern "C" int l2z_sample_run(const l2z_config *config, l2z_runstate *s, const l
 {
     L2Z_TRY(no_device_check());
     L2Z_CHECK(out_tokens && out_n && n_steps >= 0, L2Z_ERR_INVALID, "l2z_sample_run: bad arguments");
-    L2Z_TRY(check_pair(config, s, w));
+    L2Z_TRY(check_pair(config, s, w, false, true));
     L2Z_CHECK(s->comm == nullptr && s->sh.world == 1, L2Z_ERR_INVALID,
               "l2z_sample_run: the runstate is a shard (a shard holds its own rows of the logits only)");
     L2Z_TRY(check_draw("l2z_sample_run", -1, temperature, top_p, coins));  // l2z_sample_batch's rules
@@ -652,14 +769,13 @@ extern "C" int l2z_profile_forward(int token, int pos, const l2z_config *config,
                                    const l2z_weights *w, double *ms_by_kind, int *launches_by_kind,
                                    int n_kinds)
 {
-    L2Z_TRY(check_pair(config, s, w));
+    L2Z_TRY(check_pair(config, s, w, false, true));
     L2Z_CHECK(ms_by_kind && launches_by_kind && n_kinds >= KIND_COUNT, L2Z_ERR_INVALID,
               "l2z_profile_forward: need %d kind slots", (int)KIND_COUNT);
     L2Z_CHECK(token >= 0 && token < config->vocab_size && pos >= 0 && pos < config->seq_len,
               L2Z_ERR_STATE, "token/pos out of range");
     L2Z_HIP(hipSetDevice(s->device));
-    L2Z_HIP(launch_set_state(token, pos, s->d_token, s->d_pos, w->tok_emb, s->x, config->dim,
-                             s->stream));
+    L2Z_HIP(set_state(s, w, token, pos));
     Prof prof;
     int rc = enqueue_forward(s, w, STEP_GREEDY, &prof, -1, attn_variant(s, pos));
     hipError_t e = hipStreamSynchronize(s->stream);
@@ -688,7 +804,7 @@ extern "C" int l2z_profile_forward(int token, int pos, const l2z_config *config,
 extern "C" int l2z_time_kind(int kind, int pos, const l2z_config *config, l2z_runstate *s,
                              const l2z_weights *w, int reps, double *avg_ms_per_launch, int *launches)
 {
-    L2Z_TRY(check_pair(config, s, w));
+    L2Z_TRY(check_pair(config, s, w, false, true));
     L2Z_CHECK(kind >= 0 && kind < KIND_GATHER && avg_ms_per_launch && reps >= 1, L2Z_ERR_INVALID,
               "l2z_time_kind: bad arguments");
     // a shard's launches can be timed on an EMULATED rank (no transport: every input is a plain buffer, nothing waits):
@@ -697,7 +813,7 @@ extern "C" int l2z_time_kind(int kind, int pos, const l2z_config *config, l2z_ru
               "l2z_time_kind: unsharded runstates, emulated or solo ranks only (a connected shard would wait for its peers)");
     L2Z_CHECK(pos >= 0 && pos < config->seq_len, L2Z_ERR_STATE, "pos out of range");
     L2Z_HIP(hipSetDevice(s->device));
-    L2Z_HIP(launch_set_state(1, pos, s->d_token, s->d_pos, w->tok_emb, s->x, config->dim, s->stream));
+    L2Z_HIP(set_state(s, w, 1, pos));
     hipEvent_t e0, e1;
     L2Z_HIP(hipEventCreate(&e0));
     L2Z_HIP(hipEventCreate(&e1));
@@ -712,7 +828,7 @@ extern "C" int l2z_time_kind(int kind, int pos, const l2z_config *config, l2z_ru
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     // the argmax kind advanced pos; put the loop state back
-    hipError_t e2 = launch_set_state(1, pos, s->d_token, s->d_pos, w->tok_emb, s->x, config->dim, s->stream);
+    hipError_t e2 = set_state(s, w, 1, pos);
     if (e2 == hipSuccess) e2 = hipStreamSynchronize(s->stream);
     if (rc != L2Z_OK) return rc;
     L2Z_HIP(e);

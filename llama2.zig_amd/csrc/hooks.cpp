@@ -320,3 +320,46 @@ extern "C" int l2z_prefill_gemm_plan(const l2z_gemm_shape *shape, l2z_gemm_plan 
     memcpy(plan, &p, sizeof p);
     return L2Z_OK;
 }
+
+// ---------------------------------------------------------------------------
+// int8 group quantization: the activation rule on its own, and the product on its own through the
+// forward pass's kernel body (its prologue takes the quantized x as it is)
+extern "C" int l2z_q8_quantize(const float *x, size_t n, int gs, int8_t *out_q, float *out_s)
+{
+    L2Z_CHECK(x && out_q && out_s && n > 0 && n < (1u << 30), L2Z_ERR_INVALID, "l2z_q8_quantize: bad arguments");
+    L2Z_CHECK((gs == 32 || gs == 64) && n % (size_t)gs == 0, L2Z_ERR_INVALID,
+              "l2z_q8_quantize: group size %d (32 or 64, dividing n = %zu)", gs, n);
+    L2Z_TRY(ensure_device(current_device_for(nullptr)));
+    DevBuf dx, dq, ds;
+    L2Z_TRY(dx.alloc(n)); L2Z_TRY(dq.alloc(n / 4)); L2Z_TRY(ds.alloc(n / gs));
+    L2Z_TRY(dx.up(x, n));
+    L2Z_HIP(launch_q8_quantize(dx.p, n, gs, false, (int8_t *)dq.p, ds.p, nullptr));
+    L2Z_HIP(hipDeviceSynchronize());
+    L2Z_HIP(hipMemcpy(out_q, dq.p, n, hipMemcpyDeviceToHost));
+    return ds.down(out_s, n / gs);
+}
+
+extern "C" int l2z_q8_matmul(float *out, const int8_t *xq, const float *xs, const int8_t *wq, const float *ws, size_t n,
+                             size_t d, int gs)
+{
+    L2Z_CHECK(out && xq && xs && wq && ws && n > 0 && d > 0 && n < (1u << 30) && d < (1u << 30), L2Z_ERR_INVALID,
+              "l2z_q8_matmul: bad arguments");
+    L2Z_CHECK((gs == 32 || gs == 64) && n % (size_t)gs == 0, L2Z_ERR_INVALID,
+              "l2z_q8_matmul: group size %d (32 or 64, dividing n = %zu)", gs, n);
+    L2Z_TRY(ensure_device(current_device_for(nullptr)));
+    const size_t ng = n / gs;
+    DevBuf dxq, dxs, dwq, dws, dout;
+    L2Z_TRY(dxq.alloc(n / 4)); L2Z_TRY(dxs.alloc(ng)); L2Z_TRY(dwq.alloc(n * d / 4)); L2Z_TRY(dws.alloc(ng * d));
+    L2Z_TRY(dout.alloc(d));
+    L2Z_HIP(hipMemcpy(dxq.p, xq, n, hipMemcpyHostToDevice));
+    L2Z_HIP(hipMemcpy(dwq.p, wq, n * d, hipMemcpyHostToDevice));
+    L2Z_TRY(dxs.up(xs, ng)); L2Z_TRY(dws.up(ws, ng * d));
+    Q8MatvecArgs a = {};
+    a.gs = gs;
+    a.q0 = (const int8_t *)dwq.p; a.s0 = dws.p;
+    a.xq = (const int8_t *)dxq.p; a.xs = dxs.p;
+    a.b.n = (int)n; a.b.rows0 = (int)d; a.b.out0 = dout.p;
+    L2Z_HIP(launch_q8_matvec(a, EPI_STORE, 8, g_cus, nullptr));
+    L2Z_HIP(hipDeviceSynchronize());
+    return dout.down(out, d);
+}

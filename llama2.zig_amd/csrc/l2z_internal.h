@@ -81,6 +81,14 @@ enum Epilogue { EPI_STORE = 0, EPI_ROPE = 1, EPI_RESID = 2, EPI_SWIGLU = 3, EPI_
 
 constexpr int kMaxSeg = 3;
 
+// The embedding table of int8 group-quantized weights: row r is f32(q[r * dim + i]) * s[(r * dim + i) / gs].
+// q == null: the table is f32 (every kernel that hands an embedding row over takes either)
+struct Q8Emb {
+    const int8_t *q;
+    const float *s;
+    int gs;
+};
+
 // main.zig:715 argmax + main.zig:999-1000,1036 hand-over to the next step
 struct ArgmaxArgs {
     const float *logits;
@@ -97,6 +105,7 @@ struct ArgmaxArgs {
     const float *tok_emb;    // (vocab, dim): next step's embedding row -> x
     float *x;
     int dim;
+    Q8Emb emb_q8;            // q != null: the embedding table is the quantized one, tok_emb is not read
     int advance;             // 1: greedy step (write token/pos/x), 0: argmax only
     int *epoch_ctl;          // this launch closes the pass of a shard group: ctl[kCtlEpoch] += epoch_add (null: not)
     int epoch_add;
@@ -153,6 +162,27 @@ struct MatvecArgs {
     int pk_e, pk_e1, pk_e2;
     int tl_slot;              // measurement builds only (L2Z_TIMELINE): where the launch's blocks leave their stamps
 };
+
+// One mat-vec launch on int8 group-quantized weights (q8_matvec.hip).  b: the shape, the outputs and what
+// the epilogue reads, as the f32 launch's (w0 / w1 / w2, pk*, push and xin are not read); q0 / q1 / q2 and s0 / s1 / s2:
+// the segments' values [rows][n] and scales [rows][n / gs] (EPI_SWIGLU: W1 | W3 row-interleaved, like w0 there).  The
+// prologue quantizes b.x per group of gs -- after the rmsnorm with b.rms_w where that is not null --, or takes an x
+// quantized already (xq != null: n values and n / gs scales on the device; l2z_q8_matmul)
+struct Q8MatvecArgs {
+    MatvecArgs b;
+    const int8_t *q0, *q1, *q2;
+    const float *s0, *s1, *s2;
+    int gs;
+    const int8_t *xq;
+    const float *xs;
+};
+hipError_t launch_q8_matvec(const Q8MatvecArgs &a, int epi, int max_blocks_per_cu, int n_cus, hipStream_t st,
+                            int *out_grid = nullptr);
+// group quantization of count floats (a multiple of gs; src 4-byte aligned) on the device: the weight rule (round half to
+// even) or the activation rule (half away from zero)
+hipError_t launch_q8_quantize(const float *src, size_t count, int gs, bool weight_rule, int8_t *q, float *s, hipStream_t st);
+hipError_t launch_set_state_q8(int token, int pos, int *token_ptr, int *pos_ptr, const Q8Emb &emb, float *x, int dim,
+                               hipStream_t st);
 
 // main.zig:361-389: scores, softmax, att.V for the local heads of one layer
 struct AttnArgs {

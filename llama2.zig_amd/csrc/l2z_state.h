@@ -92,6 +92,20 @@ struct l2z_weights {
         int packed = 0;            // slots with a copy
     };
     PkKind pk[KIND_COUNT];
+    // int8 group-quantized weights (l2z_weights_init_q8 / _q8_from): q8_gs != 0.  Such an object is
+    // unsharded, has no f32 matrix and no packed slot -- blob is null and of the pointers above only rms_att, rms_ffn and
+    // rms_final stand, inside q8_blob: one allocation of the three norm vectors and then, per tensor, its values
+    // [layer][row][col] and its scales [layer][row][col / gs], W1 | W3 row-interleaved in one slot like the f32 layout.
+    // Only the single-sequence decode takes it (check_pair's q8_ok)
+    struct Q8Mat {
+        const int8_t *q = nullptr;
+        const float *s = nullptr;
+    };
+    int q8_gs = 0;
+    uint8_t *q8_blob = nullptr;
+    Q8Mat q_emb, q_wq, q_wk, q_wv, q_wo, q_w13, q_w2, q_cls;   // q_cls: q_emb's where the file shares them
+    bool is_q8() const { return q8_gs != 0; }
+    l2z::Q8Emb q8_emb() const { return l2z::Q8Emb{q_emb.q, q_emb.s, q8_gs}; }
     // slot j of `layer` of a kind, or null where the kind has no copy of it
     const PkMat *pk_slot(int kind, int layer, int j = 0) const
     {
@@ -211,7 +225,10 @@ namespace l2z {
 struct Prof;
 // paged_ok: the entry point takes paged runstates (the wide family); every other one that touches a KV cache through
 // s->key_cache refuses them here with L2Z_ERR_INVALID
-int check_pair(const l2z_config *config, const l2z_runstate *s, const l2z_weights *w, bool paged_ok = false);
+// q8_ok: the entry point takes int8 group-quantized weights (the single-sequence decode: l2z_transformer, the greedy and
+// sampled loops, l2z_time_kind, l2z_profile_forward); every other one refuses them here, before it enqueues anything
+int check_pair(const l2z_config *config, const l2z_runstate *s, const l2z_weights *w, bool paged_ok = false,
+               bool q8_ok = false);
 // attention variant of a position (the host knows pos and replays the graph captured for its variant):
 // 0 short context (256-thread speculative form), 1 one block per head as the shape picks, 2 split with 256
 // threads per block, 3 split with 1024

@@ -2,6 +2,7 @@
 // test hooks (rmsnorm, softmax, dot, weighted row sum) and the synthetic-checkpoint generator.
 #include "argmax_rule.h"
 #include "kernel_common.h"
+#include "q8_device.h"
 
 namespace l2z {
 namespace {
@@ -132,9 +133,23 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const ArgmaxArgs a)
     __syncthreads();
     if (a.advance && s_next >= 0) {
         // next step's embedding row -> x (main.zig:295-296), saves a launch
+        if (a.emb_q8.q != nullptr) {
+            q8_embed_row(a.emb_q8, s_next, a.dim, a.x, tid, blockDim.x);
+            return;
+        }
         const float *row = a.tok_emb + (size_t)s_next * (size_t)a.dim;
         for (int i = tid; i < a.dim; i += blockDim.x) a.x[i] = row[i];
     }
+}
+
+// the same from int8 group-quantized weights: x = f32(q) * s of the table's row
+__global__ void set_state_q8_kernel(int token, int pos, int *token_ptr, int *pos_ptr, const Q8Emb emb, float *x, int dim)
+{
+    if (threadIdx.x == 0) {
+        *token_ptr = token;
+        *pos_ptr = pos;
+    }
+    q8_embed_row(emb, token, dim, x, threadIdx.x, blockDim.x);
 }
 
 // token/pos from the host + embedding copy (main.zig:295-296)
@@ -242,6 +257,13 @@ hipError_t launch_set_state(int token, int pos, int *token_ptr, int *pos_ptr, co
     const int grid = (dim + 255) / 256 > 64 ? 64 : (dim + 255) / 256;
     hipLaunchKernelGGL(set_state_kernel, dim3(grid), dim3(256), 0, st, token, pos, token_ptr,
                        pos_ptr, tok_emb, x, dim);
+    return hipGetLastError();
+}
+
+hipError_t launch_set_state_q8(int token, int pos, int *token_ptr, int *pos_ptr, const Q8Emb &emb, float *x, int dim,
+                               hipStream_t st)
+{
+    hipLaunchKernelGGL(set_state_q8_kernel, dim3(1), dim3(1024), 0, st, token, pos, token_ptr, pos_ptr, emb, x, dim);
     return hipGetLastError();
 }
 

@@ -2,6 +2,7 @@
 // One block of 1024 threads draws the step's token from the runstate's logits with the shared row body (sample_device.h:
 // the token l2z_sample_batch draws from the same logits, temperature, top_p and coin), then hands token, pos and the next
 // embedding row over to the next replay of the step graph.
+#include "q8_device.h"
 #include "sample_device.h"
 
 namespace l2z {
@@ -30,6 +31,10 @@ __global__ __launch_bounds__(kSbThreads) void sample_step_kernel(const SampleSte
     }
     __syncthreads();
     // next step's embedding row -> x (main.zig:295-296)
+    if (a.emb_q8.q != nullptr) {
+        q8_embed_row(a.emb_q8, s_next, a.dim, a.x, tid, kSbThreads);
+        return;
+    }
     const float *row = a.tok_emb + (size_t)s_next * (size_t)a.dim;
     for (int i = tid; i < a.dim; i += kSbThreads) a.x[i] = row[i];
 }
