@@ -612,6 +612,41 @@ int l2z_weights_q8_read(const l2z_weights *w, const char *tensor_name, int layer
 int l2z_q8_quantize(const float *x, size_t n, int gs, int8_t *out_q, float *out_s);
 int l2z_q8_matmul(float *out, const int8_t *xq, const float *xs, const int8_t *wq, const float *ws, size_t n, size_t d, int gs);
 
+/* l2z_q8_matvec_case: ONE launch of the quantized mat-vec as the pass issues it, every argument the caller's; host
+ * pointers, synchronous.  epi: 0 store, 1 RoPE + KV write, 2 residual, 3 SwiGLU, 4 classifier with argmax candidates.
+ * Segments: q0 / s0 [rows0][n] and [rows0][n / gs], likewise q1, q2 (rows1, rows2; 0: unused).  SwiGLU: rows0 == rows1
+ * pairs, q0 / s0 the ONE slot of 2 * rows0 rows with W1 and W3 row-interleaved, out0 [rows0].  Residual and argmax take
+ * one segment.  x in one of three forms: quantized already (xq [n], xs [n / gs]; x and rms_w null), f32 (x [n]), or f32
+ * with the rmsnorm in the kernel (x and rms_w [n]).
+ * out0 / out1 / out2 hold out0_len / out1_len / out2_len floats and are IN and OUT: they are uploaded as they stand, the
+ * launch writes its rows, and everything comes back, so what the launch must not touch can be checked.  RoPE: `rope` is
+ * (pos + 1) * head_size / 2 {cos, sin} pairs, the leading rope_segs segments are rotated, out0 is q [rows0], out1 / out2
+ * are one layer's head-major caches [rows / head_size][seq_len][head_size] (kv_head_stride = seq_len * head_size,
+ * pos_stride = head_size, as the pass sets them); every segment holds whole heads.  Residual: out0 = resid + W.x, resid
+ * [rows0]; in_place != 0: resid is not read, out0 is both (out0 == resid on the device, as the pass's Wo and W2 launches).
+ * Argmax: out0 the logits, part_val / part_idx (room for part_cap) get the `grid` per-block candidates.
+ * max_blocks_per_cu, n_cus: what the launcher sizes its grid from; 0: the pass's own (8, the device's CU count).
+ * grid (out): the blocks launched. */
+typedef struct {
+    int epi, gs, n, rows0, rows1, rows2;
+    const int8_t *q0, *q1, *q2;
+    const float *s0, *s1, *s2;
+    const int8_t *xq;
+    const float *xs, *x, *rms_w;
+    int pos, head_size, rope_segs, seq_len;
+    const float *rope;
+    const float *resid;
+    int in_place;
+    int max_blocks_per_cu, n_cus;
+    float *out0, *out1, *out2;
+    size_t out0_len, out1_len, out2_len;
+    float *part_val;
+    int *part_idx;
+    int part_cap;
+    int grid;
+} l2z_q8_case;
+int l2z_q8_matvec_case(l2z_q8_case *c);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,8 @@ def lib():
         L.l2z_weights_q8_read.argtypes = [vp, C.c_char_p, C.c_int, i8p, fp]
         L.l2z_q8_quantize.argtypes = [fp, sz, C.c_int, i8p, fp]
         L.l2z_q8_matmul.argtypes = [fp, i8p, fp, i8p, fp, sz, sz, C.c_int]
+    if hasattr(L, "l2z_q8_matvec_case"):
+        L.l2z_q8_matvec_case.argtypes = [C.POINTER(Q8Case)]
     L.l2z_logits_write.argtypes = [vp, fp]
     L.l2z_sample_time.argtypes = [C.c_int, C.POINTER(vp), fp, fp, fp, C.c_int, C.POINTER(C.c_double)]
     L.l2z_greedy_begin.argtypes = [vp, i32p, C.c_int]
@@ -1541,6 +1543,93 @@ def q8_matmul(xq, xs, wq, ws, gs: int) -> np.ndarray:
     i8p = C.POINTER(C.c_int8)
     _chk(lib().l2z_q8_matmul(_fp(out), xq.ctypes.data_as(i8p), _fp(xs), wq.ctypes.data_as(i8p), _fp(ws), n, d, gs))
     return out
+
+
+def _q8_case_fields():
+    i8p, fp = C.POINTER(C.c_int8), C.POINTER(C.c_float)
+    return ([(n, C.c_int) for n in ("epi", "gs", "n", "rows0", "rows1", "rows2")] +
+            [(n, i8p) for n in ("q0", "q1", "q2")] + [(n, fp) for n in ("s0", "s1", "s2")] +
+            [("xq", i8p), ("xs", fp), ("x", fp), ("rms_w", fp)] +
+            [(n, C.c_int) for n in ("pos", "head_size", "rope_segs", "seq_len")] +
+            [("rope", fp), ("resid", fp), ("in_place", C.c_int), ("max_blocks_per_cu", C.c_int), ("n_cus", C.c_int)] +
+            [(n, fp) for n in ("out0", "out1", "out2")] + [(n, C.c_size_t) for n in ("out0_len", "out1_len", "out2_len")] +
+            [("part_val", fp), ("part_idx", C.POINTER(C.c_int)), ("part_cap", C.c_int), ("grid", C.c_int)])
+
+
+class Q8Case(C.Structure):
+    """include/llama2_hip_test.h l2z_q8_case."""
+    _fields_ = _q8_case_fields()
+
+
+Q8_EPIS = ("store", "rope", "resid", "swiglu", "argmax")
+
+
+def q8_matvec_case(epi: str, gs: int, segs, *, xq=None, xs=None, x=None, rms_w=None, outs=None, rope=None, pos: int = 0,
+                   head_size: int = 0, rope_segs: int = 0, seq_len: int = 0, resid=None, in_place: bool = False,
+                   max_blocks_per_cu: int = 0, n_cus: int = 0) -> dict:
+    """One launch of the quantized mat-vec as the pass issues it (l2z_q8_matvec_case).  segs: up to three (wq [rows, n] int8,
+    ws [rows, n // gs]); "swiglu": ONE entry, the 2 * pairs rows of W1 | W3 interleaved.  x: (xq, xs), or f32 x, or f32 x
+    with rms_w (the rmsnorm in the kernel).  outs: the output buffers as they stand before the launch (default: zeros of
+    the segments' rows; "rope": q, then the head-major K and V caches [kv heads, seq_len, head_size]); "resid" with in_place:
+    outs[0] is the residual.  rope: [pos + 1, head_size // 2, 2] cos / sin.  Returns {"outs", "grid", "n_pairs"} and, for
+    "argmax", "part_val" / "part_idx" (one candidate a block)."""
+    c = Q8Case()
+    keep = []   # (the arrays the structure points into)
+
+    def ptr(a, dtype, ctype):
+        a = np.ascontiguousarray(a, dtype=dtype)
+        keep.append(a)
+        return a.ctypes.data_as(C.POINTER(ctype))
+
+    c.epi, c.gs = Q8_EPIS.index(epi), gs
+    mats = [(np.ascontiguousarray(q, dtype=np.int8), _f32(s)) for q, s in segs]
+    n = mats[0][0].shape[1]
+    assert 1 <= len(mats) <= 3 and all(q.ndim == 2 and q.shape[1] == n and s.size == q.shape[0] * (n // gs) for q, s in mats)
+    rows = [q.shape[0] for q, _ in mats]
+    if epi == "swiglu":
+        assert len(mats) == 1 and rows[0] % 2 == 0
+        rows = [rows[0] // 2, rows[0] // 2]
+    c.n = n
+    c.rows0, c.rows1, c.rows2 = (rows + [0, 0])[:3]
+    for j, (q, s) in enumerate(mats):
+        setattr(c, f"q{j}", ptr(q, np.int8, C.c_int8))
+        setattr(c, f"s{j}", ptr(s, np.float32, C.c_float))
+    if xq is not None:
+        assert np.size(xq) == n and np.size(xs) == n // gs and x is None and rms_w is None
+        c.xq, c.xs = ptr(xq, np.int8, C.c_int8), ptr(xs, np.float32, C.c_float)
+    else:
+        assert np.size(x) == n and (rms_w is None or np.size(rms_w) == n)
+        c.x = ptr(x, np.float32, C.c_float)
+        if rms_w is not None:
+            c.rms_w = ptr(rms_w, np.float32, C.c_float)
+    n_out = 1 if epi == "swiglu" else len(mats)
+    if outs is None:
+        assert epi != "rope", "rope: pass q and the two caches"
+        outs = [np.zeros(r, np.float32) for r in rows[:n_out]]
+    assert len(outs) == n_out
+    outs = [np.array(o, dtype=np.float32, order="C") for o in outs]   # copies: the launch writes into them
+    for j, o in enumerate(outs):
+        setattr(c, f"out{j}", o.ctypes.data_as(C.POINTER(C.c_float)))
+        setattr(c, f"out{j}_len", o.size)
+    if epi == "rope":
+        rope = _f32(rope)
+        assert rope.size == (pos + 1) * (head_size // 2) * 2
+        c.rope = ptr(rope, np.float32, C.c_float)
+        c.pos, c.head_size, c.rope_segs, c.seq_len = pos, head_size, rope_segs, seq_len
+    if epi == "resid":
+        c.in_place = int(in_place)
+        if not in_place:
+            assert np.size(resid) == rows[0]
+            c.resid = ptr(resid, np.float32, C.c_float)
+    c.max_blocks_per_cu, c.n_cus = max_blocks_per_cu, n_cus
+    part_val, part_idx = np.zeros(8192, np.float32), np.zeros(8192, np.int32)
+    if epi == "argmax":
+        c.part_val, c.part_idx, c.part_cap = _fp(part_val), part_idx.ctypes.data_as(C.POINTER(C.c_int)), part_val.size
+    _chk(lib().l2z_q8_matvec_case(C.byref(c)))
+    res = {"outs": outs, "grid": int(c.grid), "n_pairs": rows[0] if epi == "swiglu" else (sum(rows) + 1) // 2}
+    if epi == "argmax":
+        res["part_val"], res["part_idx"] = part_val[: c.grid].copy(), part_idx[: c.grid].copy()
+    return res
 
 
 def rccl_info() -> dict:

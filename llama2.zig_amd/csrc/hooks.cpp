@@ -8,6 +8,9 @@
 //                                   the GENERIC attention kernel's device functions (block_softmax,
 //                                   attn_scores, attn_weighted_sum) -- the forms the stories / 7B
 //                                   shapes run are covered by l2z_attention_decode instead
+//   l2z_q8_quantize, l2z_q8_matmul, l2z_q8_matvec_case
+//                                   launch_q8_quantize / launch_q8_matvec: the int8 pass's own kernels, the last with
+//                                   every argument of the launch the caller's
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -362,4 +365,136 @@ extern "C" int l2z_q8_matmul(float *out, const int8_t *xq, const float *xs, cons
     L2Z_HIP(launch_q8_matvec(a, EPI_STORE, 8, g_cus, nullptr));
     L2Z_HIP(hipDeviceSynchronize());
     return dout.down(out, d);
+}
+
+// One launch of the q8 mat-vec as the pass issues it, every argument the caller's (include/llama2_hip_test.h): the
+// epilogue, up to three segments, x in any of its three forms, the RoPE table and the head-major caches, the residual in
+// place or not, and the two numbers the launcher sizes its grid from.  Goes through launch_q8_matvec as it stands.
+namespace {
+struct DevBytes {
+    void *p = nullptr;
+    ~DevBytes() { if (p) (void)hipFree(p); }
+    int up(const void *h, size_t bytes)
+    {
+        L2Z_HIP(hipMalloc(&p, bytes ? bytes : 1));
+        if (h != nullptr && bytes > 0) L2Z_HIP(hipMemcpy(p, h, bytes, hipMemcpyHostToDevice));
+        return L2Z_OK;
+    }
+};
+}  // namespace
+
+extern "C" int l2z_q8_matvec_case(l2z_q8_case *c)
+{
+    L2Z_CHECK(c != nullptr, L2Z_ERR_INVALID, "l2z_q8_matvec_case: null argument");
+    const int epi = c->epi, gs = c->gs, n = c->n;
+    L2Z_CHECK(epi >= EPI_STORE && epi <= EPI_ARGMAX, L2Z_ERR_INVALID, "l2z_q8_matvec_case: epilogue %d", epi);
+    L2Z_CHECK((gs == 32 || gs == 64) && n > 0 && n < (1 << 24) && n % gs == 0, L2Z_ERR_INVALID,
+              "l2z_q8_matvec_case: group size %d (32 or 64, dividing n = %d)", gs, n);
+    const int rows[3] = {c->rows0, c->rows1, c->rows2};
+    L2Z_CHECK(rows[0] > 0 && rows[1] >= 0 && rows[2] >= 0 && rows[0] < (1 << 22) && rows[1] < (1 << 22) && rows[2] < (1 << 22) &&
+                  (rows[1] > 0 || rows[2] == 0),
+              L2Z_ERR_INVALID, "l2z_q8_matvec_case: rows %d, %d, %d", rows[0], rows[1], rows[2]);
+    L2Z_CHECK(epi != EPI_SWIGLU || (rows[1] == rows[0] && rows[2] == 0), L2Z_ERR_INVALID,
+              "l2z_q8_matvec_case: swiglu takes rows0 == rows1 pairs of one interleaved slot");
+    L2Z_CHECK((epi != EPI_RESID && epi != EPI_ARGMAX) || (rows[1] == 0 && rows[2] == 0), L2Z_ERR_INVALID,
+              "l2z_q8_matvec_case: resid and argmax take one segment");
+    L2Z_CHECK(c->max_blocks_per_cu >= 0 && c->max_blocks_per_cu <= 8 && c->n_cus >= 0 && c->n_cus <= 4096, L2Z_ERR_INVALID,
+              "l2z_q8_matvec_case: max_blocks_per_cu %d (0 .. 8), n_cus %d (0 .. 4096)", c->max_blocks_per_cu, c->n_cus);
+    // the segments the launch reads (swiglu: one slot of 2 * rows0 interleaved rows), and x in exactly one form
+    const int8_t *hq[3] = {c->q0, c->q1, c->q2};
+    const float *hs[3] = {c->s0, c->s1, c->s2};
+    const int n_seg = epi == EPI_SWIGLU ? 1 : (rows[2] > 0 ? 3 : (rows[1] > 0 ? 2 : 1));
+    for (int j = 0; j < n_seg; j++)
+        L2Z_CHECK(hq[j] != nullptr && hs[j] != nullptr, L2Z_ERR_INVALID, "l2z_q8_matvec_case: segment %d is null", j);
+    const bool quantized = c->xq != nullptr;
+    L2Z_CHECK(quantized ? (c->xs != nullptr && c->x == nullptr && c->rms_w == nullptr) : c->x != nullptr, L2Z_ERR_INVALID,
+              "l2z_q8_matvec_case: x comes quantized (xq, xs) or as f32 (x, with or without rms_w)");
+    // the outputs: in and out, so that what the launch must not touch can be checked
+    float *ho[3] = {c->out0, c->out1, c->out2};
+    const size_t olen[3] = {c->out0_len, c->out1_len, c->out2_len};
+    const int n_out = epi == EPI_SWIGLU ? 1 : n_seg;
+    size_t kv_head_stride = 0;
+    if (epi == EPI_ROPE) {
+        const int hsz = c->head_size;
+        L2Z_CHECK(hsz > 0 && hsz % 2 == 0 && c->seq_len > 0 && c->pos >= 0 && c->pos < c->seq_len && c->rope != nullptr &&
+                      c->rope_segs >= 0 && c->rope_segs <= 3,
+                  L2Z_ERR_INVALID, "l2z_q8_matvec_case: rope: head_size %d, pos %d of seq_len %d, rope_segs %d", hsz, c->pos,
+                  c->seq_len, c->rope_segs);
+        // a pair (i, i + 1) never straddles two segments or two heads
+        L2Z_CHECK(rows[0] % hsz == 0 && rows[1] % hsz == 0 && rows[2] % hsz == 0, L2Z_ERR_INVALID,
+                  "l2z_q8_matvec_case: rope: every segment holds whole heads of %d rows", hsz);
+        kv_head_stride = (size_t)c->seq_len * hsz;
+    }
+    for (int j = 0; j < n_out; j++) {
+        size_t need = (size_t)rows[j];
+        if (epi == EPI_ROPE && j > 0) need = (size_t)(rows[j] / c->head_size) * kv_head_stride;
+        L2Z_CHECK(ho[j] != nullptr && olen[j] >= need, L2Z_ERR_INVALID, "l2z_q8_matvec_case: out%d holds %zu floats, the launch needs %zu",
+                  j, olen[j], need);
+    }
+    L2Z_CHECK(epi != EPI_RESID || c->in_place || c->resid != nullptr, L2Z_ERR_INVALID, "l2z_q8_matvec_case: resid is null");
+    L2Z_CHECK(epi != EPI_ARGMAX || (c->part_val != nullptr && c->part_idx != nullptr && c->part_cap > 0), L2Z_ERR_INVALID,
+              "l2z_q8_matvec_case: argmax needs part_val / part_idx");
+    L2Z_TRY(ensure_device(current_device_for(nullptr)));
+    const int n_cus = c->n_cus > 0 ? c->n_cus : g_cus;
+    const int mb = c->max_blocks_per_cu > 0 ? c->max_blocks_per_cu : Tunables::max_blocks_per_cu;
+    const size_t ng = (size_t)n / gs;
+
+    DevBytes dq[3], ds[3], dxq, dxs, dx, drms, dout[3], dresid, drope, dpos, dpv, dpi;
+    Q8MatvecArgs a = {};
+    a.gs = gs;
+    for (int j = 0; j < n_seg; j++) {
+        const size_t r = epi == EPI_SWIGLU ? 2 * (size_t)rows[0] : (size_t)rows[j];
+        L2Z_TRY(dq[j].up(hq[j], r * (size_t)n));
+        L2Z_TRY(ds[j].up(hs[j], r * ng * sizeof(float)));
+    }
+    a.q0 = (const int8_t *)dq[0].p; a.q1 = (const int8_t *)dq[1].p; a.q2 = (const int8_t *)dq[2].p;
+    a.s0 = (const float *)ds[0].p; a.s1 = (const float *)ds[1].p; a.s2 = (const float *)ds[2].p;
+    if (quantized) {
+        L2Z_TRY(dxq.up(c->xq, (size_t)n));
+        L2Z_TRY(dxs.up(c->xs, ng * sizeof(float)));
+        a.xq = (const int8_t *)dxq.p; a.xs = (const float *)dxs.p;
+    } else {
+        L2Z_TRY(dx.up(c->x, (size_t)n * sizeof(float)));
+        a.b.x = (const float *)dx.p;
+        if (c->rms_w != nullptr) {
+            L2Z_TRY(drms.up(c->rms_w, (size_t)n * sizeof(float)));
+            a.b.rms_w = (const float *)drms.p;
+        }
+    }
+    for (int j = 0; j < n_out; j++) L2Z_TRY(dout[j].up(ho[j], olen[j] * sizeof(float)));
+    a.b.out0 = (float *)dout[0].p; a.b.out1 = (float *)dout[1].p; a.b.out2 = (float *)dout[2].p;
+    a.b.rows0 = rows[0]; a.b.rows1 = rows[1]; a.b.rows2 = rows[2];
+    a.b.n = n;
+    if (epi == EPI_ROPE) {   // as enqueue_forward_q8's q | k | v launch
+        L2Z_TRY(drope.up(c->rope, (size_t)(c->pos + 1) * (size_t)(c->head_size / 2) * sizeof(float2)));
+        L2Z_TRY(dpos.up(&c->pos, sizeof(int)));
+        a.b.rope = (const float2 *)drope.p; a.b.pos_ptr = (const int *)dpos.p;
+        a.b.head_size = c->head_size; a.b.rope_segs = c->rope_segs;
+        a.b.pos_stride1 = c->head_size; a.b.pos_stride2 = c->head_size; a.b.kv_head_stride = kv_head_stride;
+    }
+    if (epi == EPI_RESID) {
+        if (c->in_place) {   // out0 == resid, as the pass's Wo and W2 launches: the buffer starts as the residual
+            a.b.resid = a.b.out0;
+        } else {
+            L2Z_TRY(dresid.up(c->resid, (size_t)rows[0] * sizeof(float)));
+            a.b.resid = (const float *)dresid.p;
+        }
+    }
+    if (epi == EPI_ARGMAX) {
+        const size_t room = (size_t)matvec_max_grid(n_cus);   // the launcher never launches more blocks
+        L2Z_TRY(dpv.up(nullptr, room * sizeof(float)));
+        L2Z_TRY(dpi.up(nullptr, room * sizeof(int)));
+        a.b.part_val = (float *)dpv.p; a.b.part_idx = (int *)dpi.p;
+    }
+    int grid = 0;
+    L2Z_HIP(launch_q8_matvec(a, epi, mb, n_cus, nullptr, &grid));
+    L2Z_HIP(hipDeviceSynchronize());
+    c->grid = grid;
+    for (int j = 0; j < n_out; j++) L2Z_HIP(hipMemcpy(ho[j], dout[j].p, olen[j] * sizeof(float), hipMemcpyDeviceToHost));
+    if (epi == EPI_ARGMAX) {
+        L2Z_CHECK(grid <= c->part_cap, L2Z_ERR_INVALID, "l2z_q8_matvec_case: %d candidates, room for %d", grid, c->part_cap);
+        L2Z_HIP(hipMemcpy(c->part_val, dpv.p, (size_t)grid * sizeof(float), hipMemcpyDeviceToHost));
+        L2Z_HIP(hipMemcpy(c->part_idx, dpi.p, (size_t)grid * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    return L2Z_OK;
 }

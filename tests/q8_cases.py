@@ -13,8 +13,11 @@ SHAPES = {
     "64": (64, 192, 2, 4, 2, 512, 32, 32),
     "288": (288, 768, 3, 6, 6, 1024, 32, 32),
     "512": (512, 1408, 4, 8, 8, 512, 24, 64),
+    # both loops of the kernel in the real pass: W2 rows of 4224 columns are 1.03 batches of 4096, and the classifier's
+    # 10000 pairs are more than the resident waves, so a wave takes several pairs and hands over several candidates
+    "tall": (64, 4224, 1, 2, 1, 20000, 16, 64),
 }
-SEEDS = {"64": 59, "288": 24, "512": 121}   # (picked for the largest distance of any activation quotient to a rounding boundary)
+SEEDS = {"64": 59, "288": 24, "512": 121, "tall": 799}   # (picked for the largest distance of any activation quotient to a rounding boundary; "tall": 6.6e-5 of a step, the best of seeds 0 .. 999)
 N_POS = 12
 
 # The project's parity bar, elementwise: |got - ref| <= 5e-5 + 5e-5 |ref|.  And the LOOSE bar of the one position in

@@ -184,8 +184,11 @@ def test_greedy_run_emits_the_ids_of_the_reference(gpu):
     s.close(); w.close()
 
 
-def test_greedy_run_is_the_stepped_loop_bit_for_bit(gpu):
-    cfg, gs, _, body = q8_cases.model("288")
+@pytest.mark.parametrize("name", ["288", "tall"])
+def test_greedy_run_is_the_stepped_loop_bit_for_bit(gpu, name):
+    """("tall": the classifier's waves take several pairs each, so the loop's hand-over from several candidates a wave is
+    held to s.argmax().)"""
+    cfg, gs, _, body = q8_cases.model(name)
     w = gpu.Weights.from_q8(cfg, body, True, gs)
     runs = []
     for _ in range(2):

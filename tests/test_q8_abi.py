@@ -10,7 +10,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 NAMES = {"l2z_weights_init_q8": 7, "l2z_weights_init_q8_from": 3, "l2z_weights_q8_read": 5, "l2z_q8_quantize": 5,
-         "l2z_q8_matmul": 8}
+         "l2z_q8_matmul": 8, "l2z_q8_matvec_case": 1}
 
 
 def exported(path):
@@ -50,7 +50,7 @@ def test_binding_has_the_q8_wrappers(B, ck):
         at = getattr(B.lib(), name).argtypes
         assert at is not None and len(at) == n_params, name
     assert callable(B.Weights.from_q8) and callable(B.Weights.quantized) and callable(B.Weights.q8_read)
-    assert callable(B.q8_quantize) and callable(B.q8_matmul)
+    assert callable(B.q8_quantize) and callable(B.q8_matmul) and callable(B.q8_matvec_case)
     for fn in ("quantize_q80", "v2_layout", "write_checkpoint_v2", "read_checkpoint_v2"):
         assert callable(getattr(ck, fn))
 
@@ -81,6 +81,11 @@ print(L.l2z_weights_init_q8(C.byref(cfg), body.ctypes.data_as(C.c_void_p), body.
 print(L.l2z_weights_init_q8(C.byref(cfg), body.ctypes.data_as(C.c_void_p), body.size - 1, 1, 32, None, C.byref(h)))
 print(L.l2z_weights_init_q8_from(None, 32, C.byref(h)))
 print(L.l2z_weights_q8_read(None, b"wq", 0, q.ctypes.data_as(i8p), s.ctypes.data_as(fp)))
+case = B.Q8Case(epi=0, gs=32, n=32, rows0=1, q0=q.ctypes.data_as(i8p), s0=s.ctypes.data_as(fp), xq=q.ctypes.data_as(i8p),
+                xs=s.ctypes.data_as(fp), out0=out.ctypes.data_as(fp), out0_len=1)
+print(L.l2z_q8_matvec_case(C.byref(case)))
+case.gs = 48
+print(L.l2z_q8_matvec_case(C.byref(case)))
 """
 
 
@@ -90,4 +95,4 @@ def test_q8_calls_without_a_device_return_no_device(B):
     out = subprocess.run([sys.executable, "-c", _CHILD, ROOT], check=True, capture_output=True, text=True, env=env,
                          timeout=120).stdout
     nd, inv = str(B.ERR_NO_DEVICE), str(B.ERR_INVALID)
-    assert out.split() == [nd, nd, nd, inv, inv, inv, inv], out
+    assert out.split() == [nd, nd, nd, inv, inv, inv, inv, nd, inv], out

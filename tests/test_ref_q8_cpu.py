@@ -10,6 +10,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import q8_cases  # noqa: E402
+import q8_kernel_cases  # noqa: E402
 import ref_q8  # noqa: E402
 
 f32 = np.float32
@@ -71,3 +72,28 @@ def test_matvec_modes_on_a_hand_computed_product():
     want = [96 * 0.5 * 2 - 64 * 0.25 * 4, -12192 * 1.0 * 2 + 4064 * 2.0 * 4]
     assert ref_q8.matvec(wq, ws, xq, xs, 32, "f64").tolist() == want
     assert ref_q8.matvec(wq, ws, xq, xs, 32, "f32").tolist() == want
+
+
+@pytest.mark.parametrize("n,gs,norm", q8_kernel_cases.PROLOGUE_CASES)
+def test_the_fused_prologues_inputs_keep_their_margin(n, gs, norm):
+    """tests/test_gpu_q8_kernel.py's tight prologue test relies on it: the sum of squares is exact in f32 in any order, and
+    with the norm every quotient of the reference lies at least 2^-10 from a rounding boundary -- a device factor a few
+    ulp off moves a quotient of at most 127 by under 2^-15 --, so the reference's integers are the only correct ones."""
+    x, rms_w, wq, ws = q8_kernel_cases.prologue_case(n, gs, norm)
+    k = x.astype(np.float64) * 8
+    assert np.array_equal(k, np.round(k)) and np.abs(k).max() <= 16
+    exact = float(np.sum(x.astype(np.float64) ** 2))
+    assert exact * 64 < 2 ** 24   # in units of 2^-6: every partial sum is an integer below 2^24
+    rng = np.random.default_rng(n)
+    for order in (np.arange(n), np.arange(n)[::-1], rng.permutation(n)):   # any order of the f32 sum gives it
+        assert float(np.cumsum((x[order] * x[order]).astype(f32), dtype=f32)[-1]) == exact
+    xq, xs, margin, terms = q8_kernel_cases.prologue_reference(n, gs, norm)
+    print(f"n {n} gs {gs} norm {norm}: smallest distance of a quotient to a boundary {margin:.3e}")
+    assert (xs > 0).all() and np.abs(xq).reshape(-1, gs).max(axis=1).min() == 127 and terms.shape == (wq.shape[0], n // gs)
+    if norm:
+        assert margin >= q8_kernel_cases.MARGIN
+        # ... and a factor 8 ulp off either way quantizes to the same integers
+        v = x.astype(np.float64) * (1.0 / np.sqrt(exact / n + 1e-5))
+        for off in (1 - 2.0 ** -21, 1 + 2.0 ** -21):
+            q2, s2 = ref_q8.quantize_act(((v * off) * rms_w.astype(np.float64)).astype(f32), gs)
+            assert np.array_equal(q2, xq)
