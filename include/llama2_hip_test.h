@@ -45,6 +45,11 @@ int l2z_weights_packed_read(const l2z_weights *w, int layer, float *out, size_t 
  * odd number of rows is a candidate that stays f32.  Kinds without a packed form report (0, 0). */
 int l2z_weights_packed_count_kind(const l2z_weights *w, int kind, int *n_packed, int *n_candidates);
 int l2z_weights_packed_read_kind(const l2z_weights *w, int kind, int layer, int slot, float *out, size_t n_floats);
+/* The bits a value that slot was packed at: 28 (rows of exactly 4096 values whose pairs have at most eight values below the
+ * 4-bit exponent window, each carried in the pair's patch record; L2Z_PACKED_BITS=28, the default), 29, or 0 where the slot
+ * has no packed copy.  The q|k|v slots of a layer report one form: 28 only if all three take it.  Both read calls above
+ * decode either form. */
+int l2z_weights_packed_bits_kind(const l2z_weights *w, int kind, int layer, int slot, int *bits);
 
 /* copy a named RunState buffer to the host: "x","xb","hb","q","att","logits",
  * "key_cache","value_cache" (tests only) */

@@ -329,9 +329,9 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *
             a.pos_ptr = s->d_pos; a.rope = s->rope; a.head_size = sh.hs; a.rope_segs = 2;
             const auto *pq = pk_slot(KIND_QKV, l, 0), *pkk = pk_slot(KIND_QKV, l, 1), *pv = pk_slot(KIND_QKV, l, 2);
             if (pq && pkk && pv) {  // all three slots or none
-                a.pk = pq->p; a.pk_e = pq->e;
-                a.pk1 = pkk->p; a.pk_e1 = pkk->e;
-                a.pk2 = pv->p; a.pk_e2 = pv->e;
+                a.pk = pq->p; a.pk_e = pq->e; a.pk_rec = pq->rec;
+                a.pk1 = pkk->p; a.pk_e1 = pkk->e; a.pk_rec1 = pkk->rec;
+                a.pk2 = pv->p; a.pk_e2 = pv->e; a.pk_rec2 = pv->rec;
             }
             L2Z_LAUNCH(KIND_QKV, launch_matvec(a, PRO_RMS, EPI_ROPE, mb, g_cus, st));
         }
@@ -365,7 +365,7 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *
                 a.rows0 = sh.dim_loc; a.n = c.dim;
                 x_in(a, s->xb, gi, sh.dim_loc);
                 push_to(a, 1);
-                if (const auto *p = pk_slot(KIND_WO, l)) { a.pk = p->p; a.pk_e = p->e; }
+                if (const auto *p = pk_slot(KIND_WO, l)) { a.pk = p->p; a.pk_e = p->e; a.pk_rec = p->rec; }
             }
             L2Z_LAUNCH(KIND_WO, launch_matvec(a, PRO_NONE, epi, mb, g_cus, st, nullptr, &pushed));
         }
@@ -380,7 +380,7 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *
             a.rms_w = w->rms_ffn + (size_t)l * dim;
             x_in(a, s->x, gi, sh.dim_loc);
             if (!sb) push_to(a, 2);
-            if (const auto *p = pk_slot(KIND_FFN13, l)) { a.pk = p->p; a.pk_e = p->e; }
+            if (const auto *p = pk_slot(KIND_FFN13, l)) { a.pk = p->p; a.pk_e = p->e; a.pk_rec = p->rec; }
             L2Z_LAUNCH(KIND_FFN13, launch_matvec(a, PRO_RMS, EPI_SWIGLU, mb, g_cus, st, nullptr, &pushed));
         }
         if (!sb) L2Z_TRY(gather(s->hb, sh.hid_loc));
@@ -395,7 +395,7 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *
                 a.rows0 = sh.dim_loc; a.n = c.hidden_dim;
                 x_in(a, s->hb, gi, sh.hid_loc);
                 push_to(a, 1);
-                if (const auto *p = pk_slot(KIND_FFN2, l)) { a.pk = p->p; a.pk_e = p->e; }
+                if (const auto *p = pk_slot(KIND_FFN2, l)) { a.pk = p->p; a.pk_e = p->e; a.pk_rec = p->rec; }
             }
             L2Z_LAUNCH(KIND_FFN2, launch_matvec(a, PRO_NONE, epi, mb, g_cus, st, nullptr, &pushed));
         }
@@ -414,7 +414,7 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *
                           matvec_vector_width(c.dim);
         int grid = 0;
         if (!xchg) push_to(a, 3);
-        if (const auto *p = fuse ? pk_slot(KIND_CLS, 0) : nullptr) { a.pk = p->p; a.pk_e = p->e; }
+        if (const auto *p = fuse ? pk_slot(KIND_CLS, 0) : nullptr) { a.pk = p->p; a.pk_e = p->e; a.pk_rec = p->rec; }
         L2Z_LAUNCH(KIND_CLS, launch_matvec(a, PRO_RMS, fuse ? EPI_ARGMAX : EPI_STORE, mb, g_cus, st,
                                            &grid, &pushed));
         s->n_part = fuse ? grid : 0;

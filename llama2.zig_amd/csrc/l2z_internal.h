@@ -160,6 +160,9 @@ struct MatvecArgs {
     // pk_e1 / pk_e2: every slot has its own base exponent; all three or none).  Unsharded weights only
     const uint32_t *pk, *pk1, *pk2;
     int pk_e, pk_e1, pk_e2;
+    // pk_rec != null: pk is the 28-bit form (n == 4096 only) and pk_rec its patch records, one of 16 dwords per pair
+    // (packed_w.h pk28); with three segments all three slots are 28-bit or none is
+    const uint32_t *pk_rec, *pk_rec1, *pk_rec2;
     int tl_slot;              // measurement builds only (L2Z_TIMELINE): where the launch's blocks leave their stamps
 };
 
@@ -229,6 +232,11 @@ hipError_t launch_fused_qkv_attn(const FusedQkvAttnArgs &a, int n_heads, hipStre
 hipError_t launch_pk_stats(const float *m, size_t count, uint32_t *stats, hipStream_t st);
 hipError_t launch_pk_pack(const float *m, int rows, int n, int e_base, uint32_t *pk, hipStream_t st);
 hipError_t launch_pk_unpack(const uint32_t *pk, int rows, int n, int e_base, float *out, hipStream_t st);
+// ... and the 28-bit form of rows of n == 4096 (pk28): the most escapes any pair has (max_esc preset 0), the packing (pk:
+// (rows / 2) * pk28::kPairDw dwords, rec: (rows / 2) * pk28::kRecDw dwords, 64-byte aligned) and the decode
+hipError_t launch_pk28_count(const float *m, int rows, int n, int e_base, uint32_t *max_esc, hipStream_t st);
+hipError_t launch_pk28_pack(const float *m, int rows, int n, int e_base, uint32_t *pk, uint32_t *rec, hipStream_t st);
+hipError_t launch_pk28_unpack(const uint32_t *pk, const uint32_t *rec, int rows, int n, int e_base, float *out, hipStream_t st);
 hipError_t launch_matvec(const MatvecArgs &a, int pro, int epi, int max_blocks_per_cu, int n_cus,
                          hipStream_t st, int *out_grid = nullptr, bool *pushed = nullptr);
 // true if launch_attention / launch_attention_split will honour a.push (vector kernels only)

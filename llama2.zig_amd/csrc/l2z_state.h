@@ -82,6 +82,10 @@ struct l2z_weights {
     struct PkMat {
         const uint32_t *p = nullptr;
         int e = 0;          // base exponent E
+        // the 28-bit form (pk28: rows of n == 4096 whose pairs have at most eight escapes; L2Z_PACKED_BITS): p is its
+        // stream and rec the patch records, 16 dwords per pair; null: p is the 29-bit form
+        const uint32_t *rec = nullptr;
+        int bits() const { return p == nullptr ? 0 : rec != nullptr ? 28 : 29; }
         const float *src = nullptr;  // the f32 rows it stands for
         int rows = 0, cols = 0;
     };

@@ -353,6 +353,86 @@ struct RowPacked {
     }
 };
 
+// The 28-bit form (packed_w.h pk28) of a pair whose rows are exactly one batch (XC == 4): the same two fixed sets, seven
+// 16-byte loads a lane and batch, and the pair's patch record -- 16 dwords, nearly always empty -- as ONE more dword a lane
+// (lane l holds record dword l % 16), requested with the batch it belongs to: unconditional, the same eight loads on every
+// path, so hipcc's count of the loads in flight stays exact (the decode of a batch waits with vmcnt(8), the next batch's
+// eight).  Scalar loads of the record would count in lgkmcnt with the x reads from LDS: every FMA block would then wait
+// for the NEXT pair's record, a round trip to memory.  deliver() decodes, then patches: one scalar compare of entry 0
+// against "empty" and a skipped branch; in a pair with escapes every entry's pos and bits come out of the record dword
+// with v_readlane and the thread that owns the value (pos >> 5) replaces element pos & 31 of wa / wb through a 32-way
+// select -- no memory operation on that path, and no register indexed at run time.
+struct PkRaw28 {
+    v4u q4[7];
+    uint32_t rec;
+};
+
+template <int EPI>
+struct RowPacked28 {
+    static constexpr int kSets = 2;
+    v4f wa[kRowU], wb[kRowU];
+    PkRaw28 raw[kSets];
+    int e15[kSets];
+    const uint32_t *pp, *pr;
+    int e_pt, wave_u;
+
+    __device__ __forceinline__ void init(const MvLocals &, int, int) { wave_u = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
+    __device__ __forceinline__ void point(const MvLocals &m, int u)
+    {
+        int e;
+        pp = pair_packed28<EPI>(m, u, pk28::kPairDw, pk28::kRecDw, e, pr);
+        e_pt = e - 15;
+    }
+    template <int P>
+    __device__ __forceinline__ void issue(int)
+    {
+        const int lane = threadIdx.x & 63;
+        const uint32_t *src = pp + (size_t)wave_u * pk28::kChunkDw + lane * 4;
+#pragma unroll
+        for (int i = 0; i < 7; i++) raw[P].q4[i] = __builtin_nontemporal_load((const v4u *)(src + i * 256));
+        // last: requested ahead of the planes it cost q|k|v 0.3 us a launch (profiles/packed28.md)
+        raw[P].rec = pr[lane & (pk28::kRecDw - 1)];
+        e15[P] = e_pt;
+    }
+    template <int P>
+    __device__ __forceinline__ void deliver()
+    {
+        uint32_t d[pk28::kLaneDw], t[32];
+#pragma unroll
+        for (int i = 0; i < pk28::kLaneDw; i++) {
+            const v4u v = raw[P].q4[i / 4];
+            d[i] = (i % 4 == 0) ? v.x : (i % 4 == 1) ? v.y : (i % 4 == 2) ? v.z : v.w;
+        }
+        pk28::decode_lane_t(d, t);
+        const int e = e15[P];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            wa[k] = v4f{__builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k]), e), __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 1]), e),
+                        __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 2]), e), __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 3]), e)};
+            wb[k] = v4f{__builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 4]), e), __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 5]), e),
+                        __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 6]), e), __builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 7]), e)};
+        }
+        const uint32_t rv = raw[P].rec;
+        if (__builtin_amdgcn_readfirstlane(rv) != pk28::kNoEsc) {  // entry 0's pos: the pair has escapes (rare)
+            const uint32_t tid = threadIdx.x;
+#pragma unroll 1
+            for (int n = 0; n < pk28::kMaxEsc; n++) {
+                const uint32_t pos = __builtin_amdgcn_readlane(rv, 2 * n), bits = __builtin_amdgcn_readlane(rv, 2 * n + 1);
+                if (pos == pk28::kNoEsc) break;
+                const uint32_t sel = (pos >> 5) == tid ? (pos & 31u) : 32u;
+                const float f = __uint_as_float(bits);
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        wa[k][j] = sel == (uint32_t)(8 * k + j) ? f : wa[k][j];
+                        wb[k][j] = sel == (uint32_t)(8 * k + 4 + j) ? f : wb[k][j];
+                    }
+            }
+        }
+    }
+};
+
 #ifdef L2Z_TIMELINE
 // measurement build (scripts/timeline_build.sh): wall-clock stamps (100 MHz) of every block of the row kernel, kept in
 // registers and stored at the block's end.  Per (slot, block): [0] entry, [1] first weight batch requested, [2] x staged,
@@ -374,17 +454,20 @@ unsigned long long g_mtl_launches = 0;  // row-kernel launches so far: launch i 
 // t, t+256, ...; per-thread component accumulators, (x+y)+(z+w), wave xor-shuffle,
 // then the 4 wave partials are added in wave order.  Still a function of n only.
 //
-// PK: the same kernel streaming the 29-bit packed copy of the weights (packed_w.h): the pair's chunks
+// PK = 29: the same kernel streaming the 29-bit packed copy of the weights (packed_w.h): the pair's chunks
 // are read in the same (unit, batch) order, 116 instead of 128 bytes per lane and batch, and decoded into the same
 // wa[] / wb[] right before the FMAs, so every sum is the fp32 kernel's bit for bit.  The raw words live in two fixed
 // register sets taken in turn by a loop unrolled twice: the next batch is requested before the current one is decoded,
 // no request waits on a copy of an earlier batch's words, and the decode waits for the current batch's words only.
 // ---------------------------------------------------------------------------
-template <int PRO, int EPI, int XC, bool LL, bool PK = false>
+// PK = 28: the 28-bit form of one-batch rows (RowPacked28), otherwise the same.
+template <int PRO, int EPI, int XC, bool LL, int PK = 0>
 __global__ __launch_bounds__(kBlock) void matvec_row_kernel(const MatvecArgs a)
 {
+    static_assert(PK == 0 || PK == 29 || (PK == 28 && XC == 4), "packed forms of the row kernel");
     constexpr int U = kRowU;
-    using Src = typename std::conditional<PK, RowPacked<EPI, XC>, RowF32<EPI, XC>>::type;
+    using Src = typename std::conditional<PK == 28, RowPacked28<EPI>,
+                                          typename std::conditional<PK == 29, RowPacked<EPI, XC>, RowF32<EPI, XC>>::type>::type;
     constexpr int NS = Src::kSets;
     extern __shared__ __attribute__((aligned(16))) float lds[];
 #ifdef L2Z_TIMELINE
@@ -394,7 +477,7 @@ __global__ __launch_bounds__(kBlock) void matvec_row_kernel(const MatvecArgs a)
     MvLocals m_ = mv_locals<EPI>(a);
     // packed weights are unsharded weights: no peer to push to.  Compiled out, not just never taken: the push path is a
     // loop with loads of its own, and behind it hipcc no longer counts the outstanding weight loads (vmcnt(0) again)
-    if constexpr (PK) m_.push = nullptr;
+    if constexpr (PK != 0) m_.push = nullptr;
     const MvLocals m = m_;
     const int n4 = m.n >> 2;
     const int n_batches = (n4 + kBlock * U - 1) / (kBlock * U);
@@ -587,7 +670,7 @@ MvLaunch mv_pick(int lpr, bool big_x)
     return big_x ? mv_entry<PRO, EPI, 64, 12, LL>() : mv_entry<PRO, EPI, 64, 4, LL>();
 }
 
-template <int PRO, int EPI, bool LL, bool PK = false>
+template <int PRO, int EPI, bool LL, int PK = 0>
 const void *mv_row_fn(bool big_x)
 {
     return big_x ? reinterpret_cast<const void *>(&matvec_row_kernel<PRO, EPI, 12, LL, PK>)
@@ -611,7 +694,17 @@ const void *mv_row_fn(bool big_x)
 
 const void *mv_row_pick_packed(int pro, int epi, bool big_x)
 {
-#define X(P, E, LL, SC, PK) L2Z_IF_##PK(if (pro == P && epi == E) return mv_row_fn<P, E, false, true>(big_x);)
+#define X(P, E, LL, SC, PK) L2Z_IF_##PK(if (pro == P && epi == E) return mv_row_fn<P, E, false, 29>(big_x);)
+    L2Z_MV_COMBOS(X)
+#undef X
+    return nullptr;
+}
+
+// ... on the 28-bit form: rows of one batch only (n == 4096)
+const void *mv_row_pick_packed28(int pro, int epi)
+{
+#define X(P, E, LL, SC, PK) \
+    L2Z_IF_##PK(if (pro == P && epi == E) return reinterpret_cast<const void *>(&matvec_row_kernel<P, E, 4, false, 28>);)
     L2Z_MV_COMBOS(X)
 #undef X
     return nullptr;
@@ -703,6 +796,12 @@ hipError_t launch_matvec(const MatvecArgs &a_in, int pro, int epi, int max_block
     // packed weights: the row kernel's packed form or nothing (no quiet f32 fall-back)
     if (a.pk != nullptr && (!use_row || ll || !pk::width_ok(a.n))) return hipErrorInvalidValue;
     if (a.pk != nullptr) a.push = nullptr;  // (unsharded: nothing to push to; the packed kernels have no push path)
+    // the 28-bit form: with a packed copy only, rows of one batch only, and every segment in it or none
+    const bool pk28_form = a.pk_rec != nullptr;
+    if (pk28_form && (a.pk == nullptr || !pk28::width_ok(a.n))) return hipErrorInvalidValue;
+    if (a.pk != nullptr && epi != EPI_SWIGLU &&
+        ((a.rows1 > 0 && (a.pk_rec1 != nullptr) != pk28_form) || (a.rows2 > 0 && (a.pk_rec2 != nullptr) != pk28_form)))
+        return hipErrorInvalidValue;
     // ... of every segment, pairs inside one slot
     if (a.pk != nullptr && epi != EPI_SWIGLU &&
         ((a.rows1 > 0 && a.pk1 == nullptr) || (a.rows2 > 0 && a.pk2 == nullptr) || a.rows0 % 2 || a.rows1 % 2 || a.rows2 % 2))
@@ -713,7 +812,8 @@ hipError_t launch_matvec(const MatvecArgs &a_in, int pro, int epi, int max_block
     int n_units;
     const auto padded = [n4](int batch) { return ((n4 + batch - 1) / batch) * batch; };
     if (use_row) {  // the whole block on one pair
-        k.fn = a.pk != nullptr ? mv_row_pick_packed(pro, epi, a.n > 4096) : mv_row_pick(pro, epi, a.n > 4096, ll);
+        k.fn = pk28_form ? mv_row_pick_packed28(pro, epi)
+               : a.pk != nullptr ? mv_row_pick_packed(pro, epi, a.n > 4096) : mv_row_pick(pro, epi, a.n > 4096, ll);
         lds = (size_t)(4 * padded(kBlock * kRowU) + kScratch + 4 * kWaves) * sizeof(float);
         n_units = n_pairs;
     } else if (vec) {  // 64 / lpr pairs per wave

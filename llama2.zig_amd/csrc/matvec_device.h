@@ -21,6 +21,7 @@ struct MvLocals {
     size_t push_base;     // index of out0[0] in the gathered vector
     const uint32_t *pk, *pk1, *pk2;  // packed slots of w0 / w1 / w2 (MatvecArgs::pk...; packed row kernel only)
     int pk_e, pk_e1, pk_e2;
+    const uint32_t *pk_rec, *pk_rec1, *pk_rec2;  // the 28-bit form's patch records (MatvecArgs::pk_rec...)
 };
 
 template <int EPI>
@@ -42,6 +43,7 @@ __device__ __forceinline__ MvLocals mv_locals(const MatvecArgs &a)
     m.push_base = m.push ? (size_t)m.push->rank * m.push->count : 0;
     m.pk = a.pk; m.pk1 = a.pk1; m.pk2 = a.pk2;
     m.pk_e = a.pk_e; m.pk_e1 = a.pk_e1; m.pk_e2 = a.pk_e2;
+    m.pk_rec = a.pk_rec; m.pk_rec1 = a.pk_rec1; m.pk_rec2 = a.pk_rec2;
     return m;
 }
 
@@ -98,6 +100,24 @@ __device__ __forceinline__ const uint32_t *pair_packed(const MvLocals &m, int p,
         return r.pick(m.pk, m.pk1, m.pk2) + (size_t)(r.row >> 1) * pair_dw;
     }
     e_base = m.pk_e;
+    return m.pk + (size_t)p * pair_dw;
+}
+
+// ... and of the 28-bit form (packed_w.h pk28): the pair's stream, of pair_dw dwords, and its patch record of rec_dw
+template <int EPI>
+__device__ __forceinline__ const uint32_t *pair_packed28(const MvLocals &m, int p, size_t pair_dw, size_t rec_dw, int &e_base,
+                                                         const uint32_t *&rec)
+{
+    if (p >= m.n_pairs) p = m.n_pairs - 1;
+    if (EPI == EPI_ROPE) {
+        const SegRow r = seg_row(m, 2 * p);
+        const size_t q = (size_t)(r.row >> 1);
+        e_base = r.pick(m.pk_e, m.pk_e1, m.pk_e2);
+        rec = r.pick(m.pk_rec, m.pk_rec1, m.pk_rec2) + q * rec_dw;
+        return r.pick(m.pk, m.pk1, m.pk2) + q * pair_dw;
+    }
+    e_base = m.pk_e;
+    rec = m.pk_rec + (size_t)p * rec_dw;
     return m.pk + (size_t)p * pair_dw;
 }
 

@@ -1,5 +1,6 @@
-// packed_w.hip -- builds the 29-bit packed copy of the decode mat-vec weights (packed_w.h) on the
-// device, and decodes it back to f32 for the tests.  One pass over each f32 matrix for its exponent range, one to pack.
+// packed_w.hip -- builds the 29-bit and 28-bit packed copies of the decode mat-vec weights (packed_w.h) on
+// the device, and decodes them back to f32 for the tests.  One pass over each f32 matrix for its exponent range, one over
+// a 28-bit candidate for its escapes, one to pack.
 #include "kernel_common.h"
 #include "packed_w.h"
 
@@ -93,6 +94,96 @@ __global__ __launch_bounds__(256) void pk_pack_kernel(const uint32_t *m, uint32_
     }
 }
 
+
+// ---- the 28-bit form (packed_w.h pk28): rows of exactly one batch, a block per pair ----
+
+// the lane's 32 values of pair rows ra / rb in i order (the row kernel's lane tid of the pair's only batch)
+__device__ __forceinline__ void pk28_lane_values(const uint32_t *ra, const uint32_t *rb, uint32_t (&v)[32])
+{
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            v[8 * k + j] = ra[4 * (threadIdx.x + 256 * k) + j];
+            v[8 * k + 4 + j] = rb[4 * (threadIdx.x + 256 * k) + j];
+        }
+}
+
+// max_esc: the most escapes any pair of the matrix has (preset 0)
+__global__ __launch_bounds__(256) void pk28_count_kernel(const uint32_t *m, int e_base, uint32_t *max_esc)
+{
+    __shared__ uint32_t part[4];
+    const uint32_t *pr = m + (size_t)blockIdx.x * (2 * 4096);
+    uint32_t n = 0;
+    for (int i = threadIdx.x; i < 2 * 4096; i += 256) n += pk28::is_escape(pr[i], e_base) ? 1u : 0u;
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t t = part[0] + part[1] + part[2] + part[3];
+        if (t > 0) atomicMax(max_esc, t);
+    }
+}
+
+// stream and patch record of pair blockIdx.x.  The record is compacted in pos order (thread order, then i): every thread
+// finds its first entry from the counts of the threads before it, so no atomic decides the order
+__global__ __launch_bounds__(256) void pk28_pack_kernel(const uint32_t *m, uint32_t *pk, uint32_t *rec, int e_base)
+{
+    __shared__ uint32_t cnt[256];
+    __shared__ uint32_t r[pk28::kRecDw];
+    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const uint32_t *ra = m + (size_t)(2 * q) * 4096, *rb = ra + 4096;
+    uint32_t v[32], d[pk28::kLaneDw];
+    pk28_lane_values(ra, rb, v);
+    const uint32_t esc = pk28::encode_lane(v, e_base, d);
+    uint32_t *dst = pk + (size_t)q * pk28::kPairDw + w * pk28::kChunkDw;
+#pragma unroll
+    for (int i = 0; i < pk28::kLaneDw; i++) dst[pk28::plane_off(i, lane)] = d[i];
+    cnt[tid] = __popc(esc);
+    if (tid < pk28::kRecDw) r[tid] = (tid & 1) ? 0u : pk28::kNoEsc;
+    __syncthreads();
+    if (esc != 0u) {
+        uint32_t at = 0;
+        for (int t = 0; t < tid; t++) at += cnt[t];
+#pragma unroll
+        for (int i = 0; i < 32; i++)
+            if ((esc >> i) & 1u) {
+                if (at < (uint32_t)pk28::kMaxEsc) {
+                    r[2 * at] = pk28::esc_pos(w, lane, i);
+                    r[2 * at + 1] = v[i];
+                }
+                at++;
+            }
+    }
+    __syncthreads();
+    if (tid < pk28::kRecDw) rec[(size_t)q * pk28::kRecDw + tid] = r[tid];
+}
+
+__global__ __launch_bounds__(256) void pk28_unpack_kernel(const uint32_t *pk, const uint32_t *rec, uint32_t *out, int e_base)
+{
+    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const uint32_t *src = pk + (size_t)q * pk28::kPairDw + w * pk28::kChunkDw;
+    uint32_t d[pk28::kLaneDw], t[32];
+#pragma unroll
+    for (int i = 0; i < pk28::kLaneDw; i++) d[i] = src[pk28::plane_off(i, lane)];
+    pk28::decode_lane_t(d, t);
+    uint32_t *oa = out + (size_t)(2 * q) * 4096, *ob = oa + 4096;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            oa[4 * (tid + 256 * k) + j] = __float_as_uint(__builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + j]), e_base - 15));
+            ob[4 * (tid + 256 * k) + j] = __float_as_uint(__builtin_amdgcn_ldexpf(__uint_as_float(t[8 * k + 4 + j]), e_base - 15));
+        }
+    // the escapes this thread owns, over its own stores above
+    for (int k = 0; k < pk28::kMaxEsc; k++) {
+        const uint32_t pos = rec[(size_t)q * pk28::kRecDw + 2 * k];
+        if (pos == pk28::kNoEsc || (pos >> 5) != (uint32_t)tid) continue;
+        const int i = pos & 31u;
+        ((i & 4) ? ob : oa)[4 * (tid + 256 * (i >> 3)) + (i & 3)] = rec[(size_t)q * pk28::kRecDw + 2 * k + 1];
+    }
+}
+
 }  // namespace
 
 hipError_t launch_pk_stats(const float *m, size_t count, uint32_t *stats, hipStream_t st)
@@ -117,6 +208,27 @@ hipError_t launch_pk_unpack(const uint32_t *pk, int rows, int n, int e_base, flo
     const dim3 grid(rows / 2, (n / 4 + pk::kBatchF4 - 1) / pk::kBatchF4);
     hipLaunchKernelGGL(pk_pack_kernel<false>, grid, dim3(256), 0, st, nullptr, const_cast<uint32_t *>(pk),
                        (uint32_t *)out, n, e_base);
+    return hipGetLastError();
+}
+
+hipError_t launch_pk28_count(const float *m, int rows, int n, int e_base, uint32_t *max_esc, hipStream_t st)
+{
+    if (!pk28::width_ok(n) || rows <= 0 || rows % 2) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pk28_count_kernel, dim3(rows / 2), dim3(256), 0, st, (const uint32_t *)m, e_base, max_esc);
+    return hipGetLastError();
+}
+
+hipError_t launch_pk28_pack(const float *m, int rows, int n, int e_base, uint32_t *pk, uint32_t *rec, hipStream_t st)
+{
+    if (!pk28::width_ok(n) || rows <= 0 || rows % 2) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pk28_pack_kernel, dim3(rows / 2), dim3(256), 0, st, (const uint32_t *)m, pk, rec, e_base);
+    return hipGetLastError();
+}
+
+hipError_t launch_pk28_unpack(const uint32_t *pk, const uint32_t *rec, int rows, int n, int e_base, float *out, hipStream_t st)
+{
+    if (!pk28::width_ok(n) || rows <= 0 || rows % 2) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pk28_unpack_kernel, dim3(rows / 2), dim3(256), 0, st, pk, rec, (uint32_t *)out, e_base);
     return hipGetLastError();
 }
 

@@ -37,6 +37,8 @@ Tunables read_env()
     env_int("L2Z_PF_FUSE_PLANES", &t.pf_fuse_planes);
     env_int("L2Z_PACKED_W", &t.packed_w);
     env_int("L2Z_PACKED_KINDS", &t.packed_kinds);
+    env_int("L2Z_PACKED_BITS", &t.packed_bits);
+    env_int("L2Z_PACKED28_KINDS", &t.packed28_kinds);
     return t;
 }
 
@@ -80,7 +82,8 @@ bool tunables_set(const char *name, long long v)
         {"L2Z_PF_PANEL", &t.pf_panel}, {"L2Z_PF_PANEL_MAX", &t.pf_panel_max},
         {"L2Z_PF_X3", &t.pf_x3}, {"L2Z_PF_X3_STREAM_MIN", &t.pf_x3_stream_min},
         {"L2Z_PF_FUSE_PLANES", &t.pf_fuse_planes}, {"L2Z_PACKED_W", &t.packed_w},
-        {"L2Z_PACKED_KINDS", &t.packed_kinds}};
+        {"L2Z_PACKED_KINDS", &t.packed_kinds}, {"L2Z_PACKED_BITS", &t.packed_bits},
+        {"L2Z_PACKED28_KINDS", &t.packed28_kinds}};
     for (auto &e : ints)
         if (strcmp(e.n, name) == 0) {
             *e.p = (int)v;

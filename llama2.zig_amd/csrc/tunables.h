@@ -61,6 +61,16 @@ struct Tunables {
                                //                     wo 4, ffn13 8, ffn2 16, cls 32) that stream the packed copy where the weights have one;
                                //                     default: every kind that has one.  Read when a RunState is created (the per-kind A/B of
                                //                     DESIGN.md 4.9; same bits whatever the mask)
+    int packed_bits = 28;      // L2Z_PACKED_BITS     28: slots whose rows are exactly one batch wide (n == 4096) and whose pairs have at most
+                               //                     eight values below the 4-bit exponent window are packed at 28 bits a value with a
+                               //                     patch record per pair (packed_w.h pk28); 29: every slot gets the 29-bit form, the copy
+                               //                     as it was before there was a second form.  Read when a Weights object is built; same
+                               //                     bits either way
+    int packed28_kinds = 40;   // L2Z_PACKED28_KINDS  mask over the kinds (bits as L2Z_PACKED_KINDS) whose slots may take the 28-bit form.
+                               //                     Default ffn13 | cls, the kinds that kept the byte saving at 7B (1.5 and 2.2 us a
+                               //                     launch); q|k|v and Wo, launches of 4 to 6 units a block, did not get faster and keep
+                               //                     29 bits (profiles/packed28.md); -1: every kind (tests, the per-kind A/B).  Read when a
+                               //                     Weights object is built
     int pf_panel_max = -1;     // L2Z_PF_PANEL_MAX    longest chunk that takes the panel kernel (default and maximum 96 tokens): tests of both sides
                                //                     of the switch-over
 
