@@ -1,4 +1,5 @@
-// forward.cpp -- transformer() (main.zig:285-430) as a chain of fused launches, its hipGraph
+// forward.cpp -- transformer() (main.zig:285-430) as a chain of fused launches -- one layer walk for
+// f32, packed and int8 group-quantized weights (kind_rows.h names what each launch reads) --, its hipGraph
 // capture, the on-device greedy loop (main.zig:987-1042 at temperature 0), per-kind profiling and
 // the emulated-rank driver.
 #include <algorithm>
@@ -8,6 +9,7 @@
 #include <mutex>
 
 #include "batch_host.h"
+#include "kind_rows.h"
 #include "l2z_state.h"
 
 namespace l2z {
@@ -64,108 +66,6 @@ hipError_t set_state(l2z_runstate *s, const l2z_weights *w, int token, int pos)
     return launch_set_state(token, pos, s->d_token, s->d_pos, w->tok_emb, s->x, s->cfg.dim, s->stream);
 }
 
-// The pass on int8 group-quantized weights: the same five launches a layer, the classifier and the
-// step's last node, every row mat-vec the q8 kernel -- its prologue quantizes the launch's input per group, after the
-// rmsnorm where the f32 launch has one -- and attention, the epilogues and the hand-over the f32 pass's own.  Unsharded;
-// the one-launch q | k | v + attention form of small models is not taken.
-int enqueue_forward_q8(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *prof, int only_stage, int variant,
-                       int only_kind)
-{
-    L2Z_CHECK(only_stage < 0 && s->sh.world == 1, L2Z_ERR_INVALID, "int8 group-quantized weights: unsharded passes only");
-    const bool with_step = step != STEP_NONE;
-    const bool split = variant == ATTN_SPLIT || variant == ATTN_SPLIT_S;
-    const l2z_config &c = s->cfg;
-    const Shard &sh = s->sh;
-    hipStream_t st = s->stream;
-    const size_t dim = c.dim, hid = c.hidden_dim, kvd = sh.kvd_loc;
-    const int mb = s->max_blocks, gs = w->q8_gs;
-    const size_t gd = dim / gs, gh = hid / gs;   // groups of a row of dim / of hidden_dim values
-    auto kind = [&](int k) { return only_kind < 0 || only_kind == k; };
-    for (int l = 0; l < c.n_layers; l++) {
-        float *kc = s->key_cache + (size_t)l * c.seq_len * kvd;
-        float *vc = s->value_cache + (size_t)l * c.seq_len * kvd;
-        const size_t kvh_stride = (size_t)c.seq_len * sh.hs;
-        if (kind(KIND_QKV)) {   // rmsnorm + quantize, q | k | v, RoPE, KV write
-            Q8MatvecArgs a = {};
-            a.gs = gs;
-            a.q0 = w->q_wq.q + (size_t)l * dim * dim; a.s0 = w->q_wq.s + (size_t)l * dim * gd;
-            a.q1 = w->q_wk.q + (size_t)l * kvd * dim; a.s1 = w->q_wk.s + (size_t)l * kvd * gd;
-            a.q2 = w->q_wv.q + (size_t)l * kvd * dim; a.s2 = w->q_wv.s + (size_t)l * kvd * gd;
-            a.b.out0 = s->q; a.b.out1 = kc; a.b.out2 = vc;
-            a.b.rows0 = c.dim; a.b.rows1 = sh.kvd_loc; a.b.rows2 = sh.kvd_loc;
-            a.b.pos_stride1 = sh.hs; a.b.pos_stride2 = sh.hs; a.b.kv_head_stride = kvh_stride;
-            a.b.n = c.dim; a.b.x = s->x; a.b.rms_w = w->rms_att + (size_t)l * dim;
-            a.b.pos_ptr = s->d_pos; a.b.rope = s->rope; a.b.head_size = sh.hs; a.b.rope_segs = 2;
-            L2Z_LAUNCH(KIND_QKV, launch_q8_matvec(a, EPI_ROPE, mb, g_cus, st));
-        }
-        if (kind(KIND_ATTN)) {   // attention, as the f32 pass launches it
-            AttnArgs a = {};
-            a.q = s->q; a.kcache = kc; a.vcache = vc; a.xb = s->xb;
-            a.pos_ptr = s->d_pos; a.head_size = sh.hs; a.kv_row = sh.hs; a.kv_head = kvh_stride;
-            a.kv_mul = c.n_heads / c.n_kv_heads; a.seq_len = c.seq_len;
-            a.tl_seq = s->tl_attn_seq++;
-            if (split && s->attn_nch > 1 && attention_split_supported(a))
-                L2Z_LAUNCH(KIND_ATTN, launch_attention_split(a, sh.heads_loc, s->attn_nch, s->d_attn_part, s->d_attn_cnt, st,
-                                                             variant == ATTN_SPLIT_S));
-            else
-                L2Z_LAUNCH(KIND_ATTN, launch_attention(a, sh.heads_loc, st, variant == ATTN_SHORT ? 1 : 0));
-        }
-        if (kind(KIND_WO)) {   // quantize, wo, residual
-            Q8MatvecArgs a = {};
-            a.gs = gs;
-            a.q0 = w->q_wo.q + (size_t)l * dim * dim; a.s0 = w->q_wo.s + (size_t)l * dim * gd;
-            a.b.out0 = s->x; a.b.resid = s->x; a.b.rows0 = c.dim; a.b.n = c.dim; a.b.x = s->xb;
-            L2Z_LAUNCH(KIND_WO, launch_q8_matvec(a, EPI_RESID, mb, g_cus, st));
-        }
-        if (kind(KIND_FFN13)) {   // rmsnorm + quantize, w1 | w3, SiLU * mul
-            Q8MatvecArgs a = {};
-            a.gs = gs;
-            a.q0 = w->q_w13.q + (size_t)l * 2 * hid * dim; a.s0 = w->q_w13.s + (size_t)l * 2 * hid * gd;
-            a.b.out0 = s->hb; a.b.rows0 = c.hidden_dim; a.b.rows1 = c.hidden_dim; a.b.n = c.dim; a.b.x = s->x;
-            a.b.rms_w = w->rms_ffn + (size_t)l * dim;
-            L2Z_LAUNCH(KIND_FFN13, launch_q8_matvec(a, EPI_SWIGLU, mb, g_cus, st));
-        }
-        if (kind(KIND_FFN2)) {   // quantize, w2, residual
-            Q8MatvecArgs a = {};
-            a.gs = gs;
-            a.q0 = w->q_w2.q + (size_t)l * dim * hid; a.s0 = w->q_w2.s + (size_t)l * dim * gh;
-            a.b.out0 = s->x; a.b.resid = s->x; a.b.rows0 = c.dim; a.b.n = c.hidden_dim; a.b.x = s->hb;
-            L2Z_LAUNCH(KIND_FFN2, launch_q8_matvec(a, EPI_RESID, mb, g_cus, st));
-        }
-    }
-    if (kind(KIND_CLS)) {   // final rmsnorm + quantize, classifier, one argmax candidate a block
-        Q8MatvecArgs a = {};
-        a.gs = gs;
-        a.q0 = w->q_cls.q; a.s0 = w->q_cls.s;
-        a.b.out0 = s->logits; a.b.rows0 = c.vocab_size; a.b.n = c.dim; a.b.x = s->x; a.b.rms_w = w->rms_final;
-        a.b.part_val = s->d_part_val; a.b.part_idx = s->d_part_idx;
-        int grid = 0;
-        L2Z_LAUNCH(KIND_CLS, launch_q8_matvec(a, EPI_ARGMAX, mb, g_cus, st, &grid));
-        s->n_part = grid;
-        if (only_kind < 0) (with_step ? s->n_part_step : s->n_part_fwd) = s->n_part;
-    }
-    if (step == STEP_GREEDY && kind(KIND_ARGMAX)) {
-        ArgmaxArgs a = {};
-        a.logits = s->logits; a.vocab = c.vocab_size; a.token_ptr = s->d_token;
-        if (s->n_part > 0) { a.part_val = s->d_part_val; a.part_idx = s->d_part_idx; a.n_part = s->n_part; }
-        a.pos_ptr = s->d_pos; a.prompt = s->d_prompt; a.n_prompt_ptr = s->d_n_prompt;
-        a.out_tokens = s->d_out_tokens; a.argmax_out = s->d_argmax; a.emb_q8 = w->q8_emb();
-        a.x = s->x; a.dim = c.dim; a.advance = 1;
-        L2Z_LAUNCH(KIND_ARGMAX, launch_argmax(a, st));
-    }
-    if (step == STEP_SAMPLE && kind(KIND_ARGMAX)) {
-        L2Z_CHECK(s->d_smp_ctl != nullptr && s->d_smp_scratch != nullptr, L2Z_ERR_STATE,
-                  "sampled step on a runstate l2z_sample_run has not prepared");
-        SampleStepArgs a = {};
-        a.logits = s->logits; a.vocab = c.vocab_size; a.seq_len = c.seq_len;
-        a.params = (const SampleStepParams *)s->d_smp_ctl; a.coins = s->d_smp_ctl + 2; a.scratch = s->d_smp_scratch;
-        a.token_ptr = s->d_token; a.pos_ptr = s->d_pos; a.prompt = s->d_prompt; a.n_prompt_ptr = s->d_n_prompt;
-        a.out_tokens = s->d_out_tokens; a.emb_q8 = w->q8_emb(); a.x = s->x; a.dim = c.dim;
-        L2Z_LAUNCH(KIND_ARGMAX, launch_sample_step(a, st));
-    }
-    return L2Z_OK;
-}
-
 }  // namespace
 
 // The forward pass (main.zig:285-430) as 5 launches per layer + classifier
@@ -187,17 +87,24 @@ int enqueue_forward_q8(l2z_runstate *s, const l2z_weights *w, StepKind step, Pro
 // of 4; stages between collectives: [qkv, attention, wo], [w1|w3, w2] per layer, then the classifier.  The sum over a row
 // is split differently than in the unsharded pass: logits agree at the tolerance of the parity tests, not bit for bit
 // (ranks agree with each other exactly: same partials, same order).
+//
+// One walk for every form the weights come in: a row launch's body fills the shape, the outputs and what the epilogue
+// reads, and row_launch attaches the kind's weights of that layer (kind_rows.h) -- f32 rows, their packed copy, or int8
+// values and scales -- and calls the form's launcher.  On int8 group-quantized weights every row mat-vec
+// is the q8 kernel -- its prologue quantizes the launch's input per group, after the rmsnorm where the f32 launch has
+// one --; such a pass is unsharded, and the one-launch q | k | v + attention form of small models is not taken.
 int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *prof,
                     int only_stage, int variant, int only_kind)
 {
-    if (w->is_q8()) return enqueue_forward_q8(s, w, step, prof, only_stage, variant, only_kind);
+    const bool q8 = w->is_q8();
+    L2Z_CHECK(!q8 || (only_stage < 0 && s->sh.world == 1), L2Z_ERR_INVALID, "int8 group-quantized weights: unsharded passes only");
     const bool with_step = step != STEP_NONE;
     const bool split = variant == ATTN_SPLIT || variant == ATTN_SPLIT_S;
     const l2z_config &c = s->cfg;
     const Shard &sh = s->sh;
     hipStream_t st = s->stream;
     const l2z_comm *lc = s->comm;
-    const size_t dim = c.dim, hid = c.hidden_dim;
+    const size_t dim = c.dim;
     const int mb = s->max_blocks;
     int stage = 0;
     auto want = [&]() { return only_stage < 0 || only_stage == stage; };
@@ -282,8 +189,7 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *
     };
     // a column-shard mat-vec of scheme B: the local slice x_loc (n_pad floats, zero beyond the slice) against this rank's
     // columns of all `dim` rows -> s->part; rank 0 adds the residual
-    auto col_shard = [&](MatvecArgs &a, const float *wcols, const float *x_loc, int n_pad, int *epi) {
-        a.w0 = wcols;
+    auto col_shard = [&](MatvecArgs &a, const float *x_loc, int n_pad, int *epi) {
         a.x = x_loc;
         a.n = n_pad;
         a.rows0 = c.dim;
@@ -295,8 +201,18 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *
     // packed weights: a row launch streams the 29-bit copy of its slot(s) where the weights have one and
     // the runstate's mask of kinds (L2Z_PACKED_KINDS) lets it
     const bool pk = s->packed_w && !sb && sh.world == 1 && !consume;
-    const auto pk_slot = [&](int k, int l, int j = 0) -> const l2z_weights::PkMat * {
-        return pk && ((s->packed_kinds >> k) & 1) ? w->pk_slot(k, l, j) : nullptr;
+    // the row launch of kind k: layer l's weights in the form the object holds -> a, and the form's launcher
+    auto row_launch = [&](int k, int l, MatvecArgs &a, int pro, int epi, int *grid = nullptr, bool packed_ok = true) {
+        const KindRows r = kind_rows(w, sh, k, l);
+        if (q8) {
+            Q8MatvecArgs qa = {};
+            qa.b = a;
+            qa.gs = w->q8_gs;
+            attach_rows(qa, r);
+            return launch_q8_matvec(qa, epi, mb, g_cus, st, grid);
+        }
+        attach_rows(a, r, k, pk && packed_ok && ((s->packed_kinds >> k) & 1));
+        return launch_matvec(a, pro, epi, mb, g_cus, st, grid, &pushed);
     };
     for (int l = 0; l < c.n_layers; l++) {
         // :354 loff; inside a layer the device cache is head-major, [kv heads][seq_len][head_size]: the rows
@@ -304,12 +220,11 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *
         float *kc = s->key_cache + (size_t)l * c.seq_len * sh.kvd_loc;
         float *vc = s->value_cache + (size_t)l * c.seq_len * sh.kvd_loc;
         const size_t kvh_stride = (size_t)c.seq_len * sh.hs;
-        const bool fused = s->fused_qkv_attn && !split && only_stage < 0;
+        const bool fused = s->fused_qkv_attn && !q8 && !split && only_stage < 0;
         if (fused && kind(KIND_QKV)) {    // small models: :305-389 in one launch, one block per head (fused_small.hip)
             FusedQkvAttnArgs a = {};
-            a.wq = w->wq + (size_t)l * dim * dim;
-            a.wk = w->wk + (size_t)l * dim * dim;
-            a.wv = w->wv + (size_t)l * dim * dim;
+            const KindRows r = kind_rows(w, sh, KIND_QKV, l);   // (MHA, unsharded: three (dim, dim) matrices)
+            a.wq = r.seg[0].f32; a.wk = r.seg[1].f32; a.wv = r.seg[2].f32;
             a.rms_w = w->rms_att + (size_t)l * dim; a.x = s->x; a.q_out = s->q;
             a.kcache = kc; a.vcache = vc; a.xb = s->xb; a.pos_ptr = s->d_pos; a.rope = s->rope;
             a.n = c.dim; a.head_size = sh.hs; a.seq_len = c.seq_len; a.kv_dim = sh.kvd_loc;
@@ -318,22 +233,13 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *
         }
         if (!fused && want() && kind(KIND_QKV)) {   // rmsnorm (:305) + q,k,v (:308-320) + RoPE (:336-351) + KV write (:354-358)
             MatvecArgs a = {};
-            a.w0 = w->wq + (size_t)l * sh.dim_loc * dim;
-            a.w1 = w->wk + (size_t)l * sh.kvd_loc * dim;
-            a.w2 = w->wv + (size_t)l * sh.kvd_loc * dim;
             a.out0 = s->q; a.out1 = kc; a.out2 = vc;
             a.rows0 = sh.dim_loc; a.rows1 = sh.kvd_loc; a.rows2 = sh.kvd_loc;
             a.pos_stride1 = sh.hs; a.pos_stride2 = sh.hs; a.kv_head_stride = kvh_stride;
             a.n = c.dim; a.rms_w = w->rms_att + (size_t)l * dim;
             x_in(a, s->x, gi, sh.dim_loc);  // layer 0: the embedding row, a plain buffer (gi == 0)
             a.pos_ptr = s->d_pos; a.rope = s->rope; a.head_size = sh.hs; a.rope_segs = 2;
-            const auto *pq = pk_slot(KIND_QKV, l, 0), *pkk = pk_slot(KIND_QKV, l, 1), *pv = pk_slot(KIND_QKV, l, 2);
-            if (pq && pkk && pv) {  // all three slots or none
-                a.pk = pq->p; a.pk_e = pq->e; a.pk_rec = pq->rec;
-                a.pk1 = pkk->p; a.pk_e1 = pkk->e; a.pk_rec1 = pkk->rec;
-                a.pk2 = pv->p; a.pk_e2 = pv->e; a.pk_rec2 = pv->rec;
-            }
-            L2Z_LAUNCH(KIND_QKV, launch_matvec(a, PRO_RMS, EPI_ROPE, mb, g_cus, st));
+            L2Z_LAUNCH(KIND_QKV, row_launch(KIND_QKV, l, a, PRO_RMS, EPI_ROPE));
         }
         if (!fused && want() && kind(KIND_ATTN)) {   // attention (:361-389) over the local heads
             AttnArgs a = {};
@@ -358,65 +264,57 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *
             MatvecArgs a = {};
             int epi = EPI_RESID;
             if (sb) {
-                col_shard(a, w->wo + (size_t)l * dim * sh.dimc_pad, s->xb + sh.dim0, sh.dimc_pad, &epi);
+                col_shard(a, s->xb + sh.dim0, sh.dimc_pad, &epi);
             } else {
-                a.w0 = w->wo + (size_t)l * sh.dim_loc * dim;
                 a.out0 = s->x + sh.dim0; a.resid = s->x + sh.dim0;
                 a.rows0 = sh.dim_loc; a.n = c.dim;
                 x_in(a, s->xb, gi, sh.dim_loc);
                 push_to(a, 1);
-                if (const auto *p = pk_slot(KIND_WO, l)) { a.pk = p->p; a.pk_e = p->e; a.pk_rec = p->rec; }
             }
-            L2Z_LAUNCH(KIND_WO, launch_matvec(a, PRO_NONE, epi, mb, g_cus, st, nullptr, &pushed));
+            L2Z_LAUNCH(KIND_WO, row_launch(KIND_WO, l, a, PRO_NONE, epi));
         }
         if (sb) L2Z_TRY(reduce());
         else L2Z_TRY(gather(s->x, sh.dim_loc));
         if (want() && kind(KIND_FFN13)) {   // rmsnorm (:398) + w1,w3 (:405-408) + SiLU*mul (:411-416)
-            MatvecArgs a = {};
-            a.w0 = w->w1 + (size_t)l * sh.hid_loc * 2 * dim;  // W1 | W3 row-interleaved: one linear sweep
-            a.w1 = w->w3 + (size_t)l * sh.hid_loc * 2 * dim;  // = a.w0 + dim; the kernels derive it from a.w0
+            MatvecArgs a = {};   // (the weights: W1 | W3 row-interleaved, one linear sweep -- DESIGN.md 2)
             a.out0 = sb ? s->hb : s->hb + sh.hid0;  // scheme B: the slice stays local, w2's column shard reads it from the buffer's start
             a.rows0 = sh.hid_loc; a.rows1 = sh.hid_loc; a.n = c.dim;
             a.rms_w = w->rms_ffn + (size_t)l * dim;
             x_in(a, s->x, gi, sh.dim_loc);
             if (!sb) push_to(a, 2);
-            if (const auto *p = pk_slot(KIND_FFN13, l)) { a.pk = p->p; a.pk_e = p->e; a.pk_rec = p->rec; }
-            L2Z_LAUNCH(KIND_FFN13, launch_matvec(a, PRO_RMS, EPI_SWIGLU, mb, g_cus, st, nullptr, &pushed));
+            L2Z_LAUNCH(KIND_FFN13, row_launch(KIND_FFN13, l, a, PRO_RMS, EPI_SWIGLU));
         }
         if (!sb) L2Z_TRY(gather(s->hb, sh.hid_loc));
         if (want() && kind(KIND_FFN2)) {   // w2 (:419) + residual (:422)
             MatvecArgs a = {};
             int epi = EPI_RESID;
             if (sb) {
-                col_shard(a, w->w2 + (size_t)l * dim * sh.hidc_pad, s->hb, sh.hidc_pad, &epi);
+                col_shard(a, s->hb, sh.hidc_pad, &epi);
             } else {
-                a.w0 = w->w2 + (size_t)l * sh.dim_loc * hid;
                 a.out0 = s->x + sh.dim0; a.resid = s->x + sh.dim0;
                 a.rows0 = sh.dim_loc; a.n = c.hidden_dim;
                 x_in(a, s->hb, gi, sh.hid_loc);
                 push_to(a, 1);
-                if (const auto *p = pk_slot(KIND_FFN2, l)) { a.pk = p->p; a.pk_e = p->e; a.pk_rec = p->rec; }
             }
-            L2Z_LAUNCH(KIND_FFN2, launch_matvec(a, PRO_NONE, epi, mb, g_cus, st, nullptr, &pushed));
+            L2Z_LAUNCH(KIND_FFN2, row_launch(KIND_FFN2, l, a, PRO_NONE, epi));
         }
         if (sb) L2Z_TRY(reduce());
         else L2Z_TRY(gather(s->x, sh.dim_loc));
     }
     if (want() && kind(KIND_CLS)) {   // final rmsnorm (:426) + classifier (:429)
         MatvecArgs a = {};
-        a.w0 = w->wcls; a.out0 = s->logits + sh.v0;
+        a.out0 = s->logits + sh.v0;
         a.rows0 = sh.v_loc; a.n = c.dim; a.rms_w = w->rms_final;
         x_in(a, s->x, gi, sh.dim_loc);
         a.part_val = s->d_part_val; a.part_idx = s->d_part_idx; a.row_offset = sh.v0;
         // vector path, single GPU or a shard's exchanging step: the launch also leaves one argmax candidate per block
-        // (an emulated rank timed kind by kind takes that form too: it is what a real rank's step launches)
-        const bool fuse = (sh.world == 1 || xchg || (only_kind >= 0 && with_step && s->comm && !s->comm->nccl && !s->comm->p2p)) &&
-                          matvec_vector_width(c.dim);
+        // (an emulated rank timed kind by kind takes that form too: it is what a real rank's step launches); the int8
+        // classifier always does
+        const bool fuse = q8 || ((sh.world == 1 || xchg || (only_kind >= 0 && with_step && s->comm && !s->comm->nccl && !s->comm->p2p)) &&
+                                 matvec_vector_width(c.dim));
         int grid = 0;
         if (!xchg) push_to(a, 3);
-        if (const auto *p = fuse ? pk_slot(KIND_CLS, 0) : nullptr) { a.pk = p->p; a.pk_e = p->e; a.pk_rec = p->rec; }
-        L2Z_LAUNCH(KIND_CLS, launch_matvec(a, PRO_RMS, fuse ? EPI_ARGMAX : EPI_STORE, mb, g_cus, st,
-                                           &grid, &pushed));
+        L2Z_LAUNCH(KIND_CLS, row_launch(KIND_CLS, 0, a, PRO_RMS, fuse ? EPI_ARGMAX : EPI_STORE, &grid, fuse));
         s->n_part = fuse ? grid : 0;
         // (a captured graph bakes its form in: run_forward restores the count that belongs to the graph it replays)
         if (only_stage < 0 && only_kind < 0) (with_step ? s->n_part_step : s->n_part_fwd) = s->n_part;
@@ -434,7 +332,7 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *
         a.logits = s->logits; a.vocab = c.vocab_size; a.token_ptr = s->d_token;
         if (s->n_part > 0) { a.part_val = s->d_part_val; a.part_idx = s->d_part_idx; a.n_part = s->n_part; }
         a.pos_ptr = s->d_pos; a.prompt = s->d_prompt; a.n_prompt_ptr = s->d_n_prompt;
-        a.out_tokens = s->d_out_tokens; a.argmax_out = s->d_argmax; a.tok_emb = w->tok_emb;
+        a.out_tokens = s->d_out_tokens; a.argmax_out = s->d_argmax; a.tok_emb = w->tok_emb; a.emb_q8 = w->q8_emb();
         a.x = s->x; a.dim = c.dim; a.advance = 1;
         if (xchg && only_kind < 0) {
             a.xchg = s->d_push + 3;
@@ -451,7 +349,7 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *
         a.logits = s->logits; a.vocab = c.vocab_size; a.seq_len = c.seq_len;
         a.params = (const SampleStepParams *)s->d_smp_ctl; a.coins = s->d_smp_ctl + 2; a.scratch = s->d_smp_scratch;
         a.token_ptr = s->d_token; a.pos_ptr = s->d_pos; a.prompt = s->d_prompt; a.n_prompt_ptr = s->d_n_prompt;
-        a.out_tokens = s->d_out_tokens; a.tok_emb = w->tok_emb; a.x = s->x; a.dim = c.dim;
+        a.out_tokens = s->d_out_tokens; a.tok_emb = w->tok_emb; a.emb_q8 = w->q8_emb(); a.x = s->x; a.dim = c.dim;
         L2Z_LAUNCH(KIND_ARGMAX, launch_sample_step(a, st));
     }
     return L2Z_OK;

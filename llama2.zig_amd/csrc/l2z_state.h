@@ -1,5 +1,5 @@
 // l2z_state.h -- the device-resident Weights / RunState objects behind the C ABI and the internal
-// functions the translation units share (weights.cpp, runstate.cpp, forward.cpp, prefill_host.cpp,
+// functions the translation units share (weights*.cpp, runstate.cpp, forward.cpp, prefill_host.cpp,
 // hooks.cpp).  Product code; nothing under oracle/ is referenced.
 #pragma once
 #include <cstdint>
@@ -47,6 +47,8 @@ struct TensorDesc {
 };
 std::vector<TensorDesc> tensor_table(const l2z_config &c, bool shared);
 void shard_rows(const TensorDesc &d, const Shard &s, size_t *r0, size_t *r1);
+
+void build_packed(l2z_weights *w);  // weights_packed.cpp: the packed copy of a complete f32 weights object (best effort)
 
 extern int g_cus;  // compute units of the device in use (set by ensure_device)
 int ensure_device(int device);

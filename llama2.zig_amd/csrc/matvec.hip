@@ -692,19 +692,13 @@ const void *mv_row_fn(bool big_x)
 #define L2Z_IF_1(...) __VA_ARGS__
 #define L2Z_IF_0(...)
 
-const void *mv_row_pick_packed(int pro, int epi, bool big_x)
+// ... on the packed copy; the 28-bit form: rows of one batch only (n == 4096)
+const void *mv_row_pick_packed(int pro, int epi, bool big_x, bool form28)
 {
-#define X(P, E, LL, SC, PK) L2Z_IF_##PK(if (pro == P && epi == E) return mv_row_fn<P, E, false, 29>(big_x);)
-    L2Z_MV_COMBOS(X)
-#undef X
-    return nullptr;
-}
-
-// ... on the 28-bit form: rows of one batch only (n == 4096)
-const void *mv_row_pick_packed28(int pro, int epi)
-{
-#define X(P, E, LL, SC, PK) \
-    L2Z_IF_##PK(if (pro == P && epi == E) return reinterpret_cast<const void *>(&matvec_row_kernel<P, E, 4, false, 28>);)
+#define X(P, E, LL, SC, PK)                                                                   \
+    L2Z_IF_##PK(if (pro == P && epi == E)                                                     \
+                    return form28 ? reinterpret_cast<const void *>(&matvec_row_kernel<P, E, 4, false, 28>) \
+                                  : mv_row_fn<P, E, false, 29>(big_x);)
     L2Z_MV_COMBOS(X)
 #undef X
     return nullptr;
@@ -812,8 +806,7 @@ hipError_t launch_matvec(const MatvecArgs &a_in, int pro, int epi, int max_block
     int n_units;
     const auto padded = [n4](int batch) { return ((n4 + batch - 1) / batch) * batch; };
     if (use_row) {  // the whole block on one pair
-        k.fn = pk28_form ? mv_row_pick_packed28(pro, epi)
-               : a.pk != nullptr ? mv_row_pick_packed(pro, epi, a.n > 4096) : mv_row_pick(pro, epi, a.n > 4096, ll);
+        k.fn = a.pk != nullptr ? mv_row_pick_packed(pro, epi, a.n > 4096, pk28_form) : mv_row_pick(pro, epi, a.n > 4096, ll);
         lds = (size_t)(4 * padded(kBlock * kRowU) + kScratch + 4 * kWaves) * sizeof(float);
         n_units = n_pairs;
     } else if (vec) {  // 64 / lpr pairs per wave
@@ -832,36 +825,16 @@ hipError_t launch_matvec(const MatvecArgs &a_in, int pro, int epi, int max_block
         hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    // Grid: at most what is resident at once (so every wave's prologue is paid
-    // once), units dealt round-robin so every wave gets the same count +-1.
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k.fn, kBlock, lds) != hipSuccess || occ < 1)
-        occ = 1;
-    if (occ > max_blocks_per_cu) occ = max_blocks_per_cu;
+    // Grid (matvec_device.h): at most what is resident at once, the units dealt evenly.
     // The row kernel streams best with few blocks per CU in lock step (fewer concurrent DRAM
     // streams).  Measured at 7B, whole-token rate: 2 blocks/CU 219 tok/s, 1 -> 208, 3 -> 213,
     // 4-8 -> 208-211 (single launches shift against each other under the power cap, so the
     // choice is made on the whole-token rate).
-    if (use_row && occ > tn.row_blocks) occ = tn.row_blocks;
-    int resident = occ * n_cus;
-    // several ranks sharing ONE GPU (tests): a launch must leave room for the peers' kernels it
-    // may be waiting for
-    if (tn.grid_cap > 0 && resident > tn.grid_cap) resident = tn.grid_cap;
-    int grid;
-    if (use_row) {  // a unit per block at a time
-        grid = n_units;
-        if (grid > resident) {
-            const int per_block = (n_units + resident - 1) / resident;
-            grid = (n_units + per_block - 1) / per_block;
-        }
-    } else {
-        const int blocks_needed = (n_units + kWaves - 1) / kWaves;
-        grid = blocks_needed;
-        if (grid > resident) {
-            const int per_wave = (n_units + resident * kWaves - 1) / (resident * kWaves);
-            grid = (n_units + per_wave * kWaves - 1) / (per_wave * kWaves);
-        }
-    }
+    // grid_cap: several ranks sharing ONE GPU (tests): a launch must leave room for the peers'
+    // kernels it may be waiting for
+    const int per_cu = use_row && max_blocks_per_cu > tn.row_blocks ? tn.row_blocks : max_blocks_per_cu;
+    const int resident = mv_resident_blocks(k.fn, lds, per_cu, n_cus, tn.grid_cap);
+    const int grid = use_row ? mv_grid_block_units(n_units, resident) : mv_grid_wave_units(n_units, resident);
     if (out_grid) *out_grid = grid;
     // only single-segment epilogues of the vector kernels push (wo, ffn13, ffn2, classifier)
     if (!vec || epi == EPI_ROPE || a.rows2 != 0 || (epi != EPI_SWIGLU && a.rows1 != 0)) a.push = nullptr;

@@ -1,6 +1,6 @@
 // matvec_device.h -- device helpers of the mat-vec kernels (matvec.hip): the argument block copied into locals,
 // the pair -> weight rows map, and the fused epilogues (RoPE + KV write, residual, SwiGLU, store) with what they
-// prefetch.  Anonymous namespace, like kernel_common.h.
+// prefetch; and, host side, how the launchers size a grid.  Anonymous namespace, like kernel_common.h.
 #pragma once
 #include "kernel_common.h"
 
@@ -207,6 +207,34 @@ __device__ __forceinline__ void pair_epilogue(const MvLocals &m, int p, float sa
             }
         }
     }
+}
+
+// ---- host side: the grid of a mat-vec launch (launch_matvec, launch_q8_matvec) ----
+// Blocks resident at once -- a launch has no more, so every block pays its prologue once --: what the occupancy query
+// gives the kernel with its LDS, at most blocks_per_cu a CU, at most grid_cap in all (0: no such cap)
+inline int mv_resident_blocks(const void *fn, size_t lds, int blocks_per_cu, int n_cus, int grid_cap)
+{
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, kBlock, lds) != hipSuccess || occ < 1) occ = 1;
+    if (occ > blocks_per_cu) occ = blocks_per_cu;
+    const int resident = occ * n_cus;
+    return grid_cap > 0 && resident > grid_cap ? grid_cap : resident;
+}
+// the row kernel: a unit per block at a time, every block the same count +-1
+inline int mv_grid_block_units(int n_units, int resident)
+{
+    if (n_units <= resident) return n_units;
+    const int per_block = (n_units + resident - 1) / resident;
+    return (n_units + per_block - 1) / per_block;
+}
+// kernels whose waves own the units (matvec_kernel, matvec_scalar_kernel, q8_matvec_kernel): dealt round-robin, every
+// wave the same count +-1
+inline int mv_grid_wave_units(int n_units, int resident)
+{
+    const int blocks_needed = (n_units + kWaves - 1) / kWaves;
+    if (blocks_needed <= resident) return blocks_needed;
+    const int per_wave = (n_units + resident * kWaves - 1) / (resident * kWaves);
+    return (n_units + per_wave * kWaves - 1) / (per_wave * kWaves);
 }
 
 }  // namespace

@@ -270,17 +270,9 @@ hipError_t launch_q8_matvec(const Q8MatvecArgs &a_in, int epi, int max_blocks_pe
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    // Grid: at most what is resident at once (every block pays the prologue once), pairs dealt round-robin to the waves
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, kBlock, lds) != hipSuccess || occ < 1) occ = 1;
+    // Grid (matvec_device.h): at most what is resident at once, pairs dealt round-robin to the waves
     if (max_blocks_per_cu < 1 || max_blocks_per_cu > 8) max_blocks_per_cu = 8;  // (matvec_max_grid: the candidates' room)
-    if (occ > max_blocks_per_cu) occ = max_blocks_per_cu;
-    const int resident = occ * n_cus;
-    int grid = (n_pairs + kWaves - 1) / kWaves;
-    if (grid > resident) {
-        const int per_wave = (n_pairs + resident * kWaves - 1) / (resident * kWaves);
-        grid = (n_pairs + per_wave * kWaves - 1) / (per_wave * kWaves);
-    }
+    const int grid = mv_grid_wave_units(n_pairs, mv_resident_blocks(fn, lds, max_blocks_per_cu, n_cus, 0));
     if (out_grid) *out_grid = grid;
     void *args[] = {&a};
     return hipLaunchKernel(fn, dim3(grid), dim3(kBlock), args, lds, st);

@@ -34,7 +34,7 @@ def kv_rows(s, cfg, n_pos, kvd=None):
     return [s.read(nm, l * cfg.seq_len * kvd, n_pos * kvd) for nm in ("key_cache", "value_cache") for l in range(cfg.n_layers)]
 
 
-def greedy(name, cfg, steps=8, **opts):
+def greedy(name, cfg, steps=8, sample=False, **opts):
     """steps forward passes fed with their own argmax (logits of each), then the same steps as one greedy run (the
     captured step: fused classifier argmax, argmax_kernel's hand-over), and the K / V rows both wrote"""
     for k, v in opts.items():
@@ -53,8 +53,19 @@ def greedy(name, cfg, steps=8, **opts):
     s2.greedy_begin([])
     emit(f"{name}: greedy_run ids", s2.greedy_run(w, steps))
     emit(f"{name}: greedy_run logits, K / V rows", s2.logits(), *kv_rows(s2, cfg, steps))
+    if sample:
+        sample_run(name, cfg, w, steps)
     for o in (s, s2, w):
         o.close()
+
+
+def sample_run(name, cfg, w, steps=8):
+    """the sampled loop: the same pass with the draw as its last node"""
+    s = B.RunState(cfg)
+    s.greedy_begin([3, 4])
+    coins = np.random.default_rng(7).random(steps, dtype=np.float32)
+    emit(f"{name}: sample_run ids, logits", s.sample_run(w, steps, 0.9, 0.95, coins), s.logits())
+    s.close()
 
 
 small = ck.Config(dim=288, hidden_dim=768, n_layers=2, n_heads=6, n_kv_heads=6, vocab_size=1000, seq_len=64)
@@ -65,6 +76,39 @@ B.option_set("L2Z_FUSE_SMALL", 1)
 greedy("dim 4096 packed", big, L2Z_PACKED_W=1)
 greedy("dim 4096 f32", big, L2Z_PACKED_W=0)
 B.option_set("L2Z_PACKED_W", 1)
+# ... and the packed copy in each form it can be built and attached: 28 / 29 bits, the kinds that may take 28 (the
+# default 40 = ffn13 | cls, then every kind), every single kind's launches alone on the copy (qkv 1, wo 4, ffn13 8, ffn2 16, cls 32)
+for bits, kinds28 in ((29, 40), (28, 40), (28, 63)):
+    greedy(f"dim 4096 packed, bits {bits}, 28-bit kinds {kinds28}", big, sample=True, L2Z_PACKED_BITS=bits, L2Z_PACKED28_KINDS=kinds28)
+B.option_set("L2Z_PACKED_BITS", 28)
+B.option_set("L2Z_PACKED28_KINDS", 40)
+for bit in (1, 4, 8, 16, 32):
+    greedy(f"dim 4096 packed, kinds mask {bit}", big, steps=4, L2Z_PACKED_KINDS=bit)
+B.option_set("L2Z_PACKED_KINDS", -1)
+
+# int8 group-quantized weights (tests/q8_cases.py: an MHA shape whose runstate has the fused small-model form set, and
+# the shape that takes both loops of the kernel): the stepped pass, the greedy loop, the sampled loop
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+import q8_cases  # noqa: E402
+for qname in ("288", "tall"):
+    cfg, gs, _, body = q8_cases.model(qname)
+    w = B.Weights.from_q8(cfg, body, True, gs)
+    s = B.RunState(cfg)
+    tok, lgs, ids = 1, [], []
+    for pos in range(8):
+        s.transformer(tok, pos, w)
+        lgs.append(s.logits())
+        tok = s.argmax()
+        ids.append(tok)
+    emit(f"q8 {qname}: logits of 8 steps, argmax ids", *lgs, np.array(ids, np.int32))
+    emit(f"q8 {qname}: K / V rows", *kv_rows(s, cfg, 8))
+    s2 = B.RunState(cfg)
+    s2.greedy_begin([])
+    emit(f"q8 {qname}: greedy_run ids", s2.greedy_run(w, 8))
+    emit(f"q8 {qname}: greedy_run last logits, K / V rows", s2.logits(), *kv_rows(s2, cfg, 8))
+    sample_run(f"q8 {qname}", cfg, w)
+    for o in (s, s2, w):
+        o.close()
 
 # two emulated ranks of the small model on one GPU
 comms = [B.Comm(r, 2, None, 0, emulated=True) for r in range(2)]

@@ -2,7 +2,9 @@
 """Per-kernel device-code comparison of one HIP source between two trees, without a GPU: both copies are compiled for
 gfx950 with the Makefile's flags and `--cuda-device-only -S`, the assembly is cut per kernel symbol, assembler comments,
 the __hip_cuid symbol and the function ordinal of local labels are dropped, and the instruction text is compared.  For
-kernels whose text differs, the counts of the arithmetic and memory opcodes a refactor must not move are printed side by side.
+kernels whose text differs, the counts of the arithmetic and memory opcodes a refactor must not move are printed side by side,
+and the ordered list of the s_waitcnt vmcnt(N) operands: the packed row kernels' speed rests on where the compiler lets a wave
+wait for how many loads, which a count per N does not show.
 A packed arithmetic instruction (v_pk_add_f32 ...) counts as the two scalar ones it stands for, and LDS traffic is counted in
 BYTES per lane and direction, not in instructions: the compiler pairs two ds_read_b32 into one
 ds_read2st64_b32 (and back) as the addressing around them changes -- the same bytes.
@@ -52,6 +54,11 @@ def counts(text):
     return c
 
 
+def vmcnts(text):
+    """the N of every s_waitcnt vmcnt(N), in program order"""
+    return [int(m.group(1)) for s in text if s.startswith("s_waitcnt") for m in [re.search(r"vmcnt\((\d+)\)", s)] if m]
+
+
 if __name__ == "__main__":
     parent, head = sys.argv[1], sys.argv[2]
     for src in sys.argv[3:]:
@@ -69,3 +76,5 @@ if __name__ == "__main__":
             moved = ", ".join(f"{g} {ca[g]} -> {cb[g]} (!)" for g in ca if ca[g] != cb[g])
             print(f"  {d}: instructions {len([s for s in a[k] if not s.endswith(':')])} -> {len([s for s in b[k] if not s.endswith(':')])}; "
                   + (moved or "counts equal: " + ", ".join(f"{g} {ca[g]}" for g in ca)))
+            va, vb = vmcnts(a[k]), vmcnts(b[k])
+            print(f"    vmcnt order {'equal' if va == vb else 'DIFFERS (!)'}: {' '.join(map(str, va))}" + ("" if va == vb else f" -> {' '.join(map(str, vb))}"))

@@ -12,13 +12,15 @@
 // launch_matvec over 11 widths x 6 row counts x every (prologue, epilogue) x one and three segments x LL on / off x
 // packed or not x an unaligned x x L2Z_GRID_CAP 0 / 64, with the occupancy query answering 1, 2, 4, 8 in turn;
 // launch_attention / launch_attention_split over head sizes, context lengths, forms and chunk counts; launch_argmax.
-// Every call logs its launch (or none) and its return code (profiles/decode_kernels_refactor.md).  The same program
+// launch_q8_matvec of q8_matvec.o over 7 widths x 6 row counts x every epilogue x group sizes 32 / 64 x one and three
+// segments x the same occupancy answers.
+// Every call logs its launch (or none) and its return code (profiles/decode_kernels_refactor.md, decode_pass_refactor.md).  The same program
 // built with -Xarch_host -fsanitize=address,undefined on both lines is the host-side sanitizer run of those launchers.
 //
 //   C=llama2.zig_amd/csrc
 //   hipcc --offload-arch=gfx950 -O1 -std=c++17 -fPIC -ffp-contract=off -w -I$C -Iinclude -c scripts/launch_log_probe.cpp -o /tmp/llp.o
 //   /opt/rocm/llvm/bin/clang++ /tmp/llp.o $C/prefill_gemm.o $C/prefill_skinny.o $C/prefill_panel.o $C/prefill_attention.o \
-//       $C/prefill_ragged.o $C/score.o $C/tunables.o $C/matvec.o $C/attention.o $C/misc_kernels.o -o scripts/launch_log_probe
+//       $C/prefill_ragged.o $C/score.o $C/tunables.o $C/matvec.o $C/attention.o $C/misc_kernels.o $C/q8_matvec.o -o scripts/launch_log_probe
 //   scripts/launch_log_probe [L2Z_PF_PANEL L2Z_PF_FUSE_PLANES [L2Z_PF_X3_STREAM_MIN]] > launches.log
 //   scripts/launch_log_probe decode > decode_launches.log
 #include "prefill_host.cpp"
@@ -80,7 +82,15 @@ hipError_t hipLaunchKernel(const void *fn, dim3 g, dim3 b, void **args, size_t l
 namespace l2z {
 int g_cus = 256;
 void set_error(const char *f, ...) { va_list ap; va_start(ap, f); printf("  ERROR: "); vprintf(f, ap); printf("\n"); va_end(ap); }
-int check_pair(const l2z_config *, const l2z_runstate *, const l2z_weights *) { return 0; }
+int check_pair(const l2z_config *, const l2z_runstate *, const l2z_weights *, bool, bool) { return 0; }
+int check_positions(const char *, const char *, const char *, int, int, int) { return 0; }
+int check_tokens(const char *, const char *, const int32_t *, int, int, int) { return 0; }
+int alloc_all(const char *, std::initializer_list<DeviceBuf> want)
+{
+    for (const DeviceBuf &b : want)
+        if (*b.p == nullptr && b.bytes != 0) hipMalloc(b.p, b.bytes);
+    return 0;
+}
 int comm_check(const l2z_comm *) { return 0; }
 bool comm_bulk_ok(const l2z_comm *, size_t) { return true; }
 hipError_t launch_bulk_unpack(const BulkArgs &, unsigned long long, int, float *, int, hipStream_t) { return hipSuccess; }
@@ -164,6 +174,30 @@ static void decode_sweep()
                 }
     }
     tunables_set("L2Z_GRID_CAP", 0);
+    // launch_q8_matvec: widths x rows x epilogue x group size x one and three segments x the occupancy answers, and
+    // max_blocks_per_cu values its own clamp treats differently
+    const int8_t *const qbase = (const int8_t *)0x300000000ull;
+    static const int qns[] = {64, 288, 768, 1408, 4096, 4224, 11008};
+    for (int n : qns) for (int r : rows) for (int epi = 0; epi <= 4; epi++) for (int gs : {32, 64}) for (int segs : {1, 3})
+        for (int occ : {1, 2, 4, 8}) for (int mb : {8, 0, 3, 9}) {
+            if (mb != 8 && occ != 4) continue;  // the clamp: once per shape
+            g_occ = occ;
+            Q8MatvecArgs a = {};
+            a.gs = gs;
+            a.b.n = n; a.b.x = base; a.b.rms_w = epi == EPI_RESID ? nullptr : base + (1 << 20); a.b.resid = base + (2 << 20);
+            a.q0 = qbase; a.s0 = base + (16 << 20); a.b.out0 = base + (3 << 20); a.b.rows0 = r;
+            if (epi == EPI_SWIGLU) a.b.rows1 = r;
+            if (segs == 3) {
+                a.q1 = qbase + ((size_t)1 << 30); a.s1 = base + (64 << 20); a.b.out1 = base + (4 << 20); a.b.rows1 = epi == EPI_SWIGLU ? r : (r + 1) / 2;
+                if (epi != EPI_SWIGLU) { a.q2 = qbase + ((size_t)2 << 30); a.s2 = base + (96 << 20); a.b.out2 = base + (5 << 20); a.b.rows2 = (r + 1) / 2; }
+            }
+            a.b.pos_ptr = (const int *)(base + (6 << 20)); a.b.rope = (const float2 *)(base + (7 << 20)); a.b.head_size = 64; a.b.rope_segs = 2;
+            a.b.part_val = base + (8 << 20); a.b.part_idx = (int *)(base + (9 << 20));
+            int grid = -1;
+            printf("q8 n %d rows %d epi %d gs %d segs %d occ %d mb %d\n", n, r, epi, gs, segs, occ, mb);
+            const hipError_t e = launch_q8_matvec(a, epi, mb, g_cus, nullptr, &grid);
+            printf("  -> %d grid %d\n", (int)e, grid);
+        }
     for (int hs : {11, 48, 64, 128}) for (int S : {256, 512, 1024, 2048}) for (int mis = 0; mis <= 1; mis++) {
         AttnArgs a = {};
         a.q = base + mis; a.kcache = base + (16 << 20); a.vcache = base + (64 << 20); a.xb = base + (3 << 20);
