@@ -593,7 +593,7 @@ int l2z_runstate_trim(l2z_runstate *s, int n_pos);
  * argmax rule -- is the f32 pass's.
  * WHO TAKES SUCH WEIGHTS: l2z_transformer, l2z_greedy_begin / _run, l2z_sample_run (prompt positions always step, as under
  * L2Z_PREFILL=0), l2z_time_kind, l2z_profile_forward, with an unsharded, contiguous runstate; the logits-only calls work
- * unchanged.  Every other entry point that takes weights -- l2z_prefill, l2z_score, l2z_transformer_batch, the verify
+ * unchanged; their batched prompt pass is an entry point of its own, l2z_prefill_q8 (below).  Every other entry point that takes weights -- l2z_prefill, l2z_score, l2z_transformer_batch, the verify
  * family, l2z_prefill_batch, the wide family, l2z_step_mixed, the emulated-rank hooks, l2z_weights_read -- refuses them with
  * L2Z_ERR_INVALID before anything is enqueued or changed.  Such weights are unsharded, hold no f32 matrix and no packed
  * copy.
@@ -651,6 +651,32 @@ typedef struct {
     int grid;
 } l2z_q8_case;
 int l2z_q8_matvec_case(l2z_q8_case *c);
+
+/* ---- Batched prompt pass on int8 group-quantized weights (PREVIEW) ----
+ * l2z_prefill_q8: the state change of l2z_transformer(tokens[i], pos0 + i, ...) on q8 weights for i = 0 .. n_tokens - 1
+ * -- KV rows pos0 .. pos0 + n_tokens - 1 of every layer written, the LAST position's logits (and the classifier's argmax
+ * candidates) in the runstate, so l2z_argmax, l2z_logits_read, l2z_probs_read and l2z_sample_batch work on them and
+ * l2z_transformer or l2z_sample_run may go on from pos0 + n_tokens -- with every weight matrix streamed once per chunk
+ * (l2z_prefill's chunk plan, at most 1024 rows) and multiplied on the int8 matrix cores.
+ * THE ARITHMETIC is the definition above, row by row: each row's activations are quantized by the activation rule over
+ * dim before q | k | v, Wo, W1 | W3 and the classifier and over hidden_dim before W2, and a product is
+ * sum_g f32(I_g) * ws * xs with exact integer group sums.  The f32 sum over groups runs in another (fixed) order than the
+ * stepped pass's, so the two agree up to f32 summation order, not bit for bit; the same bits from run to run.
+ * l2z_prefill, l2z_greedy_run and every other entry point are unchanged: they refuse such weights or step the prompt.
+ * A refusal enqueues nothing and changes nothing.  L2Z_ERR_NO_DEVICE without a device; L2Z_ERR_INVALID for a null
+ * argument, n_tokens < 1, f32 or packed weights (those go to l2z_prefill), a sharded or paged runstate, a config other
+ * than the objects'; L2Z_ERR_STATE for positions outside [0, seq_len) or a token outside the vocabulary.
+ *
+ * l2z_q8_quantize_rows: the pass's row launch on its own (host pointers): m rows of n floats -> out_q [m, n] and out_s
+ * [m, n / gs] by the activation rule, after the rmsnorm with rms_w [n] where that is not null.
+ * l2z_q8_gemm: the pass's GEMM on its own, store epilogue (host pointers): out [m, d] from m quantized rows (xq [m, n],
+ * xs [m, n / gs]) and d quantized weight rows (wq [d, n], ws [d, n / gs]); d a multiple of 4.  The order of a row's f32
+ * sum depends on n and gs only: a row's bits do not depend on m or on the other rows. */
+int l2z_prefill_q8(const int32_t *tokens, int n_tokens, int pos0, const l2z_config *config, l2z_runstate *s,
+                   const l2z_weights *w);
+int l2z_q8_quantize_rows(const float *x, int m, size_t n, const float *rms_w, int gs, int8_t *out_q, float *out_s);
+int l2z_q8_gemm(float *out, const int8_t *xq, const float *xs, int m, const int8_t *wq, const float *ws, size_t n, size_t d,
+                int gs);
 
 #ifdef __cplusplus
 }

@@ -137,6 +137,11 @@ def lib():
         L.l2z_q8_matmul.argtypes = [fp, i8p, fp, i8p, fp, sz, sz, C.c_int]
     if hasattr(L, "l2z_q8_matvec_case"):
         L.l2z_q8_matvec_case.argtypes = [C.POINTER(Q8Case)]
+    if hasattr(L, "l2z_prefill_q8"):  # their batched prompt pass (PREVIEW)
+        i8p = C.POINTER(C.c_int8)
+        L.l2z_prefill_q8.argtypes = [i32p, C.c_int, C.c_int, cfgp, vp, vp]
+        L.l2z_q8_quantize_rows.argtypes = [fp, C.c_int, sz, fp, C.c_int, i8p, fp]
+        L.l2z_q8_gemm.argtypes = [fp, i8p, fp, C.c_int, i8p, fp, sz, sz, C.c_int]
     L.l2z_logits_write.argtypes = [vp, fp]
     L.l2z_sample_time.argtypes = [C.c_int, C.POINTER(vp), fp, fp, fp, C.c_int, C.POINTER(C.c_double)]
     L.l2z_greedy_begin.argtypes = [vp, i32p, C.c_int]
@@ -436,6 +441,12 @@ class RunState:
         t = np.ascontiguousarray(tokens, np.int32)
         _chk(lib().l2z_prefill(t.ctypes.data_as(C.POINTER(C.c_int32)), t.size, pos0,
                                C.byref(self.cfg), self.h, w.h))
+
+    def prefill_q8(self, tokens, pos0: int, w: Weights) -> None:
+        """l2z_prefill_q8 (a preview entry point of the test library): prefill's state change on int8 group-quantized
+        weights, on the int8 matrix cores; agrees with the stepped pass up to f32 summation order."""
+        t = np.ascontiguousarray(tokens, np.int32)
+        _chk(lib().l2z_prefill_q8(t.ctypes.data_as(C.POINTER(C.c_int32)), t.size, pos0, C.byref(self.cfg), self.h, w.h))
 
     def score(self, tokens, pos0: int, w: Weights, targets=None, top1: bool = True):
         """l2z_score: prefill(tokens, pos0) plus, per position, (log-prob of its target, top-1 token id) as two arrays.
@@ -1543,6 +1554,54 @@ def q8_matmul(xq, xs, wq, ws, gs: int) -> np.ndarray:
     i8p = C.POINTER(C.c_int8)
     _chk(lib().l2z_q8_matmul(_fp(out), xq.ctypes.data_as(i8p), _fp(xs), wq.ctypes.data_as(i8p), _fp(ws), n, d, gs))
     return out
+
+
+def q8_quantize_rows(x, gs: int, rms_w=None):
+    """The row launch of the quantized prompt pass on its own (l2z_q8_quantize_rows): x [m, n] -> (q int8 [m, n], s f32
+    [m, n // gs]) by the activation rule, after the rmsnorm with rms_w [n] where given."""
+    x = _f32(x)
+    assert x.ndim == 2
+    m, n = x.shape
+    g = None if rms_w is None else _f32(rms_w).reshape(-1)
+    assert g is None or g.size == n
+    q = np.empty((m, n), np.int8)
+    s = np.empty((m, n // gs), np.float32)
+    _chk(lib().l2z_q8_quantize_rows(_fp(x), m, n, None if g is None else _fp(g), gs, q.ctypes.data_as(C.POINTER(C.c_int8)), _fp(s)))
+    return q, s
+
+
+def q8_gemm(xq, xs, wq, ws, gs: int) -> np.ndarray:
+    """The GEMM of the quantized prompt pass on its own, store epilogue (l2z_q8_gemm): xq [m, n] int8, xs [m, n // gs], wq
+    [d, n] int8, ws [d, n // gs] -> out [m, d]."""
+    xq = np.ascontiguousarray(xq, dtype=np.int8)
+    wq = np.ascontiguousarray(wq, dtype=np.int8)
+    (m, n), d = xq.shape, wq.shape[0]
+    xs, ws = _f32(xs).reshape(-1), _f32(ws).reshape(-1)
+    assert wq.shape[1] == n and xs.size == m * (n // gs) and ws.size == d * (n // gs)
+    out = np.empty((m, d), np.float32)
+    i8p = C.POINTER(C.c_int8)
+    _chk(lib().l2z_q8_gemm(_fp(out), xq.ctypes.data_as(i8p), _fp(xs), m, wq.ctypes.data_as(i8p), _fp(ws), n, d, gs))
+    return out
+
+
+def generate_q8(s: RunState, w: Weights, prompt, n_steps: int, bos: int = 1) -> np.ndarray:
+    """The greedy loop on int8 group-quantized weights with a batched prompt pass: prefill_q8 of BOS + prompt at position 0,
+    then transformer + argmax per step.  Returns the `next` of every position from 0 as l2z_greedy_run reports them (the
+    prompt's tokens, then the picks); a BOS ends the run and is the last id."""
+    prompt = [int(t) for t in prompt]
+    steps = s.cfg.seq_len if n_steps == 0 else max(1, min(int(n_steps), s.cfg.seq_len))
+    fed = ([bos] + prompt)[:steps]
+    s.prefill_q8(fed, 0, w)
+    ids = prompt[:len(fed) - 1]
+    tok = s.argmax() if len(fed) > len(prompt) else prompt[len(fed) - 1]
+    ids.append(tok)
+    for pos in range(len(fed), steps):
+        if tok == bos:
+            break
+        s.transformer(tok, pos, w)
+        tok = s.argmax()
+        ids.append(tok)
+    return np.array(ids, np.int32)
 
 
 def _q8_case_fields():

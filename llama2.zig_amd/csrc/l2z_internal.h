@@ -187,6 +187,36 @@ hipError_t launch_q8_quantize(const float *src, size_t count, int gs, bool weigh
 hipError_t launch_set_state_q8(int token, int pos, int *token_ptr, int *pos_ptr, const Q8Emb &emb, float *x, int dim,
                                hipStream_t st);
 
+// ---- the batched prompt pass on int8 group-quantized weights (q8_rows.hip, q8_gemm.hip) ----
+// The GEMM's M tile of tokens: the quantized rows of a chunk stand padded up to a multiple of it, the pad rows zero
+constexpr int kQ8GemmTile = 16;
+inline int q8_gemm_rows_padded(int m) { return (m + kQ8GemmTile - 1) / kQ8GemmTile * kQ8GemmTile; }
+// rows tokens[0 .. P) of the quantized table -> x [P, dim]; row_seq[r] = 0 and row_pos[r] = pos0 + r beside them (the
+// one-sequence table launch_ragged_rope_scatter reads; either null: not written)
+hipError_t launch_q8_embed_rows(const Q8Emb &emb, const int *tokens, int dim, int P, float *x, int pos0, int *row_seq,
+                                int *row_pos, hipStream_t st);
+// m rows of n floats, ldx apart -> their int8 values q [q8_gemm_rows_padded(m), n] and scales s [.., n / gs] by the
+// activation rule, after the rmsnorm with rms_w where that is not null (the decode prologue's arithmetic, q8_matvec.hip);
+// the pad rows are written as zeros
+hipError_t launch_q8_quantize_rows(const float *x, int ldx, int m, int n, const float *rms_w, int gs, int8_t *q, float *s,
+                                   hipStream_t st);
+// out [m, d] = the product of m quantized token rows (xq [q8_gemm_rows_padded(m), n], xs) with d quantized weight rows
+// (wq [d, n], ws [d, n / gs]; d a multiple of 4) on the int8 matrix cores, one MFMA a group.  EPI_STORE: out [m, ldo];
+// EPI_RESID: out = res + product (res [m, ldres], may be out); EPI_SWIGLU: the rows are W1 | W3 interleaved, out
+// [m, ldo] holds the d / 2 gated values.  The f32 sum over groups runs in an order that depends on n and gs only
+struct Q8GemmArgs {
+    const int8_t *xq;
+    const float *xs;
+    const int8_t *wq;
+    const float *ws;
+    float *out;
+    int ldo;
+    const float *res;
+    int ldres;
+    int m, n, d, gs;
+};
+hipError_t launch_q8_gemm(const Q8GemmArgs &a, int epi, hipStream_t st);
+
 // main.zig:361-389: scores, softmax, att.V for the local heads of one layer
 struct AttnArgs {
     const float *q;        // (n_heads_local * head_size)
