@@ -593,7 +593,8 @@ int l2z_runstate_trim(l2z_runstate *s, int n_pos);
  * argmax rule -- is the f32 pass's.
  * WHO TAKES SUCH WEIGHTS: l2z_transformer, l2z_greedy_begin / _run, l2z_sample_run (prompt positions always step, as under
  * L2Z_PREFILL=0), l2z_time_kind, l2z_profile_forward, with an unsharded, contiguous runstate; the logits-only calls work
- * unchanged; their batched prompt pass is an entry point of its own, l2z_prefill_q8 (below).  Every other entry point that takes weights -- l2z_prefill, l2z_score, l2z_transformer_batch, the verify
+ * unchanged; their batched prompt pass is an entry point of its own, l2z_prefill_q8, and so are their batched step and verify
+ * pass, l2z_transformer_batch_q8 and l2z_verify_q8 (both below).  Every other entry point that takes weights -- l2z_prefill, l2z_score, l2z_transformer_batch, the verify
  * family, l2z_prefill_batch, the wide family, l2z_step_mixed, the emulated-rank hooks, l2z_weights_read -- refuses them with
  * L2Z_ERR_INVALID before anything is enqueued or changed.  Such weights are unsharded, hold no f32 matrix and no packed
  * copy.
@@ -677,6 +678,36 @@ int l2z_prefill_q8(const int32_t *tokens, int n_tokens, int pos0, const l2z_conf
 int l2z_q8_quantize_rows(const float *x, int m, size_t n, const float *rms_w, int gs, int8_t *out_q, float *out_s);
 int l2z_q8_gemm(float *out, const int8_t *xq, const float *xs, int m, const int8_t *wq, const float *ws, size_t n, size_t d,
                 int gs);
+
+/* ---- Batched and speculative decoding on int8 group-quantized weights (PREVIEW) ----
+ * The batched step of l2z_transformer_batch on q8 weights, under names of its own: l2z_transformer_batch, the l2z_verify
+ * family and every other entry point keep refusing such weights.
+ * l2z_transformer_batch_q8: l2z_transformer_batch's contract -- 1 .. L2Z_BATCH_MAX sequences, one runstate each, one token
+ * each at its own position; each row's KV rows in its own caches and its WHOLE logits in its own runstate, so
+ * l2z_argmax_batch, l2z_sample_batch, l2z_argmax and l2z_logits_read work behind it.
+ * l2z_verify_q8: l2z_verify's contract -- 1 .. L2Z_BATCH_MAX consecutive positions of ONE sequence in one sweep of the
+ * weights, the verdict on the device -- with temperature 0 and coins NULL, l2z_verify_sample's with a temperature (coins[i]:
+ * the coin of position pos0 + i).  l2z_verify_logits_read serves its rows.
+ * THE ARITHMETIC is 4.23's definition row by row, as l2z_prefill_q8's: rows quantized by the activation rule, a product
+ * sum_g f32(I_g) * ws * xs with exact integer group sums and the f32 sum in l2z_q8_gemm's order -- the bits of a row's
+ * product are those l2z_q8_gemm gives for the same quantized row and matrix --, f32 attention (l2z_transformer_batch's
+ * and l2z_verify's kernels).  A row's results do not depend on the other rows of the call, on their number or on its
+ * place among them.
+ * A refusal enqueues nothing and changes nothing.  L2Z_ERR_NO_DEVICE without a device; L2Z_ERR_INVALID for a null argument,
+ * n / n_tokens outside [1, L2Z_BATCH_MAX], f32 or packed weights (those go to l2z_transformer_batch / l2z_verify), a sharded
+ * or paged runstate, a config other than the objects', a head_size that is no multiple of 4 or above 256, a vocab_size
+ * that is no multiple of 4, l2z_sample_batch's rules for temperature, top_p and the coins; L2Z_ERR_STATE for a position
+ * outside [0, seq_len) or a token outside the vocabulary.
+ * l2z_batch_q8_time / l2z_verify_q8_time (scripts/q8_batch_bench.py): the twins of l2z_batch_time / l2z_verify_time --
+ * one call, then `iters` passes back to back, timed by device events on the pass's stream. */
+int l2z_transformer_batch_q8(int n, const int32_t *tokens, const int32_t *pos, const l2z_config *config,
+                             l2z_runstate *const *states, const l2z_weights *w);
+int l2z_verify_q8(const int32_t *tokens, int n_tokens, int pos0, float temperature, float top_p, const float *coins,
+                  const l2z_config *config, l2z_runstate *s, const l2z_weights *w, int32_t *out_next, int *out_accepted);
+int l2z_batch_q8_time(int n, const int32_t *tokens, const int32_t *pos, const l2z_config *config, l2z_runstate *const *states,
+                      const l2z_weights *w, int iters, double *out_ms);
+int l2z_verify_q8_time(const int32_t *tokens, int n_tokens, int pos0, float temperature, float top_p, const float *coins,
+                       const l2z_config *config, l2z_runstate *s, const l2z_weights *w, int iters, double *out_ms);
 
 #ifdef __cplusplus
 }

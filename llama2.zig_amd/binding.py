@@ -142,6 +142,12 @@ def lib():
         L.l2z_prefill_q8.argtypes = [i32p, C.c_int, C.c_int, cfgp, vp, vp]
         L.l2z_q8_quantize_rows.argtypes = [fp, C.c_int, sz, fp, C.c_int, i8p, fp]
         L.l2z_q8_gemm.argtypes = [fp, i8p, fp, C.c_int, i8p, fp, sz, sz, C.c_int]
+    if hasattr(L, "l2z_transformer_batch_q8"):  # their batched step and verify pass (PREVIEW)
+        L.l2z_transformer_batch_q8.argtypes = [C.c_int, i32p, i32p, cfgp, C.POINTER(vp), vp]
+        L.l2z_verify_q8.argtypes = [i32p, C.c_int, C.c_int, C.c_float, C.c_float, fp, cfgp, vp, vp, i32p, ip]
+        L.l2z_batch_q8_time.argtypes = [C.c_int, i32p, i32p, cfgp, C.POINTER(vp), vp, C.c_int, C.POINTER(C.c_double)]
+        L.l2z_verify_q8_time.argtypes = [i32p, C.c_int, C.c_int, C.c_float, C.c_float, fp, cfgp, vp, vp, C.c_int,
+                                         C.POINTER(C.c_double)]
     L.l2z_logits_write.argtypes = [vp, fp]
     L.l2z_sample_time.argtypes = [C.c_int, C.POINTER(vp), fp, fp, fp, C.c_int, C.POINTER(C.c_double)]
     L.l2z_greedy_begin.argtypes = [vp, i32p, C.c_int]
@@ -522,6 +528,35 @@ class RunState:
                                           iters, C.byref(ms)))
         return ms.value
 
+    def _verify_q8_args(self, tokens, temperature, coins):
+        t = np.ascontiguousarray(tokens, np.int32)
+        c = None if coins is None else np.ascontiguousarray(coins, np.float32)
+        if c is not None and c.size < t.size:
+            raise ValueError(f"{c.size} coins for {t.size} rows")
+        return t, c
+
+    def verify_q8(self, tokens, pos0: int, w: Weights, temperature: float = 0.0, top_p: float = 1.0, coins=None):
+        """l2z_verify_q8 (a preview entry point of the test library): verify() on int8 group-quantized weights, or -- with a
+        temperature -- verify_sample(), coins[i] the coin of position pos0 + i.  Returns (next: int32[n], accepted)."""
+        t, c = self._verify_q8_args(tokens, temperature, coins)
+        nxt = np.zeros(max(t.size, 1), np.int32)
+        a = C.c_int(0)
+        i32p = C.POINTER(C.c_int32)
+        _chk(lib().l2z_verify_q8(t.ctypes.data_as(i32p), t.size, pos0, C.c_float(temperature), C.c_float(top_p),
+                                 None if c is None else _fp(c), C.byref(self.cfg), self.h, w.h, nxt.ctypes.data_as(i32p),
+                                 C.byref(a)))
+        return nxt[: t.size].copy(), a.value
+
+    def verify_q8_time(self, tokens, pos0: int, w: Weights, iters: int, temperature: float = 0.0, top_p: float = 1.0,
+                       coins=None) -> float:
+        """l2z_verify_q8_time: milliseconds per verify_q8 pass, device events over `iters` passes (after one untimed)."""
+        t, c = self._verify_q8_args(tokens, temperature, coins)
+        ms = C.c_double(0.0)
+        _chk(lib().l2z_verify_q8_time(t.ctypes.data_as(C.POINTER(C.c_int32)), t.size, pos0, C.c_float(temperature),
+                                      C.c_float(top_p), None if c is None else _fp(c), C.byref(self.cfg), self.h, w.h, iters,
+                                      C.byref(ms)))
+        return ms.value
+
     def verify_tree(self, tokens, parent, pos0: int, w: Weights, temperature: float = 0.0, top_p: float = 1.0, coins=None):
         """l2z_verify_tree (a preview entry point of the test library: include/llama2_hip_test.h): verify() for a TREE of
         guesses.  tokens[0] is the sequence's token at pos0 with parent[0] == -1; node i > 0 is a guess behind node
@@ -692,6 +727,24 @@ def batch_time(states, tokens, pos, w: Weights, iters: int) -> float:
     ms = C.c_double(0.0)
     _chk(lib().l2z_batch_time(n, t.ctypes.data_as(C.POINTER(C.c_int32)), p.ctypes.data_as(C.POINTER(C.c_int32)),
                               C.byref(states[0].cfg), ss, w.h, iters, C.byref(ms)))
+    return ms.value
+
+
+def transformer_batch_q8(states, tokens, pos, w: Weights) -> None:
+    """l2z_transformer_batch_q8 (a preview entry point of the test library): transformer_batch on int8 group-quantized
+    weights; argmax_batch and sample_batch work behind it."""
+    n, ss, t, p = _batch_args(states, tokens, pos)
+    cfg = states[0].cfg if n else L2ZConfig()
+    _chk(lib().l2z_transformer_batch_q8(n, t.ctypes.data_as(C.POINTER(C.c_int32)), p.ctypes.data_as(C.POINTER(C.c_int32)),
+                                        C.byref(cfg), ss, w.h))
+
+
+def batch_q8_time(states, tokens, pos, w: Weights, iters: int) -> float:
+    """l2z_batch_q8_time: milliseconds per transformer_batch_q8 step, device events over `iters` steps (after one untimed)."""
+    n, ss, t, p = _batch_args(states, tokens, pos)
+    ms = C.c_double(0.0)
+    _chk(lib().l2z_batch_q8_time(n, t.ctypes.data_as(C.POINTER(C.c_int32)), p.ctypes.data_as(C.POINTER(C.c_int32)),
+                                 C.byref(states[0].cfg), ss, w.h, iters, C.byref(ms)))
     return ms.value
 
 
@@ -1163,6 +1216,61 @@ def speculate_sample(s: RunState, w: Weights, prompt, n_steps: int, k: int, temp
         kk = min(k, steps - pos - 1)
         guesses = [int(t) for t in drafter(np.array(hist, np.int32), kk)][:kk] if kk > 0 else []
         nxt, a = s.verify_sample([hist[-1]] + guesses, pos, w, temperature, top_p, coins[g: g + 1 + len(guesses)])
+        stats["calls"] += 1
+        stats["offered"] += len(guesses)
+        stats["accepted"] += a
+        for t in nxt[: a + 1]:
+            if not (alive and pos < steps):
+                break
+            alive = emit(t)
+            stats["emitted"] += 1
+            g += 1
+            pos += alive
+    return np.array(out, np.int32), stats
+
+
+def speculate_q8(s: RunState, w: Weights, prompt, n_steps: int, k: int, drafter=None, temperature=None, top_p=None, coins=None):
+    """speculate_greedy's loop (temperature=None) or speculate_sample's on int8 group-quantized weights: RunState.prefill_q8
+    for BOS + prompt, then up to k guessed tokens verified per sweep of the weights by RunState.verify_q8.  Arguments, the
+    coins' convention (coins[g]: the coin of the g-th generated token) and the return value are theirs; the ids do not
+    depend on k or on the drafter."""
+    if not 0 <= k <= BATCH_MAX - 1:
+        raise ValueError(f"k = {k} outside [0, {BATCH_MAX - 1}]")
+    if drafter is None:
+        drafter = lookup_draft
+    sampled = temperature is not None
+    seq_len = s.cfg.seq_len
+    steps = seq_len if n_steps == 0 else max(1, min(int(n_steps), seq_len))
+    prompt = [int(t) for t in prompt][:steps]
+    if sampled:
+        top_p = 1.0 if top_p is None else top_p
+        coins = np.ascontiguousarray(coins, np.float32).reshape(-1)
+        if coins.size < steps - len(prompt):
+            raise ValueError(f"{coins.size} coins for {steps - len(prompt)} generated positions")
+    hist, out = [1], []
+    stats = {"calls": 0, "offered": 0, "accepted": 0, "emitted": 0}
+
+    def emit(t):
+        out.append(int(t))
+        hist.append(int(t))
+        return int(t) != 1
+
+    alive, pos, g = True, 0, 0  # g: generated tokens so far = the index of the next coin
+    while alive and pos < len(prompt):
+        alive = emit(prompt[pos])
+        pos += alive
+    if alive and pos < steps:
+        s.prefill_q8(np.array(hist, np.int32), 0, w)
+        alive = emit(sample_batch([s], temperature, top_p, coins[0])[0] if sampled else s.argmax())
+        g += 1
+        pos += alive
+    while alive and pos < steps:
+        kk = min(k, steps - pos - 1)
+        guesses = [int(t) for t in drafter(np.array(hist, np.int32), kk)][:kk] if kk > 0 else []
+        if sampled:
+            nxt, a = s.verify_q8([hist[-1]] + guesses, pos, w, temperature, top_p, coins[g: g + 1 + len(guesses)])
+        else:
+            nxt, a = s.verify_q8([hist[-1]] + guesses, pos, w)
         stats["calls"] += 1
         stats["offered"] += len(guesses)
         stats["accepted"] += a

@@ -63,6 +63,35 @@ __device__ inline int block_argmax_1024(const float *lg, int vocab, float *s_val
     return argmax_token(c);
 }
 
+// The batched step on int8 group-quantized weights (q8_batch.hip): its two launches that read the table.
+// Both multiply the step's m <= kBatchMax quantized rows (xq [16, n], xs [16, n / gs]: padded to the GEMM's tile, the pad
+// rows zero, as launch_q8_quantize_rows leaves them) on the int8 matrix cores with launch_q8_gemm's arithmetic, bit for bit.
+// q | k | v of a layer in one launch: q rows -> q [m, ldq] with RoPE at tab->pos[row]; the k row (RoPE) and the v row into
+// tab->kc[row] / tab->vc[row] + layer_off, head-major, at the row's position.  dim, kvd, hs: the model's dim, kv_dim and
+// head_size (hs a multiple of 4); w*_q / _k / _v: the layer's Wq [dim, n], Wk and Wv [kvd, n] and their scales
+struct Q8BatchQkvArgs {
+    const int8_t *xq;
+    const float *xs;
+    const int8_t *wq_q, *wq_k, *wq_v;
+    const float *ws_q, *ws_k, *ws_v;
+    float *q;
+    const BatchTable *tab;
+    const float2 *rope;
+    size_t layer_off, kv_head_stride;
+    int ldq, m, n, dim, kvd, hs, gs;
+};
+hipError_t launch_q8_batch_qkv(const Q8BatchQkvArgs &a, hipStream_t st);
+// the classifier [vocab, n] (vocab a multiple of 4): row r's logits -> tab->logits[r][0 .. vocab), whole
+struct Q8BatchClsArgs {
+    const int8_t *xq;
+    const float *xs;
+    const int8_t *wq;
+    const float *ws;
+    const BatchTable *tab;
+    int m, n, vocab, gs;
+};
+hipError_t launch_q8_batch_cls(const Q8BatchClsArgs &a, hipStream_t st);
+
 // l2z_sample_batch (sample_batch.hip): row b draws one token from tab->logits[b] with tab->temperature[b],
 // tab->top_p[b] and tab->coin[b] exactly as the host samplers do (llama2.zig_amd/host, main.zig:728-798), one block of
 // 1024 threads per row.  scratch: sample_scratch_floats(vocab) floats per row, row_stride apart.

@@ -22,7 +22,7 @@ void batch_free(l2z_runstate *s)
     BatchScratch *b = s->bt;
     if (b == nullptr) return;
     void *ptrs[] = {b->x, b->xn, b->q, b->att, b->h1, b->scores, b->d_tab, b->d_tokens_out, b->smp,
-                    b->v_logits, b->v_part_o, b->v_part_ml, b->d_vout};
+                    b->v_logits, b->v_part_o, b->v_part_ml, b->d_vout, b->q8_xq, b->q8_xs};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (b->h_tab) (void)hipHostFree(b->h_tab);
@@ -103,6 +103,31 @@ int verify_alloc(l2z_runstate *s)
                                              {(void **)&b->d_vout, 3 * R * 4}}));
     if (b->h_vout == nullptr) L2Z_HIP(hipHostMalloc((void **)&b->h_vout, 3 * R * 4, hipHostMallocDefault));
     b->v_seg_cap = (int)segs;
+    return L2Z_OK;
+}
+
+int q8_batch_alloc(l2z_runstate *s, int gs)
+{
+    BatchScratch *b = s->bt;
+    if (b->q8_xq != nullptr && b->q8_xs != nullptr && b->q8_gs == gs) return L2Z_OK;
+    if (b->q8_gs != gs && (b->q8_xq != nullptr || b->q8_xs != nullptr)) {   // another group size: other scale rows
+        L2Z_HIP(hipStreamSynchronize(s->stream));
+        if (b->q8_xq) { (void)hipFree(b->q8_xq); b->q8_xq = nullptr; }
+        if (b->q8_xs) { (void)hipFree(b->q8_xs); b->q8_xs = nullptr; }
+    }
+    b->q8_gs = gs;
+    const size_t R = kBatchMax, widest = (size_t)std::max(s->cfg.dim, s->cfg.hidden_dim);
+    return alloc_all("batched q8 step scratch", {{(void **)&b->q8_xq, R * widest}, {(void **)&b->q8_xs, R * (widest / (size_t)gs) * 4}});
+}
+
+int check_q8_step(const char *fn, const char *f32_entry, const l2z_runstate *s0, const l2z_weights *w)
+{
+    L2Z_CHECK(w->is_q8(), L2Z_ERR_INVALID,
+              "%s: takes int8 group-quantized weights (l2z_weights_init_q8); f32 and packed weights go to %s", fn, f32_entry);
+    L2Z_CHECK(s0->sh.hs % 4 == 0 && s0->sh.hs <= 256, L2Z_ERR_INVALID,
+              "%s: needs a head_size that is a multiple of 4, at most 256", fn);
+    L2Z_CHECK(s0->cfg.vocab_size % 4 == 0, L2Z_ERR_INVALID, "%s: needs a vocab_size that is a multiple of 4 (it is %d)", fn,
+              s0->cfg.vocab_size);
     return L2Z_OK;
 }
 
@@ -238,10 +263,72 @@ int upload_table(BatchScratch *b, const BatchTable &t, hipStream_t st, const voi
     return L2Z_OK;
 }
 
+namespace {
+
+// The step on int8 group-quantized weights.  Per layer: the rows quantized after the rmsnorm, q | k | v in one
+// launch (RoPE and the cache rows in its epilogue), the caller's attention, and the prompt pass's row launch and GEMM for Wo,
+// W1 | W3 and W2; then the classifier through the table.  Every product is the one-tile form of q8_gemm_device.h: a row's
+// bits do not depend on n, on the other rows, or on its place in the batch.
+int batch_step_q8(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *w, BatchScratch *b, LayerAttention attention)
+{
+    hipStream_t st = s0->stream;
+    const int dim = c.dim, hid = c.hidden_dim, hs = dim / c.n_heads, kvd = hs * c.n_kv_heads, gs = w->q8_gs;
+    const BatchTable *tab = b->d_tab;
+    // rows of `x` (after the rmsnorm with rms_w, if any) quantized over k, then their product with the layer's matrix
+    const auto rows = [&](const float *x, int ldx, int k, const float *rms_w) -> int {
+        L2Z_HIP(launch_q8_quantize_rows(x, ldx, n, k, rms_w, gs, b->q8_xq, b->q8_xs, st));
+        return L2Z_OK;
+    };
+    const auto gemm = [&](const l2z_weights::Q8Mat &m, int l, int d, int k, float *out, int ldo, int epi) -> int {
+        const size_t at = (size_t)l * (size_t)d * (size_t)k;
+        Q8GemmArgs a = {};
+        a.xq = b->q8_xq; a.xs = b->q8_xs; a.wq = m.q + at; a.ws = m.s + at / (size_t)gs;
+        a.out = out; a.ldo = ldo; a.res = out; a.ldres = ldo;
+        a.m = n; a.n = k; a.d = d; a.gs = gs;
+        L2Z_HIP(launch_q8_gemm(a, epi, st));
+        return L2Z_OK;
+    };
+    L2Z_HIP(launch_q8_embed_rows(w->q8_emb(), tab->tokens, dim, n, b->x, 0, nullptr, nullptr, st));  // :295
+    for (int l = 0; l < c.n_layers; l++) {
+        const size_t layer_off = (size_t)l * c.seq_len * kvd;
+        L2Z_TRY(rows(b->x, dim, dim, w->rms_att + (size_t)l * dim));  // :305
+        {   // q | k | v (:308-358): RoPE at each row's own position, k | v into each row's own caches
+            const size_t at_q = (size_t)l * dim * dim, at_kv = (size_t)l * kvd * dim;
+            Q8BatchQkvArgs a = {};
+            a.xq = b->q8_xq; a.xs = b->q8_xs;
+            a.wq_q = w->q_wq.q + at_q; a.ws_q = w->q_wq.s + at_q / (size_t)gs;
+            a.wq_k = w->q_wk.q + at_kv; a.ws_k = w->q_wk.s + at_kv / (size_t)gs;
+            a.wq_v = w->q_wv.q + at_kv; a.ws_v = w->q_wv.s + at_kv / (size_t)gs;
+            a.q = b->q; a.ldq = dim; a.tab = tab; a.rope = s0->rope;
+            a.layer_off = layer_off; a.kv_head_stride = (size_t)c.seq_len * hs;
+            a.m = n; a.n = dim; a.dim = dim; a.kvd = kvd; a.hs = hs; a.gs = gs;
+            L2Z_HIP(launch_q8_batch_qkv(a, st));
+        }
+        L2Z_TRY(attention(layer_off));  // :361-389
+        L2Z_TRY(rows(b->att, b->ld_att, dim, nullptr));
+        L2Z_TRY(gemm(w->q_wo, l, dim, dim, b->x, dim, EPI_RESID));  // :392-395
+        L2Z_TRY(rows(b->x, dim, dim, w->rms_ffn + (size_t)l * dim));  // :398
+        L2Z_TRY(gemm(w->q_w13, l, 2 * hid, dim, b->h1, b->ld_h1, EPI_SWIGLU));  // :405-416
+        L2Z_TRY(rows(b->h1, b->ld_h1, hid, nullptr));
+        L2Z_TRY(gemm(w->q_w2, l, dim, hid, b->x, dim, EPI_RESID));  // :419-422
+    }
+    L2Z_TRY(rows(b->x, dim, dim, w->rms_final));  // :426
+    {   // :429: each row's logits straight into its runstate
+        Q8BatchClsArgs a = {};
+        a.xq = b->q8_xq; a.xs = b->q8_xs; a.wq = w->q_cls.q; a.ws = w->q_cls.s; a.tab = tab;
+        a.m = n; a.n = dim; a.vocab = c.vocab_size; a.gs = gs;
+        L2Z_HIP(launch_q8_batch_cls(a, st));
+    }
+    return L2Z_OK;
+}
+
+}  // namespace
+
 // Every product is the one-tile short-prompt form at P = n whatever n is (launch_batch_skinny): a row's bits do not depend
 // on n, on the other rows, or on its place in the batch.
 int batch_step(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *w, BatchScratch *b, LayerAttention attention)
 {
+    if (w->is_q8()) return batch_step_q8(n, c, s0, w, b, attention);
     hipStream_t st = s0->stream;
     const int dim = c.dim, hid = c.hidden_dim, hs = dim / c.n_heads, kvd = hs * c.n_kv_heads;
     const BatchTable *tab = b->d_tab;
@@ -318,21 +405,27 @@ int timed_loop(hipStream_t st, int iters, double *out_ms, FnRef<int()> pass)
 
 using namespace l2z;
 
-extern "C" int l2z_transformer_batch(int n, const int32_t *tokens, const int32_t *pos, const l2z_config *config,
-                                     l2z_runstate *const *states, const l2z_weights *w)
+namespace {
+
+// l2z_transformer_batch (q8 false) and l2z_transformer_batch_q8 (true): one body, the weights' family apart
+int transformer_batch_call(const char *fn, bool q8, int n, const int32_t *tokens, const int32_t *pos, const l2z_config *config,
+                           l2z_runstate *const *states, const l2z_weights *w)
 {
     L2Z_TRY(no_device_check());
-    L2Z_CHECK(tokens != nullptr && pos != nullptr && config != nullptr && w != nullptr, L2Z_ERR_INVALID,
-              "l2z_transformer_batch: null argument");
-    L2Z_TRY(check_states("l2z_transformer_batch", n, states, config));
+    L2Z_CHECK(tokens != nullptr && pos != nullptr && config != nullptr && w != nullptr, L2Z_ERR_INVALID, "%s: null argument", fn);
+    L2Z_TRY(check_states(fn, n, states, config));
+    if (q8) L2Z_TRY(check_q8_step(fn, "l2z_transformer_batch", states[0], w));
     for (int i = 0; i < n; i++) {
-        L2Z_TRY(check_pair(config, states[i], w));
-        L2Z_TRY(check_row("l2z_transformer_batch", i, tokens[i], pos[i], 1, *config));
+        L2Z_TRY(check_pair(config, states[i], w, false, q8));
+        L2Z_TRY(check_row(fn, i, tokens[i], pos[i], 1, *config));
     }
-    L2Z_TRY(prefill_check(config, states[0]));
-    L2Z_CHECK(states[0]->sh.hs <= 256, L2Z_ERR_INVALID, "l2z_transformer_batch: head_size above 256");
+    if (!q8) {
+        L2Z_TRY(prefill_check(config, states[0]));
+        L2Z_CHECK(states[0]->sh.hs <= 256, L2Z_ERR_INVALID, "%s: head_size above 256", fn);
+    }
     L2Z_HIP(hipSetDevice(states[0]->device));
     L2Z_TRY(batch_alloc(states[0]));
+    if (q8) L2Z_TRY(q8_batch_alloc(states[0], w->q8_gs));
     BatchScratch *b = states[0]->bt;
     BatchTable t = {};
     for (int i = 0; i < n; i++) {
@@ -355,6 +448,21 @@ extern "C" int l2z_transformer_batch(int n, const int32_t *tokens, const int32_t
     L2Z_TRY(release_streams(b, n, states));
     for (int i = 0; i < n; i++) logits_whole(states[i], pos[i] + 1);
     return L2Z_OK;
+}
+
+}  // namespace
+
+extern "C" int l2z_transformer_batch(int n, const int32_t *tokens, const int32_t *pos, const l2z_config *config,
+                                     l2z_runstate *const *states, const l2z_weights *w)
+{
+    return transformer_batch_call("l2z_transformer_batch", false, n, tokens, pos, config, states, w);
+}
+
+// PREVIEW (include/llama2_hip_test.h): l2z_transformer_batch's contract on int8 group-quantized weights
+extern "C" int l2z_transformer_batch_q8(int n, const int32_t *tokens, const int32_t *pos, const l2z_config *config,
+                                        l2z_runstate *const *states, const l2z_weights *w)
+{
+    return transformer_batch_call("l2z_transformer_batch_q8", true, n, tokens, pos, config, states, w);
 }
 
 extern "C" int l2z_argmax_batch(int n, l2z_runstate *const *states, int32_t *out_tokens)
@@ -535,4 +643,14 @@ extern "C" int l2z_batch_time(int n, const int32_t *tokens, const int32_t *pos, 
     L2Z_TRY(l2z_transformer_batch(n, tokens, pos, config, states, w));  // validates, allocates
     hipStream_t st = states[0]->stream;
     return timed_loop(st, iters, out_ms, [&] { return l2z_transformer_batch(n, tokens, pos, config, states, w); });
+}
+
+// ... and its twin on int8 group-quantized weights (scripts/q8_batch_bench.py)
+extern "C" int l2z_batch_q8_time(int n, const int32_t *tokens, const int32_t *pos, const l2z_config *config,
+                                 l2z_runstate *const *states, const l2z_weights *w, int iters, double *out_ms)
+{
+    L2Z_CHECK(iters >= 1 && out_ms != nullptr, L2Z_ERR_INVALID, "l2z_batch_q8_time: bad arguments");
+    L2Z_TRY(l2z_transformer_batch_q8(n, tokens, pos, config, states, w));  // validates, allocates
+    hipStream_t st = states[0]->stream;
+    return timed_loop(st, iters, out_ms, [&] { return l2z_transformer_batch_q8(n, tokens, pos, config, states, w); });
 }

@@ -34,12 +34,23 @@ struct BatchScratch {
                                                // next[0 .. rows) | accepted[0 .. n); l2z_verify_tree: next[0 .. n) | accepted |
                                                // path[0 .. accepted])
     int v_seg_cap = 0, v_rows = 0;   // v_rows: rows of the last call (l2z_verify_logits_read)
+    // q8_batch_alloc: the step's quantized rows on int8 group-quantized weights, [kBatchMax, max(dim, hidden_dim)] int8 and
+    // their scales at group size q8_gs (a call with another group size re-makes them)
+    int8_t *q8_xq = nullptr;
+    float *q8_xs = nullptr;
+    int q8_gs = 0;
 };
 
 // s->bt and what a call needs in it beyond the step's own: the sampler's scratch, the verify family's (each on first use)
 int batch_alloc(l2z_runstate *s);
 int sample_alloc(l2z_runstate *s);
 int verify_alloc(l2z_runstate *s);
+int q8_batch_alloc(l2z_runstate *s, int gs);
+
+// What a call of the batched step on int8 group-quantized weights (l2z_transformer_batch_q8, l2z_verify_q8) asks beyond
+// check_pair(..., q8_ok = true): such weights -- f32 and packed ones go to `f32_entry` --, and a shape the step's launches
+// take; fn: the entry point a message names
+int check_q8_step(const char *fn, const char *f32_entry, const l2z_runstate *s0, const l2z_weights *w);
 
 // hipMalloc of every buffer of the list that has a size and is not there yet.  A failure leaves that pointer null, names
 // `what` and the size in the error, and is L2Z_ERR_OOM where the device is out of memory; what was allocated before it
@@ -142,7 +153,8 @@ template <class A> A attention_args(const l2z_config &c, const BatchScratch *b)
     return a;
 }
 
-// One step of the n rows of b->d_tab on s0's stream, each layer's attention by `attention`
+// One step of the n rows of b->d_tab on s0's stream, each layer's attention by `attention`.  On int8 group-quantized
+// weights (the caller has run q8_batch_alloc): the quantized step, DESIGN.md 4.25
 int batch_step(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *w, BatchScratch *b, LayerAttention attention);
 
 // The rows' draws (l2z_sample_batch's launch) from tab->logits[i] with the table's temperature, top_p and coin -> out[0 .. n)

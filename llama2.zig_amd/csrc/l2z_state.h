@@ -102,7 +102,7 @@ struct l2z_weights {
     // unsharded, has no f32 matrix and no packed slot -- blob is null and of the pointers above only rms_att, rms_ffn and
     // rms_final stand, inside q8_blob: one allocation of the three norm vectors and then, per tensor, its values
     // [layer][row][col] and its scales [layer][row][col / gs], W1 | W3 row-interleaved in one slot like the f32 layout.
-    // Only the single-sequence decode takes it (check_pair's q8_ok)
+    // Only the single-sequence decode and the q8 entry points of their own take it (check_pair's q8_ok)
     struct Q8Mat {
         const int8_t *q = nullptr;
         const float *s = nullptr;

@@ -5,6 +5,7 @@
 // A row's results depend on its own sequence's rows and caches and on the chunk's table -- never on what the other
 // sequences hold (no reduction here crosses a sequence, no block shares state between two).
 #include "prefill_common.h"
+#include "rope_device.h"
 
 namespace l2z {
 namespace {
@@ -31,24 +32,14 @@ __global__ __launch_bounds__(kPfBlock) void ragged_rope_scatter(float *q, int ld
         if (f < dim) {
             float *p = q + (size_t)row * ldq + f;
             const v4f x = *(const v4f *)p;
-            const v4f cs = *(const v4f *)(rope + (size_t)pos * (size_t)(hs >> 1) + ((f % hs) >> 1));   // {c0, s0, c1, s1}
-            v4f r;
-            r.x = x.x * cs.x - x.y * cs.y; r.y = x.x * cs.y + x.y * cs.x;
-            r.z = x.z * cs.z - x.w * cs.w; r.w = x.z * cs.w + x.w * cs.z;
-            *(v4f *)p = r;
+            *(v4f *)p = rope_rotate4(x, rope_cs4(rope, pos, hs, f));
             continue;
         }
         f -= dim;
         const bool is_k = f < kvd;
         if (!is_k) f -= kvd;
         v4f x = *(const v4f *)((is_k ? k : v) + (size_t)row * kvd + f);
-        if (is_k) {
-            const v4f cs = *(const v4f *)(rope + (size_t)pos * (size_t)(hs >> 1) + ((f % hs) >> 1));
-            v4f r;
-            r.x = x.x * cs.x - x.y * cs.y; r.y = x.x * cs.y + x.y * cs.x;
-            r.z = x.z * cs.z - x.w * cs.w; r.w = x.z * cs.w + x.w * cs.z;
-            x = r;
-        }
+        if (is_k) x = rope_rotate4(x, rope_cs4(rope, pos, hs, f));
         // head-major cache [kv head][seq_len][head_size]
         float *dst = (is_k ? sq.kc : sq.vc) + cache_off + (size_t)(f / hs) * kv_head_stride + (size_t)(f % hs);
         *(v4f *)dst = x;

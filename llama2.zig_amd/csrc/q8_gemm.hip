@@ -3,47 +3,21 @@
 //
 //   out[t][i] = sum over groups g of  f32(I[t][i][g]) * ws[i][g] * xs[t][g],   I = sum over the group of wq * xq   (int32, exact)
 //
-// Both operands are K-contiguous int8 rows, so a lane's MFMA operand is one load from either matrix: the weight rows are
-// the A side (the tile's 16 rows), the token rows the B side (its 16 columns).  One MFMA into a zeroed tile is exactly one
-// group's I for 16 x 16 (row, token) pairs -- v_mfma_i32_16x16x64_i8 at group size 64 (16 bytes a lane from either
-// matrix), v_mfma_i32_16x16x32_i8 at 32 (8 bytes) --, so a group never shares an MFMA with another and K is any whole
-// number of groups (dim 288 at group size 32: nine).  A and B of a lane cover the same 16 (8) values of the group, so the
-// tile is the sum over the whole group whatever order the instruction takes them in.  The result tile has the token on
-// the lane (lane & 15) and four consecutive weight rows in its registers (4 (lane >> 4) + r): after each group the four
-// int32 are converted, scaled by their rows' ws[g] and the token's xs[g] -- (f32(I) * ws) * xs, the decode's order, the
-// second product fused into the sum -- and added to the lane's four f32 sums.  Four consecutive output features of one
-// token a lane: a 16-byte store, and two W1 | W3 pairs of the interleaved slot, so SwiGLU is lane-local.
+// The operand layout, the K loop and both summation orders are q8_gemm_device.h's, which the batched step's launches
+// (q8_batch.hip) run too.  A lane ends with four consecutive output features of one token: a 16-byte store, and two
+// W1 | W3 pairs of the interleaved slot, so SwiGLU is lane-local.
 //
-// A block of eight waves owns 16 weight rows and up to NT tiles of 16 tokens.  The waves split K: wave w takes groups w,
-// w + 8, ... in increasing order (together the eight read 512 (256) contiguous bytes of each of the 16 rows per step),
-// leaves its partial sums in LDS, and the sums of a tile are then added in wave order 0 .. 7 by the wave that stores
-// it.  Which wave takes which group and both orders are functions of n and gs alone: the same bits from run to run,
-// whatever the other rows of the call hold and however many there are.  No atomics.
-#include "q8_device.h"
+// A block of eight waves owns 16 weight rows and up to NT tiles of 16 tokens.  Which wave takes which group and both
+// orders are functions of n and gs alone: the same bits from run to run, whatever the other rows of the call hold and
+// however many there are.  No atomics.
+#include "q8_gemm_device.h"
 
 namespace l2z {
 namespace {
 
-constexpr int kQgWaves = 8;               // K ranges of a block, one a wave
-constexpr int kQgBlock = kQgWaves * kWave;
-constexpr int kQgBatch = 4;               // groups a wave requests before it multiplies the first
-
-template <int GS> struct Q8Frag;
-template <> struct Q8Frag<64> {
-    typedef v4i T;
-    static __device__ __forceinline__ T zero() { return v4i{0, 0, 0, 0}; }
-    static __device__ __forceinline__ v4i mfma(T a, T b) { return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, v4i{0, 0, 0, 0}, 0, 0, 0); }
-};
-template <> struct Q8Frag<32> {
-    typedef long T;
-    static __device__ __forceinline__ T zero() { return 0; }
-    static __device__ __forceinline__ v4i mfma(T a, T b) { return __builtin_amdgcn_mfma_i32_16x16x32_i8(a, b, v4i{0, 0, 0, 0}, 0, 0, 0); }
-};
-
 template <int EPI, int GS, int NT>
 __global__ __launch_bounds__(kQgBlock) void q8_gemm_kernel(const Q8GemmArgs a)
 {
-    typedef typename Q8Frag<GS>::T Frag;
     constexpr int LB = GS / 4;  // bytes of a group a lane holds
     __shared__ v4f part[kQgWaves * NT * kWave];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -63,44 +37,11 @@ __global__ __launch_bounds__(kQgBlock) void q8_gemm_kernel(const Q8GemmArgs a)
     const float *xsp = a.xs + (size_t)(tile0 * kQ8GemmTile + col) * (size_t)ng;
 
     v4f acc[NT];
-#pragma unroll
-    for (int j = 0; j < NT; j++) acc[j] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
-    for (int g0 = wave; g0 < ng; g0 += kQgWaves * kQgBatch) {
-        Frag wa[kQgBatch];
-        v4f wsc[kQgBatch];
-#pragma unroll
-        for (int u = 0; u < kQgBatch; u++) {
-            const int g = g0 + kQgWaves * u;
-            const bool in = g < ng;  // (wave-uniform)
-            wa[u] = (in && a_in) ? __builtin_nontemporal_load((const Frag *)(ap + (size_t)(in ? g : 0) * GS)) : Q8Frag<GS>::zero();
-            const int gg = in ? g : 0;
-            wsc[u] = v4f{wsp[gg], wsp[ng + gg], wsp[2 * ng + gg], wsp[3 * ng + gg]};
-        }
-        // Straight-line, so that the batch's token loads are all requested before the first MFMA waits for one: a group
-        // past the row end multiplies the zero fragment against group 0 (its terms are +0: the sums keep their bits), a
-        // tile past the chunk's last is tile 0 again (its sums are never stored)
-#pragma unroll
-        for (int u = 0; u < kQgBatch; u++) {
-            const int g = g0 + kQgWaves * u < ng ? g0 + kQgWaves * u : 0;
-#pragma unroll
-            for (int j = 0; j < NT; j++) {
-                const int jj = j < nt ? j : 0;
-                const Frag xb = *(const Frag *)(bp + (size_t)jj * kQ8GemmTile * (size_t)n + (size_t)g * GS);
-                const float xs = xsp[(size_t)jj * kQ8GemmTile * (size_t)ng + g];
-                const v4i I = Q8Frag<GS>::mfma(wa[u], xb);
-                const v4f p = v4f{(float)I.x, (float)I.y, (float)I.z, (float)I.w} * wsc[u];
-                acc[j] = __builtin_elementwise_fma(p, v4f{xs, xs, xs, xs}, acc[j]);
-            }
-        }
-    }
+    q8_gemm_wave_sums<GS, NT>(ap, a_in, wsp, bp, xsp, n, nt, wave, acc);
     // the K ranges' sums of a tile, added in wave order by the wave that stores the tile
-#pragma unroll
-    for (int j = 0; j < NT; j++) part[(wave * NT + j) * kWave + lane] = acc[j];
-    __syncthreads();
+    q8_gemm_stash<NT>(part, acc, wave, lane);
     for (int j = wave; j < nt; j += kQgWaves) {
-        v4f v = part[j * kWave + lane];
-#pragma unroll
-        for (int w = 1; w < kQgWaves; w++) v += part[(w * NT + j) * kWave + lane];
+        v4f v = q8_gemm_tile_sum<NT>(part, j, lane);
         const int t = (tile0 + j) * kQ8GemmTile + col;
         if (t >= a.m || !o_in) continue;
         if (EPI == EPI_SWIGLU) {  // rows 2p, 2p + 1 = W1 row p, W3 row p: two gated values (main.zig:411-416)

@@ -33,11 +33,13 @@ int check_targets(const char *fn, const l2z_config *config, int n, l2z_runstate 
     return L2Z_OK;
 }
 
-// ... for a pass on one runstate
-int check_target(const char *fn, const l2z_config *config, l2z_runstate *s, const l2z_weights *w)
+// ... for a pass on one runstate; q8: the pass takes int8 group-quantized weights, and only those (l2z_verify_q8)
+int check_target(const char *fn, const l2z_config *config, l2z_runstate *s, const l2z_weights *w, bool q8 = false)
 {
     L2Z_CHECK(s->comm == nullptr && s->sh.world == 1, L2Z_ERR_INVALID, "%s: the runstate is a shard", fn);
-    return check_targets(fn, config, 1, &s, w);
+    if (!q8) return check_targets(fn, config, 1, &s, w);
+    L2Z_TRY(check_q8_step(fn, "l2z_verify and l2z_verify_sample", s, w));
+    return check_pair(config, s, w, false, true);
 }
 
 // ---- what the paths share after the checks ----
@@ -79,19 +81,21 @@ void verify_done(l2z_runstate *s, int rows)
 
 // ---- l2z_verify, l2z_verify_sample: n consecutive positions of ONE sequence in one sweep ----
 
-// The checks, then the table, the pass, the verdict and its copy back on s's stream; no sync.
+// The checks, then the table, the pass, the verdict and its copy back on s's stream; no sync.  q8: the step on int8
+// group-quantized weights (batch_step's other form); everything around it is the same.
 int verify_enqueue(const char *fn, const int32_t *tokens, int n, int pos0, const VerifyDraw &draw, const l2z_config *config,
-                   l2z_runstate *s, const l2z_weights *w)
+                   l2z_runstate *s, const l2z_weights *w, bool q8)
 {
     L2Z_TRY(no_device_check());
     L2Z_CHECK(tokens != nullptr && config != nullptr && s != nullptr && w != nullptr, L2Z_ERR_INVALID, "%s: null argument",
               fn);
     L2Z_CHECK(n >= 1 && n <= kBatchMax, L2Z_ERR_INVALID, "%s: n_tokens = %d outside [1, %d]", fn, n, kBatchMax);
-    L2Z_TRY(check_target(fn, config, s, w));
+    L2Z_TRY(check_target(fn, config, s, w, q8));
     L2Z_TRY(check_positions(fn, "", "positions", pos0, n, config->seq_len));
     L2Z_TRY(check_tokens(fn, "", tokens, n, config->vocab_size));
     if (draw.sampled()) L2Z_TRY(check_coins(fn, draw.coins, 0, n));
     L2Z_TRY(verify_scratch(s, draw.sampled()));
+    if (q8) L2Z_TRY(q8_batch_alloc(s, w->q8_gs));
     BatchScratch *b = s->bt;
     const int vocab = config->vocab_size;
     BatchTable t = {};
@@ -126,12 +130,12 @@ int verify_enqueue(const char *fn, const int32_t *tokens, int n, int pos0, const
 
 // The call under either name: l2z_verify is the draw at temperature 0
 int verify_call(const char *fn, const int32_t *tokens, int n, int pos0, const VerifyDraw &draw, const l2z_config *config,
-                l2z_runstate *s, const l2z_weights *w, int32_t *out_next, int *out_accepted)
+                l2z_runstate *s, const l2z_weights *w, int32_t *out_next, int *out_accepted, bool q8 = false)
 {
     L2Z_TRY(no_device_check());
     L2Z_CHECK(out_next != nullptr && out_accepted != nullptr, L2Z_ERR_INVALID, "%s: null argument", fn);
     L2Z_TRY(check_draw(fn, -1, draw.temperature, draw.top_p, draw.coins));
-    L2Z_TRY(verify_enqueue(fn, tokens, n, pos0, draw, config, s, w));
+    L2Z_TRY(verify_enqueue(fn, tokens, n, pos0, draw, config, s, w, q8));
     BatchScratch *b = s->bt;
     L2Z_HIP(hipStreamSynchronize(s->stream));
     memcpy(out_next, b->h_vout, (size_t)n * 4);
@@ -143,13 +147,13 @@ int verify_call(const char *fn, const int32_t *tokens, int n, int pos0, const Ve
 // Testing support: one call, then `iters` passes back to back (the rows' ids, the verdict and its copy included, no sync),
 // timed by device events on the runstate's stream.  The passes rewrite the same KV rows.
 int verify_time(const char *fn, const int32_t *tokens, int n, int pos0, const VerifyDraw &draw, const l2z_config *config,
-                l2z_runstate *s, const l2z_weights *w, int iters, double *out_ms)
+                l2z_runstate *s, const l2z_weights *w, int iters, double *out_ms, bool q8 = false)
 {
     L2Z_CHECK(iters >= 1 && out_ms != nullptr, L2Z_ERR_INVALID, "%s_time: bad arguments", fn);
     int32_t next[kBatchMax];
     int acc = 0;
-    L2Z_TRY(verify_call(fn, tokens, n, pos0, draw, config, s, w, next, &acc));  // validates, allocates
-    return timed_loop(s->stream, iters, out_ms, [&] { return verify_enqueue(fn, tokens, n, pos0, draw, config, s, w); });
+    L2Z_TRY(verify_call(fn, tokens, n, pos0, draw, config, s, w, next, &acc, q8));  // validates, allocates
+    return timed_loop(s->stream, iters, out_ms, [&] { return verify_enqueue(fn, tokens, n, pos0, draw, config, s, w, q8); });
 }
 
 }  // namespace
@@ -185,6 +189,25 @@ extern "C" int l2z_verify_sample_time(const int32_t *tokens, int n_tokens, int p
 {
     return verify_time("l2z_verify_sample", tokens, n_tokens, pos0, VerifyDraw{temperature, top_p, coins}, config, s, w, iters,
                        out_ms);
+}
+
+// PREVIEW (include/llama2_hip_test.h): l2z_verify's contract -- temperature 0, coins NULL -- or l2z_verify_sample's on int8
+// group-quantized weights
+extern "C" int l2z_verify_q8(const int32_t *tokens, int n_tokens, int pos0, float temperature, float top_p, const float *coins,
+                             const l2z_config *config, l2z_runstate *s, const l2z_weights *w, int32_t *out_next,
+                             int *out_accepted)
+{
+    return verify_call("l2z_verify_q8", tokens, n_tokens, pos0, VerifyDraw{temperature, top_p, coins}, config, s, w, out_next,
+                       out_accepted, true);
+}
+
+// scripts/q8_batch_bench.py
+extern "C" int l2z_verify_q8_time(const int32_t *tokens, int n_tokens, int pos0, float temperature, float top_p,
+                                  const float *coins, const l2z_config *config, l2z_runstate *s, const l2z_weights *w, int iters,
+                                  double *out_ms)
+{
+    return verify_time("l2z_verify_q8", tokens, n_tokens, pos0, VerifyDraw{temperature, top_p, coins}, config, s, w, iters,
+                       out_ms, true);
 }
 
 // Testing support (include/llama2_hip_test.h): row `row` of the last l2z_verify call's logits matrix
