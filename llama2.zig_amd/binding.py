@@ -474,17 +474,34 @@ class RunState:
         """l2z_score_slab_set (test hook): vocabulary rows per slab of score()'s classifier product, 0: the default."""
         _chk(lib().l2z_score_slab_set(self.h, slab_cols))
 
+    def _verify_call(self, name: str, tokens, pos0: int, w: Weights, draw=None, iters=None):
+        """One call of the chain verify family: lib().<name>(tokens, n, pos0, [temperature, top_p, coins,] config, runstate,
+        weights, ...) with draw = (temperature, top_p, coins) where the entry point takes a draw, and behind them next and
+        accepted -> (next: int32[n], accepted), or -- iters -- iters and the time -> milliseconds per pass."""
+        t = np.ascontiguousarray(tokens, np.int32)
+        i32p = C.POINTER(C.c_int32)
+        args = [t.ctypes.data_as(i32p), t.size, pos0]
+        if draw is not None:
+            temperature, top_p, coins = draw
+            c = None if coins is None else np.ascontiguousarray(coins, np.float32)
+            if c is not None and c.size < t.size:
+                raise ValueError(f"{c.size} coins for {t.size} rows")
+            args += [C.c_float(temperature), C.c_float(top_p), None if c is None else _fp(c)]
+        args += [C.byref(self.cfg), self.h, w.h]
+        if iters is not None:
+            ms = C.c_double(0.0)
+            _chk(getattr(lib(), name)(*args, iters, C.byref(ms)))
+            return ms.value
+        nxt = np.zeros(max(t.size, 1), np.int32)
+        a = C.c_int(0)
+        _chk(getattr(lib(), name)(*args, nxt.ctypes.data_as(i32p), C.byref(a)))
+        return nxt[: t.size].copy(), a.value
+
     def verify(self, tokens, pos0: int, w: Weights):
         """l2z_verify: tokens[0] is the sequence's token at pos0, tokens[1:] are guesses for the positions after it.
         Returns (next: int32[n], accepted): next[i] = the model's argmax after tokens[:i + 1]; next[:accepted + 1] are
         the sequence's next tokens and the runstate stands at pos0 + accepted + 1 with the logits behind next[accepted]."""
-        t = np.ascontiguousarray(tokens, np.int32)
-        nxt = np.zeros(max(t.size, 1), np.int32)
-        a = C.c_int(0)
-        i32p = C.POINTER(C.c_int32)
-        _chk(lib().l2z_verify(t.ctypes.data_as(i32p), t.size, pos0, C.byref(self.cfg), self.h, w.h, nxt.ctypes.data_as(i32p),
-                              C.byref(a)))
-        return nxt[: t.size].copy(), a.value
+        return self._verify_call("l2z_verify", tokens, pos0, w)
 
     def verify_logits(self, row: int) -> np.ndarray:
         """l2z_verify_logits_read (test hook): row `row` of the last verify() call's logits matrix."""
@@ -494,68 +511,27 @@ class RunState:
 
     def verify_time(self, tokens, pos0: int, w: Weights, iters: int) -> float:
         """l2z_verify_time: milliseconds per verify pass, device events over `iters` passes (after one untimed)."""
-        t = np.ascontiguousarray(tokens, np.int32)
-        ms = C.c_double(0.0)
-        _chk(lib().l2z_verify_time(t.ctypes.data_as(C.POINTER(C.c_int32)), t.size, pos0, C.byref(self.cfg), self.h, w.h, iters,
-                                   C.byref(ms)))
-        return ms.value
+        return self._verify_call("l2z_verify_time", tokens, pos0, w, None, iters)
 
     def verify_sample(self, tokens, pos0: int, w: Weights, temperature: float, top_p: float, coins):
         """l2z_verify_sample: verify() with next[i] drawn as sample_batch draws it from row i's logits with
         (temperature, top_p, coins[i]); coins[i] is the coin of position pos0 + i (None: NULL, for temperature 0).
         Returns (next: int32[n], accepted) as verify()."""
-        t = np.ascontiguousarray(tokens, np.int32)
-        c = None if coins is None else np.ascontiguousarray(coins, np.float32)
-        if c is not None and c.size < t.size:
-            raise ValueError(f"{c.size} coins for {t.size} rows")
-        nxt = np.zeros(max(t.size, 1), np.int32)
-        a = C.c_int(0)
-        i32p = C.POINTER(C.c_int32)
-        _chk(lib().l2z_verify_sample(t.ctypes.data_as(i32p), t.size, pos0, C.c_float(temperature), C.c_float(top_p),
-                                     None if c is None else _fp(c), C.byref(self.cfg), self.h, w.h,
-                                     nxt.ctypes.data_as(i32p), C.byref(a)))
-        return nxt[: t.size].copy(), a.value
+        return self._verify_call("l2z_verify_sample", tokens, pos0, w, (temperature, top_p, coins))
 
     def verify_sample_time(self, tokens, pos0: int, w: Weights, temperature: float, top_p: float, coins, iters: int) -> float:
         """l2z_verify_sample_time: milliseconds per sampled verify pass, device events over `iters` passes."""
-        t = np.ascontiguousarray(tokens, np.int32)
-        c = None if coins is None else np.ascontiguousarray(coins, np.float32)
-        if c is not None and c.size < t.size:
-            raise ValueError(f"{c.size} coins for {t.size} rows")
-        ms = C.c_double(0.0)
-        _chk(lib().l2z_verify_sample_time(t.ctypes.data_as(C.POINTER(C.c_int32)), t.size, pos0, C.c_float(temperature),
-                                          C.c_float(top_p), None if c is None else _fp(c), C.byref(self.cfg), self.h, w.h,
-                                          iters, C.byref(ms)))
-        return ms.value
-
-    def _verify_q8_args(self, tokens, temperature, coins):
-        t = np.ascontiguousarray(tokens, np.int32)
-        c = None if coins is None else np.ascontiguousarray(coins, np.float32)
-        if c is not None and c.size < t.size:
-            raise ValueError(f"{c.size} coins for {t.size} rows")
-        return t, c
+        return self._verify_call("l2z_verify_sample_time", tokens, pos0, w, (temperature, top_p, coins), iters)
 
     def verify_q8(self, tokens, pos0: int, w: Weights, temperature: float = 0.0, top_p: float = 1.0, coins=None):
         """l2z_verify_q8 (a preview entry point of the test library): verify() on int8 group-quantized weights, or -- with a
         temperature -- verify_sample(), coins[i] the coin of position pos0 + i.  Returns (next: int32[n], accepted)."""
-        t, c = self._verify_q8_args(tokens, temperature, coins)
-        nxt = np.zeros(max(t.size, 1), np.int32)
-        a = C.c_int(0)
-        i32p = C.POINTER(C.c_int32)
-        _chk(lib().l2z_verify_q8(t.ctypes.data_as(i32p), t.size, pos0, C.c_float(temperature), C.c_float(top_p),
-                                 None if c is None else _fp(c), C.byref(self.cfg), self.h, w.h, nxt.ctypes.data_as(i32p),
-                                 C.byref(a)))
-        return nxt[: t.size].copy(), a.value
+        return self._verify_call("l2z_verify_q8", tokens, pos0, w, (temperature, top_p, coins))
 
     def verify_q8_time(self, tokens, pos0: int, w: Weights, iters: int, temperature: float = 0.0, top_p: float = 1.0,
                        coins=None) -> float:
         """l2z_verify_q8_time: milliseconds per verify_q8 pass, device events over `iters` passes (after one untimed)."""
-        t, c = self._verify_q8_args(tokens, temperature, coins)
-        ms = C.c_double(0.0)
-        _chk(lib().l2z_verify_q8_time(t.ctypes.data_as(C.POINTER(C.c_int32)), t.size, pos0, C.c_float(temperature),
-                                      C.c_float(top_p), None if c is None else _fp(c), C.byref(self.cfg), self.h, w.h, iters,
-                                      C.byref(ms)))
-        return ms.value
+        return self._verify_call("l2z_verify_q8_time", tokens, pos0, w, (temperature, top_p, coins), iters)
 
     def verify_tree(self, tokens, parent, pos0: int, w: Weights, temperature: float = 0.0, top_p: float = 1.0, coins=None):
         """l2z_verify_tree (a preview entry point of the test library: include/llama2_hip_test.h): verify() for a TREE of
@@ -703,13 +679,23 @@ def _batch_args(states, tokens, pos):
     return n, ss, t, p
 
 
+def _batch_call(name: str, states, tokens, pos, w: Weights, iters=None):
+    """lib().<name>(n, tokens, pos, config, states, weights), or -- iters -- with iters and the time behind them ->
+    milliseconds per step.  The config is states[0]'s."""
+    n, ss, t, p = _batch_args(states, tokens, pos)
+    i32p = C.POINTER(C.c_int32)
+    args = (n, t.ctypes.data_as(i32p), p.ctypes.data_as(i32p), C.byref(states[0].cfg if n else L2ZConfig()), ss, w.h)
+    if iters is None:
+        return _chk(getattr(lib(), name)(*args))
+    ms = C.c_double(0.0)
+    _chk(getattr(lib(), name)(*args, iters, C.byref(ms)))
+    return ms.value
+
+
 def transformer_batch(states, tokens, pos, w: Weights) -> None:
     """l2z_transformer_batch: transformer(tokens[i], pos[i]) on states[i] for every i, one sweep of the weights.
     The config is states[0]'s (the call checks that every runstate and the weights share it)."""
-    n, ss, t, p = _batch_args(states, tokens, pos)
-    cfg = states[0].cfg if n else L2ZConfig()
-    _chk(lib().l2z_transformer_batch(n, t.ctypes.data_as(C.POINTER(C.c_int32)), p.ctypes.data_as(C.POINTER(C.c_int32)),
-                                     C.byref(cfg), ss, w.h))
+    _batch_call("l2z_transformer_batch", states, tokens, pos, w)
 
 
 def argmax_batch(states) -> np.ndarray:
@@ -723,29 +709,18 @@ def argmax_batch(states) -> np.ndarray:
 
 def batch_time(states, tokens, pos, w: Weights, iters: int) -> float:
     """l2z_batch_time: milliseconds per batched step, device events over `iters` steps (after one untimed)."""
-    n, ss, t, p = _batch_args(states, tokens, pos)
-    ms = C.c_double(0.0)
-    _chk(lib().l2z_batch_time(n, t.ctypes.data_as(C.POINTER(C.c_int32)), p.ctypes.data_as(C.POINTER(C.c_int32)),
-                              C.byref(states[0].cfg), ss, w.h, iters, C.byref(ms)))
-    return ms.value
+    return _batch_call("l2z_batch_time", states, tokens, pos, w, iters)
 
 
 def transformer_batch_q8(states, tokens, pos, w: Weights) -> None:
     """l2z_transformer_batch_q8 (a preview entry point of the test library): transformer_batch on int8 group-quantized
     weights; argmax_batch and sample_batch work behind it."""
-    n, ss, t, p = _batch_args(states, tokens, pos)
-    cfg = states[0].cfg if n else L2ZConfig()
-    _chk(lib().l2z_transformer_batch_q8(n, t.ctypes.data_as(C.POINTER(C.c_int32)), p.ctypes.data_as(C.POINTER(C.c_int32)),
-                                        C.byref(cfg), ss, w.h))
+    _batch_call("l2z_transformer_batch_q8", states, tokens, pos, w)
 
 
 def batch_q8_time(states, tokens, pos, w: Weights, iters: int) -> float:
     """l2z_batch_q8_time: milliseconds per transformer_batch_q8 step, device events over `iters` steps (after one untimed)."""
-    n, ss, t, p = _batch_args(states, tokens, pos)
-    ms = C.c_double(0.0)
-    _chk(lib().l2z_batch_q8_time(n, t.ctypes.data_as(C.POINTER(C.c_int32)), p.ctypes.data_as(C.POINTER(C.c_int32)),
-                                 C.byref(states[0].cfg), ss, w.h, iters, C.byref(ms)))
-    return ms.value
+    return _batch_call("l2z_batch_q8_time", states, tokens, pos, w, iters)
 
 
 def _sample_args(states, temperature, top_p, coins):
@@ -1104,19 +1079,23 @@ def lookup_draft_tree(history, depth: int, budget: int, max_ngram: int = 3):
     return tok[:n].copy(), par[:n].copy()
 
 
-def speculate_greedy(s: RunState, w: Weights, prompt, n_steps: int, k: int, drafter=None):
-    """The loop of `llama2 -t 0 --spec k`: greedy decoding of n_steps positions (0 = seq_len) from BOS + prompt, up to k
-    guessed tokens verified per sweep of the weights (RunState.verify).  drafter(history, k) -> guesses (history: BOS, then
-    everything emitted; at most k ids are used); default lookup_draft.  Returns (tokens, stats): tokens = the `next` of
-    every position from 0 as l2z_greedy_run reports them (prompt positions echo the prompt; a BOS ends the run and is the
-    last id), stats = {"calls", "offered", "accepted", "emitted"} (emitted: ids that came out of verify calls).  The ids do
-    not depend on k or on the drafter (DRAFT INVARIANCE)."""
-    if not 0 <= k <= BATCH_MAX - 1:
-        raise ValueError(f"k = {k} outside [0, {BATCH_MAX - 1}]")
-    if drafter is None:
-        drafter = lookup_draft
+def _check_guesses(what: str, n: int) -> None:
+    if not 0 <= n <= BATCH_MAX - 1:
+        raise ValueError(f"{what} = {n} outside [0, {BATCH_MAX - 1}]")
+
+
+def _speculate_one(s: RunState, prompt, n_steps: int, prefill, guess_round, draw=None):
+    """The loop behind speculate_greedy, speculate_sample, speculate_q8 and speculate_tree, which state its contract: the
+    prompt's echo, prefill(BOS + prompt) and the first id -- s.argmax(), or with draw = (temperature, top_p, coins as an f32
+    vector) sample_batch([s], temperature, top_p, coins[0]) --, then rounds until a BOS or n_steps positions.
+    guess_round(hist, pos, room, g) makes one verify call at position pos and returns (ids, offered, accepted): hist is BOS
+    and everything emitted, room the positions left behind pos, g the generated tokens so far = the index of the next coin,
+    ids the sequence's next tokens, emitted as far as the run goes.  ValueError if the coins are too short for n_steps."""
     seq_len = s.cfg.seq_len
     steps = seq_len if n_steps == 0 else max(1, min(int(n_steps), seq_len))
+    prompt = [int(t) for t in prompt][:steps]
+    if draw is not None and draw[2].size < steps - len(prompt):
+        raise ValueError(f"{draw[2].size} coins for {steps - len(prompt)} generated positions")
     hist, out = [1], []
     stats = {"calls": 0, "offered": 0, "accepted": 0, "emitted": 0}
 
@@ -1125,29 +1104,66 @@ def speculate_greedy(s: RunState, w: Weights, prompt, n_steps: int, k: int, draf
         hist.append(int(t))
         return int(t) != 1
 
-    alive, pos = True, 0
-    prompt = [int(t) for t in prompt][:steps]
+    alive, pos, g = True, 0, 0
     while alive and pos < len(prompt):
         alive = emit(prompt[pos])
         pos += alive
     if alive and pos < steps:
-        s.prefill(np.array(hist, np.int32), 0, w)
-        alive = emit(s.argmax())
+        prefill(np.array(hist, np.int32))
+        alive = emit(s.argmax() if draw is None else sample_batch([s], draw[0], draw[1], draw[2][0])[0])
+        g += 1
         pos += alive
     while alive and pos < steps:
-        kk = min(k, steps - pos - 1)
-        guesses = [int(g) for g in drafter(np.array(hist, np.int32), kk)][:kk] if kk > 0 else []
-        nxt, a = s.verify([hist[-1]] + guesses, pos, w)
+        ids, offered, accepted = guess_round(hist, pos, steps - pos - 1, g)
         stats["calls"] += 1
-        stats["offered"] += len(guesses)
-        stats["accepted"] += a
-        for t in nxt[: a + 1]:
+        stats["offered"] += offered
+        stats["accepted"] += accepted
+        for t in ids:
             if not (alive and pos < steps):
                 break
             alive = emit(t)
             stats["emitted"] += 1
+            g += 1
             pos += alive
     return np.array(out, np.int32), stats
+
+
+def _chain_round(k: int, drafter, verify):
+    """_speculate_one's round for a chain of up to k guesses: drafter(history, kk), asked only for kk > 0 guesses, then
+    verify(tokens, pos, g) -> (next, accepted) on the last id and the guesses."""
+    if drafter is None:
+        drafter = lookup_draft
+
+    def guess_round(hist, pos, room, g):
+        kk = min(k, room)
+        guesses = [int(t) for t in drafter(np.array(hist, np.int32), kk)][:kk] if kk > 0 else []
+        nxt, a = verify([hist[-1]] + guesses, pos, g)
+        return nxt[: a + 1], len(guesses), a
+    return guess_round
+
+
+def _draw_of(temperature, top_p, coins):
+    """speculate_q8's and speculate_tree's draw arguments as _speculate_one takes them: None at temperature None"""
+    if temperature is None:
+        return None
+    return temperature, 1.0 if top_p is None else top_p, np.ascontiguousarray(coins, np.float32).reshape(-1)
+
+
+def _draw_window(draw, g: int, n: int) -> tuple:
+    """what a verify call of n positions at generated index g takes behind the weights: nothing, or the draw with its coins"""
+    return () if draw is None else (draw[0], draw[1], draw[2][g: g + n])
+
+
+def speculate_greedy(s: RunState, w: Weights, prompt, n_steps: int, k: int, drafter=None):
+    """The loop of `llama2 -t 0 --spec k`: greedy decoding of n_steps positions (0 = seq_len) from BOS + prompt, up to k
+    guessed tokens verified per sweep of the weights (RunState.verify).  drafter(history, k) -> guesses (history: BOS, then
+    everything emitted; at most k ids are used); default lookup_draft.  Returns (tokens, stats): tokens = the `next` of
+    every position from 0 as l2z_greedy_run reports them (prompt positions echo the prompt; a BOS ends the run and is the
+    last id), stats = {"calls", "offered", "accepted", "emitted"} (emitted: ids that came out of verify calls).  The ids do
+    not depend on k or on the drafter (DRAFT INVARIANCE)."""
+    _check_guesses("k", k)
+    return _speculate_one(s, prompt, n_steps, lambda t: s.prefill(t, 0, w),
+                          _chain_round(k, drafter, lambda t, pos, g: s.verify(t, pos, w)))
 
 
 def coin_stream(seed: int, n: int) -> np.ndarray:
@@ -1185,48 +1201,11 @@ def speculate_sample(s: RunState, w: Weights, prompt, n_steps: int, k: int, temp
     coins[g : g + 1 + len(guesses)]; a position behind a rejected guess is drawn again by the next call with the same
     coin.  The drafter must not look at the coins.  The ids do not depend on k or on the drafter (COIN INVARIANCE).
     ValueError if `coins` is too short for n_steps."""
-    if not 0 <= k <= BATCH_MAX - 1:
-        raise ValueError(f"k = {k} outside [0, {BATCH_MAX - 1}]")
-    if drafter is None:
-        drafter = lookup_draft
-    coins = np.ascontiguousarray(coins, np.float32).reshape(-1)
-    seq_len = s.cfg.seq_len
-    steps = seq_len if n_steps == 0 else max(1, min(int(n_steps), seq_len))
-    prompt = [int(t) for t in prompt][:steps]
-    if coins.size < steps - len(prompt):
-        raise ValueError(f"{coins.size} coins for {steps - len(prompt)} generated positions")
-    hist, out = [1], []
-    stats = {"calls": 0, "offered": 0, "accepted": 0, "emitted": 0}
-
-    def emit(t):
-        out.append(int(t))
-        hist.append(int(t))
-        return int(t) != 1
-
-    alive, pos, g = True, 0, 0  # g: generated tokens so far = the index of the next coin
-    while alive and pos < len(prompt):
-        alive = emit(prompt[pos])
-        pos += alive
-    if alive and pos < steps:
-        s.prefill(np.array(hist, np.int32), 0, w)
-        alive = emit(sample_batch([s], temperature, top_p, coins[0])[0])
-        g += 1
-        pos += alive
-    while alive and pos < steps:
-        kk = min(k, steps - pos - 1)
-        guesses = [int(t) for t in drafter(np.array(hist, np.int32), kk)][:kk] if kk > 0 else []
-        nxt, a = s.verify_sample([hist[-1]] + guesses, pos, w, temperature, top_p, coins[g: g + 1 + len(guesses)])
-        stats["calls"] += 1
-        stats["offered"] += len(guesses)
-        stats["accepted"] += a
-        for t in nxt[: a + 1]:
-            if not (alive and pos < steps):
-                break
-            alive = emit(t)
-            stats["emitted"] += 1
-            g += 1
-            pos += alive
-    return np.array(out, np.int32), stats
+    _check_guesses("k", k)
+    draw = (temperature, top_p, np.ascontiguousarray(coins, np.float32).reshape(-1))
+    return _speculate_one(s, prompt, n_steps, lambda t: s.prefill(t, 0, w),
+                          _chain_round(k, drafter, lambda t, pos, g: s.verify_sample(t, pos, w, *_draw_window(draw, g, len(t)))),
+                          draw)
 
 
 def speculate_q8(s: RunState, w: Weights, prompt, n_steps: int, k: int, drafter=None, temperature=None, top_p=None, coins=None):
@@ -1234,54 +1213,11 @@ def speculate_q8(s: RunState, w: Weights, prompt, n_steps: int, k: int, drafter=
     for BOS + prompt, then up to k guessed tokens verified per sweep of the weights by RunState.verify_q8.  Arguments, the
     coins' convention (coins[g]: the coin of the g-th generated token) and the return value are theirs; the ids do not
     depend on k or on the drafter."""
-    if not 0 <= k <= BATCH_MAX - 1:
-        raise ValueError(f"k = {k} outside [0, {BATCH_MAX - 1}]")
-    if drafter is None:
-        drafter = lookup_draft
-    sampled = temperature is not None
-    seq_len = s.cfg.seq_len
-    steps = seq_len if n_steps == 0 else max(1, min(int(n_steps), seq_len))
-    prompt = [int(t) for t in prompt][:steps]
-    if sampled:
-        top_p = 1.0 if top_p is None else top_p
-        coins = np.ascontiguousarray(coins, np.float32).reshape(-1)
-        if coins.size < steps - len(prompt):
-            raise ValueError(f"{coins.size} coins for {steps - len(prompt)} generated positions")
-    hist, out = [1], []
-    stats = {"calls": 0, "offered": 0, "accepted": 0, "emitted": 0}
-
-    def emit(t):
-        out.append(int(t))
-        hist.append(int(t))
-        return int(t) != 1
-
-    alive, pos, g = True, 0, 0  # g: generated tokens so far = the index of the next coin
-    while alive and pos < len(prompt):
-        alive = emit(prompt[pos])
-        pos += alive
-    if alive and pos < steps:
-        s.prefill_q8(np.array(hist, np.int32), 0, w)
-        alive = emit(sample_batch([s], temperature, top_p, coins[0])[0] if sampled else s.argmax())
-        g += 1
-        pos += alive
-    while alive and pos < steps:
-        kk = min(k, steps - pos - 1)
-        guesses = [int(t) for t in drafter(np.array(hist, np.int32), kk)][:kk] if kk > 0 else []
-        if sampled:
-            nxt, a = s.verify_q8([hist[-1]] + guesses, pos, w, temperature, top_p, coins[g: g + 1 + len(guesses)])
-        else:
-            nxt, a = s.verify_q8([hist[-1]] + guesses, pos, w)
-        stats["calls"] += 1
-        stats["offered"] += len(guesses)
-        stats["accepted"] += a
-        for t in nxt[: a + 1]:
-            if not (alive and pos < steps):
-                break
-            alive = emit(t)
-            stats["emitted"] += 1
-            g += 1
-            pos += alive
-    return np.array(out, np.int32), stats
+    _check_guesses("k", k)
+    draw = _draw_of(temperature, top_p, coins)
+    return _speculate_one(s, prompt, n_steps, lambda t: s.prefill_q8(t, 0, w),
+                          _chain_round(k, drafter, lambda t, pos, g: s.verify_q8(t, pos, w, *_draw_window(draw, g, len(t)))),
+                          draw)
 
 
 def speculate_tree(s: RunState, w: Weights, prompt, n_steps: int, depth: int, budget: int, drafter=None, temperature=None,
@@ -1294,38 +1230,13 @@ def speculate_tree(s: RunState, w: Weights, prompt, n_steps: int, depth: int, bu
     coins[g : g + 1 + max depth].  The return convention is speculate_greedy's; stats["offered"] counts guessed nodes,
     stats["accepted"] edges walked.  The ids do not depend on depth, budget or the drafter (PATH INVARIANCE): they are
     speculate_greedy's, or speculate_sample's for the same coins."""
-    if not 0 <= budget <= BATCH_MAX - 1:
-        raise ValueError(f"budget = {budget} outside [0, {BATCH_MAX - 1}]")
+    _check_guesses("budget", budget)
     if drafter is None:
         drafter = lookup_draft_tree
-    sampled = temperature is not None
-    seq_len = s.cfg.seq_len
-    steps = seq_len if n_steps == 0 else max(1, min(int(n_steps), seq_len))
-    prompt = [int(t) for t in prompt][:steps]
-    if sampled:
-        coins = np.ascontiguousarray(coins, np.float32).reshape(-1)
-        top_p = 1.0 if top_p is None else top_p
-        if coins.size < steps - len(prompt):
-            raise ValueError(f"{coins.size} coins for {steps - len(prompt)} generated positions")
-    hist, out = [1], []
-    stats = {"calls": 0, "offered": 0, "accepted": 0, "emitted": 0}
+    draw = _draw_of(temperature, top_p, coins)
 
-    def emit(t):
-        out.append(int(t))
-        hist.append(int(t))
-        return int(t) != 1
-
-    alive, pos, g = True, 0, 0  # g: generated tokens so far = the index of the next coin
-    while alive and pos < len(prompt):
-        alive = emit(prompt[pos])
-        pos += alive
-    if alive and pos < steps:
-        s.prefill(np.array(hist, np.int32), 0, w)
-        alive = emit(sample_batch([s], temperature, top_p, coins[0])[0] if sampled else s.argmax())
-        g += 1
-        pos += alive
-    while alive and pos < steps:
-        dd, bb = min(int(depth), steps - pos - 1), min(int(budget), seq_len - pos - 1)
+    def guess_round(hist, pos, room, g):
+        dd, bb = min(int(depth), room), min(int(budget), s.cfg.seq_len - pos - 1)
         tokens, parent, dep = [hist[-1]], [-1], [0]
         if dd > 0 and bb > 0:
             gt, gp = drafter(np.array(hist, np.int32), dd, bb)
@@ -1336,21 +1247,10 @@ def speculate_tree(s: RunState, w: Weights, prompt, n_steps: int, depth: int, bu
                     continue
                 node[k + 1] = len(tokens)
                 tokens.append(int(t)); parent.append(p); dep.append(dep[p] + 1)
-        if sampled:
-            nxt, path, a = s.verify_tree(tokens, parent, pos, w, temperature, top_p, coins[g: g + 1 + max(dep)])
-        else:
-            nxt, path, a = s.verify_tree(tokens, parent, pos, w)
-        stats["calls"] += 1
-        stats["offered"] += len(tokens) - 1
-        stats["accepted"] += a
-        for t in nxt[path]:
-            if not (alive and pos < steps):
-                break
-            alive = emit(t)
-            stats["emitted"] += 1
-            g += 1
-            pos += alive
-    return np.array(out, np.int32), stats
+        nxt, path, a = s.verify_tree(tokens, parent, pos, w, *_draw_window(draw, g, 1 + max(dep)))
+        return nxt[path], len(tokens) - 1, a
+
+    return _speculate_one(s, prompt, n_steps, lambda t: s.prefill(t, 0, w), guess_round, draw)
 
 
 def speculate_batch(states, w: Weights, prompts, n_steps: int, k: int, drafter=None, *, temperature=None, top_p=None,

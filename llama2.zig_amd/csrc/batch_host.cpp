@@ -3,7 +3,7 @@
 // GEMM forms with per-row epilogues (prefill_skinny.hip, G_*_ROWS) and batch_decode.hip.  Also what a batch of samples
 // needs around the step: the on-device sampler l2z_sample_batch (sample_batch.hip) and the prompt copy
 // l2z_runstate_fork.  The step itself (batch_step) takes a layer's attention from its caller: the verify family
-// (verify_host.cpp) runs it with attention forms of its own.  batch_host.h: what the host files share -- its argument
+// (verify_host.cpp) runs it with attention forms of its own; on int8 group-quantized weights it is q8_host.cpp's.  batch_host.h: what the host files share -- its argument
 // rules, stream hand-overs and allocation helper are defined here.
 #include <algorithm>
 #include <cmath>
@@ -262,67 +262,6 @@ int upload_table(BatchScratch *b, const BatchTable &t, hipStream_t st, const voi
     L2Z_HIP(hipEventRecord(b->ev_upload, st));
     return L2Z_OK;
 }
-
-namespace {
-
-// The step on int8 group-quantized weights.  Per layer: the rows quantized after the rmsnorm, q | k | v in one
-// launch (RoPE and the cache rows in its epilogue), the caller's attention, and the prompt pass's row launch and GEMM for Wo,
-// W1 | W3 and W2; then the classifier through the table.  Every product is the one-tile form of q8_gemm_device.h: a row's
-// bits do not depend on n, on the other rows, or on its place in the batch.
-int batch_step_q8(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *w, BatchScratch *b, LayerAttention attention)
-{
-    hipStream_t st = s0->stream;
-    const int dim = c.dim, hid = c.hidden_dim, hs = dim / c.n_heads, kvd = hs * c.n_kv_heads, gs = w->q8_gs;
-    const BatchTable *tab = b->d_tab;
-    // rows of `x` (after the rmsnorm with rms_w, if any) quantized over k, then their product with the layer's matrix
-    const auto rows = [&](const float *x, int ldx, int k, const float *rms_w) -> int {
-        L2Z_HIP(launch_q8_quantize_rows(x, ldx, n, k, rms_w, gs, b->q8_xq, b->q8_xs, st));
-        return L2Z_OK;
-    };
-    const auto gemm = [&](const l2z_weights::Q8Mat &m, int l, int d, int k, float *out, int ldo, int epi) -> int {
-        const size_t at = (size_t)l * (size_t)d * (size_t)k;
-        Q8GemmArgs a = {};
-        a.xq = b->q8_xq; a.xs = b->q8_xs; a.wq = m.q + at; a.ws = m.s + at / (size_t)gs;
-        a.out = out; a.ldo = ldo; a.res = out; a.ldres = ldo;
-        a.m = n; a.n = k; a.d = d; a.gs = gs;
-        L2Z_HIP(launch_q8_gemm(a, epi, st));
-        return L2Z_OK;
-    };
-    L2Z_HIP(launch_q8_embed_rows(w->q8_emb(), tab->tokens, dim, n, b->x, 0, nullptr, nullptr, st));  // :295
-    for (int l = 0; l < c.n_layers; l++) {
-        const size_t layer_off = (size_t)l * c.seq_len * kvd;
-        L2Z_TRY(rows(b->x, dim, dim, w->rms_att + (size_t)l * dim));  // :305
-        {   // q | k | v (:308-358): RoPE at each row's own position, k | v into each row's own caches
-            const size_t at_q = (size_t)l * dim * dim, at_kv = (size_t)l * kvd * dim;
-            Q8BatchQkvArgs a = {};
-            a.xq = b->q8_xq; a.xs = b->q8_xs;
-            a.wq_q = w->q_wq.q + at_q; a.ws_q = w->q_wq.s + at_q / (size_t)gs;
-            a.wq_k = w->q_wk.q + at_kv; a.ws_k = w->q_wk.s + at_kv / (size_t)gs;
-            a.wq_v = w->q_wv.q + at_kv; a.ws_v = w->q_wv.s + at_kv / (size_t)gs;
-            a.q = b->q; a.ldq = dim; a.tab = tab; a.rope = s0->rope;
-            a.layer_off = layer_off; a.kv_head_stride = (size_t)c.seq_len * hs;
-            a.m = n; a.n = dim; a.dim = dim; a.kvd = kvd; a.hs = hs; a.gs = gs;
-            L2Z_HIP(launch_q8_batch_qkv(a, st));
-        }
-        L2Z_TRY(attention(layer_off));  // :361-389
-        L2Z_TRY(rows(b->att, b->ld_att, dim, nullptr));
-        L2Z_TRY(gemm(w->q_wo, l, dim, dim, b->x, dim, EPI_RESID));  // :392-395
-        L2Z_TRY(rows(b->x, dim, dim, w->rms_ffn + (size_t)l * dim));  // :398
-        L2Z_TRY(gemm(w->q_w13, l, 2 * hid, dim, b->h1, b->ld_h1, EPI_SWIGLU));  // :405-416
-        L2Z_TRY(rows(b->h1, b->ld_h1, hid, nullptr));
-        L2Z_TRY(gemm(w->q_w2, l, dim, hid, b->x, dim, EPI_RESID));  // :419-422
-    }
-    L2Z_TRY(rows(b->x, dim, dim, w->rms_final));  // :426
-    {   // :429: each row's logits straight into its runstate
-        Q8BatchClsArgs a = {};
-        a.xq = b->q8_xq; a.xs = b->q8_xs; a.wq = w->q_cls.q; a.ws = w->q_cls.s; a.tab = tab;
-        a.m = n; a.n = dim; a.vocab = c.vocab_size; a.gs = gs;
-        L2Z_HIP(launch_q8_batch_cls(a, st));
-    }
-    return L2Z_OK;
-}
-
-}  // namespace
 
 // Every product is the one-tile short-prompt form at P = n whatever n is (launch_batch_skinny): a row's bits do not depend
 // on n, on the other rows, or on its place in the batch.
@@ -634,23 +573,33 @@ extern "C" int l2z_sample_time(int n, l2z_runstate *const *states, const float *
     });
 }
 
+namespace {
+
+// l2z_batch_time (q8 false) and l2z_batch_q8_time (true): one body, as transformer_batch_call, whose steps it times
+int batch_time_call(const char *fn, bool q8, int n, const int32_t *tokens, const int32_t *pos, const l2z_config *config,
+                    l2z_runstate *const *states, const l2z_weights *w, int iters, double *out_ms)
+{
+    L2Z_CHECK(iters >= 1 && out_ms != nullptr, L2Z_ERR_INVALID, "%s: bad arguments", fn);
+    const auto step = [&] {
+        return transformer_batch_call(q8 ? "l2z_transformer_batch_q8" : "l2z_transformer_batch", q8, n, tokens, pos, config, states, w);
+    };
+    L2Z_TRY(step());  // validates, allocates
+    return timed_loop(states[0]->stream, iters, out_ms, step);
+}
+
+}  // namespace
+
 // Testing support (include/llama2_hip_test.h): `iters` batched steps back to back, timed by device events on the pass's
-// stream (scripts/batch_bench.py)
+// stream (scripts/batch_bench.py) ...
 extern "C" int l2z_batch_time(int n, const int32_t *tokens, const int32_t *pos, const l2z_config *config,
                               l2z_runstate *const *states, const l2z_weights *w, int iters, double *out_ms)
 {
-    L2Z_CHECK(iters >= 1 && out_ms != nullptr, L2Z_ERR_INVALID, "l2z_batch_time: bad arguments");
-    L2Z_TRY(l2z_transformer_batch(n, tokens, pos, config, states, w));  // validates, allocates
-    hipStream_t st = states[0]->stream;
-    return timed_loop(st, iters, out_ms, [&] { return l2z_transformer_batch(n, tokens, pos, config, states, w); });
+    return batch_time_call("l2z_batch_time", false, n, tokens, pos, config, states, w, iters, out_ms);
 }
 
-// ... and its twin on int8 group-quantized weights (scripts/q8_batch_bench.py)
+// ... and on int8 group-quantized weights (scripts/q8_batch_bench.py)
 extern "C" int l2z_batch_q8_time(int n, const int32_t *tokens, const int32_t *pos, const l2z_config *config,
                                  l2z_runstate *const *states, const l2z_weights *w, int iters, double *out_ms)
 {
-    L2Z_CHECK(iters >= 1 && out_ms != nullptr, L2Z_ERR_INVALID, "l2z_batch_q8_time: bad arguments");
-    L2Z_TRY(l2z_transformer_batch_q8(n, tokens, pos, config, states, w));  // validates, allocates
-    hipStream_t st = states[0]->stream;
-    return timed_loop(st, iters, out_ms, [&] { return l2z_transformer_batch_q8(n, tokens, pos, config, states, w); });
+    return batch_time_call("l2z_batch_q8_time", true, n, tokens, pos, config, states, w, iters, out_ms);
 }

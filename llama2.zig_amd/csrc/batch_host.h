@@ -154,8 +154,10 @@ template <class A> A attention_args(const l2z_config &c, const BatchScratch *b)
 }
 
 // One step of the n rows of b->d_tab on s0's stream, each layer's attention by `attention`.  On int8 group-quantized
-// weights (the caller has run q8_batch_alloc): the quantized step, DESIGN.md 4.25
+// weights (the caller has run q8_batch_alloc) it hands over to batch_step_q8 (q8_host.cpp), which walks
+// the layers as the prompt pass on such weights does (q8_layers)
 int batch_step(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *w, BatchScratch *b, LayerAttention attention);
+int batch_step_q8(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *w, BatchScratch *b, LayerAttention attention);
 
 // The rows' draws (l2z_sample_batch's launch) from tab->logits[i] with the table's temperature, top_p and coin -> out[0 .. n)
 hipError_t sample_rows(BatchScratch *b, int vocab, int *out, int n, hipStream_t st);

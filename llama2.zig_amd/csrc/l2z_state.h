@@ -222,7 +222,7 @@ struct l2z_runstate {
     float *rg_k = nullptr, *rg_v = nullptr;
     void *rg_tab = nullptr;
     int rg_cap = 0;
-    // l2z_prefill_q8 scratch (prefill_q8_host.cpp; allocated on the first call): one allocation, carved for chunks of up to
+    // l2z_prefill_q8 scratch (q8_host.cpp; allocated on the first call): one allocation, carved for chunks of up to
     // q8pf_cap rows at group size q8pf_gs
     void *q8pf = nullptr;
     int q8pf_cap = 0, q8pf_gs = 0;

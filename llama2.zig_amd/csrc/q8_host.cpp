@@ -1,10 +1,14 @@
-// prefill_q8_host.cpp -- host side of l2z_prefill_q8 (include/llama2_hip_test.h): the batched prompt pass
-// on int8 group-quantized weights.  A layer walk of its own, apart from prefill_host.cpp's: per layer four row launches
-// (q8_rows.hip: the group quantization of the chunk's rows, after the rmsnorm where the decode's launch has one), six
-// GEMM launches on the int8 matrix cores (q8_gemm.hip: q, k, v into scratch, Wo and W2 with the residual, W1 | W3 with
-// SwiGLU), the f32 pass's RoPE + cache scatter over a one-sequence table and its prompt attention.  The last row then
-// goes through the decode's own classifier launch, so the runstate is left as after a decode step.  Also the two hooks
-// that run the row launch and the GEMM on their own.
+// q8_host.cpp -- host side of the multi-row passes on int8 group-quantized weights: the prompt pass l2z_prefill_q8
+// (include/llama2_hip_test.h) and the batched step behind l2z_transformer_batch_q8 and l2z_verify_q8
+// (batch_step_q8).  Both go through ONE layer walk (q8_layers), apart from the f32 walks
+// of prefill_host.cpp and batch_step: per layer four row launches (q8_rows.hip: the group quantization of the pass's rows,
+// after the rmsnorm where the decode's launch has one) and, behind the attention, three GEMM launches on the int8 matrix
+// cores (q8_gemm.hip: Wo and W2 with the residual, W1 | W3 with SwiGLU).  How q | k | v, the cache rows and the attention
+// output come about is the caller's: the prompt pass runs three more GEMMs into scratch, the f32 pass's RoPE + cache
+// scatter over a one-sequence table and its prompt attention, and sends the last row through the decode's own classifier
+// launch, so the runstate is left as after a decode step; the step runs q | k | v as one launch (q8_batch.hip), its
+// caller's attention and the classifier through the table.  Also the two hooks that run the row launch and the GEMM on
+// their own.
 #include <algorithm>
 #include <cstring>
 
@@ -14,6 +18,56 @@
 using namespace l2z;
 
 namespace {
+
+// The rows of a pass and where its launches put them: m rows; the residual rows x, dim apart; a layer's attention output
+// att and the gated rows h at their pitches; the quantized rows xq and their scales xs (group size gs) that every product
+// reads; st: the pass's stream
+struct Q8Rows {
+    int m;
+    float *x, *att, *h;
+    int ld_att, ld_h;
+    int8_t *xq;
+    float *xs;
+    int gs;
+    hipStream_t st;
+};
+
+// rows of `x`, ldx apart (after the rmsnorm with rms_w, if any), quantized over k -> r.xq, r.xs
+int q8_quantize(const Q8Rows &r, const float *x, int ldx, int k, const float *rms_w)
+{
+    L2Z_HIP(launch_q8_quantize_rows(x, ldx, r.m, k, rms_w, r.gs, r.xq, r.xs, r.st));
+    return L2Z_OK;
+}
+
+// ... and their product with layer l's [d, k] matrix of m -> out, through the epilogue epi (the residual is out itself)
+int q8_product(const Q8Rows &r, const l2z_weights::Q8Mat &m, int l, int d, int k, float *out, int ldo, int epi)
+{
+    const size_t at = (size_t)l * (size_t)d * (size_t)k;
+    Q8GemmArgs a = {};
+    a.xq = r.xq; a.xs = r.xs; a.wq = m.q + at; a.ws = m.s + at / (size_t)r.gs;
+    a.out = out; a.ldo = ldo; a.res = out; a.ldres = ldo;
+    a.m = r.m; a.n = k; a.d = d; a.gs = r.gs;
+    L2Z_HIP(launch_q8_gemm(a, epi, r.st));
+    return L2Z_OK;
+}
+
+// The layers of a pass over r.x.  qkv_attention(l, layer_off) finds layer l's quantized rows in r.xq / r.xs, writes the
+// rows' k | v into the caches, layer_off floats in, and leaves the attention output in r.att.
+int q8_layers(const Q8Rows &r, const l2z_config &c, const l2z_weights *w, FnRef<int(int, size_t)> qkv_attention)
+{
+    const int dim = c.dim, hid = c.hidden_dim, kvd = dim / c.n_heads * c.n_kv_heads;
+    for (int l = 0; l < c.n_layers; l++) {
+        L2Z_TRY(q8_quantize(r, r.x, dim, dim, w->rms_att + (size_t)l * dim));       // :305
+        L2Z_TRY(qkv_attention(l, (size_t)l * c.seq_len * kvd));                     // :308-389
+        L2Z_TRY(q8_quantize(r, r.att, r.ld_att, dim, nullptr));
+        L2Z_TRY(q8_product(r, w->q_wo, l, dim, dim, r.x, dim, EPI_RESID));          // :392-395
+        L2Z_TRY(q8_quantize(r, r.x, dim, dim, w->rms_ffn + (size_t)l * dim));       // :398
+        L2Z_TRY(q8_product(r, w->q_w13, l, 2 * hid, dim, r.h, r.ld_h, EPI_SWIGLU));  // :405-416
+        L2Z_TRY(q8_quantize(r, r.h, r.ld_h, hid, nullptr));
+        L2Z_TRY(q8_product(r, w->q_w2, l, dim, hid, r.x, dim, EPI_RESID));          // :419-422
+    }
+    return L2Z_OK;
+}
 
 // The pass's scratch, one allocation owned by the runstate (l2z_runstate::q8pf, freed with it), carved for chunks of up to
 // `cap` rows: the residual rows, q | k | v, the attention output and the gated rows in f32; the quantized rows and their
@@ -73,44 +127,23 @@ int q8_chunk(l2z_runstate *s, const l2z_weights *w, const Q8Pf &b, const int32_t
 {
     const l2z_config &c = s->cfg;
     hipStream_t st = s->stream;
-    const int dim = c.dim, hid = c.hidden_dim, kvd = s->sh.kvd_loc, hs = s->sh.hs, gs = w->q8_gs;
+    const int dim = c.dim, kvd = s->sh.kvd_loc, hs = s->sh.hs;
     const size_t kvh_stride = (size_t)c.seq_len * hs;
     L2Z_HIP(hipMemcpyAsync(b.tokens, tokens, (size_t)P * 4, hipMemcpyHostToDevice, st));
     L2Z_HIP(launch_q8_embed_rows(w->q8_emb(), b.tokens, dim, P, b.x, pos0, b.row_seq, b.row_pos, st));
     RaggedChunk rg = {};
     rg.seq = b.seq; rg.row_seq = b.row_seq; rg.row_pos = b.row_pos;
     rg.n_seq = 1; rg.seq_max = 1; rg.k = b.k; rg.v = b.v;
-    // rows of `x` (after the rmsnorm with rms_w, if any) quantized over n, then their product with the layer's matrix
-    const auto rows = [&](const float *x, int n, const float *rms_w) -> int {
-        L2Z_HIP(launch_q8_quantize_rows(x, n, P, n, rms_w, gs, b.xq, b.xs, st));
-        return L2Z_OK;
-    };
-    const auto gemm = [&](const l2z_weights::Q8Mat &m, int l, int d, int n, float *out, int ldo, int epi) -> int {
-        const size_t at = (size_t)l * (size_t)d * (size_t)n;
-        Q8GemmArgs a = {};
-        a.xq = b.xq; a.xs = b.xs; a.wq = m.q + at; a.ws = m.s + at / (size_t)gs;
-        a.out = out; a.ldo = ldo; a.res = out; a.ldres = ldo;
-        a.m = P; a.n = n; a.d = d; a.gs = gs;
-        L2Z_HIP(launch_q8_gemm(a, epi, st));
-        return L2Z_OK;
-    };
-    for (int l = 0; l < c.n_layers; l++) {
-        const size_t layer_off = (size_t)l * c.seq_len * kvd;
-        L2Z_TRY(rows(b.x, dim, w->rms_att + (size_t)l * dim));                    // :305
-        L2Z_TRY(gemm(w->q_wq, l, dim, dim, b.q, dim, EPI_STORE));                 // :308-320
-        L2Z_TRY(gemm(w->q_wk, l, kvd, dim, b.k, kvd, EPI_STORE));
-        L2Z_TRY(gemm(w->q_wv, l, kvd, dim, b.v, kvd, EPI_STORE));
+    const Q8Rows r = {P, b.x, b.att, b.h, dim, c.hidden_dim, b.xq, b.xs, w->q8_gs, st};   // (every pitch tight)
+    return q8_layers(r, c, w, [&](int l, size_t layer_off) -> int {
+        L2Z_TRY(q8_product(r, w->q_wq, l, dim, dim, b.q, dim, EPI_STORE));        // :308-320
+        L2Z_TRY(q8_product(r, w->q_wk, l, kvd, dim, b.k, kvd, EPI_STORE));
+        L2Z_TRY(q8_product(r, w->q_wv, l, kvd, dim, b.v, kvd, EPI_STORE));
         L2Z_HIP(launch_ragged_rope_scatter(b.q, dim, rg, P, dim, kvd, hs, s->rope, layer_off, kvh_stride, st));   // :336-358
         L2Z_HIP(launch_prefill_attention(b.q, dim, s->key_cache + layer_off, s->value_cache + layer_off, b.att, dim, pos0, P,
                                          c.n_heads, hs, hs, kvh_stride, c.n_heads / c.n_kv_heads, c.seq_len, st, c.n_heads));   // :361-389
-        L2Z_TRY(rows(b.att, dim, nullptr));
-        L2Z_TRY(gemm(w->q_wo, l, dim, dim, b.x, dim, EPI_RESID));                 // :392-395
-        L2Z_TRY(rows(b.x, dim, w->rms_ffn + (size_t)l * dim));                    // :398
-        L2Z_TRY(gemm(w->q_w13, l, 2 * hid, dim, b.h, hid, EPI_SWIGLU));           // :405-416
-        L2Z_TRY(rows(b.h, hid, nullptr));
-        L2Z_TRY(gemm(w->q_w2, l, dim, hid, b.x, dim, EPI_RESID));                 // :419-422
-    }
-    return L2Z_OK;
+        return L2Z_OK;
+    });
 }
 
 // the decode's final rmsnorm + classifier launch on s->x, argmax candidates included (forward.cpp)
@@ -175,6 +208,38 @@ extern "C" int l2z_prefill_q8(const int32_t *tokens, int n_tokens, int pos0, con
     s->logits_partial = false;
     L2Z_HIP(hipStreamSynchronize(st));
     s->host_pos = pos0 + n_tokens;
+    return L2Z_OK;
+}
+
+// The step on int8 group-quantized weights.  Per layer q | k | v in one launch (RoPE and the cache rows in
+// its epilogue) and the caller's attention; then the classifier through the table.  Every product is the one-tile form of
+// q8_gemm_device.h: a row's bits do not depend on n, on the other rows, or on its place in the batch.
+int l2z::batch_step_q8(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *w, BatchScratch *b, LayerAttention attention)
+{
+    hipStream_t st = s0->stream;
+    const int dim = c.dim, hs = dim / c.n_heads, kvd = hs * c.n_kv_heads, gs = w->q8_gs;
+    const BatchTable *tab = b->d_tab;
+    const Q8Rows r = {n, b->x, b->att, b->h1, b->ld_att, b->ld_h1, b->q8_xq, b->q8_xs, gs, st};
+    L2Z_HIP(launch_q8_embed_rows(w->q8_emb(), tab->tokens, dim, n, b->x, 0, nullptr, nullptr, st));  // :295
+    L2Z_TRY(q8_layers(r, c, w, [&](int l, size_t layer_off) -> int {
+        // q | k | v (:308-358): RoPE at each row's own position, k | v into each row's own caches
+        const size_t at_q = (size_t)l * dim * dim, at_kv = (size_t)l * kvd * dim;
+        Q8BatchQkvArgs a = {};
+        a.xq = r.xq; a.xs = r.xs;
+        a.wq_q = w->q_wq.q + at_q; a.ws_q = w->q_wq.s + at_q / (size_t)gs;
+        a.wq_k = w->q_wk.q + at_kv; a.ws_k = w->q_wk.s + at_kv / (size_t)gs;
+        a.wq_v = w->q_wv.q + at_kv; a.ws_v = w->q_wv.s + at_kv / (size_t)gs;
+        a.q = b->q; a.ldq = dim; a.tab = tab; a.rope = s0->rope;
+        a.layer_off = layer_off; a.kv_head_stride = (size_t)c.seq_len * hs;
+        a.m = n; a.n = dim; a.dim = dim; a.kvd = kvd; a.hs = hs; a.gs = gs;
+        L2Z_HIP(launch_q8_batch_qkv(a, st));
+        return attention(layer_off);  // :361-389
+    }));
+    L2Z_TRY(q8_quantize(r, b->x, dim, dim, w->rms_final));  // :426
+    Q8BatchClsArgs a = {};   // :429: each row's logits straight into its runstate
+    a.xq = r.xq; a.xs = r.xs; a.wq = w->q_cls.q; a.ws = w->q_cls.s; a.tab = tab;
+    a.m = n; a.n = dim; a.vocab = c.vocab_size; a.gs = gs;
+    L2Z_HIP(launch_q8_batch_cls(a, st));
     return L2Z_OK;
 }
 
