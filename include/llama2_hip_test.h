@@ -709,6 +709,36 @@ int l2z_batch_q8_time(int n, const int32_t *tokens, const int32_t *pos, const l2
 int l2z_verify_q8_time(const int32_t *tokens, int n_tokens, int pos0, float temperature, float top_p, const float *coins,
                        const l2z_config *config, l2z_runstate *s, const l2z_weights *w, int iters, double *out_ms);
 
+/* ---- Wide decode step on int8 group-quantized weights (PREVIEW) ----
+ * l2z_transformer_wide_q8: l2z_transformer_wide's contract on q8 weights, under a name of its own -- 1 .. L2Z_WIDE_MAX
+ * sequences, one contiguous runstate each, one token each at its own position, ONE sweep of the weights; each row's KV rows
+ * in its own caches and its WHOLE logits in its own runstate, so l2z_argmax, l2z_logits_read, l2z_argmax_batch and
+ * l2z_sample_batch work behind it; out_next != NULL: every row's argmax (argmax_rule.h: strict '>', lowest index wins).
+ * l2z_transformer_wide, l2z_wide_run, l2z_verify_wide and l2z_step_mixed keep refusing such weights.
+ * THE ARITHMETIC is 4.23's definition row by row, as l2z_transformer_batch_q8's: rows quantized by the activation rule, a
+ * product sum_g f32(I_g) * ws * xs in l2z_q8_gemm's order -- q, k and v are three products, then RoPE and the cache rows --,
+ * the wide step's f32 attention (position-split, segments of 64 positions).  A row's results do not depend on the other
+ * rows of the call or on its place among them, nor on which of the two GEMM forms a product takes -- a function of n, of the
+ * product's row count d and of the device's CU count (from 17 rows on the register-blocked form where ceil(d / 32) reaches the
+ * CU count: on the 7B shape W1 | W3 and the classifier, not the 4096-row products) --, whose forms give the same bits.  The quantized rows' scratch (L2Z_WIDE_MAX rows) is states[0]'s, freed with it.
+ * A refusal enqueues nothing and changes nothing.  L2Z_ERR_NO_DEVICE without a device; L2Z_ERR_INVALID for a null argument,
+ * n outside [1, L2Z_WIDE_MAX], a runstate named twice, f32 or packed weights (those go to l2z_transformer_wide), a sharded or
+ * paged runstate, a config other than the objects', a head_size that is no multiple of 4 or above 256, a vocab_size that is
+ * no multiple of 4; L2Z_ERR_STATE for a position outside [0, seq_len) or a token outside the vocabulary.
+ *
+ * l2z_q8_gemm_wide: l2z_q8_gemm's twin (host pointers, synchronous, store epilogue) through the register-blocked form: a block owns two 16-row weight tiles and every token tile of the call.  The bits
+ * of every (token row, weight row) product are l2z_q8_gemm's.  L2Z_ERR_INVALID for m outside [17, L2Z_WIDE_MAX].
+ * l2z_q8_gemm_epi: ONE launch of either form (wide 0: l2z_q8_gemm's kernel, any m; wide 1: the register-blocked one) with
+ * the epilogue the passes give it (host pointers, synchronous).  epi 0 store: out [m, d].  epi 2 residual: out [m, d] is IN
+ * and OUT, out = out + product, in place on the device as the pass's Wo and W2 launches.  epi 3 SwiGLU: the weight rows are
+ * W1 | W3 interleaved, d a multiple of 8, out [m, d / 2] the gated values.  L2Z_ERR_INVALID for any other epi. */
+int l2z_transformer_wide_q8(int n, const int32_t *tokens, const int32_t *pos, const l2z_config *config,
+                            l2z_runstate *const *states, const l2z_weights *w, int32_t *out_next);
+int l2z_q8_gemm_wide(float *out, const int8_t *xq, const float *xs, int m, const int8_t *wq, const float *ws, size_t n,
+                     size_t d, int gs);
+int l2z_q8_gemm_epi(int epi, int wide, float *out, const int8_t *xq, const float *xs, int m, const int8_t *wq, const float *ws,
+                    size_t n, size_t d, int gs);
+
 #ifdef __cplusplus
 }
 #endif

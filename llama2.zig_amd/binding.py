@@ -135,6 +135,10 @@ def lib():
         L.l2z_weights_q8_read.argtypes = [vp, C.c_char_p, C.c_int, i8p, fp]
         L.l2z_q8_quantize.argtypes = [fp, sz, C.c_int, i8p, fp]
         L.l2z_q8_matmul.argtypes = [fp, i8p, fp, i8p, fp, sz, sz, C.c_int]
+    if hasattr(L, "l2z_transformer_wide_q8"):  # their wide step and its GEMM form (PREVIEW)
+        L.l2z_transformer_wide_q8.argtypes = [C.c_int, i32p, i32p, cfgp, C.POINTER(vp), vp, i32p]
+        L.l2z_q8_gemm_wide.argtypes = [fp, i8p, fp, C.c_int, i8p, fp, sz, sz, C.c_int]
+        L.l2z_q8_gemm_epi.argtypes = [C.c_int, C.c_int, fp, i8p, fp, C.c_int, i8p, fp, sz, sz, C.c_int]
     if hasattr(L, "l2z_q8_matvec_case"):
         L.l2z_q8_matvec_case.argtypes = [C.POINTER(Q8Case)]
     if hasattr(L, "l2z_prefill_q8"):  # their batched prompt pass (PREVIEW)
@@ -1589,6 +1593,64 @@ def q8_gemm(xq, xs, wq, ws, gs: int) -> np.ndarray:
     out = np.empty((m, d), np.float32)
     i8p = C.POINTER(C.c_int8)
     _chk(lib().l2z_q8_gemm(_fp(out), xq.ctypes.data_as(i8p), _fp(xs), m, wq.ctypes.data_as(i8p), _fp(ws), n, d, gs))
+    return out
+
+
+def q8_gemm_wide(xq, xs, wq, ws, gs: int) -> np.ndarray:
+    """q8_gemm through the register-blocked form of 17 .. WIDE_MAX rows (l2z_q8_gemm_wide): the same arguments, the same
+    bits."""
+    xq = np.ascontiguousarray(xq, dtype=np.int8)
+    wq = np.ascontiguousarray(wq, dtype=np.int8)
+    (m, n), d = xq.shape, wq.shape[0]
+    xs, ws = _f32(xs).reshape(-1), _f32(ws).reshape(-1)
+    assert wq.shape[1] == n and xs.size == m * (n // gs) and ws.size == d * (n // gs)
+    out = np.empty((m, d), np.float32)
+    i8p = C.POINTER(C.c_int8)
+    _chk(lib().l2z_q8_gemm_wide(_fp(out), xq.ctypes.data_as(i8p), _fp(xs), m, wq.ctypes.data_as(i8p), _fp(ws), n, d, gs))
+    return out
+
+
+def q8_gemm_epi(epi: str, wide: bool, xq, xs, wq, ws, gs: int, resid=None) -> np.ndarray:
+    """One launch of either q8 GEMM form with the epilogue the passes give it (l2z_q8_gemm_epi).  epi "store": out [m, d];
+    "resid": resid [m, d] + the product, in place on the device; "swiglu": wq's rows are W1 | W3 interleaved, out [m, d // 2]."""
+    xq = np.ascontiguousarray(xq, dtype=np.int8)
+    wq = np.ascontiguousarray(wq, dtype=np.int8)
+    (m, n), d = xq.shape, wq.shape[0]
+    xs, ws = _f32(xs).reshape(-1), _f32(ws).reshape(-1)
+    assert wq.shape[1] == n and xs.size == m * (n // gs) and ws.size == d * (n // gs)
+    out = np.array(resid, np.float32).reshape(m, d) if epi == "resid" else np.empty((m, d // 2 if epi == "swiglu" else d), np.float32)
+    i8p = C.POINTER(C.c_int8)
+    _chk(lib().l2z_q8_gemm_epi({"store": 0, "resid": 2, "swiglu": 3}[epi], int(wide), _fp(out), xq.ctypes.data_as(i8p), _fp(xs), m,
+                               wq.ctypes.data_as(i8p), _fp(ws), n, d, gs))
+    return out
+
+
+def transformer_wide_q8(states, tokens, pos, w: Weights, want_next: bool = True):
+    """l2z_transformer_wide_q8 (a preview entry point of the test library): transformer_wide on int8 group-quantized
+    weights, for up to WIDE_MAX contiguous runstates.  want_next: returns every row's argmax; otherwise None."""
+    n, ss, t, p = _batch_args(states, tokens, pos)
+    cfg = states[0].cfg if n else L2ZConfig()
+    i32p = C.POINTER(C.c_int32)
+    nxt = np.zeros(max(n, 1), np.int32) if want_next else None
+    _chk(lib().l2z_transformer_wide_q8(n, t.ctypes.data_as(i32p), p.ctypes.data_as(i32p), C.byref(cfg), ss, w.h,
+                                       nxt.ctypes.data_as(i32p) if want_next else None))
+    return nxt[:n].copy() if want_next else None
+
+
+def generate_wide_q8(cfg, w: Weights, prompts, n_new: int) -> np.ndarray:
+    """The greedy loop over transformer_wide_q8 for up to WIDE_MAX prompts (each with its BOS, if any, in it): a runstate a
+    prompt, prefill_q8 of the prompt at position 0 and the argmax of its last logits, then every sequence fed its own
+    argmax -- one call per step, no host argmax.  Returns the ids [n, n_new] (row i = what sequence i emitted)."""
+    states = [RunState(cfg) for _ in prompts]
+    out = np.zeros((len(states), n_new), np.int32)
+    for i, (s, prompt) in enumerate(zip(states, prompts)):
+        s.prefill_q8(prompt, 0, w)
+        out[i, 0] = s.argmax()
+    pos = np.array([len(p) for p in prompts], np.int32)
+    for k in range(1, n_new):
+        out[:, k] = transformer_wide_q8(states, out[:, k - 1], pos + (k - 1), w)
+    for s in states:
+        s.close()
     return out
 
 

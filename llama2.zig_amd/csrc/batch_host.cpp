@@ -231,7 +231,13 @@ int check_ragged_call(const RaggedCall &c, RaggedTotals *t)
         L2Z_CHECK(c.max_rows == 0 || rows <= c.max_rows, L2Z_ERR_INVALID, "%s: more than %d rows in all", fn, c.max_rows);
         t->longest = std::max(t->longest, rows_of(j));
     }
-    for (int j = 0; j < c.n; j++) L2Z_TRY(check_pair(c.config, c.states[j], c.w, true));
+    if (c.q8) {
+        L2Z_TRY(check_q8_step(fn, c.f32_entry, c.states[0], c.w));
+        for (int j = 0; j < c.n; j++)
+            L2Z_CHECK(c.states[j]->pool == nullptr, L2Z_ERR_INVALID,
+                      "%s: states[%d] is a paged runstate (l2z_runstate_init_paged); on int8 group-quantized weights the runstates are contiguous", fn, j);
+    }
+    for (int j = 0; j < c.n; j++) L2Z_TRY(check_pair(c.config, c.states[j], c.w, !c.q8, c.q8));
     L2Z_TRY(prefill_check(c.config, c.states[0]));
     if (c.temperature != nullptr) {   // l2z_sample_batch's rules for every sequence; a greedy one's coins are not read
         L2Z_CHECK(c.top_p != nullptr, L2Z_ERR_INVALID, "%s: top_p is NULL beside a temperature array", fn);

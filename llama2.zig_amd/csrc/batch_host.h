@@ -95,6 +95,10 @@ struct RaggedCall {
     const l2z_weights *w;
     // the entry's limits: sequences, rows in all, rows of one sequence (0: as many as the cache holds)
     int max_seq, max_rows, max_seq_rows;
+    // the entry takes int8 group-quantized weights and no others, contiguous runstates only (l2z_transformer_wide_q8);
+    // f32_entry: where a message sends f32 and packed weights
+    bool q8;
+    const char *f32_entry;
 };
 struct RaggedTotals {
     int R;          // rows in all
@@ -104,7 +108,7 @@ struct RaggedTotals {
 };
 // The front of such a call; a refusal enqueues nothing and changes no state.  In this order: no device, null arguments, the
 // runstates (check_states), one kind of cache (kv_check_kind), the row counts, every runstate against config and w
-// (check_pair), states[0] on the prompt pass (prefill_check), the draws and their coins, then positions and tokens sequence
+// (check_pair; a q8 entry: check_q8_step first), states[0] on the prompt pass (prefill_check), the draws and their coins, then positions and tokens sequence
 // by sequence.
 int check_ragged_call(const RaggedCall &c, RaggedTotals *t);
 
@@ -158,6 +162,12 @@ template <class A> A attention_args(const l2z_config &c, const BatchScratch *b)
 // the layers as the prompt pass on such weights does (q8_layers)
 int batch_step(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *w, BatchScratch *b, LayerAttention attention);
 int batch_step_q8(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *w, BatchScratch *b, LayerAttention attention);
+// One step of the n <= kWideMax rows of a wide table on int8 group-quantized weights (q8_host.cpp), on s0's
+// prompt scratch and stream: rg the table's chunk with the k / v scratch and the layers' attention bound, tokens the
+// table's ids (device), xq / xs the quantized rows' scratch at the weights' group size; the classifier's product -> logits
+// [n, ld_logits]
+int wide_step_q8(int n, l2z_runstate *s0, const l2z_weights *w, const RaggedChunk &rg, const int *tokens, int8_t *xq, float *xs,
+                 float *logits, int ld_logits);
 
 // The rows' draws (l2z_sample_batch's launch) from tab->logits[i] with the table's temperature, top_p and coin -> out[0 .. n)
 hipError_t sample_rows(BatchScratch *b, int vocab, int *out, int n, hipStream_t st);

@@ -216,6 +216,9 @@ struct Q8GemmArgs {
     int m, n, d, gs;
 };
 hipError_t launch_q8_gemm(const Q8GemmArgs &a, int epi, hipStream_t st);
+// The same product, bit for bit, for 17 <= m <= 128 in the register-blocked form (q8_gemm_wide.hip): a block
+// owns two weight-row tiles and every token tile of the call.  hipErrorInvalidValue for any other m
+hipError_t launch_q8_gemm_wide(const Q8GemmArgs &a, int epi, hipStream_t st);
 
 // main.zig:361-389: scores, softmax, att.V for the local heads of one layer
 struct AttnArgs {

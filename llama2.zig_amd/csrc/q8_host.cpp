@@ -14,6 +14,7 @@
 
 #include "batch_host.h"
 #include "kind_rows.h"
+#include "wide_decode.h"
 
 using namespace l2z;
 
@@ -21,7 +22,8 @@ namespace {
 
 // The rows of a pass and where its launches put them: m rows; the residual rows x, dim apart; a layer's attention output
 // att and the gated rows h at their pitches; the quantized rows xq and their scales xs (group size gs) that every product
-// reads; st: the pass's stream
+// reads; st: the pass's stream; by_rows: the pass's products take the form its row count picks (q8_gemm_form: the wide
+// step), else launch_q8_gemm whatever m is
 struct Q8Rows {
     int m;
     float *x, *att, *h;
@@ -30,7 +32,19 @@ struct Q8Rows {
     float *xs;
     int gs;
     hipStream_t st;
+    bool by_rows;
 };
+
+// THE form choice of a product of m rows where it is made by the shape: the bits are the same either
+// way, so the thresholds are measurement's to move.  From 17 rows on the register-blocked form, where its blocks of 32 weight
+// rows are at least one a CU: W1 | W3 and the classifier of the 7B shape (688 and 1000 blocks, 1.33 - 1.50 x q8_gemm_kernel at
+// 32 - 128 rows), not its 4096-row products (128 blocks on 256 CUs: 0.75 - 0.85 x; profiles/q8_wide_bench.md).  The
+// threshold rests on those two points: at exactly one block a CU (d = 8192 on 256 CUs) nothing has been measured
+hipError_t q8_gemm_form(const Q8GemmArgs &a, int epi, hipStream_t st)
+{
+    const bool wide = a.m > kQ8GemmTile && (a.d + 31) / 32 >= g_cus;
+    return wide ? launch_q8_gemm_wide(a, epi, st) : launch_q8_gemm(a, epi, st);
+}
 
 // rows of `x`, ldx apart (after the rmsnorm with rms_w, if any), quantized over k -> r.xq, r.xs
 int q8_quantize(const Q8Rows &r, const float *x, int ldx, int k, const float *rms_w)
@@ -47,7 +61,7 @@ int q8_product(const Q8Rows &r, const l2z_weights::Q8Mat &m, int l, int d, int k
     a.xq = r.xq; a.xs = r.xs; a.wq = m.q + at; a.ws = m.s + at / (size_t)r.gs;
     a.out = out; a.ldo = ldo; a.res = out; a.ldres = ldo;
     a.m = r.m; a.n = k; a.d = d; a.gs = r.gs;
-    L2Z_HIP(launch_q8_gemm(a, epi, r.st));
+    L2Z_HIP(r.by_rows ? q8_gemm_form(a, epi, r.st) : launch_q8_gemm(a, epi, r.st));
     return L2Z_OK;
 }
 
@@ -134,7 +148,7 @@ int q8_chunk(l2z_runstate *s, const l2z_weights *w, const Q8Pf &b, const int32_t
     RaggedChunk rg = {};
     rg.seq = b.seq; rg.row_seq = b.row_seq; rg.row_pos = b.row_pos;
     rg.n_seq = 1; rg.seq_max = 1; rg.k = b.k; rg.v = b.v;
-    const Q8Rows r = {P, b.x, b.att, b.h, dim, c.hidden_dim, b.xq, b.xs, w->q8_gs, st};   // (every pitch tight)
+    const Q8Rows r = {P, b.x, b.att, b.h, dim, c.hidden_dim, b.xq, b.xs, w->q8_gs, st, false};   // (every pitch tight)
     return q8_layers(r, c, w, [&](int l, size_t layer_off) -> int {
         L2Z_TRY(q8_product(r, w->q_wq, l, dim, dim, b.q, dim, EPI_STORE));        // :308-320
         L2Z_TRY(q8_product(r, w->q_wk, l, kvd, dim, b.k, kvd, EPI_STORE));
@@ -219,7 +233,7 @@ int l2z::batch_step_q8(int n, const l2z_config &c, l2z_runstate *s0, const l2z_w
     hipStream_t st = s0->stream;
     const int dim = c.dim, hs = dim / c.n_heads, kvd = hs * c.n_kv_heads, gs = w->q8_gs;
     const BatchTable *tab = b->d_tab;
-    const Q8Rows r = {n, b->x, b->att, b->h1, b->ld_att, b->ld_h1, b->q8_xq, b->q8_xs, gs, st};
+    const Q8Rows r = {n, b->x, b->att, b->h1, b->ld_att, b->ld_h1, b->q8_xq, b->q8_xs, gs, st, false};
     L2Z_HIP(launch_q8_embed_rows(w->q8_emb(), tab->tokens, dim, n, b->x, 0, nullptr, nullptr, st));  // :295
     L2Z_TRY(q8_layers(r, c, w, [&](int l, size_t layer_off) -> int {
         // q | k | v (:308-358): RoPE at each row's own position, k | v into each row's own caches
@@ -241,6 +255,34 @@ int l2z::batch_step_q8(int n, const l2z_config &c, l2z_runstate *s0, const l2z_w
     a.m = n; a.n = dim; a.vocab = c.vocab_size; a.gs = gs;
     L2Z_HIP(launch_q8_batch_cls(a, st));
     return L2Z_OK;
+}
+
+// The wide step on int8 group-quantized weights (l2z_transformer_wide_q8): n <= kWideMax rows on s0's prompt
+// scratch (wide_begin has sized it), the rows' tokens, positions and caches in the table rg reads.  Per layer q, k and v are
+// three products into scratch, then the ragged pass's RoPE + cache scatter over the table and the table owner's attention
+// (no bf16 planes: the Wo product reads quantized rows); after the layers the classifier as ONE product into logits
+// [n, ld_logits].  Every product takes the form its row count picks.
+int l2z::wide_step_q8(int n, l2z_runstate *s0, const l2z_weights *w, const RaggedChunk &rg, const int *tokens, int8_t *xq, float *xs,
+                      float *logits, int ld_logits)
+{
+    const l2z_config &c = s0->cfg;
+    hipStream_t st = s0->stream;
+    const int dim = c.dim, hs = s0->sh.hs, kvd = s0->sh.kvd_loc;
+    const size_t kvh_stride = (size_t)c.seq_len * hs;
+    const Q8Rows r = {n, s0->pf_x, s0->pf_att, s0->pf_h1, s0->pf_ld_att, s0->pf_ld_h1, xq, xs, w->q8_gs, st, true};
+    L2Z_HIP(launch_q8_embed_rows(w->q8_emb(), tokens, dim, n, r.x, 0, nullptr, nullptr, st));   // :295
+    L2Z_TRY(q8_layers(r, c, w, [&](int l, size_t layer_off) -> int {
+        L2Z_TRY(q8_product(r, w->q_wq, l, dim, dim, s0->pf_q, dim, EPI_STORE));     // :308-320
+        L2Z_TRY(q8_product(r, w->q_wk, l, kvd, dim, rg.k, kvd, EPI_STORE));
+        L2Z_TRY(q8_product(r, w->q_wv, l, kvd, dim, rg.v, kvd, EPI_STORE));
+        L2Z_HIP(launch_ragged_rope_scatter(s0->pf_q, dim, rg, n, dim, kvd, hs, s0->rope, layer_off, kvh_stride, st));   // :336-358
+        const RaggedLayer L = {s0->pf_q, dim, s0->pf_att, s0->pf_ld_att, n, c.n_heads, hs, c.n_heads / c.n_kv_heads, c.seq_len,
+                               layer_off, kvh_stride, st, nullptr, 0};
+        L2Z_HIP((*rg.attention)(L, nullptr));   // :361-389
+        return L2Z_OK;
+    }));
+    L2Z_TRY(q8_quantize(r, r.x, dim, dim, w->rms_final));   // :426
+    return q8_product(r, w->q_cls, 0, c.vocab_size, dim, logits, ld_logits, EPI_STORE);   // :429
 }
 
 // ---------------------------------------------------------------------------
@@ -272,19 +314,28 @@ extern "C" int l2z_q8_quantize_rows(const float *x, int m, size_t n, const float
     return L2Z_OK;
 }
 
-extern "C" int l2z_q8_gemm(float *out, const int8_t *xq, const float *xs, int m, const int8_t *wq, const float *ws, size_t n,
-                           size_t d, int gs)
+namespace {
+// l2z_q8_gemm (wide false) and l2z_q8_gemm_wide (true), both with the store epilogue, and l2z_q8_gemm_epi: one body, the
+// launcher and the epilogue apart.  EPI_RESID: out holds the residual on entry and is both on the device, as the pass's Wo and
+// W2 launches; EPI_SWIGLU: out is [m, d / 2]
+int q8_gemm_hook(const char *fn, bool wide, int epi, float *out, const int8_t *xq, const float *xs, int m, const int8_t *wq, const float *ws,
+                 size_t n, size_t d, int gs)
 {
     L2Z_CHECK(out && xq && xs && wq && ws && m > 0 && m <= (1 << 20) && n > 0 && d > 0 && n < (1u << 24) && d < (1u << 24),
-              L2Z_ERR_INVALID, "l2z_q8_gemm: bad arguments");
+              L2Z_ERR_INVALID, "%s: bad arguments", fn);
+    L2Z_CHECK(epi == EPI_STORE || epi == EPI_RESID || epi == EPI_SWIGLU, L2Z_ERR_INVALID, "%s: epi = %d (0 store, 2 residual, 3 SwiGLU)", fn, epi);
+    L2Z_CHECK(!wide || (m >= 17 && m <= kWideMax), L2Z_ERR_INVALID, "%s: m = %d outside [17, %d] (fewer rows go to l2z_q8_gemm)", fn, m, kWideMax);
     L2Z_CHECK((gs == 32 || gs == 64) && n % (size_t)gs == 0, L2Z_ERR_INVALID,
-              "l2z_q8_gemm: group size %d (32 or 64, dividing n = %zu)", gs, n);
-    L2Z_CHECK(d % 4 == 0, L2Z_ERR_INVALID, "l2z_q8_gemm: d = %zu (a multiple of 4: a lane stores four features)", d);
+              "%s: group size %d (32 or 64, dividing n = %zu)", fn, gs, n);
+    L2Z_CHECK(d % 4 == 0, L2Z_ERR_INVALID, "%s: d = %zu (a multiple of 4: a lane stores four features)", fn, d);
+    L2Z_CHECK(epi != EPI_SWIGLU || d % 8 == 0, L2Z_ERR_INVALID, "%s: d = %zu (SwiGLU: a multiple of 8, the gated rows' pitch one of 4)", fn, d);
     L2Z_TRY(ensure_device(current_device_for(nullptr)));
     const size_t mp = (size_t)q8_gemm_rows_padded(m), ng = n / (size_t)gs;
     DevBytes dxq, dxs, dwq, dws, dout;
     L2Z_TRY(dxq.alloc(mp * n)); L2Z_TRY(dxs.alloc(mp * ng * 4)); L2Z_TRY(dwq.alloc(d * n)); L2Z_TRY(dws.alloc(d * ng * 4));
+    const size_t out_bytes = (size_t)m * (epi == EPI_SWIGLU ? d / 2 : d) * 4;
     L2Z_TRY(dout.alloc((size_t)m * d * 4));
+    if (epi == EPI_RESID) L2Z_HIP(hipMemcpy(dout.p, out, out_bytes, hipMemcpyHostToDevice));
     // the rows stand padded to whole tiles, the pad rows zero, as the row launch leaves them
     L2Z_HIP(hipMemset(dxq.p, 0, mp * n));
     L2Z_HIP(hipMemset(dxs.p, 0, mp * ng * 4));
@@ -294,10 +345,32 @@ extern "C" int l2z_q8_gemm(float *out, const int8_t *xq, const float *xs, int m,
     L2Z_HIP(hipMemcpy(dws.p, ws, d * ng * 4, hipMemcpyHostToDevice));
     Q8GemmArgs a = {};
     a.xq = (const int8_t *)dxq.p; a.xs = (const float *)dxs.p; a.wq = (const int8_t *)dwq.p; a.ws = (const float *)dws.p;
-    a.out = (float *)dout.p; a.ldo = (int)d;
+    a.out = (float *)dout.p; a.ldo = (int)(epi == EPI_SWIGLU ? d / 2 : d);
+    a.res = a.out; a.ldres = a.ldo;
     a.m = m; a.n = (int)n; a.d = (int)d; a.gs = gs;
-    L2Z_HIP(launch_q8_gemm(a, EPI_STORE, nullptr));
+    L2Z_HIP(wide ? launch_q8_gemm_wide(a, epi, nullptr) : launch_q8_gemm(a, epi, nullptr));
     L2Z_HIP(hipDeviceSynchronize());
-    L2Z_HIP(hipMemcpy(out, dout.p, (size_t)m * d * 4, hipMemcpyDeviceToHost));
+    L2Z_HIP(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
     return L2Z_OK;
+}
+}  // namespace
+
+extern "C" int l2z_q8_gemm(float *out, const int8_t *xq, const float *xs, int m, const int8_t *wq, const float *ws, size_t n,
+                           size_t d, int gs)
+{
+    return q8_gemm_hook("l2z_q8_gemm", false, EPI_STORE, out, xq, xs, m, wq, ws, n, d, gs);
+}
+
+// PREVIEW (include/llama2_hip_test.h): the register-blocked form on its own, 17 <= m <= L2Z_WIDE_MAX
+extern "C" int l2z_q8_gemm_wide(float *out, const int8_t *xq, const float *xs, int m, const int8_t *wq, const float *ws, size_t n,
+                                size_t d, int gs)
+{
+    return q8_gemm_hook("l2z_q8_gemm_wide", true, EPI_STORE, out, xq, xs, m, wq, ws, n, d, gs);
+}
+
+// PREVIEW (include/llama2_hip_test.h): ONE launch of either form with any of the three epilogues, as the passes issue it
+extern "C" int l2z_q8_gemm_epi(int epi, int wide, float *out, const int8_t *xq, const float *xs, int m, const int8_t *wq,
+                               const float *ws, size_t n, size_t d, int gs)
+{
+    return q8_gemm_hook("l2z_q8_gemm_epi", wide != 0, epi, out, xq, xs, m, wq, ws, n, d, gs);
 }

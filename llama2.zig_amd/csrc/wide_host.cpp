@@ -1,4 +1,4 @@
-// wide_host.cpp -- host side of l2z_transformer_wide, l2z_wide_run, l2z_verify_wide and l2z_step_mixed
+// wide_host.cpp -- host side of l2z_transformer_wide, l2z_transformer_wide_q8, l2z_wide_run, l2z_verify_wide and l2z_step_mixed
 // (include/llama2_hip_test.h): up to L2Z_WIDE_MAX independent sequences advanced by one token with one sweep of the weights,
 // the loop of such steps kept on the device, the verify pass over up to L2Z_WIDE_MAX rows of many sequences, and the chunk
 // that holds decode rows AND prompt rows.
@@ -48,13 +48,18 @@ struct WideScratch {
     float *smp = nullptr;               // kWideMax rows of sample_scratch_floats(vocab)
     // l2z_step_mixed (on the first such call): its own table, kMixedSeqMax sequences and kMixedRowsMax rows, and the pinned twin
     MixedTable *d_mtab = nullptr, *h_mtab = nullptr;
+    // l2z_transformer_wide_q8 (on the first such call): the step's quantized rows, [kWideMax, max(dim, hidden_dim)] int8, and
+    // their scales at group size q8_gs (a call with another group size re-makes them)
+    int8_t *q8_xq = nullptr;
+    float *q8_xs = nullptr;
+    int q8_gs = 0;
 };
 
 void wide_free(l2z_runstate *s)
 {
     WideScratch *b = s->wd;
     if (b == nullptr) return;
-    void *ptrs[] = {b->k, b->v, b->logits, b->part, b->d_next, b->d_tab, b->d_ctl, b->d_ids, b->smp, b->d_mtab};
+    void *ptrs[] = {b->k, b->v, b->logits, b->part, b->d_next, b->d_tab, b->d_ctl, b->d_ids, b->smp, b->d_mtab, b->q8_xq, b->q8_xs};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     void *pinned[] = {b->h_next, b->h_tab, b->h_ctl, b->h_ids, b->h_mtab};
@@ -153,6 +158,21 @@ int mixed_alloc(l2z_runstate *s, int R)
     L2Z_TRY(alloc_all("l2z_step_mixed table", {{(void **)&b->d_mtab, sizeof(MixedTable)}}));
     if (b->h_mtab == nullptr) L2Z_HIP(hipHostMalloc((void **)&b->h_mtab, sizeof(MixedTable), hipHostMallocDefault));
     return L2Z_OK;
+}
+
+// l2z_transformer_wide_q8's quantized rows and scales (q8_batch_alloc's rule at kWideMax rows)
+int wide_q8_alloc(l2z_runstate *s, int gs)
+{
+    WideScratch *b = s->wd;
+    if (b->q8_xq != nullptr && b->q8_xs != nullptr && b->q8_gs == gs) return L2Z_OK;
+    if (b->q8_gs != gs && (b->q8_xq != nullptr || b->q8_xs != nullptr)) {   // another group size: other scale rows
+        L2Z_HIP(hipStreamSynchronize(s->stream));
+        if (b->q8_xq) { (void)hipFree(b->q8_xq); b->q8_xq = nullptr; }
+        if (b->q8_xs) { (void)hipFree(b->q8_xs); b->q8_xs = nullptr; }
+    }
+    b->q8_gs = gs;
+    const size_t R = kWideMax, widest = (size_t)std::max(s->cfg.dim, s->cfg.hidden_dim);
+    return alloc_all("l2z_transformer_wide_q8 scratch", {{(void **)&b->q8_xq, R * widest}, {(void **)&b->q8_xs, R * (widest / (size_t)gs) * 4}});
 }
 
 // ---- the frame of a pass: every entry point here is its RaggedCall, the front (check_ragged_call), wide_begin, its own table,
@@ -285,6 +305,37 @@ extern "C" int l2z_transformer_wide(int n, const int32_t *tokens, const int32_t 
         L2Z_HIP(launch_wide_logits_out(b->logits, b->ld_logits, b->d_tab, config->vocab_size, out_next ? b->d_next : nullptr, n, st));
         return L2Z_OK;
     }));
+    if (out_next) L2Z_HIP(hipMemcpyAsync(b->h_next, b->d_next, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    L2Z_TRY(wide_end(call));
+    if (out_next) {
+        L2Z_HIP(hipStreamSynchronize(st));
+        memcpy(out_next, b->h_next, (size_t)n * 4);
+    }
+    return L2Z_OK;
+}
+
+// PREVIEW (include/llama2_hip_test.h): l2z_transformer_wide's contract on int8 group-quantized weights.  The
+// frame is the wide family's; the step is wide_step_q8 (q8_host.cpp), the layers' attention the wide step's own.
+extern "C" int l2z_transformer_wide_q8(int n, const int32_t *tokens, const int32_t *pos, const l2z_config *config,
+                                       l2z_runstate *const *states, const l2z_weights *w, int32_t *out_next)
+{
+    const RaggedCall call = {"l2z_transformer_wide_q8", n, tokens, nullptr, pos, 1, nullptr, nullptr, nullptr, false,
+                             config, states, w, kWideMax, 0, 0, true, "l2z_transformer_wide"};
+    RaggedTotals t;
+    L2Z_TRY(check_ragged_call(call, &t));
+    L2Z_TRY(wide_begin(call, t, [&]() { return wide_q8_alloc(states[0], w->q8_gs); }));
+    l2z_runstate *s0 = states[0];
+    WideScratch *b = s0->wd;
+    hipStream_t st = s0->stream;
+    L2Z_TRY(wide_upload_table(b, call, t));
+    L2Z_HIP(hipEventRecord(b->ev_upload, st));
+    const WideAttn wa = {b->d_tab, b->part, b->seg_cap, t.deepest / kVerifySeg + 1, 0, n, 0};
+    const auto layer = [&wa](const RaggedLayer &L, bool *planes_written) { return launch_wide_attention(L, wa, planes_written); };
+    const RaggedAttention attention = layer;
+    RaggedChunk rg = table_chunk(b->d_tab, n, kWideMax, b->k, b->v, s0);
+    rg.attention = &attention;
+    L2Z_TRY(wide_step_q8(n, s0, w, rg, b->d_tab->tokens, b->q8_xq, b->q8_xs, b->logits, b->ld_logits));
+    L2Z_HIP(launch_wide_logits_out(b->logits, b->ld_logits, b->d_tab, config->vocab_size, out_next ? b->d_next : nullptr, n, st));
     if (out_next) L2Z_HIP(hipMemcpyAsync(b->h_next, b->d_next, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     L2Z_TRY(wide_end(call));
     if (out_next) {
