@@ -739,6 +739,40 @@ int l2z_q8_gemm_wide(float *out, const int8_t *xq, const float *xs, int m, const
 int l2z_q8_gemm_epi(int epi, int wide, float *out, const int8_t *xq, const float *xs, int m, const int8_t *wq, const float *ws,
                     size_t n, size_t d, int gs);
 
+/* ---- Int8 KV cache for the wide q8 step (PREVIEW) ----
+ * THE FORMAT (csrc/kv8_layout.h).  The unit is one kv head's slice of one position: head_size values and ONE f32 scale;
+ * head_size a multiple of 4 up to 256.  The rule is the activation rule of the q8 family over the slice:
+ * s = max|v| / 127 (one correctly rounded f32 division), q = roundf(v / s); an all-zero slice has s = 0 and zeros.  Its
+ * input is the f32 value the f32 cache would have held: K after RoPE, V as produced.  A reader sees f32(q) * s, one
+ * rounding.  The arrays keep the f32 cache's head-major order: K8, V8 int8 [layer][kv head][seq_len][head_size]; KS, VS
+ * f32 [layer][kv head][seq_len].
+ * l2z_runstate_init_kv8: a contiguous, unsharded runstate that holds those four arrays and no f32 caches;
+ * l2z_runstate_free frees it.  WHO TAKES IT: l2z_transformer_wide_q8 (every runstate of the call of this kind, or none:
+ * a mixed call is L2Z_ERR_INVALID), whose step then writes the rows through the format's own scatter and reads them
+ * through its own attention -- q stays f32, the bytes are converted exactly, a score is (q . k8) * ks / sqrt(head_size),
+ * a weighted value fmaf(e * vs, f32(v8), acc), segments of 64 positions and the wide step's combine; a row's result
+ * depends on its own q, its own rows 0 .. pos and its position alone --; l2z_runstate_fork as dst, from a runstate of the
+ * kind (bytes and scales of rows 0 .. n_pos - 1 copied) or from a contiguous f32 one (those rows of every layer
+ * QUANTIZED by the rule: how a prompt gets into such a runstate -- l2z_prefill_q8 on an f32 runstate, then fork); the
+ * logits-only calls (l2z_argmax*, l2z_logits_read / _write, l2z_probs_read, l2z_sample_batch, l2z_synchronize);
+ * l2z_runstate_read, where "key_cache" / "value_cache" are the logical dequantized [layer][seq_len][kv_dim] view.
+ * WHO REFUSES IT, with L2Z_ERR_INVALID before anything is enqueued or changed: every other entry point that reaches KV
+ * rows (l2z_transformer, l2z_prefill, l2z_prefill_q8, l2z_score, the greedy and sampled loops, the batched step, the
+ * verify family, l2z_prefill_batch, l2z_transformer_wide, l2z_wide_run, l2z_verify_wide, l2z_step_mixed), and
+ * l2z_runstate_fork from such a runstate into an f32 or paged one, or into one from a paged one.
+ * l2z_runstate_read_kv8: the raw rows pos0 .. pos0 + n_pos - 1 of one layer, which 0 keys / 1 values, in the reference's
+ * order: out_q [n_pos, kv_dim] and out_s [n_pos, n_kv_heads].  L2Z_ERR_INVALID for another kind of runstate or a range
+ * outside the cache.
+ * l2z_kv8_attention: the attention's two launches on their own (host pointers, synchronous, one layer): q [n, n_heads *
+ * head_size] (RoPE applied), pos [n], row i's caches k8 / v8 [n][n_kv_heads][seq_len][head_size] and ks / vs
+ * [n][n_kv_heads][seq_len] -> out [n, n_heads * head_size].  Rows beyond pos[i], and their scales, are never read.
+ * L2Z_ERR_INVALID for n outside [1, L2Z_WIDE_MAX] or a shape outside the format; L2Z_ERR_STATE for a position outside
+ * [0, seq_len). */
+int l2z_runstate_init_kv8(const l2z_config *config, l2z_runstate **out);
+int l2z_runstate_read_kv8(l2z_runstate *s, int which, int layer, int pos0, int n_pos, int8_t *out_q, float *out_s);
+int l2z_kv8_attention(float *out, const float *q, const int32_t *pos, int n, const int8_t *k8, const float *ks, const int8_t *v8,
+                      const float *vs, int n_heads, int n_kv_heads, int head_size, int seq_len);
+
 #ifdef __cplusplus
 }
 #endif

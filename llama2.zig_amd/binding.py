@@ -139,6 +139,11 @@ def lib():
         L.l2z_transformer_wide_q8.argtypes = [C.c_int, i32p, i32p, cfgp, C.POINTER(vp), vp, i32p]
         L.l2z_q8_gemm_wide.argtypes = [fp, i8p, fp, C.c_int, i8p, fp, sz, sz, C.c_int]
         L.l2z_q8_gemm_epi.argtypes = [C.c_int, C.c_int, fp, i8p, fp, C.c_int, i8p, fp, sz, sz, C.c_int]
+    if hasattr(L, "l2z_runstate_init_kv8"):  # the int8 KV cache of the wide q8 step (PREVIEW)
+        i8p = C.POINTER(C.c_int8)
+        L.l2z_runstate_init_kv8.argtypes = [cfgp, C.POINTER(vp)]
+        L.l2z_runstate_read_kv8.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, i8p, fp]
+        L.l2z_kv8_attention.argtypes = [fp, fp, i32p, C.c_int, i8p, fp, i8p, fp, C.c_int, C.c_int, C.c_int, C.c_int]
     if hasattr(L, "l2z_q8_matvec_case"):
         L.l2z_q8_matvec_case.argtypes = [C.POINTER(Q8Case)]
     if hasattr(L, "l2z_prefill_q8"):  # their batched prompt pass (PREVIEW)
@@ -417,12 +422,17 @@ class KvPool:
 
 class RunState:
     """src/main.zig:119 RunState, device resident.  pool: a paged runstate (l2z_runstate_init_paged), which holds no KV
-    caches of its own and is taken by the wide family only."""
+    caches of its own and is taken by the wide family only.  kv8: a runstate whose KV rows are int8 with one f32 scale per
+    (layer, position, kv head) (l2z_runstate_init_kv8), taken by transformer_wide_q8 and, as dst, by runstate_fork."""
 
-    def __init__(self, cfg, comm: Comm | None = None, pool: KvPool | None = None):
+    def __init__(self, cfg, comm: Comm | None = None, pool: KvPool | None = None, kv8: bool = False):
         self.cfg = _cfg(cfg)
         self.h = C.c_void_p()
         self.pool = pool   # (kept alive: the pool outlives its runstates)
+        if kv8:
+            assert comm is None and pool is None, "a runstate with int8 KV rows is contiguous and unsharded"
+            _chk(lib().l2z_runstate_init_kv8(C.byref(self.cfg), C.byref(self.h)))
+            return
         if pool is not None:
             assert comm is None, "a paged runstate is unsharded"
             _chk(lib().l2z_runstate_init_paged(C.byref(self.cfg), pool.h, C.byref(self.h)))
@@ -437,6 +447,15 @@ class RunState:
         n = C.c_int(0)
         _chk(lib().l2z_runstate_pages(self.h, C.byref(n), ids.ctypes.data_as(C.POINTER(C.c_int32)), cap))
         return ids[:cap].copy()
+
+    def read_kv8(self, which: str, layer: int, pos0: int, n_pos: int):
+        """l2z_runstate_read_kv8: the raw rows pos0 .. pos0 + n_pos - 1 of one layer's keys ("k") or values ("v") of a kv8
+        runstate: (int8 [n_pos, kv_dim], f32 scales [n_pos, n_kv_heads])."""
+        c = self.cfg
+        q = np.empty((n_pos, c.dim // c.n_heads * c.n_kv_heads), np.int8)
+        s = np.empty((n_pos, c.n_kv_heads), np.float32)
+        _chk(lib().l2z_runstate_read_kv8(self.h, {"k": 0, "v": 1}[which], layer, pos0, n_pos, q.ctypes.data_as(C.POINTER(C.c_int8)), _fp(s)))
+        return q, s
 
     def trim(self, n_pos: int) -> None:
         """l2z_runstate_trim: give back every page that lies wholly at or above n_pos."""
@@ -1635,6 +1654,21 @@ def transformer_wide_q8(states, tokens, pos, w: Weights, want_next: bool = True)
     _chk(lib().l2z_transformer_wide_q8(n, t.ctypes.data_as(i32p), p.ctypes.data_as(i32p), C.byref(cfg), ss, w.h,
                                        nxt.ctypes.data_as(i32p) if want_next else None))
     return nxt[:n].copy() if want_next else None
+
+
+def kv8_attention(q, pos, k8, ks, v8, vs, n_heads: int) -> np.ndarray:
+    """The decode attention over int8 KV rows on its own (l2z_kv8_attention): q [n, n_heads * head_size], pos [n], row i's
+    caches k8 / v8 int8 [n, kv heads, seq_len, head_size] and scales ks / vs [n, kv heads, seq_len] -> out like q."""
+    q, pos = _f32(q), np.ascontiguousarray(pos, dtype=np.int32)
+    k8, v8 = np.ascontiguousarray(k8, dtype=np.int8), np.ascontiguousarray(v8, dtype=np.int8)
+    ks, vs = _f32(ks), _f32(vs)
+    n, kvh, S, hs = k8.shape
+    assert q.shape == (n, n_heads * hs) and v8.shape == k8.shape and ks.shape == vs.shape == (n, kvh, S) and pos.shape == (n,)
+    out = np.empty_like(q)
+    i8p = C.POINTER(C.c_int8)
+    _chk(lib().l2z_kv8_attention(_fp(out), _fp(q), pos.ctypes.data_as(C.POINTER(C.c_int32)), n, k8.ctypes.data_as(i8p), _fp(ks),
+                                 v8.ctypes.data_as(i8p), _fp(vs), n_heads, kvh, hs, S))
+    return out
 
 
 def generate_wide_q8(cfg, w: Weights, prompts, n_new: int) -> np.ndarray:

@@ -237,7 +237,7 @@ int check_ragged_call(const RaggedCall &c, RaggedTotals *t)
             L2Z_CHECK(c.states[j]->pool == nullptr, L2Z_ERR_INVALID,
                       "%s: states[%d] is a paged runstate (l2z_runstate_init_paged); on int8 group-quantized weights the runstates are contiguous", fn, j);
     }
-    for (int j = 0; j < c.n; j++) L2Z_TRY(check_pair(c.config, c.states[j], c.w, !c.q8, c.q8));
+    for (int j = 0; j < c.n; j++) L2Z_TRY(check_pair(c.config, c.states[j], c.w, !c.q8, c.q8, c.kv8));
     L2Z_TRY(prefill_check(c.config, c.states[0]));
     if (c.temperature != nullptr) {   // l2z_sample_batch's rules for every sequence; a greedy one's coins are not read
         L2Z_CHECK(c.top_p != nullptr, L2Z_ERR_INVALID, "%s: top_p is NULL beside a temperature array", fn);
@@ -493,6 +493,12 @@ extern "C" int l2z_runstate_fork(l2z_runstate *dst, const l2z_runstate *src, int
     const l2z_config &c = src->cfg;
     L2Z_CHECK(n_pos >= 0 && n_pos <= c.seq_len, L2Z_ERR_STATE, "l2z_runstate_fork: n_pos = %d outside [0, %d]", n_pos,
               c.seq_len);
+    // ---- int8 KV rows (l2z_runstate_init_kv8): into such a runstate from one of its kind (a copy) or from a
+    // contiguous f32 one (its rows quantized); every other pairing with such a side is refused ----
+    const bool kv8 = dst->is_kv8();
+    L2Z_CHECK(kv8 || !src->is_kv8(), L2Z_ERR_INVALID,
+              "l2z_runstate_fork: src holds int8 KV rows, dst does not (int8 rows are not turned back into f32 or paged ones)");
+    L2Z_CHECK(!kv8 || src->pool == nullptr, L2Z_ERR_INVALID, "l2z_runstate_fork: dst holds int8 KV rows, src is paged");
     L2Z_HIP(hipSetDevice(src->device));
     // ---- a paged side (include/llama2_hip_test.h l2z_kvpool): dst gives back its pages, then shares src's whole pages
     // where both draw from one pool, and attaches private ones for the rows that are copied ----
@@ -530,7 +536,9 @@ extern "C" int l2z_runstate_fork(l2z_runstate *dst, const l2z_runstate *src, int
     // run of n_pos * head_size floats per (layer, kv head), seq_len * head_size floats apart
     const size_t hs = (size_t)c.dim / c.n_heads, pitch = (size_t)c.seq_len * hs * 4, width = (size_t)n_pos * hs * 4;
     const size_t rows = (size_t)c.n_layers * c.n_kv_heads;
-    if (paged) {
+    if (kv8) {
+        if (n_pos > 0 && rc == L2Z_OK) rc = kv8_fork_rows(dst, src, n_pos);
+    } else if (paged) {
         if (rc == L2Z_OK) rc = kv_copy_rows(dst, src, whole * kKvPage, n_pos);
     } else if (n_pos > 0 && rc == L2Z_OK) {
         hip(hipMemcpy2DAsync(dst->key_cache, pitch, src->key_cache, pitch, width, rows, hipMemcpyDeviceToDevice, dst->stream),

@@ -99,6 +99,8 @@ struct RaggedCall {
     // f32_entry: where a message sends f32 and packed weights
     bool q8;
     const char *f32_entry;
+    // the entry takes runstates with int8 KV rows (l2z_runstate_init_kv8) as well as ones with f32 rows, all of one kind
+    bool kv8;
 };
 struct RaggedTotals {
     int R;          // rows in all
@@ -107,7 +109,7 @@ struct RaggedTotals {
     bool sampled;   // some sequence draws
 };
 // The front of such a call; a refusal enqueues nothing and changes no state.  In this order: no device, null arguments, the
-// runstates (check_states), one kind of cache (kv_check_kind), the row counts, every runstate against config and w
+// runstates (check_states), one kind of cache (kv_check_kind: contiguous f32, int8 or paged), the row counts, every runstate against config and w
 // (check_pair; a q8 entry: check_q8_step first), states[0] on the prompt pass (prefill_check), the draws and their coins, then positions and tokens sequence
 // by sequence.
 int check_ragged_call(const RaggedCall &c, RaggedTotals *t);

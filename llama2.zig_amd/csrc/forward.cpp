@@ -36,7 +36,7 @@ struct Prof {
         }                                                                                 \
     } while (0)
 
-int check_pair(const l2z_config *config, const l2z_runstate *s, const l2z_weights *w, bool paged_ok, bool q8_ok)
+int check_pair(const l2z_config *config, const l2z_runstate *s, const l2z_weights *w, bool paged_ok, bool q8_ok, bool kv8_ok)
 {
     L2Z_CHECK(config && s && w, L2Z_ERR_INVALID, "null config / runstate / weights");
     L2Z_CHECK(q8_ok || !w->is_q8(), L2Z_ERR_INVALID,
@@ -47,6 +47,8 @@ int check_pair(const l2z_config *config, const l2z_runstate *s, const l2z_weight
     L2Z_CHECK(paged_ok || s->pool == nullptr, L2Z_ERR_INVALID,
               "a paged runstate (l2z_runstate_init_paged) is taken by the wide family only: l2z_prefill_batch, "
               "l2z_transformer_wide, l2z_wide_run, l2z_verify_wide");
+    L2Z_CHECK(kv8_ok || !s->is_kv8(), L2Z_ERR_INVALID,
+              "a runstate with int8 KV rows (l2z_runstate_init_kv8) is taken by l2z_transformer_wide_q8 only");
     L2Z_CHECK(memcmp(config, &s->cfg, sizeof *config) == 0 &&
                   memcmp(config, &w->cfg, sizeof *config) == 0,
               L2Z_ERR_INVALID, "config does not match the one RunState / Weights were built with");
@@ -532,6 +534,7 @@ extern "C" int l2z_greedy_begin(l2z_runstate *s, const int32_t *prompt, int n_pr
               L2Z_ERR_INVALID, "l2z_greedy_begin: bad arguments");
     L2Z_CHECK(n_prompt <= s->cfg.seq_len, L2Z_ERR_INVALID, "prompt longer than seq_len");
     L2Z_CHECK(s->pool == nullptr, L2Z_ERR_INVALID, "l2z_greedy_begin: a paged runstate is taken by the wide family only");
+    L2Z_CHECK(!s->is_kv8(), L2Z_ERR_INVALID, "l2z_greedy_begin: a runstate with int8 KV rows is taken by l2z_transformer_wide_q8 only");
     for (int i = 0; i < n_prompt; i++)
         L2Z_CHECK(prompt[i] >= 0 && prompt[i] < s->cfg.vocab_size, L2Z_ERR_INVALID,
                   "prompt[%d] = %d out of vocabulary", i, prompt[i]);

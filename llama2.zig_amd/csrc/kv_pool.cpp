@@ -21,6 +21,9 @@ int kv_check_kind(const char *fn, int n, l2z_runstate *const *states)
                   "%s: states[%d] is %s, states[0] is not (the runstates of a call are all contiguous or all paged)", fn, i,
                   states[i]->pool ? "paged" : "contiguous");
         L2Z_CHECK(states[i]->pool == pool, L2Z_ERR_INVALID, "%s: states[%d] draws its pages from another pool than states[0]", fn, i);
+        L2Z_CHECK(states[i]->is_kv8() == states[0]->is_kv8(), L2Z_ERR_INVALID,
+                  "%s: states[%d] holds %s KV rows, states[0] does not (the runstates of a call are of one kind)", fn, i,
+                  states[i]->is_kv8() ? "int8" : "f32");
     }
     return L2Z_OK;
 }

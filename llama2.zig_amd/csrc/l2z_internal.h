@@ -441,6 +441,9 @@ struct RaggedLayer {
 // A chunk's attention as the layer loop sees it (prefill_host.cpp prefill_stage): the owner of the chunk's table binds its
 // own launcher and that launcher's table to it
 using RaggedAttention = FnRef<hipError_t(const RaggedLayer &, bool *planes_written)>;
+// ... and the launch between a layer's q | k | v products and its attention, where the table's owner brings one: q [P, ldq]
+// rotated in place, the chunk's k / v rows into the sequences' caches (launch_ragged_rope_scatter's contract)
+using RaggedScatter = FnRef<hipError_t(float *q, int ldq, int P, size_t layer_off, size_t kv_head_stride, hipStream_t st)>;
 // The table of one chunk (device pointers; built on the host and uploaded with the tokens).  tiles: the flash attention's
 // blocks -- .x the sequence slot, .y the first of its (up to 64) queries as a row of that sequence's segment --, the
 // ones with the most key rows first.  The layer loop knows no caller: whoever owns the table says how many sequence slots
@@ -459,6 +462,8 @@ struct RaggedChunk {
                             // attention launches, alive for the pass (the wide step's, the wide verify's, the mixed chunk's)
     const int *att_rows;    // != null: the n_att_rows rows launch_ragged_attention's block-per-(head, row) form serves (the
     int n_att_rows;         // flash form's are the tile list's); null: all P
+    const RaggedScatter *scatter;   // null: launch_ragged_rope_scatter on this table; else the launch in its place, alive for the
+                            // pass (int8 KV rows, kv8.h: wide_step_q8 takes it as it takes the attention)
 };
 // q [P, dim] rotated in place, k rotated, and k / v stored into row row_pos[r] of sequence row_seq[r]'s caches: the
 // arithmetic of the q | k | v product's own epilogue (prefill_gemm.hip), one launch

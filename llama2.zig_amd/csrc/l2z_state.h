@@ -152,6 +152,11 @@ struct l2z_runstate {
     l2z::KvSeq pg;
     int32_t *d_pages = nullptr, *h_pages = nullptr;
     bool pages_dirty = false;
+    // l2z_runstate_init_kv8 (kv8_layout.h): the KV rows as int8 values [layer][kv head][seq_len][head_size] and
+    // one f32 scale per (layer, kv head, position), in place of key_cache / value_cache, which such a runstate does not have
+    int8_t *k8 = nullptr, *v8 = nullptr;
+    float *ks8 = nullptr, *vs8 = nullptr;
+    bool is_kv8() const { return k8 != nullptr; }
     float2 *rope = nullptr;  // (seq_len, head_size/2) {cos, sin}
     // loop state on the device
     int *d_token = nullptr, *d_pos = nullptr, *d_prompt = nullptr, *d_n_prompt = nullptr;
@@ -237,8 +242,10 @@ struct Prof;
 // s->key_cache refuses them here with L2Z_ERR_INVALID
 // q8_ok: the entry point takes int8 group-quantized weights (the single-sequence decode: l2z_transformer, the greedy and
 // sampled loops, l2z_time_kind, l2z_profile_forward); every other one refuses them here, before it enqueues anything
+// kv8_ok: the entry point takes runstates with int8 KV rows (l2z_runstate_init_kv8: l2z_transformer_wide_q8 alone); every
+// other one refuses them here, so none of them reaches a kernel with such a runstate's null key_cache / value_cache
 int check_pair(const l2z_config *config, const l2z_runstate *s, const l2z_weights *w, bool paged_ok = false,
-               bool q8_ok = false);
+               bool q8_ok = false, bool kv8_ok = false);
 // attention variant of a position (the host knows pos and replays the graph captured for its variant):
 // 0 short context (256-thread speculative form), 1 one block per head as the shape picks, 2 split with 256
 // threads per block, 3 split with 1024
@@ -278,7 +285,8 @@ int prefill_rows_logits(l2z_runstate *s, const l2z_weights *w, int P, float *out
 int ragged_alloc(l2z_runstate *s, int need);
 
 // kv_pool.cpp: paged runstates in a call of the wide family (a call without them passes through all of these untouched)
-// The runstates are of one kind -- all contiguous, or all paged from one pool made with their config --, else L2Z_ERR_INVALID
+// The runstates are of one kind -- all contiguous with f32 rows, all with int8 rows (l2z_runstate_init_kv8), or all paged from
+// one pool made with their config --, else L2Z_ERR_INVALID
 int kv_check_kind(const char *fn, int n, l2z_runstate *const *states);
 // Before anything is enqueued: sequence j will write positions pos0[j] .. pos0[j] + (counts ? counts[j] : count) - 1.
 // L2Z_ERR_STATE if one of them lies in a page shared with another sequence or a page below pos0[j] is not attached, L2Z_ERR_OOM if the pool's free pages do not cover
@@ -295,6 +303,10 @@ int kv_release(l2z_runstate *s, int n_pos);
 // rows 0 .. n_pos - 1 of src's caches -> dst's, on dst's stream, either of them paged (both paged: rows r0 .. only)
 int kv_copy_rows(l2z_runstate *dst, const l2z_runstate *src, int r0, int n_pos);
 void kv_runstate_free(l2z_runstate *s);   // l2z_runstate_free's part: pages back, tables freed, the pool's count down
+
+// kv8_host.cpp: l2z_runstate_fork's rows into a runstate with int8 KV rows, on dst's stream: rows 0 .. n_pos - 1 of every
+// layer copied (src of the same kind) or quantized (src contiguous f32: kv8_scatter.hip's slice function)
+int kv8_fork_rows(l2z_runstate *dst, const l2z_runstate *src, int n_pos);
 
 // batch_host.cpp
 void batch_free(l2z_runstate *s);

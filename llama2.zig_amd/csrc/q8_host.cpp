@@ -259,7 +259,8 @@ int l2z::batch_step_q8(int n, const l2z_config &c, l2z_runstate *s0, const l2z_w
 
 // The wide step on int8 group-quantized weights (l2z_transformer_wide_q8): n <= kWideMax rows on s0's prompt
 // scratch (wide_begin has sized it), the rows' tokens, positions and caches in the table rg reads.  Per layer q, k and v are
-// three products into scratch, then the ragged pass's RoPE + cache scatter over the table and the table owner's attention
+// three products into scratch, then the ragged pass's RoPE + cache scatter over the table -- or the table owner's launch in its
+// place (rg.scatter: int8 KV rows) -- and the table owner's attention
 // (no bf16 planes: the Wo product reads quantized rows); after the layers the classifier as ONE product into logits
 // [n, ld_logits].  Every product takes the form its row count picks.
 int l2z::wide_step_q8(int n, l2z_runstate *s0, const l2z_weights *w, const RaggedChunk &rg, const int *tokens, int8_t *xq, float *xs,
@@ -275,7 +276,8 @@ int l2z::wide_step_q8(int n, l2z_runstate *s0, const l2z_weights *w, const Ragge
         L2Z_TRY(q8_product(r, w->q_wq, l, dim, dim, s0->pf_q, dim, EPI_STORE));     // :308-320
         L2Z_TRY(q8_product(r, w->q_wk, l, kvd, dim, rg.k, kvd, EPI_STORE));
         L2Z_TRY(q8_product(r, w->q_wv, l, kvd, dim, rg.v, kvd, EPI_STORE));
-        L2Z_HIP(launch_ragged_rope_scatter(s0->pf_q, dim, rg, n, dim, kvd, hs, s0->rope, layer_off, kvh_stride, st));   // :336-358
+        if (rg.scatter != nullptr) L2Z_HIP((*rg.scatter)(s0->pf_q, dim, n, layer_off, kvh_stride, st));   // (int8 KV rows, kv8.h)
+        else L2Z_HIP(launch_ragged_rope_scatter(s0->pf_q, dim, rg, n, dim, kvd, hs, s0->rope, layer_off, kvh_stride, st));   // :336-358
         const RaggedLayer L = {s0->pf_q, dim, s0->pf_att, s0->pf_ld_att, n, c.n_heads, hs, c.n_heads / c.n_kv_heads, c.seq_len,
                                layer_off, kvh_stride, st, nullptr, 0};
         L2Z_HIP((*rg.attention)(L, nullptr));   // :361-389

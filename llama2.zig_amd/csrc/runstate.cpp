@@ -7,13 +7,15 @@
 #include <mutex>
 #include <vector>
 
+#include "kv8_layout.h"
 #include "l2z_state.h"
 
 using namespace l2z;
 
 // ---------------------------------------------------------------------------
-// src/main.zig:137 RunState.init; pool != null (l2z_runstate_init_paged): no caches, a page table instead
-static int runstate_make(const l2z_config *config, const l2z_comm *comm, l2z_kvpool *pool, l2z_runstate **out)
+// src/main.zig:137 RunState.init; pool != null (l2z_runstate_init_paged): no caches, a page table instead; kv8
+// (l2z_runstate_init_kv8): no f32 caches, the four arrays of kv8_layout.h instead
+static int runstate_make(const l2z_config *config, const l2z_comm *comm, l2z_kvpool *pool, l2z_runstate **out, bool kv8 = false)
 {
     L2Z_CHECK(config != nullptr && out != nullptr, L2Z_ERR_INVALID, "runstate_init: null argument");
     const int dev = current_device_for(comm);
@@ -74,7 +76,12 @@ static int runstate_make(const l2z_config *config, const l2z_comm *comm, l2z_kvp
     if (sh.scheme_b) alloc((void **)&s->part, (size_t)c.dim * 4);
     alloc((void **)&s->q, (size_t)c.dim * 4);
     alloc((void **)&s->logits, (size_t)c.vocab_size * 4);
-    if (pool == nullptr) {
+    if (kv8) {
+        alloc((void **)&s->k8, kv);
+        alloc((void **)&s->v8, kv);
+        alloc((void **)&s->ks8, kv / (size_t)sh.hs * 4);
+        alloc((void **)&s->vs8, kv / (size_t)sh.hs * 4);
+    } else if (pool == nullptr) {
         alloc((void **)&s->key_cache, kv * 4);
         alloc((void **)&s->value_cache, kv * 4);
     } else {
@@ -188,6 +195,17 @@ extern "C" int l2z_runstate_init_paged(const l2z_config *config, l2z_kvpool *poo
     return runstate_make(config, nullptr, pool, out);
 }
 
+// PREVIEW (include/llama2_hip_test.h): a contiguous, unsharded runstate whose KV rows are int8
+extern "C" int l2z_runstate_init_kv8(const l2z_config *config, l2z_runstate **out)
+{
+    L2Z_CHECK(config != nullptr && out != nullptr, L2Z_ERR_INVALID, "l2z_runstate_init_kv8: null argument");
+    const l2z_config &c = *config;
+    L2Z_CHECK(c.dim > 0 && c.n_heads > 0 && c.n_kv_heads > 0 && c.n_layers > 0 && c.seq_len > 0 && c.dim % c.n_heads == 0 &&
+                  c.n_heads % c.n_kv_heads == 0 && kv8::head_size_ok(c.dim / c.n_heads),
+              L2Z_ERR_INVALID, "l2z_runstate_init_kv8: the format takes a head_size that is a multiple of 4, at most 256");
+    return runstate_make(config, nullptr, nullptr, out, true);
+}
+
 extern "C" void l2z_runstate_free(l2z_runstate *s)
 {
     if (!s) return;
@@ -202,7 +220,7 @@ extern "C" void l2z_runstate_free(l2z_runstate *s)
                     s->d_token, s->d_pos, s->d_prompt, s->d_n_prompt, s->d_out_tokens, s->d_argmax,
                     s->d_probs, s->d_part_val, s->d_part_idx, s->d_attn_part, s->d_attn_cnt, s->pf_x, s->pf_xn, s->pf_q,
                     s->pf_att, s->pf_h1, s->pf_stage, s->pf_part, s->pf_tokens, s->d_push, s->pf_sk.part, s->pf_sk.cnt, s->pf_sk.x3, s->pf_sk.x3b, s->part, s->sc_ws, s->sc_seq,
-                    s->rg_k, s->rg_v, s->rg_tab, s->q8pf, s->d_smp_ctl, s->d_smp_scratch};
+                    s->rg_k, s->rg_v, s->rg_tab, s->q8pf, s->d_smp_ctl, s->d_smp_scratch, s->k8, s->v8, s->ks8, s->vs8};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (s->h_stage) (void)hipHostFree(s->h_stage);
@@ -246,6 +264,8 @@ extern "C" int l2z_runstate_read(l2z_runstate *s, const char *name, size_t offse
     else if (k == "value_cache") { p = s->value_cache; n = kv; }
     const bool paged_kv = s->pool != nullptr && (k == "key_cache" || k == "value_cache");
     if (paged_kv) p = k == "key_cache" ? s->pool->k : s->pool->v;   // (the pages are gathered below)
+    const bool kv8_kv = s->is_kv8() && (k == "key_cache" || k == "value_cache");
+    if (kv8_kv) p = k == "key_cache" ? s->ks8 : s->vs8;   // (the logical view f32(q) * s is formed below)
     L2Z_CHECK(p != nullptr, L2Z_ERR_INVALID, "l2z_runstate_read: unknown buffer '%s'", name);
     L2Z_CHECK(offset + count <= n, L2Z_ERR_INVALID, "l2z_runstate_read: out of range");
     L2Z_HIP(hipSetDevice(s->device));
@@ -268,6 +288,13 @@ extern "C" int l2z_runstate_read(l2z_runstate *s, const char *name, size_t offse
                                         p + (size_t)s->pg.pages[pg] * s->pool->page_floats + l * (kvd / hs) * run, run * 4,
                                         rows * hs * 4, kvd / hs, hipMemcpyDeviceToHost));
                 }
+            } else if (kv8_kv) {
+                // the layer's bytes and scales, then what a reader of the format sees: f32(q) * s, one rounding
+                std::vector<int8_t> q8(layer);
+                std::vector<float> sc(layer / hs);
+                L2Z_HIP(hipMemcpy(q8.data(), (k == "key_cache" ? s->k8 : s->v8) + l * layer, layer, hipMemcpyDeviceToHost));
+                L2Z_HIP(hipMemcpy(sc.data(), p + l * (layer / hs), layer / hs * 4, hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < layer; i++) host[i] = (float)q8[i] * sc[i / hs];
             } else
                 L2Z_HIP(hipMemcpy(host.data(), p + l * layer, layer * sizeof(float), hipMemcpyDeviceToHost));
             const size_t lo = std::max(offset, l * layer), hi = std::min(offset + count, (l + 1) * layer);
@@ -279,6 +306,35 @@ extern "C" int l2z_runstate_read(l2z_runstate *s, const char *name, size_t offse
         return L2Z_OK;
     }
     L2Z_HIP(hipMemcpy(out, p + offset, count * sizeof(float), hipMemcpyDeviceToHost));
+    return L2Z_OK;
+}
+
+// PREVIEW (include/llama2_hip_test.h): the raw int8 rows pos0 .. pos0 + n_pos - 1 of one layer of a kv8 runstate, in the
+// reference's order: out_q [n_pos, kv_dim], out_s [n_pos, n_kv_heads]; which: 0 keys, 1 values
+extern "C" int l2z_runstate_read_kv8(l2z_runstate *s, int which, int layer, int pos0, int n_pos, int8_t *out_q, float *out_s)
+{
+    L2Z_CHECK(s != nullptr && out_q != nullptr && out_s != nullptr, L2Z_ERR_INVALID, "l2z_runstate_read_kv8: null argument");
+    L2Z_CHECK(s->is_kv8(), L2Z_ERR_INVALID, "l2z_runstate_read_kv8: not a runstate with int8 KV rows (l2z_runstate_init_kv8)");
+    const l2z_config &c = s->cfg;
+    L2Z_CHECK((which == 0 || which == 1) && layer >= 0 && layer < c.n_layers && n_pos >= 1 && pos0 >= 0 && pos0 <= c.seq_len - n_pos,
+              L2Z_ERR_INVALID, "l2z_runstate_read_kv8: which = %d, layer = %d, positions %d .. %lld out of range", which, layer, pos0,
+              (long long)pos0 + n_pos - 1);
+    L2Z_HIP(hipSetDevice(s->device));
+    L2Z_HIP(hipStreamSynchronize(s->stream));
+    const kv8::Dims d = {c.n_layers, c.n_kv_heads, c.seq_len, s->sh.hs};
+    const size_t hs = (size_t)d.head_size, kvh_n = (size_t)c.n_kv_heads;
+    // head-major on the device: one strided copy per array brings [kv head][n_pos], permuted to [n_pos][kv head] below
+    std::vector<int8_t> q((size_t)n_pos * kvh_n * hs);
+    std::vector<float> sc((size_t)n_pos * kvh_n);
+    L2Z_HIP(hipMemcpy2D(q.data(), hs * n_pos, (which ? s->v8 : s->k8) + kv8::value_at(d, layer, 0, pos0, 0), (size_t)d.seq_len * hs,
+                        hs * n_pos, kvh_n, hipMemcpyDeviceToHost));
+    L2Z_HIP(hipMemcpy2D(sc.data(), (size_t)n_pos * 4, (which ? s->vs8 : s->ks8) + kv8::scale_at(d, layer, 0, pos0), (size_t)d.seq_len * 4,
+                        (size_t)n_pos * 4, kvh_n, hipMemcpyDeviceToHost));
+    for (size_t h = 0; h < kvh_n; h++)
+        for (size_t t = 0; t < (size_t)n_pos; t++) {
+            memcpy(out_q + (t * kvh_n + h) * hs, q.data() + (h * n_pos + t) * hs, hs);
+            out_s[t * kvh_n + h] = sc[h * n_pos + t];
+        }
     return L2Z_OK;
 }
 

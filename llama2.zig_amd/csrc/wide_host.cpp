@@ -16,6 +16,7 @@
 #include <cstring>
 
 #include "batch_host.h"
+#include "kv8.h"
 #include "mixed_step.h"
 #include "wide_decode.h"
 
@@ -86,8 +87,12 @@ void wide_verify_forget(l2z_runstate *s)
 
 namespace {
 
-constexpr size_t kTabBytes = sizeof(WideTable) + sizeof(WideVerdictCtl);
+// behind the table, in the same allocations and the same copy: l2z_verify_wide's controls, or the sequences' int8 arrays
+// (l2z_transformer_wide_q8 on runstates with int8 KV rows: Kv8Seq, slot j = sequence j)
+constexpr size_t kCtlBytes = sizeof(WideTable) + sizeof(WideVerdictCtl), kKv8Bytes = sizeof(WideTable) + kWideMax * sizeof(Kv8Seq);
+constexpr size_t kTabBytes = kCtlBytes > kKv8Bytes ? kCtlBytes : kKv8Bytes;
 static_assert(sizeof(WideTable) % alignof(WideVerdictCtl) == 0, "the controls sit right behind the table");
+static_assert(sizeof(WideTable) % alignof(Kv8Seq) == 0, "the int8 arrays' table sits right behind the table");
 
 int wide_alloc(l2z_runstate *s)
 {
@@ -258,7 +263,13 @@ int wide_upload_table(WideScratch *b, const RaggedCall &c, const RaggedTotals &t
                 ctl->coins[r] = c.temperature[j] > 0.0f ? c.coins[r] : 0.0f;
         }
     }
-    L2Z_HIP(hipMemcpyAsync(b->d_tab, t, ctl_up ? kTabBytes : sizeof(WideTable), hipMemcpyHostToDevice, c.states[0]->stream));
+    const bool kv8_up = c.states[0]->is_kv8();   // (never beside the controls: such runstates come to the q8 step alone)
+    if (kv8_up) {
+        Kv8Seq *q8 = (Kv8Seq *)(t + 1);
+        for (int j = 0; j < c.n; j++) q8[j] = {c.states[j]->k8, c.states[j]->v8, c.states[j]->ks8, c.states[j]->vs8};
+    }
+    L2Z_HIP(hipMemcpyAsync(b->d_tab, t, ctl_up ? kCtlBytes : kv8_up ? kKv8Bytes : sizeof(WideTable), hipMemcpyHostToDevice,
+                           c.states[0]->stream));
     return L2Z_OK;
 }
 
@@ -320,7 +331,7 @@ extern "C" int l2z_transformer_wide_q8(int n, const int32_t *tokens, const int32
                                        l2z_runstate *const *states, const l2z_weights *w, int32_t *out_next)
 {
     const RaggedCall call = {"l2z_transformer_wide_q8", n, tokens, nullptr, pos, 1, nullptr, nullptr, nullptr, false,
-                             config, states, w, kWideMax, 0, 0, true, "l2z_transformer_wide"};
+                             config, states, w, kWideMax, 0, 0, true, "l2z_transformer_wide", true};
     RaggedTotals t;
     L2Z_TRY(check_ragged_call(call, &t));
     L2Z_TRY(wide_begin(call, t, [&]() { return wide_q8_alloc(states[0], w->q8_gs); }));
@@ -330,10 +341,22 @@ extern "C" int l2z_transformer_wide_q8(int n, const int32_t *tokens, const int32
     L2Z_TRY(wide_upload_table(b, call, t));
     L2Z_HIP(hipEventRecord(b->ev_upload, st));
     const WideAttn wa = {b->d_tab, b->part, b->seg_cap, t.deepest / kVerifySeg + 1, 0, n, 0};
-    const auto layer = [&wa](const RaggedLayer &L, bool *planes_written) { return launch_wide_attention(L, wa, planes_written); };
+    // runstates with int8 KV rows (all of the call or none: kv_check_kind): the scatter and the attention of kv8.h over the
+    // arrays' table behind the WideTable; else exactly the launches of the f32 caches
+    const bool kv8 = s0->is_kv8();
+    const Kv8Seq *seq8 = (const Kv8Seq *)(b->d_tab + 1);
+    const auto layer = [&](const RaggedLayer &L, bool *planes_written) {
+        return kv8 ? launch_kv8_attention(L, wa, seq8, planes_written) : launch_wide_attention(L, wa, planes_written);
+    };
     const RaggedAttention attention = layer;
     RaggedChunk rg = table_chunk(b->d_tab, n, kWideMax, b->k, b->v, s0);
     rg.attention = &attention;
+    const auto scatter8 = [&](float *q, int ldq, int P, size_t layer_off, size_t kv_head_stride, hipStream_t stream) {
+        return launch_kv8_rope_scatter(q, ldq, rg, seq8, P, config->dim, s0->sh.kvd_loc, s0->sh.hs, config->seq_len, s0->rope, layer_off,
+                                       kv_head_stride, stream);
+    };
+    const RaggedScatter scatter = scatter8;
+    if (kv8) rg.scatter = &scatter;
     L2Z_TRY(wide_step_q8(n, s0, w, rg, b->d_tab->tokens, b->q8_xq, b->q8_xs, b->logits, b->ld_logits));
     L2Z_HIP(launch_wide_logits_out(b->logits, b->ld_logits, b->d_tab, config->vocab_size, out_next ? b->d_next : nullptr, n, st));
     if (out_next) L2Z_HIP(hipMemcpyAsync(b->h_next, b->d_next, (size_t)n * 4, hipMemcpyDeviceToHost, st));
