@@ -747,13 +747,15 @@ int l2z_q8_gemm_epi(int epi, int wide, float *out, const int8_t *xq, const float
  * rounding.  The arrays keep the f32 cache's head-major order: K8, V8 int8 [layer][kv head][seq_len][head_size]; KS, VS
  * f32 [layer][kv head][seq_len].
  * l2z_runstate_init_kv8: a contiguous, unsharded runstate that holds those four arrays and no f32 caches;
- * l2z_runstate_free frees it.  WHO TAKES IT: l2z_transformer_wide_q8 (every runstate of the call of this kind, or none:
+ * l2z_runstate_free frees it.  WHO TAKES IT: l2z_prefill_kv8 (the prompt pass straight into the int8 rows, DESIGN.md 4.29,
+ * below); l2z_transformer_wide_q8 (every runstate of the call of this kind, or none:
  * a mixed call is L2Z_ERR_INVALID), whose step then writes the rows through the format's own scatter and reads them
  * through its own attention -- q stays f32, the bytes are converted exactly, a score is (q . k8) * ks / sqrt(head_size),
  * a weighted value fmaf(e * vs, f32(v8), acc), segments of 64 positions and the wide step's combine; a row's result
  * depends on its own q, its own rows 0 .. pos and its position alone --; l2z_runstate_fork as dst, from a runstate of the
  * kind (bytes and scales of rows 0 .. n_pos - 1 copied) or from a contiguous f32 one (those rows of every layer
- * QUANTIZED by the rule: how a prompt gets into such a runstate -- l2z_prefill_q8 on an f32 runstate, then fork); the
+ * QUANTIZED by the rule: the way a prompt took into such a runstate before l2z_prefill_kv8 -- l2z_prefill_q8 on an f32
+ * runstate, then fork); the
  * logits-only calls (l2z_argmax*, l2z_logits_read / _write, l2z_probs_read, l2z_sample_batch, l2z_synchronize);
  * l2z_runstate_read, where "key_cache" / "value_cache" are the logical dequantized [layer][seq_len][kv_dim] view.
  * WHO REFUSES IT, with L2Z_ERR_INVALID before anything is enqueued or changed: every other entry point that reaches KV
@@ -772,6 +774,33 @@ int l2z_runstate_init_kv8(const l2z_config *config, l2z_runstate **out);
 int l2z_runstate_read_kv8(l2z_runstate *s, int which, int layer, int pos0, int n_pos, int8_t *out_q, float *out_s);
 int l2z_kv8_attention(float *out, const float *q, const int32_t *pos, int n, const int8_t *k8, const float *ks, const int8_t *v8,
                       const float *vs, int n_heads, int n_kv_heads, int head_size, int seq_len);
+
+/* ---- Prompt pass straight into int8 KV rows (PREVIEW) ----
+ * l2z_prefill_kv8: l2z_prefill_q8's contract and state change on q8 weights and a runstate made by l2z_runstate_init_kv8,
+ * under a name of its own (l2z_prefill_q8 keeps refusing such a runstate).  Rows pos0 .. pos0 + n_tokens - 1 of K8 / KS /
+ * V8 / VS are written in every layer and no other row, byte or scale is touched; the last position's logits and argmax
+ * candidates are left in the runstate; l2z_transformer_wide_q8 goes on from pos0 + n_tokens.  No f32 cache exists at any
+ * point.  THE ARITHMETIC: the products, chunks and scratch are l2z_prefill_q8's; per layer the format's scatter (4.28) runs
+ * FIRST and the attention then reads the int8 arrays alone, the chunk's own rows included, so what a query sees at key t is
+ * f32(q8) * s -- the values the wide step would see had the prompt been stepped.  The attention has two forms.  Head sizes
+ * 64 and 128, chunks of more than 32 rows: one block per (head, 64 queries) on the F32 matrix cores, q in f32, the K and V
+ * tiles int8 in LDS and f32 only in registers, a score (q . k8) * ks / sqrt(head_size), a weight e * vs, running softmax.
+ * Every other head size and chunks of at most 32 rows: the rows go through l2z_kv8_attention's launches, at most
+ * L2Z_WIDE_MAX rows a launch, so a row's bits are those of the wide step at that position.
+ * A refusal enqueues nothing and changes nothing.  L2Z_ERR_NO_DEVICE without a device; L2Z_ERR_INVALID for a null argument,
+ * n_tokens < 1, f32 or packed weights, a runstate without int8 KV rows (those go to l2z_prefill_q8), a sharded or paged
+ * runstate, a config other than the objects', a head_size that is no multiple of 4 or above 256; L2Z_ERR_STATE for a
+ * position outside [0, seq_len) or a token outside the vocabulary.
+ * l2z_kv8_prefill_attention: the attention on its own (host pointers, synchronous, one layer, one sequence): q and out
+ * [P, n_heads * head_size] (RoPE applied; row i at position pos0 + i), k8 / v8 [n_kv_heads][seq_len][head_size], ks / vs
+ * [n_kv_heads][seq_len].  form 0: by shape; 1: the row form; 3: the matrix-core form, L2Z_ERR_INVALID unless head_size is
+ * 64 or 128 and P > 32.  The matrix-core form reads whole tiles of 64 rows (never past row seq_len - 1): bytes and scales
+ * beyond a query's position may be anything, NaN patterns included, and the result does not depend on them.
+ * L2Z_ERR_STATE for positions outside [0, seq_len). */
+int l2z_prefill_kv8(const int32_t *tokens, int n_tokens, int pos0, const l2z_config *config, l2z_runstate *s,
+                    const l2z_weights *w);
+int l2z_kv8_prefill_attention(int form, float *out, const float *q, int pos0, int P, const int8_t *k8, const float *ks,
+                              const int8_t *v8, const float *vs, int n_heads, int n_kv_heads, int head_size, int seq_len);
 
 #ifdef __cplusplus
 }

@@ -144,6 +144,10 @@ def lib():
         L.l2z_runstate_init_kv8.argtypes = [cfgp, C.POINTER(vp)]
         L.l2z_runstate_read_kv8.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, i8p, fp]
         L.l2z_kv8_attention.argtypes = [fp, fp, i32p, C.c_int, i8p, fp, i8p, fp, C.c_int, C.c_int, C.c_int, C.c_int]
+    if hasattr(L, "l2z_prefill_kv8"):  # the prompt pass straight into int8 KV rows (PREVIEW)
+        i8p = C.POINTER(C.c_int8)
+        L.l2z_prefill_kv8.argtypes = [i32p, C.c_int, C.c_int, cfgp, vp, vp]
+        L.l2z_kv8_prefill_attention.argtypes = [C.c_int, fp, fp, C.c_int, C.c_int, i8p, fp, i8p, fp, C.c_int, C.c_int, C.c_int, C.c_int]
     if hasattr(L, "l2z_q8_matvec_case"):
         L.l2z_q8_matvec_case.argtypes = [C.POINTER(Q8Case)]
     if hasattr(L, "l2z_prefill_q8"):  # their batched prompt pass (PREVIEW)
@@ -423,7 +427,7 @@ class KvPool:
 class RunState:
     """src/main.zig:119 RunState, device resident.  pool: a paged runstate (l2z_runstate_init_paged), which holds no KV
     caches of its own and is taken by the wide family only.  kv8: a runstate whose KV rows are int8 with one f32 scale per
-    (layer, position, kv head) (l2z_runstate_init_kv8), taken by transformer_wide_q8 and, as dst, by runstate_fork."""
+    (layer, position, kv head) (l2z_runstate_init_kv8), taken by prefill_kv8, transformer_wide_q8 and, as dst, by runstate_fork."""
 
     def __init__(self, cfg, comm: Comm | None = None, pool: KvPool | None = None, kv8: bool = False):
         self.cfg = _cfg(cfg)
@@ -476,6 +480,12 @@ class RunState:
         weights, on the int8 matrix cores; agrees with the stepped pass up to f32 summation order."""
         t = np.ascontiguousarray(tokens, np.int32)
         _chk(lib().l2z_prefill_q8(t.ctypes.data_as(C.POINTER(C.c_int32)), t.size, pos0, C.byref(self.cfg), self.h, w.h))
+
+    def prefill_kv8(self, tokens, pos0: int, w: Weights) -> None:
+        """l2z_prefill_kv8 (a preview entry point of the test library): prefill_q8's state change on a kv8 runstate, the rows
+        written straight into the int8 arrays and the attention read from them."""
+        t = np.ascontiguousarray(tokens, np.int32)
+        _chk(lib().l2z_prefill_kv8(t.ctypes.data_as(C.POINTER(C.c_int32)), t.size, pos0, C.byref(self.cfg), self.h, w.h))
 
     def score(self, tokens, pos0: int, w: Weights, targets=None, top1: bool = True):
         """l2z_score: prefill(tokens, pos0) plus, per position, (log-prob of its target, top-1 token id) as two arrays.
@@ -1668,6 +1678,22 @@ def kv8_attention(q, pos, k8, ks, v8, vs, n_heads: int) -> np.ndarray:
     i8p = C.POINTER(C.c_int8)
     _chk(lib().l2z_kv8_attention(_fp(out), _fp(q), pos.ctypes.data_as(C.POINTER(C.c_int32)), n, k8.ctypes.data_as(i8p), _fp(ks),
                                  v8.ctypes.data_as(i8p), _fp(vs), n_heads, kvh, hs, S))
+    return out
+
+
+def kv8_prefill_attention(form: int, q, pos0: int, k8, ks, v8, vs, n_heads: int) -> np.ndarray:
+    """The prompt attention over int8 KV rows on its own (l2z_kv8_prefill_attention): q [P, n_heads * head_size], row i at
+    position pos0 + i, over ONE sequence's k8 / v8 int8 [kv heads, seq_len, head_size] and scales ks / vs [kv heads, seq_len]
+    -> out like q.  form 0: by shape, 1: the row form, 3: the matrix-core form."""
+    q, ks, vs = _f32(q), _f32(ks), _f32(vs)
+    k8, v8 = np.ascontiguousarray(k8, dtype=np.int8), np.ascontiguousarray(v8, dtype=np.int8)
+    kvh, S, hs = k8.shape
+    P = q.shape[0]
+    assert q.shape == (P, n_heads * hs) and v8.shape == k8.shape and ks.shape == vs.shape == (kvh, S)
+    out = np.empty_like(q)
+    i8p = C.POINTER(C.c_int8)
+    _chk(lib().l2z_kv8_prefill_attention(form, _fp(out), _fp(q), pos0, P, k8.ctypes.data_as(i8p), _fp(ks), v8.ctypes.data_as(i8p),
+                                         _fp(vs), n_heads, kvh, hs, S))
     return out
 
 

@@ -1,7 +1,8 @@
 // kv8.h -- the launches of the int8 KV cache (kv8_layout.h): the write side (kv8_scatter.hip: RoPE, the
 // slice quantization and the scatter of a chunk's rows; the conversion of f32 cache rows behind l2z_runstate_fork) and the
-// read side (kv8_attention.hip: decode attention of up to kWideMax one-row sequences over int8 rows).  Host side:
-// kv8_host.cpp, wide_host.cpp.
+// read side (kv8_attention.hip: decode attention of up to kWideMax one-row sequences over int8 rows;
+// kv8_prefill_attention.hip: causal attention of a prompt chunk over one sequence's int8 rows).  Host side: kv8_host.cpp,
+// wide_host.cpp, q8_host.cpp (l2z_prefill_kv8).
 #pragma once
 #include "wide_decode.h"
 
@@ -31,5 +32,35 @@ hipError_t launch_kv8_quantize_cache(const float *src, int8_t *dst, float *dst_s
 // heads, segment, row), the flash partials per (row, head, segment) in wa.part -- and wide_combine as it stands.  seq8:
 // device, slot i = row i.  Keys beyond wa.tab->pos[i] are never read, nor their scales.
 hipError_t launch_kv8_attention(const RaggedLayer &L, const WideAttn &wa, const Kv8Seq *seq8, bool *planes_written = nullptr);
+
+// ---- the prompt attention over int8 rows (kv8_prefill_attention.hip) ----
+// The ONE sequence of a prompt chunk as the two forms find it: its arrays (the matrix-core form's kernel arguments) and, on
+// the device, what the row form's launches read -- kWideMax slots that all name the sequence (slot 0 is also what
+// launch_kv8_rope_scatter reads over a one-sequence table), then a WideTable per slice of kWideMax rows, of which pos[j] =
+// pos0 + kWideMax * i + j alone is read -- and the wide step's partials.  kv8_prompt_tables fills the host image of slots
+// and tables for a chunk, in that order, kv8_prompt_table_bytes of it (with_rows false: the slots alone).
+struct Kv8Prompt {
+    Kv8Seq seq;
+    const Kv8Seq *slots;     // device: [kWideMax]
+    const WideTable *tab;    // device: [ceil(P / kWideMax)]
+    float *part;             // wide_part_floats
+    int seg_cap;             // verify_segments(seq_len)
+};
+inline size_t kv8_prompt_table_bytes(int P, bool with_rows)
+{
+    return kWideMax * sizeof(Kv8Seq) + (with_rows ? (size_t)((P + kWideMax - 1) / kWideMax) * sizeof(WideTable) : 0);
+}
+void kv8_prompt_tables(void *host, const Kv8Seq &seq, int pos0, int P, bool with_rows);
+// the matrix-core form's shape rule: head_size 64 or 128 and more than 32 rows; everything else takes the row form
+bool kv8_prefill_flash_shape(int head_size, int P);
+// Causal attention of rows 0 .. P - 1 of q [P, ldq] (RoPE applied; row i at position pos0 + i) over rows 0 .. pos0 + P - 1
+// of seq8's arrays into out [P, ldo].  form 0: by kv8_prefill_flash_shape; 1: the row form -- launch_kv8_attention over
+// slices of at most kWideMax rows, a row's arithmetic the wide step's own --; 3: the matrix-core form (hipErrorInvalidValue
+// where its shape rule does not hold).  The matrix-core form loads whole tiles of 64 rows, clamped to row seq_len - 1: rows
+// beyond a query's position are read and their bytes and scales may be anything; the result does not depend on them.
+// layer_off / kv_head_stride: in VALUES
+hipError_t launch_kv8_prefill_attention(const float *q, int ldq, const Kv8Prompt &seq8, float *out, int ldo, int pos0, int P,
+                                        int n_heads, int head_size, int kv_mul, int seq_len, size_t layer_off, size_t kv_head_stride,
+                                        hipStream_t st, int form = 0);
 
 }  // namespace l2z

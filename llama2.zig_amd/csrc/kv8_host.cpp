@@ -1,7 +1,9 @@
 // kv8_host.cpp -- host side of the int8 KV cache beside wide_host.cpp's l2z_transformer_wide_q8 and runstate.cpp's
 // l2z_runstate_init_kv8 / l2z_runstate_read_kv8 (include/llama2_hip_test.h): the rows l2z_runstate_fork
-// puts into such a runstate, and the hook that runs the attention's two launches on their own.
+// puts into such a runstate, the tables the prompt attention's row form reads (l2z_prefill_kv8, q8_host.cpp; DESIGN.md
+// 4.29), and the hooks that run the decode attention's two launches and the prompt attention on their own.
 #include <algorithm>
+#include <cstring>
 #include <vector>
 
 #include "batch_host.h"
@@ -26,6 +28,16 @@ int l2z::kv8_fork_rows(l2z_runstate *dst, const l2z_runstate *src, int n_pos)
     L2Z_HIP(hipMemcpy2DAsync(dst->ks8, S * 4, src->ks8, S * 4, (size_t)n_pos * 4, runs, hipMemcpyDeviceToDevice, st));
     L2Z_HIP(hipMemcpy2DAsync(dst->vs8, S * 4, src->vs8, S * 4, (size_t)n_pos * 4, runs, hipMemcpyDeviceToDevice, st));
     return L2Z_OK;
+}
+
+void l2z::kv8_prompt_tables(void *host, const Kv8Seq &seq, int pos0, int P, bool with_rows)
+{
+    memset(host, 0, kv8_prompt_table_bytes(P, with_rows));
+    Kv8Seq *slots = (Kv8Seq *)host;
+    std::fill(slots, slots + kWideMax, seq);
+    if (!with_rows) return;
+    WideTable *tab = (WideTable *)(slots + kWideMax);
+    for (int r = 0; r < P; r++) tab[r / kWideMax].pos[r % kWideMax] = pos0 + r;
 }
 
 namespace {
@@ -80,5 +92,47 @@ extern "C" int l2z_kv8_attention(float *out, const float *q, const int32_t *pos,
     L2Z_HIP(launch_kv8_attention(L, wa, (const Kv8Seq *)dseq.p));
     L2Z_HIP(hipDeviceSynchronize());
     L2Z_HIP(hipMemcpy(out, dout.p, (size_t)n * dim * 4, hipMemcpyDeviceToHost));
+    return L2Z_OK;
+}
+
+// PREVIEW (include/llama2_hip_test.h): launch_kv8_prefill_attention on its own -- host pointers, synchronous, one layer, one
+// sequence
+extern "C" int l2z_kv8_prefill_attention(int form, float *out, const float *q, int pos0, int P, const int8_t *k8, const float *ks,
+                                         const int8_t *v8, const float *vs, int n_heads, int n_kv_heads, int head_size, int seq_len)
+{
+    L2Z_TRY(no_device_check());
+    L2Z_CHECK(out && q && k8 && ks && v8 && vs, L2Z_ERR_INVALID, "l2z_kv8_prefill_attention: null argument");
+    L2Z_CHECK(kv8::head_size_ok(head_size) && n_heads >= 1 && n_kv_heads >= 1 && n_heads % n_kv_heads == 0 && seq_len >= 1 &&
+                  seq_len <= (1 << 20) && n_heads <= (1 << 12),
+              L2Z_ERR_INVALID, "l2z_kv8_prefill_attention: head_size %d (a multiple of 4, at most 256), %d heads on %d kv heads, seq_len %d",
+              head_size, n_heads, n_kv_heads, seq_len);
+    L2Z_CHECK(P >= 1, L2Z_ERR_INVALID, "l2z_kv8_prefill_attention: P = %d (at least 1)", P);
+    L2Z_CHECK(form == 0 || form == 1 || (form == 3 && kv8_prefill_flash_shape(head_size, P)), L2Z_ERR_INVALID,
+              "l2z_kv8_prefill_attention: form %d (0 by shape, 1 the row form, 3 the matrix-core form: head_size 64 or 128 and more "
+              "than 32 rows; head_size %d, %d rows)", form, head_size, P);
+    L2Z_TRY(check_positions("l2z_kv8_prefill_attention", "", "positions", pos0, P, seq_len));
+    L2Z_TRY(ensure_device(current_device_for(nullptr)));
+    const size_t hs = (size_t)head_size, S = (size_t)seq_len, dim = (size_t)n_heads * hs, row_s = (size_t)n_kv_heads * S;
+    const bool with_rows = form == 1 || !kv8_prefill_flash_shape(head_size, P);
+    DevBytes dq, dout, dk, dv, dks, dvs, dtab, dpart;
+    L2Z_TRY(dq.put(q, (size_t)P * dim * 4)); L2Z_TRY(dout.put(nullptr, (size_t)P * dim * 4));
+    L2Z_TRY(dk.put(k8, row_s * hs)); L2Z_TRY(dv.put(v8, row_s * hs));
+    L2Z_TRY(dks.put(ks, row_s * 4)); L2Z_TRY(dvs.put(vs, row_s * 4));
+    Kv8Prompt pr = {};
+    pr.seq = {(int8_t *)dk.p, (int8_t *)dv.p, (float *)dks.p, (float *)dvs.p};
+    std::vector<uint8_t> tab(kv8_prompt_table_bytes(P, with_rows));
+    kv8_prompt_tables(tab.data(), pr.seq, pos0, P, with_rows);
+    L2Z_TRY(dtab.put(tab.data(), tab.size()));
+    pr.slots = (const Kv8Seq *)dtab.p;
+    pr.tab = (const WideTable *)(pr.slots + kWideMax);
+    pr.seg_cap = verify_segments(seq_len);
+    if (with_rows) {
+        L2Z_TRY(dpart.put(nullptr, wide_part_floats(n_heads, pr.seg_cap, head_size) * 4));
+        pr.part = (float *)dpart.p;
+    }
+    L2Z_HIP(launch_kv8_prefill_attention((const float *)dq.p, (int)dim, pr, (float *)dout.p, (int)dim, pos0, P, n_heads, head_size,
+                                         n_heads / n_kv_heads, seq_len, 0, S * hs, nullptr, form));
+    L2Z_HIP(hipDeviceSynchronize());
+    L2Z_HIP(hipMemcpy(out, dout.p, (size_t)P * dim * 4, hipMemcpyDeviceToHost));
     return L2Z_OK;
 }

@@ -5,15 +5,19 @@
 // after the rmsnorm where the decode's launch has one) and, behind the attention, three GEMM launches on the int8 matrix
 // cores (q8_gemm.hip: Wo and W2 with the residual, W1 | W3 with SwiGLU).  How q | k | v, the cache rows and the attention
 // output come about is the caller's: the prompt pass runs three more GEMMs into scratch, the f32 pass's RoPE + cache
-// scatter over a one-sequence table and its prompt attention, and sends the last row through the decode's own classifier
-// launch, so the runstate is left as after a decode step; the step runs q | k | v as one launch (q8_batch.hip), its
-// caller's attention and the classifier through the table.  Also the two hooks that run the row launch and the GEMM on
-// their own.
+// scatter over a one-sequence table and its prompt attention -- on a runstate with int8 KV rows (l2z_prefill_kv8, DESIGN.md
+// 4.29) the format's scatter and the prompt attention over the int8 arrays (kv8.h) in their place -- and sends the last
+// row through the decode's own classifier launch, so the runstate is left as after a decode step; the step runs
+// q | k | v as one launch (q8_batch.hip), its caller's attention and the classifier through the table.  Also the two hooks
+// that run the row launch and the GEMM on their own.
 #include <algorithm>
 #include <cstring>
+#include <vector>
 
 #include "batch_host.h"
 #include "kind_rows.h"
+#include "kv8.h"
+#include "kv8_layout.h"
 #include "wide_decode.h"
 
 using namespace l2z;
@@ -85,12 +89,16 @@ int q8_layers(const Q8Rows &r, const l2z_config &c, const l2z_weights *w, FnRef<
 
 // The pass's scratch, one allocation owned by the runstate (l2z_runstate::q8pf, freed with it), carved for chunks of up to
 // `cap` rows: the residual rows, q | k | v, the attention output and the gated rows in f32; the quantized rows and their
-// scales at the widest K; the tokens and the one-sequence table of the scatter
+// scales at the widest K; the tokens and the one-sequence table of the scatter.  Behind them, in a runstate with int8 KV
+// rows alone (l2z_prefill_kv8; the f32 runstate's carving is what it was): the slots and the slices' tables of the prompt
+// attention's row form (kv8.h Kv8Prompt) and the wide step's partials
 struct Q8Pf {
     float *x, *q, *k, *v, *att, *h, *xs;
     int8_t *xq;
     int *tokens, *row_seq, *row_pos;
     RaggedSeq *seq;
+    void *kv8_tab;
+    float *kv8_part;
     size_t bytes;
 };
 
@@ -118,6 +126,10 @@ Q8Pf q8pf_carve(const l2z_runstate *s, int gs, size_t cap)
     b.row_seq = (int *)take(cap * 4);
     b.row_pos = (int *)take(cap * 4);
     b.seq = (RaggedSeq *)take(sizeof(RaggedSeq));
+    if (s->is_kv8()) {
+        b.kv8_tab = take(kv8_prompt_table_bytes((int)cap, true));
+        b.kv8_part = (float *)take(wide_part_floats(c.n_heads, verify_segments(c.seq_len), s->sh.hs) * 4);
+    }
     b.bytes = off;
     return b;
 }
@@ -136,13 +148,20 @@ int q8pf_alloc(l2z_runstate *s, int gs, int need)
     return L2Z_OK;
 }
 
+// A chunk's launch between its q | k | v products and its attention -- q [P, dim] rotated in place, the chunk's k / v rows
+// into the sequence's cache through the one-sequence table rg -- and its causal attention into b.att, as the pass's owner
+// brings them: the f32 caches' (l2z_prefill_q8) or the int8 rows' (l2z_prefill_kv8), the way wide_step_q8 takes rg.scatter /
+// rg.attention
+using Q8Scatter = FnRef<hipError_t(const RaggedChunk &rg, int P, size_t layer_off)>;
+using Q8Attention = FnRef<hipError_t(int pos0, int P, size_t layer_off)>;
+
 // one chunk: rows pos0 .. pos0 + P - 1 through every layer; the residual rows are left in b.x
-int q8_chunk(l2z_runstate *s, const l2z_weights *w, const Q8Pf &b, const int32_t *tokens, int P, int pos0)
+int q8_chunk(l2z_runstate *s, const l2z_weights *w, const Q8Pf &b, const int32_t *tokens, int P, int pos0, Q8Scatter scatter,
+             Q8Attention attention)
 {
     const l2z_config &c = s->cfg;
     hipStream_t st = s->stream;
-    const int dim = c.dim, kvd = s->sh.kvd_loc, hs = s->sh.hs;
-    const size_t kvh_stride = (size_t)c.seq_len * hs;
+    const int dim = c.dim, kvd = s->sh.kvd_loc;
     L2Z_HIP(hipMemcpyAsync(b.tokens, tokens, (size_t)P * 4, hipMemcpyHostToDevice, st));
     L2Z_HIP(launch_q8_embed_rows(w->q8_emb(), b.tokens, dim, P, b.x, pos0, b.row_seq, b.row_pos, st));
     RaggedChunk rg = {};
@@ -153,9 +172,8 @@ int q8_chunk(l2z_runstate *s, const l2z_weights *w, const Q8Pf &b, const int32_t
         L2Z_TRY(q8_product(r, w->q_wq, l, dim, dim, b.q, dim, EPI_STORE));        // :308-320
         L2Z_TRY(q8_product(r, w->q_wk, l, kvd, dim, b.k, kvd, EPI_STORE));
         L2Z_TRY(q8_product(r, w->q_wv, l, kvd, dim, b.v, kvd, EPI_STORE));
-        L2Z_HIP(launch_ragged_rope_scatter(b.q, dim, rg, P, dim, kvd, hs, s->rope, layer_off, kvh_stride, st));   // :336-358
-        L2Z_HIP(launch_prefill_attention(b.q, dim, s->key_cache + layer_off, s->value_cache + layer_off, b.att, dim, pos0, P,
-                                         c.n_heads, hs, hs, kvh_stride, c.n_heads / c.n_kv_heads, c.seq_len, st, c.n_heads));   // :361-389
+        L2Z_HIP(scatter(rg, P, layer_off));        // :336-358
+        L2Z_HIP(attention(pos0, P, layer_off));    // :361-389
         return L2Z_OK;
     });
 }
@@ -175,23 +193,25 @@ int q8_classifier(l2z_runstate *s, const l2z_weights *w)
     return L2Z_OK;
 }
 
-}  // namespace
-
-extern "C" int l2z_prefill_q8(const int32_t *tokens, int n_tokens, int pos0, const l2z_config *config, l2z_runstate *s,
-                              const l2z_weights *w)
+// l2z_prefill_q8 (kv8 false: an f32 runstate) and l2z_prefill_kv8 (true: one with int8 KV rows): one front,
+// one chunk loop; they differ in the kind of runstate they take and in the scatter and the attention they hand q8_chunk
+int prefill_q8_pass(const char *fn, bool kv8, const int32_t *tokens, int n_tokens, int pos0, const l2z_config *config, l2z_runstate *s,
+                    const l2z_weights *w)
 {
     // ---- checks: a refusal enqueues nothing and changes no state ----
     L2Z_TRY(no_device_check());
-    L2Z_CHECK(tokens != nullptr && config != nullptr && s != nullptr && w != nullptr, L2Z_ERR_INVALID, "l2z_prefill_q8: null argument");
-    L2Z_CHECK(n_tokens >= 1, L2Z_ERR_INVALID, "l2z_prefill_q8: n_tokens = %d (at least 1)", n_tokens);
+    L2Z_CHECK(tokens != nullptr && config != nullptr && s != nullptr && w != nullptr, L2Z_ERR_INVALID, "%s: null argument", fn);
+    L2Z_CHECK(n_tokens >= 1, L2Z_ERR_INVALID, "%s: n_tokens = %d (at least 1)", fn, n_tokens);
     L2Z_CHECK(w->is_q8(), L2Z_ERR_INVALID,
-              "l2z_prefill_q8: takes int8 group-quantized weights (l2z_weights_init_q8); f32 and packed weights go to l2z_prefill");
-    L2Z_TRY(check_pair(config, s, w, false, true));   // (a sharded or paged runstate, another config)
+              "%s: takes int8 group-quantized weights (l2z_weights_init_q8); f32 and packed weights go to l2z_prefill", fn);
+    L2Z_CHECK(!kv8 || s->is_kv8(), L2Z_ERR_INVALID,
+              "l2z_prefill_kv8: takes a runstate with int8 KV rows (l2z_runstate_init_kv8); every other one goes to l2z_prefill_q8");
+    L2Z_TRY(check_pair(config, s, w, false, true, kv8));   // (a sharded or paged runstate, another config; kv8 false: int8 KV rows)
     const int hs = s->sh.hs;
     L2Z_CHECK(hs % 4 == 0 && hs <= 256 && s->sh.kvd_loc % 4 == 0, L2Z_ERR_INVALID,
-              "l2z_prefill_q8: needs a head_size that is a multiple of 4, at most 256");
-    L2Z_TRY(check_positions("l2z_prefill_q8", "", "positions", pos0, n_tokens, config->seq_len));
-    L2Z_TRY(check_tokens("l2z_prefill_q8", "", tokens, n_tokens, config->vocab_size));
+              "%s: needs a head_size that is a multiple of 4, at most 256", fn);
+    L2Z_TRY(check_positions(fn, "", "positions", pos0, n_tokens, config->seq_len));
+    L2Z_TRY(check_tokens(fn, "", tokens, n_tokens, config->vocab_size));
     L2Z_HIP(hipSetDevice(s->device));
     int longest = 0;   // the plan's longest chunk sizes the scratch before anything is enqueued
     for (int done = 0; done < n_tokens;) {
@@ -203,13 +223,48 @@ extern "C" int l2z_prefill_q8(const int32_t *tokens, int n_tokens, int pos0, con
     const Q8Pf b = q8pf_carve(s, w->q8_gs, (size_t)s->q8pf_cap);
 
     // ---- the pass ----
+    const l2z_config &c = s->cfg;
     hipStream_t st = s->stream;
+    const int dim = c.dim, kvd = s->sh.kvd_loc, kv_mul = c.n_heads / c.n_kv_heads;
+    const size_t kvh_stride = (size_t)c.seq_len * hs;
     RaggedSeq seq = {};
     seq.kc = s->key_cache; seq.vc = s->value_cache;
     L2Z_HIP(hipMemcpyAsync(b.seq, &seq, sizeof seq, hipMemcpyHostToDevice, st));
+    // the f32 caches: the f32 pass's RoPE + cache scatter and its prompt attention
+    const auto scatter32 = [&](const RaggedChunk &rg, int P, size_t layer_off) {
+        return launch_ragged_rope_scatter(b.q, dim, rg, P, dim, kvd, hs, s->rope, layer_off, kvh_stride, st);
+    };
+    const auto attention32 = [&](int p0, int P, size_t layer_off) {
+        return launch_prefill_attention(b.q, dim, s->key_cache + layer_off, s->value_cache + layer_off, b.att, dim, p0, P, c.n_heads, hs,
+                                        hs, kvh_stride, kv_mul, c.seq_len, st, c.n_heads);
+    };
+    // int8 rows: the format's scatter FIRST, then the attention over the int8 arrays alone, the chunk's own rows included
+    Kv8Prompt pr = {};
+    pr.seq = {s->k8, s->v8, s->ks8, s->vs8};
+    if (kv8) {
+        pr.slots = (const Kv8Seq *)b.kv8_tab;
+        pr.tab = (const WideTable *)(pr.slots + kWideMax);
+        pr.part = b.kv8_part;
+        pr.seg_cap = verify_segments(c.seq_len);
+    }
+    const auto scatter8 = [&](const RaggedChunk &rg, int P, size_t layer_off) {
+        return launch_kv8_rope_scatter(b.q, dim, rg, pr.slots, P, dim, kvd, hs, c.seq_len, s->rope, layer_off, kvh_stride, st);
+    };
+    const auto attention8 = [&](int p0, int P, size_t layer_off) {
+        return launch_kv8_prefill_attention(b.q, dim, pr, b.att, dim, p0, P, c.n_heads, hs, kv_mul, c.seq_len, layer_off, kvh_stride, st);
+    };
+    std::vector<uint8_t> tab;   // the chunk's slots and row tables on the host, alive until the chunk's synchronize
     for (int done = 0; done < n_tokens;) {
         const int P = prefill_next_chunk_of(*config, n_tokens - done);
-        L2Z_TRY(q8_chunk(s, w, b, tokens + done, P, pos0 + done));
+        if (kv8) {   // one copy before the layer loop
+            const bool with_rows = !kv8_prefill_flash_shape(hs, P);
+            tab.resize(kv8_prompt_table_bytes(P, with_rows));
+            kv8_prompt_tables(tab.data(), pr.seq, pos0 + done, P, with_rows);
+            L2Z_HIP(hipMemcpyAsync(b.kv8_tab, tab.data(), tab.size(), hipMemcpyHostToDevice, st));
+            L2Z_TRY(q8_chunk(s, w, b, tokens + done, P, pos0 + done, scatter8, attention8));
+        } else {
+            L2Z_TRY(q8_chunk(s, w, b, tokens + done, P, pos0 + done, scatter32, attention32));
+        }
         if (done + P == n_tokens)   // the last position's residual row is RunState.x
             L2Z_HIP(hipMemcpyAsync(s->x, b.x + (size_t)(P - 1) * config->dim, (size_t)config->dim * 4, hipMemcpyDeviceToDevice, st));
         L2Z_HIP(hipStreamSynchronize(st));   // the caller's tokens may now be reused
@@ -223,6 +278,21 @@ extern "C" int l2z_prefill_q8(const int32_t *tokens, int n_tokens, int pos0, con
     L2Z_HIP(hipStreamSynchronize(st));
     s->host_pos = pos0 + n_tokens;
     return L2Z_OK;
+}
+
+}  // namespace
+
+extern "C" int l2z_prefill_q8(const int32_t *tokens, int n_tokens, int pos0, const l2z_config *config, l2z_runstate *s,
+                              const l2z_weights *w)
+{
+    return prefill_q8_pass("l2z_prefill_q8", false, tokens, n_tokens, pos0, config, s, w);
+}
+
+// PREVIEW (include/llama2_hip_test.h): l2z_prefill_q8's contract on a runstate with int8 KV rows
+extern "C" int l2z_prefill_kv8(const int32_t *tokens, int n_tokens, int pos0, const l2z_config *config, l2z_runstate *s,
+                               const l2z_weights *w)
+{
+    return prefill_q8_pass("l2z_prefill_kv8", true, tokens, n_tokens, pos0, config, s, w);
 }
 
 // The step on int8 group-quantized weights.  Per layer q | k | v in one launch (RoPE and the cache rows in
