@@ -2,10 +2,13 @@
 tests/test_kv8_prefill_reference_cpu.py): a shape with head_size 64 and GQA -- the smallest that takes the matrix-core
 attention -- and its float64 reference with int8 rows, teacher-forced over N_REF tokens.
 
-SEED is the first of seeds 0 .. 99 for which the reference's own f32 and f64 modes have no position over the parity bar
-(a flipped byte stays in the cache and moves every later position; seed 0 has 49 positions over it, up to 2.0e-2 of the
-scale, seed 1 none: largest deviation between the modes 4.0e-7 of the scale, measured on the CPU);
-tests/test_kv8_prefill_reference_cpu.py asserts it.
+SEED is the first of seeds 0 .. 39 for which the reference's own f32 and f64 modes have no position over the parity bar
+(a flipped byte stays in the cache and moves every later position) UNDER EVERY KERNEL SET numpy may dispatch to: its f32 exp,
+cos and sin differ in the last bit between the AVX-512 kernels, the AVX2 ones and the baseline, and that bit decides which
+side of a rounding boundary a byte lands on.  Positions over the bar, with AVX-512 / without (measured on the CPU, the second
+by NPY_DISABLE_CPU_FEATURES): seed 0 49 / 77, seed 1 none / 50 (up to 1.8e-2 of the scale), seed 2 none / none, also with AVX2
+and FMA3, and with AVX, disabled: largest deviation between the modes 3.9e-7 / 3.3e-7 of the scale;
+tests/test_kv8_prefill_reference_cpu.py asserts it on the kernels of the machine it runs on.
 """
 import functools
 
@@ -15,7 +18,7 @@ import kv8_cases
 import ref_q8
 
 SHAPE = (128, 384, 2, 2, 1, 512, 160, 64)   # dim, hidden_dim, layers, heads, kv heads, vocab, seq_len, group size
-SEED = 1
+SEED = 2
 N_REF = 101
 
 

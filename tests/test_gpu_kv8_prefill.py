@@ -58,9 +58,17 @@ def attention64(q, pos0, k8, ks, v8, vs, H):
     return out
 
 
+SPANS = [(0, 33), (0, 64), (0, 65), (37, 100), (64, 33), (130, 70)]
+FLASH_SHAPES, ROW_SHAPES = [(3, 2, 1, 64), (3, 2, 2, 128), (3, 4, 1, 128)], [(1, 6, 6, 48), (1, 2, 1, 16)]
+# the row form in two slices of its 128-row launches, the second one's rows starting inside a segment of 64 keys
+ROW_SPANS = SPANS + [(0, 150), (20, 140)]
+# the matrix-core form in four query tiles, the last key tile clamped at S_KERNEL
+FLASH_SPANS = SPANS + [(0, 200)]
+KERNEL_CASES = [shape + span for shape in FLASH_SHAPES for span in FLASH_SPANS] + [shape + span for shape in ROW_SHAPES for span in ROW_SPANS]
+
+
 @pytest.mark.parametrize("fill", ["random", "adversarial"])
-@pytest.mark.parametrize("pos0,P", [(0, 33), (0, 64), (0, 65), (37, 100), (64, 33), (130, 70)])
-@pytest.mark.parametrize("form,H,KVH,hs", [(3, 2, 1, 64), (3, 2, 2, 128), (3, 4, 1, 128), (1, 6, 6, 48), (1, 2, 1, 16)])
+@pytest.mark.parametrize("form,H,KVH,hs,pos0,P", KERNEL_CASES)
 def test_the_attention_meets_the_parity_bar_against_float64(gpu, form, H, KVH, hs, pos0, P, fill):
     q, k8, ks, v8, vs = kernel_inputs(H, KVH, hs, pos0, P, fill)
     want = attention64(q, pos0, k8, ks, v8, vs, H)
