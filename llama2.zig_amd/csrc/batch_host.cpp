@@ -4,7 +4,7 @@
 // needs around the step: the on-device sampler l2z_sample_batch (sample_batch.hip) and the prompt copy
 // l2z_runstate_fork.  The step itself (batch_step) takes a layer's attention from its caller: the verify family
 // (verify_host.cpp) runs it with attention forms of its own; on int8 group-quantized weights it is q8_host.cpp's.  batch_host.h: what the host files share -- its argument
-// rules, stream hand-overs and allocation helper are defined here.
+// rules are defined here.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -17,24 +17,7 @@ static_assert(l2z::kBatchMax == L2Z_BATCH_MAX, "include/llama2_hip.h L2Z_BATCH_M
 
 namespace l2z {
 
-void batch_free(l2z_runstate *s)
-{
-    BatchScratch *b = s->bt;
-    if (b == nullptr) return;
-    void *ptrs[] = {b->x, b->xn, b->q, b->att, b->h1, b->scores, b->d_tab, b->d_tokens_out, b->smp,
-                    b->v_logits, b->v_part_o, b->v_part_ml, b->d_vout, b->q8_xq, b->q8_xs};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    if (b->h_tab) (void)hipHostFree(b->h_tab);
-    if (b->h_tokens_out) (void)hipHostFree(b->h_tokens_out);
-    if (b->h_vout) (void)hipHostFree(b->h_vout);
-    for (hipEvent_t e : b->ev_in)
-        if (e) (void)hipEventDestroy(e);
-    if (b->ev_done) (void)hipEventDestroy(b->ev_done);
-    if (b->ev_upload) (void)hipEventDestroy(b->ev_upload);
-    delete b;
-    s->bt = nullptr;
-}
+void BatchScratchDelete::operator()(BatchScratch *b) const { delete b; }
 
 namespace {
 
@@ -55,69 +38,49 @@ int batch_alloc(l2z_runstate *s)
 {
     if (s->bt != nullptr) return L2Z_OK;
     const l2z_config &c = s->cfg;
-    BatchScratch *b = new BatchScratch();
-    s->bt = b;  // freed with the runstate whatever happens below
+    // built here, the runstate's only once all of it stands: a failure below frees what there is with `made`
+    std::unique_ptr<BatchScratch, BatchScratchDelete> made(new BatchScratch());
+    BatchScratch *b = made.get();
     b->ld_xn = bt_ld(c.dim); b->ld_att = bt_ld(c.dim); b->ld_h1 = bt_ld(c.hidden_dim);
     const size_t R = kBatchMax;
-    L2Z_TRY(alloc_all("batched step scratch",
-                      {{(void **)&b->x, R * c.dim * 4}, {(void **)&b->xn, R * b->ld_xn * 4}, {(void **)&b->q, R * c.dim * 4},
-                       {(void **)&b->att, R * b->ld_att * 4}, {(void **)&b->h1, R * b->ld_h1 * 4},
-                       {(void **)&b->scores, R * (size_t)c.n_heads * c.seq_len * 4},
-                       {(void **)&b->d_tab, sizeof(BatchTable) + kTabExtra}, {(void **)&b->d_tokens_out, R * 4}}));
-    L2Z_HIP(hipHostMalloc((void **)&b->h_tab, sizeof(BatchTable) + kTabExtra, hipHostMallocDefault));
+    int cap = 0;
+    L2Z_TRY(grow("batched step scratch", &cap, 1, 1, nullptr, 0, [] { return L2Z_OK; },
+                 {{b->x, R * c.dim * 4}, {b->xn, R * b->ld_xn * 4}, {b->q, R * c.dim * 4}, {b->att, R * b->ld_att * 4},
+                  {b->h1, R * b->ld_h1 * 4}, {b->scores, R * (size_t)c.n_heads * c.seq_len * 4},
+                  {b->d_tab, sizeof(BatchTable) + kTabExtra}, {b->d_tokens_out, R * 4},
+                  {b->h_tab, sizeof(BatchTable) + kTabExtra}, {b->h_tokens_out, R * 4}}));
     b->d_behind = b->d_tab + 1;
     b->h_behind = b->h_tab + 1;
-    L2Z_HIP(hipHostMalloc((void **)&b->h_tokens_out, R * 4, hipHostMallocDefault));
-    for (hipEvent_t &e : b->ev_in) L2Z_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    L2Z_HIP(hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
-    L2Z_HIP(hipEventCreateWithFlags(&b->ev_upload, hipEventDisableTiming));
+    for (OwnedEvent &e : b->ev_in) L2Z_HIP(hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
+    L2Z_HIP(hipEventCreateWithFlags(b->ev_done.put(), hipEventDisableTiming));
+    L2Z_HIP(hipEventCreateWithFlags(b->ev_upload.put(), hipEventDisableTiming));
     // the pad columns are multiplied against whatever follows a W row: zeros, once
     L2Z_HIP(hipMemset(b->xn, 0, R * b->ld_xn * 4));
     L2Z_HIP(hipMemset(b->att, 0, R * b->ld_att * 4));
     L2Z_HIP(hipMemset(b->h1, 0, R * b->ld_h1 * 4));
+    s->bt = std::move(made);
     return L2Z_OK;
 }
 
 int sample_alloc(l2z_runstate *s)
 {
-    BatchScratch *b = s->bt;
-    if (b->smp != nullptr) return L2Z_OK;
+    BatchScratch *b = s->bt.get();
     const size_t stride = sample_scratch_floats(s->cfg.vocab_size);
-    L2Z_TRY(alloc_all("l2z_sample_batch scratch", {{(void **)&b->smp, kBatchMax * stride * 4}}));
+    L2Z_TRY(b->smp.make(kBatchMax * stride * 4, "l2z_sample_batch scratch"));
     b->smp_stride = stride;
     return L2Z_OK;
 }
 
 int verify_alloc(l2z_runstate *s)
 {
-    BatchScratch *b = s->bt;
-    if (b->v_logits != nullptr && b->v_part_o != nullptr && b->v_part_ml != nullptr && b->d_vout != nullptr &&
-        b->h_vout != nullptr)
-        return L2Z_OK;
+    BatchScratch *b = s->bt.get();
     const l2z_config &c = s->cfg;
     const size_t R = kBatchMax, segs = (size_t)verify_segments(c.seq_len), hs = (size_t)c.dim / c.n_heads;
-    // (a call that failed part of the way left some of them: those stay)
-    L2Z_TRY(alloc_all("l2z_verify scratch", {{(void **)&b->v_logits, R * (size_t)c.vocab_size * 4},
-                                             {(void **)&b->v_part_o, R * c.n_heads * segs * hs * 4},
-                                             {(void **)&b->v_part_ml, R * c.n_heads * segs * 2 * 4},
-                                             {(void **)&b->d_vout, 3 * R * 4}}));
-    if (b->h_vout == nullptr) L2Z_HIP(hipHostMalloc((void **)&b->h_vout, 3 * R * 4, hipHostMallocDefault));
+    L2Z_TRY(grow("l2z_verify scratch", &b->v_cap, 1, 1, nullptr, 0, [] { return L2Z_OK; },
+                 {{b->v_logits, R * (size_t)c.vocab_size * 4}, {b->v_part_o, R * c.n_heads * segs * hs * 4},
+                  {b->v_part_ml, R * c.n_heads * segs * 2 * 4}, {b->d_vout, 3 * R * 4}, {b->h_vout, 3 * R * 4}}));
     b->v_seg_cap = (int)segs;
     return L2Z_OK;
-}
-
-int q8_batch_alloc(l2z_runstate *s, int gs)
-{
-    BatchScratch *b = s->bt;
-    if (b->q8_xq != nullptr && b->q8_xs != nullptr && b->q8_gs == gs) return L2Z_OK;
-    if (b->q8_gs != gs && (b->q8_xq != nullptr || b->q8_xs != nullptr)) {   // another group size: other scale rows
-        L2Z_HIP(hipStreamSynchronize(s->stream));
-        if (b->q8_xq) { (void)hipFree(b->q8_xq); b->q8_xq = nullptr; }
-        if (b->q8_xs) { (void)hipFree(b->q8_xs); b->q8_xs = nullptr; }
-    }
-    b->q8_gs = gs;
-    const size_t R = kBatchMax, widest = (size_t)std::max(s->cfg.dim, s->cfg.hidden_dim);
-    return alloc_all("batched q8 step scratch", {{(void **)&b->q8_xq, R * widest}, {(void **)&b->q8_xs, R * (widest / (size_t)gs) * 4}});
 }
 
 int check_q8_step(const char *fn, const char *f32_entry, const l2z_runstate *s0, const l2z_weights *w)
@@ -128,20 +91,6 @@ int check_q8_step(const char *fn, const char *f32_entry, const l2z_runstate *s0,
               "%s: needs a head_size that is a multiple of 4, at most 256", fn);
     L2Z_CHECK(s0->cfg.vocab_size % 4 == 0, L2Z_ERR_INVALID, "%s: needs a vocab_size that is a multiple of 4 (it is %d)", fn,
               s0->cfg.vocab_size);
-    return L2Z_OK;
-}
-
-int alloc_all(const char *what, std::initializer_list<DeviceBuf> want)
-{
-    for (const DeviceBuf &w : want) {
-        if (*w.p != nullptr || w.bytes == 0) continue;
-        const hipError_t e = hipMalloc(w.p, w.bytes);
-        if (e != hipSuccess) {
-            *w.p = nullptr;
-            set_error("%s allocation (%zu bytes) failed: %s", what, w.bytes, hipGetErrorString(e));
-            return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
-        }
-    }
     return L2Z_OK;
 }
 
@@ -370,8 +319,8 @@ int transformer_batch_call(const char *fn, bool q8, int n, const int32_t *tokens
     }
     L2Z_HIP(hipSetDevice(states[0]->device));
     L2Z_TRY(batch_alloc(states[0]));
-    if (q8) L2Z_TRY(q8_batch_alloc(states[0], w->q8_gs));
-    BatchScratch *b = states[0]->bt;
+    BatchScratch *b = states[0]->bt.get();
+    if (q8) L2Z_TRY(q8_rows_alloc("batched q8 step scratch", states[0], b, kBatchMax, w->q8_gs));
     BatchTable t = {};
     for (int i = 0; i < n; i++) {
         t.tokens[i] = tokens[i];
@@ -381,7 +330,8 @@ int transformer_batch_call(const char *fn, bool q8, int n, const int32_t *tokens
         t.logits[i] = states[i]->logits;
     }
     hipStream_t st = states[0]->stream;
-    L2Z_TRY(join_streams(b, n, states));
+    StreamScope pass(b, n, states);
+    L2Z_TRY(pass.joined());
     L2Z_TRY(upload_table(b, t, st));
     BatchAttnArgs a = attention_args<BatchAttnArgs>(*config, b);  // one block per (head, row), each row on its own caches
     a.scores = b->scores; a.tab = b->d_tab; a.seq_len = config->seq_len;
@@ -390,7 +340,7 @@ int transformer_batch_call(const char *fn, bool q8, int n, const int32_t *tokens
         L2Z_HIP(launch_batch_attention(a, n, st));
         return L2Z_OK;
     }));
-    L2Z_TRY(release_streams(b, n, states));
+    L2Z_TRY(pass.release());
     for (int i = 0; i < n; i++) logits_whole(states[i], pos[i] + 1);
     return L2Z_OK;
 }
@@ -417,14 +367,16 @@ extern "C" int l2z_argmax_batch(int n, l2z_runstate *const *states, int32_t *out
     L2Z_TRY(check_states("l2z_argmax_batch", n, states, nullptr));
     L2Z_HIP(hipSetDevice(states[0]->device));
     L2Z_TRY(batch_alloc(states[0]));
-    BatchScratch *b = states[0]->bt;
+    BatchScratch *b = states[0]->bt.get();
     BatchTable t = {};
     for (int i = 0; i < n; i++) t.logits[i] = states[i]->logits;
     hipStream_t st = states[0]->stream;
-    L2Z_TRY(join_streams(b, n, states));
+    StreamScope pass(b, n, states);
+    L2Z_TRY(pass.joined());
     L2Z_TRY(upload_table(b, t, st));
     L2Z_HIP(launch_batch_argmax(b->d_tab, states[0]->cfg.vocab_size, b->d_tokens_out, n, st));
     L2Z_HIP(hipMemcpyAsync(b->h_tokens_out, b->d_tokens_out, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    L2Z_TRY(pass.release());
     L2Z_HIP(hipStreamSynchronize(st));
     memcpy(out_tokens, b->h_tokens_out, (size_t)n * 4);
     return L2Z_OK;
@@ -433,8 +385,10 @@ extern "C" int l2z_argmax_batch(int n, l2z_runstate *const *states, int32_t *out
 namespace l2z {
 namespace {
 
-// l2z_sample_batch's checks, table and launch on states[0]'s stream (no copy back)
-int sample_enqueue(int n, l2z_runstate *const *states, const float *temperature, const float *top_p, const float *coins)
+// l2z_sample_batch's checks, table and launch on states[0]'s stream (no copy back); pass: the scope of the launch, made here
+// once the scratch with its events stands, released by the caller behind whatever it adds
+int sample_enqueue(int n, l2z_runstate *const *states, const float *temperature, const float *top_p, const float *coins,
+                   std::optional<StreamScope> &pass)
 {
     L2Z_TRY(no_device_check());
     L2Z_CHECK(temperature != nullptr && top_p != nullptr && coins != nullptr, L2Z_ERR_INVALID,
@@ -447,7 +401,7 @@ int sample_enqueue(int n, l2z_runstate *const *states, const float *temperature,
     L2Z_HIP(hipSetDevice(states[0]->device));
     L2Z_TRY(batch_alloc(states[0]));
     L2Z_TRY(sample_alloc(states[0]));
-    BatchScratch *b = states[0]->bt;
+    BatchScratch *b = states[0]->bt.get();
     BatchTable t = {};
     for (int i = 0; i < n; i++) {
         t.logits[i] = states[i]->logits;
@@ -456,7 +410,8 @@ int sample_enqueue(int n, l2z_runstate *const *states, const float *temperature,
         t.coin[i] = coins[i];
     }
     hipStream_t st = states[0]->stream;
-    L2Z_TRY(join_streams(b, n, states));
+    pass.emplace(b, n, states);
+    L2Z_TRY(pass->joined());
     L2Z_TRY(upload_table(b, t, st));
     L2Z_HIP(sample_rows(b, states[0]->cfg.vocab_size, b->d_tokens_out, n, st));
     return L2Z_OK;
@@ -469,11 +424,12 @@ extern "C" int l2z_sample_batch(int n, l2z_runstate *const *states, const float 
                                 const float *coins, int32_t *out_tokens)
 {
     L2Z_CHECK(out_tokens != nullptr, L2Z_ERR_INVALID, "l2z_sample_batch: null argument");
-    L2Z_TRY(sample_enqueue(n, states, temperature, top_p, coins));
-    BatchScratch *b = states[0]->bt;
+    std::optional<StreamScope> pass;
+    L2Z_TRY(sample_enqueue(n, states, temperature, top_p, coins, pass));
+    BatchScratch *b = states[0]->bt.get();
     hipStream_t st = states[0]->stream;
     L2Z_HIP(hipMemcpyAsync(b->h_tokens_out, b->d_tokens_out, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    L2Z_TRY(release_streams(b, n, states));
+    L2Z_TRY(pass->release());
     L2Z_HIP(hipStreamSynchronize(st));
     memcpy(out_tokens, b->h_tokens_out, (size_t)n * 4);
     return L2Z_OK;
@@ -579,9 +535,10 @@ extern "C" int l2z_sample_time(int n, l2z_runstate *const *states, const float *
                                const float *coins, int iters, double *out_ms)
 {
     L2Z_CHECK(iters >= 1 && out_ms != nullptr, L2Z_ERR_INVALID, "l2z_sample_time: bad arguments");
-    L2Z_TRY(sample_enqueue(n, states, temperature, top_p, coins));  // validates, allocates, warms up
+    std::optional<StreamScope> pass;   // (released behind the timed launches, when it ends)
+    L2Z_TRY(sample_enqueue(n, states, temperature, top_p, coins, pass));  // validates, allocates, warms up
     hipStream_t st = states[0]->stream;
-    BatchScratch *b = states[0]->bt;
+    BatchScratch *b = states[0]->bt.get();
     return timed_loop(st, iters, out_ms, [&]() -> int {
         return sample_rows(b, states[0]->cfg.vocab_size, b->d_tokens_out, n, st) == hipSuccess ? L2Z_OK : L2Z_ERR_HIP;
     });

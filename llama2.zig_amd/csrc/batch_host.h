@@ -4,7 +4,7 @@
 // front of a call of the ragged family made of them (check_ragged_call), the stream hand-overs, the scratch allocation and
 // the batched step itself.
 #pragma once
-#include <initializer_list>
+#include <optional>
 
 #include "batch_decode.h"
 #include "l2z_state.h"
@@ -15,51 +15,62 @@ namespace l2z {
 // freed with it): the activation rows of kBatchMax sequences, the attention scores, the device table and its pinned
 // host twin, and the events that order the pass against the runstates' own streams.
 struct BatchScratch {
-    float *x = nullptr, *xn = nullptr, *q = nullptr, *att = nullptr, *h1 = nullptr, *scores = nullptr;
+    Owned<float> x, xn, q, att, h1, scores;
     int ld_xn = 0, ld_att = 0, ld_h1 = 0;
-    BatchTable *d_tab = nullptr, *h_tab = nullptr;
+    Owned<BatchTable> d_tab;
+    Pinned<BatchTable> h_tab;
     // what sits behind the table in the same allocations: l2z_verify_batch's VerifyGroupTable or l2z_verify_tree's
     // VerifyTreeTable
     void *d_behind = nullptr, *h_behind = nullptr;
-    int *d_tokens_out = nullptr, *h_tokens_out = nullptr;
-    hipEvent_t ev_in[kBatchMax] = {};
-    hipEvent_t ev_done = nullptr;
-    hipEvent_t ev_upload = nullptr;  // the last table copy: the pinned table may be rewritten once it has completed
-    float *smp = nullptr;            // sample_alloc: kBatchMax rows of sample_scratch_floats(vocab)
+    Owned<int> d_tokens_out;
+    Pinned<int> h_tokens_out;
+    OwnedEvent ev_in[kBatchMax];
+    OwnedEvent ev_done;
+    OwnedEvent ev_upload;            // the last table copy: the pinned table may be rewritten once it has completed
+    Owned<float> smp;                // sample_alloc: kBatchMax rows of sample_scratch_floats(vocab)
     size_t smp_stride = 0;
     // verify_alloc: the [kBatchMax, vocab] logits matrix, the attention partials ([kBatchMax, n_heads, v_seg_cap,
     // head_size] and [..., 2]), the verdict on the device and pinned
-    float *v_logits = nullptr, *v_part_o = nullptr, *v_part_ml = nullptr;
-    int *d_vout = nullptr, *h_vout = nullptr;  // 3 * kBatchMax ints (l2z_verify: next[0 .. n) | accepted; l2z_verify_batch:
+    Owned<float> v_logits, v_part_o, v_part_ml;
+    Owned<int> d_vout;
+    Pinned<int> h_vout;                        // 3 * kBatchMax ints (l2z_verify: next[0 .. n) | accepted; l2z_verify_batch:
                                                // next[0 .. rows) | accepted[0 .. n); l2z_verify_tree: next[0 .. n) | accepted |
                                                // path[0 .. accepted])
+    int v_cap = 0;                   // (0 or 1: the five are there)
     int v_seg_cap = 0, v_rows = 0;   // v_rows: rows of the last call (l2z_verify_logits_read)
-    // q8_batch_alloc: the step's quantized rows on int8 group-quantized weights, [kBatchMax, max(dim, hidden_dim)] int8 and
-    // their scales at group size q8_gs (a call with another group size re-makes them)
-    int8_t *q8_xq = nullptr;
-    float *q8_xs = nullptr;
-    int q8_gs = 0;
+    // q8_rows_alloc: the step's quantized rows on int8 group-quantized weights, [kBatchMax, max(dim, hidden_dim)] int8 and
+    // their scales at group size q8_gs (a call with another group size re-makes them; q8_cap: 0 or 1, both are there)
+    Owned<int8_t> q8_xq;
+    Owned<float> q8_xs;
+    int q8_cap = 0, q8_gs = 0;
 };
 
 // s->bt and what a call needs in it beyond the step's own: the sampler's scratch, the verify family's (each on first use)
 int batch_alloc(l2z_runstate *s);
 int sample_alloc(l2z_runstate *s);
 int verify_alloc(l2z_runstate *s);
-int q8_batch_alloc(l2z_runstate *s, int gs);
+
+// the grow rule's drain where a group is remade behind work queued on s's stream
+inline int drain_stream(l2z_runstate *s)
+{
+    L2Z_HIP(hipStreamSynchronize(s->stream));
+    return L2Z_OK;
+}
+
+// The quantized rows of a step on int8 group-quantized weights in b (BatchScratch or WideScratch: q8_xq, q8_xs, made for
+// group size q8_gs): `rows` rows of max(dim, hidden_dim) int8 and their scales.  Another group size means other scale rows:
+// both are remade once s's stream has drained
+template <class Scratch> int q8_rows_alloc(const char *what, l2z_runstate *s, Scratch *b, size_t rows, int gs)
+{
+    const size_t widest = (size_t)(s->cfg.dim > s->cfg.hidden_dim ? s->cfg.dim : s->cfg.hidden_dim);
+    return grow(what, &b->q8_cap, 1, 1, &b->q8_gs, gs, [&] { return b->q8_cap != 0 ? drain_stream(s) : L2Z_OK; },
+                {{b->q8_xq, rows * widest}, {b->q8_xs, rows * (widest / (size_t)gs) * 4}});
+}
 
 // What a call of the batched step on int8 group-quantized weights (l2z_transformer_batch_q8, l2z_verify_q8) asks beyond
 // check_pair(..., q8_ok = true): such weights -- f32 and packed ones go to `f32_entry` --, and a shape the step's launches
 // take; fn: the entry point a message names
 int check_q8_step(const char *fn, const char *f32_entry, const l2z_runstate *s0, const l2z_weights *w);
-
-// hipMalloc of every buffer of the list that has a size and is not there yet.  A failure leaves that pointer null, names
-// `what` and the size in the error, and is L2Z_ERR_OOM where the device is out of memory; what was allocated before it
-// stays with its owner, whose clean-up rule is the caller's.
-struct DeviceBuf {
-    void **p;
-    size_t bytes;
-};
-int alloc_all(const char *what, std::initializer_list<DeviceBuf> want);
 
 int no_device_check();
 // the runstates of one call: non-null, pairwise distinct, unsharded, on one device, all made with *c (c: states[0]'s
@@ -114,23 +125,47 @@ struct RaggedTotals {
 // by sequence.
 int check_ragged_call(const RaggedCall &c, RaggedTotals *t);
 
-// the pass on states[0]'s stream waits for everything already queued on every runstate's stream ... (b: a scratch with
-// an event per runstate, ev_in[], and ev_done)
-template <class Scratch> int join_streams(Scratch *b, int n, l2z_runstate *const *states)
-{
-    for (int i = 1; i < n; i++) {
-        L2Z_HIP(hipEventRecord(b->ev_in[i], states[i]->stream));
-        L2Z_HIP(hipStreamWaitEvent(states[0]->stream, b->ev_in[i], 0));
+// A pass on states[0]'s stream over several runstates, as a scope (b: a scratch with an event per runstate, ev_in[], and
+// ev_done).  Made, the pass's stream waits for everything already queued on every runstate's stream (joined(): that
+// hand-over's code).  release(): every runstate's stream waits for the pass, once.  A scope that ends unreleased -- a call
+// that failed in between -- releases then, ignoring errors: no path leaves the other streams unordered behind what was
+// enqueued.
+class StreamScope {
+  public:
+    template <class Scratch>
+    StreamScope(Scratch *b, int n, l2z_runstate *const *states) : ev_in_(b->ev_in), ev_done_(b->ev_done), n_(n), states_(states)
+    {
+        joined_ = join();
     }
-    return L2Z_OK;
-}
-// ... and every runstate's stream waits for the pass
-template <class Scratch> int release_streams(Scratch *b, int n, l2z_runstate *const *states)
-{
-    L2Z_HIP(hipEventRecord(b->ev_done, states[0]->stream));
-    for (int i = 1; i < n; i++) L2Z_HIP(hipStreamWaitEvent(states[i]->stream, b->ev_done, 0));
-    return L2Z_OK;
-}
+    StreamScope(const StreamScope &) = delete;
+    StreamScope &operator=(const StreamScope &) = delete;
+    ~StreamScope() { (void)release(); }
+    int joined() const { return joined_; }
+    int release()
+    {
+        if (released_) return L2Z_OK;
+        released_ = true;
+        L2Z_HIP(hipEventRecord(ev_done_, states_[0]->stream));
+        for (int i = 1; i < n_; i++) L2Z_HIP(hipStreamWaitEvent(states_[i]->stream, ev_done_, 0));
+        return L2Z_OK;
+    }
+
+  private:
+    int join()
+    {
+        for (int i = 1; i < n_; i++) {
+            L2Z_HIP(hipEventRecord(ev_in_[i], states_[i]->stream));
+            L2Z_HIP(hipStreamWaitEvent(states_[0]->stream, ev_in_[i], 0));
+        }
+        return L2Z_OK;
+    }
+    const OwnedEvent *ev_in_;
+    hipEvent_t ev_done_;
+    int n_;
+    l2z_runstate *const *states_;
+    int joined_ = L2Z_OK;
+    bool released_ = false;
+};
 
 // The call left WHOLE logits in s, not a classifier's per-block candidates (l2z_argmax scans them), and s's next position
 // is next_pos
@@ -160,7 +195,7 @@ template <class A> A attention_args(const l2z_config &c, const BatchScratch *b)
 }
 
 // One step of the n rows of b->d_tab on s0's stream, each layer's attention by `attention`.  On int8 group-quantized
-// weights (the caller has run q8_batch_alloc) it hands over to batch_step_q8 (q8_host.cpp), which walks
+// weights (the caller has run q8_rows_alloc) it hands over to batch_step_q8 (q8_host.cpp), which walks
 // the layers as the prompt pass on such weights does (q8_layers)
 int batch_step(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *w, BatchScratch *b, LayerAttention attention);
 int batch_step_q8(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weights *w, BatchScratch *b, LayerAttention attention);

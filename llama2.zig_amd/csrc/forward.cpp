@@ -349,7 +349,7 @@ int enqueue_forward(l2z_runstate *s, const l2z_weights *w, StepKind step, Prof *
                   "sampled step on a runstate l2z_sample_run has not prepared");
         SampleStepArgs a = {};
         a.logits = s->logits; a.vocab = c.vocab_size; a.seq_len = c.seq_len;
-        a.params = (const SampleStepParams *)s->d_smp_ctl; a.coins = s->d_smp_ctl + 2; a.scratch = s->d_smp_scratch;
+        a.params = (const SampleStepParams *)s->d_smp_ctl.get(); a.coins = s->d_smp_ctl + 2; a.scratch = s->d_smp_scratch;
         a.token_ptr = s->d_token; a.pos_ptr = s->d_pos; a.prompt = s->d_prompt; a.n_prompt_ptr = s->d_n_prompt;
         a.out_tokens = s->d_out_tokens; a.tok_emb = w->tok_emb; a.emb_q8 = w->q8_emb(); a.x = s->x; a.dim = c.dim;
         L2Z_LAUNCH(KIND_ARGMAX, launch_sample_step(a, st));
@@ -364,7 +364,7 @@ int attn_variant(const l2z_runstate *s, int pos)
 }
 
 int build_graph(l2z_runstate *s, const l2z_weights *w, StepKind step, int variant,
-                hipGraphExec_t *out)
+                OwnedGraphExec *out)
 {
     hipGraph_t graph = nullptr;
     L2Z_HIP(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
@@ -375,7 +375,7 @@ int build_graph(l2z_runstate *s, const l2z_weights *w, StepKind step, int varian
         return rc;
     }
     L2Z_HIP(e);
-    e = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
+    e = hipGraphInstantiate(out->put(), graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     L2Z_HIP(e);
     return L2Z_OK;
@@ -384,14 +384,14 @@ int build_graph(l2z_runstate *s, const l2z_weights *w, StepKind step, int varian
 void drop_graphs(l2z_runstate *s)
 {
     for (int v = 0; v < ATTN_VARIANTS; v++) {
-        if (s->g_forward[v]) { (void)hipGraphExecDestroy(s->g_forward[v]); s->g_forward[v] = nullptr; }
-        if (s->g_step[v]) { (void)hipGraphExecDestroy(s->g_step[v]); s->g_step[v] = nullptr; }
-        if (s->g_sample[v]) { (void)hipGraphExecDestroy(s->g_sample[v]); s->g_sample[v] = nullptr; }
+        s->g_forward[v].reset();
+        s->g_step[v].reset();
+        s->g_sample[v].reset();
     }
     s->graph_w_uid = 0;
 }
 
-hipGraphExec_t *graph_slot(l2z_runstate *s, StepKind step, int variant)
+OwnedGraphExec *graph_slot(l2z_runstate *s, StepKind step, int variant)
 {
     return step == STEP_SAMPLE ? &s->g_sample[variant] : step == STEP_GREEDY ? &s->g_step[variant] : &s->g_forward[variant];
 }
@@ -419,7 +419,7 @@ int ensure_graph(l2z_runstate *s, const l2z_weights *w, int variant, StepKind st
             if (rc == L2Z_OK) rc = build_graph(s, w, STEP_GREEDY, v, &s->g_step[v]);
         }
     }
-    hipGraphExec_t *slot = graph_slot(s, step, variant);
+    OwnedGraphExec *slot = graph_slot(s, step, variant);
     if (rc == L2Z_OK && *slot) return L2Z_OK;
     if (rc != L2Z_OK || build_graph(s, w, step, variant, slot) != L2Z_OK) {
         // capture is an optimisation, not a requirement: run the same launches eagerly
@@ -514,11 +514,11 @@ extern "C" int l2z_probs_read(l2z_runstate *s, float temperature, float *out_pro
     L2Z_CHECK(temperature > 0.0f, L2Z_ERR_INVALID, "l2z_probs_read: temperature %g (0 is the argmax path)", (double)temperature);
     L2Z_HIP(hipSetDevice(s->device));
     L2Z_TRY(ensure_logits(s));
-    if (s->d_probs == nullptr) L2Z_HIP(hipMalloc(&s->d_probs, (size_t)s->cfg.vocab_size * sizeof(float)));
+    L2Z_TRY(s->d_probs.make((size_t)s->cfg.vocab_size * sizeof(float), "l2z_probs_read"));
     L2Z_HIP(launch_probs(s->d_probs, s->logits, s->cfg.vocab_size, temperature, s->stream));
     // through a pinned buffer: a copy into pageable memory is staged by the runtime anyway, slower
     const size_t bytes = (size_t)s->cfg.vocab_size * sizeof(float);
-    if (s->h_stage == nullptr) L2Z_HIP(hipHostMalloc((void **)&s->h_stage, bytes, hipHostMallocDefault));
+    L2Z_TRY(s->h_stage.make(bytes, "l2z_probs_read landing buffer"));
     L2Z_HIP(hipMemcpyAsync(s->h_stage, s->d_probs, bytes, hipMemcpyDeviceToHost, s->stream));
     L2Z_HIP(hipStreamSynchronize(s->stream));
     L2Z_TRY(comm_check(s->comm));
@@ -643,12 +643,13 @@ extern "C" int l2z_sample_run(const l2z_config *config, l2z_runstate *s, const l
     L2Z_HIP(hipSetDevice(s->device));
     const size_t ctl_bytes = (2 + (size_t)config->seq_len) * sizeof(float);
     if (s->d_smp_ctl == nullptr) {
-        L2Z_HIP(hipMalloc((void **)&s->d_smp_ctl, ctl_bytes));
-        L2Z_HIP(hipMemset(s->d_smp_ctl, 0, ctl_bytes));
+        L2Z_TRY(s->d_smp_ctl.make(ctl_bytes, "l2z_sample_run controls"));
+        const hipError_t e = hipMemset(s->d_smp_ctl, 0, ctl_bytes);
+        if (e != hipSuccess) s->d_smp_ctl.reset();   // (never kept unzeroed)
+        L2Z_HIP(e);
     }
-    if (s->h_smp_ctl == nullptr) L2Z_HIP(hipHostMalloc((void **)&s->h_smp_ctl, ctl_bytes, hipHostMallocDefault));
-    if (s->d_smp_scratch == nullptr)
-        L2Z_HIP(hipMalloc((void **)&s->d_smp_scratch, sample_scratch_floats(config->vocab_size) * sizeof(float)));
+    L2Z_TRY(s->h_smp_ctl.make(ctl_bytes, "l2z_sample_run controls"));
+    L2Z_TRY(s->d_smp_scratch.make(sample_scratch_floats(config->vocab_size) * sizeof(float), "l2z_sample_run scratch"));
     // this call's temperature, top_p and coins (at the positions its steps take) -> the device, behind everything queued.
     // The pinned twin is free to rewrite: only these copies read it, and no call returns with them in flight (at least one
     // step is left, so step_loop syncs the stream behind them -- after the prompt's pass or after the first chunk)
@@ -781,7 +782,7 @@ extern "C" int l2z_emu_transformer(int n_ranks, l2z_runstate *const *ss,
         else if (stage % 4 == 2) { which = 2; count = sh0.hid_loc; }
         else { which = 1; count = sh0.dim_loc; }
         auto buf = [&](l2z_runstate *s) {
-            return which == 0 ? s->xb : which == 1 ? s->x : which == 2 ? s->hb : s->logits;
+            return (which == 0 ? s->xb : which == 1 ? s->x : which == 2 ? s->hb : s->logits).get();
         };
         for (int src = 0; src < n_ranks; src++)
             for (int dst = 0; dst < n_ranks; dst++)

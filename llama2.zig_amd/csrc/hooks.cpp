@@ -24,10 +24,8 @@ using namespace l2z;
 // ---------------------------------------------------------------------------
 // Kernel-level test hooks: upload, launch, download.
 namespace {
-struct DevBuf {
-    float *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n) { L2Z_HIP(hipMalloc(&p, (n ? n : 1) * sizeof(float))); return L2Z_OK; }
+struct DevBuf : HookBuf<float> {   // (counted in floats)
+    int alloc(size_t n) { return HookBuf::alloc(n * sizeof(float)); }
     int up(const float *h, size_t n) { L2Z_HIP(hipMemcpy(p, h, n * sizeof(float), hipMemcpyHostToDevice)); return L2Z_OK; }
     int down(float *h, size_t n) { L2Z_HIP(hipMemcpy(h, p, n * sizeof(float), hipMemcpyDeviceToHost)); return L2Z_OK; }
 };
@@ -44,15 +42,15 @@ extern "C" int l2z_matmul_fused(int N, float *const *outs, const float *x, const
     L2Z_TRY(dx.alloc(n));
     L2Z_TRY(dx.up(x, n));
     MatvecArgs a = {};
-    a.n = (int)n; a.x = dx.p;
+    a.n = (int)n; a.x = dx.p.get();
     for (int j = 0; j < N; j++) {
         L2Z_TRY(dw[j].alloc(n * d));
         L2Z_TRY(dw[j].up(ws[j], n * d));
         L2Z_TRY(dout[j].alloc(d));
     }
-    a.w0 = dw[0].p; a.out0 = dout[0].p; a.rows0 = (int)d;
-    if (N > 1) { a.w1 = dw[1].p; a.out1 = dout[1].p; a.rows1 = (int)d; }
-    if (N > 2) { a.w2 = dw[2].p; a.out2 = dout[2].p; a.rows2 = (int)d; }
+    a.w0 = dw[0].p.get(); a.out0 = dout[0].p.get(); a.rows0 = (int)d;
+    if (N > 1) { a.w1 = dw[1].p.get(); a.out1 = dout[1].p.get(); a.rows1 = (int)d; }
+    if (N > 2) { a.w2 = dw[2].p.get(); a.out2 = dout[2].p.get(); a.rows2 = (int)d; }
     L2Z_HIP(launch_matvec(a, PRO_NONE, EPI_STORE, 8, g_cus, nullptr));
     L2Z_HIP(hipDeviceSynchronize());
     for (int j = 0; j < N; j++) L2Z_TRY(dout[j].down(outs[j], d));
@@ -74,7 +72,7 @@ extern "C" int l2z_rmsnorm(float *o, const float *x, const float *w, size_t n)
     DevBuf dx, dw, dout;
     L2Z_TRY(dx.alloc(n)); L2Z_TRY(dw.alloc(n)); L2Z_TRY(dout.alloc(n));
     L2Z_TRY(dx.up(x, n)); L2Z_TRY(dw.up(w, n));
-    L2Z_HIP(launch_rmsnorm(dout.p, dx.p, dw.p, (int)n, nullptr));
+    L2Z_HIP(launch_rmsnorm(dout.p.get(), dx.p.get(), dw.p.get(), (int)n, nullptr));
     L2Z_HIP(hipDeviceSynchronize());
     return dout.down(o, n);
 }
@@ -85,7 +83,7 @@ extern "C" int l2z_softmax(float *x, size_t n)
     L2Z_TRY(ensure_device(current_device_for(nullptr)));
     DevBuf dx;
     L2Z_TRY(dx.alloc(n)); L2Z_TRY(dx.up(x, n));
-    L2Z_HIP(launch_softmax(dx.p, (int)n, nullptr));
+    L2Z_HIP(launch_softmax(dx.p.get(), (int)n, nullptr));
     L2Z_HIP(hipDeviceSynchronize());
     return dx.down(x, n);
 }
@@ -97,7 +95,7 @@ extern "C" int l2z_vector_dot_product(float *out, const float *x, const float *y
     DevBuf dx, dy, dout;
     L2Z_TRY(dx.alloc(n)); L2Z_TRY(dy.alloc(n)); L2Z_TRY(dout.alloc(1));
     L2Z_TRY(dx.up(x, n)); L2Z_TRY(dy.up(y, n));
-    L2Z_HIP(launch_dot(dout.p, dx.p, dy.p, (int)n, nullptr));
+    L2Z_HIP(launch_dot(dout.p.get(), dx.p.get(), dy.p.get(), (int)n, nullptr));
     L2Z_HIP(hipDeviceSynchronize());
     return dout.down(out, 1);
 }
@@ -115,7 +113,7 @@ extern "C" int l2z_vector_weighted_sum_rows(float *xout, size_t xout_len, const 
     DevBuf dr, dw, dout;
     L2Z_TRY(dr.alloc(rows_len)); L2Z_TRY(dw.alloc(n_weights)); L2Z_TRY(dout.alloc(xout_len));
     L2Z_TRY(dr.up(rows, rows_len)); L2Z_TRY(dw.up(weights, n_weights));
-    L2Z_HIP(launch_weighted_sum_rows(dout.p, (int)xout_len, dr.p, (int)row_stride, dw.p,
+    L2Z_HIP(launch_weighted_sum_rows(dout.p.get(), (int)xout_len, dr.p.get(), (int)row_stride, dw.p.get(),
                                      (int)n_weights, nullptr));
     L2Z_HIP(hipDeviceSynchronize());
     return dout.down(xout, xout_len);
@@ -126,15 +124,14 @@ extern "C" int l2z_argmax_host(const float *x, size_t n, size_t *out_index)
     L2Z_CHECK(x && out_index && n > 0 && n < (1u << 30), L2Z_ERR_INVALID, "l2z_argmax_host: bad arguments");
     L2Z_TRY(ensure_device(current_device_for(nullptr)));
     DevBuf dx;
-    int *didx = nullptr;
+    Owned<int> didx;
     L2Z_TRY(dx.alloc(n)); L2Z_TRY(dx.up(x, n));
-    L2Z_HIP(hipMalloc(&didx, sizeof(int)));
+    L2Z_TRY(didx.make(sizeof(int), "test hook buffer"));
     ArgmaxArgs a = {};
-    a.logits = dx.p; a.vocab = (int)n; a.argmax_out = didx; a.advance = 0;
+    a.logits = dx.p.get(); a.vocab = (int)n; a.argmax_out = didx; a.advance = 0;
     hipError_t e = launch_argmax(a, nullptr);
     int idx = 0;
     if (e == hipSuccess) e = hipMemcpy(&idx, didx, sizeof(int), hipMemcpyDeviceToHost);
-    (void)hipFree(didx);
     L2Z_HIP(e);
     *out_index = (size_t)idx;
     return L2Z_OK;
@@ -174,7 +171,7 @@ extern "C" int l2z_prefill_attention(int form, float *out, const float *q, const
     const std::vector<float> hk = to_head_major(kcache, seq_len, n_kv_heads, head_size),
                              hv = to_head_major(vcache, seq_len, n_kv_heads, head_size);
     L2Z_TRY(dq.up(q, n_queries * dim)); L2Z_TRY(dk.up(hk.data(), seq_len * kvd)); L2Z_TRY(dv.up(hv.data(), seq_len * kvd));
-    const hipError_t e = launch_prefill_attention(dq.p, (int)dim, dk.p, dv.p, dout.p, (int)dim, pos0, n_queries, n_heads,
+    const hipError_t e = launch_prefill_attention(dq.p.get(), (int)dim, dk.p.get(), dv.p.get(), dout.p.get(), (int)dim, pos0, n_queries, n_heads,
                                                   head_size, head_size, (size_t)seq_len * head_size, n_heads / n_kv_heads,
                                                   seq_len, nullptr, n_heads, form);
     L2Z_HIP(e);
@@ -196,13 +193,13 @@ extern "C" int l2z_attention_decode(int form, int nch, float *out, const float *
     const size_t dim = (size_t)n_heads * head_size, kvd = (size_t)n_kv_heads * head_size;
     const size_t kvn = (size_t)seq_len * kvd;
     DevBuf dq, dk, dv, dout, dpart;
-    int *dpos = nullptr, *dcnt = nullptr;
+    Owned<int> dpos, dcnt;
     L2Z_TRY(dq.alloc(dim)); L2Z_TRY(dk.alloc(kvn)); L2Z_TRY(dv.alloc(kvn)); L2Z_TRY(dout.alloc(dim));
     const std::vector<float> hk = to_head_major(kcache, seq_len, n_kv_heads, head_size),
                              hv = to_head_major(vcache, seq_len, n_kv_heads, head_size);
     L2Z_TRY(dq.up(q, dim)); L2Z_TRY(dk.up(hk.data(), kvn)); L2Z_TRY(dv.up(hv.data(), kvn));
     AttnArgs a = {};
-    a.q = dq.p; a.kcache = dk.p; a.vcache = dv.p; a.xb = dout.p;
+    a.q = dq.p.get(); a.kcache = dk.p.get(); a.vcache = dv.p.get(); a.xb = dout.p.get();
     a.head_size = head_size; a.kv_row = head_size; a.kv_head = (size_t)seq_len * head_size;
     a.kv_mul = n_heads / n_kv_heads; a.seq_len = seq_len;
     const bool fast_ok = attention_split_supported(a);  // same conditions as the fast kernels
@@ -210,8 +207,8 @@ extern "C" int l2z_attention_decode(int form, int nch, float *out, const float *
               "l2z_attention_decode: form %d needs head_size %% 4 == 0 and <= 256", form);
     const size_t att_lds = attention_lds_bytes(head_size, seq_len, fast_ok);
     L2Z_CHECK(att_lds <= 160 * 1024, L2Z_ERR_INVALID, "l2z_attention_decode: seq_len too long for LDS");
-    hipError_t e = hipMalloc(&dpos, sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dpos, &pos, sizeof(int), hipMemcpyHostToDevice);
+    L2Z_TRY(dpos.make(sizeof(int), "test hook buffer"));
+    hipError_t e = hipMemcpy(dpos, &pos, sizeof(int), hipMemcpyHostToDevice);
     a.pos_ptr = dpos;
     int use_nch = 0;
     if (e == hipSuccess && (form == 3 || (form == 0 && fast_ok && pos >= 256 && seq_len > 256))) {
@@ -220,22 +217,19 @@ extern "C" int l2z_attention_decode(int form, int nch, float *out, const float *
         if (use_nch < 2) use_nch = form == 3 ? 2 : 0;
     }
     if (e == hipSuccess && use_nch > 1) {
-        int rc = dpart.alloc(attention_split_part_floats(n_heads, head_size, use_nch));
-        if (rc != L2Z_OK) { (void)hipFree(dpos); return rc; }
-        e = hipMalloc(&dcnt, (size_t)n_heads * sizeof(int));
-        if (e == hipSuccess) e = hipMemset(dcnt, 0, (size_t)n_heads * sizeof(int));
+        L2Z_TRY(dpart.alloc(attention_split_part_floats(n_heads, head_size, use_nch)));
+        L2Z_TRY(dcnt.make((size_t)n_heads * sizeof(int), "test hook buffer"));
+        e = hipMemset(dcnt, 0, (size_t)n_heads * sizeof(int));
         // twice: the second launch finds the counters as the first one left them
         const bool small = pos < attention_split_wide_pos(seq_len);  // as the forward pass picks at this position
-        if (e == hipSuccess) e = launch_attention_split(a, n_heads, use_nch, dpart.p, dcnt, nullptr, small);
-        if (e == hipSuccess) e = launch_attention_split(a, n_heads, use_nch, dpart.p, dcnt, nullptr, small);
+        if (e == hipSuccess) e = launch_attention_split(a, n_heads, use_nch, dpart.p.get(), dcnt, nullptr, small);
+        if (e == hipSuccess) e = launch_attention_split(a, n_heads, use_nch, dpart.p.get(), dcnt, nullptr, small);
     } else if (e == hipSuccess) {
         // form 0: what the forward pass launches at this position (attn_variant: the short-context form first)
         const int auto_form = pos < attention_short_pos(head_size, seq_len) ? 1 : 0;
         e = launch_attention(a, n_heads, nullptr, form == 3 || form == 0 ? auto_form : form);
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    (void)hipFree(dpos);
-    if (dcnt) (void)hipFree(dcnt);
     L2Z_HIP(e);
     return dout.down(out, dim);
 }
@@ -336,9 +330,9 @@ extern "C" int l2z_q8_quantize(const float *x, size_t n, int gs, int8_t *out_q, 
     DevBuf dx, dq, ds;
     L2Z_TRY(dx.alloc(n)); L2Z_TRY(dq.alloc(n / 4)); L2Z_TRY(ds.alloc(n / gs));
     L2Z_TRY(dx.up(x, n));
-    L2Z_HIP(launch_q8_quantize(dx.p, n, gs, false, (int8_t *)dq.p, ds.p, nullptr));
+    L2Z_HIP(launch_q8_quantize(dx.p.get(), n, gs, false, (int8_t *)dq.p.get(), ds.p.get(), nullptr));
     L2Z_HIP(hipDeviceSynchronize());
-    L2Z_HIP(hipMemcpy(out_q, dq.p, n, hipMemcpyDeviceToHost));
+    L2Z_HIP(hipMemcpy(out_q, dq.p.get(), n, hipMemcpyDeviceToHost));
     return ds.down(out_s, n / gs);
 }
 
@@ -354,14 +348,14 @@ extern "C" int l2z_q8_matmul(float *out, const int8_t *xq, const float *xs, cons
     DevBuf dxq, dxs, dwq, dws, dout;
     L2Z_TRY(dxq.alloc(n / 4)); L2Z_TRY(dxs.alloc(ng)); L2Z_TRY(dwq.alloc(n * d / 4)); L2Z_TRY(dws.alloc(ng * d));
     L2Z_TRY(dout.alloc(d));
-    L2Z_HIP(hipMemcpy(dxq.p, xq, n, hipMemcpyHostToDevice));
-    L2Z_HIP(hipMemcpy(dwq.p, wq, n * d, hipMemcpyHostToDevice));
+    L2Z_HIP(hipMemcpy(dxq.p.get(), xq, n, hipMemcpyHostToDevice));
+    L2Z_HIP(hipMemcpy(dwq.p.get(), wq, n * d, hipMemcpyHostToDevice));
     L2Z_TRY(dxs.up(xs, ng)); L2Z_TRY(dws.up(ws, ng * d));
     Q8MatvecArgs a = {};
     a.gs = gs;
-    a.q0 = (const int8_t *)dwq.p; a.s0 = dws.p;
-    a.xq = (const int8_t *)dxq.p; a.xs = dxs.p;
-    a.b.n = (int)n; a.b.rows0 = (int)d; a.b.out0 = dout.p;
+    a.q0 = (const int8_t *)dwq.p.get(); a.s0 = dws.p.get();
+    a.xq = (const int8_t *)dxq.p.get(); a.xs = dxs.p.get();
+    a.b.n = (int)n; a.b.rows0 = (int)d; a.b.out0 = dout.p.get();
     L2Z_HIP(launch_q8_matvec(a, EPI_STORE, 8, g_cus, nullptr));
     L2Z_HIP(hipDeviceSynchronize());
     return dout.down(out, d);
@@ -370,19 +364,6 @@ extern "C" int l2z_q8_matmul(float *out, const int8_t *xq, const float *xs, cons
 // One launch of the q8 mat-vec as the pass issues it, every argument the caller's (include/llama2_hip_test.h): the
 // epilogue, up to three segments, x in any of its three forms, the RoPE table and the head-major caches, the residual in
 // place or not, and the two numbers the launcher sizes its grid from.  Goes through launch_q8_matvec as it stands.
-namespace {
-struct DevBytes {
-    void *p = nullptr;
-    ~DevBytes() { if (p) (void)hipFree(p); }
-    int up(const void *h, size_t bytes)
-    {
-        L2Z_HIP(hipMalloc(&p, bytes ? bytes : 1));
-        if (h != nullptr && bytes > 0) L2Z_HIP(hipMemcpy(p, h, bytes, hipMemcpyHostToDevice));
-        return L2Z_OK;
-    }
-};
-}  // namespace
-
 extern "C" int l2z_q8_matvec_case(l2z_q8_case *c)
 {
     L2Z_CHECK(c != nullptr, L2Z_ERR_INVALID, "l2z_q8_matvec_case: null argument");
@@ -439,36 +420,36 @@ extern "C" int l2z_q8_matvec_case(l2z_q8_case *c)
     const int mb = c->max_blocks_per_cu > 0 ? c->max_blocks_per_cu : Tunables::max_blocks_per_cu;
     const size_t ng = (size_t)n / gs;
 
-    DevBytes dq[3], ds[3], dxq, dxs, dx, drms, dout[3], dresid, drope, dpos, dpv, dpi;
+    HookBuf<void> dq[3], ds[3], dxq, dxs, dx, drms, dout[3], dresid, drope, dpos, dpv, dpi;
     Q8MatvecArgs a = {};
     a.gs = gs;
     for (int j = 0; j < n_seg; j++) {
         const size_t r = epi == EPI_SWIGLU ? 2 * (size_t)rows[0] : (size_t)rows[j];
-        L2Z_TRY(dq[j].up(hq[j], r * (size_t)n));
-        L2Z_TRY(ds[j].up(hs[j], r * ng * sizeof(float)));
+        L2Z_TRY(dq[j].put(hq[j], r * (size_t)n));
+        L2Z_TRY(ds[j].put(hs[j], r * ng * sizeof(float)));
     }
-    a.q0 = (const int8_t *)dq[0].p; a.q1 = (const int8_t *)dq[1].p; a.q2 = (const int8_t *)dq[2].p;
-    a.s0 = (const float *)ds[0].p; a.s1 = (const float *)ds[1].p; a.s2 = (const float *)ds[2].p;
+    a.q0 = (const int8_t *)dq[0].p.get(); a.q1 = (const int8_t *)dq[1].p.get(); a.q2 = (const int8_t *)dq[2].p.get();
+    a.s0 = (const float *)ds[0].p.get(); a.s1 = (const float *)ds[1].p.get(); a.s2 = (const float *)ds[2].p.get();
     if (quantized) {
-        L2Z_TRY(dxq.up(c->xq, (size_t)n));
-        L2Z_TRY(dxs.up(c->xs, ng * sizeof(float)));
-        a.xq = (const int8_t *)dxq.p; a.xs = (const float *)dxs.p;
+        L2Z_TRY(dxq.put(c->xq, (size_t)n));
+        L2Z_TRY(dxs.put(c->xs, ng * sizeof(float)));
+        a.xq = (const int8_t *)dxq.p.get(); a.xs = (const float *)dxs.p.get();
     } else {
-        L2Z_TRY(dx.up(c->x, (size_t)n * sizeof(float)));
-        a.b.x = (const float *)dx.p;
+        L2Z_TRY(dx.put(c->x, (size_t)n * sizeof(float)));
+        a.b.x = (const float *)dx.p.get();
         if (c->rms_w != nullptr) {
-            L2Z_TRY(drms.up(c->rms_w, (size_t)n * sizeof(float)));
-            a.b.rms_w = (const float *)drms.p;
+            L2Z_TRY(drms.put(c->rms_w, (size_t)n * sizeof(float)));
+            a.b.rms_w = (const float *)drms.p.get();
         }
     }
-    for (int j = 0; j < n_out; j++) L2Z_TRY(dout[j].up(ho[j], olen[j] * sizeof(float)));
-    a.b.out0 = (float *)dout[0].p; a.b.out1 = (float *)dout[1].p; a.b.out2 = (float *)dout[2].p;
+    for (int j = 0; j < n_out; j++) L2Z_TRY(dout[j].put(ho[j], olen[j] * sizeof(float)));
+    a.b.out0 = (float *)dout[0].p.get(); a.b.out1 = (float *)dout[1].p.get(); a.b.out2 = (float *)dout[2].p.get();
     a.b.rows0 = rows[0]; a.b.rows1 = rows[1]; a.b.rows2 = rows[2];
     a.b.n = n;
     if (epi == EPI_ROPE) {   // as enqueue_forward_q8's q | k | v launch
-        L2Z_TRY(drope.up(c->rope, (size_t)(c->pos + 1) * (size_t)(c->head_size / 2) * sizeof(float2)));
-        L2Z_TRY(dpos.up(&c->pos, sizeof(int)));
-        a.b.rope = (const float2 *)drope.p; a.b.pos_ptr = (const int *)dpos.p;
+        L2Z_TRY(drope.put(c->rope, (size_t)(c->pos + 1) * (size_t)(c->head_size / 2) * sizeof(float2)));
+        L2Z_TRY(dpos.put(&c->pos, sizeof(int)));
+        a.b.rope = (const float2 *)drope.p.get(); a.b.pos_ptr = (const int *)dpos.p.get();
         a.b.head_size = c->head_size; a.b.rope_segs = c->rope_segs;
         a.b.pos_stride1 = c->head_size; a.b.pos_stride2 = c->head_size; a.b.kv_head_stride = kv_head_stride;
     }
@@ -476,25 +457,25 @@ extern "C" int l2z_q8_matvec_case(l2z_q8_case *c)
         if (c->in_place) {   // out0 == resid, as the pass's Wo and W2 launches: the buffer starts as the residual
             a.b.resid = a.b.out0;
         } else {
-            L2Z_TRY(dresid.up(c->resid, (size_t)rows[0] * sizeof(float)));
-            a.b.resid = (const float *)dresid.p;
+            L2Z_TRY(dresid.put(c->resid, (size_t)rows[0] * sizeof(float)));
+            a.b.resid = (const float *)dresid.p.get();
         }
     }
     if (epi == EPI_ARGMAX) {
         const size_t room = (size_t)matvec_max_grid(n_cus);   // the launcher never launches more blocks
-        L2Z_TRY(dpv.up(nullptr, room * sizeof(float)));
-        L2Z_TRY(dpi.up(nullptr, room * sizeof(int)));
-        a.b.part_val = (float *)dpv.p; a.b.part_idx = (int *)dpi.p;
+        L2Z_TRY(dpv.put(nullptr, room * sizeof(float)));
+        L2Z_TRY(dpi.put(nullptr, room * sizeof(int)));
+        a.b.part_val = (float *)dpv.p.get(); a.b.part_idx = (int *)dpi.p.get();
     }
     int grid = 0;
     L2Z_HIP(launch_q8_matvec(a, epi, mb, n_cus, nullptr, &grid));
     L2Z_HIP(hipDeviceSynchronize());
     c->grid = grid;
-    for (int j = 0; j < n_out; j++) L2Z_HIP(hipMemcpy(ho[j], dout[j].p, olen[j] * sizeof(float), hipMemcpyDeviceToHost));
+    for (int j = 0; j < n_out; j++) L2Z_HIP(hipMemcpy(ho[j], dout[j].p.get(), olen[j] * sizeof(float), hipMemcpyDeviceToHost));
     if (epi == EPI_ARGMAX) {
         L2Z_CHECK(grid <= c->part_cap, L2Z_ERR_INVALID, "l2z_q8_matvec_case: %d candidates, room for %d", grid, c->part_cap);
-        L2Z_HIP(hipMemcpy(c->part_val, dpv.p, (size_t)grid * sizeof(float), hipMemcpyDeviceToHost));
-        L2Z_HIP(hipMemcpy(c->part_idx, dpi.p, (size_t)grid * sizeof(int), hipMemcpyDeviceToHost));
+        L2Z_HIP(hipMemcpy(c->part_val, dpv.p.get(), (size_t)grid * sizeof(float), hipMemcpyDeviceToHost));
+        L2Z_HIP(hipMemcpy(c->part_idx, dpi.p.get(), (size_t)grid * sizeof(int), hipMemcpyDeviceToHost));
     }
     return L2Z_OK;
 }

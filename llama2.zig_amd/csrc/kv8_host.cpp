@@ -40,19 +40,6 @@ void l2z::kv8_prompt_tables(void *host, const Kv8Seq &seq, int pos0, int P, bool
     for (int r = 0; r < P; r++) tab[r / kWideMax].pos[r % kWideMax] = pos0 + r;
 }
 
-namespace {
-struct DevBytes {
-    void *p = nullptr;
-    ~DevBytes() { if (p) (void)hipFree(p); }
-    int put(const void *from, size_t bytes)
-    {
-        L2Z_HIP(hipMalloc(&p, bytes ? bytes : 1));
-        if (from != nullptr) L2Z_HIP(hipMemcpy(p, from, bytes, hipMemcpyHostToDevice));
-        return L2Z_OK;
-    }
-};
-}  // namespace
-
 // PREVIEW (include/llama2_hip_test.h): launch_kv8_attention on its own -- host pointers, synchronous, one layer
 extern "C" int l2z_kv8_attention(float *out, const float *q, const int32_t *pos, int n, const int8_t *k8, const float *ks,
                                  const int8_t *v8, const float *vs, int n_heads, int n_kv_heads, int head_size, int seq_len)
@@ -72,7 +59,7 @@ extern "C" int l2z_kv8_attention(float *out, const float *q, const int32_t *pos,
     L2Z_TRY(ensure_device(current_device_for(nullptr)));
     const size_t hs = (size_t)head_size, S = (size_t)seq_len, dim = (size_t)n_heads * hs;
     const size_t row_s = (size_t)n_kv_heads * S, row_v = row_s * hs;   // one row's scales, values
-    DevBytes dq, dout, dk, dv, dks, dvs, dtab, dseq, dpart;
+    HookBuf<void> dq, dout, dk, dv, dks, dvs, dtab, dseq, dpart;
     L2Z_TRY(dq.put(q, (size_t)n * dim * 4)); L2Z_TRY(dout.put(nullptr, (size_t)n * dim * 4));
     L2Z_TRY(dk.put(k8, (size_t)n * row_v)); L2Z_TRY(dv.put(v8, (size_t)n * row_v));
     L2Z_TRY(dks.put(ks, (size_t)n * row_s * 4)); L2Z_TRY(dvs.put(vs, (size_t)n * row_s * 4));
@@ -80,18 +67,18 @@ extern "C" int l2z_kv8_attention(float *out, const float *q, const int32_t *pos,
     std::vector<Kv8Seq> seq((size_t)n);
     for (int i = 0; i < n; i++) {
         tab[0].pos[i] = pos[i];
-        seq[(size_t)i] = {(int8_t *)dk.p + i * row_v, (int8_t *)dv.p + i * row_v, (float *)dks.p + i * row_s, (float *)dvs.p + i * row_s};
+        seq[(size_t)i] = {(int8_t *)dk.p.get() + i * row_v, (int8_t *)dv.p.get() + i * row_v, (float *)dks.p.get() + i * row_s, (float *)dvs.p.get() + i * row_s};
     }
     L2Z_TRY(dtab.put(tab.data(), sizeof(WideTable)));
     L2Z_TRY(dseq.put(seq.data(), seq.size() * sizeof(Kv8Seq)));
     const int seg_cap = verify_segments(seq_len);
     L2Z_TRY(dpart.put(nullptr, wide_part_floats(n_heads, seg_cap, head_size) * 4));
-    const WideAttn wa = {(const WideTable *)dtab.p, (float *)dpart.p, seg_cap, deepest / kVerifySeg + 1, 0, n, 0};
-    const RaggedLayer L = {(const float *)dq.p, (int)dim, (float *)dout.p, (int)dim, n, n_heads, head_size, n_heads / n_kv_heads, seq_len,
+    const WideAttn wa = {(const WideTable *)dtab.p.get(), (float *)dpart.p.get(), seg_cap, deepest / kVerifySeg + 1, 0, n, 0};
+    const RaggedLayer L = {(const float *)dq.p.get(), (int)dim, (float *)dout.p.get(), (int)dim, n, n_heads, head_size, n_heads / n_kv_heads, seq_len,
                            0, S * hs, nullptr, nullptr, 0};
-    L2Z_HIP(launch_kv8_attention(L, wa, (const Kv8Seq *)dseq.p));
+    L2Z_HIP(launch_kv8_attention(L, wa, (const Kv8Seq *)dseq.p.get()));
     L2Z_HIP(hipDeviceSynchronize());
-    L2Z_HIP(hipMemcpy(out, dout.p, (size_t)n * dim * 4, hipMemcpyDeviceToHost));
+    L2Z_HIP(hipMemcpy(out, dout.p.get(), (size_t)n * dim * 4, hipMemcpyDeviceToHost));
     return L2Z_OK;
 }
 
@@ -114,25 +101,25 @@ extern "C" int l2z_kv8_prefill_attention(int form, float *out, const float *q, i
     L2Z_TRY(ensure_device(current_device_for(nullptr)));
     const size_t hs = (size_t)head_size, S = (size_t)seq_len, dim = (size_t)n_heads * hs, row_s = (size_t)n_kv_heads * S;
     const bool with_rows = form == 1 || !kv8_prefill_flash_shape(head_size, P);
-    DevBytes dq, dout, dk, dv, dks, dvs, dtab, dpart;
+    HookBuf<void> dq, dout, dk, dv, dks, dvs, dtab, dpart;
     L2Z_TRY(dq.put(q, (size_t)P * dim * 4)); L2Z_TRY(dout.put(nullptr, (size_t)P * dim * 4));
     L2Z_TRY(dk.put(k8, row_s * hs)); L2Z_TRY(dv.put(v8, row_s * hs));
     L2Z_TRY(dks.put(ks, row_s * 4)); L2Z_TRY(dvs.put(vs, row_s * 4));
     Kv8Prompt pr = {};
-    pr.seq = {(int8_t *)dk.p, (int8_t *)dv.p, (float *)dks.p, (float *)dvs.p};
+    pr.seq = {(int8_t *)dk.p.get(), (int8_t *)dv.p.get(), (float *)dks.p.get(), (float *)dvs.p.get()};
     std::vector<uint8_t> tab(kv8_prompt_table_bytes(P, with_rows));
     kv8_prompt_tables(tab.data(), pr.seq, pos0, P, with_rows);
     L2Z_TRY(dtab.put(tab.data(), tab.size()));
-    pr.slots = (const Kv8Seq *)dtab.p;
+    pr.slots = (const Kv8Seq *)dtab.p.get();
     pr.tab = (const WideTable *)(pr.slots + kWideMax);
     pr.seg_cap = verify_segments(seq_len);
     if (with_rows) {
         L2Z_TRY(dpart.put(nullptr, wide_part_floats(n_heads, pr.seg_cap, head_size) * 4));
-        pr.part = (float *)dpart.p;
+        pr.part = (float *)dpart.p.get();
     }
-    L2Z_HIP(launch_kv8_prefill_attention((const float *)dq.p, (int)dim, pr, (float *)dout.p, (int)dim, pos0, P, n_heads, head_size,
+    L2Z_HIP(launch_kv8_prefill_attention((const float *)dq.p.get(), (int)dim, pr, (float *)dout.p.get(), (int)dim, pos0, P, n_heads, head_size,
                                          n_heads / n_kv_heads, seq_len, 0, S * hs, nullptr, form));
     L2Z_HIP(hipDeviceSynchronize());
-    L2Z_HIP(hipMemcpy(out, dout.p, (size_t)P * dim * 4, hipMemcpyDeviceToHost));
+    L2Z_HIP(hipMemcpy(out, dout.p.get(), (size_t)P * dim * 4, hipMemcpyDeviceToHost));
     return L2Z_OK;
 }

@@ -129,15 +129,11 @@ int kv_copy_rows(l2z_runstate *dst, const l2z_runstate *src, int r0, int n_pos)
     return L2Z_OK;
 }
 
-void kv_runstate_free(l2z_runstate *s)
+void kv_runstate_free(l2z_kvpool *pool, KvSeq &pg)
 {
-    if (s->pool == nullptr) return;
-    s->pool->alloc.release(s->pg);   // (l2z_runstate_free has drained the stream)
-    s->pool->live--;
-    if (s->d_pages) (void)hipFree(s->d_pages);
-    if (s->h_pages) (void)hipHostFree(s->h_pages);
-    s->d_pages = s->h_pages = nullptr;
-    s->pool = nullptr;
+    if (pool == nullptr) return;
+    pool->alloc.release(pg);   // (l2z_runstate_free has drained the stream)
+    pool->live--;
 }
 
 }  // namespace l2z

@@ -3,17 +3,61 @@
 // hooks.cpp).  Product code; nothing under oracle/ is referenced.
 #pragma once
 #include <cstdint>
+#include <memory>
 #include <vector>
 
 #include "kv_pages.h"
 #include "l2z_comm.h"
 #include "l2z_internal.h"
+#include "owned.h"
 #include "tunables.h"
 
 namespace l2z {
 
 struct BatchScratch;  // batch_host.h
 struct WideScratch;   // wide_host.cpp
+// (a runstate owns one of each; their members free themselves: batch_host.cpp, wide_host.cpp)
+struct BatchScratchDelete { void operator()(BatchScratch *b) const; };
+struct WideScratchDelete { void operator()(WideScratch *b) const; };
+
+// owned.h's owner for a handle of the runtime (an event, a graph executable): null by default, destroyed with its owner
+template <class H, hipError_t (*Destroy)(H)> class OwnedHandle {
+  public:
+    OwnedHandle() = default;
+    OwnedHandle(const OwnedHandle &) = delete;
+    OwnedHandle &operator=(const OwnedHandle &) = delete;
+    ~OwnedHandle() { reset(); }
+    void reset()
+    {
+        if (h_ != nullptr) (void)Destroy(h_);
+        h_ = nullptr;
+    }
+    H get() const { return h_; }
+    operator H() const { return h_; }
+    H *put()   // where a create call writes the new handle
+    {
+        reset();
+        return &h_;
+    }
+
+  private:
+    H h_ = nullptr;
+};
+// The throw-away device buffer of a test hook (hooks.cpp, q8_host.cpp, kv8_host.cpp: host pointers in, one launch, host
+// pointers out): the owner type, made with at least one byte and, from != null, filled from the host
+template <class T> struct HookBuf {
+    Owned<T> p;
+    int alloc(size_t bytes) { return p.make(bytes ? bytes : 1, "test hook buffer"); }
+    int put(const void *from, size_t bytes)
+    {
+        L2Z_TRY(alloc(bytes));
+        if (from != nullptr && bytes > 0) L2Z_HIP(hipMemcpy(p, from, bytes, hipMemcpyHostToDevice));
+        return L2Z_OK;
+    }
+};
+
+using OwnedEvent = OwnedHandle<hipEvent_t, hipEventDestroy>;
+using OwnedGraphExec = OwnedHandle<hipGraphExec_t, hipGraphExecDestroy>;
 
 // ----- shard geometry (DESIGN.md "Sharding"; world == 1 -> everything local) -----
 struct Shard {
@@ -143,54 +187,62 @@ struct l2z_runstate {
     hipStream_t stream = nullptr;
     // main.zig:119-135 (k, v, xb2, hb2, logits_indexed have no device twin:
     // k/v go straight into the cache rows, xb2/hb2 are fused away)
-    float *x = nullptr, *xb = nullptr, *hb = nullptr, *q = nullptr, *logits = nullptr;
-    float *part = nullptr;    // scheme B: this rank's partial [dim] output of wo / w2 (rank 0's includes the residual), summed by the all-reduce
-    float *key_cache = nullptr, *value_cache = nullptr;   // (a paged runstate has neither)
+    l2z::Owned<float> x, xb, hb, q, logits;
+    l2z::Owned<float> part;    // scheme B: this rank's partial [dim] output of wo / w2 (rank 0's includes the residual), summed by the all-reduce
+    l2z::Owned<float> key_cache, value_cache;   // (a paged runstate has neither)
     // l2z_runstate_init_paged: the pool the KV rows live in, this sequence's page table on the host, and its device
     // copy with the pinned twin the copy is made from (pages_dirty: the table changed since the last copy was enqueued)
     l2z_kvpool *pool = nullptr;
     l2z::KvSeq pg;
-    int32_t *d_pages = nullptr, *h_pages = nullptr;
+    l2z::Owned<int32_t> d_pages;
+    l2z::Pinned<int32_t> h_pages;
     bool pages_dirty = false;
     // l2z_runstate_init_kv8 (kv8_layout.h): the KV rows as int8 values [layer][kv head][seq_len][head_size] and
     // one f32 scale per (layer, kv head, position), in place of key_cache / value_cache, which such a runstate does not have
-    int8_t *k8 = nullptr, *v8 = nullptr;
-    float *ks8 = nullptr, *vs8 = nullptr;
+    l2z::Owned<int8_t> k8, v8;
+    l2z::Owned<float> ks8, vs8;
     bool is_kv8() const { return k8 != nullptr; }
-    float2 *rope = nullptr;  // (seq_len, head_size/2) {cos, sin}
+    l2z::Owned<float2> rope;  // (seq_len, head_size/2) {cos, sin}
     // loop state on the device
-    int *d_token = nullptr, *d_pos = nullptr, *d_prompt = nullptr, *d_n_prompt = nullptr;
-    int *d_out_tokens = nullptr, *d_argmax = nullptr;
+    l2z::Owned<int> d_token, d_pos, d_prompt, d_n_prompt;
+    l2z::Owned<int> d_out_tokens, d_argmax;
     // batched prefill scratch (allocated on first l2z_prefill): [kPrefillChunk, dim|hidden]
-    float *pf_x = nullptr, *pf_xn = nullptr, *pf_q = nullptr, *pf_att = nullptr;
-    float *pf_h1 = nullptr;
+    l2z::Owned<float> pf_x, pf_xn, pf_q, pf_att;
+    l2z::Owned<float> pf_h1;
     int pf_ld_xn = 0, pf_ld_att = 0, pf_ld_h1 = 0;   // row pitches of pf_xn / pf_att / pf_h1 (prefill_host.cpp pf_ld: zero-padded)
-    float *pf_stage = nullptr;  // sharded: [world][P, n_loc] blocks of the matrix being gathered
-    float *pf_part = nullptr;   // scheme B: this rank's partial [P, dim] product of its column shard of Wo / W2
-    int *pf_tokens = nullptr;
+    l2z::Owned<float> pf_stage;  // sharded: [world][P, n_loc] blocks of the matrix being gathered
+    l2z::Owned<float> pf_part;   // scheme B: this rank's partial [P, dim] product of its column shard of Wo / W2
+    l2z::Owned<int> pf_tokens;
     l2z::DeferredSum pf_pending = {nullptr, 1, 128, 1, false};   // K ranges' sums of Wo / W2 the next rmsnorm launch adds (prefill_host.cpp)
     l2z::PlanesReady pf_planes_att = l2z::PLANES_SPLIT, pf_planes_h1 = l2z::PLANES_SPLIT;   // whether the attention output's / the gated rows' planes stand (prefill_host.cpp)
-    l2z::SplitKWs pf_sk = {nullptr, nullptr, 0, 0, nullptr, 0, nullptr, 0};  // split-K workspace of the tile GEMM (chunks of <= 256 tokens)
+    // split-K workspace of the tile GEMM (chunks of <= 256 tokens): what the launchers are handed, written once the owners
+    // beside it hold all of it -- the planes with the chunk scratch, the K ranges' sums and counters once (pf_sk_cap: 0 or 1)
+    l2z::SplitKWs pf_sk = {nullptr, nullptr, 0, 0, nullptr, 0, nullptr, 0};
+    l2z::Owned<void> pf_sk_x3, pf_sk_x3b;
+    l2z::Owned<float> pf_sk_part;
+    l2z::Owned<int> pf_sk_cnt;
+    int pf_sk_cap = 0;
     int pf_cap = 0;             // tokens per chunk the scratch above was allocated for
     // l2z_score (prefill_host.cpp; allocated on the first call, a runstate that never scores holds none of it):
     // sc_ws: one allocation per chunk capacity -- the [sc_cap, sc_slab_n] logits slab, the segments' partials, the targets' logits;
     // sc_seq: targets, log-probs and top-1 ids of a whole call (seq_len each), copied to the host once per call
-    void *sc_ws = nullptr, *sc_seq = nullptr;
+    l2z::Owned<void> sc_ws, sc_seq;
     size_t sc_ws_bytes = 0;
     int sc_cap = 0, sc_slab_n = 0;   // tokens per chunk / vocabulary columns per slab sc_ws was allocated for
     int sc_slab_force = 0;           // l2z_score_slab_set (tests): columns per slab, 0: by the workspace budget
-    float *d_probs = nullptr;     // l2z_probs_read: softmax(logits / temperature), allocated on first use
-    float *h_stage = nullptr;     // ... and its pinned host landing buffer
+    l2z::Owned<float> d_probs;     // l2z_probs_read: softmax(logits / temperature), allocated on first use
+    l2z::Pinned<float> h_stage;     // ... and its pinned host landing buffer
     // l2z_sample_run (allocated on the first call, a runstate that never samples in the loop holds none of it): what the
     // sampled step's last node reads -- {temperature, top_p}, then one coin per position (2 + seq_len floats) --, its pinned
     // host twin, and the row body's scratch (sample_scratch_floats(vocab))
-    float *d_smp_ctl = nullptr, *h_smp_ctl = nullptr, *d_smp_scratch = nullptr;
-    float *d_part_val = nullptr;  // classifier launch's per-block argmax candidates
-    int *d_part_idx = nullptr;
+    l2z::Owned<float> d_smp_ctl, d_smp_scratch;
+    l2z::Pinned<float> h_smp_ctl;
+    l2z::Owned<float> d_part_val;  // classifier launch's per-block argmax candidates
+    l2z::Owned<int> d_part_idx;
     int n_part = 0;               // 0: argmax scans the logits instead
     int n_part_step = 0, n_part_fwd = 0;  // ... as left by the captured step / forward graphs (a shard's differ)
-    float *d_attn_part = nullptr; // split attention: per (head, chunk) partials
-    int *d_attn_cnt = nullptr;    // split attention: arrivals per local head (zero between launches)
+    l2z::Owned<float> d_attn_part; // split attention: per (head, chunk) partials
+    l2z::Owned<int> d_attn_cnt;    // split attention: arrivals per local head (zero between launches)
     int attn_nch = 0;             // 0: one block per head at every position
     int attn_split_pos = 0;       // positions >= this use the split form (host picks the graph)
     int attn_short_pos = 0;       // positions < this use the 256-thread speculative one-block-per-head form
@@ -198,15 +250,15 @@ struct l2z_runstate {
     // graphs, keyed by the uid of the weights they were captured with (a freed object's address
     // is commonly handed to the next one)
     uint64_t graph_w_uid = 0;
-    hipGraphExec_t g_forward[4] = {nullptr, nullptr, nullptr, nullptr}, g_step[4] = {nullptr, nullptr, nullptr, nullptr};  // [attention variant]
-    hipGraphExec_t g_sample[4] = {nullptr, nullptr, nullptr, nullptr};  // the sampled step's, each captured on its first sampled step (forward.cpp ensure_graph)
+    l2z::OwnedGraphExec g_forward[4], g_step[4];  // [attention variant]
+    l2z::OwnedGraphExec g_sample[4];  // the sampled step's, each captured on its first sampled step (forward.cpp ensure_graph)
     bool use_graphs = true;
     int host_pos = 0;   // next position the greedy loop will run
     bool done = false;  // greedy loop saw BOS
     std::vector<int32_t> h_prompt;  // host copy of the greedy loop's prompt (prefill path)
     // peer-write transport: device copies of the four gathers' descriptions (xb, x, hb, logits) for
     // the kernels that push their outputs to the peers themselves (MatvecArgs::push)
-    l2z::P2pArgs *d_push = nullptr;
+    l2z::Owned<l2z::P2pArgs> d_push;
     int n_gathers = 0;        // collectives per forward pass at world > 1: 4 gathers per layer + logits (scheme B: 2 all-reduces per layer + logits)
     bool ll_consume = false;  // peer-write transport, consumer side: mat-vecs read their gathered input
                               // as LL words from the landing slot; no gather launch except the logits
@@ -221,17 +273,17 @@ struct l2z_runstate {
     bool packed_w = true;          // L2Z_PACKED_W at creation: decode mat-vecs stream the weights' packed copy where it exists
     int packed_kinds = -1;         // L2Z_PACKED_KINDS at creation: bit k = launches of kind k may take it
     int tl_attn_seq = 0;           // attention launches enqueued so far (AttnArgs::tl_seq, measurement builds)
-    l2z::BatchScratch *bt = nullptr;  // batched decode scratch of the calls that name this runstate first (batch_host.cpp)
+    std::unique_ptr<l2z::BatchScratch, l2z::BatchScratchDelete> bt;  // batched decode scratch of the calls that name this runstate first (batch_host.cpp)
     // l2z_prefill_batch scratch of the calls that name this runstate first (prefill_batch_host.cpp): a chunk's key / value
     // rows [rg_cap, kv_dim] between their product and the scatter into the sequences' caches, and the chunk's table
-    float *rg_k = nullptr, *rg_v = nullptr;
-    void *rg_tab = nullptr;
+    l2z::Owned<float> rg_k, rg_v;
+    l2z::Owned<void> rg_tab;
     int rg_cap = 0;
     // l2z_prefill_q8 scratch (q8_host.cpp; allocated on the first call): one allocation, carved for chunks of up to
     // q8pf_cap rows at group size q8pf_gs
-    void *q8pf = nullptr;
+    l2z::Owned<void> q8pf;
     int q8pf_cap = 0, q8pf_gs = 0;
-    l2z::WideScratch *wd = nullptr;   // l2z_transformer_wide / l2z_wide_run scratch of the calls that name this runstate first (wide_host.cpp)
+    std::unique_ptr<l2z::WideScratch, l2z::WideScratchDelete> wd;   // l2z_transformer_wide / l2z_wide_run scratch of the calls that name this runstate first (wide_host.cpp)
 };
 
 namespace l2z {
@@ -302,16 +354,14 @@ inline size_t kv_page_floats(const l2z_runstate *s) { return s->pool != nullptr 
 int kv_release(l2z_runstate *s, int n_pos);
 // rows 0 .. n_pos - 1 of src's caches -> dst's, on dst's stream, either of them paged (both paged: rows r0 .. only)
 int kv_copy_rows(l2z_runstate *dst, const l2z_runstate *src, int r0, int n_pos);
-void kv_runstate_free(l2z_runstate *s);   // l2z_runstate_free's part: pages back, tables freed, the pool's count down
+// l2z_runstate_free's part for a paged runstate (pool null: nothing): its pages back, the pool's count down
+void kv_runstate_free(l2z_kvpool *pool, KvSeq &pg);
 
 // kv8_host.cpp: l2z_runstate_fork's rows into a runstate with int8 KV rows, on dst's stream: rows 0 .. n_pos - 1 of every
 // layer copied (src of the same kind) or quantized (src contiguous f32: kv8_scatter.hip's slice function)
 int kv8_fork_rows(l2z_runstate *dst, const l2z_runstate *src, int n_pos);
 
-// batch_host.cpp
-void batch_free(l2z_runstate *s);
 // wide_host.cpp
-void wide_free(l2z_runstate *s);
 // l2z_verify_logits_read: row `row` of the logits matrix of s's last l2z_verify_wide call as states[0] (null: s's last verify
 // call was not that, or the matrix has no such row); and the end of that: another call has taken the matrix or s's turn
 const float *wide_verify_row(const l2z_runstate *s, int row);

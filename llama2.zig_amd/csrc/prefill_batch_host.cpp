@@ -22,19 +22,10 @@ size_t tab_bytes(int cap) { return kRaggedMaxSeq * sizeof(RaggedSeq) + (size_t)c
 // (l2z_step_mixed takes rg_k / rg_v from here too: wide_host.cpp)
 int l2z::ragged_alloc(l2z_runstate *s, int need)
 {
-    if (s->rg_cap >= need) return L2Z_OK;
-    const size_t P = (size_t)(need + 511) / 512 * 512;   // as prefill_alloc
+    const size_t P = (size_t)round_cap(need, 512);   // as prefill_alloc
     const size_t kvd = (size_t)s->sh.kvd_loc;
-    L2Z_HIP(hipStreamSynchronize(s->stream));
-    void **bufs[] = {(void **)&s->rg_k, (void **)&s->rg_v, &s->rg_tab};
-    for (void **b : bufs)
-        if (*b) { (void)hipFree(*b); *b = nullptr; }
-    s->rg_cap = 0;
-    // (after a failure, what was allocated is freed with the runstate)
-    L2Z_TRY(alloc_all("l2z_prefill_batch scratch",
-                      {{(void **)&s->rg_k, P * kvd * 4}, {(void **)&s->rg_v, P * kvd * 4}, {&s->rg_tab, tab_bytes((int)P)}}));
-    s->rg_cap = (int)P;
-    return L2Z_OK;
+    return grow("l2z_prefill_batch scratch", &s->rg_cap, need, 512, nullptr, 0, [&] { return drain_stream(s); },
+                {{s->rg_k, P * kvd * 4}, {s->rg_v, P * kvd * 4}, {s->rg_tab, tab_bytes((int)P)}});
 }
 
 extern "C" int l2z_prefill_batch(int n, const int32_t *tokens, const int32_t *n_tokens, const int32_t *pos0,
@@ -64,7 +55,8 @@ extern "C" int l2z_prefill_batch(int n, const int32_t *tokens, const int32_t *n_
     // ---- the pass, on states[0]'s stream: it waits for every runstate's stream ... ----
     L2Z_TRY(batch_alloc(s0));  // (the events)
     L2Z_TRY(kv_attach("l2z_prefill_batch", n, states, pos0, n_tokens, 0));   // (paged runstates: the last refusal)
-    L2Z_TRY(join_streams(s0->bt, n, states));
+    StreamScope pass(s0->bt.get(), n, states);
+    L2Z_TRY(pass.joined());
     L2Z_TRY(kv_upload(n, states, st));
     int first[kRaggedMaxSeq];   // a sequence's first row among the concatenated rows
     for (int j = 0, g = 0; j < n; g += n_tokens[j], j++) first[j] = g;
@@ -97,7 +89,7 @@ extern "C" int l2z_prefill_batch(int n, const int32_t *tokens, const int32_t *n_
         std::stable_sort(tiles.begin(), tiles.end(), [](const Tile &a, const Tile &b) { return a.keys > b.keys; });
         L2Z_CHECK(tiles.size() <= tab_tiles_max(s0->rg_cap), L2Z_ERR_INVALID, "l2z_prefill_batch: tile table overflow");
         for (size_t i = 0; i < tiles.size(); i++) h_tiles[i] = make_int2(tiles[i].slot, tiles[i].q0);
-        unsigned char *d_tab = (unsigned char *)s0->rg_tab;
+        unsigned char *d_tab = (unsigned char *)s0->rg_tab.get();
         RaggedChunk rg = {};
         rg.seq = (const RaggedSeq *)d_tab;
         rg.row_seq = (const int *)(d_tab + ((unsigned char *)h_row_seq - h_tab.data()));
@@ -118,7 +110,7 @@ extern "C" int l2z_prefill_batch(int n, const int32_t *tokens, const int32_t *n_
     }
     // ---- ... and every runstate's stream waits for the pass: the usual final rmsnorm + classifier launch (:426-429) of
     // each runstate, on its own stream, leaves its logits in place ----
-    L2Z_TRY(release_streams(s0->bt, n, states));
+    L2Z_TRY(pass.release());
     int last_pos[kRaggedMaxSeq], last_tok[kRaggedMaxSeq];
     for (int j = 0; j < n; j++) {
         l2z_runstate *s = states[j];

@@ -38,63 +38,53 @@ int pf_ld(int n)
 int prefill_alloc(l2z_runstate *s, int need)
 {
     const l2z_config &c = s->cfg;
-    if (s->pf_cap >= need) return L2Z_OK;
     // first use, or a longer chunk than any before (a prompt of >= 1024 tokens; L2Z_PF_CHUNK through
     // l2z_option_set): start over, in steps of 512 tokens
-    const size_t P = (size_t)(need + 511) / 512 * 512;
-    L2Z_HIP(hipStreamSynchronize(s->stream));
-    float **bufs[] = {&s->pf_x, &s->pf_xn, &s->pf_q, &s->pf_att, &s->pf_h1, &s->pf_stage, &s->pf_part};
-    for (float **b : bufs)
-        if (*b) { (void)hipFree(*b); *b = nullptr; }
-    if (s->pf_tokens) { (void)hipFree(s->pf_tokens); s->pf_tokens = nullptr; }
-    if (s->pf_sk.x3) { (void)hipFree(s->pf_sk.x3); s->pf_sk.x3 = nullptr; s->pf_sk.x3_bytes = 0; }
-    if (s->pf_sk.x3b) { (void)hipFree(s->pf_sk.x3b); s->pf_sk.x3b = nullptr; s->pf_sk.x3b_bytes = 0; }
-    s->pf_cap = 0;
+    const size_t P = (size_t)round_cap(need, 512);
     const size_t widest = (size_t)(c.dim > c.hidden_dim ? c.dim : c.hidden_dim);
     // (scheme B reads the local attention / hidden blocks as rows of the column shards' PADDED width: a 1-rank group's
     // padded width can exceed the model's)
     const size_t att_w = (size_t)pf_ld(std::max(c.dim, s->sh.scheme_b ? s->sh.dimc_pad : 0));
     const size_t h1_w = (size_t)pf_ld(std::max(c.hidden_dim, s->sh.scheme_b ? s->sh.hidc_pad : 0));
     const size_t xn_w = (size_t)pf_ld(c.dim);
-    s->pf_ld_xn = (int)xn_w; s->pf_ld_att = (int)att_w; s->pf_ld_h1 = (int)h1_w;
-    // (after a failure, what was allocated is freed with the runstate, or on the next attempt)
-    L2Z_TRY(alloc_all("prefill scratch", {
-        {(void **)&s->pf_x, P * c.dim * 4},   {(void **)&s->pf_xn, P * xn_w * 4},
-        {(void **)&s->pf_q, P * c.dim * 4},   {(void **)&s->pf_att, P * att_w * 4},
-        {(void **)&s->pf_h1, P * h1_w * 4},
-        // sharded: [world][P, n / world] blocks of the matrix being gathered
-        {(void **)&s->pf_stage, s->sh.world > 1 ? P * widest * 4 : 0},
-        // scheme B: this rank's partial [P, dim] products of its column shards of Wo / W2 (summed by the bulk all-reduce)
-        {(void **)&s->pf_part, s->sh.scheme_b ? P * c.dim * 4 : 0},
-        {(void **)&s->pf_tokens, P * 4},
-        // the tile GEMM on the bf16 matrix cores: one launch's activation matrix as three planes of bf16 terms
-        {(void **)&s->pf_sk.x3, P * 3 * std::max(std::max(xn_w, att_w), h1_w) * 2},
-        // ... and the gated hidden rows' planes, written by the W1 | W3 launch while it reads its own (unsharded pass)
-        {(void **)&s->pf_sk.x3b, s->sh.world > 1 ? 0 : P * 3 * h1_w * 2}}));
-    s->pf_cap = (int)P;
-    s->pf_sk.x3_bytes = P * 3 * std::max(std::max(xn_w, att_w), h1_w) * 2;
-    s->pf_sk.x3b_bytes = s->sh.world > 1 ? 0 : P * 3 * h1_w * 2;
-    // the pad columns are never written and must be zeros: the GEMMs multiply them against whatever follows a W row
-    // (scheme B: against the column shards' own zero columns)
-    L2Z_HIP(hipMemsetAsync(s->pf_xn, 0, P * xn_w * 4, s->stream));
-    L2Z_HIP(hipMemsetAsync(s->pf_att, 0, P * att_w * 4, s->stream));
-    L2Z_HIP(hipMemsetAsync(s->pf_h1, 0, P * h1_w * 4, s->stream));
-    if (s->pf_sk.part == nullptr) {
-        // split-K family of the tile GEMM (chunks of 33 ... 256 tokens): accumulator dumps of up to 4 K ranges of
-        // the widest launch of a layer (q | k | v, or W1 | W3 side by side), one arrival counter per output tile
-        const Shard &sh = s->sh;
-        const size_t widest_launch = std::max((size_t)sh.dim_loc + 2 * (size_t)sh.kvd_loc, 2 * (size_t)sh.hid_loc) + 128;
-        const size_t floats = (size_t)kPanelWsRows * widest_launch;  // (the split-K family needs 4 kSplitKMaxTokens rows of it)
-        const int n_cnt = 1 << 16;
-        hipError_t e = hipMalloc((void **)&s->pf_sk.part, floats * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&s->pf_sk.cnt, (size_t)n_cnt * 4);
-        if (e == hipSuccess) e = hipMemset(s->pf_sk.cnt, 0, (size_t)n_cnt * 4);
-        if (e != hipSuccess) {
-            set_error("prefill split-K workspace allocation failed: %s", hipGetErrorString(e));
-            return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
-        }
-        s->pf_sk.part_floats = floats;
-        s->pf_sk.cnt_ints = n_cnt;
+    // the tile GEMM on the bf16 matrix cores: one launch's activation matrix as three planes of bf16 terms, and the gated
+    // hidden rows' planes, written by the W1 | W3 launch while it reads its own (unsharded pass)
+    const size_t x3_bytes = P * 3 * std::max(std::max(xn_w, att_w), h1_w) * 2, x3b_bytes = s->sh.world > 1 ? 0 : P * 3 * h1_w * 2;
+    bool remade = false;
+    L2Z_TRY(grow("prefill scratch", &s->pf_cap, need, 512, nullptr, 0, [&] { return drain_stream(s); },
+                 {{s->pf_x, P * c.dim * 4}, {s->pf_xn, P * xn_w * 4}, {s->pf_q, P * c.dim * 4}, {s->pf_att, P * att_w * 4},
+                  {s->pf_h1, P * h1_w * 4},
+                  // sharded: [world][P, n / world] blocks of the matrix being gathered
+                  {s->pf_stage, s->sh.world > 1 ? P * widest * 4 : 0},
+                  // scheme B: this rank's partial [P, dim] products of its column shards of Wo / W2 (summed by the bulk all-reduce)
+                  {s->pf_part, s->sh.scheme_b ? P * c.dim * 4 : 0},
+                  {s->pf_tokens, P * 4}, {s->pf_sk_x3, x3_bytes}, {s->pf_sk_x3b, x3b_bytes}},
+                 &remade));
+    if (remade) {   // (what describes the scratch is written now that it stands)
+        s->pf_ld_xn = (int)xn_w; s->pf_ld_att = (int)att_w; s->pf_ld_h1 = (int)h1_w;
+        s->pf_sk.x3 = s->pf_sk_x3; s->pf_sk.x3_bytes = x3_bytes;
+        s->pf_sk.x3b = s->pf_sk_x3b; s->pf_sk.x3b_bytes = x3b_bytes;
+        // the pad columns are never written and must be zeros: the GEMMs multiply them against whatever follows a W row
+        // (scheme B: against the column shards' own zero columns)
+        L2Z_HIP(hipMemsetAsync(s->pf_xn, 0, P * xn_w * 4, s->stream));
+        L2Z_HIP(hipMemsetAsync(s->pf_att, 0, P * att_w * 4, s->stream));
+        L2Z_HIP(hipMemsetAsync(s->pf_h1, 0, P * h1_w * 4, s->stream));
+    }
+    // split-K family of the tile GEMM (chunks of 33 ... 256 tokens): accumulator dumps of up to 4 K ranges of the widest
+    // launch of a layer (q | k | v, or W1 | W3 side by side), one arrival counter per output tile.  Made once, a group of
+    // its own: a call that could not make it is not done, and the next one tries again
+    const Shard &sh = s->sh;
+    const size_t widest_launch = std::max((size_t)sh.dim_loc + 2 * (size_t)sh.kvd_loc, 2 * (size_t)sh.hid_loc) + 128;
+    const size_t floats = (size_t)kPanelWsRows * widest_launch;  // (the split-K family needs 4 kSplitKMaxTokens rows of it)
+    const int n_cnt = 1 << 16;
+    L2Z_TRY(grow("prefill split-K workspace", &s->pf_sk_cap, 1, 1, nullptr, 0, [] { return L2Z_OK; },
+                 {{s->pf_sk_part, floats * 4}, {s->pf_sk_cnt, (size_t)n_cnt * 4}}, &remade));
+    if (remade) {
+        const hipError_t e = hipMemset(s->pf_sk_cnt, 0, (size_t)n_cnt * 4);
+        if (e != hipSuccess) drop(&s->pf_sk_cap, nullptr, {{s->pf_sk_part, 0}, {s->pf_sk_cnt, 0}});   // (never kept unzeroed)
+        L2Z_HIP(e);
+        s->pf_sk.part = s->pf_sk_part; s->pf_sk.part_floats = floats;
+        s->pf_sk.cnt = s->pf_sk_cnt; s->pf_sk.cnt_ints = n_cnt;
     }
     return L2Z_OK;
 }
@@ -522,22 +512,14 @@ int score_alloc(l2z_runstate *s, int need)
         const size_t n_slabs = (nseg * kScoreSeg + cols - 1) / cols;
         cols = (nseg + n_slabs - 1) / n_slabs * kScoreSeg;
     }
-    if (s->sc_seq == nullptr) {
-        L2Z_HIP(hipMalloc(&s->sc_seq, (size_t)c.seq_len * 3 * 4));
-    }
-    if (s->sc_ws != nullptr && cap == (size_t)s->sc_cap && cols == (size_t)s->sc_slab_n) return L2Z_OK;
+    L2Z_TRY(s->sc_seq.make((size_t)c.seq_len * 3 * 4, "l2z_score sequence arrays"));
     const size_t bytes = cap * cols * 4 + cap * nseg * 12 + cap * 4;
     L2Z_CHECK(bytes <= kScoreWsMaxBytes, L2Z_ERR_INVALID,
               "l2z_score: chunks of %zu tokens need a %zu-byte workspace (limit %zu): lower L2Z_PF_CHUNK", cap, bytes, kScoreWsMaxBytes);
-    L2Z_HIP(hipStreamSynchronize(s->stream));
-    if (s->sc_ws) { (void)hipFree(s->sc_ws); s->sc_ws = nullptr; s->sc_cap = 0; s->sc_slab_n = 0; s->sc_ws_bytes = 0; }
-    hipError_t e = hipMalloc(&s->sc_ws, bytes);
-    if (e != hipSuccess) {
-        s->sc_ws = nullptr;
-        set_error("score workspace allocation (%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
-    }
-    s->sc_cap = (int)cap; s->sc_slab_n = (int)cols; s->sc_ws_bytes = bytes;
+    // (cap never falls below the capacity held: the workspace is remade for a longer chunk or another slab width)
+    L2Z_TRY(grow("score workspace", &s->sc_cap, (int)cap, 512, &s->sc_slab_n, (int)cols, [&] { return drain_stream(s); },
+                 {{s->sc_ws, bytes}}));
+    s->sc_ws_bytes = bytes;
     return L2Z_OK;
 }
 
@@ -590,7 +572,7 @@ int score_chunk(l2z_runstate *s, const l2z_weights *w, const ScoreCall *sc, int 
     hipStream_t st = s->stream;
     const int nseg = score_nseg(s->cfg);
     L2Z_CHECK(s->sc_ws != nullptr && P <= s->sc_cap, L2Z_ERR_INVALID, "l2z_score: no workspace for a chunk of %d tokens", P);
-    float *slab = (float *)s->sc_ws;
+    float *slab = (float *)s->sc_ws.get();
     ScoreArgs a = {};
     a.slab = slab; a.ld = s->sc_slab_n; a.P = P; a.nseg = nseg;
     a.part_m = slab + (size_t)s->sc_cap * s->sc_slab_n;
@@ -794,7 +776,7 @@ extern "C" int l2z_score(const int32_t *tokens, int n_tokens, int pos0, const in
         done += P;
     }
     L2Z_TRY(score_alloc(s, longest));
-    int *d_targets = (int *)s->sc_seq;
+    int *d_targets = (int *)s->sc_seq.get();
     float *d_logprob = (float *)(d_targets + config->seq_len);
     int *d_top1 = (int *)(d_logprob + config->seq_len);
     const ScoreCall sc = {targets ? d_targets : nullptr, out_logprob ? d_logprob : nullptr, out_top1 ? d_top1 : nullptr};
@@ -883,7 +865,7 @@ extern "C" int l2z_emu_prefill(int n_ranks, l2z_runstate *const *ss, const l2z_w
                     L2Z_HIP(hipStreamSynchronize(ss[r]->stream));
                 }
                 const StageOut o0 = stage_out(ss[0], k);
-                L2Z_TRY(exchange((size_t)P * o0.n_loc, [](l2z_runstate *s) { return s->pf_stage; }));
+                L2Z_TRY(exchange((size_t)P * o0.n_loc, [](l2z_runstate *s) { return s->pf_stage.get(); }));
                 for (int r = 0; r < n_ranks; r++) {
                     const StageOut o = stage_out(ss[r], k);
                     BulkArgs a = {};
@@ -907,7 +889,7 @@ extern "C" int l2z_emu_prefill(int n_ranks, l2z_runstate *const *ss, const l2z_w
         L2Z_TRY(prefill_classifier(ss[r], ws[r]));
     }
     L2Z_TRY(sync_all());
-    L2Z_TRY(exchange((size_t)ss[0]->sh.v_loc, [](l2z_runstate *s) { return s->logits; }));
+    L2Z_TRY(exchange((size_t)ss[0]->sh.v_loc, [](l2z_runstate *s) { return s->logits.get(); }));
     for (int r = 0; r < n_ranks; r++) ss[r]->host_pos = pos0 + n_tokens;
     return L2Z_OK;
 }

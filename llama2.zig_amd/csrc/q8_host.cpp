@@ -106,7 +106,7 @@ Q8Pf q8pf_carve(const l2z_runstate *s, int gs, size_t cap)
 {
     const l2z_config &c = s->cfg;
     const size_t dim = c.dim, hid = c.hidden_dim, kvd = s->sh.kvd_loc, widest = std::max(dim, hid);
-    uint8_t *base = (uint8_t *)s->q8pf;
+    uint8_t *base = (uint8_t *)s->q8pf.get();
     size_t off = 0;
     const auto take = [&](size_t bytes) {
         uint8_t *p = base + off;
@@ -136,16 +136,9 @@ Q8Pf q8pf_carve(const l2z_runstate *s, int gs, size_t cap)
 
 int q8pf_alloc(l2z_runstate *s, int gs, int need)
 {
-    if (s->q8pf != nullptr && s->q8pf_cap >= need && s->q8pf_gs == gs) return L2Z_OK;
-    const size_t cap = (size_t)(need + 511) / 512 * 512;   // as prefill_alloc (a multiple of the GEMM's tile)
-    L2Z_HIP(hipStreamSynchronize(s->stream));
-    if (s->q8pf) { (void)hipFree(s->q8pf); s->q8pf = nullptr; }
-    s->q8pf_cap = 0;
-    const size_t bytes = q8pf_carve(s, gs, cap).bytes;
-    L2Z_TRY(alloc_all("l2z_prefill_q8 scratch", {{&s->q8pf, bytes}}));
-    s->q8pf_cap = (int)cap;
-    s->q8pf_gs = gs;
-    return L2Z_OK;
+    const size_t cap = (size_t)round_cap(need, 512);   // as prefill_alloc (a multiple of the GEMM's tile)
+    return grow("l2z_prefill_q8 scratch", &s->q8pf_cap, need, 512, &s->q8pf_gs, gs, [&] { return drain_stream(s); },
+                {{s->q8pf, q8pf_carve(s, gs, cap).bytes}});
 }
 
 // A chunk's launch between its q | k | v products and its attention -- q [P, dim] rotated in place, the chunk's k / v rows
@@ -359,14 +352,6 @@ int l2z::wide_step_q8(int n, l2z_runstate *s0, const l2z_weights *w, const Ragge
 
 // ---------------------------------------------------------------------------
 // The pass's two launches on their own (host pointers, synchronous)
-namespace {
-struct DevBytes {
-    void *p = nullptr;
-    ~DevBytes() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) { L2Z_HIP(hipMalloc(&p, bytes ? bytes : 1)); return L2Z_OK; }
-};
-}  // namespace
-
 extern "C" int l2z_q8_quantize_rows(const float *x, int m, size_t n, const float *rms_w, int gs, int8_t *out_q, float *out_s)
 {
     L2Z_CHECK(x && out_q && out_s && m > 0 && m <= (1 << 20) && n > 0 && n < (1u << 24), L2Z_ERR_INVALID, "l2z_q8_quantize_rows: bad arguments");
@@ -374,15 +359,15 @@ extern "C" int l2z_q8_quantize_rows(const float *x, int m, size_t n, const float
               "l2z_q8_quantize_rows: group size %d (32 or 64, dividing n = %zu)", gs, n);
     L2Z_TRY(ensure_device(current_device_for(nullptr)));
     const size_t mp = (size_t)q8_gemm_rows_padded(m), ng = n / (size_t)gs;
-    DevBytes dx, dw, dq, ds;
+    HookBuf<void> dx, dw, dq, ds;
     L2Z_TRY(dx.alloc((size_t)m * n * 4)); L2Z_TRY(dw.alloc(n * 4)); L2Z_TRY(dq.alloc(mp * n)); L2Z_TRY(ds.alloc(mp * ng * 4));
-    L2Z_HIP(hipMemcpy(dx.p, x, (size_t)m * n * 4, hipMemcpyHostToDevice));
-    if (rms_w) L2Z_HIP(hipMemcpy(dw.p, rms_w, n * 4, hipMemcpyHostToDevice));
-    L2Z_HIP(launch_q8_quantize_rows((const float *)dx.p, (int)n, m, (int)n, rms_w ? (const float *)dw.p : nullptr, gs, (int8_t *)dq.p,
-                                    (float *)ds.p, nullptr));
+    L2Z_HIP(hipMemcpy(dx.p.get(), x, (size_t)m * n * 4, hipMemcpyHostToDevice));
+    if (rms_w) L2Z_HIP(hipMemcpy(dw.p.get(), rms_w, n * 4, hipMemcpyHostToDevice));
+    L2Z_HIP(launch_q8_quantize_rows((const float *)dx.p.get(), (int)n, m, (int)n, rms_w ? (const float *)dw.p.get() : nullptr, gs, (int8_t *)dq.p.get(),
+                                    (float *)ds.p.get(), nullptr));
     L2Z_HIP(hipDeviceSynchronize());
-    L2Z_HIP(hipMemcpy(out_q, dq.p, (size_t)m * n, hipMemcpyDeviceToHost));
-    L2Z_HIP(hipMemcpy(out_s, ds.p, (size_t)m * ng * 4, hipMemcpyDeviceToHost));
+    L2Z_HIP(hipMemcpy(out_q, dq.p.get(), (size_t)m * n, hipMemcpyDeviceToHost));
+    L2Z_HIP(hipMemcpy(out_s, ds.p.get(), (size_t)m * ng * 4, hipMemcpyDeviceToHost));
     return L2Z_OK;
 }
 
@@ -403,26 +388,26 @@ int q8_gemm_hook(const char *fn, bool wide, int epi, float *out, const int8_t *x
     L2Z_CHECK(epi != EPI_SWIGLU || d % 8 == 0, L2Z_ERR_INVALID, "%s: d = %zu (SwiGLU: a multiple of 8, the gated rows' pitch one of 4)", fn, d);
     L2Z_TRY(ensure_device(current_device_for(nullptr)));
     const size_t mp = (size_t)q8_gemm_rows_padded(m), ng = n / (size_t)gs;
-    DevBytes dxq, dxs, dwq, dws, dout;
+    HookBuf<void> dxq, dxs, dwq, dws, dout;
     L2Z_TRY(dxq.alloc(mp * n)); L2Z_TRY(dxs.alloc(mp * ng * 4)); L2Z_TRY(dwq.alloc(d * n)); L2Z_TRY(dws.alloc(d * ng * 4));
     const size_t out_bytes = (size_t)m * (epi == EPI_SWIGLU ? d / 2 : d) * 4;
     L2Z_TRY(dout.alloc((size_t)m * d * 4));
-    if (epi == EPI_RESID) L2Z_HIP(hipMemcpy(dout.p, out, out_bytes, hipMemcpyHostToDevice));
+    if (epi == EPI_RESID) L2Z_HIP(hipMemcpy(dout.p.get(), out, out_bytes, hipMemcpyHostToDevice));
     // the rows stand padded to whole tiles, the pad rows zero, as the row launch leaves them
-    L2Z_HIP(hipMemset(dxq.p, 0, mp * n));
-    L2Z_HIP(hipMemset(dxs.p, 0, mp * ng * 4));
-    L2Z_HIP(hipMemcpy(dxq.p, xq, (size_t)m * n, hipMemcpyHostToDevice));
-    L2Z_HIP(hipMemcpy(dxs.p, xs, (size_t)m * ng * 4, hipMemcpyHostToDevice));
-    L2Z_HIP(hipMemcpy(dwq.p, wq, d * n, hipMemcpyHostToDevice));
-    L2Z_HIP(hipMemcpy(dws.p, ws, d * ng * 4, hipMemcpyHostToDevice));
+    L2Z_HIP(hipMemset(dxq.p.get(), 0, mp * n));
+    L2Z_HIP(hipMemset(dxs.p.get(), 0, mp * ng * 4));
+    L2Z_HIP(hipMemcpy(dxq.p.get(), xq, (size_t)m * n, hipMemcpyHostToDevice));
+    L2Z_HIP(hipMemcpy(dxs.p.get(), xs, (size_t)m * ng * 4, hipMemcpyHostToDevice));
+    L2Z_HIP(hipMemcpy(dwq.p.get(), wq, d * n, hipMemcpyHostToDevice));
+    L2Z_HIP(hipMemcpy(dws.p.get(), ws, d * ng * 4, hipMemcpyHostToDevice));
     Q8GemmArgs a = {};
-    a.xq = (const int8_t *)dxq.p; a.xs = (const float *)dxs.p; a.wq = (const int8_t *)dwq.p; a.ws = (const float *)dws.p;
-    a.out = (float *)dout.p; a.ldo = (int)(epi == EPI_SWIGLU ? d / 2 : d);
+    a.xq = (const int8_t *)dxq.p.get(); a.xs = (const float *)dxs.p.get(); a.wq = (const int8_t *)dwq.p.get(); a.ws = (const float *)dws.p.get();
+    a.out = (float *)dout.p.get(); a.ldo = (int)(epi == EPI_SWIGLU ? d / 2 : d);
     a.res = a.out; a.ldres = a.ldo;
     a.m = m; a.n = (int)n; a.d = (int)d; a.gs = gs;
     L2Z_HIP(wide ? launch_q8_gemm_wide(a, epi, nullptr) : launch_q8_gemm(a, epi, nullptr));
     L2Z_HIP(hipDeviceSynchronize());
-    L2Z_HIP(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
+    L2Z_HIP(hipMemcpy(out, dout.p.get(), out_bytes, hipMemcpyDeviceToHost));
     return L2Z_OK;
 }
 }  // namespace

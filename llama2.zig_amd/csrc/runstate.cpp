@@ -13,6 +13,19 @@
 using namespace l2z;
 
 // ---------------------------------------------------------------------------
+// owned.h's two raw functions: every scratch buffer of a runstate comes from here and goes back here
+int l2z::raw_alloc(Mem kind, void **p, size_t bytes, const char *what)
+{
+    const hipError_t e = kind == Mem::Pinned ? hipHostMalloc(p, bytes, hipHostMallocDefault) : hipMalloc(p, bytes);
+    if (e == hipSuccess) return L2Z_OK;
+    *p = nullptr;
+    set_error("%s allocation (%zu bytes) failed: %s", what, bytes, hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
+}
+
+void l2z::raw_free(Mem kind, void *p) { (void)(kind == Mem::Pinned ? hipHostFree(p) : hipFree(p)); }
+
+// ---------------------------------------------------------------------------
 // src/main.zig:137 RunState.init; pool != null (l2z_runstate_init_paged): no caches, a page table instead; kv8
 // (l2z_runstate_init_kv8): no f32 caches, the four arrays of kv8_layout.h instead
 static int runstate_make(const l2z_config *config, const l2z_comm *comm, l2z_kvpool *pool, l2z_runstate **out, bool kv8 = false)
@@ -65,40 +78,41 @@ static int runstate_make(const l2z_config *config, const l2z_comm *comm, l2z_kvp
 
     const size_t kv = (size_t)c.n_layers * c.seq_len * sh.kvd_loc;
     hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
-    auto alloc = [&](void **p, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc(p, bytes ? bytes : 4);
-        if (e == hipSuccess) e = hipMemset(*p, 0, bytes ? bytes : 4);
+    int rc = L2Z_OK;   // (the first allocation that fails; e: the first other call)
+    auto alloc = [&](auto &p, size_t bytes) {
+        if (e == hipSuccess && rc == L2Z_OK) rc = p.make(bytes ? bytes : 4, "RunState");
+        if (e == hipSuccess && rc == L2Z_OK) e = hipMemset(p, 0, bytes ? bytes : 4);
     };
-    alloc((void **)&s->x, (size_t)c.dim * 4);
+    alloc(s->x, (size_t)c.dim * 4);
     // (+ 256: scheme B's column-shard mat-vecs read their local slice padded to the shard's row width; the pad stays zero)
-    alloc((void **)&s->xb, ((size_t)c.dim + 256) * 4);
-    alloc((void **)&s->hb, ((size_t)c.hidden_dim + 256) * 4);
-    if (sh.scheme_b) alloc((void **)&s->part, (size_t)c.dim * 4);
-    alloc((void **)&s->q, (size_t)c.dim * 4);
-    alloc((void **)&s->logits, (size_t)c.vocab_size * 4);
+    alloc(s->xb, ((size_t)c.dim + 256) * 4);
+    alloc(s->hb, ((size_t)c.hidden_dim + 256) * 4);
+    if (sh.scheme_b) alloc(s->part, (size_t)c.dim * 4);
+    alloc(s->q, (size_t)c.dim * 4);
+    alloc(s->logits, (size_t)c.vocab_size * 4);
     if (kv8) {
-        alloc((void **)&s->k8, kv);
-        alloc((void **)&s->v8, kv);
-        alloc((void **)&s->ks8, kv / (size_t)sh.hs * 4);
-        alloc((void **)&s->vs8, kv / (size_t)sh.hs * 4);
+        alloc(s->k8, kv);
+        alloc(s->v8, kv);
+        alloc(s->ks8, kv / (size_t)sh.hs * 4);
+        alloc(s->vs8, kv / (size_t)sh.hs * 4);
     } else if (pool == nullptr) {
-        alloc((void **)&s->key_cache, kv * 4);
-        alloc((void **)&s->value_cache, kv * 4);
+        alloc(s->key_cache, kv * 4);
+        alloc(s->value_cache, kv * 4);
     } else {
         s->pg.init(c.seq_len);
-        alloc((void **)&s->d_pages, s->pg.pages.size() * 4);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&s->h_pages, s->pg.pages.size() * 4, hipHostMallocDefault);
+        alloc(s->d_pages, s->pg.pages.size() * 4);
+        if (e == hipSuccess && rc == L2Z_OK) rc = s->h_pages.make(s->pg.pages.size() * 4, "RunState page table");
         s->pages_dirty = true;   // (the first pass uploads the table whatever it attaches)
     }
-    alloc((void **)&s->rope, (size_t)c.seq_len * (sh.hs / 2) * sizeof(float2));
-    alloc((void **)&s->d_token, 4);
-    alloc((void **)&s->d_pos, 4);
-    alloc((void **)&s->d_n_prompt, 4);
-    alloc((void **)&s->d_argmax, 4);
-    alloc((void **)&s->d_prompt, (size_t)c.seq_len * 4);
-    alloc((void **)&s->d_out_tokens, (size_t)c.seq_len * 4);
-    alloc((void **)&s->d_part_val, (size_t)matvec_max_grid(g_cus) * 4);
-    alloc((void **)&s->d_part_idx, (size_t)matvec_max_grid(g_cus) * 4);
+    alloc(s->rope, (size_t)c.seq_len * (sh.hs / 2) * sizeof(float2));
+    alloc(s->d_token, 4);
+    alloc(s->d_pos, 4);
+    alloc(s->d_n_prompt, 4);
+    alloc(s->d_argmax, 4);
+    alloc(s->d_prompt, (size_t)c.seq_len * 4);
+    alloc(s->d_out_tokens, (size_t)c.seq_len * 4);
+    alloc(s->d_part_val, (size_t)matvec_max_grid(g_cus) * 4);
+    alloc(s->d_part_idx, (size_t)matvec_max_grid(g_cus) * 4);
     {   // Attention form by position.  One block per head is fastest while the
         // context is short; from pos 256 on, the split form (nch blocks per head + combine)
         // wins and keeps winning (2.4x at pos 2047 on the 7B shape); below it the one-block form runs
@@ -120,11 +134,11 @@ static int runstate_make(const l2z_config *config, const l2z_comm *comm, l2z_kvp
         if (nch > 1 && s->attn_short_pos > s->attn_split_pos) s->attn_short_pos = s->attn_split_pos;
         if (nch > 1) {
             s->attn_nch = nch;
-            alloc((void **)&s->d_attn_part, attention_split_part_floats(sh.heads_loc, sh.hs, nch) * 4);
-            alloc((void **)&s->d_attn_cnt, (size_t)sh.heads_loc * 4);
+            alloc(s->d_attn_part, attention_split_part_floats(sh.heads_loc, sh.hs, nch) * 4);
+            alloc(s->d_attn_cnt, (size_t)sh.heads_loc * 4);
         }
     }
-    if (comm_uses_p2p(comm) && e == hipSuccess) {
+    if (comm_uses_p2p(comm) && e == hipSuccess && rc == L2Z_OK) {
         // consumer-side gathers need every producer to push and every consumer to read LL words:
         // the vector mat-vec kernels and the vector attention kernels
         AttnArgs aa = {};
@@ -139,16 +153,16 @@ static int runstate_make(const l2z_config *config, const l2z_comm *comm, l2z_kvp
         comm_p2p_args(comm, sh.scheme_b ? s->part : s->x, sh.scheme_b ? (size_t)c.dim : (size_t)sh.dim_loc, s->ll_consume, &t[1]);
         comm_p2p_args(comm, s->hb, (size_t)sh.hid_loc, s->ll_consume, &t[2]);
         comm_p2p_args(comm, s->logits, (size_t)sh.v_loc, false, &t[3]);
-        alloc((void **)&s->d_push, sizeof t);
-        if (e == hipSuccess) e = hipMemcpy(s->d_push, t, sizeof t, hipMemcpyHostToDevice);
+        alloc(s->d_push, sizeof t);
+        if (e == hipSuccess && rc == L2Z_OK) e = hipMemcpy(s->d_push, t, sizeof t, hipMemcpyHostToDevice);
         // greedy steps end in the candidate exchange where the classifier takes the vector kernels (their fused
         // argmax epilogue) and the slots hold the 2 * world words
         s->xchg_steps = tn.argmax_xchg != 0 && matvec_vector_width(c.dim) && sh.v_loc >= 2 && comm->slot_floats >= 2 * (size_t)sh.world;
     }
-    if (e != hipSuccess) {
-        set_error("RunState allocation failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess || rc != L2Z_OK) {
+        if (e != hipSuccess) set_error("RunState allocation failed: %s", hipGetErrorString(e));
         l2z_runstate_free(s);
-        return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
+        return rc != L2Z_OK ? rc : e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
     }
     // RoPE table: exactly main.zig:338-342 evaluated once per (pos, pair) on the host in f32
     // -- freq = 1/pow(10000, (i % hs)/hs); val = pos*freq; cos(val), sin(val) -- instead of
@@ -211,29 +225,15 @@ extern "C" void l2z_runstate_free(l2z_runstate *s)
     if (!s) return;
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
-    for (int v = 0; v < l2z::ATTN_VARIANTS; v++) {
-        if (s->g_forward[v]) (void)hipGraphExecDestroy(s->g_forward[v]);
-        if (s->g_step[v]) (void)hipGraphExecDestroy(s->g_step[v]);
-        if (s->g_sample[v]) (void)hipGraphExecDestroy(s->g_sample[v]);
-    }
-    void *ptrs[] = {s->x, s->xb, s->hb, s->q, s->logits, s->key_cache, s->value_cache, s->rope,
-                    s->d_token, s->d_pos, s->d_prompt, s->d_n_prompt, s->d_out_tokens, s->d_argmax,
-                    s->d_probs, s->d_part_val, s->d_part_idx, s->d_attn_part, s->d_attn_cnt, s->pf_x, s->pf_xn, s->pf_q,
-                    s->pf_att, s->pf_h1, s->pf_stage, s->pf_part, s->pf_tokens, s->d_push, s->pf_sk.part, s->pf_sk.cnt, s->pf_sk.x3, s->pf_sk.x3b, s->part, s->sc_ws, s->sc_seq,
-                    s->rg_k, s->rg_v, s->rg_tab, s->q8pf, s->d_smp_ctl, s->d_smp_scratch, s->k8, s->v8, s->ks8, s->vs8};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    if (s->h_stage) (void)hipHostFree(s->h_stage);
-    if (s->h_smp_ctl) (void)hipHostFree(s->h_smp_ctl);
-    if (s->pool == nullptr) {   // (a paged runstate whose allocation failed half way: the pool does not know it yet)
-        if (s->d_pages) (void)hipFree(s->d_pages);
-        if (s->h_pages) (void)hipHostFree(s->h_pages);
-    }
-    l2z::kv_runstate_free(s);
-    l2z::batch_free(s);
-    l2z::wide_free(s);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
+    // the graphs first, then every buffer and the side scratch (the members free themselves), the pages back to the pool (one
+    // that does not know this runstate yet -- its allocation failed half way -- is not set), and the stream last
+    l2z::drop_graphs(s);
+    const hipStream_t stream = s->stream;
+    l2z_kvpool *pool = s->pool;
+    l2z::KvSeq pg = std::move(s->pg);
     delete s;
+    l2z::kv_runstate_free(pool, pg);
+    if (stream) (void)hipStreamDestroy(stream);
 }
 
 // Which structure this runstate runs (a test that asks for an option checks here that it got it): bit 3 sharding

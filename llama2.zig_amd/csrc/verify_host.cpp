@@ -95,8 +95,8 @@ int verify_enqueue(const char *fn, const int32_t *tokens, int n, int pos0, const
     L2Z_TRY(check_tokens(fn, "", tokens, n, config->vocab_size));
     if (draw.sampled()) L2Z_TRY(check_coins(fn, draw.coins, 0, n));
     L2Z_TRY(verify_scratch(s, draw.sampled()));
-    if (q8) L2Z_TRY(q8_batch_alloc(s, w->q8_gs));
-    BatchScratch *b = s->bt;
+    BatchScratch *b = s->bt.get();
+    if (q8) L2Z_TRY(q8_rows_alloc("batched q8 step scratch", s, b, kBatchMax, w->q8_gs));
     const int vocab = config->vocab_size;
     BatchTable t = {};
     for (int i = 0; i < n; i++) {
@@ -136,7 +136,7 @@ int verify_call(const char *fn, const int32_t *tokens, int n, int pos0, const Ve
     L2Z_CHECK(out_next != nullptr && out_accepted != nullptr, L2Z_ERR_INVALID, "%s: null argument", fn);
     L2Z_TRY(check_draw(fn, -1, draw.temperature, draw.top_p, draw.coins));
     L2Z_TRY(verify_enqueue(fn, tokens, n, pos0, draw, config, s, w, q8));
-    BatchScratch *b = s->bt;
+    BatchScratch *b = s->bt.get();
     L2Z_HIP(hipStreamSynchronize(s->stream));
     memcpy(out_next, b->h_vout, (size_t)n * 4);
     *out_accepted = b->h_vout[n];
@@ -267,7 +267,7 @@ extern "C" int l2z_verify_batch(int n, const int32_t *tokens, const int32_t *n_t
     }
     l2z_runstate *s0 = states[0];
     L2Z_TRY(verify_scratch(s0, sampled));
-    BatchScratch *b = s0->bt;
+    BatchScratch *b = s0->bt.get();
     const int vocab = config->vocab_size;
     // ---- the step's table (a row per position) and the row groups (one per sequence) ----
     BatchTable t = {};
@@ -291,7 +291,8 @@ extern "C" int l2z_verify_batch(int n, const int32_t *tokens, const int32_t *n_t
         }
     }
     hipStream_t st = s0->stream;
-    L2Z_TRY(join_streams(b, n, states));
+    StreamScope pass(b, n, states);
+    L2Z_TRY(pass.joined());
     L2Z_TRY(upload_table(b, t, st, &g, sizeof g));
     const VerifyGroupTable *d_groups = (const VerifyGroupTable *)b->d_behind;
     VerifyBatchAttnArgs a = verify_attention_args<VerifyBatchAttnArgs>(*config, b);
@@ -305,7 +306,7 @@ extern "C" int l2z_verify_batch(int n, const int32_t *tokens, const int32_t *n_t
     L2Z_TRY(verify_ids(b, sampled, vocab, R, st));
     L2Z_HIP(launch_verify_batch_accept(b->d_tab, d_groups, b->v_logits, vocab, b->d_vout, R, n, st));
     L2Z_HIP(hipMemcpyAsync(b->h_vout, b->d_vout, (size_t)(R + n) * 4, hipMemcpyDeviceToHost, st));
-    L2Z_TRY(release_streams(b, n, states));
+    L2Z_TRY(pass.release());
     for (int j = 0; j < n; j++) verify_done(states[j], j == 0 ? R : 0);  // the matrix is states[0]'s
     L2Z_HIP(hipStreamSynchronize(st));
     memcpy(out_next, b->h_vout, (size_t)R * 4);
@@ -355,7 +356,7 @@ int verify_tree_enqueue(const int32_t *tokens, const int32_t *parent, int n, int
     L2Z_TRY(check_positions(fn, "", "cache rows", pos0, n, config->seq_len));
     L2Z_TRY(check_tokens(fn, "", tokens, n, config->vocab_size));
     L2Z_TRY(verify_scratch(s, draw.sampled()));
-    BatchScratch *b = s->bt;
+    BatchScratch *b = s->bt.get();
     const int vocab = config->vocab_size;
     const size_t hs = (size_t)config->dim / config->n_heads;
     BatchTable t = {};
@@ -401,7 +402,7 @@ extern "C" int l2z_verify_tree(const int32_t *tokens, const int32_t *parent, int
     L2Z_CHECK(out_next != nullptr && out_path != nullptr && out_accepted != nullptr, L2Z_ERR_INVALID,
               "l2z_verify_tree: null argument");
     L2Z_TRY(verify_tree_enqueue(tokens, parent, n_nodes, pos0, temperature, top_p, coins, config, s, w));
-    BatchScratch *b = s->bt;
+    BatchScratch *b = s->bt.get();
     L2Z_HIP(hipStreamSynchronize(s->stream));
     const int a = b->h_vout[n_nodes];
     memcpy(out_next, b->h_vout, (size_t)n_nodes * 4);

@@ -30,53 +30,44 @@ namespace l2z {
 // rows' next ids, the device table with its pinned twin, and the events that order the pass against up to kWideMax
 // streams (BatchScratch's are kBatchMax).
 struct WideScratch {
-    float *k = nullptr, *v = nullptr;   // [kWideMax, kv_dim]
-    float *logits = nullptr;            // [kWideMax, ld_logits]
+    Owned<float> k, v;                  // [kWideMax, kv_dim]
+    Owned<float> logits;                // [kWideMax, ld_logits]
     int ld_logits = 0;                  // vocab_size rounded up to 4: every row 16-byte aligned
-    float *part = nullptr;              // wide_part_floats
+    Owned<float> part;                  // wide_part_floats
     int seg_cap = 0;
-    int *d_next = nullptr, *h_next = nullptr;   // [2 kWideMax]: the rows' ids; l2z_verify_wide: next[0 .. R) | accepted[0 .. n)
-    WideTable *d_tab = nullptr, *h_tab = nullptr;   // with room for l2z_verify_wide's WideVerdictCtl behind
+    Owned<int> d_next;                  // [2 kWideMax]: the rows' ids; l2z_verify_wide: next[0 .. R) | accepted[0 .. n)
+    Pinned<int> h_next;
+    Owned<WideTable> d_tab;             // with room for l2z_verify_wide's WideVerdictCtl behind
+    Pinned<WideTable> h_tab;
     int v_rows = 0;                     // rows of the logits matrix l2z_verify_logits_read may read: the last call was l2z_verify_wide
-    hipEvent_t ev_in[kWideMax] = {};
-    hipEvent_t ev_done = nullptr;
-    hipEvent_t ev_upload = nullptr;     // the last table copy: the pinned table may be rewritten once it has completed
+    OwnedEvent ev_in[kWideMax];
+    OwnedEvent ev_done;
+    OwnedEvent ev_upload;               // the last table copy: the pinned table may be rewritten once it has completed
     // l2z_wide_run (each on the first call that needs it): a call's temperature | top_p ([kWideMax] each) | coins and its
     // ids, [n_steps, n] both, on the device and pinned, sized on demand; the sampler's scratch of kWideMax rows
-    float *d_ctl = nullptr, *h_ctl = nullptr;
-    int *d_ids = nullptr, *h_ids = nullptr;
-    size_t run_cap = 0;                 // entries of coins / ids the four buffers hold
-    float *smp = nullptr;               // kWideMax rows of sample_scratch_floats(vocab)
-    // l2z_step_mixed (on the first such call): its own table, kMixedSeqMax sequences and kMixedRowsMax rows, and the pinned twin
-    MixedTable *d_mtab = nullptr, *h_mtab = nullptr;
+    Owned<float> d_ctl;
+    Pinned<float> h_ctl;
+    Owned<int> d_ids;
+    Pinned<int> h_ids;
+    int run_cap = 0;                    // entries of coins / ids the four buffers hold
+    Owned<float> smp;                   // kWideMax rows of sample_scratch_floats(vocab)
+    // l2z_step_mixed (on the first such call): its own table, kMixedSeqMax sequences and kMixedRowsMax rows, and the pinned
+    // twin (mtab_cap: 0 or 1, both are there)
+    Owned<MixedTable> d_mtab;
+    Pinned<MixedTable> h_mtab;
+    int mtab_cap = 0;
     // l2z_transformer_wide_q8 (on the first such call): the step's quantized rows, [kWideMax, max(dim, hidden_dim)] int8, and
-    // their scales at group size q8_gs (a call with another group size re-makes them)
-    int8_t *q8_xq = nullptr;
-    float *q8_xs = nullptr;
-    int q8_gs = 0;
+    // their scales at group size q8_gs (a call with another group size re-makes them; q8_cap: 0 or 1, both are there)
+    Owned<int8_t> q8_xq;
+    Owned<float> q8_xs;
+    int q8_cap = 0, q8_gs = 0;
 };
 
-void wide_free(l2z_runstate *s)
-{
-    WideScratch *b = s->wd;
-    if (b == nullptr) return;
-    void *ptrs[] = {b->k, b->v, b->logits, b->part, b->d_next, b->d_tab, b->d_ctl, b->d_ids, b->smp, b->d_mtab, b->q8_xq, b->q8_xs};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    void *pinned[] = {b->h_next, b->h_tab, b->h_ctl, b->h_ids, b->h_mtab};
-    for (void *p : pinned)
-        if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : b->ev_in)
-        if (e) (void)hipEventDestroy(e);
-    if (b->ev_done) (void)hipEventDestroy(b->ev_done);
-    if (b->ev_upload) (void)hipEventDestroy(b->ev_upload);
-    delete b;
-    s->wd = nullptr;
-}
+void WideScratchDelete::operator()(WideScratch *b) const { delete b; }
 
 const float *wide_verify_row(const l2z_runstate *s, int row)
 {
-    const WideScratch *b = s->wd;
+    const WideScratch *b = s->wd.get();
     return b != nullptr && row >= 0 && row < b->v_rows ? b->logits + (size_t)row * b->ld_logits : nullptr;
 }
 
@@ -98,86 +89,47 @@ int wide_alloc(l2z_runstate *s)
 {
     if (s->wd != nullptr) return L2Z_OK;
     const l2z_config &c = s->cfg;
-    WideScratch *b = new WideScratch();
-    s->wd = b;
+    // built here, the runstate's only once all of it stands: a failure below frees what there is with `made`
+    std::unique_ptr<WideScratch, WideScratchDelete> made(new WideScratch());
+    WideScratch *b = made.get();
     const size_t R = kWideMax, kvd = (size_t)s->sh.kvd_loc;
     b->ld_logits = (c.vocab_size + 3) / 4 * 4;
     b->seg_cap = verify_segments(c.seq_len);
-    int rc = alloc_all("l2z_transformer_wide scratch",
-                       {{(void **)&b->k, R * kvd * 4}, {(void **)&b->v, R * kvd * 4}, {(void **)&b->logits, R * b->ld_logits * 4},
-                        {(void **)&b->part, wide_part_floats(c.n_heads, b->seg_cap, s->sh.hs) * 4},
-                        {(void **)&b->d_next, 2 * R * 4}, {(void **)&b->d_tab, kTabBytes}});
-    auto hip = [&rc](hipError_t e) {
-        if (rc == L2Z_OK && e != hipSuccess) {
-            set_error("l2z_transformer_wide scratch: %s", hipGetErrorString(e));
-            rc = L2Z_ERR_HIP;
-        }
-    };
-    hip(hipHostMalloc((void **)&b->h_tab, kTabBytes, hipHostMallocDefault));
-    hip(hipHostMalloc((void **)&b->h_next, 2 * R * 4, hipHostMallocDefault));
-    for (hipEvent_t &e : b->ev_in) hip(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    hip(hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
-    hip(hipEventCreateWithFlags(&b->ev_upload, hipEventDisableTiming));
-    if (rc != L2Z_OK) wide_free(s);  // the next call starts over
-    return rc;
+    int cap = 0;
+    L2Z_TRY(grow("l2z_transformer_wide scratch", &cap, 1, 1, nullptr, 0, [] { return L2Z_OK; },
+                 {{b->k, R * kvd * 4}, {b->v, R * kvd * 4}, {b->logits, R * b->ld_logits * 4},
+                  {b->part, wide_part_floats(c.n_heads, b->seg_cap, s->sh.hs) * 4}, {b->d_next, 2 * R * 4}, {b->d_tab, kTabBytes},
+                  {b->h_tab, kTabBytes}, {b->h_next, 2 * R * 4}}));
+    for (OwnedEvent &e : b->ev_in) L2Z_HIP(hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
+    L2Z_HIP(hipEventCreateWithFlags(b->ev_done.put(), hipEventDisableTiming));
+    L2Z_HIP(hipEventCreateWithFlags(b->ev_upload.put(), hipEventDisableTiming));
+    s->wd = std::move(made);
+    return L2Z_OK;
 }
 
 // the sampler's row body's scratch for kWideMax rows (a call in which some sequence draws)
 int sampler_alloc(l2z_runstate *s)
 {
-    return alloc_all("wide sampler scratch", {{(void **)&s->wd->smp, (size_t)kWideMax * sample_scratch_floats(s->cfg.vocab_size) * 4}});
+    return s->wd->smp.make((size_t)kWideMax * sample_scratch_floats(s->cfg.vocab_size) * 4, "wide sampler scratch");
 }
 
 // what an l2z_wide_run call of `entries` = n_steps * n ids needs beyond the step's own
-int run_alloc(l2z_runstate *s, size_t entries)
+int run_alloc(l2z_runstate *s, int entries)
 {
-    WideScratch *b = s->wd;
-    if (entries <= b->run_cap) return L2Z_OK;
-    // (every earlier run has completed: the call is synchronous)
-    if (b->d_ctl) (void)hipFree(b->d_ctl);
-    if (b->d_ids) (void)hipFree(b->d_ids);
-    if (b->h_ctl) (void)hipHostFree(b->h_ctl);
-    if (b->h_ids) (void)hipHostFree(b->h_ids);
-    b->d_ctl = b->h_ctl = nullptr;
-    b->d_ids = b->h_ids = nullptr;
-    b->run_cap = 0;
-    const size_t cap = (entries + 4095) / 4096 * 4096, ctl = (2 * (size_t)kWideMax + cap) * 4;
-    hipError_t e = hipMalloc((void **)&b->d_ctl, ctl);
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_ids, cap * 4);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_ctl, ctl, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_ids, cap * 4, hipHostMallocDefault);
-    if (e != hipSuccess) {  // (what was allocated is freed on the next attempt)
-        set_error("l2z_wide_run coins / ids allocation (%zu bytes) failed: %s", ctl + cap * 4, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? L2Z_ERR_OOM : L2Z_ERR_HIP;
-    }
-    b->run_cap = cap;
-    return L2Z_OK;
+    WideScratch *b = s->wd.get();
+    const size_t cap = (size_t)round_cap(entries, 4096), ctl = (2 * (size_t)kWideMax + cap) * 4;
+    // (nothing to drain: every earlier run has completed, the call is synchronous)
+    return grow("l2z_wide_run coins / ids", &b->run_cap, entries, 4096, nullptr, 0, [] { return L2Z_OK; },
+                {{b->d_ctl, ctl}, {b->d_ids, cap * 4}, {b->h_ctl, ctl}, {b->h_ids, cap * 4}});
 }
 
 // l2z_step_mixed's own table, and the chunk's key / value rows before the scatter (WideScratch's hold kWideMax rows only)
 int mixed_alloc(l2z_runstate *s, int R)
 {
-    WideScratch *b = s->wd;
+    WideScratch *b = s->wd.get();
     L2Z_TRY(ragged_alloc(s, R));
-    if (b->d_mtab != nullptr && b->h_mtab != nullptr) return L2Z_OK;
-    L2Z_TRY(alloc_all("l2z_step_mixed table", {{(void **)&b->d_mtab, sizeof(MixedTable)}}));
-    if (b->h_mtab == nullptr) L2Z_HIP(hipHostMalloc((void **)&b->h_mtab, sizeof(MixedTable), hipHostMallocDefault));
-    return L2Z_OK;
-}
-
-// l2z_transformer_wide_q8's quantized rows and scales (q8_batch_alloc's rule at kWideMax rows)
-int wide_q8_alloc(l2z_runstate *s, int gs)
-{
-    WideScratch *b = s->wd;
-    if (b->q8_xq != nullptr && b->q8_xs != nullptr && b->q8_gs == gs) return L2Z_OK;
-    if (b->q8_gs != gs && (b->q8_xq != nullptr || b->q8_xs != nullptr)) {   // another group size: other scale rows
-        L2Z_HIP(hipStreamSynchronize(s->stream));
-        if (b->q8_xq) { (void)hipFree(b->q8_xq); b->q8_xq = nullptr; }
-        if (b->q8_xs) { (void)hipFree(b->q8_xs); b->q8_xs = nullptr; }
-    }
-    b->q8_gs = gs;
-    const size_t R = kWideMax, widest = (size_t)std::max(s->cfg.dim, s->cfg.hidden_dim);
-    return alloc_all("l2z_transformer_wide_q8 scratch", {{(void **)&b->q8_xq, R * widest}, {(void **)&b->q8_xs, R * (widest / (size_t)gs) * 4}});
+    return grow("l2z_step_mixed table", &b->mtab_cap, 1, 1, nullptr, 0, [] { return L2Z_OK; },
+                {{b->d_mtab, sizeof(MixedTable)}, {b->h_mtab, sizeof(MixedTable)}});
 }
 
 // ---- the frame of a pass: every entry point here is its RaggedCall, the front (check_ragged_call), wide_begin, its own table,
@@ -186,9 +138,9 @@ int wide_q8_alloc(l2z_runstate *s, int gs)
 // What stands between the front and the first launch, on states[0]: its device, the scratch of a chunk of t.R rows and of the
 // wide step, the sampler's where some sequence draws, `more` (the entry's own allocations), the pages of paged runstates --
 // the last refusal --, then the pass's stream joined with every runstate's and the page tables on their way.
-// (A failure after join_streams returns without release_streams: the other runstates' streams are then not ordered behind
-// what was enqueued.  "A refusal changes no state" covers the checks.)
-int wide_begin(const RaggedCall &c, const RaggedTotals &t, FnRef<int()> more)
+// pass: the scope of the pass, made here once the scratch with its events stands; wide_end releases it, and so does its
+// end on every path that does not get there.  ("A refusal changes no state" covers the checks.)
+int wide_begin(const RaggedCall &c, const RaggedTotals &t, FnRef<int()> more, std::optional<StreamScope> &pass)
 {
     l2z_runstate *s0 = c.states[0];
     L2Z_HIP(hipSetDevice(s0->device));
@@ -197,7 +149,8 @@ int wide_begin(const RaggedCall &c, const RaggedTotals &t, FnRef<int()> more)
     if (t.sampled) L2Z_TRY(sampler_alloc(s0));
     L2Z_TRY(more());
     L2Z_TRY(kv_attach(c.fn, c.n, c.states, c.pos0, c.n_tokens, c.n_tokens != nullptr ? 0 : c.n_steps));
-    L2Z_TRY(join_streams(s0->wd, c.n, c.states));
+    pass.emplace(s0->wd.get(), c.n, c.states);
+    L2Z_TRY(pass->joined());
     return kv_upload(c.n, c.states, s0->stream);
 }
 const auto nothing_more = []() -> int { return L2Z_OK; };   // (an entry with no allocations of its own)
@@ -205,9 +158,9 @@ const auto nothing_more = []() -> int { return L2Z_OK; };   // (an entry with no
 // Every runstate's stream waits for the pass, and the host bookkeeping: states[0]'s matrix is this call's now, and a
 // runstate's next position is the one behind its rows and steps (verdict_pending, l2z_verify_wide: known only once the
 // verdict is back; what l2z_verify_logits_read may read is states[0]'s matrix and nothing older)
-int wide_end(const RaggedCall &c, bool verdict_pending = false)
+int wide_end(const RaggedCall &c, StreamScope &pass, bool verdict_pending = false)
 {
-    L2Z_TRY(release_streams(c.states[0]->wd, c.n, c.states));
+    L2Z_TRY(pass.release());
     for (int j = 0; j < c.n; j++) {
         l2z_runstate *s = c.states[j];
         if (!verdict_pending) logits_whole(s, c.pos0[j] + (c.n_tokens != nullptr ? c.n_tokens[j] : 1) + c.n_steps - 1);
@@ -281,13 +234,13 @@ int wide_upload_table(WideScratch *b, const RaggedCall &c, const RaggedTotals &t
 // pf_tokens, written by the step before.
 int wide_step(l2z_runstate *s0, const l2z_weights *w, int n_seq, int R, int deepest, int verify_m, bool from_table, FnRef<int()> last)
 {
-    WideScratch *b = s0->wd;
+    WideScratch *b = s0->wd.get();
     const WideAttn wa = {b->d_tab, b->part, b->seg_cap, deepest / kVerifySeg + 1, verify_m, n_seq, kv_page_floats(s0)};
     const auto layer = [&wa](const RaggedLayer &L, bool *planes_written) {
         return wa.verify_m != 0 ? launch_wide_verify_attention(L, wa, planes_written) : launch_wide_attention(L, wa, planes_written);
     };
     const RaggedAttention attention = layer;
-    RaggedChunk rg = table_chunk(b->d_tab, n_seq, kWideMax, b->k, b->v, s0);
+    RaggedChunk rg = table_chunk(b->d_tab.get(), n_seq, kWideMax, b->k, b->v, s0);
     rg.attention = &attention;
     L2Z_TRY(prefill_ragged_chunk(s0, w, from_table ? b->h_tab->tokens : nullptr, R, rg));
     if (from_table) L2Z_HIP(hipEventRecord(b->ev_upload, s0->stream));
@@ -307,9 +260,10 @@ extern "C" int l2z_transformer_wide(int n, const int32_t *tokens, const int32_t 
                              config, states, w, kWideMax, 0, 0};
     RaggedTotals t;
     L2Z_TRY(check_ragged_call(call, &t));
-    L2Z_TRY(wide_begin(call, t, nothing_more));
+    std::optional<StreamScope> pass;
+    L2Z_TRY(wide_begin(call, t, nothing_more, pass));
     l2z_runstate *s0 = states[0];
-    WideScratch *b = s0->wd;
+    WideScratch *b = s0->wd.get();
     hipStream_t st = s0->stream;
     L2Z_TRY(wide_upload_table(b, call, t));
     L2Z_TRY(wide_step(s0, w, n, n, t.deepest, 0, true, [&]() -> int {
@@ -317,7 +271,7 @@ extern "C" int l2z_transformer_wide(int n, const int32_t *tokens, const int32_t 
         return L2Z_OK;
     }));
     if (out_next) L2Z_HIP(hipMemcpyAsync(b->h_next, b->d_next, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    L2Z_TRY(wide_end(call));
+    L2Z_TRY(wide_end(call, *pass));
     if (out_next) {
         L2Z_HIP(hipStreamSynchronize(st));
         memcpy(out_next, b->h_next, (size_t)n * 4);
@@ -334,9 +288,10 @@ extern "C" int l2z_transformer_wide_q8(int n, const int32_t *tokens, const int32
                              config, states, w, kWideMax, 0, 0, true, "l2z_transformer_wide", true};
     RaggedTotals t;
     L2Z_TRY(check_ragged_call(call, &t));
-    L2Z_TRY(wide_begin(call, t, [&]() { return wide_q8_alloc(states[0], w->q8_gs); }));
+    std::optional<StreamScope> pass;
+    L2Z_TRY(wide_begin(call, t, [&]() { return q8_rows_alloc("l2z_transformer_wide_q8 scratch", states[0], states[0]->wd.get(), kWideMax, w->q8_gs); }, pass));
     l2z_runstate *s0 = states[0];
-    WideScratch *b = s0->wd;
+    WideScratch *b = s0->wd.get();
     hipStream_t st = s0->stream;
     L2Z_TRY(wide_upload_table(b, call, t));
     L2Z_HIP(hipEventRecord(b->ev_upload, st));
@@ -349,7 +304,7 @@ extern "C" int l2z_transformer_wide_q8(int n, const int32_t *tokens, const int32
         return kv8 ? launch_kv8_attention(L, wa, seq8, planes_written) : launch_wide_attention(L, wa, planes_written);
     };
     const RaggedAttention attention = layer;
-    RaggedChunk rg = table_chunk(b->d_tab, n, kWideMax, b->k, b->v, s0);
+    RaggedChunk rg = table_chunk(b->d_tab.get(), n, kWideMax, b->k, b->v, s0);
     rg.attention = &attention;
     const auto scatter8 = [&](float *q, int ldq, int P, size_t layer_off, size_t kv_head_stride, hipStream_t stream) {
         return launch_kv8_rope_scatter(q, ldq, rg, seq8, P, config->dim, s0->sh.kvd_loc, s0->sh.hs, config->seq_len, s0->rope, layer_off,
@@ -360,7 +315,7 @@ extern "C" int l2z_transformer_wide_q8(int n, const int32_t *tokens, const int32
     L2Z_TRY(wide_step_q8(n, s0, w, rg, b->d_tab->tokens, b->q8_xq, b->q8_xs, b->logits, b->ld_logits));
     L2Z_HIP(launch_wide_logits_out(b->logits, b->ld_logits, b->d_tab, config->vocab_size, out_next ? b->d_next : nullptr, n, st));
     if (out_next) L2Z_HIP(hipMemcpyAsync(b->h_next, b->d_next, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    L2Z_TRY(wide_end(call));
+    L2Z_TRY(wide_end(call, *pass));
     if (out_next) {
         L2Z_HIP(hipStreamSynchronize(st));
         memcpy(out_next, b->h_next, (size_t)n * 4);
@@ -381,9 +336,10 @@ extern "C" int l2z_wide_run(int n, const int32_t *first_tokens, const int32_t *p
     RaggedTotals t;
     L2Z_TRY(check_ragged_call(call, &t));
     const size_t entries = (size_t)n_steps * n;
-    L2Z_TRY(wide_begin(call, t, [&]() { return run_alloc(states[0], entries); }));   // (paged runstates: every step's pages, up front)
+    std::optional<StreamScope> pass;
+    L2Z_TRY(wide_begin(call, t, [&]() { return run_alloc(states[0], (int)entries); }, pass));   // (paged runstates: every step's pages, up front)
     l2z_runstate *s0 = states[0];
-    WideScratch *b = s0->wd;
+    WideScratch *b = s0->wd.get();
     hipStream_t st = s0->stream;
 
     // ---- the run: the first step's table and the coins, n_steps steps back to back ----
@@ -411,7 +367,7 @@ extern "C" int l2z_wide_run(int n, const int32_t *first_tokens, const int32_t *p
         }));
     }
     L2Z_HIP(hipMemcpyAsync(b->h_ids, b->d_ids, entries * 4, hipMemcpyDeviceToHost, st));
-    L2Z_TRY(wide_end(call));
+    L2Z_TRY(wide_end(call, *pass));
     L2Z_HIP(hipStreamSynchronize(st));
     memcpy(out_tokens, b->h_ids, entries * 4);
     return L2Z_OK;
@@ -428,9 +384,10 @@ extern "C" int l2z_verify_wide(int n, const int32_t *tokens, const int32_t *n_to
                              config, states, w, kWideMax, kWideMax, kBatchMax};
     RaggedTotals t;
     L2Z_TRY(check_ragged_call(call, &t));
-    L2Z_TRY(wide_begin(call, t, nothing_more));
+    std::optional<StreamScope> pass;
+    L2Z_TRY(wide_begin(call, t, nothing_more, pass));
     l2z_runstate *s0 = states[0];
-    WideScratch *b = s0->wd;
+    WideScratch *b = s0->wd.get();
     hipStream_t st = s0->stream;
     const int R = t.R;
     int m = 1;  // the smallest instantiation that holds the longest sequence
@@ -452,7 +409,7 @@ extern "C" int l2z_verify_wide(int n, const int32_t *tokens, const int32_t *n_to
         return L2Z_OK;
     }));
     L2Z_HIP(hipMemcpyAsync(b->h_next, b->d_next, (size_t)(R + n) * 4, hipMemcpyDeviceToHost, st));
-    L2Z_TRY(wide_end(call, true));
+    L2Z_TRY(wide_end(call, *pass, true));
     L2Z_HIP(hipStreamSynchronize(st));
     b->v_rows = R;  // (only a pass that completed leaves the hook a matrix)
     memcpy(out_next, b->h_next, (size_t)R * 4);
@@ -478,9 +435,10 @@ extern "C" int l2z_step_mixed(int n, const int32_t *tokens, const int32_t *n_tok
     const int R = t.R;
     MixedPlan plan;
     L2Z_CHECK(mixed_plan(n, n_tokens, pos0, &plan) && plan.R == R, L2Z_ERR_INVALID, "l2z_step_mixed: no plan for this layout");
-    L2Z_TRY(wide_begin(call, t, [&]() { return mixed_alloc(states[0], R); }));
+    std::optional<StreamScope> pass;
+    L2Z_TRY(wide_begin(call, t, [&]() { return mixed_alloc(states[0], R); }, pass));
     l2z_runstate *s0 = states[0];
-    WideScratch *b = s0->wd;
+    WideScratch *b = s0->wd.get();
     hipStream_t st = s0->stream;
 
     // ---- the table (rewritten only once the last copy is done): what both tables start with, then the plan's lists and the
@@ -503,7 +461,7 @@ extern "C" int l2z_step_mixed(int n, const int32_t *tokens, const int32_t *n_tok
     // the (row, slot) list for the rest (mixed_step.hip) ----
     const MixedAttn ma = {b->d_mtab, b->part, b->seg_cap, std::max(plan.deepest_dec, 0) / kVerifySeg + 1, plan.n_dec,
                           plan.n_prompt_rows, kv_page_floats(s0)};
-    RaggedChunk rg = table_chunk(b->d_mtab, n, kMixedSeqMax, s0->rg_k, s0->rg_v, s0);
+    RaggedChunk rg = table_chunk(b->d_mtab.get(), n, kMixedSeqMax, s0->rg_k, s0->rg_v, s0);
     rg.tiles = b->d_mtab->tiles; rg.n_tiles = plan.n_tiles;
     rg.att_rows = b->d_mtab->prompt_rows; rg.n_att_rows = plan.n_prompt_rows;
     const auto layer = [&](const RaggedLayer &L, bool *planes_written) { return launch_mixed_attention(L, ma, rg, planes_written); };
@@ -522,7 +480,7 @@ extern "C" int l2z_step_mixed(int n, const int32_t *tokens, const int32_t *n_tok
     if (t.sampled) { d.scratch = b->smp; d.row_stride = sample_scratch_floats(config->vocab_size); }
     L2Z_HIP(launch_mixed_draw_out(d, n, st));
     L2Z_HIP(hipMemcpyAsync(b->h_next, b->d_next, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    L2Z_TRY(wide_end(call));
+    L2Z_TRY(wide_end(call, *pass));
     L2Z_HIP(hipStreamSynchronize(st));
     memcpy(out_next, b->h_next, (size_t)n * 4);
     return L2Z_OK;
