@@ -748,7 +748,7 @@ int l2z_q8_gemm_epi(int epi, int wide, float *out, const int8_t *xq, const float
  * f32 [layer][kv head][seq_len].
  * l2z_runstate_init_kv8: a contiguous, unsharded runstate that holds those four arrays and no f32 caches;
  * l2z_runstate_free frees it.  WHO TAKES IT: l2z_prefill_kv8 (the prompt pass straight into the int8 rows, DESIGN.md 4.29,
- * below); l2z_transformer_wide_q8 (every runstate of the call of this kind, or none:
+ * below); l2z_verify_kv8 (the verify pass over the int8 rows, DESIGN.md 4.31, below); l2z_transformer_wide_q8 (every runstate of the call of this kind, or none:
  * a mixed call is L2Z_ERR_INVALID), whose step then writes the rows through the format's own scatter and reads them
  * through its own attention -- q stays f32, the bytes are converted exactly, a score is (q . k8) * ks / sqrt(head_size),
  * a weighted value fmaf(e * vs, f32(v8), acc), segments of 64 positions and the wide step's combine; a row's result
@@ -801,6 +801,38 @@ int l2z_prefill_kv8(const int32_t *tokens, int n_tokens, int pos0, const l2z_con
                     const l2z_weights *w);
 int l2z_kv8_prefill_attention(int form, float *out, const float *q, int pos0, int P, const int8_t *k8, const float *ks,
                               const int8_t *v8, const float *vs, int n_heads, int n_kv_heads, int head_size, int seq_len);
+
+/* ---- Speculative verify over int8 KV rows (PREVIEW) ----
+ * l2z_verify_kv8: l2z_verify_q8's contract, word for word, on q8 weights and a runstate made by l2z_runstate_init_kv8, under
+ * a name of its own (l2z_verify_q8 keeps refusing such a runstate): 1 .. L2Z_BATCH_MAX consecutive positions of ONE sequence
+ * in one sweep of the weights, the verdict on the device; greedy at temperature 0 with coins NULL, l2z_verify_sample's rule
+ * with a temperature (coins[i]: the coin of position pos0 + i).  ON RETURN rows pos0 .. pos0 + n_tokens - 1 of K8 / KS / V8 /
+ * VS are written in every layer and no other byte or scale; the runstate's logits are row a's, a = *out_accepted; its next
+ * position is pos0 + a + 1; l2z_transformer_wide_q8, l2z_prefill_kv8, the logits-only calls and l2z_runstate_fork go on from
+ * there; l2z_verify_logits_read serves the call's rows.  The call is synchronous.
+ * THE ARITHMETIC is the pass l2z_prefill_kv8 runs for a chunk of those rows, with the classifier as one product over all
+ * rows and with an attention of its own: one block per (kv head, segment of 64 positions) reads the segment's bytes and
+ * scales ONCE and serves every row and query head from them; row i's result is, bit for bit, what l2z_kv8_attention gives a
+ * one-row sequence at position pos0 + i.  STEPPING IDENTITY: every byte and scale the call leaves below the next position,
+ * and every row's logits, are those of l2z_transformer_wide_q8 (n = 1) stepping through the same tokens; so ids, final
+ * logits and rows do not depend on n_tokens, on the guesses or on how positions were cut into calls.
+ * A refusal enqueues nothing and changes nothing.  L2Z_ERR_NO_DEVICE without a device; L2Z_ERR_INVALID for a null argument,
+ * n_tokens outside [1, L2Z_BATCH_MAX], f32 or packed weights, a runstate without int8 KV rows (f32, paged, sharded), a config
+ * other than the objects', a head_size that is no multiple of 4 or above 256, a vocab_size that is no multiple of 4,
+ * l2z_sample_batch's rules for temperature, top_p and the coins; L2Z_ERR_STATE for a position outside [0, seq_len) or a token
+ * outside the vocabulary.
+ * l2z_verify_kv8_time (scripts/kv8_verify_bench.py): the twin of l2z_verify_q8_time.
+ * l2z_kv8_verify_attention: the attention's two launches on their own (host pointers, synchronous, one layer, one sequence),
+ * in l2z_kv8_prefill_attention's layouts: q and out [n, n_heads * head_size] (RoPE applied; row i at position pos0 + i).
+ * Bytes and scales beyond pos0 + n - 1 are never read; those between a row's position and pos0 + n - 1 are read and do not
+ * reach that row, NaN scales included.  L2Z_ERR_INVALID for n outside [1, L2Z_BATCH_MAX] or a shape outside the format;
+ * L2Z_ERR_STATE for positions outside [0, seq_len). */
+int l2z_verify_kv8(const int32_t *tokens, int n_tokens, int pos0, float temperature, float top_p, const float *coins,
+                   const l2z_config *config, l2z_runstate *s, const l2z_weights *w, int32_t *out_next, int *out_accepted);
+int l2z_verify_kv8_time(const int32_t *tokens, int n_tokens, int pos0, float temperature, float top_p, const float *coins,
+                        const l2z_config *config, l2z_runstate *s, const l2z_weights *w, int iters, double *out_ms);
+int l2z_kv8_verify_attention(float *out, const float *q, int pos0, int n, const int8_t *k8, const float *ks, const int8_t *v8,
+                             const float *vs, int n_heads, int n_kv_heads, int head_size, int seq_len);
 
 #ifdef __cplusplus
 }

@@ -148,6 +148,12 @@ def lib():
         i8p = C.POINTER(C.c_int8)
         L.l2z_prefill_kv8.argtypes = [i32p, C.c_int, C.c_int, cfgp, vp, vp]
         L.l2z_kv8_prefill_attention.argtypes = [C.c_int, fp, fp, C.c_int, C.c_int, i8p, fp, i8p, fp, C.c_int, C.c_int, C.c_int, C.c_int]
+    if hasattr(L, "l2z_verify_kv8"):  # the verify pass over int8 KV rows (PREVIEW)
+        i8p = C.POINTER(C.c_int8)
+        L.l2z_verify_kv8.argtypes = [i32p, C.c_int, C.c_int, C.c_float, C.c_float, fp, cfgp, vp, vp, i32p, ip]
+        L.l2z_verify_kv8_time.argtypes = [i32p, C.c_int, C.c_int, C.c_float, C.c_float, fp, cfgp, vp, vp, C.c_int,
+                                          C.POINTER(C.c_double)]
+        L.l2z_kv8_verify_attention.argtypes = [fp, fp, C.c_int, C.c_int, i8p, fp, i8p, fp, C.c_int, C.c_int, C.c_int, C.c_int]
     if hasattr(L, "l2z_q8_matvec_case"):
         L.l2z_q8_matvec_case.argtypes = [C.POINTER(Q8Case)]
     if hasattr(L, "l2z_prefill_q8"):  # their batched prompt pass (PREVIEW)
@@ -427,12 +433,13 @@ class KvPool:
 class RunState:
     """src/main.zig:119 RunState, device resident.  pool: a paged runstate (l2z_runstate_init_paged), which holds no KV
     caches of its own and is taken by the wide family only.  kv8: a runstate whose KV rows are int8 with one f32 scale per
-    (layer, position, kv head) (l2z_runstate_init_kv8), taken by prefill_kv8, transformer_wide_q8 and, as dst, by runstate_fork."""
+    (layer, position, kv head) (l2z_runstate_init_kv8), taken by prefill_kv8, verify_kv8, transformer_wide_q8 and, as dst, by runstate_fork."""
 
     def __init__(self, cfg, comm: Comm | None = None, pool: KvPool | None = None, kv8: bool = False):
         self.cfg = _cfg(cfg)
         self.h = C.c_void_p()
         self.pool = pool   # (kept alive: the pool outlives its runstates)
+        self.kv8 = bool(kv8)
         if kv8:
             assert comm is None and pool is None, "a runstate with int8 KV rows is contiguous and unsharded"
             _chk(lib().l2z_runstate_init_kv8(C.byref(self.cfg), C.byref(self.h)))
@@ -565,6 +572,17 @@ class RunState:
                        coins=None) -> float:
         """l2z_verify_q8_time: milliseconds per verify_q8 pass, device events over `iters` passes (after one untimed)."""
         return self._verify_call("l2z_verify_q8_time", tokens, pos0, w, (temperature, top_p, coins), iters)
+
+    def verify_kv8(self, tokens, pos0: int, w: Weights, temperature: float = 0.0, top_p: float = 1.0, coins=None):
+        """l2z_verify_kv8 (a preview entry point of the test library): verify_q8() on a kv8 runstate, the guessed rows written
+        straight into the int8 arrays and the attention read from them, a segment's bytes once for all rows.  Returns
+        (next: int32[n], accepted)."""
+        return self._verify_call("l2z_verify_kv8", tokens, pos0, w, (temperature, top_p, coins))
+
+    def verify_kv8_time(self, tokens, pos0: int, w: Weights, iters: int, temperature: float = 0.0, top_p: float = 1.0,
+                        coins=None) -> float:
+        """l2z_verify_kv8_time: milliseconds per verify_kv8 pass, device events over `iters` passes (after one untimed)."""
+        return self._verify_call("l2z_verify_kv8_time", tokens, pos0, w, (temperature, top_p, coins), iters)
 
     def verify_tree(self, tokens, parent, pos0: int, w: Weights, temperature: float = 0.0, top_p: float = 1.0, coins=None):
         """l2z_verify_tree (a preview entry point of the test library: include/llama2_hip_test.h): verify() for a TREE of
@@ -1243,13 +1261,15 @@ def speculate_sample(s: RunState, w: Weights, prompt, n_steps: int, k: int, temp
 
 def speculate_q8(s: RunState, w: Weights, prompt, n_steps: int, k: int, drafter=None, temperature=None, top_p=None, coins=None):
     """speculate_greedy's loop (temperature=None) or speculate_sample's on int8 group-quantized weights: RunState.prefill_q8
-    for BOS + prompt, then up to k guessed tokens verified per sweep of the weights by RunState.verify_q8.  Arguments, the
+    for BOS + prompt, then up to k guessed tokens verified per sweep of the weights by RunState.verify_q8 -- on a kv8
+    runstate RunState.prefill_kv8 and RunState.verify_kv8 in their place.  Arguments, the
     coins' convention (coins[g]: the coin of the g-th generated token) and the return value are theirs; the ids do not
     depend on k or on the drafter."""
     _check_guesses("k", k)
     draw = _draw_of(temperature, top_p, coins)
-    return _speculate_one(s, prompt, n_steps, lambda t: s.prefill_q8(t, 0, w),
-                          _chain_round(k, drafter, lambda t, pos, g: s.verify_q8(t, pos, w, *_draw_window(draw, g, len(t)))),
+    prefill, verify = ("prefill_kv8", "verify_kv8") if getattr(s, "kv8", False) else ("prefill_q8", "verify_q8")
+    return _speculate_one(s, prompt, n_steps, lambda t: getattr(s, prefill)(t, 0, w),
+                          _chain_round(k, drafter, lambda t, pos, g: getattr(s, verify)(t, pos, w, *_draw_window(draw, g, len(t)))),
                           draw)
 
 
@@ -1694,6 +1714,22 @@ def kv8_prefill_attention(form: int, q, pos0: int, k8, ks, v8, vs, n_heads: int)
     i8p = C.POINTER(C.c_int8)
     _chk(lib().l2z_kv8_prefill_attention(form, _fp(out), _fp(q), pos0, P, k8.ctypes.data_as(i8p), _fp(ks), v8.ctypes.data_as(i8p),
                                          _fp(vs), n_heads, kvh, hs, S))
+    return out
+
+
+def kv8_verify_attention(q, pos0: int, k8, ks, v8, vs, n_heads: int) -> np.ndarray:
+    """The verify attention over int8 KV rows on its own (l2z_kv8_verify_attention): q [n, n_heads * head_size], n <= BATCH_MAX,
+    row i at position pos0 + i, over ONE sequence's arrays in kv8_prefill_attention's layouts -> out like q.  Row i's bits
+    are kv8_prefill_attention(1, ...)'s."""
+    q, ks, vs = _f32(q), _f32(ks), _f32(vs)
+    k8, v8 = np.ascontiguousarray(k8, dtype=np.int8), np.ascontiguousarray(v8, dtype=np.int8)
+    kvh, S, hs = k8.shape
+    n = q.shape[0]
+    assert q.shape == (n, n_heads * hs) and v8.shape == k8.shape and ks.shape == vs.shape == (kvh, S)
+    out = np.empty_like(q)
+    i8p = C.POINTER(C.c_int8)
+    _chk(lib().l2z_kv8_verify_attention(_fp(out), _fp(q), pos0, n, k8.ctypes.data_as(i8p), _fp(ks), v8.ctypes.data_as(i8p), _fp(vs),
+                                        n_heads, kvh, hs, S))
     return out
 
 

@@ -206,6 +206,16 @@ int batch_step_q8(int n, const l2z_config &c, l2z_runstate *s0, const l2z_weight
 int wide_step_q8(int n, l2z_runstate *s0, const l2z_weights *w, const RaggedChunk &rg, const int *tokens, int8_t *xq, float *xs,
                  float *logits, int ld_logits);
 
+// The verify pass over int8 KV rows on int8 group-quantized weights (l2z_verify_kv8; q8_host.cpp), on s's
+// prompt-pass scratch (verify_kv8_scratch: sized for kBatchMax rows under the grow rule, before anything is enqueued) and
+// stream: n <= kBatchMax rows of s's sequence at positions pos0 .., their ids in tokens (device), the sequence's arrays in
+// seq8[0] (device); every layer's rows pos0 .. pos0 + n - 1 of the int8 arrays are written, the classifier's one product
+// -> logits [n, ld_logits]
+struct Kv8Seq;   // kv8.h
+int verify_kv8_scratch(l2z_runstate *s, const l2z_weights *w);
+int verify_kv8_pass(int n, int pos0, l2z_runstate *s, const l2z_weights *w, const int *tokens, const Kv8Seq *seq8, float *logits,
+                    int ld_logits);
+
 // The rows' draws (l2z_sample_batch's launch) from tab->logits[i] with the table's temperature, top_p and coin -> out[0 .. n)
 hipError_t sample_rows(BatchScratch *b, int vocab, int *out, int n, hipStream_t st);
 

@@ -1,8 +1,9 @@
 // kv8.h -- the launches of the int8 KV cache (kv8_layout.h): the write side (kv8_scatter.hip: RoPE, the
 // slice quantization and the scatter of a chunk's rows; the conversion of f32 cache rows behind l2z_runstate_fork) and the
 // read side (kv8_attention.hip: decode attention of up to kWideMax one-row sequences over int8 rows;
-// kv8_prefill_attention.hip: causal attention of a prompt chunk over one sequence's int8 rows).  Host side: kv8_host.cpp,
-// wide_host.cpp, q8_host.cpp (l2z_prefill_kv8).
+// kv8_prefill_attention.hip: causal attention of a prompt chunk over one sequence's int8 rows; kv8_verify_attention.hip:
+// that of up to kBatchMax guessed rows, a segment's bytes read once for all of them).  Host side: kv8_host.cpp,
+// wide_host.cpp, q8_host.cpp (l2z_prefill_kv8, l2z_verify_kv8's pass), verify_host.cpp (l2z_verify_kv8).
 #pragma once
 #include "wide_decode.h"
 
@@ -32,6 +33,17 @@ hipError_t launch_kv8_quantize_cache(const float *src, int8_t *dst, float *dst_s
 // heads, segment, row), the flash partials per (row, head, segment) in wa.part -- and wide_combine as it stands.  seq8:
 // device, slot i = row i.  Keys beyond wa.tab->pos[i] are never read, nor their scales.
 hipError_t launch_kv8_attention(const RaggedLayer &L, const WideAttn &wa, const Kv8Seq *seq8, bool *planes_written = nullptr);
+
+// ---- the verify attention over int8 rows (kv8_verify_attention.hip) ----
+// Causal attention of rows 0 .. n - 1 (n = L.P <= kBatchMax) of q [n, ldq] (RoPE applied; row i at position pos0 + i) of ONE
+// sequence, seq8[seq] (device), over its rows 0 .. pos0 + n - 1 into out [n, ldo], two launches: kv8_verify_attention --
+// block (kv head, segment) reads the segment's bytes and scales once and serves every row and every query head of the kv
+// head from them, the flash partials per (row, head, segment) in wa.part, the wide step's layout -- and wide_combine as it
+// stands (wa.tab->pos[i] = pos0 + i; wa.n_seg = the segments up to pos0 + n - 1).  Row i's bits are those launch_kv8_attention
+// leaves for a one-row sequence at pos0 + i.  Keys beyond pos0 + n - 1 are never read, nor their scales; a key between a
+// row's position and pos0 + n - 1 is read and does not reach that row.  hipErrorInvalidValue as launch_kv8_attention
+hipError_t launch_kv8_verify_attention(const RaggedLayer &L, const WideAttn &wa, const Kv8Seq *seq8, int seq, int pos0,
+                                       bool *planes_written = nullptr);
 
 // ---- the prompt attention over int8 rows (kv8_prefill_attention.hip) ----
 // The ONE sequence of a prompt chunk as the two forms find it: its arrays (the matrix-core form's kernel arguments) and, on

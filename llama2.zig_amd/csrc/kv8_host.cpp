@@ -1,7 +1,8 @@
 // kv8_host.cpp -- host side of the int8 KV cache beside wide_host.cpp's l2z_transformer_wide_q8 and runstate.cpp's
 // l2z_runstate_init_kv8 / l2z_runstate_read_kv8 (include/llama2_hip_test.h): the rows l2z_runstate_fork
 // puts into such a runstate, the tables the prompt attention's row form reads (l2z_prefill_kv8, q8_host.cpp; DESIGN.md
-// 4.29), and the hooks that run the decode attention's two launches and the prompt attention on their own.
+// 4.29), and the hooks that run the decode attention's two launches, the prompt attention and the verify attention (DESIGN.md
+// 4.31) on their own.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -121,5 +122,40 @@ extern "C" int l2z_kv8_prefill_attention(int form, float *out, const float *q, i
                                          n_heads / n_kv_heads, seq_len, 0, S * hs, nullptr, form));
     L2Z_HIP(hipDeviceSynchronize());
     L2Z_HIP(hipMemcpy(out, dout.p.get(), (size_t)P * dim * 4, hipMemcpyDeviceToHost));
+    return L2Z_OK;
+}
+
+// PREVIEW (include/llama2_hip_test.h): launch_kv8_verify_attention on its own -- host pointers, synchronous, one
+// layer, one sequence; the layouts are l2z_kv8_prefill_attention's
+extern "C" int l2z_kv8_verify_attention(float *out, const float *q, int pos0, int n, const int8_t *k8, const float *ks,
+                                        const int8_t *v8, const float *vs, int n_heads, int n_kv_heads, int head_size, int seq_len)
+{
+    L2Z_TRY(no_device_check());
+    L2Z_CHECK(out && q && k8 && ks && v8 && vs, L2Z_ERR_INVALID, "l2z_kv8_verify_attention: null argument");
+    L2Z_CHECK(n >= 1 && n <= kBatchMax, L2Z_ERR_INVALID, "l2z_kv8_verify_attention: n = %d outside [1, %d]", n, kBatchMax);
+    L2Z_CHECK(kv8::head_size_ok(head_size) && n_heads >= 1 && n_kv_heads >= 1 && n_heads % n_kv_heads == 0 && seq_len >= 1 &&
+                  seq_len <= (1 << 20) && n_heads <= (1 << 12),
+              L2Z_ERR_INVALID, "l2z_kv8_verify_attention: head_size %d (a multiple of 4, at most 256), %d heads on %d kv heads, seq_len %d",
+              head_size, n_heads, n_kv_heads, seq_len);
+    L2Z_TRY(check_positions("l2z_kv8_verify_attention", "", "positions", pos0, n, seq_len));
+    L2Z_TRY(ensure_device(current_device_for(nullptr)));
+    const size_t hs = (size_t)head_size, S = (size_t)seq_len, dim = (size_t)n_heads * hs, row_s = (size_t)n_kv_heads * S;
+    HookBuf<void> dq, dout, dk, dv, dks, dvs, dtab, dpart;
+    L2Z_TRY(dq.put(q, (size_t)n * dim * 4)); L2Z_TRY(dout.put(nullptr, (size_t)n * dim * 4));
+    L2Z_TRY(dk.put(k8, row_s * hs)); L2Z_TRY(dv.put(v8, row_s * hs));
+    L2Z_TRY(dks.put(ks, row_s * 4)); L2Z_TRY(dvs.put(vs, row_s * 4));
+    const Kv8Seq seq = {(int8_t *)dk.p.get(), (int8_t *)dv.p.get(), (float *)dks.p.get(), (float *)dvs.p.get()};
+    std::vector<uint8_t> tab(kv8_prompt_table_bytes(n, true));   // the slots, then the table whose pos[] the combine reads
+    kv8_prompt_tables(tab.data(), seq, pos0, n, true);
+    L2Z_TRY(dtab.put(tab.data(), tab.size()));
+    const Kv8Seq *slots = (const Kv8Seq *)dtab.p.get();
+    const int seg_cap = verify_segments(seq_len);
+    L2Z_TRY(dpart.put(nullptr, wide_part_floats(n_heads, seg_cap, head_size) * 4));
+    const WideAttn wa = {(const WideTable *)(slots + kWideMax), (float *)dpart.p.get(), seg_cap, (pos0 + n - 1) / kVerifySeg + 1, 0, 1, 0};
+    const RaggedLayer L = {(const float *)dq.p.get(), (int)dim, (float *)dout.p.get(), (int)dim, n, n_heads, head_size, n_heads / n_kv_heads, seq_len,
+                           0, S * hs, nullptr, nullptr, 0};
+    L2Z_HIP(launch_kv8_verify_attention(L, wa, slots, 0, pos0));
+    L2Z_HIP(hipDeviceSynchronize());
+    L2Z_HIP(hipMemcpy(out, dout.p.get(), (size_t)n * dim * 4, hipMemcpyDeviceToHost));
     return L2Z_OK;
 }

@@ -8,8 +8,10 @@
 // scatter over a one-sequence table and its prompt attention -- on a runstate with int8 KV rows (l2z_prefill_kv8, DESIGN.md
 // 4.29) the format's scatter and the prompt attention over the int8 arrays (kv8.h) in their place -- and sends the last
 // row through the decode's own classifier launch, so the runstate is left as after a decode step; the step runs
-// q | k | v as one launch (q8_batch.hip), its caller's attention and the classifier through the table.  Also the two hooks
-// that run the row launch and the GEMM on their own.
+// q | k | v as one launch (q8_batch.hip), its caller's attention and the classifier through the table.  The verify pass over
+// int8 KV rows (verify_kv8_pass) is the prompt pass's chunk of at most 16 rows with an attention that reads a
+// segment once for all of them and the wide step's one-product classifier.  Also the two hooks that run the row launch and
+// the GEMM on their own.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -344,6 +346,45 @@ int l2z::wide_step_q8(int n, l2z_runstate *s0, const l2z_weights *w, const Ragge
         const RaggedLayer L = {s0->pf_q, dim, s0->pf_att, s0->pf_ld_att, n, c.n_heads, hs, c.n_heads / c.n_kv_heads, c.seq_len,
                                layer_off, kvh_stride, st, nullptr, 0};
         L2Z_HIP((*rg.attention)(L, nullptr));   // :361-389
+        return L2Z_OK;
+    }));
+    L2Z_TRY(q8_quantize(r, r.x, dim, dim, w->rms_final));   // :426
+    return q8_product(r, w->q_cls, 0, c.vocab_size, dim, logits, ld_logits, EPI_STORE);   // :429
+}
+
+// The verify pass over int8 KV rows (l2z_verify_kv8, verify_host.cpp): n <= kBatchMax rows of ONE sequence at
+// positions pos0 .., on the prompt pass's scratch (verify_kv8_scratch has sized it).  It is the chunk l2z_prefill_kv8 runs
+// for those rows -- the same products, launch_kv8_rope_scatter over the one-sequence table -- with two differences: the
+// layers' attention is launch_kv8_verify_attention, which reads a segment's bytes once for all rows, and the classifier
+// runs as ONE product over all rows into logits [n, ld_logits], as wide_step_q8 ends.  Nothing comes up from the host here:
+// tokens and seq8 (slot 0 = the sequence's arrays) stand on the device behind the caller's table copy, and the rows'
+// positions are written by the embed launch -- into the pos[] of the WideTable wide_combine reads and the scatter's row_pos
+// at once.
+int l2z::verify_kv8_scratch(l2z_runstate *s, const l2z_weights *w) { return q8pf_alloc(s, w->q8_gs, kBatchMax); }
+
+int l2z::verify_kv8_pass(int n, int pos0, l2z_runstate *s, const l2z_weights *w, const int *tokens, const Kv8Seq *seq8, float *logits,
+                         int ld_logits)
+{
+    const l2z_config &c = s->cfg;
+    hipStream_t st = s->stream;
+    const int dim = c.dim, hs = s->sh.hs, kvd = s->sh.kvd_loc;
+    const size_t kvh_stride = (size_t)c.seq_len * hs;
+    const Q8Pf b = q8pf_carve(s, w->q8_gs, (size_t)s->q8pf_cap);
+    const WideTable *tab = (const WideTable *)((const Kv8Seq *)b.kv8_tab + kWideMax);   // (kv8.h Kv8Prompt: behind the slots)
+    int *row_pos = const_cast<int32_t *>(tab->pos);
+    L2Z_HIP(launch_q8_embed_rows(w->q8_emb(), tokens, dim, n, b.x, pos0, b.row_seq, row_pos, st));   // :295
+    RaggedChunk rg = {};
+    rg.seq = b.seq; rg.row_seq = b.row_seq; rg.row_pos = row_pos;
+    rg.n_seq = 1; rg.seq_max = 1; rg.k = b.k; rg.v = b.v;
+    const WideAttn wa = {tab, b.kv8_part, verify_segments(c.seq_len), (pos0 + n - 1) / kVerifySeg + 1, 0, 1, 0};
+    const Q8Rows r = {n, b.x, b.att, b.h, dim, c.hidden_dim, b.xq, b.xs, w->q8_gs, st, false};   // (every pitch tight)
+    L2Z_TRY(q8_layers(r, c, w, [&](int l, size_t layer_off) -> int {
+        L2Z_TRY(q8_product(r, w->q_wq, l, dim, dim, b.q, dim, EPI_STORE));        // :308-320
+        L2Z_TRY(q8_product(r, w->q_wk, l, kvd, dim, b.k, kvd, EPI_STORE));
+        L2Z_TRY(q8_product(r, w->q_wv, l, kvd, dim, b.v, kvd, EPI_STORE));
+        L2Z_HIP(launch_kv8_rope_scatter(b.q, dim, rg, seq8, n, dim, kvd, hs, c.seq_len, s->rope, layer_off, kvh_stride, st));   // :336-358
+        const RaggedLayer L = {b.q, dim, b.att, dim, n, c.n_heads, hs, c.n_heads / c.n_kv_heads, c.seq_len, layer_off, kvh_stride, st, nullptr, 0};
+        L2Z_HIP(launch_kv8_verify_attention(L, wa, seq8, 0, pos0));                 // :361-389
         return L2Z_OK;
     }));
     L2Z_TRY(q8_quantize(r, r.x, dim, dim, w->rms_final));   // :426

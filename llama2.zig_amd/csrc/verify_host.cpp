@@ -1,6 +1,7 @@
 // verify_host.cpp -- host side of the verify family: the batched step (batch_host.cpp's batch_step) with the rows being
 // guessed positions, and the verdict on the device.  l2z_verify / l2z_verify_sample: consecutive positions of ONE sequence
-// (verify.hip).  l2z_verify_batch: that for the rows of several sequences at once, attention and verdict per sequence
+// (verify.hip); l2z_verify_q8 and l2z_verify_kv8: that on int8 group-quantized weights, the latter over int8 KV rows, where
+// the step is q8_host.cpp's verify_kv8_pass.  l2z_verify_batch: that for the rows of several sequences at once, attention and verdict per sequence
 // (verify_batch.hip).  l2z_verify_tree: the nodes of a tree of guesses on one sequence, with the compaction of the accepted
 // path (verify_tree.hip).  Every path reads the same way: checks (a refusal enqueues nothing and changes no state), scratch,
 // table, the step with the path's attention, the rows' next ids (verify_ids), the path's accept kernel, the copy back.
@@ -9,6 +10,7 @@
 #include <cstring>
 
 #include "batch_host.h"
+#include "kv8.h"
 
 namespace l2z {
 namespace {
@@ -33,13 +35,19 @@ int check_targets(const char *fn, const l2z_config *config, int n, l2z_runstate 
     return L2Z_OK;
 }
 
-// ... for a pass on one runstate; q8: the pass takes int8 group-quantized weights, and only those (l2z_verify_q8)
-int check_target(const char *fn, const l2z_config *config, l2z_runstate *s, const l2z_weights *w, bool q8 = false)
+// What a pass on one runstate runs on: f32 (or packed) weights and f32 KV rows; int8 group-quantized weights, and only those,
+// on f32 KV rows (l2z_verify_q8); such weights on a runstate with int8 KV rows, and only such a one (l2z_verify_kv8)
+enum VerifyOn { ON_F32 = 0, ON_Q8, ON_KV8 };
+
+// ... for a pass on one runstate
+int check_target(const char *fn, const l2z_config *config, l2z_runstate *s, const l2z_weights *w, VerifyOn on = ON_F32)
 {
     L2Z_CHECK(s->comm == nullptr && s->sh.world == 1, L2Z_ERR_INVALID, "%s: the runstate is a shard", fn);
-    if (!q8) return check_targets(fn, config, 1, &s, w);
+    if (on == ON_F32) return check_targets(fn, config, 1, &s, w);
     L2Z_TRY(check_q8_step(fn, "l2z_verify and l2z_verify_sample", s, w));
-    return check_pair(config, s, w, false, true);
+    L2Z_CHECK(on != ON_KV8 || s->is_kv8(), L2Z_ERR_INVALID,
+              "%s: takes a runstate with int8 KV rows (l2z_runstate_init_kv8); every other one goes to l2z_verify_q8", fn);
+    return check_pair(config, s, w, false, true, on == ON_KV8);
 }
 
 // ---- what the paths share after the checks ----
@@ -81,22 +89,24 @@ void verify_done(l2z_runstate *s, int rows)
 
 // ---- l2z_verify, l2z_verify_sample: n consecutive positions of ONE sequence in one sweep ----
 
-// The checks, then the table, the pass, the verdict and its copy back on s's stream; no sync.  q8: the step on int8
-// group-quantized weights (batch_step's other form); everything around it is the same.
+// The checks, then the table, the pass, the verdict and its copy back on s's stream; no sync.  ON_Q8: the step on int8
+// group-quantized weights (batch_step's other form); ON_KV8: the pass over int8 KV rows (verify_kv8_pass), the
+// sequence's arrays behind the table in the same copy; everything around either is the same.
 int verify_enqueue(const char *fn, const int32_t *tokens, int n, int pos0, const VerifyDraw &draw, const l2z_config *config,
-                   l2z_runstate *s, const l2z_weights *w, bool q8)
+                   l2z_runstate *s, const l2z_weights *w, VerifyOn on)
 {
     L2Z_TRY(no_device_check());
     L2Z_CHECK(tokens != nullptr && config != nullptr && s != nullptr && w != nullptr, L2Z_ERR_INVALID, "%s: null argument",
               fn);
     L2Z_CHECK(n >= 1 && n <= kBatchMax, L2Z_ERR_INVALID, "%s: n_tokens = %d outside [1, %d]", fn, n, kBatchMax);
-    L2Z_TRY(check_target(fn, config, s, w, q8));
+    L2Z_TRY(check_target(fn, config, s, w, on));
     L2Z_TRY(check_positions(fn, "", "positions", pos0, n, config->seq_len));
     L2Z_TRY(check_tokens(fn, "", tokens, n, config->vocab_size));
     if (draw.sampled()) L2Z_TRY(check_coins(fn, draw.coins, 0, n));
     L2Z_TRY(verify_scratch(s, draw.sampled()));
     BatchScratch *b = s->bt.get();
-    if (q8) L2Z_TRY(q8_rows_alloc("batched q8 step scratch", s, b, kBatchMax, w->q8_gs));
+    if (on == ON_Q8) L2Z_TRY(q8_rows_alloc("batched q8 step scratch", s, b, kBatchMax, w->q8_gs));
+    if (on == ON_KV8) L2Z_TRY(verify_kv8_scratch(s, w));
     const int vocab = config->vocab_size;
     BatchTable t = {};
     for (int i = 0; i < n; i++) {
@@ -112,15 +122,21 @@ int verify_enqueue(const char *fn, const int32_t *tokens, int n, int pos0, const
         }
     }
     hipStream_t st = s->stream;
-    L2Z_TRY(upload_table(b, t, st));
-    VerifyAttnArgs a = verify_attention_args<VerifyAttnArgs>(*config, b);
-    a.pos0 = pos0;
-    L2Z_TRY(batch_step(n, *config, s, w, b, [&](size_t layer_off) -> int {
-        a.kc = s->key_cache + layer_off; a.vc = s->value_cache + layer_off;
-        L2Z_HIP(launch_verify_attention(a, n, st));
-        L2Z_HIP(launch_verify_combine(a, n, st));
-        return L2Z_OK;
-    }));
+    if (on == ON_KV8) {
+        const Kv8Seq seq8 = {s->k8, s->v8, s->ks8, s->vs8};
+        L2Z_TRY(upload_table(b, t, st, &seq8, sizeof seq8));
+        L2Z_TRY(verify_kv8_pass(n, pos0, s, w, b->d_tab->tokens, (const Kv8Seq *)b->d_behind, b->v_logits, vocab));
+    } else {
+        L2Z_TRY(upload_table(b, t, st));
+        VerifyAttnArgs a = verify_attention_args<VerifyAttnArgs>(*config, b);
+        a.pos0 = pos0;
+        L2Z_TRY(batch_step(n, *config, s, w, b, [&](size_t layer_off) -> int {
+            a.kc = s->key_cache + layer_off; a.vc = s->value_cache + layer_off;
+            L2Z_HIP(launch_verify_attention(a, n, st));
+            L2Z_HIP(launch_verify_combine(a, n, st));
+            return L2Z_OK;
+        }));
+    }
     L2Z_TRY(verify_ids(b, draw.sampled(), vocab, n, st));
     L2Z_HIP(launch_verify_accept(b->d_tab, b->v_logits, vocab, b->d_vout, s->logits, n, st));
     L2Z_HIP(hipMemcpyAsync(b->h_vout, b->d_vout, (size_t)(n + 1) * 4, hipMemcpyDeviceToHost, st));
@@ -130,12 +146,12 @@ int verify_enqueue(const char *fn, const int32_t *tokens, int n, int pos0, const
 
 // The call under either name: l2z_verify is the draw at temperature 0
 int verify_call(const char *fn, const int32_t *tokens, int n, int pos0, const VerifyDraw &draw, const l2z_config *config,
-                l2z_runstate *s, const l2z_weights *w, int32_t *out_next, int *out_accepted, bool q8 = false)
+                l2z_runstate *s, const l2z_weights *w, int32_t *out_next, int *out_accepted, VerifyOn on = ON_F32)
 {
     L2Z_TRY(no_device_check());
     L2Z_CHECK(out_next != nullptr && out_accepted != nullptr, L2Z_ERR_INVALID, "%s: null argument", fn);
     L2Z_TRY(check_draw(fn, -1, draw.temperature, draw.top_p, draw.coins));
-    L2Z_TRY(verify_enqueue(fn, tokens, n, pos0, draw, config, s, w, q8));
+    L2Z_TRY(verify_enqueue(fn, tokens, n, pos0, draw, config, s, w, on));
     BatchScratch *b = s->bt.get();
     L2Z_HIP(hipStreamSynchronize(s->stream));
     memcpy(out_next, b->h_vout, (size_t)n * 4);
@@ -147,13 +163,13 @@ int verify_call(const char *fn, const int32_t *tokens, int n, int pos0, const Ve
 // Testing support: one call, then `iters` passes back to back (the rows' ids, the verdict and its copy included, no sync),
 // timed by device events on the runstate's stream.  The passes rewrite the same KV rows.
 int verify_time(const char *fn, const int32_t *tokens, int n, int pos0, const VerifyDraw &draw, const l2z_config *config,
-                l2z_runstate *s, const l2z_weights *w, int iters, double *out_ms, bool q8 = false)
+                l2z_runstate *s, const l2z_weights *w, int iters, double *out_ms, VerifyOn on = ON_F32)
 {
     L2Z_CHECK(iters >= 1 && out_ms != nullptr, L2Z_ERR_INVALID, "%s_time: bad arguments", fn);
     int32_t next[kBatchMax];
     int acc = 0;
-    L2Z_TRY(verify_call(fn, tokens, n, pos0, draw, config, s, w, next, &acc, q8));  // validates, allocates
-    return timed_loop(s->stream, iters, out_ms, [&] { return verify_enqueue(fn, tokens, n, pos0, draw, config, s, w, q8); });
+    L2Z_TRY(verify_call(fn, tokens, n, pos0, draw, config, s, w, next, &acc, on));  // validates, allocates
+    return timed_loop(s->stream, iters, out_ms, [&] { return verify_enqueue(fn, tokens, n, pos0, draw, config, s, w, on); });
 }
 
 }  // namespace
@@ -198,7 +214,7 @@ extern "C" int l2z_verify_q8(const int32_t *tokens, int n_tokens, int pos0, floa
                              int *out_accepted)
 {
     return verify_call("l2z_verify_q8", tokens, n_tokens, pos0, VerifyDraw{temperature, top_p, coins}, config, s, w, out_next,
-                       out_accepted, true);
+                       out_accepted, ON_Q8);
 }
 
 // scripts/q8_batch_bench.py
@@ -207,7 +223,25 @@ extern "C" int l2z_verify_q8_time(const int32_t *tokens, int n_tokens, int pos0,
                                   double *out_ms)
 {
     return verify_time("l2z_verify_q8", tokens, n_tokens, pos0, VerifyDraw{temperature, top_p, coins}, config, s, w, iters,
-                       out_ms, true);
+                       out_ms, ON_Q8);
+}
+
+// PREVIEW (include/llama2_hip_test.h): l2z_verify_q8's contract on a runstate with int8 KV rows
+extern "C" int l2z_verify_kv8(const int32_t *tokens, int n_tokens, int pos0, float temperature, float top_p, const float *coins,
+                              const l2z_config *config, l2z_runstate *s, const l2z_weights *w, int32_t *out_next,
+                              int *out_accepted)
+{
+    return verify_call("l2z_verify_kv8", tokens, n_tokens, pos0, VerifyDraw{temperature, top_p, coins}, config, s, w, out_next,
+                       out_accepted, ON_KV8);
+}
+
+// scripts/kv8_verify_bench.py
+extern "C" int l2z_verify_kv8_time(const int32_t *tokens, int n_tokens, int pos0, float temperature, float top_p,
+                                   const float *coins, const l2z_config *config, l2z_runstate *s, const l2z_weights *w, int iters,
+                                   double *out_ms)
+{
+    return verify_time("l2z_verify_kv8", tokens, n_tokens, pos0, VerifyDraw{temperature, top_p, coins}, config, s, w, iters,
+                       out_ms, ON_KV8);
 }
 
 // Testing support (include/llama2_hip_test.h): row `row` of the last l2z_verify call's logits matrix
